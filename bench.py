@@ -8,7 +8,12 @@ lat-lon, 512 batched fp64 fields.  A "step" is ONE pass of the hot path
 normalisation + masking, one fused HIP launch through the C ABI) over one
 batch of 512 synthetic fields that are already resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+
+`--dump-outputs DIR` writes what the LAST timed step computed -- the remapped
+array a caller of `engine.remap_tensor` receives -- as .npy files (class
+OutputDump).  Every input is seeded and built deterministically (make_map),
+so two builds run with the same arguments can be compared output for output.
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): destination
 rows are sharded over the ranks (nnz-balanced contiguous ranges), every
@@ -118,7 +123,14 @@ def parse_args():
     ap.add_argument('--force-dist', action='store_true',
                     help='initialise RCCL even with one rank (exercises '
                          'the N > 1 code path on a 1-GPU box)')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the output of the last timed step to '
+                         'DIR/*.npy (float64; a fixed, seeded sample when '
+                         'it is larger than 16 MB; rank 0\'s rows when N > 1)')
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
 
 
 def self_launch(args):
@@ -200,11 +212,12 @@ def barrier(dist):
     torch.cuda.synchronize()
 
 
-def time_steps(launch, steps, warmup, dist):
+def time_steps(launch, steps, warmup, dist, after=None):
     """
     warmup untimed, then EXACTLY `steps` timed between barrier + synchronize.
     Returns (wall_s, mean_ms, [per-launch ms], shader clock in MHz right
-    behind the timed region).
+    behind the timed region).  `after(i)`, if given, is called behind the
+    timed region with the index of its last launch (OutputDump.take).
 
     ``mean_ms`` is the average launch duration over the timed region: ONE pair
     of HIP events on the launch stream (torch's current stream is the stream
@@ -237,6 +250,8 @@ def time_steps(launch, steps, warmup, dist):
     from pyremap_amd import engine
     mhz = engine.clock_probe(torch.cuda.current_device())
     torch.cuda.synchronize()
+    if after is not None:
+        after(warmup + steps - 1)
     if marks:
         prev = first
         gaps = []
@@ -312,6 +327,26 @@ def make_fields(n_a, K, layout, sets, seed, device, nan_frac=0.0,
             x.index_fill_(cell_axis, dead.nonzero().squeeze(1), float('nan'))
         out.append(x)
     return out
+
+
+def make_map(name, device, locality):
+    """
+    `synthetic.make_config(name)` on `device`, the same map in every run.
+    Its rows are scaled by sums that `index_add_` accumulates with float64
+    atomics on the GPU, in an order (and so to last bits) that changes from
+    run to run; torch's deterministic algorithms fix that order.  The random
+    draws, and so the map's structure, are those of the plain call.
+    """
+    import torch
+
+    from pyremap_amd import synthetic
+    was = torch.are_deterministic_algorithms_enabled()
+    warn = torch.is_deterministic_algorithms_warn_only_enabled()
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    try:
+        return synthetic.make_config(name, device=device, locality=locality)
+    finally:
+        torch.use_deterministic_algorithms(was, warn_only=warn)
 
 
 class Workload:
@@ -427,7 +462,7 @@ def prepare(name, args, rank, world, dist, K=None, mode=None, layout=None,
 
     t0 = time.perf_counter()
     w.locality = locality or args.locality
-    m = synthetic.make_config(name, device=device, locality=w.locality)
+    m = make_map(name, device, w.locality)
     full = engine.RemapPlan.from_triplets(
         m.row, m.col, m.S, m.frac_b, m.n_a, m.n_b, index_base=1,
         device=device)
@@ -597,12 +632,12 @@ def time_pipelined(w, args, dist, reps=5, n_batches=4):
     return out
 
 
-def measure(w, args, dist, steps=None, warmup=None):
+def measure(w, args, dist, steps=None, warmup=None, after=None):
     """W warm-up + K timed steps of a prepared workload."""
-    steps = steps or args.steps
+    steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
     wall, mean_ms, per_launch, mhz = time_steps(w.launch, steps, warmup,
-                                                dist)
+                                                dist, after)
     in_order = [round(t, 4) for t in per_launch[:20]]
     per_launch.sort()
     m, plan = w.m, w.plan
@@ -1351,6 +1386,76 @@ def write_details(path, line, details):
         print(f'bench.py: side file {path}: {exc}', file=sys.stderr)
 
 
+#: --dump-outputs: an output up to DUMP_WHOLE_BYTES is written whole; a
+#: larger one as DUMP_SAMPLE values at positions drawn with DUMP_SEED.  With
+#: the validity flags (and the positions) at most 48 MB in all
+DUMP_WHOLE_BYTES = 16 << 20
+DUMP_SAMPLE = 1 << 21
+DUMP_SEED = 2024
+
+
+class OutputDump:
+    """
+    `--dump-outputs DIR`: the remapped array the metric workload's LAST timed
+    step wrote -- what `engine.remap_tensor` returns to its caller -- kept on
+    the device right behind the timed region (`take`: one copy or gather on
+    the launch stream, no synchronise) and written by `write` as
+
+    * `remapped.npy`: the whole array, its shape, float64 -- when it holds at
+      most DUMP_WHOLE_BYTES; otherwise the values at DUMP_SAMPLE distinct
+      flat positions drawn with a fixed seed, in ascending order.  Every
+      value is finite: where the array holds NaN (a destination cell no
+      source cell overlaps, or one the masked mode leaves out) it holds 0.0,
+      and
+    * `remapped_valid.npy` (same shape) says which: 1.0 where the array's
+      value is finite, 0.0 where it is not;
+    * for a sample also `remapped_index.npy`: its flat positions, and
+      `remapped_shape.npy`: the array's shape (all float64).
+
+    The positions depend on the shape alone; the map and the fields are
+    seeded and built deterministically (make_map, make_fields): the same
+    arguments give the same inputs in every run.
+    """
+
+    def __init__(self, w):
+        import numpy as np
+        import torch
+        y = w.outs[0]
+        self.w = w
+        self.shape = tuple(y.shape)
+        self.index = None
+        self.taken = None
+        if y.numel() * 8 > DUMP_WHOLE_BYTES:
+            rng = np.random.default_rng(DUMP_SEED)
+            self.index = np.sort(rng.choice(y.numel(), DUMP_SAMPLE,
+                                            replace=False))
+            self.index_dev = torch.from_numpy(self.index).to(y.device)
+
+    def take(self, i):
+        """Launch `i` was the last timed step: keep what it wrote (before a
+        later launch reuses its output buffer)."""
+        y = self.w.outs[i % self.w.sets]
+        if self.index is None:
+            self.taken = y.clone()
+        else:
+            self.taken = y.reshape(-1).index_select(0, self.index_dev)
+
+    def write(self, path):
+        import numpy as np
+        os.makedirs(path, exist_ok=True)
+        values = self.taken.cpu().numpy().astype(np.float64, copy=False)
+        valid = np.isfinite(values)
+        np.save(os.path.join(path, 'remapped.npy'),
+                np.where(valid, values, 0.0))
+        np.save(os.path.join(path, 'remapped_valid.npy'),
+                valid.astype(np.float64))
+        if self.index is not None:
+            np.save(os.path.join(path, 'remapped_index.npy'),
+                    self.index.astype(np.float64))
+            np.save(os.path.join(path, 'remapped_shape.npy'),
+                    np.array(self.shape, dtype=np.float64))
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -1379,6 +1484,7 @@ def main():
     # metric workload last.
     t = mark('init_s', t_start)
     main_w = prepare(args.workload, args, rank, world, dist)
+    dump = OutputDump(main_w) if args.dump_outputs and rank == 0 else None
     t = mark('prepare_metric_workload_s', t)
     ready = prepare_extras(args, rank, world, dist, extra, big=False)
     t = mark('prepare_small_extras_s', t)
@@ -1392,11 +1498,12 @@ def main():
     t = mark('copy_ceiling_s', t)
     pipelined = None
     res = None
+    take = dump.take if dump is not None else None
     if args.metric_first:
-        res = measure(main_w, args, dist)
+        res = measure(main_w, args, dist, after=take)
     measure_extras(ready, args, dist, extra)
     if res is None:
-        res = measure(main_w, args, dist)
+        res = measure(main_w, args, dist, after=take)
     # a long run behind it, for the record: the steady-state launch time
     a = torch.cuda.Event(enable_timing=True)
     b = torch.cuda.Event(enable_timing=True)
@@ -1522,6 +1629,8 @@ def main():
                                  pipelined, details_path=shown_path)
     details['phases_s'] = phases
     write_details(details_path, line, details)
+    if dump is not None:
+        dump.write(args.dump_outputs)
     # the JSON line is the LAST thing on stdout: every rank is done first
     # (RCCL prints a version banner on stdout when its communicator comes up
     # or goes down, whichever happens to be later)

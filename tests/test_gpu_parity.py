@@ -2075,6 +2075,66 @@ def test_bench_single_gpu_line_parses_and_is_small(tmp_path):
     assert details['line'] == line and details['phases_s']['total_s'] > 0
 
 
+def test_bench_dump_outputs_is_the_last_timed_step(dev, tmp_path):
+    """
+    `bench.py --dump-outputs DIR`: what the last of exactly `--steps` timed
+    steps computed, the same in two runs, and bit for bit the oracle's
+    result on that step's input (config 2 with 128 fields: a seeded sample
+    of its (180, 360, 128) float64 output, 66 MB); NaNs of the output (the
+    destination cells nothing overlaps) as 0.0 and a validity flag of 0.
+    """
+    import importlib.util
+    import json
+    import subprocess
+    import sys
+    from oracle import oracle
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in ('a', 'b'):
+        out = tmp_path / run
+        proc = subprocess.run(
+            [sys.executable, os.path.join(repo, 'bench.py'), '--gpus', '1',
+             '--workload', 'config2', '--fields', '128', '--steps', '4',
+             '--warmup', '1', '--no-extra', '--no-cpu', '--details',
+             str(out / 'extra.json'), '--dump-outputs', str(out)],
+            capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert proc.returncode == 0, proc.stderr[-2000:]
+        line = json.loads(proc.stdout.strip().splitlines()[-1])
+        assert line['steps'] == 4 and line['warmup'] == 1
+        assert line['ms_per_step'] > 0
+        names = ('', '_valid', '_index', '_shape')
+        dumps.append({n: np.load(out / f'remapped{n}.npy') for n in names})
+        assert sum(os.path.getsize(out / f'remapped{n}.npy')
+                   for n in names) < 64 << 20
+    for n in dumps[0]:
+        assert dumps[0][n].dtype == np.float64
+        assert np.isfinite(dumps[0][n]).all()
+        assert np.array_equal(dumps[0][n], dumps[1][n], equal_nan=True)
+    got, valid = dumps[0][''], dumps[0]['_valid']
+    idx, shape = dumps[0]['_index'], dumps[0]['_shape']
+    assert list(shape) == [180, 360, 128]
+    # the inputs bench.py made: seeded map, seeded fields (3 sets); the last
+    # timed launch is warm-up + steps - 1 = 4, set 4 % 3 = 1
+    spec = importlib.util.spec_from_file_location(
+        'bench_for_dump', os.path.join(repo, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    m = bench.make_map('config2', dev, 'mesh')
+    x = bench.make_fields(m.n_a, 128, 'nk', 3, 1234, dev)[1].cpu().numpy()
+    mm = m.numpy()
+    csr = oracle.coo_to_csr(mm['row'] - 1, mm['col'] - 1, mm['S'], m.n_b,
+                            m.n_a)
+    ref = np.ma.filled(oracle.remap_numpy_array(
+        csr, mm['frac_b'], m.dst_dims, x, [0], None), np.nan)
+    assert ref.shape == (180, 360, 128)
+    want = ref.reshape(-1)[idx.astype(np.int64)]
+    ok = ~np.isnan(want)
+    assert ok.any() and not ok.all()
+    assert np.array_equal(valid, ok.astype(np.float64))
+    assert (got[~ok] == 0.0).all()
+    assert np.array_equal(got[ok].view(np.int64), want[ok].view(np.int64))
+
+
 def test_plan_handle_device_inputs_and_strided_fields(dev):
     """
     The opaque plan handle beyond what INTEGRATION.md's stub uses: triplets

@@ -983,6 +983,65 @@ def test_bench_line_drops_rows_rather_than_overflow():
     assert len(details['workloads']) > 200
 
 
+def test_bench_output_dump_whole_and_sampled(tmp_path, monkeypatch):
+    """bench.OutputDump (--dump-outputs): the buffer the last timed launch
+    wrote, whole when small, else a seeded sample with its positions and the
+    shape -- float64 files of finite values only (NaN as 0.0 beside a
+    validity flag), the same positions in every run, within the size
+    limit."""
+    import types
+    torch = pytest.importorskip('torch')
+    bench = _bench_module()
+    outs = [torch.full((6, 5, 4), float(s), dtype=torch.float64)
+            for s in range(3)]
+    outs[1][1, 2, 3] = float('nan')   # a destination cell nothing overlaps
+    w = types.SimpleNamespace(outs=outs, sets=3)
+    dump = bench.OutputDump(w)
+    dump.take(7)                      # warm-up + steps - 1: set 7 % 3 = 1
+    outs[1].fill_(-1.0)               # a later launch reuses the buffer
+    dump.write(str(tmp_path / 'whole'))
+    assert sorted(os.listdir(tmp_path / 'whole')) == ['remapped.npy',
+                                                      'remapped_valid.npy']
+    got = np.load(tmp_path / 'whole' / 'remapped.npy')
+    valid = np.load(tmp_path / 'whole' / 'remapped_valid.npy')
+    for a in (got, valid):
+        assert a.dtype == np.float64 and a.shape == (6, 5, 4)
+        assert np.isfinite(a).all()
+    assert got[1, 2, 3] == 0.0 and valid[1, 2, 3] == 0.0
+    assert valid.sum() == got.size - 1
+    assert (got[valid == 1.0] == 1.0).all()
+
+    # the real limits: a whole array and its flags, or a sample with its
+    # flags and positions, stay under 64 MB
+    assert 2 * bench.DUMP_WHOLE_BYTES + 4096 < 64 << 20
+    assert 3 * 8 * bench.DUMP_SAMPLE + 4096 < 64 << 20
+
+    monkeypatch.setattr(bench, 'DUMP_WHOLE_BYTES', 8 * 100)
+    monkeypatch.setattr(bench, 'DUMP_SAMPLE', 50)
+    ys = torch.arange(3 * 120, dtype=torch.float64).reshape(3, 6, 5, 4)
+    ys[2].view(-1)[::7] = float('nan')
+    w = types.SimpleNamespace(outs=list(ys), sets=3)
+    files = []
+    for run in ('a', 'b'):
+        dump = bench.OutputDump(w)
+        dump.take(2)
+        dump.write(str(tmp_path / run))
+        files.append({n: np.load(tmp_path / run / f'remapped{n}.npy')
+                      for n in ('', '_valid', '_index', '_shape')})
+    a, b = files
+    for n in a:
+        assert a[n].dtype == np.float64 and np.array_equal(a[n], b[n])
+        assert np.isfinite(a[n]).all()
+    idx = a['_index']
+    assert idx.shape == (50,) and (np.diff(idx) > 0).all()
+    assert 0 <= idx[0] and idx[-1] < 120
+    assert list(a['_shape']) == [6, 5, 4]
+    want = ys[2].numpy().reshape(-1)[idx.astype(int)]
+    assert np.array_equal(a['_valid'], (~np.isnan(want)).astype(np.float64))
+    assert 0 < a['_valid'].sum() < 50
+    assert np.array_equal(a[''], np.where(np.isnan(want), 0.0, want))
+
+
 # ---------------------------------------------------------------------------
 # round 5: the DPP hazard scanner, the stamped traffic files, the batches of a
 # Dataset's small variables (host logic, no GPU)
