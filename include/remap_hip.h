@@ -845,6 +845,89 @@ int remap_stream_copy(void *dst, const void *src, size_t bytes, void *stream);
 REMAP_API
 int remap_clock_probe(int64_t *ticks_out, int32_t micros, void *stream);
 
+/*
+ * ---------------------------------------------------------------------------
+ * Conservative overlaps between an MPAS cell mesh and a lat-lon grid (an
+ * addition: the reference has ESMF_RegridWeightGen --method conserve compute
+ * them, pyremap/remapper/build_map.py).  ESMF's geometry: every cell is a
+ * spherical polygon with great-circle edges, lat-lon cells included (their
+ * corners joined by great-circle arcs; a polar row's cells are triangles).
+ * The overlap list is what both directions of a first-order conservative map
+ * are made of (pyremap_amd/weights.py turns it into S and frac_b).
+ *
+ * Call remap_overlap_latlon_sizes() first: it counts the candidate pairs
+ * (mesh cell, lat-lon cell whose boxes meet) on `stream` and reads the count
+ * back (it synchronises `stream`), and returns it with the workspace size.
+ * remap_overlap_latlon() is then asynchronous on `stream` except for ONE
+ * host read-back: the number of entries (and the error bits) after the
+ * clipping, before the sort.  No floating-point atomics: two calls give
+ * bitwise-identical outputs.
+ * ---------------------------------------------------------------------------
+ */
+
+/* the largest nEdgesOnCell this build serves (clip polygons live in LDS) */
+#define REMAP_OVERLAP_MAX_EDGES 10
+
+/* error bits behind a REMAP_ERR_UNSUPPORTED of the overlap calls */
+enum {
+    REMAP_OVERLAP_ERR_EDGES = 1,      /* nEdgesOnCell > REMAP_OVERLAP_MAX_EDGES */
+    REMAP_OVERLAP_ERR_VERTEX = 2,     /* < 3 distinct vertices, bad index      */
+    REMAP_OVERLAP_ERR_HEMISPHERE = 4, /* a pair's vertex within acos(0.1) of
+                                         the horizon of the mesh cell's centre
+                                         (the gnomonic projection's limit)     */
+    REMAP_OVERLAP_ERR_CAPACITY = 8    /* n_pairs differs from the count        */
+};
+
+typedef struct remap_overlap_geom {
+    int64_t n_cells;            /* mesh cells (nCells)                        */
+    int64_t n_vertices;         /* mesh vertices (nVertices)                  */
+    int64_t n_lat;              /* grid rows                                  */
+    int64_t n_lon;              /* grid columns; grid cell = row * n_lon + col */
+    int32_t max_edges;          /* maxEdges: the row stride of verticesOnCell */
+    int32_t reserved;           /* 0                                          */
+    /* how far north (south) of its corners' latitude a grid cell's
+     * great-circle edge reaches, at most over the grid, radians; candidate
+     * rows are widened by it */
+    double lat_slack;
+    const int32_t *vertices_on_cell; /* (device) n_cells x max_edges, 1-based */
+    const int32_t *n_edges_on_cell;  /* (device) n_cells                      */
+    const double *lat_vertex;   /* (device) n_vertices, radians               */
+    const double *lon_vertex;   /* (device) n_vertices, radians               */
+    const double *lat_corner;   /* (device) n_lat + 1, radians, monotone,
+                                   within [-pi/2, pi/2]                       */
+    const double *lon_corner;   /* (device) n_lon + 1, radians, monotone; a
+                                   grid spanning 2 pi closes in longitude     */
+} remap_overlap_geom;
+
+/*
+ *   counter (device) 2 x int64 of scratch;  n_pairs_out (host) candidate
+ *   pairs;  workspace_bytes_out (host) what remap_overlap_latlon() needs.
+ */
+REMAP_API
+int remap_overlap_latlon_sizes(const remap_overlap_geom *geom,
+                               int64_t *counter, int64_t *n_pairs_out,
+                               size_t *workspace_bytes_out, void *stream);
+
+/*
+ * The overlap areas A (steradians) of every (destination, source) pair with
+ * A > 1e-14 x area(destination cell), sorted by (dst, src), 0-based.  The
+ * destination is the mesh when dst_is_mesh != 0, the grid otherwise.
+ *
+ *   dst_out, src_out, area_out (device) n_pairs capacity each, the first
+ *   *n_entries_out meaningful;  frac_b_out (device) one per destination
+ *   cell: min(sum of its entries / its area, 1), summed in entry order;
+ *   mesh_area_out (device) n_cells, grid_area_out (device) n_lat x n_lon:
+ *   the polygons' own areas;  n_entries_out (host) one int64.
+ */
+REMAP_API
+int remap_overlap_latlon(const remap_overlap_geom *geom, int32_t dst_is_mesh,
+                         int64_t n_pairs, void *workspace,
+                         size_t workspace_bytes, int32_t *dst_out,
+                         int32_t *src_out, double *area_out,
+                         double *frac_b_out, double *mesh_area_out,
+                         double *grid_area_out, int64_t *n_entries_out,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,7 @@ EXPORTS = (
     'remap_pack_columns_workspace', 'remap_pack_columns',
     'remap_gather_rows', 'remap_plan_prepare_short_runs',
     'remap_clock_probe',
+    'remap_overlap_latlon_sizes', 'remap_overlap_latlon',
 )
 
 
@@ -241,6 +242,22 @@ class _Field(ctypes.Structure):        # struct remap_field
 _lib = None
 
 
+class _OverlapGeom(ctypes.Structure):  # struct remap_overlap_geom
+    _fields_ = [('n_cells', ctypes.c_int64),
+                ('n_vertices', ctypes.c_int64),
+                ('n_lat', ctypes.c_int64),
+                ('n_lon', ctypes.c_int64),
+                ('max_edges', ctypes.c_int32),
+                ('reserved', ctypes.c_int32),
+                ('lat_slack', ctypes.c_double),
+                ('vertices_on_cell', ctypes.c_void_p),
+                ('n_edges_on_cell', ctypes.c_void_p),
+                ('lat_vertex', ctypes.c_void_p),
+                ('lon_vertex', ctypes.c_void_p),
+                ('lat_corner', ctypes.c_void_p),
+                ('lon_corner', ctypes.c_void_p)]
+
+
 class EngineError(RuntimeError):
     """A failure reported by libremap_hip.so (message from the C side)."""
 
@@ -378,6 +395,17 @@ def load_library():
     lib.remap_clock_probe.restype = ctypes.c_int
     lib.remap_clock_probe.argtypes = [ctypes.c_void_p, ctypes.c_int32,
                                       ctypes.c_void_p]
+    lib.remap_overlap_latlon_sizes.restype = ctypes.c_int
+    lib.remap_overlap_latlon_sizes.argtypes = [
+        ctypes.POINTER(_OverlapGeom), ctypes.c_void_p,
+        ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_size_t),
+        ctypes.c_void_p]
+    lib.remap_overlap_latlon.restype = ctypes.c_int
+    lib.remap_overlap_latlon.argtypes = [
+        ctypes.POINTER(_OverlapGeom), ctypes.c_int32, ctypes.c_int64,
+        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]
     if lib.remap_abi_version() != ABI_VERSION:
         raise EngineError(
             f'{path} has ABI {lib.remap_abi_version()}, expected '
@@ -2020,3 +2048,78 @@ def stream_copy(dst, src):
         _check(lib.remap_stream_copy(_ptr(dst), _ptr(src), nbytes,
                                      _stream_ptr(src.device)),
                'remap_stream_copy')
+
+
+# ---------------------------------------------------------------------------
+# conservative overlaps: MPAS cell mesh <-> lat-lon grid
+# ---------------------------------------------------------------------------
+
+def overlap_latlon(vertices_on_cell, n_edges_on_cell, lat_vertex, lon_vertex,
+                   lat_corner, lon_corner, lat_slack, dst_is_mesh,
+                   timing=None):
+    """
+    The overlap areas between the cells of an MPAS mesh (``verticesOnCell``
+    1-based, ``nEdgesOnCell``, ``latVertex`` / ``lonVertex`` in radians) and
+    the cells of a lat-lon grid (corner axes in radians; cell ``j * n_lon +
+    i``), through ``remap_overlap_latlon`` (``include/remap_hip.h``).  All
+    tensors on one HIP device; ``lat_slack``: the grid's great-circle bulge
+    (radians).
+
+    Returns ``(dst, src, A, frac_b, mesh_area, grid_area)``: 0-based int32
+    indices and float64 areas (steradians) of the entries sorted by
+    ``(dst, src)`` -- the mesh is the destination when ``dst_is_mesh`` --
+    ``frac_b`` per destination cell, and both sets of polygon areas.
+    ``timing``: a dict that receives ``n_pairs`` and the GPU ``ms`` of the
+    overlap call (events on the stream).
+    """
+    torch = require_gpu()
+    lib = load_library()
+    dev = vertices_on_cell.device
+    voc = vertices_on_cell.to(torch.int32).contiguous()
+    noc = n_edges_on_cell.to(torch.int32).contiguous()
+    lat_v = lat_vertex.to(torch.float64).contiguous()
+    lon_v = lon_vertex.to(torch.float64).contiguous()
+    lat_c = lat_corner.to(torch.float64).contiguous()
+    lon_c = lon_corner.to(torch.float64).contiguous()
+    n_cells, max_edges = voc.shape
+    n_lat, n_lon = lat_c.numel() - 1, lon_c.numel() - 1
+    geom = _OverlapGeom(n_cells, lat_v.numel(), n_lat, n_lon, max_edges, 0,
+                        float(lat_slack), voc.data_ptr(), noc.data_ptr(),
+                        lat_v.data_ptr(), lon_v.data_ptr(), lat_c.data_ptr(),
+                        lon_c.data_ptr())
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        counter = torch.zeros(2, dtype=torch.int64, device=dev)
+        n_pairs = ctypes.c_int64()
+        nbytes = ctypes.c_size_t()
+        _check(lib.remap_overlap_latlon_sizes(
+            ctypes.byref(geom), _ptr(counter), ctypes.byref(n_pairs),
+            ctypes.byref(nbytes), stream), 'remap_overlap_latlon_sizes')
+        n = n_pairs.value
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        dst = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        src = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        A = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        mesh_area = torch.empty(n_cells, dtype=torch.float64, device=dev)
+        grid_area = torch.empty(n_lat * n_lon, dtype=torch.float64,
+                                device=dev)
+        frac_b = torch.empty(n_cells if dst_is_mesh else n_lat * n_lon,
+                             dtype=torch.float64, device=dev)
+        n_entries = ctypes.c_int64()
+        if timing is not None:
+            t0 = torch.cuda.Event(enable_timing=True)
+            t1 = torch.cuda.Event(enable_timing=True)
+            t0.record()
+        _check(lib.remap_overlap_latlon(
+            ctypes.byref(geom), 1 if dst_is_mesh else 0, n, _ptr(ws),
+            nbytes.value, _ptr(dst), _ptr(src), _ptr(A), _ptr(frac_b),
+            _ptr(mesh_area), _ptr(grid_area), ctypes.byref(n_entries),
+            stream), 'remap_overlap_latlon')
+        if timing is not None:
+            t1.record()
+            t1.synchronize()
+            timing['n_pairs'] = n
+            timing['ms'] = t0.elapsed_time(t1)
+        del ws
+        m = n_entries.value
+    return dst[:m], src[:m], A[:m], frac_b, mesh_area, grid_area

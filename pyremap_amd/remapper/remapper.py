@@ -144,7 +144,10 @@ class Remapper:
         form: ``conserve`` / ``bilinear`` / ``neareststod`` between two
         lat-lon grids, or two grids of one projection, and ``bilinear`` from
         an MPAS mesh (cells, edges or vertices, given by its mesh file) to
-        anything -- ESMF's weights, reproduced (:mod:`pyremap_amd.weights`).  The file is written to
+        anything -- ESMF's weights, reproduced (:mod:`pyremap_amd.weights`) --
+        and ``conserve`` between an MPAS cell mesh (given by its mesh file)
+        and a lat-lon grid, either way: ESMF's first-order conservative map,
+        the cell overlaps clipped on the GPU.  The file is written to
         ``map_filename`` (default name as in ``setup.py:29-42``).
         """
         from pyremap_amd.remapper.setup import _setup_remapper
@@ -153,8 +156,9 @@ class Remapper:
                 'pyremap_amd applies existing mapping files on the GPU; '
                 'build the mapping file with ESMF_RegridWeightGen / mbtempest '
                 '(e.g. through pyremap) and pass it as map_filename, or use '
-                "map_tool='analytic' for lat-lon / projection grid pairs and "
-                "bilinear maps from an MPAS mesh")
+                "map_tool='analytic' for lat-lon / projection grid pairs, "
+                "bilinear maps from an MPAS mesh and conserve maps between an "
+                "MPAS cell mesh and a lat-lon grid")
         _setup_remapper(self)
         from pyremap_amd.weights import write_weights
         if logger is not None:

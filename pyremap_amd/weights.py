@@ -30,6 +30,13 @@ axes the common methods have closed forms:
   for ``test_mpas_{cell,edge,vertex}_to_latlon`` and
   ``test_mpas_cell_to_stereographic`` to rounding, the unmapped cells
   included.
+* ``conserve`` between an MPAS cell mesh (given by its mesh file) and a
+  lat-lon grid, either way (:func:`conserve_mesh_latlon`) -- ESMF's
+  first-order conservative map: every cell a spherical polygon with
+  great-circle edges (lat-lon cells too), S[i, j] = area(dst i n src j) /
+  area(dst i), ``frac_b`` = min(sum_j area(dst i n src j) / area(dst i), 1).
+  The overlaps are clipped on the GPU (``remap_overlap_latlon``,
+  ``pyremap_amd/csrc/remap_overlap.hip``).
 
 The result is a :class:`pyremap_amd.io.mapfile.MappingFile` with exactly the
 schema ESMF writes (1-based ``row``/``col``, Fortran-ordered grid dims), so it
@@ -39,6 +46,7 @@ import numpy as np
 
 from pyremap_amd.descriptor import (
     LatLonGridDescriptor,
+    MpasCellMeshDescriptor,
     MpasMeshDescriptor,
     PointCollectionDescriptor,
     ProjectionGridDescriptor,
@@ -707,6 +715,100 @@ def bilinear_3d(src_descriptor, plat, plon, tol=1e-10, chunk=1 << 20):
     return row[keep], col[keep], S[keep], mapped
 
 
+# ---------------------------------------------------------------------------
+# conserve between an MPAS cell mesh and a lat-lon grid: polygon clipping on
+# the GPU
+# ---------------------------------------------------------------------------
+
+_MESH_VARIABLES = ('verticesOnCell', 'nEdgesOnCell', 'latVertex', 'lonVertex')
+
+
+def mesh_polygons(descriptor):
+    """The cell polygons of an MPAS mesh from its file: ``(verticesOnCell
+    (nCells, maxEdges) 1-based, nEdgesOnCell, latVertex, lonVertex)``, the
+    coordinates in radians."""
+    if getattr(descriptor, 'filename', None) is None:
+        raise ValueError(
+            'conservative weights with an MPAS mesh need its mesh file '
+            '(cell polygons): construct the descriptor with filename=')
+    from pyremap_amd.io.netcdf import open_dataset
+    ds = open_dataset(descriptor.filename)
+    missing = [v for v in _MESH_VARIABLES if v not in ds]
+    if missing:
+        raise ValueError(
+            f'{descriptor.filename}: conservative weights need the mesh '
+            f'variables {list(_MESH_VARIABLES)}; missing {missing}')
+    voc = np.asarray(ds['verticesOnCell'].values, dtype=np.int32)
+    noc = np.asarray(ds['nEdgesOnCell'].values, dtype=np.int32)
+    lat = np.asarray(ds['latVertex'].values, dtype=np.float64)
+    lon = np.asarray(ds['lonVertex'].values, dtype=np.float64)
+    return voc, noc, lat, lon
+
+
+def latlon_corners(descriptor):
+    """(lat corners clipped to +-pi/2, lon corners), radians, of a lat-lon
+    grid, and the largest distance in latitude by which one of its cells'
+    great-circle edges leaves its corners' latitude (the arc between two
+    corners on one parallel bulges poleward)."""
+    _, _, lat_e, lon_e, period, _ = _axes(descriptor)
+    lat_e = np.asarray(lat_e, dtype=np.float64)
+    lon_e = np.asarray(lon_e, dtype=np.float64)
+    span = abs(lon_e[-1] - lon_e[0])
+    if period is not None and abs(span - 2.0 * np.pi) > 1e-9:
+        raise ValueError(
+            f'a global lat-lon grid must close in longitude: its corners span '
+            f'{np.degrees(span)} degrees')
+    half = 0.5 * np.abs(np.diff(lon_e)).max()
+    if half >= 0.5 * np.pi:
+        raise ValueError('lat-lon cells wider than 180 degrees in longitude '
+                         'have no great-circle edges')
+    phi = np.abs(lat_e[np.abs(lat_e) < 0.5 * np.pi])
+    bulge = np.arctan(np.tan(phi) / np.cos(half)) - phi if len(phi) else \
+        np.zeros(1)
+    return lat_e, lon_e, float(bulge.max(initial=0.0))
+
+
+def conserve_mesh_latlon(mesh_descriptor, grid_descriptor, mesh_is_src=True,
+                         device=None, timing=None):
+    """
+    First-order conservative weights between an MPAS cell mesh (its file)
+    and a lat-lon grid, either direction, ESMF's ``destarea`` normalisation:
+    ``S_ij = A_ij / A_i`` and ``frac_b_i = min(sum_j A_ij / A_i, 1)``, where
+    ``A_ij`` is the spherical area of destination cell ``i`` n source cell
+    ``j`` and ``A_i`` the destination cell's area, every cell a polygon with
+    great-circle edges.  Rows without overlap have no entries and
+    ``frac_b = 0``.  The overlaps come from the GPU
+    (:func:`pyremap_amd.engine.overlap_latlon`).
+    """
+    from pyremap_amd import engine
+    torch = engine.require_gpu()
+    voc, noc, lat_v, lon_v = mesh_polygons(mesh_descriptor)
+    lat_e, lon_e, slack = latlon_corners(grid_descriptor)
+    if device is None:
+        device = f'cuda:{torch.cuda.current_device()}'
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    dst, src, A, frac_b, mesh_area, grid_area = engine.overlap_latlon(
+        dev(voc), dev(noc), dev(lat_v), dev(lon_v), dev(lat_e), dev(lon_e),
+        slack, dst_is_mesh=not mesh_is_src, timing=timing)
+    dst = dst.cpu().numpy()
+    src = src.cpu().numpy()
+    A = A.cpu().numpy()
+    frac_b = frac_b.cpu().numpy()
+    dst_area = (grid_area if mesh_is_src else mesh_area).cpu().numpy()
+    S = A / dst_area[dst]
+    n_mesh, n_grid = len(noc), (len(lat_e) - 1) * (len(lon_e) - 1)
+    mesh_dims = np.array([n_mesh], dtype=np.int32)
+    grid_dims = np.array([len(lon_e) - 1, len(lat_e) - 1], dtype=np.int32)
+    if mesh_is_src:
+        n_a, n_b, src_dims, dst_dims = n_mesh, n_grid, mesh_dims, grid_dims
+    else:
+        n_a, n_b, src_dims, dst_dims = n_grid, n_mesh, grid_dims, mesh_dims
+    return MappingFile(n_a, n_b, src_dims, dst_dims,
+                       (dst + 1).astype(np.int32), (src + 1).astype(np.int32),
+                       S, frac_b)
+
 
 def _cell_centres(descriptor):
     """(lat, lon) in radians of every cell centre of a rectangular grid, in
@@ -731,10 +833,20 @@ def build_weights(src_descriptor, dst_descriptor, method='conserve'):
     The mapping between two rectangular grids (lat-lon or on a map
     projection; ``conserve`` only between grids of the same kind), or from
     one to scattered points (an MPAS mesh's cell / edge / vertex positions,
-    a point collection), as a :class:`MappingFile`.
+    a point collection), as a :class:`MappingFile`.  ``conserve`` also
+    between an MPAS cell mesh given by its mesh file and a lat-lon grid,
+    either way (:func:`conserve_mesh_latlon`, on the GPU).
     """
     if method not in METHODS:
         raise ValueError(f'method {method!r}: expected one of {METHODS}')
+    if method == 'conserve':
+        for mesh, grid, mesh_is_src in ((src_descriptor, dst_descriptor, True),
+                                        (dst_descriptor, src_descriptor,
+                                         False)):
+            if isinstance(mesh, MpasCellMeshDescriptor) and \
+                    getattr(mesh, 'filename', None) is not None and \
+                    isinstance(grid, LatLonGridDescriptor):
+                return conserve_mesh_latlon(mesh, grid, mesh_is_src)
     points = _points(dst_descriptor)
     if isinstance(src_descriptor, MpasMeshDescriptor):
         if points is not None:
