@@ -38,11 +38,8 @@
 //    the chunk-major work list, so the ~nnz/n_a re-touches of a source row by
 //    neighbouring destination rows hit that XCD's L2 instead of going back
 //    to Infinity Cache / HBM eight times.
-#include <cstdlib>
 #include <type_traits>
 #include <utility>
-
-#include <hip/hip_ext.h>
 
 #include "remap_common.h"
 
@@ -80,22 +77,55 @@ namespace {
 // ---------------------------------------------------------------------------
 // host-side dispatch
 // ---------------------------------------------------------------------------
+
+// pick(mode) with the call's mode as a compile-time tag (a
+// std::integral_constant, which converts to the kernel template's int):
+// RAW, FRACB, and MASKED for anything else.  MASKED = false: a family without
+// the masked mode, FRACB for anything but RAW.
+template <bool MASKED = true, class F>
+auto by_mode(int mode, F pick)
+{
+    switch (mode) {
+    case REMAP_MODE_RAW:
+        return pick(std::integral_constant<int, REMAP_MODE_RAW>());
+    case REMAP_MODE_FRACB:
+        return pick(std::integral_constant<int, REMAP_MODE_FRACB>());
+    default:
+        if constexpr (MASKED)
+            return pick(std::integral_constant<int, REMAP_MODE_MASKED>());
+        else
+            return pick(std::integral_constant<int, REMAP_MODE_FRACB>());
+    }
+}
+
+// ... and pick(mode, fma) with REMAP_FLAG_FMA as a second tag
+template <bool MASKED = true, class F>
+auto by_mode(int mode, bool fma, F pick)
+{
+    return by_mode<MASKED>(mode, [&](auto m) {
+        return fma ? pick(m, std::true_type()) : pick(m, std::false_type());
+    });
+}
+
+// go(X) with the call's fields typed: float for float32, else double
+template <class F>
+auto with_x(const remap_apply_args *a, bool f32, F go)
+{
+    return f32 ? go(static_cast<const float *>(a->X))
+               : go(static_cast<const double *>(a->X));
+}
+
+template <class P>
+using elem_t = std::remove_const_t<std::remove_pointer_t<P>>;
+
 typedef void (*kernel_fn)(const KParams, const uint32_t);
 
 template <typename XT, int VEC, int TILES, int UNROLL>
 kernel_fn pick_rowwave(int mode, bool fma)
 {
-    switch (mode) {
-    case REMAP_MODE_RAW:
-        return fma ? spmm_rowwave<XT, VEC, TILES, REMAP_MODE_RAW, true, UNROLL>
-                   : spmm_rowwave<XT, VEC, TILES, REMAP_MODE_RAW, false, UNROLL>;
-    case REMAP_MODE_FRACB:
-        return fma ? spmm_rowwave<XT, VEC, TILES, REMAP_MODE_FRACB, true, UNROLL>
-                   : spmm_rowwave<XT, VEC, TILES, REMAP_MODE_FRACB, false, UNROLL>;
-    default:
-        return fma ? spmm_rowwave<XT, VEC, TILES, REMAP_MODE_MASKED, true, UNROLL>
-                   : spmm_rowwave<XT, VEC, TILES, REMAP_MODE_MASKED, false, UNROLL>;
-    }
+    return by_mode(mode, fma, [](auto m, auto f) {
+        return spmm_rowwave<XT, VEC, TILES, m, f, UNROLL>;
+    });
 }
 
 template <typename XT>
@@ -116,17 +146,9 @@ kernel_fn pick_rowwave_shape(int vec, int tiles, int mode, bool fma)
 template <typename XT, int UNR>
 kernel_fn pick_rowlane_mode(int mode, bool fma)
 {
-    switch (mode) {
-    case REMAP_MODE_RAW:
-        return fma ? spmm_rowlane<XT, REMAP_MODE_RAW, true, UNR>
-                   : spmm_rowlane<XT, REMAP_MODE_RAW, false, UNR>;
-    case REMAP_MODE_FRACB:
-        return fma ? spmm_rowlane<XT, REMAP_MODE_FRACB, true, UNR>
-                   : spmm_rowlane<XT, REMAP_MODE_FRACB, false, UNR>;
-    default:
-        return fma ? spmm_rowlane<XT, REMAP_MODE_MASKED, true, UNR>
-                   : spmm_rowlane<XT, REMAP_MODE_MASKED, false, UNR>;
-    }
+    return by_mode(mode, fma, [](auto m, auto f) {
+        return spmm_rowlane<XT, m, f, UNR>;
+    });
 }
 
 // entries fetched together per lane: 4 (config 3's map, us per launch with
@@ -144,17 +166,9 @@ kernel_fn pick_rowlane(int unr, int mode, bool fma)
 template <typename XT, int TT, int UNR>
 kernel_fn pick_rowcell_mode(int mode, bool fma)
 {
-    switch (mode) {
-    case REMAP_MODE_RAW:
-        return fma ? spmm_rowcell<XT, REMAP_MODE_RAW, true, TT, UNR>
-                   : spmm_rowcell<XT, REMAP_MODE_RAW, false, TT, UNR>;
-    case REMAP_MODE_FRACB:
-        return fma ? spmm_rowcell<XT, REMAP_MODE_FRACB, true, TT, UNR>
-                   : spmm_rowcell<XT, REMAP_MODE_FRACB, false, TT, UNR>;
-    default:
-        return fma ? spmm_rowcell<XT, REMAP_MODE_MASKED, true, TT, UNR>
-                   : spmm_rowcell<XT, REMAP_MODE_MASKED, false, TT, UNR>;
-    }
+    return by_mode(mode, fma, [](auto m, auto f) {
+        return spmm_rowcell<XT, m, f, TT, UNR>;
+    });
 }
 
 // tune[1] = fields per lane (4, 8, 16), tune[2] = entries fetched together
@@ -175,17 +189,9 @@ kernel_fn pick_rowcell(int tt, int unr, int mode, bool fma)
 template <typename XT, int SUB, bool TREE>
 kernel_fn pick_rowsub_mode(int mode, bool fma)
 {
-    switch (mode) {
-    case REMAP_MODE_RAW:
-        return fma ? spmm_rowsub<XT, REMAP_MODE_RAW, true, SUB, TREE>
-                   : spmm_rowsub<XT, REMAP_MODE_RAW, false, SUB, TREE>;
-    case REMAP_MODE_FRACB:
-        return fma ? spmm_rowsub<XT, REMAP_MODE_FRACB, true, SUB, TREE>
-                   : spmm_rowsub<XT, REMAP_MODE_FRACB, false, SUB, TREE>;
-    default:
-        return fma ? spmm_rowsub<XT, REMAP_MODE_MASKED, true, SUB, TREE>
-                   : spmm_rowsub<XT, REMAP_MODE_MASKED, false, SUB, TREE>;
-    }
+    return by_mode(mode, fma, [](auto m, auto f) {
+        return spmm_rowsub<XT, m, f, SUB, TREE>;
+    });
 }
 
 template <typename XT>
@@ -207,17 +213,9 @@ typedef void (*patch_fn)(const KParams, const uint32_t, const int32_t *,
 template <typename XT, int WC, bool DMA, int BLOCK = kPatchBlock>
 patch_fn pick_patch_wc(int mode, bool fma)
 {
-    switch (mode) {
-    case REMAP_MODE_RAW:
-        return fma ? spmm_patch<XT, REMAP_MODE_RAW, true, WC, DMA, BLOCK>
-                   : spmm_patch<XT, REMAP_MODE_RAW, false, WC, DMA, BLOCK>;
-    case REMAP_MODE_FRACB:
-        return fma ? spmm_patch<XT, REMAP_MODE_FRACB, true, WC, DMA, BLOCK>
-                   : spmm_patch<XT, REMAP_MODE_FRACB, false, WC, DMA, BLOCK>;
-    default:
-        return fma ? spmm_patch<XT, REMAP_MODE_MASKED, true, WC, DMA, BLOCK>
-                   : spmm_patch<XT, REMAP_MODE_MASKED, false, WC, DMA, BLOCK>;
-    }
+    return by_mode(mode, fma, [](auto m, auto f) {
+        return spmm_patch<XT, m, f, WC, DMA, BLOCK>;
+    });
 }
 
 // wc = columns per K-chunk (128 / 64); dma = 16-byte LDS-DMA pieces of
@@ -251,17 +249,9 @@ typedef void (*cell_fn)(const KParams, const uint32_t, const int32_t *,
 template <typename XT, int TT, int LAYOUT>
 cell_fn pick_patchcell_mode(int mode, bool fma)
 {
-    switch (mode) {
-    case REMAP_MODE_RAW:
-        return fma ? spmm_patchcell<XT, REMAP_MODE_RAW, true, TT, LAYOUT>
-                   : spmm_patchcell<XT, REMAP_MODE_RAW, false, TT, LAYOUT>;
-    case REMAP_MODE_FRACB:
-        return fma ? spmm_patchcell<XT, REMAP_MODE_FRACB, true, TT, LAYOUT>
-                   : spmm_patchcell<XT, REMAP_MODE_FRACB, false, TT, LAYOUT>;
-    default:
-        return fma ? spmm_patchcell<XT, REMAP_MODE_MASKED, true, TT, LAYOUT>
-                   : spmm_patchcell<XT, REMAP_MODE_MASKED, false, TT, LAYOUT>;
-    }
+    return by_mode(mode, fma, [](auto m, auto f) {
+        return spmm_patchcell<XT, m, f, TT, LAYOUT>;
+    });
 }
 
 template <typename XT, int LAYOUT>
@@ -272,20 +262,13 @@ cell_fn pick_patchcell_tt(int tt, int mode, bool fma)
                       : pick_patchcell_mode<XT, 8, LAYOUT>(mode, fma);
 }
 
-template <typename XT, int TT, int BLOCK>
+// RUNS: (Time, nCells, 4 ... 15) a batch at a time, 4 or 6 columns per chunk
+template <typename XT, int TT, int BLOCK, bool RUNS = false>
 cell_fn pick_patchtime_mode(int mode, bool fma)
 {
-    switch (mode) {
-    case REMAP_MODE_RAW:
-        return fma ? spmm_patchtime<XT, REMAP_MODE_RAW, true, TT, BLOCK>
-                   : spmm_patchtime<XT, REMAP_MODE_RAW, false, TT, BLOCK>;
-    case REMAP_MODE_FRACB:
-        return fma ? spmm_patchtime<XT, REMAP_MODE_FRACB, true, TT, BLOCK>
-                   : spmm_patchtime<XT, REMAP_MODE_FRACB, false, TT, BLOCK>;
-    default:
-        return fma ? spmm_patchtime<XT, REMAP_MODE_MASKED, true, TT, BLOCK>
-                   : spmm_patchtime<XT, REMAP_MODE_MASKED, false, TT, BLOCK>;
-    }
+    return by_mode(mode, fma, [](auto m, auto f) {
+        return spmm_patchtime<XT, m, f, TT, BLOCK, RUNS>;
+    });
 }
 
 template <typename XT, int BLOCK>
@@ -296,36 +279,14 @@ cell_fn pick_patchtime_tt(int tt, int mode, bool fma)
                      : pick_patchtime_mode<XT, 8, BLOCK>(mode, fma);
 }
 
-// (Time, nCells, 4 ... 15): a batch at a time, 4 or 8 columns per chunk
-template <typename XT, int BLOCK, int TT>
-cell_fn pick_patchruns_mode(int mode, bool fma)
-{
-    switch (mode) {
-    case REMAP_MODE_RAW:
-        return fma ? spmm_patchtime<XT, REMAP_MODE_RAW, true, TT, BLOCK, true>
-                   : spmm_patchtime<XT, REMAP_MODE_RAW, false, TT, BLOCK,
-                                    true>;
-    case REMAP_MODE_FRACB:
-        return fma ? spmm_patchtime<XT, REMAP_MODE_FRACB, true, TT, BLOCK,
-                                    true>
-                   : spmm_patchtime<XT, REMAP_MODE_FRACB, false, TT, BLOCK,
-                                    true>;
-    default:
-        return fma ? spmm_patchtime<XT, REMAP_MODE_MASKED, true, TT, BLOCK,
-                                    true>
-                   : spmm_patchtime<XT, REMAP_MODE_MASKED, false, TT, BLOCK,
-                                    true>;
-    }
-}
-
 // (8 columns per chunk -- one chunk per batch at L = 8 -- was built and
 // measured in round 5: slower at every L, 0.63 against 0.59 ms at L = 8, 0.83
 // against 0.68 at L = 10: twice the LDS image, half the workgroups per CU)
 template <typename XT, int TT>
 cell_fn pick_patchruns_block(int mode, bool fma, int block)
 {
-    return block == 256 ? pick_patchruns_mode<XT, 256, TT>(mode, fma)
-                        : pick_patchruns_mode<XT, 512, TT>(mode, fma);
+    return block == 256 ? pick_patchtime_mode<XT, TT, 256, true>(mode, fma)
+                        : pick_patchtime_mode<XT, TT, 512, true>(mode, fma);
 }
 
 template <typename XT>
@@ -364,21 +325,6 @@ cell_fn pick_patchcell(int tt, int mode, bool fma, int layout)
 // LDS a workgroup may ask for and still leave room for a second one per CU
 constexpr uint32_t kPatchLdsMax = 160 * 1024;
 
-bool patch_usable(const remap_apply_args *a, int64_t K64)
-{
-    return a->patch_ptr && a->patch_ucol && a->patch_lidx &&
-           a->patch_rowptr && a->patch_val && a->patch_rows > 0 &&
-           a->patch_rows < kPatchBlock && a->n_patches > 0 &&
-           a->patch_umax >= 0 && a->patch_emax >= 0 && K64 >= 2 &&
-           (a->patch_row_bytes == 1024 || a->patch_row_bytes == 512) &&
-           patch_lds_bytes(a->patch_umax, a->patch_emax, a->patch_rows,
-                           a->patch_row_bytes) <= kPatchLdsMax &&
-           a->row_end - a->row_begin <=
-               a->n_patches * (int64_t)a->patch_rows &&
-           a->row_end - a->row_begin >
-               (a->n_patches - 1) * (int64_t)a->patch_rows;
-}
-
 template <typename XT>
 struct ScalarFn {
     typedef void (*type)(const KParams, const uint32_t, const int64_t *,
@@ -389,17 +335,9 @@ struct ScalarFn {
 template <typename XT, int VEC, int TILES>
 typename ScalarFn<XT>::type pick_rowscalar_mode(int mode, bool fma)
 {
-    switch (mode) {
-    case REMAP_MODE_RAW:
-        return fma ? spmm_rowscalar<XT, VEC, TILES, REMAP_MODE_RAW, true>
-                   : spmm_rowscalar<XT, VEC, TILES, REMAP_MODE_RAW, false>;
-    case REMAP_MODE_FRACB:
-        return fma ? spmm_rowscalar<XT, VEC, TILES, REMAP_MODE_FRACB, true>
-                   : spmm_rowscalar<XT, VEC, TILES, REMAP_MODE_FRACB, false>;
-    default:
-        return fma ? spmm_rowscalar<XT, VEC, TILES, REMAP_MODE_MASKED, true>
-                   : spmm_rowscalar<XT, VEC, TILES, REMAP_MODE_MASKED, false>;
-    }
+    return by_mode(mode, fma, [](auto m, auto f) {
+        return spmm_rowscalar<XT, VEC, TILES, m, f>;
+    });
 }
 
 template <typename XT>
@@ -413,38 +351,33 @@ typename ScalarFn<XT>::type pick_rowscalar(int vec, int tiles, int mode,
                       : pick_rowscalar_mode<XT, 2, 2>(mode, fma);
 }
 
-template <typename XT>
-int launch_rowscalar(const remap_apply_args *a, const KParams &p, int vec,
-                     int tiles, bool fma, int64_t grid, hipStream_t stream)
+// Every launch: `grid` workgroups of `block` threads with `lds_bytes` of
+// dynamic LDS (past 64 KiB by attribute), then the launch error.  Diagnostic
+// build only (tune[7]): KiB of unused dynamic LDS per block at the least, an
+// occupancy throttle for bottleneck experiments.
+template <typename... P, typename... A>
+int launch(void (*fn)(P...), const remap_apply_args *a, int64_t grid,
+           uint32_t block, uint32_t lds_bytes, hipStream_t stream,
+           const A &...args)
 {
-    typename ScalarFn<XT>::type fn =
-        pick_rowscalar<XT>(vec, tiles, a->mode, fma);
-    hipLaunchKernelGGL(fn, dim3(static_cast<uint32_t>(grid)), dim3(kBlock), 0,
-                       stream, p, a->flags, a->A.rowptr, a->A.col, a->A.val,
-                       a->row_order, a->frac_b,
-                       static_cast<const XT *>(a->X));
-    REMAP_HIP_CHECK(hipGetLastError());
-    return REMAP_OK;
-}
-
-// Diagnostic build only (tune[7]): KiB of unused dynamic LDS per block, an
-// occupancy throttle for bottleneck experiments.  The product build launches
-// with no dynamic LDS.
-hipError_t diag_lds_throttle(const remap_apply_args *a, const void *fn,
-                             uint32_t &lds_bytes)
-{
+    if (grid <= 0 || grid > 0x7fffffffLL)
+        return fail(REMAP_ERR_UNSUPPORTED,
+                    "remap_apply_f64: grid of %lld blocks; split the rows",
+                    (long long)grid);
 #ifdef REMAP_DIAG
     if (a->tune[7] > 0 && (uint32_t)a->tune[7] * 1024u > lds_bytes)
         lds_bytes = a->tune[7] * 1024u;
-    if (lds_bytes > 64 * 1024)
-        return hipFuncSetAttribute(
-            fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
 #else
     (void)a;
-    (void)fn;
-    (void)lds_bytes;
 #endif
-    return hipSuccess;
+    if (lds_bytes > 64 * 1024)
+        REMAP_HIP_CHECK(hipFuncSetAttribute(
+            reinterpret_cast<const void *>(fn),
+            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    hipLaunchKernelGGL(fn, dim3(static_cast<uint32_t>(grid)), dim3(block),
+                       lds_bytes, stream, args...);
+    REMAP_HIP_CHECK(hipGetLastError());
+    return REMAP_OK;
 }
 
 template <typename XT>
@@ -457,23 +390,9 @@ struct GroupFn {
 template <typename XT, int TILES, int G, int UNR, int VEC>
 typename GroupFn<XT>::type pick_rowgroup_mode(int mode, bool fma)
 {
-    switch (mode) {
-    case REMAP_MODE_RAW:
-        return fma ? spmm_rowgroup<XT, TILES, REMAP_MODE_RAW, true, G, UNR,
-                                   VEC>
-                   : spmm_rowgroup<XT, TILES, REMAP_MODE_RAW, false, G, UNR,
-                                   VEC>;
-    case REMAP_MODE_FRACB:
-        return fma ? spmm_rowgroup<XT, TILES, REMAP_MODE_FRACB, true, G, UNR,
-                                   VEC>
-                   : spmm_rowgroup<XT, TILES, REMAP_MODE_FRACB, false, G, UNR,
-                                   VEC>;
-    default:
-        return fma ? spmm_rowgroup<XT, TILES, REMAP_MODE_MASKED, true, G, UNR,
-                                   VEC>
-                   : spmm_rowgroup<XT, TILES, REMAP_MODE_MASKED, false, G,
-                                   UNR, VEC>;
-    }
+    return by_mode(mode, fma, [](auto m, auto f) {
+        return spmm_rowgroup<XT, TILES, m, f, G, UNR, VEC>;
+    });
 }
 
 template <typename XT, int G, int UNR>
@@ -509,17 +428,9 @@ typename GroupFn<XT>::type pick_rowgroup_shape(int unr, int tiles, int vec,
 template <int BLOCK>
 GroupFn<double>::type pick_rowgroup_lock(int mode)
 {
-    switch (mode) {
-    case REMAP_MODE_RAW:
-        return spmm_rowgroup<double, 1, REMAP_MODE_RAW, false, 4, 8, 2, true,
-                             BLOCK>;
-    case REMAP_MODE_FRACB:
-        return spmm_rowgroup<double, 1, REMAP_MODE_FRACB, false, 4, 8, 2,
-                             true, BLOCK>;
-    default:
-        return spmm_rowgroup<double, 1, REMAP_MODE_MASKED, false, 4, 8, 2,
-                             true, BLOCK>;
-    }
+    return by_mode(mode, [](auto m) {
+        return spmm_rowgroup<double, 1, m, false, 4, 8, 2, true, BLOCK>;
+    });
 }
 #endif
 
@@ -527,23 +438,9 @@ GroupFn<double>::type pick_rowgroup_lock(int mode)
 template <int TILES, int G, int UNR>
 GroupFn<double>::type pick_grouproll_mode(int mode, bool fma)
 {
-    switch (mode) {
-    case REMAP_MODE_RAW:
-        return fma ? spmm_grouproll<double, TILES, REMAP_MODE_RAW, true, G,
-                                    UNR, 2>
-                   : spmm_grouproll<double, TILES, REMAP_MODE_RAW, false, G,
-                                    UNR, 2>;
-    case REMAP_MODE_FRACB:
-        return fma ? spmm_grouproll<double, TILES, REMAP_MODE_FRACB, true, G,
-                                    UNR, 2>
-                   : spmm_grouproll<double, TILES, REMAP_MODE_FRACB, false, G,
-                                    UNR, 2>;
-    default:
-        return fma ? spmm_grouproll<double, TILES, REMAP_MODE_MASKED, true, G,
-                                    UNR, 2>
-                   : spmm_grouproll<double, TILES, REMAP_MODE_MASKED, false,
-                                    G, UNR, 2>;
-    }
+    return by_mode(mode, fma, [](auto m, auto f) {
+        return spmm_grouproll<double, TILES, m, f, G, UNR, 2>;
+    });
 }
 
 template <int G>
@@ -557,10 +454,9 @@ GroupFn<double>::type pick_grouproll(int unr, int tiles, int mode, bool fma)
 }
 
 template <typename XT>
-int launch_rowgroup(const remap_apply_args *a, const KParams &p, int tiles,
-                    int unr, int vec, int wpb, bool fma, int64_t grid,
-                    hipStream_t stream, bool lock = false, int roll = 0,
-                    bool cell_masks = false)
+typename GroupFn<XT>::type pick_rowgroup(const remap_apply_args *a, int tiles,
+                                         int unr, int vec, int wpb, bool fma,
+                                         bool lock, int roll, bool cell_masks)
 {
     typename GroupFn<XT>::type fn =
         a->group_rows == 8
@@ -594,83 +490,9 @@ int launch_rowgroup(const remap_apply_args *a, const KParams &p, int tiles,
     }
 #else
     (void)lock;
+    (void)wpb;
 #endif
-    uint32_t lds_bytes = 0;
-    REMAP_HIP_CHECK(diag_lds_throttle(a, reinterpret_cast<const void *>(fn),
-                                      lds_bytes));
-    hipLaunchKernelGGL(fn, dim3(static_cast<uint32_t>(grid)),
-                       dim3(kWave * wpb), lds_bytes, stream, p, a->flags,
-                       a->group_meta,
-                       a->group_col, a->group_w, a->group_mask, a->group_rid,
-                       a->group_frac, static_cast<const XT *>(a->X));
-    REMAP_HIP_CHECK(hipGetLastError());
-    return REMAP_OK;
-}
-
-// REMAP_FLAG_BATCH_MASKS, masked mode on 8-row groups: time-major columns,
-// one normaliser per lane and row (spmm_grouptime.h)
-template <typename XT>
-int launch_grouptime(const remap_apply_args *a, const KParams &p, int wpb,
-                     bool fma, int64_t grid, hipStream_t stream)
-{
-    typename GroupFn<XT>::type fn = fma ? spmm_grouptime<XT, true, 8, 8, 4>
-                                        : spmm_grouptime<XT, false, 8, 8, 4>;
-    hipLaunchKernelGGL(fn, dim3(static_cast<uint32_t>(grid)),
-                       dim3(kWave * wpb), 0, stream, p, a->flags,
-                       a->group_meta, a->group_col, a->group_w, a->group_mask,
-                       a->group_rid, a->group_frac,
-                       static_cast<const XT *>(a->X));
-    REMAP_HIP_CHECK(hipGetLastError());
-    return REMAP_OK;
-}
-
-// ... and through the LDS ring of the shared form where the mapping has the
-// shared lists (spmm_timeshare.h): float64 fields in whole 16-byte pieces
-int launch_timeshare(const remap_apply_args *a, const KParams &p, bool fma,
-                     int64_t grid, hipStream_t stream)
-{
-    void (*fn)(const KParams, const uint32_t, const int64_t *,
-               const int32_t *, const double *, const int32_t *,
-               const int32_t *, const int64_t *, const int32_t *,
-               const int32_t *, const double *) =
-        fma ? spmm_timeshare<true, 1> : spmm_timeshare<false, 1>;
-    // the ring: two buffers of 8 entries x (4 slices x 512 B); 2 x 4 slots
-    // of a step's weights; slack
-    uint32_t lds_bytes = 2u * (8u * 2048u + 4u * 512u) + 512u;
-    REMAP_HIP_CHECK(diag_lds_throttle(a, reinterpret_cast<const void *>(fn),
-                                      lds_bytes));
-    hipLaunchKernelGGL(fn, dim3(static_cast<uint32_t>(grid)), dim3(kWave * 4),
-                       lds_bytes, stream, p, a->flags, a->group_meta,
-                       a->group_col, a->group_w, a->group_mask, a->group_rid,
-                       a->share_meta, a->share_col, a->share_mask,
-                       static_cast<const double *>(a->X));
-    REMAP_HIP_CHECK(hipGetLastError());
-    return REMAP_OK;
-}
-
-// REMAP_FLAG_CELL_MASKS through the LDS ring of the shared form: one
-// normaliser per ROW (spmm_cellshare.h); float64 fields in whole 16-byte
-// pieces, 256 columns per workgroup
-int launch_cellshare(const remap_apply_args *a, const KParams &p, bool fma,
-                     int64_t grid, hipStream_t stream)
-{
-    void (*fn)(const KParams, const uint32_t, const int64_t *,
-               const int32_t *, const double *, const int32_t *,
-               const int32_t *, const int64_t *, const int32_t *,
-               const int32_t *, const double *) =
-        fma ? spmm_cellshare<true, 1> : spmm_cellshare<false, 1>;
-    // the ring: two buffers of 8 entries x 2 KiB; 2 x 4 slots of a step's
-    // weights; slack
-    uint32_t lds_bytes = 2u * (8u * 2048u + 4u * 512u) + 512u;
-    REMAP_HIP_CHECK(diag_lds_throttle(a, reinterpret_cast<const void *>(fn),
-                                      lds_bytes));
-    hipLaunchKernelGGL(fn, dim3(static_cast<uint32_t>(grid)), dim3(kWave * 4),
-                       lds_bytes, stream, p, a->flags, a->group_meta,
-                       a->group_col, a->group_w, a->group_mask, a->group_rid,
-                       a->share_meta, a->share_col, a->share_mask,
-                       static_cast<const double *>(a->X));
-    REMAP_HIP_CHECK(hipGetLastError());
-    return REMAP_OK;
+    return fn;
 }
 
 // the shared form (spmm_groupshare.h): float64, two elements per lane
@@ -685,59 +507,12 @@ typedef void (*share_fn)(const KParams, const uint32_t, const int64_t *,
 // the masked mode with per-lane normalisers, 32.1 at one K tile and 37.8 at
 // two against 27.0 of the 8-row groups: profiles/r06_analysis/
 // config5_share.md.  The masked mode's shared form is spmm_timeshare.)
-template <int TILES, bool FMA>
-share_fn pick_groupshare(int mode)
+template <int TILES>
+share_fn pick_groupshare(int mode, bool fma)
 {
-    return mode == REMAP_MODE_RAW
-               ? spmm_groupshare<TILES, REMAP_MODE_RAW, FMA, 4, 8, 2, 2>
-               : spmm_groupshare<TILES, REMAP_MODE_FRACB, FMA, 4, 8, 2, 2>;
-}
-
-int launch_groupshare(const remap_apply_args *a, const KParams &p, int tiles,
-                      bool fma, int64_t grid, hipStream_t stream)
-{
-    share_fn fn = tiles == 1 ? (fma ? pick_groupshare<1, true>(a->mode)
-                                    : pick_groupshare<1, false>(a->mode))
-                             : (fma ? pick_groupshare<2, true>(a->mode)
-                                    : pick_groupshare<2, false>(a->mode));
-    // the ring: two buffers of 8 entries, 1 KiB per entry and K tile; 2 x 4
-    // slots of a step's weights; slack for the lanes that read past the last
-    // slot
-    uint32_t lds_bytes =
-        2u * (8u * 1024u * static_cast<uint32_t>(tiles) + 4u * 512u) + 512u;
-    REMAP_HIP_CHECK(diag_lds_throttle(a, reinterpret_cast<const void *>(fn),
-                                      lds_bytes));
-    hipLaunchKernelGGL(fn, dim3(static_cast<uint32_t>(grid)),
-                       dim3(kWave * 4), lds_bytes, stream, p, a->flags,
-                       a->group_meta, a->group_w, a->group_rid, a->group_frac,
-                       a->share_meta, a->share_col, a->share_mask,
-                       static_cast<const double *>(a->X));
-    REMAP_HIP_CHECK(hipGetLastError());
-    return REMAP_OK;
-}
-
-// the shared form for at most 64 columns (spmm_narrowshare.h)
-int launch_narrowshare(const remap_apply_args *a, const KParams &p, bool fma,
-                       int64_t grid, hipStream_t stream)
-{
-    share_fn fn =
-        a->mode == REMAP_MODE_RAW
-            ? (fma ? spmm_narrowshare<REMAP_MODE_RAW, true, 2>
-                   : spmm_narrowshare<REMAP_MODE_RAW, false, 2>)
-            : (fma ? spmm_narrowshare<REMAP_MODE_FRACB, true, 2>
-                   : spmm_narrowshare<REMAP_MODE_FRACB, false, 2>);
-    // the ring: two buffers of 8 entries x 512 B; 2 x 4 slots of a step's
-    // weights; slack
-    uint32_t lds_bytes = 2u * (8u * 512u + 4u * 512u) + 512u;
-    REMAP_HIP_CHECK(diag_lds_throttle(a, reinterpret_cast<const void *>(fn),
-                                      lds_bytes));
-    hipLaunchKernelGGL(fn, dim3(static_cast<uint32_t>(grid)),
-                       dim3(kWave * 4), lds_bytes, stream, p, a->flags,
-                       a->group_meta, a->group_w, a->group_rid, a->group_frac,
-                       a->share_meta, a->share_col, a->share_mask,
-                       static_cast<const double *>(a->X));
-    REMAP_HIP_CHECK(hipGetLastError());
-    return REMAP_OK;
+    return by_mode<false>(mode, fma, [](auto m, auto f) {
+        return spmm_groupshare<TILES, m, f, 4, 8, 2, 2>;
+    });
 }
 
 bool aligned(const void *p, size_t a)
@@ -758,10 +533,14 @@ struct Call {
     bool can_vec2;        // two elements per lane: even strides, aligned bases
     bool dma16;           // 16-byte pieces of X rows are aligned and whole
     bool small_offsets;   // byte offsets inside a row fit 32 bits
+    bool patch_covers;    // a patch plan covering [row_begin, row_end) is
+                          // attached
     bool patch_ok;        // a usable patch plan is attached
     bool cell_ok;         // a patch plan family 7 can use is attached
     bool group_ok;        // a usable row-group schedule is attached
     bool share_ok;        // ... and shared union lists on top of it
+    bool ring_ok;         // ... that the LDS-ring forms can take: 4 waves,
+                          // float64 in whole 16-byte pieces, flat addresses
     bool strip_ok;        // a strip schedule this call can run on is attached
 };
 
@@ -838,17 +617,22 @@ int check_args(const remap_apply_args *a, Call &c)
     c.small_offsets =
         ((a->n_batch - 1) * a->x_batch_stride + a->k_inner) *
             (int64_t)xelem < (int64_t(1) << 31);
-    c.patch_ok = patch_usable(a, c.K);
-    c.cell_ok = a->patch_ptr && a->patch_ucol && a->patch_lidx &&
-                a->patch_rowptr && a->patch_val && a->patch_rows > 0 &&
-                a->n_patches > 0 && a->patch_umax >= 0 &&
+    c.patch_covers = a->patch_ptr && a->patch_ucol && a->patch_lidx &&
+                     a->patch_rowptr && a->patch_val && a->patch_rows > 0 &&
+                     a->n_patches > 0 &&
+                     c.n_rows <= a->n_patches * (int64_t)a->patch_rows &&
+                     c.n_rows > (a->n_patches - 1) * (int64_t)a->patch_rows;
+    c.patch_ok = c.patch_covers && a->patch_rows < kPatchBlock &&
+                 a->patch_umax >= 0 && a->patch_emax >= 0 && c.K >= 2 &&
+                 (a->patch_row_bytes == 1024 || a->patch_row_bytes == 512) &&
+                 patch_lds_bytes(a->patch_umax, a->patch_emax, a->patch_rows,
+                                 a->patch_row_bytes) <= kPatchLdsMax;
+    c.cell_ok = c.patch_covers && a->patch_umax >= 0 &&
                 // the LDS image run_patchcell asks for at its smallest TT:
                 // its pitch is the padded list length, not umax
                 (int64_t)((a->patch_umax + 2) & ~1) *
                         (a->patch_ell_base ? 1 : 4) * 8 <=
-                    (int64_t)kPatchLdsMax &&
-                c.n_rows <= a->n_patches * (int64_t)a->patch_rows &&
-                c.n_rows > (a->n_patches - 1) * (int64_t)a->patch_rows;
+                    (int64_t)kPatchLdsMax;
     c.group_ok = a->group_meta && a->group_col && a->group_w &&
                  a->group_mask && a->group_rid && a->group_frac &&
                  (a->group_rows == 8 || a->group_rows == 4 ||
@@ -860,6 +644,11 @@ int check_args(const remap_apply_args *a, Call &c)
                  a->share_col && a->share_mask &&
                  (a->share_waves == 2 || a->share_waves == 4) &&
                  a->share_reserved == 0;
+    // the forms of family 10 through an LDS ring address X with a flat
+    // 64-bit address per lane (LDS-DMA): any batch stride
+    c.ring_ok = c.share_ok && a->share_waves == 4 && c.dma16 &&
+                a->x_src_fold == 0 && a->x_row_stride >= 0 &&
+                a->x_row_stride < (int64_t(1) << 29);
     const remap_strips *st = a->strips;
     c.strip_ok = st && st->n_units > 0 && st->steps_per_unit > 0 &&
                  st->rows_per_wave > 0 && st->ring_slots >= 2 &&
@@ -955,16 +744,12 @@ bool runs_usable(const remap_apply_args *a, const Call &c)
 // consecutive long rows per patch, row-major entries (no patch_ell_base).
 bool longwave_usable(const remap_apply_args *a, const Call &c)
 {
-    return a->patch_ptr && a->patch_ucol && a->patch_lidx &&
-           a->patch_rowptr && a->patch_val && !a->patch_ell_base &&
-           a->patch_rows > 0 && a->patch_rows <= kPatchWaves &&
-           a->n_patches > 0 && a->A.max_row_nnz > 0 &&
+    return c.patch_covers && !a->patch_ell_base &&
+           a->patch_rows <= kPatchWaves && a->A.max_row_nnz > 0 &&
            a->patch_rows * (2 * kLongPre * kLongCellBytes +
                             ((a->A.max_row_nnz + 15) / 16 * 16 + 16) *
                                 (int64_t)kLongRecordBytes) <=
-               (int64_t)kPatchLdsMax &&
-           c.n_rows <= a->n_patches * (int64_t)a->patch_rows &&
-           c.n_rows > (a->n_patches - 1) * (int64_t)a->patch_rows;
+               (int64_t)kPatchLdsMax;
 }
 
 // Does the LDS patch kernel (family 5) take a call of K fields?  Its time is
@@ -1001,18 +786,16 @@ constexpr int64_t kNarrowMinK = 34;
 // this call take one of them?
 bool wide_share(const remap_apply_args *a, const Call &c)
 {
-    if (!c.share_ok || !c.dma16 || a->x_src_fold != 0 ||
-        a->x_row_stride < 0 || a->x_row_stride >= (int64_t(1) << 29))
+    if (!c.ring_ok)
         return false;
     if (a->mode == REMAP_MODE_MASKED && (a->flags & REMAP_FLAG_CELL_MASKS) &&
-        a->share_waves == 4 && (a->tune[5] == 0 || a->tune[5] == 32) &&
-        a->group_rows == 8 && c.K > 128)
+        (a->tune[5] == 0 || a->tune[5] == 32) && c.K > 128)
         return true;   // spmm_cellshare.h
     if (a->mode == REMAP_MODE_MASKED)
-        return a->share_waves == 4 && a->n_batch >= 3 &&
+        return a->n_batch >= 3 &&
                (a->flags & (REMAP_FLAG_BATCH_MASKS | REMAP_FLAG_CELL_MASKS)) &&
                (a->tune[5] == 0 || a->tune[5] == 32);
-    return a->share_waves == 4 && a->tune[5] == 32 && c.K >= kShareMinK;
+    return a->tune[5] == 32 && c.K >= kShareMinK;
 }
 
 // REMAP_FLAG_TUNE_HINT: can the preferred family serve this call?
@@ -1081,20 +864,17 @@ int automatic_family(const remap_apply_args *a, const Call &c)
     return a->A.csr_pad >= 8 ? 6 : 1;
 }
 
-// (row blocks x K chunks) work list -> grid size, XCD-aware or not.
-int shape_grid(KParams &p, int64_t n_rowblocks, int64_t n_chunks, bool xcd,
-               int64_t &grid)
+// (row blocks x K chunks) work list -> grid size, XCD-aware or not;
+// side_by_side (tune[4] = 3 on the row-group forms): the K-chunks of a row
+// block side by side.  launch() checks the grid's size.
+int64_t shape_grid(KParams &p, int64_t n_rowblocks, int64_t n_chunks,
+                   bool xcd, bool side_by_side = false)
 {
     p.n_rowblocks = n_rowblocks;
     p.n_blocks = n_rowblocks * n_chunks;
-    p.xcd_map = xcd ? 1 : 0;
+    p.xcd_map = (xcd ? 1 : 0) | (side_by_side ? 2 : 0);
     p.blocks_per_xcd = (p.n_blocks + kXcds - 1) / kXcds;
-    grid = xcd ? p.blocks_per_xcd * kXcds : p.n_blocks;
-    if (grid <= 0 || grid > 0x7fffffffLL)
-        return fail(REMAP_ERR_UNSUPPORTED,
-                    "remap_apply_f64: grid of %lld blocks; split the rows",
-                    (long long)grid);
-    return REMAP_OK;
+    return xcd ? p.blocks_per_xcd * kXcds : p.n_blocks;
 }
 
 int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -1143,6 +923,9 @@ int run_rowgroup(const remap_apply_args *a, const Call &c, KParams p,
                     "row-group schedule for [row_begin, row_end) and 32-bit "
                     "offsets (or the shared lists and a float64 field in "
                     "whole 16-byte pieces)");
+    // tune[4] = 3: the K-chunks of a row block side by side
+    const bool side = a->tune[4] == 3;
+    const double *X64 = static_cast<const double *>(a->X);
     // REMAP_FLAG_CELL_MASKS with the shared lists (remap_schedule_auto builds
     // them on entry-rich mappings): the per-row normaliser through the LDS
     // ring (spmm_cellshare.h) -- flat 64-bit addresses, so a (Time, nCells,
@@ -1150,20 +933,20 @@ int run_rowgroup(const remap_apply_args *a, const Call &c, KParams p,
     // (f32, odd strides, at most 128 columns) takes the forms below;
     // tune[5] = 8 keeps the 8-row groups (spmm_groupmask.h).
     if ((a->flags & REMAP_FLAG_CELL_MASKS) && a->mode == REMAP_MODE_MASKED &&
-        (a->tune[5] == 0 || a->tune[5] == 32) && a->group_rows == 8 &&
-        c.share_ok &&
-        a->share_waves == 4 && c.dma16 && c.K > 128 && a->x_src_fold == 0 &&
-        a->x_row_stride >= 0 && a->x_row_stride < (int64_t(1) << 29)) {
+        (a->tune[5] == 0 || a->tune[5] == 32) && c.ring_ok && c.K > 128) {
         p.rows_per_wave = 1;
         const int64_t k_chunks = shape_tiles(p, a, c.K, kWave * 2, 2);
-        int64_t grid;
-        const int rc = shape_grid(p, ceil_div(a->n_groups, (int64_t)4),
-                                  k_chunks, a->tune[4] != 1, grid);
-        if (rc != REMAP_OK)
-            return rc;
-        if (a->tune[4] == 3)
-            p.xcd_map |= 2;
-        return launch_cellshare(a, p, c.fma, grid, stream);
+        const int64_t grid = shape_grid(p, ceil_div(a->n_groups, (int64_t)4),
+                                        k_chunks, a->tune[4] != 1, side);
+        // one normaliser per ROW; 256 columns per workgroup.  The ring: two
+        // buffers of 8 entries x 2 KiB; 2 x 4 slots of a step's weights;
+        // slack
+        return launch(c.fma ? spmm_cellshare<true, 1>
+                            : spmm_cellshare<false, 1>,
+                      a, grid, kWave * 4, 2u * (8u * 2048u + 4u * 512u) + 512u,
+                      stream, p, a->flags, a->group_meta, a->group_col,
+                      a->group_w, a->group_mask, a->group_rid, a->share_meta,
+                      a->share_col, a->share_mask, X64);
     }
     // tune[5] = 32: the shared form (spmm_groupshare.h) -- W waves, one
     // union through an LDS ring; float64 fields in whole 16-byte pieces,
@@ -1171,31 +954,29 @@ int run_rowgroup(const remap_apply_args *a, const Call &c, KParams p,
     // of the same schedule (a preference under REMAP_FLAG_TUNE_HINT, an
     // error otherwise).
     if (a->tune[5] == 32 && c.K <= kWave && c.K >= kNarrowMinK &&
-        c.share_ok && a->share_waves == 4 && c.dma16 &&
-        a->mode != REMAP_MODE_MASKED && a->x_src_fold == 0 &&
-        a->x_row_stride >= 0 && a->x_row_stride < (int64_t(1) << 29)) {
+        c.ring_ok && a->mode != REMAP_MODE_MASKED) {
         // at most 64 columns: a lane per column, two union entries per DMA
         // instruction (spmm_narrowshare.h)
         const int64_t k_chunks = shape_tiles(p, a, c.K, kWave, 1);
         if (p.bpc == 0) {
             p.rows_per_wave = 1;
-            int64_t grid;
-            const int rc = shape_grid(p, ceil_div(a->n_groups, (int64_t)4),
-                                      k_chunks, a->tune[4] != 1, grid);
-            if (rc != REMAP_OK)
-                return rc;
-            if (a->tune[4] == 3)
-                p.xcd_map |= 2;
-            return launch_narrowshare(a, p, c.fma, grid, stream);
+            const int64_t grid =
+                shape_grid(p, ceil_div(a->n_groups, (int64_t)4), k_chunks,
+                           a->tune[4] != 1, side);
+            // the ring: two buffers of 8 entries x 512 B; 2 x 4 slots of a
+            // step's weights; slack
+            const auto fn = by_mode<false>(a->mode, c.fma, [](auto m, auto f) {
+                return spmm_narrowshare<m, f, 2>;
+            });
+            return launch(fn, a, grid, kWave * 4,
+                          2u * (8u * 512u + 4u * 512u) + 512u, stream, p,
+                          a->flags, a->group_meta, a->group_w, a->group_rid,
+                          a->group_frac, a->share_meta, a->share_col,
+                          a->share_mask, X64);
         }
     }
     if (a->tune[5] == 32) {
-        const bool can = c.share_ok && a->share_waves == 4 && c.dma16 &&
-                         c.K >= kShareMinK &&
-                         a->mode != REMAP_MODE_MASKED &&
-                         a->x_src_fold == 0 && a->x_row_stride >= 0 &&
-                         a->x_row_stride < (int64_t(1) << 29);
-        if (can) {
+        if (c.ring_ok && c.K >= kShareMinK && a->mode != REMAP_MODE_MASKED) {
             // K tiles per wave: 2 (256 columns per workgroup and step); at
             // most 128 columns -- ONE 3-D field of 104 ... 128 levels --: 1
             const int tiles = (a->tune[2] == 1 || c.K <= 128) ? 1 : 2;
@@ -1204,14 +985,19 @@ int run_rowgroup(const remap_apply_args *a, const Call &c, KParams p,
                 shape_tiles(p, a, c.K, kWave * 2, tiles);
             const int64_t n_super =
                 ceil_div(a->n_groups, (int64_t)a->share_waves);
-            int64_t grid;
-            const int rc =
-                shape_grid(p, n_super, k_chunks, a->tune[4] != 1, grid);
-            if (rc != REMAP_OK)
-                return rc;
-            if (a->tune[4] == 3)
-                p.xcd_map |= 2;
-            return launch_groupshare(a, p, tiles, c.fma, grid, stream);
+            const int64_t grid =
+                shape_grid(p, n_super, k_chunks, a->tune[4] != 1, side);
+            // the ring: two buffers of 8 entries, 1 KiB per entry and K tile;
+            // 2 x 4 slots of a step's weights; slack for the lanes that read
+            // past the last slot
+            return launch(tiles == 1 ? pick_groupshare<1>(a->mode, c.fma)
+                                     : pick_groupshare<2>(a->mode, c.fma),
+                          a, grid, kWave * 4,
+                          2u * (8u * 1024u * static_cast<uint32_t>(tiles) +
+                                4u * 512u) + 512u,
+                          stream, p, a->flags, a->group_meta, a->group_w,
+                          a->group_rid, a->group_frac, a->share_meta,
+                          a->share_col, a->share_mask, X64);
         }
         if (!(a->flags & REMAP_FLAG_TUNE_HINT))
             return fail(REMAP_ERR_UNSUPPORTED,
@@ -1240,35 +1026,38 @@ int run_rowgroup(const remap_apply_args *a, const Call &c, KParams p,
         p.bpc = 0;
         const int64_t n_lb = ceil_div(a->k_inner, kWave);
         const int64_t n_tb = ceil_div(a->n_batch, kTimeBlock);
-        int64_t grid;
         // with the shared lists: one union per 4 x 8 tile through the LDS
         // ring (spmm_timeshare.h; tune[5] = 9 keeps the form below)
-        if (c.share_ok && a->share_waves == 4 && c.dma16 &&
-            a->tune[5] != 9 && a->x_row_stride >= 0 &&
-            a->x_row_stride < (int64_t(1) << 29)) {
+        if (c.ring_ok && a->tune[5] != 9) {
             p.rows_per_wave = 1;
-            const int rc = shape_grid(p, ceil_div(a->n_groups, (int64_t)4),
-                                      n_lb * n_tb, a->tune[4] != 1, grid);
-            if (rc != REMAP_OK)
-                return rc;
-            if (a->tune[4] == 3)
-                p.xcd_map |= 2;
-            return launch_timeshare(a, p, c.fma, grid, stream);
+            const int64_t grid =
+                shape_grid(p, ceil_div(a->n_groups, (int64_t)4), n_lb * n_tb,
+                           a->tune[4] != 1, side);
+            // the ring: two buffers of 8 entries x (4 slices x 512 B); 2 x 4
+            // slots of a step's weights; slack
+            return launch(c.fma ? spmm_timeshare<true, 1>
+                                : spmm_timeshare<false, 1>,
+                          a, grid, kWave * 4,
+                          2u * (8u * 2048u + 4u * 512u) + 512u, stream, p,
+                          a->flags, a->group_meta, a->group_col, a->group_w,
+                          a->group_mask, a->group_rid, a->share_meta,
+                          a->share_col, a->share_mask, X64);
         }
         if (!c.small_offsets)
             return fail(REMAP_ERR_UNSUPPORTED,
                         "remap_apply_f64: batches further apart than 32-bit "
                         "offsets reach need the shared lists");
-        const int rc = shape_grid(
+        const int64_t grid = shape_grid(
             p, ceil_div(a->n_groups, (int64_t)wpb * p.rows_per_wave),
-            n_lb * n_tb, a->tune[4] != 1, grid);
-        if (rc != REMAP_OK)
-            return rc;
-        if (a->tune[4] == 3)
-            p.xcd_map |= 2;
-        return c.f32 ? launch_grouptime<float>(a, p, wpb, c.fma, grid, stream)
-                     : launch_grouptime<double>(a, p, wpb, c.fma, grid,
-                                                stream);
+            n_lb * n_tb, a->tune[4] != 1, side);
+        return with_x(a, c.f32, [&](auto X) {
+            typedef elem_t<decltype(X)> XT;
+            return launch(c.fma ? spmm_grouptime<XT, true, 8, 8, 4>
+                                : spmm_grouptime<XT, false, 8, 8, 4>,
+                          a, grid, kWave * wpb, 0, stream, p, a->flags,
+                          a->group_meta, a->group_col, a->group_w,
+                          a->group_mask, a->group_rid, a->group_frac, X);
+        });
     }
     // f32 rows are half as long: two K tiles per wave keep the bytes per
     // wave and row at 1 KiB (measured +7 % on config 3 with f32 fields).
@@ -1342,22 +1131,19 @@ int run_rowgroup(const remap_apply_args *a, const Call &c, KParams p,
         p.bpc != kBatchPerChunk && !lock &&
         a->group_rows == 4)
         unr = 16;
-    int64_t grid;
-    const int rc = shape_grid(
-        p, ceil_div(a->n_groups, (int64_t)wpb * gpw), k_chunks,
-        a->tune[4] != 1, grid);
-    if (rc != REMAP_OK)
-        return rc;
-    if (a->tune[4] == 3)   // the K-chunks of a row block side by side
-        p.xcd_map |= 2;
+    const int64_t grid =
+        shape_grid(p, ceil_div(a->n_groups, (int64_t)wpb * gpw), k_chunks,
+                   a->tune[4] != 1, side);
     // tune[5] = 26 / 28: the rolling form, 6 / 8 union entries in flight
     const int roll = a->tune[5] == 26 ? 6 : a->tune[5] == 28 ? 8 : 0;
-    return c.f32 ? launch_rowgroup<float>(a, p, tiles, unr, vec, wpb, c.fma,
-                                          grid, stream, false, 0,
-                                          cell_masks && vec == 2)
-                 : launch_rowgroup<double>(a, p, tiles, unr, vec, wpb, c.fma,
-                                           grid, stream, lock, roll,
-                                           cell_masks && vec == 2);
+    return with_x(a, c.f32, [&](auto X) {
+        return launch(pick_rowgroup<elem_t<decltype(X)>>(
+                          a, tiles, unr, vec, wpb, c.fma, lock, roll,
+                          cell_masks && vec == 2),
+                      a, grid, kWave * wpb, 0, stream, p, a->flags,
+                      a->group_meta, a->group_col, a->group_w, a->group_mask,
+                      a->group_rid, a->group_frac, X);
+    });
 }
 
 int run_patch(const remap_apply_args *a, const Call &c, KParams p,
@@ -1375,12 +1161,9 @@ int run_patch(const remap_apply_args *a, const Call &c, KParams p,
     // 16-byte pieces go by LDS-DMA, everything else through registers.
     const int wc = (!c.can_vec2 || c.K <= 64) ? 64 : a->patch_row_bytes / 8;
     const int row_bytes = wc * 8;
-    int64_t grid;
-    const int rc = shape_grid(p, a->n_patches,
-                              shape_tiles(p, a, c.K, wc, 1),
-                              a->tune[4] == 0 || a->tune[4] == 2, grid);
-    if (rc != REMAP_OK)
-        return rc;
+    const int64_t grid = shape_grid(p, a->n_patches,
+                                    shape_tiles(p, a, c.K, wc, 1),
+                                    a->tune[4] == 0 || a->tune[4] == 2);
     uint32_t lds_bytes = patch_lds_bytes(a->patch_umax, a->patch_emax,
                                          a->patch_rows, row_bytes);
     if (lds_bytes < 1024)
@@ -1398,49 +1181,23 @@ int run_patch(const remap_apply_args *a, const Call &c, KParams p,
     const int block = (wc == 64 && small_blocks && a->patch_rows <= 512)
                           ? 512
                           : kPatchBlock;
-    patch_fn pf = pick_patch(c.f32, a->mode, c.fma, wc, c.dma16, block);
-    REMAP_HIP_CHECK(diag_lds_throttle(a, reinterpret_cast<const void *>(pf),
-                                      lds_bytes));
-    if (lds_bytes > 64 * 1024)
-        REMAP_HIP_CHECK(hipFuncSetAttribute(
-            reinterpret_cast<const void *>(pf),
-            hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-    hipLaunchKernelGGL(pf, dim3(static_cast<uint32_t>(grid)),
-                       dim3(block), lds_bytes, stream, p, a->flags,
-                       a->patch_rowptr, a->patch_val, a->patch_lidx,
-                       a->patch_ptr, a->patch_ucol, a->row_order, a->frac_b,
-                       a->patch_rows, a->patch_umax, a->patch_emax,
-                       a->n_patches);
-    REMAP_HIP_CHECK(hipGetLastError());
-    return REMAP_OK;
-}
-
-int launch_plain(kernel_fn fn, const remap_apply_args *a, const KParams &p,
-                 int64_t grid, hipStream_t stream)
-{
-    uint32_t lds_bytes = 0;
-    REMAP_HIP_CHECK(diag_lds_throttle(a, reinterpret_cast<const void *>(fn),
-                                      lds_bytes));
-    hipLaunchKernelGGL(fn, dim3(static_cast<uint32_t>(grid)), dim3(kBlock),
-                       lds_bytes, stream, p, a->flags);
-    REMAP_HIP_CHECK(hipGetLastError());
-    return REMAP_OK;
+    return launch(pick_patch(c.f32, a->mode, c.fma, wc, c.dma16, block), a,
+                  grid, block, lds_bytes, stream, p, a->flags,
+                  a->patch_rowptr, a->patch_val, a->patch_lidx, a->patch_ptr,
+                  a->patch_ucol, a->row_order, a->frac_b, a->patch_rows,
+                  a->patch_umax, a->patch_emax, a->n_patches);
 }
 
 int run_rowlane(const remap_apply_args *a, const Call &c, const KParams &p,
                 hipStream_t stream)
 {
-    const int64_t grid = ceil_div(c.n_rows * c.K, kBlock);
-    if (grid <= 0 || grid > 0x7fffffffLL)
-        return fail(REMAP_ERR_UNSUPPORTED,
-                    "remap_apply_f64: grid of %lld blocks; split the rows",
-                    (long long)grid);
     int unr = a->tune[1];
     if (unr != 1 && unr != 4 && unr != 8)
         unr = 4;
-    return launch_plain(c.f32 ? pick_rowlane<float>(unr, a->mode, c.fma)
-                              : pick_rowlane<double>(unr, a->mode, c.fma),
-                        a, p, grid, stream);
+    return launch(c.f32 ? pick_rowlane<float>(unr, a->mode, c.fma)
+                        : pick_rowlane<double>(unr, a->mode, c.fma),
+                  a, ceil_div(c.n_rows * c.K, kBlock), kBlock, 0, stream, p,
+                  a->flags);
 }
 
 // family 4: lanes across rows, TT fields per lane
@@ -1454,14 +1211,11 @@ int run_rowcell(const remap_apply_args *a, const Call &c, KParams p,
     if (unr != 1 && unr != 2 && unr != 4)
         unr = 2;
     p.row_order = nullptr;   // lanes = consecutive rows: coalesced Y stores
-    int64_t grid;
-    const int rc = shape_grid(p, ceil_div(c.n_rows, kBlock),
-                              ceil_div(c.K, tt), a->tune[4] != 1, grid);
-    if (rc != REMAP_OK)
-        return rc;
-    return launch_plain(c.f32 ? pick_rowcell<float>(tt, unr, a->mode, c.fma)
-                              : pick_rowcell<double>(tt, unr, a->mode, c.fma),
-                        a, p, grid, stream);
+    const int64_t grid = shape_grid(p, ceil_div(c.n_rows, kBlock),
+                                    ceil_div(c.K, tt), a->tune[4] != 1);
+    return launch(c.f32 ? pick_rowcell<float>(tt, unr, a->mode, c.fma)
+                        : pick_rowcell<double>(tt, unr, a->mode, c.fma),
+                  a, grid, kBlock, 0, stream, p, a->flags);
 }
 
 // family 7: LDS-staged patches, lanes across rows, TT fields per lane.
@@ -1578,12 +1332,9 @@ int run_patchcell(const remap_apply_args *a, const Call &c, KParams p,
                     a->y_batch_stride % 2 == 0 && aligned(a->Y, 16) &&
                     a->tune[5] != 1;
     }
-    int64_t grid;
-    const int rc = shape_grid(p, a->n_patches,
-                              persistent ? groups : n_chunks,
-                              a->tune[4] != 1, grid);
-    if (rc != REMAP_OK)
-        return rc;
+    const int64_t grid = shape_grid(p, a->n_patches,
+                                    persistent ? groups : n_chunks,
+                                    a->tune[4] != 1);
     uint32_t lds_bytes =
         static_cast<uint32_t>(upitch) * tt * 8u *
             (persistent && !one_image ? 2u : 1u) +
@@ -1600,40 +1351,18 @@ int run_patchcell(const remap_apply_args *a, const Call &c, KParams p,
                      : pick_patchtime<double>(tt, a->mode, c.fma, block))
             : (c.f32 ? pick_patchcell<float>(tt, a->mode, c.fma, layout)
                      : pick_patchcell<double>(tt, a->mode, c.fma, layout));
-    if (lds_bytes > 64 * 1024)
-        REMAP_HIP_CHECK(hipFuncSetAttribute(
-            reinterpret_cast<const void *>(fn),
-            hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-    hipLaunchKernelGGL(fn, dim3(static_cast<uint32_t>(grid)),
-                       dim3(launch_block), lds_bytes, stream, p, a->flags,
-                       a->patch_rowptr,
-                       a->patch_val, a->patch_lidx,
-                       a->patch_ptr, a->patch_ucol, a->row_order, a->frac_b,
-                       a->patch_rows, upitch, a->n_patches,
-                       a->patch_ell_base);
-    REMAP_HIP_CHECK(hipGetLastError());
-    return REMAP_OK;
+    return launch(fn, a, grid, launch_block, lds_bytes, stream, p, a->flags,
+                  a->patch_rowptr, a->patch_val, a->patch_lidx, a->patch_ptr,
+                  a->patch_ucol, a->row_order, a->frac_b, a->patch_rows,
+                  upitch, a->n_patches, a->patch_ell_base);
 }
 
-typedef void (*strip_fn)(const KParams, const int32_t *, const int32_t *,
-                         const int32_t *, const int32_t *, const int64_t *,
-                         const char *, int32_t, int32_t, int32_t, int32_t,
-                         int32_t, int64_t);
-
 template <int DEPTH>
-strip_fn pick_strip_mode(int mode, bool fma)
+auto pick_strip(int mode, bool fma)
 {
-    switch (mode) {
-    case REMAP_MODE_RAW:
-        return fma ? spmm_strip<REMAP_MODE_RAW, true, DEPTH>
-                   : spmm_strip<REMAP_MODE_RAW, false, DEPTH>;
-    case REMAP_MODE_FRACB:
-        return fma ? spmm_strip<REMAP_MODE_FRACB, true, DEPTH>
-                   : spmm_strip<REMAP_MODE_FRACB, false, DEPTH>;
-    default:
-        return fma ? spmm_strip<REMAP_MODE_MASKED, true, DEPTH>
-                   : spmm_strip<REMAP_MODE_MASKED, false, DEPTH>;
-    }
+    return by_mode(mode, fma, [](auto m, auto f) {
+        return spmm_strip<m, f, DEPTH>;
+    });
 }
 
 // family 8: one workgroup per (strip segment, 64-column K-chunk), unit-major
@@ -1648,20 +1377,14 @@ int run_strip(const remap_apply_args *a, const Call &c, KParams p,
     const remap_strips *st = a->strips;
     const int64_t n_chunks = ceil_div(c.K, kStripRowBytes / 8);
     // unit-major work list: shape_grid's "chunks" are the slow index
-    int64_t grid;
-    const int rc = shape_grid(p, n_chunks, st->n_units, a->tune[4] != 1,
-                              grid);
-    if (rc != REMAP_OK)
-        return rc;
-    strip_fn fn;
-    switch (st->depth) {
-    case 1: fn = pick_strip_mode<1>(a->mode, c.fma); break;
-    case 2: fn = pick_strip_mode<2>(a->mode, c.fma); break;
-    case 3: fn = pick_strip_mode<3>(a->mode, c.fma); break;
-    case 4: fn = pick_strip_mode<4>(a->mode, c.fma); break;
-    case 5: fn = pick_strip_mode<5>(a->mode, c.fma); break;
-    default: fn = pick_strip_mode<6>(a->mode, c.fma); break;
-    }
+    const int64_t grid =
+        shape_grid(p, n_chunks, st->n_units, a->tune[4] != 1);
+    const auto fn = st->depth == 1   ? pick_strip<1>(a->mode, c.fma)
+                    : st->depth == 2 ? pick_strip<2>(a->mode, c.fma)
+                    : st->depth == 3 ? pick_strip<3>(a->mode, c.fma)
+                    : st->depth == 4 ? pick_strip<4>(a->mode, c.fma)
+                    : st->depth == 5 ? pick_strip<5>(a->mode, c.fma)
+                                     : pick_strip<6>(a->mode, c.fma);
     // + 256 bytes of slack: the compute waves read a row's records sixteen
     // at a time (lane l: record l % 16) whatever the row holds -- on the
     // last row of a block that fills its meta slot the look-ahead read runs
@@ -1670,41 +1393,24 @@ int run_strip(const remap_apply_args *a, const Call &c, KParams p,
     const uint32_t lds_bytes =
         static_cast<uint32_t>(st->ring_slots + 2) * kStripRowBytes +
         static_cast<uint32_t>(st->depth + 1) * st->meta_slot_bytes + 256;
-    if (lds_bytes > 64 * 1024)
-        REMAP_HIP_CHECK(hipFuncSetAttribute(
-            reinterpret_cast<const void *>(fn),
-            hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-    hipLaunchKernelGGL(fn, dim3(static_cast<uint32_t>(grid)),
-                       dim3((st->waves + st->depth) * kWave), lds_bytes,
-                       stream, p, st->unit_steps, st->arr_ptr, st->arr_src,
-                       st->arr_slot, st->meta_ptr,
-                       static_cast<const char *>(st->meta),
-                       st->steps_per_unit, st->rows_per_wave, st->ring_slots,
-                       st->meta_slot_bytes, st->waves, n_chunks);
-    REMAP_HIP_CHECK(hipGetLastError());
-    return REMAP_OK;
+    return launch(fn, a, grid, (st->waves + st->depth) * kWave, lds_bytes,
+                  stream, p, st->unit_steps, st->arr_ptr, st->arr_src,
+                  st->arr_slot, st->meta_ptr,
+                  static_cast<const char *>(st->meta), st->steps_per_unit,
+                  st->rows_per_wave, st->ring_slots, st->meta_slot_bytes,
+                  st->waves, n_chunks);
 }
 
-typedef void (*long_fn)(const KParams, const uint32_t, const int32_t);
-
 template <typename XT, int TT>
-long_fn pick_longrow_mode(int mode, bool fma)
+auto pick_longrow_mode(int mode, bool fma)
 {
-    switch (mode) {
-    case REMAP_MODE_RAW:
-        return fma ? spmm_longrow<XT, REMAP_MODE_RAW, true, TT>
-                   : spmm_longrow<XT, REMAP_MODE_RAW, false, TT>;
-    case REMAP_MODE_FRACB:
-        return fma ? spmm_longrow<XT, REMAP_MODE_FRACB, true, TT>
-                   : spmm_longrow<XT, REMAP_MODE_FRACB, false, TT>;
-    default:
-        return fma ? spmm_longrow<XT, REMAP_MODE_MASKED, true, TT>
-                   : spmm_longrow<XT, REMAP_MODE_MASKED, false, TT>;
-    }
+    return by_mode(mode, fma, [](auto m, auto f) {
+        return spmm_longrow<XT, m, f, TT>;
+    });
 }
 
 template <typename XT>
-long_fn pick_longrow(int tt, int mode, bool fma)
+auto pick_longrow(int tt, int mode, bool fma)
 {
     switch (tt) {
     case 1: return pick_longrow_mode<XT, 1>(mode, fma);
@@ -1747,39 +1453,20 @@ int run_longrow(const remap_apply_args *a, const Call &c, KParams p,
         return fail(REMAP_ERR_UNSUPPORTED,
                     "remap_apply_f64: rows of %lld entries do not fit the "
                     "long-row kernel's LDS image", (long long)a->A.max_row_nnz);
-    int64_t grid;
-    const int rc = shape_grid(p, c.n_rows, ceil_div(c.K, tt),
-                              a->tune[4] != 1, grid);
-    if (rc != REMAP_OK)
-        return rc;
-    const long_fn fn = c.f32 ? pick_longrow<float>(tt, a->mode, c.fma)
-                             : pick_longrow<double>(tt, a->mode, c.fma);
-    if (lds > 64 * 1024)
-        REMAP_HIP_CHECK(hipFuncSetAttribute(
-            reinterpret_cast<const void *>(fn),
-            hipFuncAttributeMaxDynamicSharedMemorySize,
-            static_cast<int>(lds)));
-    hipLaunchKernelGGL(fn, dim3(static_cast<uint32_t>(grid)), dim3(kWave),
-                       static_cast<uint32_t>(lds), stream, p, a->flags,
-                       static_cast<int32_t>(pitch));
-    REMAP_HIP_CHECK(hipGetLastError());
-    return REMAP_OK;
+    const int64_t grid =
+        shape_grid(p, c.n_rows, ceil_div(c.K, tt), a->tune[4] != 1);
+    return launch(c.f32 ? pick_longrow<float>(tt, a->mode, c.fma)
+                        : pick_longrow<double>(tt, a->mode, c.fma),
+                  a, grid, kWave, static_cast<uint32_t>(lds), stream, p,
+                  a->flags, static_cast<int32_t>(pitch));
 }
 
 template <typename XT>
 patch_fn pick_longwave(int mode, bool fma)
 {
-    switch (mode) {
-    case REMAP_MODE_RAW:
-        return fma ? spmm_longwave<XT, REMAP_MODE_RAW, true>
-                   : spmm_longwave<XT, REMAP_MODE_RAW, false>;
-    case REMAP_MODE_FRACB:
-        return fma ? spmm_longwave<XT, REMAP_MODE_FRACB, true>
-                   : spmm_longwave<XT, REMAP_MODE_FRACB, false>;
-    default:
-        return fma ? spmm_longwave<XT, REMAP_MODE_MASKED, true>
-                   : spmm_longwave<XT, REMAP_MODE_MASKED, false>;
-    }
+    return by_mode(mode, fma, [](auto m, auto f) {
+        return spmm_longwave<XT, m, f>;
+    });
 }
 
 int run_longwave(const remap_apply_args *a, const Call &c, KParams p,
@@ -1790,12 +1477,9 @@ int run_longwave(const remap_apply_args *a, const Call &c, KParams p,
                     "remap_apply_f64: the long-wave kernel needs a row-major "
                     "patch plan of at most %d rows per patch covering "
                     "[row_begin, row_end)", kPatchWaves);
-    int64_t grid;
-    const int rc = shape_grid(p, a->n_patches,
-                              shape_tiles(p, a, c.K, kWave, 1),
-                              a->tune[4] == 2, grid);
-    if (rc != REMAP_OK)
-        return rc;
+    const int64_t grid = shape_grid(p, a->n_patches,
+                                    shape_tiles(p, a, c.K, kWave, 1),
+                                    a->tune[4] == 2);
     // per wave: two windows of 8 cells, 512 bytes per cell, and the row's
     // records (a multiple of 16, + 16: the last batch is read whole)
     const int64_t epitch = (a->A.max_row_nnz + 15) / 16 * 16 + 16;
@@ -1808,39 +1492,13 @@ int run_longwave(const remap_apply_args *a, const Call &c, KParams p,
                     "fit the long-wave kernel's LDS image (A.max_row_nnz "
                     "must be given)", a->patch_rows,
                     (long long)a->A.max_row_nnz);
-    const uint32_t lds_bytes = static_cast<uint32_t>(lds_need);
-    const patch_fn fn = c.f32 ? pick_longwave<float>(a->mode, c.fma)
-                              : pick_longwave<double>(a->mode, c.fma);
-    if (lds_bytes > 64 * 1024)
-        REMAP_HIP_CHECK(hipFuncSetAttribute(
-            reinterpret_cast<const void *>(fn),
-            hipFuncAttributeMaxDynamicSharedMemorySize,
-            static_cast<int>(lds_bytes)));
-#ifdef REMAP_DIAG
-    // (experiment, diagnostic build: the long rows' launch without the AQL
-    // barrier bit -- hipExtAnyOrderLaunch -- so that it may overlap the short
-    // rows' launch in front of it; hip_ext.h says gfx9 ignores the flag)
-    if (getenv("REMAP_ANY_ORDER")) {
-        hipExtLaunchKernelGGL(
-            fn, dim3(static_cast<uint32_t>(grid)),
-            dim3(static_cast<uint32_t>(a->patch_rows) * kWave), lds_bytes,
-            stream, nullptr, nullptr, hipExtAnyOrderLaunch, p, a->flags,
-            a->patch_rowptr, a->patch_val, a->patch_lidx, a->patch_ptr,
-            a->patch_ucol, a->row_order, a->frac_b, a->patch_rows,
-            a->patch_umax, static_cast<int32_t>(epitch), a->n_patches);
-        REMAP_HIP_CHECK(hipGetLastError());
-        return REMAP_OK;
-    }
-#endif
-    hipLaunchKernelGGL(fn, dim3(static_cast<uint32_t>(grid)),
-                       dim3(static_cast<uint32_t>(a->patch_rows) * kWave),
-                       lds_bytes, stream, p, a->flags, a->patch_rowptr,
-                       a->patch_val, a->patch_lidx, a->patch_ptr,
-                       a->patch_ucol, a->row_order, a->frac_b, a->patch_rows,
-                       a->patch_umax, static_cast<int32_t>(epitch),
-                       a->n_patches);
-    REMAP_HIP_CHECK(hipGetLastError());
-    return REMAP_OK;
+    return launch(c.f32 ? pick_longwave<float>(a->mode, c.fma)
+                        : pick_longwave<double>(a->mode, c.fma),
+                  a, grid, static_cast<uint32_t>(a->patch_rows) * kWave,
+                  static_cast<uint32_t>(lds_need), stream, p, a->flags,
+                  a->patch_rowptr, a->patch_val, a->patch_lidx, a->patch_ptr,
+                  a->patch_ucol, a->row_order, a->frac_b, a->patch_rows,
+                  a->patch_umax, static_cast<int32_t>(epitch), a->n_patches);
 }
 
 // family 3: a sub-group of 8 (4 for rows of at most 4 entries: bilinear
@@ -1853,16 +1511,11 @@ int run_rowsub(const remap_apply_args *a, const Call &c, const KParams &p,
         sub = (a->A.max_row_nnz > 0 && a->A.max_row_nnz <= 4) ? 4 : 8;
     if (sub != 4 && sub != 8)
         return fail(REMAP_ERR_ARG, "remap_apply_f64: tune[1] = %d", sub);
-    const int64_t grid = ceil_div(c.n_rows, kBlock / sub);
-    if (grid <= 0 || grid > 0x7fffffffLL)
-        return fail(REMAP_ERR_UNSUPPORTED,
-                    "remap_apply_f64: grid of %lld blocks; split the rows",
-                    (long long)grid);
     const bool tree = (a->flags & REMAP_FLAG_TREE) != 0;
-    return launch_plain(
-        c.f32 ? pick_rowsub<float>(sub, tree, a->mode, c.fma)
-              : pick_rowsub<double>(sub, tree, a->mode, c.fma),
-        a, p, grid, stream);
+    return launch(c.f32 ? pick_rowsub<float>(sub, tree, a->mode, c.fma)
+                        : pick_rowsub<double>(sub, tree, a->mode, c.fma),
+                  a, ceil_div(c.n_rows, kBlock / sub), kBlock, 0, stream, p,
+                  a->flags);
 }
 
 // families 1 (vector-memory metadata) and 6 (scalar-cache metadata)
@@ -1905,22 +1558,22 @@ int run_rowwave(const remap_apply_args *a, const Call &c, KParams p,
     if (rpw < 1 || rpw > 1024)
         return fail(REMAP_ERR_ARG, "remap_apply_f64: tune[3] = %d", rpw);
     p.rows_per_wave = rpw;
-    int64_t grid;
-    const int rc = shape_grid(
+    const int64_t grid = shape_grid(
         p, ceil_div(c.n_rows, (int64_t)kWavesPerBlock * rpw),
         shape_tiles(p, a, c.K, kWave * vec, tiles),
-        a->tune[4] == 0 || a->tune[4] == 2, grid);
-    if (rc != REMAP_OK)
-        return rc;
+        a->tune[4] == 0 || a->tune[4] == 2);
     if (family == 6)
-        return c.f32 ? launch_rowscalar<float>(a, p, vec, tiles, c.fma, grid,
-                                               stream)
-                     : launch_rowscalar<double>(a, p, vec, tiles, c.fma,
-                                                grid, stream);
-    return launch_plain(
-        c.f32 ? pick_rowwave_shape<float>(vec, tiles, a->mode, c.fma)
-              : pick_rowwave_shape<double>(vec, tiles, a->mode, c.fma),
-        a, p, grid, stream);
+        return with_x(a, c.f32, [&](auto X) {
+            return launch(pick_rowscalar<elem_t<decltype(X)>>(
+                              vec, tiles, a->mode, c.fma),
+                          a, grid, kBlock, 0, stream, p, a->flags,
+                          a->A.rowptr, a->A.col, a->A.val, a->row_order,
+                          a->frac_b, X);
+        });
+    return launch(c.f32 ? pick_rowwave_shape<float>(vec, tiles, a->mode, c.fma)
+                        : pick_rowwave_shape<double>(vec, tiles, a->mode,
+                                                     c.fma),
+                  a, grid, kBlock, 0, stream, p, a->flags);
 }
 
 }  // namespace
