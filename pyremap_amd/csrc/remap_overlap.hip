@@ -43,9 +43,15 @@ namespace remap {
 namespace {
 
 // the largest nEdgesOnCell this build serves (MPAS meshes have at most 9 or
-// so); one clip by a half-plane adds at most one vertex: four lat-lon edges
+// so); one clip by a half-plane adds at most one vertex: four lat-lon edges.
+// Rounding can break that bound where mesh vertices lie on a lat-lon edge
+// (their signs alternate along it); a polygon that would outgrow kMaxOut is
+// an error (kErrClip), never truncated
 constexpr int kMaxEdges = REMAP_OVERLAP_MAX_EDGES;
 constexpr int kMaxOut = kMaxEdges + 4;
+// the status bit of that error, next to REMAP_OVERLAP_ERR_* (the bits stay
+// inside the library: callers see REMAP_ERR_UNSUPPORTED and the message)
+constexpr int kErrClip = 16;
 constexpr int kClipBlock = 64;
 constexpr int kPrepBlock = 64;
 // every vertex of a pair must be within acos(kMinCos) ~ 84 deg of the mesh
@@ -500,20 +506,29 @@ __global__ __launch_bounds__(kClipBlock) void clip_pairs(
         for (int k = 0; k < n; ++k) {
             const double ex = px[cur][k][lane], ey = py[cur][k][lane];
             const double se = dx * (ey - ay) - dy * (ex - ax);
-            if ((se >= 0.0) != (ss >= 0.0) && m < kMaxOut) {
-                const double t = ss / (ss - se);
-                px[nxt][m][lane] = sx + t * (ex - sx);
-                py[nxt][m][lane] = sy + t * (ey - sy);
+            if ((se >= 0.0) != (ss >= 0.0)) {
+                if (m < kMaxOut) {
+                    const double t = ss / (ss - se);
+                    px[nxt][m][lane] = sx + t * (ex - sx);
+                    py[nxt][m][lane] = sy + t * (ey - sy);
+                }
                 ++m;
             }
-            if (se >= 0.0 && m < kMaxOut) {
-                px[nxt][m][lane] = ex;
-                py[nxt][m][lane] = ey;
+            if (se >= 0.0) {
+                if (m < kMaxOut) {
+                    px[nxt][m][lane] = ex;
+                    py[nxt][m][lane] = ey;
+                }
                 ++m;
             }
             sx = ex;
             sy = ey;
             ss = se;
+        }
+        if (m > kMaxOut) {
+            atomicOr(status, kErrClip);
+            area[p] = 0.0;
+            return;
         }
         n = m;
         cur = nxt;
@@ -847,7 +862,7 @@ int overlap(const remap_overlap_geom *geom, int32_t dst_is_mesh,
     const int64_t n_entries = back[0];
     const int err = static_cast<int>(back[1] & 0xffffffff);
     if (err)
-        return fail(REMAP_ERR_UNSUPPORTED, "remap_overlap_latlon: %s%s%s%s",
+        return fail(REMAP_ERR_UNSUPPORTED, "remap_overlap_latlon: %s%s%s%s%s",
                     (err & REMAP_OVERLAP_ERR_EDGES)
                         ? "a cell has more edges than this build serves "
                           "(REMAP_OVERLAP_MAX_EDGES); "
@@ -859,6 +874,10 @@ int overlap(const remap_overlap_geom *geom, int32_t dst_is_mesh,
                     (err & REMAP_OVERLAP_ERR_HEMISPHERE)
                         ? "a candidate pair has a vertex outside the "
                           "tangent hemisphere of the mesh cell's centre; "
+                        : "",
+                    (err & kErrClip)
+                        ? "a clipped polygon outgrew its REMAP_OVERLAP_MAX_EDGES "
+                          "+ 4 vertices (mesh vertices on a lat-lon edge); "
                         : "",
                     (err & REMAP_OVERLAP_ERR_CAPACITY)
                         ? "more candidate pairs than n_pairs (a stale "

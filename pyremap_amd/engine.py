@@ -2100,11 +2100,14 @@ def overlap_latlon(vertices_on_cell, n_edges_on_cell, lat_vertex, lon_vertex,
         dst = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         src = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         A = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
-        mesh_area = torch.empty(n_cells, dtype=torch.float64, device=dev)
+        # (never empty: the C side wants every output pointer, even for a
+        # mesh without cells)
+        mesh_area = torch.empty(max(n_cells, 1), dtype=torch.float64,
+                                device=dev)
         grid_area = torch.empty(n_lat * n_lon, dtype=torch.float64,
                                 device=dev)
-        frac_b = torch.empty(n_cells if dst_is_mesh else n_lat * n_lon,
-                             dtype=torch.float64, device=dev)
+        n_dst = n_cells if dst_is_mesh else n_lat * n_lon
+        frac_b = torch.empty(max(n_dst, 1), dtype=torch.float64, device=dev)
         n_entries = ctypes.c_int64()
         if timing is not None:
             t0 = torch.cuda.Event(enable_timing=True)
@@ -2122,4 +2125,5 @@ def overlap_latlon(vertices_on_cell, n_edges_on_cell, lat_vertex, lon_vertex,
             timing['ms'] = t0.elapsed_time(t1)
         del ws
         m = n_entries.value
-    return dst[:m], src[:m], A[:m], frac_b, mesh_area, grid_area
+    return (dst[:m], src[:m], A[:m], frac_b[:n_dst], mesh_area[:n_cells],
+            grid_area)

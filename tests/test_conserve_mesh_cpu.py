@@ -90,9 +90,18 @@ def mesh_cells(path):
     """Counter-clockwise unit-vector polygons of an MPAS mesh's cells."""
     from pyremap_amd.io.netcdf import open_dataset
     ds = open_dataset(path)
-    voc = np.asarray(ds['verticesOnCell'].values) - 1
-    noc = np.asarray(ds['nEdgesOnCell'].values)
-    xyz = unit(ds['latVertex'].values, ds['lonVertex'].values)
+    return mesh_cells_from_arrays(ds['verticesOnCell'].values,
+                                  ds['nEdgesOnCell'].values,
+                                  ds['latVertex'].values,
+                                  ds['lonVertex'].values)
+
+
+def mesh_cells_from_arrays(voc, noc, lat_v, lon_v):
+    """The same from the mesh arrays (``verticesOnCell`` 1-based, radians);
+    a closing vertex equal to the first one is dropped like a repeat."""
+    voc = np.asarray(voc) - 1
+    noc = np.asarray(noc)
+    xyz = unit(lat_v, lon_v)
     return [ccw(xyz[voc[c, :noc[c]]]) for c in range(len(noc))]
 
 
@@ -185,6 +194,259 @@ def test_reference_tiles_the_sphere():
     lon = np.radians(np.linspace(0.0, 360.0, 25))
     total = sum(polygon_area(c) for c in grid_cells(lat, lon))
     assert abs(total - 4 * np.pi) < 1e-12
+
+
+def latlon_cell_area(s, n, dlon):
+    """Closed form of a lat-lon cell with great-circle edges between the
+    latitudes s < n, dlon wide: the triangle from the north pole to its
+    southern corners less the one to its northern corners."""
+    return _cap_triangle(s, dlon) - _cap_triangle(n, dlon)
+
+
+def test_latlon_cells_match_closed_form():
+    """Every row of coarse global grids (the polar rows are triangles, one
+    row straddles the equator) and of a fine polar cap."""
+    d = np.radians
+    for lat_e, lon_e in ((d(np.arange(-90.0, 90.1, 10.0)),
+                          d(np.arange(-180.0, 180.1, 10.0))),
+                         (d(np.arange(-90.0, 90.1, 15.0)),
+                          d(np.arange(0.0, 360.1, 15.0))),
+                         (d(np.arange(84.0, 90.01, 0.25)),
+                          d(np.arange(-1.0, 1.01, 0.25)))):
+        got = np.array([polygon_area(c) for c in grid_cells(lat_e, lon_e)])
+        want = np.array([latlon_cell_area(lat_e[j], lat_e[j + 1],
+                                          lon_e[i + 1] - lon_e[i])
+                         for j in range(len(lat_e) - 1)
+                         for i in range(len(lon_e) - 1)])
+        assert np.abs(got / want - 1.0).max() < 1e-12
+    # the lune of two meridians 10 deg apart: 2 dlon
+    lune = sum(latlon_cell_area(d(a), d(a + 10.0), d(10.0))
+               for a in range(-90, 90, 10))
+    assert abs(lune - 2 * d(10.0)) < 1e-14
+
+
+# ---------------------------------------------------------------------------
+# meshes built in memory (the cases of tests/test_gpu_overlap_edges.py)
+# ---------------------------------------------------------------------------
+
+def grid_arrays(lat_deg, lon_deg, regional=None):
+    """(lat corners, lon corners, lat slack) in radians of the lat-lon grid
+    with these corners (degrees), as build_weights passes them to the GPU."""
+    from pyremap_amd import LatLonGridDescriptor
+    from pyremap_amd.weights import latlon_corners
+    return latlon_corners(LatLonGridDescriptor.create(
+        np.asarray(lat_deg, np.float64), np.asarray(lon_deg, np.float64),
+        units='degrees', mesh_name='grid', regional=regional))
+
+
+def _latlon_of(p):
+    p = p / np.linalg.norm(p, axis=-1, keepdims=True)
+    return np.arcsin(np.clip(p[..., 2], -1.0, 1.0)), \
+        np.arctan2(p[..., 1], p[..., 0])
+
+
+def _on_arc(lat, lon, t):
+    """(lat, lon) of the points of the great-circle arcs from (lat[..., 0],
+    lon[..., 0]) to (lat[..., 1], lon[..., 1]) at the fractions t of the
+    chord; a pole stays exactly a pole."""
+    p = unit(lat, lon)
+    q = (1.0 - t) * p[..., 0, :] + t * p[..., 1, :]
+    la, lo = _latlon_of(q)
+    pole = np.abs(q[..., 2]) == np.linalg.norm(q, axis=-1)
+    la = np.where(pole, np.sign(q[..., 2]) * 0.5 * np.pi, la)
+    return la, lo
+
+
+def quad_mesh(lat_e, lon_e, n_edges=4):
+    """An MPAS-style mesh (verticesOnCell 1-based, nEdgesOnCell, latVertex,
+    lonVertex) whose cells are the cells of the lat-lon grid with these
+    ascending corners (radians), C order, counter-clockwise, corners shared
+    and given exactly the grid's values (the polar rows: two corners on the
+    pole).  n_edges=10 puts more vertices on the great-circle edges: the
+    thirds of the edges along parallels, the midpoints of the meridians."""
+    lat_e, lon_e = np.asarray(lat_e, np.float64), np.asarray(lon_e, np.float64)
+    nj, ni = len(lat_e) - 1, len(lon_e) - 1
+    la, lo = np.meshgrid(lat_e, lon_e, indexing='ij')
+    lat_v, lon_v = [la.reshape(-1)], [lo.reshape(-1)]
+    j, i = np.meshgrid(np.arange(nj), np.arange(ni), indexing='ij')
+    j, i = j.reshape(-1), i.reshape(-1)
+
+    def corner(jj, ii):
+        return jj * (ni + 1) + ii + 1
+    sw, se, ne, nw = corner(j, i), corner(j, i + 1), corner(j + 1, i + 1), \
+        corner(j + 1, i)
+    if n_edges == 4:
+        voc = np.stack([sw, se, ne, nw], axis=1)
+    elif n_edges == 10:
+        base = len(lat_v[0])
+        s, n, w, e = lat_e[j], lat_e[j + 1], lon_e[i], lon_e[i + 1]
+        # per cell: S 1/3, S 2/3, E 1/2, N 1/3, N 2/3 (from east), W 1/2
+        arcs = [((s, s), (w, e), 1 / 3), ((s, s), (w, e), 2 / 3),
+                ((s, n), (e, e), 0.5), ((n, n), (e, w), 1 / 3),
+                ((n, n), (e, w), 2 / 3), ((n, s), (w, w), 0.5)]
+        ids = []
+        for k, ((a, b), (c, d), t) in enumerate(arcs):
+            pla, plo = _on_arc(np.stack([a, b], -1), np.stack([c, d], -1), t)
+            lat_v.append(pla)
+            lon_v.append(plo)
+            ids.append(base + k * len(j) + np.arange(len(j)) + 1)
+        voc = np.stack([sw, ids[0], ids[1], se, ids[2], ne, ids[3], ids[4],
+                        nw, ids[5]], axis=1)
+    else:
+        raise ValueError('n_edges is 4 or 10')
+    return (voc.astype(np.int32), np.full(len(j), n_edges, np.int32),
+            np.concatenate(lat_v), np.concatenate(lon_v))
+
+
+def disc_mesh(lat0, lon0, radius, n=6):
+    """One cell: n vertices at ``radius`` (radians) around (lat0, lon0)."""
+    c = unit(lat0, lon0)
+    e1 = np.cross([0.0, 0.0, 1.0], c)
+    e1 /= np.linalg.norm(e1)
+    e2 = np.cross(c, e1)
+    ang = 2 * np.pi * np.arange(n) / n
+    p = np.cos(radius) * c + np.sin(radius) * (
+        np.cos(ang)[:, None] * e1 + np.sin(ang)[:, None] * e2)
+    lat, lon = _latlon_of(p)
+    return (np.arange(1, n + 1, dtype=np.int32)[None, :],
+            np.array([n], np.int32), lat, lon)
+
+
+MESH_VARIANTS = ('rotate', 'reverse', 'repeat', 'close', 'lon2pi', 'pad',
+                 'densify')
+
+
+def vary_mesh(kind, voc, noc, lat_v, lon_v, seed=0):
+    """The same cells written differently: every cell's vertex list rotated,
+    reversed (clockwise), with one vertex repeated, closed by a copy of its
+    first vertex; lonVertex +-2 pi; verticesOnCell padded to maxEdges = 10
+    with junk after nEdgesOnCell; great-circle midpoints inserted until
+    nEdgesOnCell = 10 (new vertices, one cell's own)."""
+    rng = np.random.default_rng(seed)
+    voc, noc = np.asarray(voc, np.int32), np.asarray(noc, np.int32)
+    lat_v, lon_v = np.asarray(lat_v, np.float64), np.asarray(lon_v, np.float64)
+    n_cells = len(noc)
+    rows = [list(voc[c, :noc[c]]) for c in range(n_cells)]
+    width = voc.shape[1]
+    if kind == 'rotate':
+        rows = [r[k:] + r[:k] for r, k in
+                zip(rows, rng.integers(0, 10, n_cells) % noc)]
+    elif kind == 'reverse':
+        rows = [r[::-1] for r in rows]
+    elif kind == 'repeat':
+        rows = [r[:k + 1] + r[k:] for r, k in
+                zip(rows, rng.integers(0, 10, n_cells) % noc)]
+        width += 1
+    elif kind == 'close':
+        rows = [r + r[:1] for r in rows]
+        width += 1
+    elif kind == 'lon2pi':
+        lon_v = lon_v + 2 * np.pi * rng.choice([-1.0, 1.0], len(lon_v))
+    elif kind == 'pad':
+        width = 10
+    elif kind == 'densify':
+        new_lat, new_lon = [lat_v], [lon_v]
+        n_v = len(lat_v)
+        for c, r in enumerate(rows):
+            k = 0
+            while len(r) < 10:
+                k %= len(r)
+                a, b = r[k], r[(k + 1) % len(r)]
+                la, lo = _on_arc(lat_v[[a - 1, b - 1]], lon_v[[a - 1, b - 1]],
+                                 0.5)
+                new_lat.append(np.atleast_1d(la))
+                new_lon.append(np.atleast_1d(lo))
+                n_v += 1
+                r = r[:k + 1] + [n_v] + r[k + 1:]
+                k += 2
+            rows[c] = r
+        lat_v, lon_v = np.concatenate(new_lat), np.concatenate(new_lon)
+        width = 10
+    else:
+        raise ValueError(kind)
+    out = rng.integers(-5, len(lat_v) + 100, (n_cells, width)).astype(np.int32)
+    if kind != 'pad':
+        out[:] = 0
+    for c, r in enumerate(rows):
+        out[c, :len(r)] = r
+    return out, np.array([len(r) for r in rows], np.int32), lat_v, lon_v
+
+
+def test_quad_mesh_is_the_grid():
+    d = np.radians
+    lat_e = d(np.arange(-90.0, 90.1, 30.0))
+    lon_e = d(np.arange(-180.0, 180.1, 45.0))
+    grid = grid_cells(lat_e, lon_e)
+    want = np.array([polygon_area(c) for c in grid])
+    for n_edges in (4, 10):
+        voc, noc, lat_v, lon_v = quad_mesh(lat_e, lon_e, n_edges)
+        assert voc.shape == (len(grid), n_edges) and np.all(noc == n_edges)
+        assert voc.min() >= 1 and voc.max() <= len(lat_v)
+        cells = mesh_cells_from_arrays(voc, noc, lat_v, lon_v)
+        got = np.array([polygon_area(c) for c in cells])
+        assert np.abs(got - want).max() < 1e-15
+        # the polar rows: the two pole corners are one vertex, exactly
+        polar = [len(c) for c in cells[:8] + cells[-8:]]
+        assert polar == [3 if n_edges == 4 else 7] * 16
+        # the added vertices lie on the cell's great-circle edges
+        for c in range(8, len(cells) - 8):
+            n = [np.cross(a, b) for a, b in
+                 zip(grid[c], np.roll(grid[c], -1, axis=0))]
+            dist = np.array([[abs(p @ m) / np.linalg.norm(m) for m in n]
+                             for p in cells[c]]).min(axis=1)
+            assert dist.max() < 1e-15
+            assert abs(polygon_area(clip(cells[c], grid[c])) - want[c]) \
+                < 1e-15
+
+
+def test_mesh_variants_keep_the_cells():
+    from pyremap_amd import synthetic
+    m = synthetic.icosahedral_mesh(3)
+    arrays = (m['verticesOnCell'], m['nEdgesOnCell'], m['latVertex'],
+              m['lonVertex'])
+    base = mesh_cells_from_arrays(*arrays)
+    want = np.array([polygon_area(c) for c in base])
+    box = grid_cells(np.radians([10.0, 40.0]), np.radians([20.0, 70.0]))[0]
+    cut = np.array([polygon_area(clip(c, box)) for c in base])
+    assert (cut > 0).sum() > 5
+    for kind in MESH_VARIANTS:
+        voc, noc, lat_v, lon_v = vary_mesh(kind, *arrays)
+        assert voc.shape[1] >= noc.max() and voc.shape[1] <= 10
+        assert len(noc) == len(base)
+        cells = mesh_cells_from_arrays(voc, noc, lat_v, lon_v)
+        got = np.array([polygon_area(c) for c in cells])
+        assert np.abs(got - want).max() < 1e-15, kind
+        got = np.array([polygon_area(clip(c, box)) for c in cells])
+        assert np.abs(got - cut).max() < 1e-15, kind
+        if kind == 'reverse':
+            raw = unit(lat_v, lon_v)[voc[0, :noc[0]] - 1]
+            assert polygon_area(raw) < 0
+        if kind in ('repeat', 'close'):
+            assert np.all(noc == arrays[1] + 1)
+        if kind == 'pad':
+            assert voc.shape[1] == 10
+            junk = np.concatenate([voc[c, noc[c]:] for c in range(len(noc))])
+            assert (junk < 1).any() and (junk > len(lat_v)).any()
+        if kind == 'densify':
+            assert np.all(noc == 10)
+            assert all(len(c) == 10 for c in cells)
+
+
+def test_bulge_keeps_a_cell_in_the_southern_row():
+    """30 deg wide columns: the great-circle edge between the corners at
+    60N bulges 0.85 deg north at mid-column, so a cell at 60.4N lies in the
+    southern row's cell only."""
+    lat_e, lon_e, slack = grid_arrays([30.0, 60.0, 90.0], [0.0, 30.0, 60.0])
+    want = np.arctan(np.tan(np.radians(60.0)) / np.cos(np.radians(15.0))) \
+        - np.radians(60.0)
+    assert 0.85 < np.degrees(want) < 0.86 and want <= slack < 0.02
+    cell = mesh_cells_from_arrays(*disc_mesh(np.radians(60.4),
+                                             np.radians(15.0),
+                                             np.radians(0.2)))[0]
+    grid = grid_cells(lat_e, lon_e)
+    a = polygon_area(cell)
+    assert abs(polygon_area(clip(cell, grid[0])) - a) < 1e-18
+    assert [polygon_area(clip(cell, g)) for g in grid[1:]] == [0.0] * 3
 
 
 def test_qu240_polygon_areas_match_area_cell():

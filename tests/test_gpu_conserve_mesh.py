@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from test_conserve_mesh_cpu import (QU240, FIXTURES, grid_cells, mesh_cells,
+                                    mesh_cells_from_arrays, polygon_area,
                                     reference_overlaps)
 
 pytestmark = pytest.mark.gpu
@@ -29,56 +30,111 @@ def _qu240():
     return MpasCellMeshDescriptor(QU240, mesh_name='oQU240')
 
 
+def reference(mesh_p, grid_p):
+    """The numpy clipper's overlaps (mesh cell, grid cell, A) and both sets
+    of polygon areas."""
+    ref = reference_overlaps(mesh_p, grid_p)
+    m_area = np.array([polygon_area(p) for p in mesh_p])
+    g_area = np.array([polygon_area(p) for p in grid_p])
+    return ref, m_area, g_area
+
+
+def wanted(ref, m_area, g_area, dst_is_mesh):
+    """{(dst, src): S} of the reference, 0-based, ESMF's destarea
+    normalisation."""
+    if dst_is_mesh:
+        return {(c, g): A / m_area[c] for c, g, A in ref}
+    return {(g, c): A / g_area[g] for c, g, A in ref}
+
+
+def check_map(row, col, S, frac_b, want, n_dst):
+    """A map (1-based row, col) against the reference ``want``: the same
+    entries >= 1e-13 both ways, |dS| <= 1e-13, frac_b within 1e-12, keys
+    sorted and unique.  Returns {(dst, src): S}, 0-based."""
+    assert len(frac_b) == n_dst
+    row, col = np.asarray(row, np.int64), np.asarray(col, np.int64)
+    got = {(r - 1, c - 1): s for r, c, s in zip(row, col, S)}
+    if len(row):
+        # 1-based, sorted by (row, col), no duplicates
+        assert row.min() >= 1 and col.min() >= 1
+        key = (row - 1) * (1 << 32) + (col - 1)
+        assert np.all(np.diff(key) > 0)
+    big_got = {k for k, s in got.items() if s >= 1e-13}
+    big_want = {k for k, s in want.items() if s >= 1e-13}
+    assert big_got <= set(want), sorted(big_got - set(want))[:5]
+    assert big_want <= set(got), sorted(big_want - set(got))[:5]
+    err = max((abs(got.get(k, 0.0) - want.get(k, 0.0))
+               for k in set(got) | set(want)), default=0.0)
+    assert err <= 1e-13, err
+    # frac_b from the same sums
+    sums = np.zeros(n_dst)
+    for (i, j), s in want.items():
+        sums[i] += s
+    assert np.abs(frac_b - np.minimum(sums, 1.0)).max(initial=0.0) <= 1e-12
+    empty = np.bincount(row - 1, minlength=n_dst) == 0
+    assert np.all(frac_b[empty] == 0.0)
+    return got
+
+
+def gpu_map(voc, noc, lat_v, lon_v, lat_e, lon_e, slack, dst_is_mesh):
+    """engine.overlap_latlon on mesh and grid arrays (numpy): the map as
+    conserve_mesh_latlon forms it, (row, col) 1-based, S = A / A_dst, and
+    frac_b."""
+    from pyremap_amd import engine
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    dst, src, A, frac_b, mesh_area, grid_area = engine.overlap_latlon(
+        dev(voc), dev(noc), dev(lat_v), dev(lon_v), dev(lat_e), dev(lon_e),
+        slack, dst_is_mesh=dst_is_mesh)
+    dst, src = dst.cpu().numpy(), src.cpu().numpy()
+    dst_area = (mesh_area if dst_is_mesh else grid_area).cpu().numpy()
+    return dst + 1, src + 1, A.cpu().numpy() / dst_area[dst], \
+        frac_b.cpu().numpy()
+
+
+def parity_arrays(voc, noc, lat_v, lon_v, lat_e, lon_e, slack, ref=None):
+    """Both directions of a mesh and a grid given as arrays against the
+    numpy clipper (``ref``: its ``reference()`` of these cells, when the
+    caller has it).  Returns the reference and the two maps as
+    {(dst, src): S}, the mesh as destination first."""
+    if ref is None:
+        ref = reference(mesh_cells_from_arrays(voc, noc, lat_v, lon_v),
+                        grid_cells(lat_e, lon_e))
+    n_grid = (len(lat_e) - 1) * (len(lon_e) - 1)
+    maps = []
+    for dst_is_mesh in (True, False):
+        row, col, S, frac_b = gpu_map(voc, noc, lat_v, lon_v, lat_e, lon_e,
+                                      slack, dst_is_mesh)
+        maps.append(check_map(row, col, S, frac_b,
+                              wanted(*ref, dst_is_mesh),
+                              len(noc) if dst_is_mesh else n_grid))
+    return ref, maps
+
+
 def _parity(grid):
     """Both directions of QU240 <-> ``grid`` against the numpy clipper."""
     from pyremap_amd.weights import build_weights, latlon_corners
     lat_e, lon_e, _ = latlon_corners(grid)
     mesh_p = mesh_cells(QU240)
     grid_p = grid_cells(lat_e, lon_e)
-    ref = reference_overlaps(mesh_p, grid_p)
-    assert len(ref) > 100
-    m_area = np.array([_area(p) for p in mesh_p])
-    g_area = np.array([_area(p) for p in grid_p])
+    ref = reference(mesh_p, grid_p)
+    assert len(ref[0]) > 100
     mesh = _qu240()
     for mesh_is_src in (True, False):
         if mesh_is_src:
             m = build_weights(mesh, grid, 'conserve')
-            want = {(g, c): A / g_area[g] for c, g, A in ref}
             n_dst = len(grid_p)
             assert list(m.src_grid_dims) == [len(mesh_p)]
             assert list(m.dst_grid_dims) == [len(lon_e) - 1, len(lat_e) - 1]
         else:
             m = build_weights(grid, mesh, 'conserve')
-            want = {(c, g): A / m_area[c] for c, g, A in ref}
             n_dst = len(mesh_p)
             assert list(m.dst_grid_dims) == [len(mesh_p)]
-        assert m.n_b == n_dst and len(m.frac_b) == n_dst
-        row, col = m.row.astype(np.int64), m.col.astype(np.int64)
-        # 1-based, sorted by (row, col), no duplicates
-        assert row.min() >= 1 and col.min() >= 1
-        key = (row - 1) * (1 << 32) + (col - 1)
-        assert np.all(np.diff(key) > 0)
-        got = {(r - 1, c - 1): s for r, c, s in zip(row, col, m.S)}
-        big_got = {k for k, s in got.items() if s >= 1e-13}
-        big_want = {k for k, s in want.items() if s >= 1e-13}
-        assert big_got <= set(want), sorted(big_got - set(want))[:5]
-        assert big_want <= set(got), sorted(big_want - set(got))[:5]
-        err = max(abs(got.get(k, 0.0) - want.get(k, 0.0))
-                  for k in set(got) | set(want))
-        assert err <= 1e-13, err
-        # frac_b from the same sums
-        sums = np.zeros(n_dst)
-        for (i, j), s in want.items():
-            sums[i] += s
-        assert np.abs(m.frac_b - np.minimum(sums, 1.0)).max() <= 1e-12
-        empty = np.bincount(row - 1, minlength=n_dst) == 0
-        assert np.all(m.frac_b[empty] == 0.0)
+        assert m.n_b == n_dst
+        check_map(m.row, m.col, m.S, m.frac_b,
+                  wanted(*ref, not mesh_is_src), n_dst)
     return m
-
-
-def _area(p):
-    from test_conserve_mesh_cpu import polygon_area
-    return polygon_area(p)
 
 
 def test_qu240_to_2deg_matches_reference_clipper():
@@ -200,7 +256,6 @@ def test_remapper_qu240_conserve_end_to_end(tmp_path):
     y = np.asarray(out.values)[0]
     assert y.shape == (90, 180)
     # areas: the polygons of both meshes (the kernel's own formula)
-    from test_conserve_mesh_cpu import polygon_area
     a_src = np.array([polygon_area(p) for p in mesh_cells(QU240)])
     lat_e, lon_e, _ = latlon_corners(grid)
     a_dst = np.array([polygon_area(p) for p in grid_cells(lat_e, lon_e)])
