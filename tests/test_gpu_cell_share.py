@@ -12,7 +12,7 @@ remap_numpy.py:262-266, 277-278.
 import numpy as np
 import pytest
 
-from helpers import assert_bitwise
+from helpers import assert_bitwise, check_sum_bound
 from test_gpu_group_forms import _check, _fields
 
 pytestmark = pytest.mark.gpu
@@ -142,6 +142,8 @@ def test_cell_share_fma_is_close(dev):
         ok = ~ref_mask
         np.testing.assert_allclose(y.cpu().numpy()[ok], ref[ok], rtol=1e-12,
                                    atol=1e-13)
+        check_sum_bound(csr, mm['frac_b'], x, y.cpu().numpy(), 'masked', 0.3,
+                        got_mask=mask.cpu().numpy(), what=tag)
 
 
 def _reference_tnl(csr, frac_b, f, thr):

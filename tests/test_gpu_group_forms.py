@@ -15,7 +15,7 @@ Reference arithmetic: remap_numpy.py:258-278.
 import numpy as np
 import pytest
 
-from helpers import assert_bitwise
+from helpers import assert_bitwise, check_sum_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -122,6 +122,8 @@ def test_cell_masks_fma_is_close(dev):
         assert np.array_equal(mask.cpu().numpy().astype(bool), ref_mask), tag
         ok = ~ref_mask
         np.testing.assert_allclose(got[ok], ref[ok], rtol=1e-12, atol=1e-13)
+        check_sum_bound(csr, mm['frac_b'], x, got, 'masked', 0.3,
+                        got_mask=mask.cpu().numpy(), what=tag)
 
 
 def test_scan_kinds_and_three_gated_launches(dev):

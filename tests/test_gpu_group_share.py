@@ -9,7 +9,7 @@ own entries in ascending column order, scipy's csr_matvecs).
 import numpy as np
 import pytest
 
-from helpers import assert_bitwise
+from helpers import assert_bitwise, check_sum_bound
 from test_gpu_group_forms import _check, _fields
 
 pytestmark = pytest.mark.gpu
@@ -199,6 +199,8 @@ def test_shared_form_long_lists_one_dimensional_and_fma(dev):
     ok = ~ref_mask
     np.testing.assert_allclose(y.cpu().numpy()[ok], ref[ok], rtol=1e-12,
                                atol=1e-13)
+    check_sum_bound(csr, mm['frac_b'], x, y.cpu().numpy(), 'fracb',
+                    what='shared form, FMA')
 
 
 def test_shared_form_layouts_and_what_it_declines(dev):

@@ -11,7 +11,7 @@ column-major entries.  Every value against the oracle, bit for bit.
 import numpy as np
 import pytest
 
-from helpers import assert_bitwise
+from helpers import assert_bitwise, check_sum_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -242,6 +242,8 @@ def test_wave_per_long_row_windows_through_lds(dev, which, rows, monkeypatch):
                               engine.MODE_FRACB, flags=engine.FLAG_FMA)
     np.testing.assert_allclose(got.cpu().numpy(), np.ma.filled(want, np.nan),
                                rtol=1e-12, atol=1e-13)
+    check_sum_bound(csr, frac_b, x, got.cpu().numpy().reshape(-1, 96),
+                    'fracb', what=f'{rows} rows FMA')
 
 
 def test_bench_pole_cap_map_at_full_size(dev, monkeypatch):

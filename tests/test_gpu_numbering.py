@@ -15,7 +15,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import assert_bitwise, golden_map
+from helpers import assert_bitwise, golden_map, oracle_threads
 
 pytestmark = pytest.mark.gpu
 
@@ -96,7 +96,7 @@ def test_config3_renumbered_every_row_bitwise(dev, locality):
             threshold=0.01)
         ref, ref_mask = oracle.remap_flat(csr, frac_b, x.cpu().numpy(),
                                           masked, 0.01,
-                                          nthreads=os.cpu_count() or 1)
+                                          nthreads=oracle_threads())
         ref[ref_mask] = np.nan
         assert_bitwise(y.cpu().numpy().reshape(m.n_b, K), ref,
                        f'config3 {locality} masked={masked}')

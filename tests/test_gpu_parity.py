@@ -14,7 +14,8 @@ import os
 import numpy as np
 import pytest
 
-from helpers import assert_bitwise, golden_cases, golden_files, golden_map
+from helpers import (assert_bitwise, check_sum_bound, golden_cases,
+                     golden_files, golden_map, oracle_threads)
 
 pytestmark = pytest.mark.gpu
 
@@ -325,6 +326,7 @@ def test_fma_flag_is_close_not_identical(problem, dev):
     got = y.cpu().numpy()
     scale = np.abs(ref).max()
     np.testing.assert_allclose(got, ref, rtol=1e-13, atol=1e-13 * scale)
+    check_sum_bound(p['csr'], p['frac_b'], x, got, 'raw', what='FMA raw')
     assert not np.array_equal(got, ref)
 
 
@@ -683,7 +685,7 @@ def test_config3_full_size_bitwise_and_properties(dev):
     csr = oracle.OracleCSR(rowptr, col, val, (m.n_b, m.n_a))
     frac_b = m.frac_b.cpu().numpy()
     ref, ref_mask = oracle.remap_flat(csr, frac_b, x.cpu().numpy(), False,
-                                      0.0, nthreads=os.cpu_count() or 1)
+                                      0.0, nthreads=oracle_threads())
     ref[ref_mask] = np.nan
     assert_bitwise(y.cpu().numpy().reshape(m.n_b, K), ref, 'config3 full')
     del ref
@@ -1255,7 +1257,7 @@ def test_full_size_every_value_bitwise(dev, name, mode):
     rowptr, col, val = plan.to_host_csr()
     csr = oracle.OracleCSR(rowptr, col, val, (m.n_b, m.n_a))
     frac_b = m.frac_b.cpu().numpy()
-    threads = os.cpu_count() or 1
+    threads = oracle_threads()
     step = 16
     for k0 in range(0, K, step):
         xs = x[:, k0:k0 + step].contiguous().cpu().numpy()
@@ -1509,6 +1511,8 @@ def test_tree_flag_is_close_not_identical(problem, dev):
     scale = np.abs(ref[ok]).max()
     assert np.abs(ys[engine.FLAG_TREE][ok] - ref[ok]).max() <= 1e-13 * scale
     assert np.array_equal(np.isnan(ys[engine.FLAG_TREE]), ref_mask)
+    check_sum_bound(p['csr'], p['frac_b'], x, ys[engine.FLAG_TREE], 'fracb',
+                    what='TREE')
     # long rows make the association visible
     assert not np.array_equal(ys[engine.FLAG_TREE][ok], ref[ok])
 

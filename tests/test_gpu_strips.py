@@ -7,7 +7,7 @@ stencils).  Every value against the oracle, bit for bit, through the C ABI.
 import numpy as np
 import pytest
 
-from helpers import assert_bitwise
+from helpers import assert_bitwise, check_sum_bound
 
 pytestmark = pytest.mark.gpu
 
@@ -91,6 +91,7 @@ def test_strip_kernel_fma_and_fallback(dev):
     assert np.array_equal(np.isnan(y), ref_mask)
     scale = np.abs(ref[ok]).max()
     assert np.abs(y[ok] - ref[ok]).max() <= 1e-13 * scale
+    check_sum_bound(csr, mm['frac_b'], x, y, 'fracb', what='strips FMA')
     # (Time, nCells, levels): several batches
     x3 = rng.standard_normal((3, m.n_a, 64))
     x3d = torch.from_numpy(x3).to(dev)
