@@ -875,7 +875,9 @@ enum {
     REMAP_OVERLAP_ERR_HEMISPHERE = 4, /* a pair's vertex within acos(0.1) of
                                          the horizon of the mesh cell's centre
                                          (the gnomonic projection's limit)     */
-    REMAP_OVERLAP_ERR_CAPACITY = 8    /* n_pairs differs from the count        */
+    REMAP_OVERLAP_ERR_CAPACITY = 8,   /* n_pairs differs from the count        */
+    REMAP_OVERLAP_ERR_CONVEX = 32     /* a clipper cell (mesh b of
+                                         remap_overlap_meshes) is not convex  */
 };
 
 typedef struct remap_overlap_geom {
@@ -926,6 +928,67 @@ int remap_overlap_latlon(const remap_overlap_geom *geom, int32_t dst_is_mesh,
                          int32_t *src_out, double *area_out,
                          double *frac_b_out, double *mesh_area_out,
                          double *grid_area_out, int64_t *n_entries_out,
+                         void *stream);
+
+/*
+ * ---------------------------------------------------------------------------
+ * Conservative overlaps between two MPAS cell meshes a and b (the same
+ * geometry, normalisation and sliver rule as remap_overlap_latlon).  Cells of
+ * b are found for each cell of a through a global uniform lat-lon raster of
+ * buckets sized to b; every candidate (a, b) pair is clipped once, a's
+ * polygon by b's (b's cells must be convex: REMAP_OVERLAP_ERR_CONVEX), so
+ * both directions (dst_is_b) give the same overlap list, transposed, with
+ * the same bits.
+ *
+ * remap_overlap_meshes_sizes() counts the candidate pairs and reads the
+ * count back (it synchronises `stream`, and allocates and frees device
+ * memory of one int32 per bucket).  remap_overlap_meshes() is then
+ * asynchronous on `stream` except for TWO host read-backs: the bucket key
+ * counts (and the cells' error bits) after the cell preparation, and the
+ * number of entries (and the remaining error bits) before the sort.  No
+ * floating-point atomics: two calls give bitwise-identical outputs.
+ * ---------------------------------------------------------------------------
+ */
+typedef struct remap_overlap_mesh {
+    int64_t n_cells;            /* nCells                                     */
+    int64_t n_vertices;         /* nVertices                                  */
+    int32_t max_edges;          /* maxEdges: the row stride of verticesOnCell */
+    int32_t reserved;           /* 0                                          */
+    const int32_t *vertices_on_cell; /* (device) n_cells x max_edges, 1-based */
+    const int32_t *n_edges_on_cell;  /* (device) n_cells                      */
+    const double *lat_vertex;   /* (device) n_vertices, radians               */
+    const double *lon_vertex;   /* (device) n_vertices, radians               */
+} remap_overlap_mesh;
+
+/*
+ *   counter (device) 4 x int64 of scratch;  n_pairs_out (host) candidate
+ *   pairs;  workspace_bytes_out (host) what remap_overlap_meshes() needs.
+ */
+REMAP_API
+int remap_overlap_meshes_sizes(const remap_overlap_mesh *a,
+                               const remap_overlap_mesh *b, int64_t *counter,
+                               int64_t *n_pairs_out,
+                               size_t *workspace_bytes_out, void *stream);
+
+/*
+ * The overlap areas A (steradians) of every (destination, source) pair with
+ * A > 1e-14 x area(destination cell), sorted by (dst, src), 0-based.  The
+ * destination is mesh b when dst_is_b != 0, mesh a otherwise.
+ *
+ *   dst_out, src_out, area_out (device) n_pairs capacity each, the first
+ *   *n_entries_out meaningful;  frac_b_out (device) one per destination
+ *   cell: min(sum of its entries / its area, 1), summed in entry order;
+ *   a_area_out (device) a->n_cells, b_area_out (device) b->n_cells: the
+ *   polygons' own areas;  n_entries_out (host) one int64.
+ */
+REMAP_API
+int remap_overlap_meshes(const remap_overlap_mesh *a,
+                         const remap_overlap_mesh *b, int32_t dst_is_b,
+                         int64_t n_pairs, void *workspace,
+                         size_t workspace_bytes, int32_t *dst_out,
+                         int32_t *src_out, double *area_out,
+                         double *frac_b_out, double *a_area_out,
+                         double *b_area_out, int64_t *n_entries_out,
                          void *stream);
 
 #ifdef __cplusplus

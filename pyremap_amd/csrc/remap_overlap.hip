@@ -30,6 +30,11 @@
 //                  order -> frac_b = min(sum / A_dst, 1)
 // The polygons being clipped live in per-lane LDS slots (runtime-indexed
 // private arrays would go to scratch on gfx950).
+//
+// Between two MPAS meshes (remap_overlap_meshes, further down) the same
+// cell preparation runs against a raster of lat-lon buckets, candidate pairs
+// come from the buckets the cells' boxes share, and clip_pairs_poly clips a
+// cell of one mesh by a (convex) cell of the other.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -412,6 +417,9 @@ __global__ __launch_bounds__(kBlock) void grid_area(Geom G, bool swap,
     area[g] = fabs(quad_area(grid_cell(G.lat_c, G.lon_c, G.n_lon, g, swap)));
 }
 
+// kBucketMajor: the keys grid cell << 32 | cell instead (a mesh's bucket
+// lists, remap_overlap_meshes)
+template <bool kBucketMajor>
 __global__ __launch_bounds__(kBlock) void fill_pairs(
     Geom G, const Box *__restrict__ boxes, const uint64_t *__restrict__ offs,
     int64_t capacity, uint64_t *__restrict__ keys, int32_t *__restrict__ status)
@@ -428,13 +436,14 @@ __global__ __launch_bounds__(kBlock) void fill_pairs(
     }
     if (c == G.n_cells - 1 && o + cnt != capacity)
         atomicOr(status, REMAP_OVERLAP_ERR_CAPACITY);
-    const uint64_t hi = static_cast<uint64_t>(c) << 32;
+    const uint64_t cc = static_cast<uint64_t>(c);
+    const uint64_t hi = cc << 32;
     for (int32_t r = b.r0; r <= b.r1; ++r) {
         const uint64_t base = static_cast<uint64_t>(r) * G.n_lon;
         for (int32_t i = b.a0; i <= b.a1; ++i)
-            keys[o++] = hi | (base + i);
+            keys[o++] = kBucketMajor ? (base + i) << 32 | cc : hi | (base + i);
         for (int32_t i = b.b0; i <= b.b1; ++i)
-            keys[o++] = hi | (base + i);
+            keys[o++] = kBucketMajor ? (base + i) << 32 | cc : hi | (base + i);
     }
 }
 
@@ -830,7 +839,7 @@ int overlap(const remap_overlap_geom *geom, int32_t dst_is_mesh,
             temp, tb, static_cast<const uint64_t *>(counts), offs,
             uint64_t(0), static_cast<size_t>(G.n_cells),
             rocprim::plus<uint64_t>(), stream)));
-        hipLaunchKernelGGL(fill_pairs, dim3(blocks(G.n_cells, kBlock)),
+        hipLaunchKernelGGL(fill_pairs<false>, dim3(blocks(G.n_cells, kBlock)),
                            dim3(kBlock), 0, stream, G, boxes, offs, n_pairs,
                            keys, status);
         REMAP_HIP_CHECK(hipGetLastError());
@@ -904,6 +913,870 @@ int overlap(const remap_overlap_geom *geom, int32_t dst_is_mesh,
     return REMAP_OK;
 }
 
+
+// ---------------------------------------------------------------------------
+// two MPAS meshes (remap_overlap_meshes): the cells of mesh a (subject)
+// clipped by those of mesh b (clipper), candidates through a global uniform
+// lat-lon raster of buckets sized to b
+//   bucket_edges   the raster's corners: n_lat rows of pi / n_lat, 2 n_lat
+//                  columns from 0 to 2 pi
+//   cell_prep      both meshes against the raster (lat_slack 0: buckets are
+//                  true lat-lon rectangles); boxes as bucket ranges
+//   cell_shape     one lane per cell: the angular radius of its polygon about
+//                  its centre; b's cells checked convex
+//   -- read-back: the bucket key counts and the cells' error bits --
+//   fill_pairs     b: bucket << 32 | b, radix sorted; bucket_starts: where
+//                  each bucket's cells begin; a: a << 32 | bucket
+//   pair_counts / scan / expand_pairs  (a, bucket) -> (a, b) for every b of
+//                  the bucket; radix sort; unique (a pair is found once per
+//                  bucket the two boxes share)
+//   clip_pairs_poly  one lane per unique pair: a's polygon by b's edges in
+//                  the gnomonic plane of a's centre
+//   flag / scan / scatter, radix sort, dst_sums as above, a in the "mesh"
+//   and b in the "grid" half of the keys (dst_is_b only re-keys)
+// ---------------------------------------------------------------------------
+
+// one clip by an edge of a convex clipper adds at most one vertex
+constexpr int kMaxOutPoly = 2 * kMaxEdges;
+// a clipper vertex may lie this far (x the cell's longest edge) on the wrong
+// side of another edge's great circle: collinear vertices, rounded
+constexpr double kConvexTol = 1e-9;
+// bucket rows of the raster: sqrt(n_b / 2), within these bounds
+constexpr int64_t kMinBucketRows = 2;
+constexpr int64_t kMaxBucketRows = 8192;
+constexpr uint64_t kLow = 0xffffffffull;
+
+// a prepared polygon in global memory (cell_xyz of one cell)
+struct CellRing {
+    const double *p;
+    __device__ V3 operator[](int k) const
+    {
+        return {p[3 * k], p[3 * k + 1], p[3 * k + 2]};
+    }
+};
+
+// every vertex on the left of every edge's great circle (counter-clockwise),
+// within kConvexTol of the longest edge
+template <class R>
+__device__ bool convex_cell(const R &v, int nv)
+{
+    double len = 0.0;
+    for (int k = 0; k < nv; ++k) {
+        const V3 d = sub(v[k + 1 < nv ? k + 1 : 0], v[k]);
+        len = fmax(len, sqrt(dot(d, d)));
+    }
+    for (int e = 0; e < nv; ++e) {
+        const int f = e + 1 < nv ? e + 1 : 0;
+        const V3 n = cross(v[e], v[f]);
+        const double lim = -kConvexTol * len * sqrt(dot(n, n));
+        for (int k = 0; k < nv; ++k)
+            if (k != e && k != f && dot(n, v[k]) < lim)
+                return false;
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(kBlock) void bucket_edges(
+    int64_t n_lat, int64_t n_lon, double *__restrict__ lat_c,
+    double *__restrict__ lon_c)
+{
+    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (k <= n_lat)
+        lat_c[k] = k == n_lat ? kHalfPi
+                              : -kHalfPi + kPi * static_cast<double>(k) /
+                                               static_cast<double>(n_lat);
+    if (k <= n_lon)
+        lon_c[k] = k == n_lon ? kTwoPi
+                              : kTwoPi * static_cast<double>(k) /
+                                    static_cast<double>(n_lon);
+}
+
+// the count-only pass of remap_overlap_meshes_sizes: mesh b adds its cells
+// to the buckets their boxes cover (hist), mesh a sums hist over its boxes
+__global__ __launch_bounds__(kPrepBlock) void mesh_count(
+    Geom G, bool is_b, uint32_t *__restrict__ hist,
+    unsigned long long *__restrict__ n_keys,
+    unsigned long long *__restrict__ n_cand, int32_t *__restrict__ status)
+{
+    __shared__ double sx[kMaxEdges][kPrepBlock], sy[kMaxEdges][kPrepBlock],
+        sz[kMaxEdges][kPrepBlock];
+    const int lane = threadIdx.x;
+    const int64_t c = (int64_t)blockIdx.x * kPrepBlock + lane;
+    if (c >= G.n_cells)
+        return;
+    const Ring xyz = {&sx[0][lane], &sy[0][lane], &sz[0][lane], kPrepBlock};
+    int nv;
+    V3 cc;
+    double area;
+    Box b;
+    const int err = prep_cell(G, c, xyz, &nv, &cc, &area, &b);
+    if (err) {
+        atomicOr(status, err);
+        return;
+    }
+    if (is_b && !convex_cell(xyz, nv))
+        atomicOr(status, REMAP_OVERLAP_ERR_CONVEX);
+    const int64_t cnt = box_count(b);
+    if (cnt)
+        atomicAdd(n_keys, static_cast<unsigned long long>(cnt));
+    unsigned long long s = 0;
+    for (int32_t r = b.r0; r <= b.r1 && cnt; ++r) {
+        const int64_t base = static_cast<int64_t>(r) * G.n_lon;
+        for (int half = 0; half < 2; ++half) {
+            const int32_t i0 = half ? b.b0 : b.a0, i1 = half ? b.b1 : b.a1;
+            for (int32_t i = i0; i <= i1; ++i) {
+                if (is_b)
+                    atomicAdd(&hist[base + i], 1u);
+                else
+                    s += hist[base + i];
+            }
+        }
+    }
+    if (s)
+        atomicAdd(n_cand, s);
+}
+
+// one lane per prepared cell: the radius of the cap about its centre that
+// holds its polygon; with `convex`, the convexity of a clipper cell
+__global__ __launch_bounds__(kBlock) void cell_shape(
+    int64_t n_cells, int32_t max_edges, bool convex,
+    const double *__restrict__ cell_xyz, const int32_t *__restrict__ cell_nv,
+    const double *__restrict__ cell_centre, double *__restrict__ radius,
+    int32_t *__restrict__ status)
+{
+    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= n_cells)
+        return;
+    const int nv = cell_nv[c];
+    const CellRing v = {cell_xyz + c * max_edges * 3};
+    const V3 cc = {cell_centre[c * 3], cell_centre[c * 3 + 1],
+                   cell_centre[c * 3 + 2]};
+    double r = 0.0;
+    for (int k = 0; k < nv; ++k) {
+        const V3 q = v[k];
+        const V3 x = cross(cc, q);
+        r = fmax(r, atan2(sqrt(dot(x, x)), dot(cc, q)));
+    }
+    radius[c] = r;
+    if (convex && nv >= 3 && !convex_cell(v, nv))
+        atomicOr(status, REMAP_OVERLAP_ERR_CONVEX);
+}
+
+__global__ void scan_total(int64_t n, const uint64_t *__restrict__ counts,
+                           const uint64_t *__restrict__ offs,
+                           int64_t *__restrict__ out)
+{
+    if (threadIdx.x == 0 && n > 0)
+        *out = static_cast<int64_t>(offs[n - 1] + counts[n - 1]);
+}
+
+// where the cells of bucket k begin in the sorted keys bucket << 32 | b
+// (k = n_buckets: the end)
+__global__ __launch_bounds__(kBlock) void bucket_starts(
+    int64_t n_buckets, int64_t n_keys, const uint64_t *__restrict__ keys,
+    uint32_t *__restrict__ start)
+{
+    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (k > n_buckets)
+        return;
+    const uint64_t want = static_cast<uint64_t>(k) << 32;
+    int64_t lo = 0, hi = n_keys;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (keys[mid] < want)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    start[k] = static_cast<uint32_t>(lo);
+}
+
+// the cells of b in the bucket of every key a << 32 | bucket
+__global__ __launch_bounds__(kBlock) void pair_counts(
+    int64_t n_keys, int64_t n_buckets, const uint64_t *__restrict__ keys,
+    const uint32_t *__restrict__ start, uint64_t *__restrict__ counts)
+{
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n_keys)
+        return;
+    const uint64_t k = keys[p] & kLow;
+    counts[p] = k < static_cast<uint64_t>(n_buckets) ? start[k + 1] - start[k]
+                                                     : 0;
+}
+
+__global__ __launch_bounds__(kBlock) void expand_pairs(
+    int64_t n_keys, int64_t n_buckets, const uint64_t *__restrict__ keys,
+    const uint64_t *__restrict__ counts, const uint64_t *__restrict__ offs,
+    const uint32_t *__restrict__ start, const uint64_t *__restrict__ bkeys,
+    int64_t capacity, uint64_t *__restrict__ pairs,
+    int32_t *__restrict__ status)
+{
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n_keys)
+        return;
+    const uint64_t key = keys[p];
+    const uint64_t k = key & kLow;
+    const int64_t cnt = static_cast<int64_t>(counts[p]);
+    int64_t o = static_cast<int64_t>(offs[p]);
+    if (o + cnt > capacity) {
+        atomicOr(status, REMAP_OVERLAP_ERR_CAPACITY);
+        return;
+    }
+    if (p == n_keys - 1 && o + cnt != capacity)
+        atomicOr(status, REMAP_OVERLAP_ERR_CAPACITY);
+    if (!cnt || k >= static_cast<uint64_t>(n_buckets))
+        return;
+    const uint64_t hi = key & ~kLow;
+    for (uint32_t i = start[k]; i < start[k + 1]; ++i)
+        pairs[o++] = hi | (bkeys[i] & kLow);
+}
+
+// one lane per unique candidate pair a << 32 | b: the area of a's polygon
+// clipped by b's (convex) in the gnomonic plane of a's centre; lanes past
+// the unique count (their keys ~0) write 0
+__global__ __launch_bounds__(kClipBlock) void clip_pairs_poly(
+    int64_t n_a, int32_t max_edges_a, int64_t n_b, int32_t max_edges_b,
+    int64_t n_pairs, const uint64_t *__restrict__ n_unique,
+    const uint64_t *__restrict__ keys, const double *__restrict__ xyz_a,
+    const int32_t *__restrict__ nv_a, const double *__restrict__ centre_a,
+    const double *__restrict__ radius_a, const double *__restrict__ xyz_b,
+    const int32_t *__restrict__ nv_b, const double *__restrict__ centre_b,
+    const double *__restrict__ radius_b, double *__restrict__ area,
+    int32_t *__restrict__ status)
+{
+    // the polygon being clipped, ping-pong: [buffer][vertex][lane]
+    __shared__ double px[2][kMaxOutPoly][kClipBlock];
+    __shared__ double py[2][kMaxOutPoly][kClipBlock];
+    const int lane = threadIdx.x;
+    const int64_t p = (int64_t)blockIdx.x * kClipBlock + lane;
+    if (p >= n_pairs)
+        return;
+    if (static_cast<uint64_t>(p) >= *n_unique) {
+        area[p] = 0.0;
+        return;
+    }
+    const uint64_t key = keys[p];
+    const int64_t a = static_cast<int64_t>(key >> 32);
+    const int64_t b = static_cast<int64_t>(key & kLow);
+    if (a >= n_a || b >= n_b) {
+        atomicOr(status, REMAP_OVERLAP_ERR_CAPACITY);
+        area[p] = 0.0;
+        return;
+    }
+    const V3 ca = {centre_a[a * 3], centre_a[a * 3 + 1], centre_a[a * 3 + 2]};
+    const V3 cb = {centre_b[b * 3], centre_b[b * 3 + 1], centre_b[b * 3 + 2]};
+    // the caps that hold the two polygons are apart: no overlap (and no
+    // projection of cells too far apart for it)
+    const V3 xc = cross(ca, cb);
+    if (atan2(sqrt(dot(xc, xc)), dot(ca, cb)) >
+        radius_a[a] + radius_b[b] + kBoxEps) {
+        area[p] = 0.0;
+        return;
+    }
+    // tangent-plane basis at a's centre
+    const V3 ref = fabs(ca.z) < 0.9 ? V3{0.0, 0.0, 1.0} : V3{1.0, 0.0, 0.0};
+    const V3 e1 = normalized(cross(ref, ca));
+    const V3 e2 = cross(ca, e1);
+    const int na = nv_a[a], nb = nv_b[b];
+    const double *vb = xyz_b + b * max_edges_b * 3;
+    bool bad = false;
+    for (int k = 0; k < kMaxEdges; ++k) {
+        if (k < na) {
+            const double *v = xyz_a + (a * max_edges_a + k) * 3;
+            const V3 q = {v[0], v[1], v[2]};
+            const double t = dot(q, ca);
+            bad |= !(t >= kMinCos);
+            px[0][k][lane] = dot(q, e1) / t;
+            py[0][k][lane] = dot(q, e2) / t;
+        }
+    }
+    for (int k = 0; k < nb; ++k) {
+        const V3 q = {vb[3 * k], vb[3 * k + 1], vb[3 * k + 2]};
+        bad |= !(dot(q, ca) >= kMinCos);
+    }
+    if (bad) {
+        atomicOr(status, REMAP_OVERLAP_ERR_HEMISPHERE);
+        area[p] = 0.0;
+        return;
+    }
+    auto project = [&](int k, double *x, double *y) {
+        const V3 q = {vb[3 * k], vb[3 * k + 1], vb[3 * k + 2]};
+        const double t = dot(q, ca);
+        *x = dot(q, e1) / t;
+        *y = dot(q, e2) / t;
+    };
+    double fx, fy;
+    project(0, &fx, &fy);
+    double ax = fx, ay = fy;
+    int n = na, cur = 0;
+    for (int e = 0; e < nb && n > 0; ++e) {
+        double bx = fx, by = fy;
+        if (e + 1 < nb)
+            project(e + 1, &bx, &by);
+        const double dx = bx - ax, dy = by - ay;
+        if (dx != 0.0 || dy != 0.0) {
+            const int nxt = cur ^ 1;
+            int m = 0;
+            double sx = px[cur][n - 1][lane], sy = py[cur][n - 1][lane];
+            double ss = dx * (sy - ay) - dy * (sx - ax);
+            for (int k = 0; k < n; ++k) {
+                const double ex = px[cur][k][lane], ey = py[cur][k][lane];
+                const double se = dx * (ey - ay) - dy * (ex - ax);
+                if ((se >= 0.0) != (ss >= 0.0)) {
+                    if (m < kMaxOutPoly) {
+                        const double t = ss / (ss - se);
+                        px[nxt][m][lane] = sx + t * (ex - sx);
+                        py[nxt][m][lane] = sy + t * (ey - sy);
+                    }
+                    ++m;
+                }
+                if (se >= 0.0) {
+                    if (m < kMaxOutPoly) {
+                        px[nxt][m][lane] = ex;
+                        py[nxt][m][lane] = ey;
+                    }
+                    ++m;
+                }
+                sx = ex;
+                sy = ey;
+                ss = se;
+            }
+            if (m > kMaxOutPoly) {
+                atomicOr(status, kErrClip);
+                area[p] = 0.0;
+                return;
+            }
+            n = m;
+            cur = nxt;
+        }
+        ax = bx;
+        ay = by;
+    }
+    // the fan of Van Oosterom-Strackee triangles straight from the plane:
+    // the unit vector of (x, y) is (c + x e1 + y e2) / r, r = sqrt(1 + x^2 +
+    // y^2), so det(a, b, c) and the dot products come from the small plane
+    // coordinates instead of differences of lifted unit vectors
+    double s = 0.0;
+    if (n >= 3) {
+        const double x0 = px[cur][0][lane], y0 = py[cur][0][lane];
+        const double r0 = sqrt(1.0 + x0 * x0 + y0 * y0);
+        double x1 = px[cur][1][lane], y1 = py[cur][1][lane];
+        double r1 = sqrt(1.0 + x1 * x1 + y1 * y1);
+        for (int k = 2; k < n; ++k) {
+            const double x2 = px[cur][k][lane], y2 = py[cur][k][lane];
+            const double r2 = sqrt(1.0 + x2 * x2 + y2 * y2);
+            const double num = ((x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0)) /
+                               (r0 * r1 * r2);
+            const double den = 1.0 + (1.0 + x0 * x1 + y0 * y1) / (r0 * r1) +
+                               (1.0 + x1 * x2 + y1 * y2) / (r1 * r2) +
+                               (1.0 + x2 * x0 + y2 * y0) / (r2 * r0);
+            s += 2.0 * atan2(num, den);
+            x1 = x2;
+            y1 = y2;
+            r1 = r2;
+        }
+    }
+    area[p] = s > 0.0 ? s : 0.0;
+}
+
+int check_mesh(const remap_overlap_mesh *m, const char *name, Geom *G)
+{
+    if (!m)
+        return fail(REMAP_ERR_ARG, "remap_overlap_meshes: NULL mesh %s",
+                    name);
+    if (m->n_cells < 0 || m->n_vertices < 0 || m->max_edges < 3)
+        return fail(REMAP_ERR_ARG, "remap_overlap_meshes: bad sizes of mesh %s",
+                    name);
+    if (m->max_edges > kMaxEdges)
+        return fail(REMAP_ERR_UNSUPPORTED,
+                    "remap_overlap_meshes: maxEdges %d of mesh %s exceeds the "
+                    "%d this build serves (REMAP_OVERLAP_MAX_EDGES)",
+                    m->max_edges, name, kMaxEdges);
+    if (m->n_cells >= (int64_t(1) << 31))
+        return fail(REMAP_ERR_UNSUPPORTED,
+                    "remap_overlap_meshes: mesh %s beyond 32-bit indices",
+                    name);
+    if (m->n_cells > 0 && (!m->vertices_on_cell || !m->n_edges_on_cell ||
+                           !m->lat_vertex || !m->lon_vertex))
+        return fail(REMAP_ERR_ARG, "remap_overlap_meshes: NULL array of mesh %s",
+                    name);
+    *G = {m->n_cells, m->n_vertices, 0, 0, m->max_edges, 0.0,
+          m->vertices_on_cell, m->n_edges_on_cell, m->lat_vertex,
+          m->lon_vertex, nullptr, nullptr};
+    return REMAP_OK;
+}
+
+// the bucket raster of mesh b: about one of its cells per bucket
+void bucket_raster(int64_t n_b, Geom *A, Geom *B)
+{
+    int64_t n_lat = static_cast<int64_t>(sqrt(0.5 * static_cast<double>(n_b)) + 0.5);
+    n_lat = n_lat < kMinBucketRows ? kMinBucketRows
+                                   : (n_lat > kMaxBucketRows ? kMaxBucketRows : n_lat);
+    A->n_lat = B->n_lat = n_lat;
+    A->n_lon = B->n_lon = 2 * n_lat;
+}
+
+// the error bits of one mesh, or of the pairs (name NULL), as text
+void describe(const char *name, int err, char *out, size_t size)
+{
+    out[0] = '\0';
+    if (!err)
+        return;
+    snprintf(out, size, "%s%s%s%s%s%s%s%s", name ? "mesh " : "",
+             name ? name : "", name ? ": " : "",
+             (err & REMAP_OVERLAP_ERR_EDGES)
+                 ? "a cell has more edges than this build serves "
+                   "(REMAP_OVERLAP_MAX_EDGES); "
+                 : "",
+             (err & REMAP_OVERLAP_ERR_VERTEX)
+                 ? "a cell has fewer than 3 distinct vertices or a vertex "
+                   "index out of range; "
+                 : "",
+             (err & REMAP_OVERLAP_ERR_CONVEX)
+                 ? "a cell is not convex (mesh b's cells clip); "
+                 : "",
+             (err & REMAP_OVERLAP_ERR_HEMISPHERE)
+                 ? "a candidate pair has a vertex outside the tangent "
+                   "hemisphere of the mesh a cell's centre; "
+                 : "",
+             (err & kErrClip)
+                 ? "a clipped polygon outgrew its 2 x REMAP_OVERLAP_MAX_EDGES "
+                   "vertices; "
+                 : "");
+    if (err & REMAP_OVERLAP_ERR_CAPACITY) {
+        const size_t n = strlen(out);
+        snprintf(out + n, size - n, "the candidate pairs differ from n_pairs "
+                                    "(a stale remap_overlap_meshes_sizes); ");
+    }
+}
+
+int meshes_fail(int err_a, int err_b, int err_p)
+{
+    char text[3][192];
+    describe("a", err_a, text[0], sizeof(text[0]));
+    describe("b", err_b, text[1], sizeof(text[1]));
+    describe(nullptr, err_p, text[2], sizeof(text[2]));
+    return fail(REMAP_ERR_UNSUPPORTED, "remap_overlap_meshes: %s%s%s", text[0],
+                text[1], text[2]);
+}
+
+// one mesh's prepared cells in the workspace
+struct SideLayout {
+    size_t xyz, nv, centre, radius, boxes, counts, offs;
+};
+
+struct MeshLayout {
+    // known from the sizes of the meshes
+    size_t lat_c, lon_c, start, back, temp0, fixed;
+    SideLayout a, b;
+    size_t temp0_bytes;
+    // known from the bucket key counts (the first read-back)
+    size_t bkeys, bkeys_s, akeys, pcnt, poff, cand, cand_s, parea, area_c,
+        head, slot, temp, total;
+    size_t temp_bytes;
+};
+
+// the read-back words: [0] b's keys, [1] a's keys, [2] the error bits of a
+// (low half) and b (high half), [3] unique pairs, [4] entries, [5] the
+// pairs' error bits
+constexpr int kBackWords = 6;
+
+size_t take(size_t *off, size_t bytes)
+{
+    const size_t at = *off;
+    *off += align_up(bytes);
+    return at;
+}
+
+SideLayout side_layout(const Geom &G, size_t *off)
+{
+    const size_t c = static_cast<size_t>(G.n_cells > 0 ? G.n_cells : 1);
+    SideLayout s;
+    s.xyz = take(off, c * G.max_edges * 3 * 8);
+    s.nv = take(off, c * 4);
+    s.centre = take(off, c * 3 * 8);
+    s.radius = take(off, c * 8);
+    s.boxes = take(off, c * sizeof(Box));
+    s.counts = take(off, c * 8);
+    s.offs = take(off, c * 8);
+    return s;
+}
+
+int mesh_fixed_layout(const Geom &A, const Geom &B, MeshLayout *L)
+{
+    const size_t nc = static_cast<size_t>(
+        (A.n_cells > B.n_cells ? A.n_cells : B.n_cells) > 0
+            ? (A.n_cells > B.n_cells ? A.n_cells : B.n_cells)
+            : 1);
+    REMAP_HIP_CHECK((rocprim::exclusive_scan(
+        nullptr, L->temp0_bytes, static_cast<const uint64_t *>(nullptr),
+        static_cast<uint64_t *>(nullptr), uint64_t(0), nc,
+        rocprim::plus<uint64_t>())));
+    const size_t n_buckets = static_cast<size_t>(A.n_lat * A.n_lon);
+    size_t off = 0;
+    L->lat_c = take(&off, (A.n_lat + 1) * 8);
+    L->lon_c = take(&off, (A.n_lon + 1) * 8);
+    L->start = take(&off, (n_buckets + 1) * 4);
+    L->back = take(&off, kBackWords * 8);
+    L->a = side_layout(A, &off);
+    L->b = side_layout(B, &off);
+    L->temp0 = take(&off, L->temp0_bytes);
+    L->fixed = off;
+    return REMAP_OK;
+}
+
+int mesh_var_layout(int64_t n_akeys, int64_t n_bkeys, int64_t n_pairs,
+                    MeshLayout *L)
+{
+    const size_t na = static_cast<size_t>(n_akeys > 0 ? n_akeys : 1);
+    const size_t nb = static_cast<size_t>(n_bkeys > 0 ? n_bkeys : 1);
+    const size_t n = static_cast<size_t>(n_pairs > 0 ? n_pairs : 1);
+    size_t t[6];
+    REMAP_HIP_CHECK((rocprim::radix_sort_keys(
+        nullptr, t[0], static_cast<const uint64_t *>(nullptr),
+        static_cast<uint64_t *>(nullptr), nb, 0u, 64u)));
+    REMAP_HIP_CHECK((rocprim::exclusive_scan(
+        nullptr, t[1], static_cast<const uint64_t *>(nullptr),
+        static_cast<uint64_t *>(nullptr), uint64_t(0), na,
+        rocprim::plus<uint64_t>())));
+    REMAP_HIP_CHECK((rocprim::radix_sort_keys(
+        nullptr, t[2], static_cast<const uint64_t *>(nullptr),
+        static_cast<uint64_t *>(nullptr), n, 0u, 64u)));
+    REMAP_HIP_CHECK((rocprim::unique(
+        nullptr, t[3], static_cast<const uint64_t *>(nullptr),
+        static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr),
+        n)));
+    REMAP_HIP_CHECK((rocprim::exclusive_scan(
+        nullptr, t[4], static_cast<const uint32_t *>(nullptr),
+        static_cast<uint32_t *>(nullptr), 0u, n, rocprim::plus<uint32_t>())));
+    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
+        nullptr, t[5], static_cast<const uint64_t *>(nullptr),
+        static_cast<uint64_t *>(nullptr), static_cast<const double *>(nullptr),
+        static_cast<double *>(nullptr), n, 0u, 64u)));
+    L->temp_bytes = 0;
+    for (size_t b : t)
+        L->temp_bytes = b > L->temp_bytes ? b : L->temp_bytes;
+    size_t off = L->fixed;
+    L->bkeys = take(&off, nb * 8);
+    L->bkeys_s = take(&off, nb * 8);
+    L->akeys = take(&off, na * 8);
+    L->pcnt = take(&off, na * 8);
+    L->poff = take(&off, na * 8);
+    // candidates; then the unique pairs; then the sorted entry keys
+    L->cand = take(&off, n * 8);
+    // sorted candidates; then the kept entries' keys
+    L->cand_s = take(&off, n * 8);
+    L->parea = take(&off, n * 8);
+    L->area_c = take(&off, n * 8);
+    L->head = take(&off, n * 4);
+    L->slot = take(&off, n * 4);
+    L->temp = take(&off, L->temp_bytes);
+    L->total = off;
+    return REMAP_OK;
+}
+
+int meshes_sizes(const remap_overlap_mesh *mesh_a,
+                 const remap_overlap_mesh *mesh_b, int64_t *counter,
+                 int64_t *n_pairs_out, size_t *bytes_out, hipStream_t stream)
+{
+    Geom A, B;
+    int rc = check_mesh(mesh_a, "a", &A);
+    if (rc == REMAP_OK)
+        rc = check_mesh(mesh_b, "b", &B);
+    if (rc != REMAP_OK)
+        return rc;
+    if (!counter || !n_pairs_out || !bytes_out)
+        return fail(REMAP_ERR_ARG, "remap_overlap_meshes_sizes: NULL output");
+    bucket_raster(B.n_cells, &A, &B);
+    const int64_t n_buckets = A.n_lat * A.n_lon;
+    // the histogram of b's cells over the buckets, and the raster
+    const size_t hist_bytes = align_up(n_buckets * 4);
+    const size_t bytes = hist_bytes + align_up((A.n_lat + 1) * 8) +
+                         align_up((A.n_lon + 1) * 8);
+    char *buf = nullptr;
+    REMAP_HIP_CHECK(hipMalloc(&buf, bytes));
+    uint32_t *hist = reinterpret_cast<uint32_t *>(buf);
+    double *lat_c = reinterpret_cast<double *>(buf + hist_bytes);
+    double *lon_c = lat_c + align_up((A.n_lat + 1) * 8) / 8;
+    A.lat_c = B.lat_c = lat_c;
+    A.lon_c = B.lon_c = lon_c;
+    int64_t got[4];
+    hipError_t err = hipMemsetAsync(counter, 0, 4 * sizeof(int64_t), stream);
+    if (err == hipSuccess)
+        err = hipMemsetAsync(hist, 0, n_buckets * 4, stream);
+    if (err == hipSuccess) {
+        hipLaunchKernelGGL(bucket_edges, dim3(blocks(A.n_lon + 1, kBlock)),
+                           dim3(kBlock), 0, stream, A.n_lat, A.n_lon, lat_c,
+                           lon_c);
+        unsigned long long *cnt = reinterpret_cast<unsigned long long *>(counter);
+        int32_t *status = reinterpret_cast<int32_t *>(counter + 3);
+        if (B.n_cells > 0)
+            hipLaunchKernelGGL(mesh_count, dim3(blocks(B.n_cells, kPrepBlock)),
+                               dim3(kPrepBlock), 0, stream, B, true, hist,
+                               cnt + 2, cnt, status + 1);
+        if (A.n_cells > 0)
+            hipLaunchKernelGGL(mesh_count, dim3(blocks(A.n_cells, kPrepBlock)),
+                               dim3(kPrepBlock), 0, stream, A, false, hist,
+                               cnt + 1, cnt, status);
+        err = hipGetLastError();
+    }
+    if (err == hipSuccess)
+        err = hipMemcpyAsync(got, counter, sizeof(got), hipMemcpyDeviceToHost,
+                             stream);
+    if (err == hipSuccess)
+        err = hipStreamSynchronize(stream);
+    const hipError_t freed = hipFree(buf);
+    REMAP_HIP_CHECK(err);
+    REMAP_HIP_CHECK(freed);
+    const int err_a = static_cast<int>(got[3] & 0xffffffff);
+    const int err_b = static_cast<int>((got[3] >> 32) & 0xffffffff);
+    if (err_a || err_b)
+        return meshes_fail(err_a, err_b, 0);
+    MeshLayout lay;
+    rc = mesh_fixed_layout(A, B, &lay);
+    if (rc == REMAP_OK)
+        rc = mesh_var_layout(got[1], got[2], got[0], &lay);
+    if (rc != REMAP_OK)
+        return rc;
+    *n_pairs_out = got[0];
+    *bytes_out = lay.total;
+    return REMAP_OK;
+}
+
+struct Side {
+    double *xyz, *centre, *radius;
+    int32_t *nv;
+    Box *boxes;
+    uint64_t *counts, *offs;
+};
+
+Side side_at(char *ws, const SideLayout &s)
+{
+    return {reinterpret_cast<double *>(ws + s.xyz),
+            reinterpret_cast<double *>(ws + s.centre),
+            reinterpret_cast<double *>(ws + s.radius),
+            reinterpret_cast<int32_t *>(ws + s.nv),
+            reinterpret_cast<Box *>(ws + s.boxes),
+            reinterpret_cast<uint64_t *>(ws + s.counts),
+            reinterpret_cast<uint64_t *>(ws + s.offs)};
+}
+
+// cell_prep, cell_shape, the scan of the bucket counts and its total
+int prep_side(const Geom &G, bool clipper, const Side &s, double *area,
+              void *temp, size_t temp_bytes, int64_t *total, int32_t *status,
+              hipStream_t stream)
+{
+    if (G.n_cells <= 0)
+        return REMAP_OK;
+    hipLaunchKernelGGL(cell_prep, dim3(blocks(G.n_cells, kPrepBlock)),
+                       dim3(kPrepBlock), 0, stream, G, s.xyz, s.nv, s.centre,
+                       area, s.boxes, s.counts, nullptr, status);
+    REMAP_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(cell_shape, dim3(blocks(G.n_cells, kBlock)),
+                       dim3(kBlock), 0, stream, G.n_cells, G.max_edges,
+                       clipper, s.xyz, s.nv, s.centre, s.radius, status);
+    REMAP_HIP_CHECK(hipGetLastError());
+    size_t tb = temp_bytes;
+    REMAP_HIP_CHECK((rocprim::exclusive_scan(
+        temp, tb, static_cast<const uint64_t *>(s.counts), s.offs,
+        uint64_t(0), static_cast<size_t>(G.n_cells),
+        rocprim::plus<uint64_t>(), stream)));
+    hipLaunchKernelGGL(scan_total, dim3(1), dim3(kWave), 0, stream, G.n_cells,
+                       s.counts, s.offs, total);
+    REMAP_HIP_CHECK(hipGetLastError());
+    return REMAP_OK;
+}
+
+int meshes(const remap_overlap_mesh *mesh_a, const remap_overlap_mesh *mesh_b,
+           int32_t dst_is_b, int64_t n_pairs, void *workspace,
+           size_t workspace_bytes, int32_t *dst_out, int32_t *src_out,
+           double *area_out, double *frac_b_out, double *a_area_out,
+           double *b_area_out, int64_t *n_entries_out, hipStream_t stream)
+{
+    Geom A, B;
+    int rc = check_mesh(mesh_a, "a", &A);
+    if (rc == REMAP_OK)
+        rc = check_mesh(mesh_b, "b", &B);
+    if (rc != REMAP_OK)
+        return rc;
+    if (n_pairs < 0 || n_pairs >= (int64_t(1) << 32) - 1)
+        return fail(REMAP_ERR_UNSUPPORTED,
+                    "remap_overlap_meshes: %lld candidate pairs",
+                    static_cast<long long>(n_pairs));
+    if (!frac_b_out || !a_area_out || !b_area_out || !n_entries_out ||
+        (n_pairs > 0 && (!dst_out || !src_out || !area_out)))
+        return fail(REMAP_ERR_ARG, "remap_overlap_meshes: NULL output");
+    bucket_raster(B.n_cells, &A, &B);
+    const int64_t n_buckets = A.n_lat * A.n_lon;
+    MeshLayout lay;
+    rc = mesh_fixed_layout(A, B, &lay);
+    if (rc != REMAP_OK)
+        return rc;
+    if (!workspace || workspace_bytes < lay.fixed)
+        return fail(REMAP_ERR_WORKSPACE,
+                    "remap_overlap_meshes: workspace of %zu bytes, need at "
+                    "least %zu",
+                    workspace_bytes, lay.fixed);
+    char *ws = static_cast<char *>(workspace);
+    double *lat_c = reinterpret_cast<double *>(ws + lay.lat_c);
+    double *lon_c = reinterpret_cast<double *>(ws + lay.lon_c);
+    uint32_t *start = reinterpret_cast<uint32_t *>(ws + lay.start);
+    int64_t *back = reinterpret_cast<int64_t *>(ws + lay.back);
+    int32_t *status_ab = reinterpret_cast<int32_t *>(back + 2);
+    int32_t *status = reinterpret_cast<int32_t *>(back + 5);
+    const Side sa = side_at(ws, lay.a), sb = side_at(ws, lay.b);
+    A.lat_c = B.lat_c = lat_c;
+    A.lon_c = B.lon_c = lon_c;
+
+    REMAP_HIP_CHECK(hipMemsetAsync(back, 0, kBackWords * 8, stream));
+    hipLaunchKernelGGL(bucket_edges, dim3(blocks(A.n_lon + 1, kBlock)),
+                       dim3(kBlock), 0, stream, A.n_lat, A.n_lon, lat_c,
+                       lon_c);
+    REMAP_HIP_CHECK(hipGetLastError());
+    void *temp0 = ws + lay.temp0;
+    rc = prep_side(B, true, sb, b_area_out, temp0, lay.temp0_bytes, back,
+                   status_ab + 1, stream);
+    if (rc == REMAP_OK)
+        rc = prep_side(A, false, sa, a_area_out, temp0, lay.temp0_bytes,
+                       back + 1, status_ab, stream);
+    if (rc != REMAP_OK)
+        return rc;
+    // read-back 1: the bucket keys of both meshes, the cells' error bits
+    int64_t got[3];
+    REMAP_HIP_CHECK(hipMemcpyAsync(got, back, sizeof(got),
+                                   hipMemcpyDeviceToHost, stream));
+    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+    const int64_t n_bkeys = got[0], n_akeys = got[1];
+    const int err_a = static_cast<int>(got[2] & 0xffffffff);
+    const int err_b = static_cast<int>((got[2] >> 32) & 0xffffffff);
+    if (err_a || err_b)
+        return meshes_fail(err_a, err_b, 0);
+    if (n_bkeys >= (int64_t(1) << 32) - 1 || n_akeys >= (int64_t(1) << 32) - 1)
+        return fail(REMAP_ERR_UNSUPPORTED,
+                    "remap_overlap_meshes: %lld / %lld bucket keys",
+                    static_cast<long long>(n_akeys),
+                    static_cast<long long>(n_bkeys));
+    if (n_pairs > 0 && n_akeys == 0)
+        return meshes_fail(0, 0, REMAP_OVERLAP_ERR_CAPACITY);
+    rc = mesh_var_layout(n_akeys, n_bkeys, n_pairs, &lay);
+    if (rc != REMAP_OK)
+        return rc;
+    if (workspace_bytes < lay.total)
+        return fail(REMAP_ERR_WORKSPACE,
+                    "remap_overlap_meshes: workspace of %zu bytes, need %zu",
+                    workspace_bytes, lay.total);
+    uint64_t *bkeys = reinterpret_cast<uint64_t *>(ws + lay.bkeys);
+    uint64_t *bkeys_s = reinterpret_cast<uint64_t *>(ws + lay.bkeys_s);
+    uint64_t *akeys = reinterpret_cast<uint64_t *>(ws + lay.akeys);
+    uint64_t *pcnt = reinterpret_cast<uint64_t *>(ws + lay.pcnt);
+    uint64_t *poff = reinterpret_cast<uint64_t *>(ws + lay.poff);
+    uint64_t *cand = reinterpret_cast<uint64_t *>(ws + lay.cand);
+    uint64_t *cand_s = reinterpret_cast<uint64_t *>(ws + lay.cand_s);
+    double *parea = reinterpret_cast<double *>(ws + lay.parea);
+    double *area_c = reinterpret_cast<double *>(ws + lay.area_c);
+    uint32_t *head = reinterpret_cast<uint32_t *>(ws + lay.head);
+    uint32_t *slot = reinterpret_cast<uint32_t *>(ws + lay.slot);
+    uint64_t *n_unique = reinterpret_cast<uint64_t *>(back + 3);
+    int64_t *n_kept = back + 4;
+    void *temp = ws + lay.temp;
+
+    // b's bucket lists
+    if (n_bkeys > 0) {
+        hipLaunchKernelGGL(fill_pairs<true>, dim3(blocks(B.n_cells, kBlock)),
+                           dim3(kBlock), 0, stream, B, sb.boxes, sb.offs,
+                           n_bkeys, bkeys, status);
+        REMAP_HIP_CHECK(hipGetLastError());
+        size_t tb = lay.temp_bytes;
+        REMAP_HIP_CHECK((rocprim::radix_sort_keys(
+            temp, tb, static_cast<const uint64_t *>(bkeys), bkeys_s,
+            static_cast<size_t>(n_bkeys), 0u, 64u, stream)));
+    }
+    hipLaunchKernelGGL(bucket_starts, dim3(blocks(n_buckets + 1, kBlock)),
+                       dim3(kBlock), 0, stream, n_buckets, n_bkeys, bkeys_s,
+                       start);
+    REMAP_HIP_CHECK(hipGetLastError());
+    // a's (cell, bucket) keys, expanded to (a, b) candidates
+    if (n_akeys > 0) {
+        const uint32_t nb = blocks(n_akeys, kBlock);
+        hipLaunchKernelGGL(fill_pairs<false>, dim3(blocks(A.n_cells, kBlock)),
+                           dim3(kBlock), 0, stream, A, sa.boxes, sa.offs,
+                           n_akeys, akeys, status);
+        REMAP_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(pair_counts, dim3(nb), dim3(kBlock), 0, stream,
+                           n_akeys, n_buckets, akeys, start, pcnt);
+        REMAP_HIP_CHECK(hipGetLastError());
+        size_t tb = lay.temp_bytes;
+        REMAP_HIP_CHECK((rocprim::exclusive_scan(
+            temp, tb, static_cast<const uint64_t *>(pcnt), poff, uint64_t(0),
+            static_cast<size_t>(n_akeys), rocprim::plus<uint64_t>(), stream)));
+        hipLaunchKernelGGL(expand_pairs, dim3(nb), dim3(kBlock), 0, stream,
+                           n_akeys, n_buckets, akeys, pcnt, poff, start,
+                           bkeys_s, n_pairs, cand, status);
+        REMAP_HIP_CHECK(hipGetLastError());
+    }
+    const bool dst_is_a = dst_is_b == 0;
+    if (n_pairs > 0) {
+        size_t tb = lay.temp_bytes;
+        REMAP_HIP_CHECK((rocprim::radix_sort_keys(
+            temp, tb, static_cast<const uint64_t *>(cand), cand_s,
+            static_cast<size_t>(n_pairs), 0u, 64u, stream)));
+        // the unique pairs into cand, the rest of it ~0 (no pair)
+        REMAP_HIP_CHECK(hipMemsetAsync(cand, 0xff, n_pairs * 8, stream));
+        tb = lay.temp_bytes;
+        REMAP_HIP_CHECK((rocprim::unique(
+            temp, tb, static_cast<const uint64_t *>(cand_s), cand, n_unique,
+            static_cast<size_t>(n_pairs), rocprim::equal_to<uint64_t>(),
+            stream)));
+        hipLaunchKernelGGL(clip_pairs_poly, dim3(blocks(n_pairs, kClipBlock)),
+                           dim3(kClipBlock), 0, stream, A.n_cells, A.max_edges,
+                           B.n_cells, B.max_edges, n_pairs, n_unique, cand,
+                           sa.xyz, sa.nv, sa.centre, sa.radius, sb.xyz, sb.nv,
+                           sb.centre, sb.radius, parea, status);
+        REMAP_HIP_CHECK(hipGetLastError());
+        const uint32_t nb = blocks(n_pairs, kBlock);
+        hipLaunchKernelGGL(flag_kept, dim3(nb), dim3(kBlock), 0, stream,
+                           n_pairs, A.n_cells, B.n_cells, dst_is_a, cand,
+                           parea, a_area_out, b_area_out, head);
+        REMAP_HIP_CHECK(hipGetLastError());
+        tb = lay.temp_bytes;
+        REMAP_HIP_CHECK((rocprim::exclusive_scan(
+            temp, tb, static_cast<const uint32_t *>(head), slot, 0u,
+            static_cast<size_t>(n_pairs), rocprim::plus<uint32_t>(), stream)));
+        hipLaunchKernelGGL(scatter_kept, dim3(nb), dim3(kBlock), 0, stream,
+                           n_pairs, dst_is_a, cand, parea, head, slot, cand_s,
+                           area_c, n_kept);
+        REMAP_HIP_CHECK(hipGetLastError());
+    }
+    // read-back 2: how many entries to sort, the pairs' error bits
+    int64_t kept[2];
+    REMAP_HIP_CHECK(hipMemcpyAsync(kept, n_kept, 16, hipMemcpyDeviceToHost,
+                                   stream));
+    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+    const int64_t n_entries = kept[0];
+    if (const int err = static_cast<int>(kept[1] & 0xffffffff))
+        return meshes_fail(0, 0, err);
+    *n_entries_out = n_entries;
+    if (n_entries > 0) {
+        size_t tb = lay.temp_bytes;
+        REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
+            temp, tb, static_cast<const uint64_t *>(cand_s), cand,
+            static_cast<const double *>(area_c), area_out,
+            static_cast<size_t>(n_entries), 0u, 64u, stream)));
+        hipLaunchKernelGGL(split_keys, dim3(blocks(n_entries, kBlock)),
+                           dim3(kBlock), 0, stream, n_kept, n_pairs, cand,
+                           dst_out, src_out);
+        REMAP_HIP_CHECK(hipGetLastError());
+    }
+    const int64_t n_dst = dst_is_a ? A.n_cells : B.n_cells;
+    if (n_dst > 0) {
+        hipLaunchKernelGGL(dst_sums, dim3(blocks(n_dst, kBlock)), dim3(kBlock),
+                           0, stream, n_dst, n_kept, dst_out, area_out,
+                           dst_is_a ? a_area_out : b_area_out, frac_b_out);
+        REMAP_HIP_CHECK(hipGetLastError());
+    }
+    return REMAP_OK;
+}
+
 }  // namespace
 }  // namespace remap
 
@@ -930,6 +1803,30 @@ int remap_overlap_latlon(const remap_overlap_geom *geom, int32_t dst_is_mesh,
                           workspace_bytes, dst_out, src_out, area_out,
                           frac_b_out, mesh_area_out, grid_area_out,
                           n_entries_out, static_cast<hipStream_t>(stream));
+}
+
+int remap_overlap_meshes_sizes(const remap_overlap_mesh *a,
+                               const remap_overlap_mesh *b, int64_t *counter,
+                               int64_t *n_pairs_out,
+                               size_t *workspace_bytes_out, void *stream)
+{
+    return remap::meshes_sizes(a, b, counter, n_pairs_out, workspace_bytes_out,
+                               static_cast<hipStream_t>(stream));
+}
+
+int remap_overlap_meshes(const remap_overlap_mesh *a,
+                         const remap_overlap_mesh *b, int32_t dst_is_b,
+                         int64_t n_pairs, void *workspace,
+                         size_t workspace_bytes, int32_t *dst_out,
+                         int32_t *src_out, double *area_out,
+                         double *frac_b_out, double *a_area_out,
+                         double *b_area_out, int64_t *n_entries_out,
+                         void *stream)
+{
+    return remap::meshes(a, b, dst_is_b, n_pairs, workspace, workspace_bytes,
+                         dst_out, src_out, area_out, frac_b_out, a_area_out,
+                         b_area_out, n_entries_out,
+                         static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

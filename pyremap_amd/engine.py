@@ -77,6 +77,7 @@ EXPORTS = (
     'remap_gather_rows', 'remap_plan_prepare_short_runs',
     'remap_clock_probe',
     'remap_overlap_latlon_sizes', 'remap_overlap_latlon',
+    'remap_overlap_meshes_sizes', 'remap_overlap_meshes',
 )
 
 
@@ -258,6 +259,17 @@ class _OverlapGeom(ctypes.Structure):  # struct remap_overlap_geom
                 ('lon_corner', ctypes.c_void_p)]
 
 
+class _OverlapMesh(ctypes.Structure):  # struct remap_overlap_mesh
+    _fields_ = [('n_cells', ctypes.c_int64),
+                ('n_vertices', ctypes.c_int64),
+                ('max_edges', ctypes.c_int32),
+                ('reserved', ctypes.c_int32),
+                ('vertices_on_cell', ctypes.c_void_p),
+                ('n_edges_on_cell', ctypes.c_void_p),
+                ('lat_vertex', ctypes.c_void_p),
+                ('lon_vertex', ctypes.c_void_p)]
+
+
 class EngineError(RuntimeError):
     """A failure reported by libremap_hip.so (message from the C side)."""
 
@@ -406,6 +418,18 @@ def load_library():
         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]
+    lib.remap_overlap_meshes_sizes.restype = ctypes.c_int
+    lib.remap_overlap_meshes_sizes.argtypes = [
+        ctypes.POINTER(_OverlapMesh), ctypes.POINTER(_OverlapMesh),
+        ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
+        ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
+    lib.remap_overlap_meshes.restype = ctypes.c_int
+    lib.remap_overlap_meshes.argtypes = [
+        ctypes.POINTER(_OverlapMesh), ctypes.POINTER(_OverlapMesh),
+        ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
+        ctypes.c_void_p]
     if lib.remap_abi_version() != ABI_VERSION:
         raise EngineError(
             f'{path} has ABI {lib.remap_abi_version()}, expected '
@@ -2127,3 +2151,78 @@ def overlap_latlon(vertices_on_cell, n_edges_on_cell, lat_vertex, lon_vertex,
         m = n_entries.value
     return (dst[:m], src[:m], A[:m], frac_b[:n_dst], mesh_area[:n_cells],
             grid_area)
+
+
+# ---------------------------------------------------------------------------
+# conservative overlaps: MPAS cell mesh <-> MPAS cell mesh
+# ---------------------------------------------------------------------------
+
+def overlap_meshes(mesh_a, mesh_b, dst_is_b, timing=None):
+    """
+    The overlap areas between the cells of two MPAS meshes, each given as
+    ``(verticesOnCell 1-based, nEdgesOnCell, latVertex, lonVertex)`` (radians)
+    tensors on one HIP device, through ``remap_overlap_meshes``
+    (``include/remap_hip.h``).  Mesh a's polygons are clipped by mesh b's,
+    which must be convex; both directions use the same overlap list.
+
+    Returns ``(dst, src, A, frac_b, a_area, b_area)``: 0-based int32 indices
+    and float64 areas (steradians) of the entries sorted by ``(dst, src)``
+    -- mesh b is the destination when ``dst_is_b`` -- ``frac_b`` per
+    destination cell, and both sets of polygon areas.  ``timing``: a dict
+    that receives ``n_pairs`` (candidates) and the GPU ``ms`` of the overlap
+    call (events on the stream).
+    """
+    torch = require_gpu()
+    lib = load_library()
+    dev = mesh_a[0].device
+    keep = []
+
+    def geom(mesh):
+        voc = mesh[0].to(torch.int32).contiguous()
+        noc = mesh[1].to(torch.int32).contiguous()
+        lat_v = mesh[2].to(torch.float64).contiguous()
+        lon_v = mesh[3].to(torch.float64).contiguous()
+        keep.extend((voc, noc, lat_v, lon_v))
+        return _OverlapMesh(voc.shape[0], lat_v.numel(), voc.shape[1], 0,
+                            voc.data_ptr(), noc.data_ptr(), lat_v.data_ptr(),
+                            lon_v.data_ptr())
+    ga, gb = geom(mesh_a), geom(mesh_b)
+    n_a, n_b = ga.n_cells, gb.n_cells
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        counter = torch.zeros(4, dtype=torch.int64, device=dev)
+        n_pairs = ctypes.c_int64()
+        nbytes = ctypes.c_size_t()
+        _check(lib.remap_overlap_meshes_sizes(
+            ctypes.byref(ga), ctypes.byref(gb), _ptr(counter),
+            ctypes.byref(n_pairs), ctypes.byref(nbytes), stream),
+            'remap_overlap_meshes_sizes')
+        n = n_pairs.value
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        dst = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        src = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        A = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        # (never empty: the C side wants every output pointer)
+        a_area = torch.empty(max(n_a, 1), dtype=torch.float64, device=dev)
+        b_area = torch.empty(max(n_b, 1), dtype=torch.float64, device=dev)
+        n_dst = n_b if dst_is_b else n_a
+        frac_b = torch.empty(max(n_dst, 1), dtype=torch.float64, device=dev)
+        n_entries = ctypes.c_int64()
+        if timing is not None:
+            t0 = torch.cuda.Event(enable_timing=True)
+            t1 = torch.cuda.Event(enable_timing=True)
+            t0.record()
+        _check(lib.remap_overlap_meshes(
+            ctypes.byref(ga), ctypes.byref(gb), 1 if dst_is_b else 0, n,
+            _ptr(ws), nbytes.value, _ptr(dst), _ptr(src), _ptr(A),
+            _ptr(frac_b), _ptr(a_area), _ptr(b_area), ctypes.byref(n_entries),
+            stream), 'remap_overlap_meshes')
+        if timing is not None:
+            t1.record()
+            t1.synchronize()
+            timing['n_pairs'] = n
+            timing['ms'] = t0.elapsed_time(t1)
+        del ws
+        m = n_entries.value
+    return (dst[:m], src[:m], A[:m], frac_b[:n_dst], a_area[:n_a],
+            b_area[:n_b])

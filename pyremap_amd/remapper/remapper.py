@@ -146,8 +146,10 @@ class Remapper:
         an MPAS mesh (cells, edges or vertices, given by its mesh file) to
         anything -- ESMF's weights, reproduced (:mod:`pyremap_amd.weights`) --
         and ``conserve`` between an MPAS cell mesh (given by its mesh file)
-        and a lat-lon grid, either way: ESMF's first-order conservative map,
-        the cell overlaps clipped on the GPU.  The file is written to
+        and a lat-lon grid, either way, or between two MPAS cell meshes
+        (``src_from_mpas`` / ``dst_from_mpas``): ESMF's first-order
+        conservative map, the cell overlaps clipped on the GPU.  The file is
+        written to
         ``map_filename`` (default name as in ``setup.py:29-42``).
         """
         from pyremap_amd.remapper.setup import _setup_remapper
@@ -158,7 +160,8 @@ class Remapper:
                 '(e.g. through pyremap) and pass it as map_filename, or use '
                 "map_tool='analytic' for lat-lon / projection grid pairs, "
                 "bilinear maps from an MPAS mesh and conserve maps between an "
-                "MPAS cell mesh and a lat-lon grid")
+                "MPAS cell mesh and a lat-lon grid or another MPAS cell "
+                "mesh")
         _setup_remapper(self)
         from pyremap_amd.weights import write_weights
         if logger is not None:

@@ -37,6 +37,9 @@ axes the common methods have closed forms:
   area(dst i), ``frac_b`` = min(sum_j area(dst i n src j) / area(dst i), 1).
   The overlaps are clipped on the GPU (``remap_overlap_latlon``,
   ``pyremap_amd/csrc/remap_overlap.hip``).
+* ``conserve`` between two MPAS cell meshes (both given by their mesh files,
+  :func:`conserve_mesh_mesh`) -- the same map, the overlaps of the two
+  meshes' polygons clipped on the GPU (``remap_overlap_meshes``).
 
 The result is a :class:`pyremap_amd.io.mapfile.MappingFile` with exactly the
 schema ESMF writes (1-based ``row``/``col``, Fortran-ordered grid dims), so it
@@ -810,6 +813,44 @@ def conserve_mesh_latlon(mesh_descriptor, grid_descriptor, mesh_is_src=True,
                        S, frac_b)
 
 
+def conserve_mesh_mesh(src_descriptor, dst_descriptor, device=None,
+                       timing=None):
+    """
+    First-order conservative weights between two MPAS cell meshes (their
+    files), ESMF's ``destarea`` normalisation as in
+    :func:`conserve_mesh_latlon`.  The overlaps come from the GPU
+    (:func:`pyremap_amd.engine.overlap_meshes`): the polygons of the mesh
+    with more cells (the source on a tie) are clipped by those of the other,
+    whose cells must be convex.  The maps of the two directions hold the
+    same overlap areas, transposed.
+    """
+    from pyremap_amd import engine
+    torch = engine.require_gpu()
+    src = mesh_polygons(src_descriptor)
+    dst = mesh_polygons(dst_descriptor)
+    if device is None:
+        device = f'cuda:{torch.cuda.current_device()}'
+
+    def dev(arrays):
+        return [torch.from_numpy(np.ascontiguousarray(a)).to(device)
+                for a in arrays]
+    n_src, n_dst = len(src[1]), len(dst[1])
+    src_is_a = n_src >= n_dst
+    mesh_a, mesh_b = (src, dst) if src_is_a else (dst, src)
+    row, col, A, frac_b, a_area, b_area = engine.overlap_meshes(
+        dev(mesh_a), dev(mesh_b), dst_is_b=src_is_a, timing=timing)
+    row = row.cpu().numpy()
+    col = col.cpu().numpy()
+    A = A.cpu().numpy()
+    frac_b = frac_b.cpu().numpy()
+    dst_area = (b_area if src_is_a else a_area).cpu().numpy()
+    S = A / dst_area[row]
+    return MappingFile(n_src, n_dst, np.array([n_src], dtype=np.int32),
+                       np.array([n_dst], dtype=np.int32),
+                       (row + 1).astype(np.int32), (col + 1).astype(np.int32),
+                       S, frac_b)
+
+
 def _cell_centres(descriptor):
     """(lat, lon) in radians of every cell centre of a rectangular grid, in
     C order, and its Fortran-ordered dims."""
@@ -835,11 +876,17 @@ def build_weights(src_descriptor, dst_descriptor, method='conserve'):
     one to scattered points (an MPAS mesh's cell / edge / vertex positions,
     a point collection), as a :class:`MappingFile`.  ``conserve`` also
     between an MPAS cell mesh given by its mesh file and a lat-lon grid,
-    either way (:func:`conserve_mesh_latlon`, on the GPU).
+    either way (:func:`conserve_mesh_latlon`, on the GPU), and between two
+    MPAS cell meshes given by their mesh files (:func:`conserve_mesh_mesh`,
+    on the GPU).
     """
     if method not in METHODS:
         raise ValueError(f'method {method!r}: expected one of {METHODS}')
     if method == 'conserve':
+        if all(isinstance(d, MpasCellMeshDescriptor) and
+               getattr(d, 'filename', None) is not None
+               for d in (src_descriptor, dst_descriptor)):
+            return conserve_mesh_mesh(src_descriptor, dst_descriptor)
         for mesh, grid, mesh_is_src in ((src_descriptor, dst_descriptor, True),
                                         (dst_descriptor, src_descriptor,
                                          False)):

@@ -7,6 +7,10 @@ on the warm second call, and the numpy reference clipper's per-pair rate on
 a sample of the same pairs (tests/test_conserve_mesh_cpu.py).
 
     python tools/overlap_timing.py [--sizes 153:0.5,608:0.25] [--sample 2000]
+    python tools/overlap_timing.py --meshes 608:400,153:100
+
+--meshes times remap_overlap_meshes instead, between the icosahedral meshes
+n1 (clipped) and n2 (clipping), the same way.
 
 One JSON line per size: cells, grid cells, candidates, entries, ms.
 """
@@ -27,7 +31,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--sizes', default='153:0.5,608:0.25')
     ap.add_argument('--sample', type=int, default=2000)
+    ap.add_argument('--meshes', default=None,
+                    help='n1:n2,... icosahedral mesh pairs (mesh <-> mesh)')
     args = ap.parse_args()
+    if args.meshes:
+        return time_meshes(args.meshes, args.sample)
     import torch
     from pyremap_amd import engine, synthetic
     from pyremap_amd.descriptor import get_lat_lon_descriptor
@@ -81,6 +89,57 @@ def main():
             'numpy_ref_est_s': round(runs[1]['n_pairs'] * ref_s / len(pick),
                                      1),
             'sample_max_dS': float(err.max()),
+            'mesh_gen_s': round(gen_s, 1)}), flush=True)
+
+
+def time_meshes(pairs, sample):
+    import torch
+    from pyremap_amd import engine, synthetic
+    from test_conserve_mesh_cpu import clip, polygon_area, unit
+    engine.require_gpu()
+    dev = 'cuda:0'
+    for item in pairs.split(','):
+        n1, n2 = (int(x) for x in item.split(':'))
+        t0 = time.time()
+        meshes = [synthetic.icosahedral_mesh(n) for n in (n1, n2)]
+        gen_s = time.time() - t0
+        arrays = [[torch.from_numpy(np.ascontiguousarray(m[k])).to(dev)
+                   for k in ('verticesOnCell', 'nEdgesOnCell', 'latVertex',
+                             'lonVertex')] for m in meshes]
+        runs = []
+        for _ in range(2):
+            timing = {}
+            out = engine.overlap_meshes(*arrays, dst_is_b=True,
+                                        timing=timing)
+            torch.cuda.synchronize()
+            runs.append(timing)
+        dst, src, A = (x.cpu().numpy() for x in out[:3])
+        b_area = out[5].cpu().numpy()
+        # the numpy reference on a sample of the entries
+        rng = np.random.default_rng(0)
+        pick = rng.choice(len(dst), size=min(sample, len(dst)),
+                          replace=False)
+        xyz = [unit(m['latVertex'], m['lonVertex']) for m in meshes]
+
+        def poly(k, c):
+            m = meshes[k]
+            return xyz[k][m['verticesOnCell'][c, :m['nEdgesOnCell'][c]] - 1]
+        t0 = time.time()
+        ref = [polygon_area(clip(poly(0, src[k]), poly(1, dst[k])))
+               for k in pick]
+        ref_s = time.time() - t0
+        err = np.abs(np.array(ref) - A[pick]) / b_area[dst[pick]]
+        print(json.dumps({
+            'mesh_a_cells': int(len(meshes[0]['nEdgesOnCell'])),
+            'mesh_b_cells': int(len(meshes[1]['nEdgesOnCell'])),
+            'candidates': int(runs[1]['n_pairs']), 'entries': int(len(dst)),
+            'ms_first': round(runs[0]['ms'], 3),
+            'ms_warm': round(runs[1]['ms'], 3),
+            'numpy_ref_pairs_per_s': round(len(pick) / ref_s, 1),
+            'numpy_ref_est_s': round(runs[1]['n_pairs'] * ref_s / len(pick),
+                                     1),
+            'sample_max_dS': float(err.max()),
+            'sum_A_minus_4pi': float(A.sum() - 4 * np.pi),
             'mesh_gen_s': round(gen_s, 1)}), flush=True)
 
 
