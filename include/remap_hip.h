@@ -412,7 +412,7 @@ typedef struct remap_apply_args {
      * (group, entry, member) order is every wave's own contiguous stream.
      * The workgroup sends each distinct source row of the supergroup ONCE
      * from global memory into an LDS ring (LDS-DMA) and every wave adds the
-     * entries its own rows own from there (csrc/spmm_groupshare.h); a row
+     * entries its own rows own from there (csrc/spmm_sharering.h); a row
      * still adds its entries in ascending column order, so results are
      * unchanged.  Used by family 10 on float64 fields with even strides:
      * with tune[5] = 32 in the frac_b and raw modes on at least 104
@@ -508,7 +508,7 @@ REMAP_API int remap_groups_build(const remap_csr *A, const double *frac_b,
 
 /*
  * Build the SHARED union lists of the shared form of family 10
- * (remap_apply_args.share_*; csrc/spmm_groupshare.h) on top of an 8-row
+ * (remap_apply_args.share_*; csrc/spmm_sharering.h) on top of an 8-row
  * group schedule remap_groups_build has made for the same rows: supergroup s
  * = work slots [8 * share_waves * s, + 8 * share_waves) of that schedule
  * (build it with the same share_waves, so that a supergroup is a 4 x 4 /

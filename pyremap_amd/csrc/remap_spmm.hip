@@ -61,6 +61,7 @@ namespace {
 #include "spmm_rowgroup.h"
 #include "spmm_grouproll.h"
 #include "spmm_groupmask.h"
+#include "spmm_sharering.h"
 #include "spmm_groupshare.h"
 #include "spmm_grouptime.h"
 #include "spmm_timeshare.h"
@@ -495,23 +496,20 @@ typename GroupFn<XT>::type pick_rowgroup(const remap_apply_args *a, int tiles,
     return fn;
 }
 
-// the shared form (spmm_groupshare.h): float64, two elements per lane
+// the shared form (spmm_sharering.h, spmm_groupshare.h): float64, two
+// elements per lane
 typedef void (*share_fn)(const KParams, const uint32_t, const int64_t *,
                          const double *, const int32_t *, const double *,
                          const int64_t *, const int32_t *, const int32_t *,
                          const double *);
 
-// (built, measured on config 5 and NOT instantiated here -- the template
-// keeps the parameters: 2-wave workgroups over 4 x 4 tiles, 28.5 ms against
-// 20.5; rings of 8 x 3, 4 x 3, 4 x 4 entries x buffers, 31.2 / 21.4 / 21.2;
-// the masked mode with per-lane normalisers, 32.1 at one K tile and 37.8 at
-// two against 27.0 of the 8-row groups: profiles/r06_analysis/
-// config5_share.md.  The masked mode's shared form is spmm_timeshare.)
+// (other ring shapes and the masked mode were built, measured on config 5
+// and are not instantiated: spmm_sharering.h, spmm_groupshare.h)
 template <int TILES>
 share_fn pick_groupshare(int mode, bool fma)
 {
     return by_mode<false>(mode, fma, [](auto m, auto f) {
-        return spmm_groupshare<TILES, m, f, 4, 8, 2, 2>;
+        return spmm_groupshare<TILES, m, f, 2>;
     });
 }
 
@@ -780,10 +778,9 @@ constexpr int64_t kShareMinK = 104;
 constexpr int64_t kNarrowMinK = 34;
 
 // The forms of family 10 that address X with a flat 64-bit address per lane
-// (LDS-DMA: spmm_groupshare.h, spmm_timeshare.h, spmm_cellshare.h) also serve
-// fields whose batches lie further apart than 32-bit offsets reach -- (Time,
-// nCells, nVertLevels) on a 3.7 M-cell mesh: 1.9 GB per time slice.  Does
-// this call take one of them?
+// (LDS-DMA: spmm_sharering.h) also serve fields whose batches lie further
+// apart than 32-bit offsets reach -- (Time, nCells, nVertLevels) on a 3.7
+// M-cell mesh: 1.9 GB per time slice.  Does this call take one of them?
 bool wide_share(const remap_apply_args *a, const Call &c)
 {
     if (!c.ring_ok)
@@ -938,17 +935,16 @@ int run_rowgroup(const remap_apply_args *a, const Call &c, KParams p,
         const int64_t k_chunks = shape_tiles(p, a, c.K, kWave * 2, 2);
         const int64_t grid = shape_grid(p, ceil_div(a->n_groups, (int64_t)4),
                                         k_chunks, a->tune[4] != 1, side);
-        // one normaliser per ROW; 256 columns per workgroup.  The ring: two
-        // buffers of 8 entries x 2 KiB; 2 x 4 slots of a step's weights;
-        // slack
+        // one normaliser per ROW; 256 columns per workgroup; 2 KiB of an
+        // entry in the ring
         return launch(c.fma ? spmm_cellshare<true, 1>
                             : spmm_cellshare<false, 1>,
-                      a, grid, kWave * 4, 2u * (8u * 2048u + 4u * 512u) + 512u,
+                      a, grid, kWave * 4, ShareRing<2 * 1024>::kLdsBytes,
                       stream, p, a->flags, a->group_meta, a->group_col,
                       a->group_w, a->group_mask, a->group_rid, a->share_meta,
                       a->share_col, a->share_mask, X64);
     }
-    // tune[5] = 32: the shared form (spmm_groupshare.h) -- W waves, one
+    // tune[5] = 32: the shared form (spmm_sharering.h) -- 4 waves, one
     // union through an LDS ring; float64 fields in whole 16-byte pieces,
     // at least 104 columns (kShareMinK).  A call it cannot serve takes the 8-row groups
     // of the same schedule (a preference under REMAP_FLAG_TUNE_HINT, an
@@ -963,14 +959,13 @@ int run_rowgroup(const remap_apply_args *a, const Call &c, KParams p,
             const int64_t grid =
                 shape_grid(p, ceil_div(a->n_groups, (int64_t)4), k_chunks,
                            a->tune[4] != 1, side);
-            // the ring: two buffers of 8 entries x 512 B; 2 x 4 slots of a
-            // step's weights; slack
+            // (512 B of an entry in the ring)
             const auto fn = by_mode<false>(a->mode, c.fma, [](auto m, auto f) {
                 return spmm_narrowshare<m, f, 2>;
             });
             return launch(fn, a, grid, kWave * 4,
-                          2u * (8u * 512u + 4u * 512u) + 512u, stream, p,
-                          a->flags, a->group_meta, a->group_w, a->group_rid,
+                          ShareRing<512>::kLdsBytes, stream, p, a->flags,
+                          a->group_meta, a->group_w, a->group_rid,
                           a->group_frac, a->share_meta, a->share_col,
                           a->share_mask, X64);
         }
@@ -987,14 +982,12 @@ int run_rowgroup(const remap_apply_args *a, const Call &c, KParams p,
                 ceil_div(a->n_groups, (int64_t)a->share_waves);
             const int64_t grid =
                 shape_grid(p, n_super, k_chunks, a->tune[4] != 1, side);
-            // the ring: two buffers of 8 entries, 1 KiB per entry and K tile;
-            // 2 x 4 slots of a step's weights; slack for the lanes that read
-            // past the last slot
+            // (1 KiB per entry and K tile in the ring)
             return launch(tiles == 1 ? pick_groupshare<1>(a->mode, c.fma)
                                      : pick_groupshare<2>(a->mode, c.fma),
                           a, grid, kWave * 4,
-                          2u * (8u * 1024u * static_cast<uint32_t>(tiles) +
-                                4u * 512u) + 512u,
+                          tiles == 1 ? ShareRing<1024>::kLdsBytes
+                                     : ShareRing<2048>::kLdsBytes,
                           stream, p, a->flags, a->group_meta, a->group_w,
                           a->group_rid, a->group_frac, a->share_meta,
                           a->share_col, a->share_mask, X64);
@@ -1033,12 +1026,11 @@ int run_rowgroup(const remap_apply_args *a, const Call &c, KParams p,
             const int64_t grid =
                 shape_grid(p, ceil_div(a->n_groups, (int64_t)4), n_lb * n_tb,
                            a->tune[4] != 1, side);
-            // the ring: two buffers of 8 entries x (4 slices x 512 B); 2 x 4
-            // slots of a step's weights; slack
+            // (4 slices x 512 B of an entry in the ring)
             return launch(c.fma ? spmm_timeshare<true, 1>
                                 : spmm_timeshare<false, 1>,
                           a, grid, kWave * 4,
-                          2u * (8u * 2048u + 4u * 512u) + 512u, stream, p,
+                          ShareRing<4 * 512>::kLdsBytes, stream, p,
                           a->flags, a->group_meta, a->group_col, a->group_w,
                           a->group_mask, a->group_rid, a->share_meta,
                           a->share_col, a->share_mask, X64);

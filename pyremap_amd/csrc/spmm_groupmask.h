@@ -33,14 +33,32 @@
 // two forms.  Without the flag sums start at +0.0 and never are -0.0.)
 // ---------------------------------------------------------------------------
 
+// A lane's VEC elements of a source row: through a buffer descriptor of the
+// row where the lane's byte offset from the row's base fits 32 bits, through
+// a flat address where it is an element offset of 64 (the batches of a (Time,
+// nCells, nVertLevels) field: spmm_cellshare.h)
+template <typename XT, int VEC>
+__device__ __forceinline__ typename XVec<XT, VEC>::type general_load_x(
+    const XT *row, const uint32_t xo)
+{
+    return load_x_buf<XT, VEC>(row_rsrc(row), xo);
+}
+
+template <typename XT, int VEC>
+__device__ __forceinline__ typename XVec<XT, VEC>::type general_load_x(
+    const XT *row, const int64_t xoff)
+{
+    return load_x<XT, VEC>(row + xoff);
+}
+
 // one K tile of one group with per-lane normalisers (spmm_rowgroup's masked
 // body at TILES = 1), epilogue included
-template <typename XT, bool FMA, int G, int UNR, int VEC>
+template <typename XT, bool FMA, int G, int UNR, int VEC, typename XOFF>
 __device__ __forceinline__ void groupmask_general_tile(
     const KParams &p, const int64_t s, const int64_t woff0, const int64_t e,
     const int32_t *__restrict__ gcol, const double *__restrict__ gw,
     const int32_t *__restrict__ gmask, const int32_t *__restrict__ grid,
-    const XT *__restrict__ X, const uint32_t xo, const int64_t yoff_t,
+    const XT *__restrict__ X, const XOFF xo, const int64_t yoff_t,
     const bool act_t, const int64_t slot0, const int nmem, const int lane)
 {
     typedef typename XVec<XT, VEC>::type xvec_t;
@@ -63,11 +81,9 @@ __device__ __forceinline__ void groupmask_general_tile(
         xvec_t xv[UNR];
 #pragma unroll
         for (int uu = 0; uu < UNR; ++uu) {
-            if (uu < n) {
-                const __amdgpu_buffer_rsrc_t xr = row_rsrc(
-                    X + static_cast<int64_t>(cv[uu]) * p.ldx);
-                xv[uu] = load_x_buf<XT, VEC>(xr, xo);
-            }
+            if (uu < n)
+                xv[uu] = general_load_x<XT, VEC>(
+                    X + static_cast<int64_t>(cv[uu]) * p.ldx, xo);
         }
         asm volatile("" ::: "memory");
         int idx = 0;

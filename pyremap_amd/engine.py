@@ -1103,7 +1103,7 @@ class RemapPlan:
         shared source rows).
 
         ``share`` = 2 or 4: also build the SHARED union lists of the shared
-        form (``csrc/spmm_groupshare.h``, ``remap_share_build``): 2 / 4
+        form (``csrc/spmm_sharering.h``, ``remap_share_build``): 2 / 4
         consecutive 8-row groups -- a 4 x 4 / 4 x 8 tile of the grid, walked
         row-major inside the supertiles -- get one union served by one
         workgroup through LDS.  ``groups['share']['ratio']`` is their union
