@@ -876,8 +876,8 @@ enum {
                                          the horizon of the mesh cell's centre
                                          (the gnomonic projection's limit)     */
     REMAP_OVERLAP_ERR_CAPACITY = 8,   /* n_pairs differs from the count        */
-    REMAP_OVERLAP_ERR_CONVEX = 32     /* a clipper cell (mesh b of
-                                         remap_overlap_meshes) is not convex  */
+    REMAP_OVERLAP_ERR_CONVEX = 32     /* a clipper cell (b of remap_overlap_meshes
+                                         / _grids) is not convex              */
 };
 
 typedef struct remap_overlap_geom {
@@ -990,6 +990,78 @@ int remap_overlap_meshes(const remap_overlap_mesh *a,
                          double *frac_b_out, double *a_area_out,
                          double *b_area_out, int64_t *n_entries_out,
                          void *stream);
+
+/*
+ * ---------------------------------------------------------------------------
+ * Conservative overlaps where at least one side is a structured 2-D grid
+ * given by its corner arrays (the same geometry, normalisation and sliver
+ * rule as remap_overlap_latlon).  A side is an MPAS cell mesh or a grid of
+ * ny x nx cells; grid cell j * nx + i is the spherical polygon through the
+ * corners (j, i), (j, i + 1), (j + 1, i + 1), (j + 1, i), great-circle edges,
+ * consecutive equal corners dropped (a cell may be a triangle), either
+ * orientation.  Side a's polygons are clipped by side b's (b's cells must be
+ * convex: REMAP_OVERLAP_ERR_CONVEX); both directions (dst_is_b) give the same
+ * overlap list, transposed, with the same bits.
+ *
+ * Candidates come from a pyramid of bounding caps over the grid's own
+ * ny x nx index space (2 x 2 nodes per node), walked once per cell of the
+ * other side; when both sides are grids the pyramid is b's.  Nothing but the
+ * corner arrays is needed: a pole inside the grid and cells across the
+ * longitude seam are served.  A grid has at most 16384 cells a side.
+ *
+ * remap_overlap_grids_sizes() prepares both sides and counts the candidate
+ * pairs in device memory of its own (it allocates and frees it, and
+ * synchronises `stream`).  remap_overlap_grids() is then asynchronous on
+ * `stream` except for ONE host read-back: the number of entries (and every
+ * error bit) after the clipping, before the sort.  No floating-point
+ * atomics: two calls give bitwise-identical outputs.
+ * ---------------------------------------------------------------------------
+ */
+typedef struct remap_overlap_grid {
+    int64_t ny;                 /* cell rows                                  */
+    int64_t nx;                 /* cell columns                               */
+    const double *lat_corner;   /* (device) (ny + 1) x (nx + 1), C order,
+                                   radians, within [-pi/2, pi/2]              */
+    const double *lon_corner;   /* (device) (ny + 1) x (nx + 1), radians, any
+                                   branch                                     */
+} remap_overlap_grid;
+
+/* one side: exactly one of the two is non-NULL */
+typedef struct remap_overlap_side {
+    const remap_overlap_mesh *mesh;
+    const remap_overlap_grid *grid;
+} remap_overlap_side;
+
+/*
+ *   n_pairs_out (host) candidate pairs;  workspace_bytes_out (host) what
+ *   remap_overlap_grids() needs.  At least one side must be a grid.
+ */
+REMAP_API
+int remap_overlap_grids_sizes(const remap_overlap_side *a,
+                              const remap_overlap_side *b,
+                              int64_t *n_pairs_out,
+                              size_t *workspace_bytes_out, void *stream);
+
+/*
+ * The overlap areas A (steradians) of every (destination, source) pair with
+ * A > 1e-14 x area(destination cell), sorted by (dst, src), 0-based.  The
+ * destination is side b when dst_is_b != 0, side a otherwise.
+ *
+ *   dst_out, src_out, area_out (device) n_pairs capacity each, the first
+ *   *n_entries_out meaningful;  frac_b_out (device) one per destination
+ *   cell: min(sum of its entries / its area, 1), summed in entry order;
+ *   a_area_out, b_area_out (device) one per cell of a / b: the polygons'
+ *   own areas;  n_entries_out (host) one int64.
+ */
+REMAP_API
+int remap_overlap_grids(const remap_overlap_side *a,
+                        const remap_overlap_side *b, int32_t dst_is_b,
+                        int64_t n_pairs, void *workspace,
+                        size_t workspace_bytes, int32_t *dst_out,
+                        int32_t *src_out, double *area_out,
+                        double *frac_b_out, double *a_area_out,
+                        double *b_area_out, int64_t *n_entries_out,
+                        void *stream);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,14 @@
 // cell preparation runs against a raster of lat-lon buckets, candidate pairs
 // come from the buckets the cells' boxes share, and clip_pairs_poly clips a
 // cell of one mesh by a (convex) cell of the other.
+//
+// With a structured 2-D grid given by its corner arrays on one side or both
+// (remap_overlap_grids, at the end) the grid's cells are prepared straight
+// from the corners, candidates come from a pyramid of bounding caps over
+// the grid's own index space, and clip_pairs_poly and everything behind it
+// are the mesh path's.  Host read-backs: one in remap_overlap_latlon, two in
+// remap_overlap_meshes, one in remap_overlap_grids (the entry count with
+// every error bit, before the sort); each _sizes call reads its count back.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -212,6 +220,39 @@ struct Ring {
     }
 };
 
+// A ring whose consecutive duplicates are dropped already: the closing
+// duplicate dropped too, turned counter-clockwise, its area (the fan from
+// vertex 0) and its centre.  Returns the error bits; *nv is 0 on an error.
+__device__ int finish_ring(Ring xyz, int *nv_io, V3 *centre, double *area)
+{
+    int nv = *nv_io;
+    *nv_io = 0;
+    *area = 0.0;
+    while (nv > 1 && xyz[nv - 1].x == xyz[0].x && xyz[nv - 1].y == xyz[0].y &&
+           xyz[nv - 1].z == xyz[0].z)
+        --nv;
+    if (nv < 3)
+        return REMAP_OVERLAP_ERR_VERTEX;
+    double a = 0.0;
+    for (int k = 1; k + 1 < nv; ++k)
+        a += tri_area(xyz[0], xyz[k], xyz[k + 1]);
+    if (a < 0.0) {
+        for (int k = 1, l = nv - 1; k < l; ++k, --l) {
+            const V3 t = xyz[k];
+            xyz.set(k, xyz[l]);
+            xyz.set(l, t);
+        }
+        a = -a;
+    }
+    *area = a;
+    *nv_io = nv;
+    V3 s = {0.0, 0.0, 0.0};
+    for (int k = 0; k < nv; ++k)
+        s = {s.x + xyz[k].x, s.y + xyz[k].y, s.z + xyz[k].z};
+    *centre = normalized(s);
+    return 0;
+}
+
 // One mesh cell: its vertices (deduplicated, counter-clockwise) into xyz,
 // its centre, area and box.  Returns the error bits.
 __device__ int prep_cell(const Geom &G, int64_t c, Ring xyz, int *nv_out,
@@ -239,29 +280,10 @@ __device__ int prep_cell(const Geom &G, int64_t c, Ring xyz, int *nv_out,
         }
         xyz.set(nv++, p);
     }
-    while (nv > 1 && xyz[nv - 1].x == xyz[0].x && xyz[nv - 1].y == xyz[0].y &&
-           xyz[nv - 1].z == xyz[0].z)
-        --nv;
-    if (nv < 3)
-        return REMAP_OVERLAP_ERR_VERTEX;
-    double a = 0.0;
-    for (int k = 1; k + 1 < nv; ++k)
-        a += tri_area(xyz[0], xyz[k], xyz[k + 1]);
-    if (a < 0.0) {
-        for (int k = 1, l = nv - 1; k < l; ++k, --l) {
-            const V3 t = xyz[k];
-            xyz.set(k, xyz[l]);
-            xyz.set(l, t);
-        }
-        a = -a;
-    }
-    *area = a;
+    if (const int err = finish_ring(xyz, &nv, centre, area))
+        return err;
     *nv_out = nv;
-    V3 s = {0.0, 0.0, 0.0};
-    for (int k = 0; k < nv; ++k)
-        s = {s.x + xyz[k].x, s.y + xyz[k].y, s.z + xyz[k].z};
-    const V3 cc = normalized(s);
-    *centre = cc;
+    const V3 cc = *centre;
 
     // latitude: the vertices, the arcs' extrema, the poles inside
     double zmin = 1.0, zmax = -1.0;
@@ -1587,6 +1609,75 @@ int prep_side(const Geom &G, bool clipper, const Side &s, double *area,
     return REMAP_OK;
 }
 
+// the buffers of the pairs (n_pairs each) behind clip_pairs_poly
+struct PairWork {
+    uint64_t *cand, *cand_s;   // the pairs a << 32 | b; the kept entries' keys
+    double *parea, *area_c;
+    uint32_t *head, *slot;
+    uint64_t *n_unique;
+    int64_t *n_kept;
+    int32_t *status;
+    void *temp;
+    size_t temp_bytes;
+};
+
+// clip_pairs_poly over the pairs in w.cand (the first *w.n_unique of
+// n_pairs), then flag / scan / scatter: the kept entries re-keyed
+// (dst, src) in w.cand_s / w.area_c, their number in *w.n_kept
+int clip_and_keep(const Geom &A, const Side &sa, const Geom &B, const Side &sb,
+                  bool dst_is_a, int64_t n_pairs, const PairWork &w,
+                  const double *a_area, const double *b_area,
+                  hipStream_t stream)
+{
+    hipLaunchKernelGGL(clip_pairs_poly, dim3(blocks(n_pairs, kClipBlock)),
+                       dim3(kClipBlock), 0, stream, A.n_cells, A.max_edges,
+                       B.n_cells, B.max_edges, n_pairs, w.n_unique, w.cand,
+                       sa.xyz, sa.nv, sa.centre, sa.radius, sb.xyz, sb.nv,
+                       sb.centre, sb.radius, w.parea, w.status);
+    REMAP_HIP_CHECK(hipGetLastError());
+    const uint32_t nb = blocks(n_pairs, kBlock);
+    hipLaunchKernelGGL(flag_kept, dim3(nb), dim3(kBlock), 0, stream, n_pairs,
+                       A.n_cells, B.n_cells, dst_is_a, w.cand, w.parea, a_area,
+                       b_area, w.head);
+    REMAP_HIP_CHECK(hipGetLastError());
+    size_t tb = w.temp_bytes;
+    REMAP_HIP_CHECK((rocprim::exclusive_scan(
+        w.temp, tb, static_cast<const uint32_t *>(w.head), w.slot, 0u,
+        static_cast<size_t>(n_pairs), rocprim::plus<uint32_t>(), stream)));
+    hipLaunchKernelGGL(scatter_kept, dim3(nb), dim3(kBlock), 0, stream,
+                       n_pairs, dst_is_a, w.cand, w.parea, w.head, w.slot,
+                       w.cand_s, w.area_c, w.n_kept);
+    REMAP_HIP_CHECK(hipGetLastError());
+    return REMAP_OK;
+}
+
+// the kept entries sorted by (dst, src) into the outputs, frac_b of every
+// destination cell (w.cand is the sort's key output)
+int sort_and_sum(int64_t n_dst, int64_t n_entries, int64_t n_pairs,
+                 const PairWork &w, int32_t *dst_out, int32_t *src_out,
+                 double *area_out, const double *dst_area, double *frac_b_out,
+                 hipStream_t stream)
+{
+    if (n_entries > 0) {
+        size_t tb = w.temp_bytes;
+        REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
+            w.temp, tb, static_cast<const uint64_t *>(w.cand_s), w.cand,
+            static_cast<const double *>(w.area_c), area_out,
+            static_cast<size_t>(n_entries), 0u, 64u, stream)));
+        hipLaunchKernelGGL(split_keys, dim3(blocks(n_entries, kBlock)),
+                           dim3(kBlock), 0, stream, w.n_kept, n_pairs, w.cand,
+                           dst_out, src_out);
+        REMAP_HIP_CHECK(hipGetLastError());
+    }
+    if (n_dst > 0) {
+        hipLaunchKernelGGL(dst_sums, dim3(blocks(n_dst, kBlock)), dim3(kBlock),
+                           0, stream, n_dst, w.n_kept, dst_out, area_out,
+                           dst_area, frac_b_out);
+        REMAP_HIP_CHECK(hipGetLastError());
+    }
+    return REMAP_OK;
+}
+
 int meshes(const remap_overlap_mesh *mesh_a, const remap_overlap_mesh *mesh_b,
            int32_t dst_is_b, int64_t n_pairs, void *workspace,
            size_t workspace_bytes, int32_t *dst_out, int32_t *src_out,
@@ -1715,6 +1806,8 @@ int meshes(const remap_overlap_mesh *mesh_a, const remap_overlap_mesh *mesh_b,
         REMAP_HIP_CHECK(hipGetLastError());
     }
     const bool dst_is_a = dst_is_b == 0;
+    const PairWork work = {cand, cand_s, parea, area_c, head, slot, n_unique,
+                           n_kept, status, temp, lay.temp_bytes};
     if (n_pairs > 0) {
         size_t tb = lay.temp_bytes;
         REMAP_HIP_CHECK((rocprim::radix_sort_keys(
@@ -1727,25 +1820,10 @@ int meshes(const remap_overlap_mesh *mesh_a, const remap_overlap_mesh *mesh_b,
             temp, tb, static_cast<const uint64_t *>(cand_s), cand, n_unique,
             static_cast<size_t>(n_pairs), rocprim::equal_to<uint64_t>(),
             stream)));
-        hipLaunchKernelGGL(clip_pairs_poly, dim3(blocks(n_pairs, kClipBlock)),
-                           dim3(kClipBlock), 0, stream, A.n_cells, A.max_edges,
-                           B.n_cells, B.max_edges, n_pairs, n_unique, cand,
-                           sa.xyz, sa.nv, sa.centre, sa.radius, sb.xyz, sb.nv,
-                           sb.centre, sb.radius, parea, status);
-        REMAP_HIP_CHECK(hipGetLastError());
-        const uint32_t nb = blocks(n_pairs, kBlock);
-        hipLaunchKernelGGL(flag_kept, dim3(nb), dim3(kBlock), 0, stream,
-                           n_pairs, A.n_cells, B.n_cells, dst_is_a, cand,
-                           parea, a_area_out, b_area_out, head);
-        REMAP_HIP_CHECK(hipGetLastError());
-        tb = lay.temp_bytes;
-        REMAP_HIP_CHECK((rocprim::exclusive_scan(
-            temp, tb, static_cast<const uint32_t *>(head), slot, 0u,
-            static_cast<size_t>(n_pairs), rocprim::plus<uint32_t>(), stream)));
-        hipLaunchKernelGGL(scatter_kept, dim3(nb), dim3(kBlock), 0, stream,
-                           n_pairs, dst_is_a, cand, parea, head, slot, cand_s,
-                           area_c, n_kept);
-        REMAP_HIP_CHECK(hipGetLastError());
+        rc = clip_and_keep(A, sa, B, sb, dst_is_a, n_pairs, work, a_area_out,
+                           b_area_out, stream);
+        if (rc != REMAP_OK)
+            return rc;
     }
     // read-back 2: how many entries to sort, the pairs' error bits
     int64_t kept[2];
@@ -1756,25 +1834,629 @@ int meshes(const remap_overlap_mesh *mesh_a, const remap_overlap_mesh *mesh_b,
     if (const int err = static_cast<int>(kept[1] & 0xffffffff))
         return meshes_fail(0, 0, err);
     *n_entries_out = n_entries;
-    if (n_entries > 0) {
-        size_t tb = lay.temp_bytes;
-        REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-            temp, tb, static_cast<const uint64_t *>(cand_s), cand,
-            static_cast<const double *>(area_c), area_out,
-            static_cast<size_t>(n_entries), 0u, 64u, stream)));
-        hipLaunchKernelGGL(split_keys, dim3(blocks(n_entries, kBlock)),
-                           dim3(kBlock), 0, stream, n_kept, n_pairs, cand,
-                           dst_out, src_out);
+    return sort_and_sum(dst_is_a ? A.n_cells : B.n_cells, n_entries, n_pairs,
+                        work, dst_out, src_out, area_out,
+                        dst_is_a ? a_area_out : b_area_out, frac_b_out,
+                        stream);
+}
+
+// ---------------------------------------------------------------------------
+// structured 2-D grids (remap_overlap_grids): a side is an MPAS mesh or a
+// grid of ny x nx cells given by its (ny + 1) x (nx + 1) corner arrays, cell
+// j * nx + i the polygon of the corners (j, i), (j, i + 1), (j + 1, i + 1),
+// (j + 1, i).  Side a is the subject, side b the convex clipper, as above;
+// what differs is everything in front of clip_pairs_poly:
+//   quad_prep      one lane per grid cell: corners -> unit xyz, duplicates
+//                  dropped, counter-clockwise, area, centre (finish_ring, as
+//                  for mesh cells; no verticesOnCell table); cell_shape as
+//                  above (radius; b convex).  A mesh side: prep_side as above
+//                  against a raster of one bucket (its boxes are not used)
+//   pyramid_level  bounding caps over the grid's cells, level 0 the cells'
+//                  own caps, each node above over 2 x 2 nodes below: centre =
+//                  normalised sum of the children's centres, radius = max
+//                  (angle to child centre + child radius) + kBoxEps; pi =
+//                  "always descend" (children that cancel, a global grid)
+//   pyramid_walk   one lane per cell of the OTHER side: depth first from the
+//                  root with an explicit stack in LDS, a node entered when
+//                  the angle between the centres is at most the sum of the
+//                  radii (+ kBoxEps, clip_pairs_poly's own test); a level-0
+//                  node is a candidate.  Count pass, exclusive scan, fill
+//                  pass with the same walk: keys a << 32 | b whichever side
+//                  walked, unique, in a fixed order
+//   clip_pairs_poly, flag / scan / scatter, radix sort, dst_sums as above
+// The pyramid is the grid side's; when both sides are grids it is b's (the
+// clipper, the side with fewer cells: the side with more cells has the
+// lanes).  Nothing but the corner arrays is needed: a pole inside the grid,
+// cells across the longitude seam and cells of the other side outside the
+// grid are caps like any other.
+// ---------------------------------------------------------------------------
+
+// levels = ceil(log2(max(ny, nx))) + 1; a stack entry packs level (4 bits),
+// row and column (14 bits each)
+constexpr int kMaxLevels = 15;
+constexpr int64_t kMaxGridSide = int64_t(1) << (kMaxLevels - 1);
+// a depth-first walk of a 4-ary tree: a pop and up to four pushes per level
+constexpr int kMaxStack = 3 * kMaxLevels + 1;
+constexpr int kWalkBlock = 64;
+
+struct GridGeom {
+    int64_t ny, nx;
+    const double *lat, *lon;
+};
+
+struct Pyramid {
+    int32_t levels;
+    int64_t ny, nx;
+    const double *centre0, *radius0;   // level 0: the cells' own caps
+    double *nodes;                     // levels >= 1: (x, y, z, radius)
+    const int64_t *first;              // first[l]: where level l >= 1 begins
+};
+
+__host__ __device__ inline int64_t level_dim(int64_t n, int l)
+{
+    return (n + (int64_t(1) << l) - 1) >> l;
+}
+
+int pyramid_levels(int64_t ny, int64_t nx)
+{
+    const int64_t n = ny > nx ? ny : nx;
+    int levels = 1;
+    while (level_dim(n, levels - 1) > 1)
+        ++levels;
+    return levels;
+}
+
+// first[l] of every level; returns the number of nodes above level 0
+__host__ __device__ inline int64_t pyramid_first(int64_t ny, int64_t nx,
+                                                 int levels, int64_t *first)
+{
+    int64_t n = 0;
+    for (int l = 1; l < levels; ++l) {
+        if (first)
+            first[l] = n;
+        n += level_dim(ny, l) * level_dim(nx, l);
+    }
+    return n;
+}
+
+__global__ void pyramid_table(int64_t ny, int64_t nx, int levels,
+                              int64_t *__restrict__ first)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        first[0] = 0;
+        pyramid_first(ny, nx, levels, first);
+    }
+}
+
+__device__ inline void node_cap(const Pyramid &P, int l, int64_t j, int64_t i,
+                                V3 *c, double *r)
+{
+    if (l == 0) {
+        const int64_t k = j * P.nx + i;
+        *c = {P.centre0[3 * k], P.centre0[3 * k + 1], P.centre0[3 * k + 2]};
+        *r = P.radius0[k];
+    } else {
+        const double *n =
+            P.nodes + (P.first[l] + j * level_dim(P.nx, l) + i) * 4;
+        *c = {n[0], n[1], n[2]};
+        *r = n[3];
+    }
+}
+
+__device__ inline double angle(V3 a, V3 b)
+{
+    const V3 x = cross(a, b);
+    return atan2(sqrt(dot(x, x)), dot(a, b));
+}
+
+// one lane per grid cell: its polygon from the corner arrays
+__global__ __launch_bounds__(kPrepBlock) void quad_prep(
+    GridGeom Q, double *__restrict__ cell_xyz, int32_t *__restrict__ cell_nv,
+    double *__restrict__ cell_centre, double *__restrict__ cell_area,
+    int32_t *__restrict__ status)
+{
+    __shared__ double sx[4][kPrepBlock], sy[4][kPrepBlock], sz[4][kPrepBlock];
+    const int lane = threadIdx.x;
+    const int64_t c = (int64_t)blockIdx.x * kPrepBlock + lane;
+    if (c >= Q.ny * Q.nx)
+        return;
+    const Ring xyz = {&sx[0][lane], &sy[0][lane], &sz[0][lane], kPrepBlock};
+    const int64_t j = c / Q.nx, i = c - j * Q.nx;
+    const int64_t sw = j * (Q.nx + 1) + i;
+    int nv = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t at = sw + (k == 1 || k == 2 ? 1 : 0) +
+                           (k >= 2 ? Q.nx + 1 : 0);
+        const V3 p = unit_latlon(Q.lat[at], Q.lon[at]);
+        if (nv > 0) {
+            const V3 q = xyz[nv - 1];
+            if (p.x == q.x && p.y == q.y && p.z == q.z)
+                continue;
+        }
+        xyz.set(nv++, p);
+    }
+    V3 cc = {0.0, 0.0, 1.0};
+    double area;
+    const int err = finish_ring(xyz, &nv, &cc, &area);
+    if (err)
+        atomicOr(status, err);
+    for (int k = 0; k < nv; ++k) {
+        const V3 v = xyz[k];
+        double *o = cell_xyz + (c * 4 + k) * 3;
+        o[0] = v.x;
+        o[1] = v.y;
+        o[2] = v.z;
+    }
+    cell_nv[c] = nv;
+    cell_centre[c * 3 + 0] = cc.x;
+    cell_centre[c * 3 + 1] = cc.y;
+    cell_centre[c * 3 + 2] = cc.z;
+    cell_area[c] = area;
+}
+
+// one lane per node of level l >= 1, the level below it complete
+__global__ __launch_bounds__(kBlock) void pyramid_level(Pyramid P, int l)
+{
+    const int64_t w = level_dim(P.nx, l), h = level_dim(P.ny, l);
+    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (k >= w * h)
+        return;
+    const int64_t J = k / w, I = k - J * w;
+    const int64_t ch = level_dim(P.ny, l - 1), cw = level_dim(P.nx, l - 1);
+    V3 s = {0.0, 0.0, 0.0};
+    bool open = false;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int64_t j = 2 * J + (q >> 1), i = 2 * I + (q & 1);
+        if (j < ch && i < cw) {
+            V3 c;
+            double r;
+            node_cap(P, l - 1, j, i, &c, &r);
+            s = {s.x + c.x, s.y + c.y, s.z + c.z};
+            open |= !(r < kPi);
+        }
+    }
+    const double len = sqrt(dot(s, s));
+    V3 cc = {0.0, 0.0, 1.0};
+    double rad = kPi;
+    // (children that cancel, or one that is open itself: always descend)
+    if (!open && len > 1e-3) {
+        cc = {s.x / len, s.y / len, s.z / len};
+        rad = 0.0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t j = 2 * J + (q >> 1), i = 2 * I + (q & 1);
+            if (j < ch && i < cw) {
+                V3 c;
+                double r;
+                node_cap(P, l - 1, j, i, &c, &r);
+                rad = fmax(rad, angle(cc, c) + r);
+            }
+        }
+        rad += kBoxEps;
+        if (!(rad < kPi))
+            rad = kPi;
+    }
+    double *n = P.nodes + (P.first[l] + k) * 4;
+    n[0] = cc.x;
+    n[1] = cc.y;
+    n[2] = cc.z;
+    n[3] = rad;
+}
+
+// one lane per cell of the walking side: the grid cells whose caps meet its
+// cap.  Count pass: counts[w]; fill pass (kFill): the keys at offs[w]
+template <bool kFill>
+__global__ __launch_bounds__(kWalkBlock) void pyramid_walk(
+    Pyramid P, int64_t n_w, const double *__restrict__ centre_w,
+    const double *__restrict__ radius_w, const int32_t *__restrict__ nv_w,
+    bool walker_is_a, uint64_t *__restrict__ counts,
+    const uint64_t *__restrict__ offs, int64_t capacity,
+    uint64_t *__restrict__ keys, int32_t *__restrict__ status)
+{
+    __shared__ uint32_t stack[kMaxStack][kWalkBlock];
+    const int lane = threadIdx.x;
+    const int64_t w = (int64_t)blockIdx.x * kWalkBlock + lane;
+    if (w >= n_w)
+        return;
+    int64_t o = 0, room = 0;
+    if (kFill) {
+        o = static_cast<int64_t>(offs[w]);
+        room = static_cast<int64_t>(counts[w]);
+        if (o + room > capacity) {
+            atomicOr(status, REMAP_OVERLAP_ERR_CAPACITY);
+            return;
+        }
+        if (w == n_w - 1 && o + room != capacity)
+            atomicOr(status, REMAP_OVERLAP_ERR_CAPACITY);
+    }
+    int64_t cnt = 0;
+    if (nv_w[w] >= 3) {
+        const V3 cw = {centre_w[w * 3], centre_w[w * 3 + 1],
+                       centre_w[w * 3 + 2]};
+        const double rw = radius_w[w];
+        int top = 0;
+        stack[top++][lane] = static_cast<uint32_t>(P.levels - 1) << 28;
+        while (top > 0) {
+            const uint32_t e = stack[--top][lane];
+            const int l = static_cast<int>(e >> 28);
+            const int64_t j = (e >> 14) & 0x3fffu, i = e & 0x3fffu;
+            V3 c;
+            double r;
+            node_cap(P, l, j, i, &c, &r);
+            if (r < kPi && !(angle(cw, c) <= rw + r + kBoxEps))
+                continue;
+            if (l == 0) {
+                if (kFill && cnt < room) {
+                    const uint64_t g = static_cast<uint64_t>(j * P.nx + i);
+                    const uint64_t me = static_cast<uint64_t>(w);
+                    keys[o + cnt] = walker_is_a ? me << 32 | g : g << 32 | me;
+                }
+                ++cnt;
+                continue;
+            }
+            const int64_t ch = level_dim(P.ny, l - 1);
+            const int64_t cwid = level_dim(P.nx, l - 1);
+            // pushed in reverse: popped in row-major order
+            for (int q = 3; q >= 0; --q) {
+                const int64_t jj = 2 * j + (q >> 1), ii = 2 * i + (q & 1);
+                if (jj < ch && ii < cwid) {
+                    if (top < kMaxStack)
+                        stack[top++][lane] =
+                            static_cast<uint32_t>(l - 1) << 28 |
+                            static_cast<uint32_t>(jj) << 14 |
+                            static_cast<uint32_t>(ii);
+                    else
+                        atomicOr(status, REMAP_OVERLAP_ERR_CAPACITY);
+                }
+            }
+        }
+    }
+    if (!kFill)
+        counts[w] = static_cast<uint64_t>(cnt);
+    else if (cnt != room)
+        atomicOr(status, REMAP_OVERLAP_ERR_CAPACITY);
+}
+
+// one side of remap_overlap_grids, checked: G.n_cells / G.max_edges hold
+// for either kind (a grid: ny x nx cells of 4 corners)
+struct GridSide {
+    bool is_grid;
+    Geom G;
+    GridGeom Q;
+};
+
+int check_side(const remap_overlap_side *s, const char *name, GridSide *out)
+{
+    if (!s || (s->mesh != nullptr) == (s->grid != nullptr))
+        return fail(REMAP_ERR_ARG,
+                    "remap_overlap_grids: side %s needs exactly one of mesh "
+                    "and grid", name);
+    out->is_grid = s->grid != nullptr;
+    out->Q = {0, 0, nullptr, nullptr};
+    if (!out->is_grid) {
+        const int rc = check_mesh(s->mesh, name, &out->G);
+        out->G.n_lat = out->G.n_lon = 1;
+        return rc;
+    }
+    const remap_overlap_grid *g = s->grid;
+    if (g->ny < 1 || g->nx < 1 || !g->lat_corner || !g->lon_corner)
+        return fail(REMAP_ERR_ARG, "remap_overlap_grids: bad grid %s", name);
+    if (g->ny > kMaxGridSide || g->nx > kMaxGridSide)
+        return fail(REMAP_ERR_UNSUPPORTED,
+                    "remap_overlap_grids: grid %s of %lld x %lld cells; at "
+                    "most %lld a side",
+                    name, static_cast<long long>(g->ny),
+                    static_cast<long long>(g->nx),
+                    static_cast<long long>(kMaxGridSide));
+    out->Q = {g->ny, g->nx, g->lat_corner, g->lon_corner};
+    out->G = {g->ny * g->nx, 0, 1, 1, 4, 0.0, nullptr, nullptr, nullptr,
+              nullptr, nullptr, nullptr};
+    return REMAP_OK;
+}
+
+// the error bits of one side, or of the pairs (name NULL), as text, the
+// bits' names included
+void describe_side(const char *name, int err, char *out, size_t size)
+{
+    out[0] = '\0';
+    if (!err)
+        return;
+    snprintf(out, size, "%s%s%s%s%s%s%s%s%s", name ? "side " : "",
+             name ? name : "", name ? ": " : "",
+             (err & REMAP_OVERLAP_ERR_EDGES)
+                 ? "a cell has more edges than this build serves "
+                   "(REMAP_OVERLAP_ERR_EDGES); "
+                 : "",
+             (err & REMAP_OVERLAP_ERR_VERTEX)
+                 ? "a cell has fewer than 3 distinct corners or a vertex "
+                   "index out of range (REMAP_OVERLAP_ERR_VERTEX); "
+                 : "",
+             (err & REMAP_OVERLAP_ERR_CONVEX)
+                 ? "a cell is not convex and side b's cells clip "
+                   "(REMAP_OVERLAP_ERR_CONVEX); "
+                 : "",
+             (err & REMAP_OVERLAP_ERR_HEMISPHERE)
+                 ? "a candidate pair has a vertex outside the tangent "
+                   "hemisphere of the side a cell's centre "
+                   "(REMAP_OVERLAP_ERR_HEMISPHERE); "
+                 : "",
+             (err & kErrClip)
+                 ? "a clipped polygon outgrew its 2 x REMAP_OVERLAP_MAX_EDGES "
+                   "vertices; "
+                 : "",
+             (err & REMAP_OVERLAP_ERR_CAPACITY)
+                 ? "the candidate pairs differ from n_pairs, a stale "
+                   "remap_overlap_grids_sizes (REMAP_OVERLAP_ERR_CAPACITY); "
+                 : "");
+}
+
+int grids_fail(int err_a, int err_b, int err_p)
+{
+    char text[3][256];
+    describe_side("a", err_a, text[0], sizeof(text[0]));
+    describe_side("b", err_b, text[1], sizeof(text[1]));
+    describe_side(nullptr, err_p, text[2], sizeof(text[2]));
+    return fail(REMAP_ERR_UNSUPPORTED, "remap_overlap_grids: %s%s%s", text[0],
+                text[1], text[2]);
+}
+
+// the workspace in front of the pairs: the mesh path's (a raster of one
+// bucket, both sides, the read-back words) and the pyramid
+struct GridLayout {
+    MeshLayout m;
+    size_t first, nodes;
+    int levels;
+    const GridSide *index, *walker;   // whose pyramid; whose lanes walk it
+};
+
+int grid_fixed_layout(const GridSide &A, const GridSide &B, GridLayout *L)
+{
+    const int rc = mesh_fixed_layout(A.G, B.G, &L->m);
+    if (rc != REMAP_OK)
+        return rc;
+    L->index = B.is_grid ? &B : &A;
+    L->walker = B.is_grid ? &A : &B;
+    const GridGeom &Q = L->index->Q;
+    L->levels = pyramid_levels(Q.ny, Q.nx);
+    const int64_t n_nodes = pyramid_first(Q.ny, Q.nx, L->levels, nullptr);
+    L->first = take(&L->m.fixed, kMaxLevels * 8);
+    L->nodes = take(&L->m.fixed, static_cast<size_t>(n_nodes + 1) * 4 * 8);
+    return REMAP_OK;
+}
+
+int prep_grid_side(const GridSide &S, bool clipper, const Side &s,
+                   double *area, int32_t *status, hipStream_t stream)
+{
+    hipLaunchKernelGGL(quad_prep, dim3(blocks(S.G.n_cells, kPrepBlock)),
+                       dim3(kPrepBlock), 0, stream, S.Q, s.xyz, s.nv, s.centre,
+                       area, status);
+    REMAP_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(cell_shape, dim3(blocks(S.G.n_cells, kBlock)),
+                       dim3(kBlock), 0, stream, S.G.n_cells, S.G.max_edges,
+                       clipper, s.xyz, s.nv, s.centre, s.radius, status);
+    REMAP_HIP_CHECK(hipGetLastError());
+    return REMAP_OK;
+}
+
+// both sides prepared, the pyramid, the count pass and its scan: the number
+// of candidates in back[3], the sides' error bits in back[2], the walker's
+// counts / offs ready for the fill pass.  The areas go to a_area / b_area.
+int grid_candidates(GridSide &A, GridSide &B, const GridLayout &L, char *ws,
+                    double *a_area, double *b_area, Pyramid *pyramid,
+                    hipStream_t stream)
+{
+    const MeshLayout &lay = L.m;
+    double *lat_c = reinterpret_cast<double *>(ws + lay.lat_c);
+    double *lon_c = reinterpret_cast<double *>(ws + lay.lon_c);
+    int64_t *back = reinterpret_cast<int64_t *>(ws + lay.back);
+    int32_t *status_ab = reinterpret_cast<int32_t *>(back + 2);
+    void *temp0 = ws + lay.temp0;
+    A.G.lat_c = B.G.lat_c = lat_c;
+    A.G.lon_c = B.G.lon_c = lon_c;
+    REMAP_HIP_CHECK(hipMemsetAsync(back, 0, kBackWords * 8, stream));
+    hipLaunchKernelGGL(bucket_edges, dim3(1), dim3(kBlock), 0, stream,
+                       int64_t(1), int64_t(1), lat_c, lon_c);
+    REMAP_HIP_CHECK(hipGetLastError());
+    for (int k = 0; k < 2; ++k) {
+        const GridSide &S = k ? A : B;
+        const Side s = side_at(ws, k ? lay.a : lay.b);
+        double *area = k ? a_area : b_area;
+        int32_t *status = k ? status_ab : status_ab + 1;
+        const int rc = S.is_grid
+            ? prep_grid_side(S, k == 0, s, area, status, stream)
+            : prep_side(S.G, k == 0, s, area, temp0, lay.temp0_bytes,
+                        back + k, status, stream);
+        if (rc != REMAP_OK)
+            return rc;
+    }
+    const Side si = side_at(ws, L.index == &A ? lay.a : lay.b);
+    const Side sw = side_at(ws, L.walker == &A ? lay.a : lay.b);
+    const GridGeom &Q = L.index->Q;
+    int64_t *first = reinterpret_cast<int64_t *>(ws + L.first);
+    const Pyramid P = {L.levels, Q.ny, Q.nx, si.centre, si.radius,
+                       reinterpret_cast<double *>(ws + L.nodes), first};
+    *pyramid = P;
+    hipLaunchKernelGGL(pyramid_table, dim3(1), dim3(kWave), 0, stream, Q.ny,
+                       Q.nx, L.levels, first);
+    REMAP_HIP_CHECK(hipGetLastError());
+    for (int l = 1; l < L.levels; ++l) {
+        const int64_t n = level_dim(Q.ny, l) * level_dim(Q.nx, l);
+        hipLaunchKernelGGL(pyramid_level, dim3(blocks(n, kBlock)),
+                           dim3(kBlock), 0, stream, P, l);
         REMAP_HIP_CHECK(hipGetLastError());
     }
-    const int64_t n_dst = dst_is_a ? A.n_cells : B.n_cells;
-    if (n_dst > 0) {
-        hipLaunchKernelGGL(dst_sums, dim3(blocks(n_dst, kBlock)), dim3(kBlock),
-                           0, stream, n_dst, n_kept, dst_out, area_out,
-                           dst_is_a ? a_area_out : b_area_out, frac_b_out);
+    const int64_t n_w = L.walker->G.n_cells;
+    if (n_w > 0) {
+        hipLaunchKernelGGL(pyramid_walk<false>, dim3(blocks(n_w, kWalkBlock)),
+                           dim3(kWalkBlock), 0, stream, P, n_w, sw.centre,
+                           sw.radius, sw.nv, L.walker == &A, sw.counts,
+                           nullptr, int64_t(0), nullptr, status_ab);
+        REMAP_HIP_CHECK(hipGetLastError());
+        size_t tb = lay.temp0_bytes;
+        REMAP_HIP_CHECK((rocprim::exclusive_scan(
+            temp0, tb, static_cast<const uint64_t *>(sw.counts), sw.offs,
+            uint64_t(0), static_cast<size_t>(n_w), rocprim::plus<uint64_t>(),
+            stream)));
+        hipLaunchKernelGGL(scan_total, dim3(1), dim3(kWave), 0, stream, n_w,
+                           sw.counts, sw.offs, back + 3);
         REMAP_HIP_CHECK(hipGetLastError());
     }
     return REMAP_OK;
+}
+
+int check_sides(const remap_overlap_side *a, const remap_overlap_side *b,
+                GridSide *A, GridSide *B)
+{
+    int rc = check_side(a, "a", A);
+    if (rc == REMAP_OK)
+        rc = check_side(b, "b", B);
+    if (rc != REMAP_OK)
+        return rc;
+    if (!A->is_grid && !B->is_grid)
+        return fail(REMAP_ERR_ARG, "remap_overlap_grids: neither side is a "
+                                   "grid (two meshes: remap_overlap_meshes)");
+    return REMAP_OK;
+}
+
+int grids_sizes(const remap_overlap_side *side_a,
+                const remap_overlap_side *side_b, int64_t *n_pairs_out,
+                size_t *bytes_out, hipStream_t stream)
+{
+    GridSide A, B;
+    int rc = check_sides(side_a, side_b, &A, &B);
+    if (rc != REMAP_OK)
+        return rc;
+    if (!n_pairs_out || !bytes_out)
+        return fail(REMAP_ERR_ARG, "remap_overlap_grids_sizes: NULL output");
+    GridLayout L;
+    rc = grid_fixed_layout(A, B, &L);
+    if (rc != REMAP_OK)
+        return rc;
+    // the count pass needs both sides prepared: in memory of its own, with
+    // the two area arrays behind it
+    const size_t na = static_cast<size_t>(A.G.n_cells > 0 ? A.G.n_cells : 1);
+    const size_t nb = static_cast<size_t>(B.G.n_cells > 0 ? B.G.n_cells : 1);
+    size_t bytes = L.m.fixed;
+    const size_t at_a = take(&bytes, na * 8), at_b = take(&bytes, nb * 8);
+    char *buf = nullptr;
+    REMAP_HIP_CHECK(hipMalloc(&buf, bytes));
+    Pyramid P;
+    int64_t got[2] = {0, 0};
+    rc = grid_candidates(A, B, L, buf, reinterpret_cast<double *>(buf + at_a),
+                         reinterpret_cast<double *>(buf + at_b), &P, stream);
+    hipError_t err = hipSuccess;
+    if (rc == REMAP_OK) {
+        err = hipMemcpyAsync(got, buf + L.m.back + 16, sizeof(got),
+                             hipMemcpyDeviceToHost, stream);
+        if (err == hipSuccess)
+            err = hipStreamSynchronize(stream);
+    } else {
+        (void)hipStreamSynchronize(stream);
+    }
+    const hipError_t freed = hipFree(buf);
+    if (rc != REMAP_OK)
+        return rc;
+    REMAP_HIP_CHECK(err);
+    REMAP_HIP_CHECK(freed);
+    const int err_a = static_cast<int>(got[0] & 0xffffffff);
+    const int err_b = static_cast<int>((got[0] >> 32) & 0xffffffff);
+    if (err_a || err_b)
+        return grids_fail(err_a, err_b, 0);
+    if (got[1] >= (int64_t(1) << 32) - 1)
+        return fail(REMAP_ERR_UNSUPPORTED,
+                    "remap_overlap_grids: %lld candidate pairs",
+                    static_cast<long long>(got[1]));
+    rc = mesh_var_layout(0, 0, got[1], &L.m);
+    if (rc != REMAP_OK)
+        return rc;
+    *n_pairs_out = got[1];
+    *bytes_out = L.m.total;
+    return REMAP_OK;
+}
+
+int grids(const remap_overlap_side *side_a, const remap_overlap_side *side_b,
+          int32_t dst_is_b, int64_t n_pairs, void *workspace,
+          size_t workspace_bytes, int32_t *dst_out, int32_t *src_out,
+          double *area_out, double *frac_b_out, double *a_area_out,
+          double *b_area_out, int64_t *n_entries_out, hipStream_t stream)
+{
+    GridSide A, B;
+    int rc = check_sides(side_a, side_b, &A, &B);
+    if (rc != REMAP_OK)
+        return rc;
+    if (n_pairs < 0 || n_pairs >= (int64_t(1) << 32) - 1)
+        return fail(REMAP_ERR_UNSUPPORTED,
+                    "remap_overlap_grids: %lld candidate pairs",
+                    static_cast<long long>(n_pairs));
+    if (!frac_b_out || !a_area_out || !b_area_out || !n_entries_out ||
+        (n_pairs > 0 && (!dst_out || !src_out || !area_out)))
+        return fail(REMAP_ERR_ARG, "remap_overlap_grids: NULL output");
+    GridLayout L;
+    rc = grid_fixed_layout(A, B, &L);
+    if (rc == REMAP_OK)
+        rc = mesh_var_layout(0, 0, n_pairs, &L.m);
+    if (rc != REMAP_OK)
+        return rc;
+    const MeshLayout &lay = L.m;
+    if (!workspace || workspace_bytes < lay.total)
+        return fail(REMAP_ERR_WORKSPACE,
+                    "remap_overlap_grids: workspace of %zu bytes, need %zu",
+                    workspace_bytes, lay.total);
+    char *ws = static_cast<char *>(workspace);
+    Pyramid P;
+    rc = grid_candidates(A, B, L, ws, a_area_out, b_area_out, &P, stream);
+    if (rc != REMAP_OK)
+        return rc;
+    int64_t *back = reinterpret_cast<int64_t *>(ws + lay.back);
+    const Side sa = side_at(ws, lay.a), sb = side_at(ws, lay.b);
+    const Side sw = L.walker == &A ? sa : sb;
+    const PairWork work = {reinterpret_cast<uint64_t *>(ws + lay.cand),
+                           reinterpret_cast<uint64_t *>(ws + lay.cand_s),
+                           reinterpret_cast<double *>(ws + lay.parea),
+                           reinterpret_cast<double *>(ws + lay.area_c),
+                           reinterpret_cast<uint32_t *>(ws + lay.head),
+                           reinterpret_cast<uint32_t *>(ws + lay.slot),
+                           reinterpret_cast<uint64_t *>(back + 3),
+                           back + 4,
+                           reinterpret_cast<int32_t *>(back + 5),
+                           ws + lay.temp,
+                           lay.temp_bytes};
+    const bool dst_is_a = dst_is_b == 0;
+    const int64_t n_w = L.walker->G.n_cells;
+    if (n_w > 0) {
+        // (with n_pairs 0 it only checks that there are none)
+        hipLaunchKernelGGL(pyramid_walk<true>, dim3(blocks(n_w, kWalkBlock)),
+                           dim3(kWalkBlock), 0, stream, P, n_w, sw.centre,
+                           sw.radius, sw.nv, L.walker == &A, sw.counts,
+                           sw.offs, n_pairs, work.cand, work.status);
+        REMAP_HIP_CHECK(hipGetLastError());
+    }
+    if (n_pairs > 0) {
+        rc = clip_and_keep(A.G, sa, B.G, sb, dst_is_a, n_pairs, work,
+                           a_area_out, b_area_out, stream);
+        if (rc != REMAP_OK)
+            return rc;
+    }
+    // the one read-back: the sides' error bits, the candidates, how many
+    // entries to sort, the pairs' error bits
+    int64_t got[4];
+    REMAP_HIP_CHECK(hipMemcpyAsync(got, back + 2, sizeof(got),
+                                   hipMemcpyDeviceToHost, stream));
+    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+    const int err_a = static_cast<int>(got[0] & 0xffffffff);
+    const int err_b = static_cast<int>((got[0] >> 32) & 0xffffffff);
+    int err_p = static_cast<int>(got[3] & 0xffffffff);
+    if (got[1] != n_pairs)
+        err_p |= REMAP_OVERLAP_ERR_CAPACITY;
+    if (err_a || err_b || err_p)
+        return grids_fail(err_a, err_b, err_p);
+    *n_entries_out = got[2];
+    return sort_and_sum(dst_is_a ? A.G.n_cells : B.G.n_cells, got[2], n_pairs,
+                        work, dst_out, src_out, area_out,
+                        dst_is_a ? a_area_out : b_area_out, frac_b_out,
+                        stream);
 }
 
 }  // namespace
@@ -1827,6 +2509,30 @@ int remap_overlap_meshes(const remap_overlap_mesh *a,
                          dst_out, src_out, area_out, frac_b_out, a_area_out,
                          b_area_out, n_entries_out,
                          static_cast<hipStream_t>(stream));
+}
+
+int remap_overlap_grids_sizes(const remap_overlap_side *a,
+                              const remap_overlap_side *b,
+                              int64_t *n_pairs_out,
+                              size_t *workspace_bytes_out, void *stream)
+{
+    return remap::grids_sizes(a, b, n_pairs_out, workspace_bytes_out,
+                              static_cast<hipStream_t>(stream));
+}
+
+int remap_overlap_grids(const remap_overlap_side *a,
+                        const remap_overlap_side *b, int32_t dst_is_b,
+                        int64_t n_pairs, void *workspace,
+                        size_t workspace_bytes, int32_t *dst_out,
+                        int32_t *src_out, double *area_out,
+                        double *frac_b_out, double *a_area_out,
+                        double *b_area_out, int64_t *n_entries_out,
+                        void *stream)
+{
+    return remap::grids(a, b, dst_is_b, n_pairs, workspace, workspace_bytes,
+                        dst_out, src_out, area_out, frac_b_out, a_area_out,
+                        b_area_out, n_entries_out,
+                        static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -219,16 +219,34 @@ class LatLon2DGridDescriptor(MeshDescriptor):
 
     @classmethod
     def create(cls, lat, lon, lat_dim='y', lon_dim='x', units='degrees',
-               mesh_name=None, regional=True):
+               mesh_name=None, regional=True, lat_corner=None,
+               lon_corner=None):
         """From 2-D centre arrays (no reference counterpart: its only
-        constructor reads a file)."""
+        constructor reads a file).  ``lat_corner`` / ``lon_corner``: the
+        cells' corners, ``(ny + 1, nx + 1)`` in the same units; without them
+        the corners are extrapolated from the centres in lat-lon space (the
+        reference's way), which is meaningless across the longitude seam or
+        a pole."""
         from pyremap_amd.descriptor.corners import extrapolate_corners_2d
+        if (lat_corner is None) != (lon_corner is None):
+            raise ValueError('lat_corner and lon_corner go together')
         d = cls(mesh_name=mesh_name, regional=regional)
         d.lat = np.asarray(lat, dtype=np.float64)
         d.lon = np.asarray(lon, dtype=np.float64)
         d.units = units
-        d.lat_corner = extrapolate_corners_2d(d.lat)
-        d.lon_corner = extrapolate_corners_2d(d.lon)
+        if lat_corner is None:
+            d.lat_corner = extrapolate_corners_2d(d.lat)
+            d.lon_corner = extrapolate_corners_2d(d.lon)
+        else:
+            d.lat_corner = np.array(lat_corner, dtype=np.float64)
+            d.lon_corner = np.array(lon_corner, dtype=np.float64)
+            want = (d.lat.shape[0] + 1, d.lat.shape[1] + 1) \
+                if d.lat.ndim == 2 else None
+            if d.lat_corner.shape != want or d.lon_corner.shape != want:
+                raise ValueError(
+                    f'corner arrays of shapes {d.lat_corner.shape} and '
+                    f'{d.lon_corner.shape} for centres of shape '
+                    f'{d.lat.shape}: expected (ny + 1, nx + 1)')
         d.history = _history()
         d._set_coords('lat', 'lon', lat_dim, lon_dim)
         return d

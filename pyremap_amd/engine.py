@@ -78,6 +78,7 @@ EXPORTS = (
     'remap_clock_probe',
     'remap_overlap_latlon_sizes', 'remap_overlap_latlon',
     'remap_overlap_meshes_sizes', 'remap_overlap_meshes',
+    'remap_overlap_grids_sizes', 'remap_overlap_grids',
 )
 
 
@@ -270,6 +271,18 @@ class _OverlapMesh(ctypes.Structure):  # struct remap_overlap_mesh
                 ('lon_vertex', ctypes.c_void_p)]
 
 
+class _OverlapGrid(ctypes.Structure):  # struct remap_overlap_grid
+    _fields_ = [('ny', ctypes.c_int64),
+                ('nx', ctypes.c_int64),
+                ('lat_corner', ctypes.c_void_p),
+                ('lon_corner', ctypes.c_void_p)]
+
+
+class _OverlapSide(ctypes.Structure):  # struct remap_overlap_side
+    _fields_ = [('mesh', ctypes.POINTER(_OverlapMesh)),
+                ('grid', ctypes.POINTER(_OverlapGrid))]
+
+
 class EngineError(RuntimeError):
     """A failure reported by libremap_hip.so (message from the C side)."""
 
@@ -426,6 +439,18 @@ def load_library():
     lib.remap_overlap_meshes.restype = ctypes.c_int
     lib.remap_overlap_meshes.argtypes = [
         ctypes.POINTER(_OverlapMesh), ctypes.POINTER(_OverlapMesh),
+        ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
+        ctypes.c_void_p]
+    lib.remap_overlap_grids_sizes.restype = ctypes.c_int
+    lib.remap_overlap_grids_sizes.argtypes = [
+        ctypes.POINTER(_OverlapSide), ctypes.POINTER(_OverlapSide),
+        ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_size_t),
+        ctypes.c_void_p]
+    lib.remap_overlap_grids.restype = ctypes.c_int
+    lib.remap_overlap_grids.argtypes = [
+        ctypes.POINTER(_OverlapSide), ctypes.POINTER(_OverlapSide),
         ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
@@ -2217,6 +2242,93 @@ def overlap_meshes(mesh_a, mesh_b, dst_is_b, timing=None):
             _ptr(ws), nbytes.value, _ptr(dst), _ptr(src), _ptr(A),
             _ptr(frac_b), _ptr(a_area), _ptr(b_area), ctypes.byref(n_entries),
             stream), 'remap_overlap_meshes')
+        if timing is not None:
+            t1.record()
+            t1.synchronize()
+            timing['n_pairs'] = n
+            timing['ms'] = t0.elapsed_time(t1)
+        del ws
+        m = n_entries.value
+    return (dst[:m], src[:m], A[:m], frac_b[:n_dst], a_area[:n_a],
+            b_area[:n_b])
+
+
+# ---------------------------------------------------------------------------
+# conservative overlaps with a structured 2-D grid on one side or both
+# ---------------------------------------------------------------------------
+
+def overlap_grids(side_a, side_b, dst_is_b, timing=None):
+    """
+    The overlap areas between the cells of two sides, at least one of them a
+    structured 2-D grid, through ``remap_overlap_grids``
+    (``include/remap_hip.h``).  A side is a grid ``(lat_corner, lon_corner)``
+    -- two ``(ny + 1, nx + 1)`` tensors in radians, cell ``j * nx + i`` --
+    or an MPAS mesh ``(verticesOnCell 1-based, nEdgesOnCell, latVertex,
+    lonVertex)`` as in :func:`overlap_meshes`; all tensors on one HIP device.
+    Side a's polygons are clipped by side b's, which must be convex; both
+    directions use the same overlap list.
+
+    Returns ``(dst, src, A, frac_b, a_area, b_area)`` as
+    :func:`overlap_meshes` does -- side b is the destination when
+    ``dst_is_b``.  ``timing``: a dict that receives ``n_pairs`` (candidates)
+    and the GPU ``ms`` of the overlap call (events on the stream).
+    """
+    torch = require_gpu()
+    lib = load_library()
+    dev = side_a[0].device
+    keep = []
+
+    def side(arrays):
+        if len(arrays) == 2:
+            lat = arrays[0].to(torch.float64).contiguous()
+            lon = arrays[1].to(torch.float64).contiguous()
+            if lat.dim() != 2 or lat.shape != lon.shape or \
+                    min(lat.shape) < 2:
+                raise ValueError(
+                    f'grid corners of shapes {tuple(lat.shape)} and '
+                    f'{tuple(lon.shape)}: expected two (ny + 1, nx + 1) '
+                    f'arrays')
+            g = _OverlapGrid(lat.shape[0] - 1, lat.shape[1] - 1,
+                             lat.data_ptr(), lon.data_ptr())
+            keep.extend((lat, lon, g))
+            return _OverlapSide(None, ctypes.pointer(g)), int(g.ny * g.nx)
+        voc = arrays[0].to(torch.int32).contiguous()
+        noc = arrays[1].to(torch.int32).contiguous()
+        lat_v = arrays[2].to(torch.float64).contiguous()
+        lon_v = arrays[3].to(torch.float64).contiguous()
+        m = _OverlapMesh(voc.shape[0], lat_v.numel(), voc.shape[1], 0,
+                         voc.data_ptr(), noc.data_ptr(), lat_v.data_ptr(),
+                         lon_v.data_ptr())
+        keep.extend((voc, noc, lat_v, lon_v, m))
+        return _OverlapSide(ctypes.pointer(m), None), int(m.n_cells)
+    (ga, n_a), (gb, n_b) = side(side_a), side(side_b)
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        n_pairs = ctypes.c_int64()
+        nbytes = ctypes.c_size_t()
+        _check(lib.remap_overlap_grids_sizes(
+            ctypes.byref(ga), ctypes.byref(gb), ctypes.byref(n_pairs),
+            ctypes.byref(nbytes), stream), 'remap_overlap_grids_sizes')
+        n = n_pairs.value
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        dst = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        src = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        A = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        # (never empty: the C side wants every output pointer)
+        a_area = torch.empty(max(n_a, 1), dtype=torch.float64, device=dev)
+        b_area = torch.empty(max(n_b, 1), dtype=torch.float64, device=dev)
+        n_dst = n_b if dst_is_b else n_a
+        frac_b = torch.empty(max(n_dst, 1), dtype=torch.float64, device=dev)
+        n_entries = ctypes.c_int64()
+        if timing is not None:
+            t0 = torch.cuda.Event(enable_timing=True)
+            t1 = torch.cuda.Event(enable_timing=True)
+            t0.record()
+        _check(lib.remap_overlap_grids(
+            ctypes.byref(ga), ctypes.byref(gb), 1 if dst_is_b else 0, n,
+            _ptr(ws), nbytes.value, _ptr(dst), _ptr(src), _ptr(A),
+            _ptr(frac_b), _ptr(a_area), _ptr(b_area), ctypes.byref(n_entries),
+            stream), 'remap_overlap_grids')
         if timing is not None:
             t1.record()
             t1.synchronize()

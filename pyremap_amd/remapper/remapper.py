@@ -147,8 +147,12 @@ class Remapper:
         anything -- ESMF's weights, reproduced (:mod:`pyremap_amd.weights`) --
         and ``conserve`` between an MPAS cell mesh (given by its mesh file)
         and a lat-lon grid, either way, or between two MPAS cell meshes
-        (``src_from_mpas`` / ``dst_from_mpas``): ESMF's first-order
-        conservative map, the cell overlaps clipped on the GPU.  The file is
+        (``src_from_mpas`` / ``dst_from_mpas``), and between a grid given by
+        2-D latitude / longitude arrays with their corners
+        (``LatLon2DGridDescriptor``) and an MPAS cell mesh, a lat-lon grid or
+        another such grid, either way: ESMF's first-order conservative map,
+        the cell overlaps clipped on the GPU.  ``bilinear`` / ``neareststod``
+        also go towards a 2-D grid (its cell centres).  The file is
         written to
         ``map_filename`` (default name as in ``setup.py:29-42``).
         """
@@ -161,7 +165,8 @@ class Remapper:
                 "map_tool='analytic' for lat-lon / projection grid pairs, "
                 "bilinear maps from an MPAS mesh and conserve maps between an "
                 "MPAS cell mesh and a lat-lon grid or another MPAS cell "
-                "mesh")
+                "mesh, or between a 2-D lat-lon grid (its corner arrays) and "
+                "an MPAS cell mesh, a lat-lon grid or another 2-D grid")
         _setup_remapper(self)
         from pyremap_amd.weights import write_weights
         if logger is not None:

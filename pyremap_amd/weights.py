@@ -40,6 +40,14 @@ axes the common methods have closed forms:
 * ``conserve`` between two MPAS cell meshes (both given by their mesh files,
   :func:`conserve_mesh_mesh`) -- the same map, the overlaps of the two
   meshes' polygons clipped on the GPU (``remap_overlap_meshes``).
+* ``conserve`` between a grid given by 2-D latitude / longitude arrays with
+  their ``(ny + 1, nx + 1)`` corner arrays (``LatLon2DGridDescriptor``: a
+  regional-model, tripolar or polar stereographic grid with its corners
+  written out) and an MPAS cell mesh given by its mesh file, a lat-lon grid
+  or another such grid, either way (:func:`conserve_grid`) -- the same map,
+  every grid cell the great-circle polygon of its four corners
+  (``remap_overlap_grids``).  ``bilinear`` and ``neareststod`` go TOWARDS
+  such a grid (its cell centres are points for the source), not from it.
 
 The result is a :class:`pyremap_amd.io.mapfile.MappingFile` with exactly the
 schema ESMF writes (1-based ``row``/``col``, Fortran-ordered grid dims), so it
@@ -48,6 +56,7 @@ goes through the same ``_load_mapping`` as any other mapping file.
 import numpy as np
 
 from pyremap_amd.descriptor import (
+    LatLon2DGridDescriptor,
     LatLonGridDescriptor,
     MpasCellMeshDescriptor,
     MpasMeshDescriptor,
@@ -851,10 +860,112 @@ def conserve_mesh_mesh(src_descriptor, dst_descriptor, device=None,
                        S, frac_b)
 
 
+# ---------------------------------------------------------------------------
+# conserve with a 2-D lat-lon grid (its corner arrays) on one side or both
+# ---------------------------------------------------------------------------
+
+_GRID_PAIRS = ('conserve with a 2-D lat-lon grid (LatLon2DGridDescriptor) is '
+               'served between it and an MPAS cell mesh given by its mesh '
+               'file, a LatLonGridDescriptor or another 2-D lat-lon grid, '
+               'either way')
+
+
+def grid_corners(descriptor):
+    """The ``(ny + 1, nx + 1)`` corner arrays ``(lat, lon)`` in radians of a
+    2-D lat-lon grid, checked, or of a lat-lon grid (the outer product of
+    its corner axes, latitudes clipped to +-pi/2)."""
+    if isinstance(descriptor, LatLonGridDescriptor):
+        lat_e, lon_e, _ = latlon_corners(descriptor)
+        lat, lon = np.meshgrid(lat_e, lon_e, indexing='ij')
+        return np.ascontiguousarray(lat), np.ascontiguousarray(lon)
+    scale = 1.0 if 'rad' in descriptor.units else np.pi / 180.0
+    shape = np.shape(descriptor.lat)
+    want = (shape[0] + 1, shape[1] + 1) if len(shape) == 2 else None
+    lat = np.asarray(descriptor.lat_corner, dtype=np.float64)
+    lon = np.asarray(descriptor.lon_corner, dtype=np.float64)
+    if want is None or lat.shape != want or lon.shape != want:
+        raise ValueError(
+            f'the corner arrays of a 2-D grid of {shape} cells must have the '
+            f'shape (ny + 1, nx + 1) = {want}, not {lat.shape} and '
+            f'{lon.shape}')
+    if not (np.isfinite(lat).all() and np.isfinite(lon).all()):
+        raise ValueError('the corner arrays of a 2-D grid must be finite')
+    lat, lon = lat * scale, lon * scale
+    if np.abs(lat).max() > 0.5 * np.pi + 1e-9:
+        raise ValueError(
+            f'corner latitudes beyond +-90 degrees: '
+            f'{np.degrees(lat.min())} .. {np.degrees(lat.max())}')
+    return np.clip(lat, -0.5 * np.pi, 0.5 * np.pi), lon
+
+
+def _grid_side(descriptor):
+    """(arrays for engine.overlap_grids, cells, Fortran-ordered dims) of one
+    side of :func:`conserve_grid`, or a ValueError naming the served pairs."""
+    if isinstance(descriptor, (LatLon2DGridDescriptor, LatLonGridDescriptor)):
+        lat, lon = grid_corners(descriptor)
+        ny, nx = lat.shape[0] - 1, lat.shape[1] - 1
+        return (lat, lon), ny * nx, [nx, ny]
+    if isinstance(descriptor, MpasCellMeshDescriptor) and \
+            getattr(descriptor, 'filename', None) is not None:
+        arrays = mesh_polygons(descriptor)
+        return arrays, len(arrays[1]), [len(arrays[1])]
+    what = type(descriptor).__name__
+    if isinstance(descriptor, MpasCellMeshDescriptor):
+        what += ' without its mesh file'
+    raise ValueError(f'{_GRID_PAIRS}; not with a {what}')
+
+
+def conserve_grid(src_descriptor, dst_descriptor, device=None, timing=None):
+    """
+    First-order conservative weights where at least one side is a grid given
+    by 2-D latitude / longitude arrays and their ``(ny + 1, nx + 1)`` corner
+    arrays (``LatLon2DGridDescriptor``), the other an MPAS cell mesh (its
+    file), a lat-lon grid or another 2-D grid; ESMF's ``destarea``
+    normalisation as in :func:`conserve_mesh_latlon`.  Grid cell ``j * nx +
+    i`` is the spherical polygon with great-circle edges through the corners
+    ``(j, i)``, ``(j, i + 1)``, ``(j + 1, i + 1)``, ``(j + 1, i)``.  The
+    overlaps come from the GPU (:func:`pyremap_amd.engine.overlap_grids`):
+    the polygons of the side with more cells (the source on a tie) are
+    clipped by those of the other, whose cells must be convex.  The maps of
+    the two directions hold the same overlap areas, transposed.
+    """
+    from pyremap_amd import engine
+    if not any(isinstance(d, LatLon2DGridDescriptor)
+               for d in (src_descriptor, dst_descriptor)):
+        raise ValueError(f'{_GRID_PAIRS}; neither side is one')
+    src, n_src, src_dims = _grid_side(src_descriptor)
+    dst, n_dst, dst_dims = _grid_side(dst_descriptor)
+    torch = engine.require_gpu()
+    if device is None:
+        device = f'cuda:{torch.cuda.current_device()}'
+
+    def dev(arrays):
+        return [torch.from_numpy(np.ascontiguousarray(a)).to(device)
+                for a in arrays]
+    src_is_a = n_src >= n_dst
+    side_a, side_b = (src, dst) if src_is_a else (dst, src)
+    row, col, A, frac_b, a_area, b_area = engine.overlap_grids(
+        dev(side_a), dev(side_b), dst_is_b=src_is_a, timing=timing)
+    row = row.cpu().numpy()
+    col = col.cpu().numpy()
+    A = A.cpu().numpy()
+    frac_b = frac_b.cpu().numpy()
+    dst_area = (b_area if src_is_a else a_area).cpu().numpy()
+    S = A / dst_area[row]
+    return MappingFile(n_src, n_dst, np.array(src_dims, dtype=np.int32),
+                       np.array(dst_dims, dtype=np.int32),
+                       (row + 1).astype(np.int32), (col + 1).astype(np.int32),
+                       S, frac_b)
+
+
 def _cell_centres(descriptor):
     """(lat, lon) in radians of every cell centre of a rectangular grid, in
     C order, and its Fortran-ordered dims."""
-    if isinstance(descriptor, LatLonGridDescriptor):
+    if isinstance(descriptor, LatLon2DGridDescriptor):
+        scale = 1.0 if 'rad' in descriptor.units else np.pi / 180.0
+        lat = np.asarray(descriptor.lat, dtype=np.float64) * scale
+        lon = np.asarray(descriptor.lon, dtype=np.float64) * scale
+    elif isinstance(descriptor, LatLonGridDescriptor):
         scale = 1.0 if 'rad' in descriptor.units else np.pi / 180.0
         lat, lon = np.meshgrid(np.asarray(descriptor.lat) * scale,
                                np.asarray(descriptor.lon) * scale,
@@ -878,10 +989,17 @@ def build_weights(src_descriptor, dst_descriptor, method='conserve'):
     between an MPAS cell mesh given by its mesh file and a lat-lon grid,
     either way (:func:`conserve_mesh_latlon`, on the GPU), and between two
     MPAS cell meshes given by their mesh files (:func:`conserve_mesh_mesh`,
-    on the GPU).
+    on the GPU), and between a 2-D lat-lon grid with its corner arrays and
+    an MPAS cell mesh, a lat-lon grid or another 2-D grid
+    (:func:`conserve_grid`, on the GPU).  ``bilinear`` / ``neareststod``
+    towards a 2-D lat-lon grid take its cell centres as points.
     """
     if method not in METHODS:
         raise ValueError(f'method {method!r}: expected one of {METHODS}')
+    if method == 'conserve' and any(
+            isinstance(d, LatLon2DGridDescriptor)
+            for d in (src_descriptor, dst_descriptor)):
+        return conserve_grid(src_descriptor, dst_descriptor)
     if method == 'conserve':
         if all(isinstance(d, MpasCellMeshDescriptor) and
                getattr(d, 'filename', None) is not None
@@ -904,6 +1022,10 @@ def build_weights(src_descriptor, dst_descriptor, method='conserve'):
     if points is not None:
         return _to_points(src_descriptor, points[0], points[1],
                           [len(points[0])], method)
+    if isinstance(dst_descriptor, LatLon2DGridDescriptor):
+        # (bilinear and neareststod: conserve went to conserve_grid)
+        lat, lon, dims = _cell_centres(dst_descriptor)
+        return _to_points(src_descriptor, lat, lon, dims, method)
     if method == 'bilinear':
         # the destination cell centres are points for the source grid
         lat, lon, dims = _cell_centres(dst_descriptor)

@@ -12,6 +12,16 @@ a sample of the same pairs (tests/test_conserve_mesh_cpu.py).
 --meshes times remap_overlap_meshes instead, between the icosahedral meshes
 n1 (clipped) and n2 (clipping), the same way.
 
+    python tools/overlap_timing.py --grids 153:arctic:10,153:latlon:0.5
+
+--grids times remap_overlap_grids between the icosahedral mesh n and a
+structured grid handed over as corner arrays -- ``arctic:d``: the Arctic
+stereographic grid 6000 x 6000 km with d km cells; ``latlon:r``: the global
+r degree lat-lon grid -- the side with more cells clipped, and in the same
+process the same grid written as a four-vertex MPAS mesh through
+remap_overlap_meshes, the two routes alternating, ``--repeat`` warm calls
+each (for latlon also remap_overlap_latlon on the same mesh and grid).
+
 One JSON line per size: cells, grid cells, candidates, entries, ms.
 """
 import argparse
@@ -33,9 +43,14 @@ def main():
     ap.add_argument('--sample', type=int, default=2000)
     ap.add_argument('--meshes', default=None,
                     help='n1:n2,... icosahedral mesh pairs (mesh <-> mesh)')
+    ap.add_argument('--grids', default=None,
+                    help='n:arctic:km or n:latlon:deg,... (mesh <-> 2-D grid)')
+    ap.add_argument('--repeat', type=int, default=5)
     args = ap.parse_args()
     if args.meshes:
         return time_meshes(args.meshes, args.sample)
+    if args.grids:
+        return time_grids(args.grids, args.sample, args.repeat)
     import torch
     from pyremap_amd import engine, synthetic
     from pyremap_amd.descriptor import get_lat_lon_descriptor
@@ -141,6 +156,116 @@ def time_meshes(pairs, sample):
             'sample_max_dS': float(err.max()),
             'sum_A_minus_4pi': float(A.sum() - 4 * np.pi),
             'mesh_gen_s': round(gen_s, 1)}), flush=True)
+
+
+def time_grids(cases, sample, repeat):
+    import torch
+    from pyremap_amd import engine, synthetic
+    from pyremap_amd.descriptor import get_lat_lon_descriptor
+    from pyremap_amd.polar import get_polar_descriptor
+    from pyremap_amd.weights import grid_corners, latlon_corners
+    from test_conserve_mesh_cpu import ccw, clip, polygon_area, unit
+    engine.require_gpu()
+    dev = 'cuda:0'
+
+    def to_dev(arrays):
+        return [torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                for a in arrays]
+    for item in cases.split(','):
+        n, kind, res = item.split(':')
+        n, res = int(n), float(res)
+        t0 = time.time()
+        m = synthetic.icosahedral_mesh(n)
+        gen_s = time.time() - t0
+        mesh = [m[k] for k in ('verticesOnCell', 'nEdgesOnCell', 'latVertex',
+                               'lonVertex')]
+        latlon = None
+        if kind == 'latlon':
+            latlon = get_lat_lon_descriptor(res, res)
+            lat, lon = grid_corners(latlon)
+        else:
+            p = get_polar_descriptor(6000.0, 6000.0, res, res,
+                                     projection='arctic')
+            lat, lon = p.project_to_lat_lon(*np.meshgrid(p.x_corner,
+                                                         p.y_corner))
+            lat, lon = np.radians(lat), np.radians(lon)
+        ny, nx = lat.shape[0] - 1, lat.shape[1] - 1
+        j, i = (x.reshape(-1) for x in np.meshgrid(
+            np.arange(ny), np.arange(nx), indexing='ij'))
+        corners = np.stack([j * (nx + 1) + i, j * (nx + 1) + i + 1,
+                            (j + 1) * (nx + 1) + i + 1, (j + 1) * (nx + 1) + i],
+                           axis=1)
+        quad = [(corners + 1).astype(np.int32), np.full(ny * nx, 4, np.int32),
+                lat.reshape(-1), lon.reshape(-1)]
+        grid_is_a = ny * nx > len(mesh[1])
+        mesh_d, grid_d, quad_d = to_dev(mesh), to_dev((lat, lon)), to_dev(quad)
+        routes = {
+            'grids': lambda t: engine.overlap_grids(
+                *((grid_d, mesh_d) if grid_is_a else (mesh_d, grid_d)),
+                dst_is_b=True, timing=t),
+            'meshes': lambda t: engine.overlap_meshes(
+                *((quad_d, mesh_d) if grid_is_a else (mesh_d, quad_d)),
+                dst_is_b=True, timing=t)}
+        if latlon is not None:
+            lat_e, lon_e, slack = latlon_corners(latlon)
+            axes = to_dev((lat_e, lon_e))
+            routes['latlon'] = lambda t: engine.overlap_latlon(
+                *mesh_d, *axes, slack, dst_is_mesh=grid_is_a, timing=t)
+        runs = {name: [] for name in routes}
+        outs, failed = {}, {}
+        for _ in range(repeat + 1):
+            for name, call in routes.items():
+                if name in failed:
+                    continue
+                timing = {}
+                try:
+                    out = call(timing)
+                except engine.EngineError as e:
+                    failed[name] = str(e)[:200]
+                    continue
+                torch.cuda.synchronize()
+                runs[name].append(timing)
+                outs[name] = [x.cpu().numpy() for x in out[:3]] + \
+                    [out[5].cpu().numpy()]
+                del out
+        row = {'mesh_cells': int(len(mesh[1])), 'grid': f'{kind} {res}',
+               'grid_cells': int(ny * nx),
+               'clipped': 'grid' if grid_is_a else 'mesh',
+               'mesh_gen_s': round(gen_s, 1)}
+        for name, t in runs.items():
+            if name in failed:
+                row[name] = {'error': failed[name]}
+                continue
+            warm = sorted(x['ms'] for x in t[1:])
+            row[name] = {'candidates': int(t[-1]['n_pairs']),
+                         'entries': int(len(outs[name][0])),
+                         'ms_first': round(t[0]['ms'], 3),
+                         'ms_warm_min': round(warm[0], 3),
+                         'ms_warm_median': round(warm[len(warm) // 2], 3),
+                         'ms_warm_max': round(warm[-1], 3)}
+        # the numpy reference on a sample of the grid route's entries (the
+        # destination is side b; the side with more cells is clipped)
+        if 'grids' in outs:
+            dst, src, A, b_area = outs['grids']
+            rng = np.random.default_rng(0)
+            pick = rng.choice(len(dst), size=min(sample, len(dst)),
+                              replace=False)
+            xyz = unit(m['latVertex'], m['lonVertex'])
+
+            def mesh_poly(c):
+                return ccw(xyz[mesh[0][c, :mesh[1][c]] - 1])
+
+            def grid_poly(g):
+                return ccw(unit(lat.reshape(-1)[corners[g]],
+                                lon.reshape(-1)[corners[g]]))
+            ref = []
+            for k in pick:
+                a, b = (grid_poly(src[k]), mesh_poly(dst[k])) if grid_is_a \
+                    else (mesh_poly(src[k]), grid_poly(dst[k]))
+                ref.append(polygon_area(clip(a, b)))
+            err = np.abs(np.array(ref) - A[pick]) / b_area[dst[pick]]
+            row['sample_max_dS'] = float(err.max())
+        print(json.dumps(row), flush=True)
 
 
 if __name__ == '__main__':
