@@ -1063,6 +1063,66 @@ int remap_overlap_grids(const remap_overlap_side *a,
                         double *b_area_out, int64_t *n_entries_out,
                         void *stream);
 
+/*
+ * ---------------------------------------------------------------------------
+ * Nearest source point of every destination point: ESMF's `neareststod`.
+ * src_xyz (n_src, 3) and dst_xyz (n_dst, 3) are fp64, finite, C order (unit
+ * vectors for points on the sphere, but nothing assumes it).  For destination
+ * i and source j
+ *     dx = src[j].x - dst[i].x   (likewise y, z)
+ *     d2(i, j) = (dx * dx + dy * dy) + dz * dz
+ * in IEEE fp64 in that order, no contraction, and nearest_out[i] is the j
+ * (0-based) that minimises (d2(i, j), j) lexicographically: the smallest
+ * distance, and among equal d2 bit patterns the lowest source index.  Exact:
+ * the result is a pure function of the inputs, whatever their distribution
+ * (regional sources, clusters, duplicates, any numbering).
+ *
+ * The sources are sorted by a Morton code (rocPRIM radix sort), a tree of
+ * axis-aligned boxes is built over the sorted array (8 points a leaf, 4
+ * nodes a node) and walked depth first by one lane per destination point;
+ * a node is skipped only when its bound -- d2's own formula on the distance
+ * to the box, which never exceeds the d2 of a point inside -- is STRICTLY
+ * greater than the best d2 so far, so ties survive.  No atomics: two calls
+ * give identical bytes.  Everything is asynchronous on `stream`, nothing is
+ * read back; the workspace depends on (n_src, n_dst) alone.
+ *
+ *   REMAP_ERR_ARG        a NULL array, n_src < 1, n_dst < 0, n_src > 2^31 - 1
+ *   REMAP_ERR_WORKSPACE  workspace_bytes below remap_nearest_workspace()'s
+ *   n_dst == 0           REMAP_OK, nothing is launched
+ * ---------------------------------------------------------------------------
+ */
+/*
+ * Launches nothing and touches no device memory; the size of rocPRIM's sort
+ * buffer is asked of rocPRIM, which may look up the current device's
+ * properties to choose its configuration (as remap_csr_from_coo_workspace
+ * and remap_groups_workspace do): call it with the device current that
+ * remap_nearest() will run on.
+ */
+REMAP_API
+int remap_nearest_workspace(int64_t n_src, int64_t n_dst, size_t *bytes_out);
+
+/*
+ *   src_xyz, dst_xyz, nearest_out, workspace (device);  nearest_out one
+ *   int32 per destination point.
+ */
+REMAP_API
+int remap_nearest(const double *src_xyz, int64_t n_src, const double *dst_xyz,
+                  int64_t n_dst, int32_t *nearest_out, void *workspace,
+                  size_t workspace_bytes, void *stream);
+
+/*
+ * remap_nearest() for measurements: the same launches with events between
+ * the phases.  This one WAITS for the last event, then writes
+ * phase_ms_out[0..2] (host): milliseconds of keys + sort + gather, of the
+ * boxes, and of the walk.  (With n_dst == 0 the first two phases still run.)
+ */
+REMAP_API
+int remap_nearest_timed(const double *src_xyz, int64_t n_src,
+                        const double *dst_xyz, int64_t n_dst,
+                        int32_t *nearest_out, void *workspace,
+                        size_t workspace_bytes, float *phase_ms_out,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,6 +79,7 @@ EXPORTS = (
     'remap_overlap_latlon_sizes', 'remap_overlap_latlon',
     'remap_overlap_meshes_sizes', 'remap_overlap_meshes',
     'remap_overlap_grids_sizes', 'remap_overlap_grids',
+    'remap_nearest_workspace', 'remap_nearest', 'remap_nearest_timed',
 )
 
 
@@ -455,6 +456,18 @@ def load_library():
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
         ctypes.c_void_p]
+    lib.remap_nearest_workspace.restype = ctypes.c_int
+    lib.remap_nearest_workspace.argtypes = [
+        ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]
+    lib.remap_nearest.restype = ctypes.c_int
+    lib.remap_nearest.argtypes = [
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.remap_nearest_timed.restype = ctypes.c_int
+    lib.remap_nearest_timed.argtypes = [
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
     if lib.remap_abi_version() != ABI_VERSION:
         raise EngineError(
             f'{path} has ABI {lib.remap_abi_version()}, expected '
@@ -2338,3 +2351,76 @@ def overlap_grids(side_a, side_b, dst_is_b, timing=None):
         m = n_entries.value
     return (dst[:m], src[:m], A[:m], frac_b[:n_dst], a_area[:n_a],
             b_area[:n_b])
+
+
+# ---------------------------------------------------------------------------
+# nearest source point of every destination point (ESMF's neareststod)
+# ---------------------------------------------------------------------------
+
+def nearest_points(src_xyz, dst_xyz, timing=None, phases=False):
+    """
+    The index (0-based, ``int32``) of the source point nearest to every
+    destination point, through ``remap_nearest`` (``include/remap_hip.h``):
+    ``src_xyz (n_src, 3)`` and ``dst_xyz (n_dst, 3)`` are contiguous fp64
+    tensors on one HIP device, finite.  Exact: the minimum of ``d2 = (dx*dx +
+    dy*dy) + dz*dz`` in fp64 in that order, the lowest source index among
+    equal ``d2``; two calls give identical bytes.  Asynchronous on the
+    current stream.
+
+    ``timing``: a dict that receives the GPU ``ms`` of the call (events on
+    the stream).  With ``phases=True`` (measurements only: the library then
+    waits for the walk before it returns) the call goes through
+    ``remap_nearest_timed`` and the dict also receives ``sort_ms``,
+    ``pyramid_ms`` and ``walk_ms``.
+    """
+    torch = require_gpu()
+    lib = load_library()
+    for name, t in (('src_xyz', src_xyz), ('dst_xyz', dst_xyz)):
+        if not torch.is_tensor(t) or not t.is_cuda or \
+                t.dtype != torch.float64 or t.dim() != 2 or \
+                t.shape[1] != 3 or not t.is_contiguous():
+            raise ValueError(
+                f'{name}: expected a contiguous (n, 3) float64 tensor on a '
+                f'HIP device')
+    if src_xyz.device != dst_xyz.device:
+        raise ValueError(
+            f'src_xyz on {src_xyz.device}, dst_xyz on {dst_xyz.device}: '
+            f'expected one device')
+    n_src, n_dst = src_xyz.shape[0], dst_xyz.shape[0]
+    if n_src < 1:
+        raise ValueError('nearest_points needs at least one source point')
+    if phases and timing is None:
+        raise ValueError('phases=True needs a timing dict to fill')
+    dev = src_xyz.device
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        nbytes = ctypes.c_size_t()
+        _check(lib.remap_nearest_workspace(n_src, n_dst,
+                                           ctypes.byref(nbytes)),
+               'remap_nearest_workspace')
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        out = torch.empty(n_dst, dtype=torch.int32, device=dev)
+        if timing is not None:
+            t0 = torch.cuda.Event(enable_timing=True)
+            t1 = torch.cuda.Event(enable_timing=True)
+            t0.record()
+        if phases:
+            ms = (ctypes.c_float * 3)()
+            _check(lib.remap_nearest_timed(
+                _ptr(src_xyz), n_src, _ptr(dst_xyz), n_dst, _ptr(out),
+                _ptr(ws), nbytes.value, ms, stream), 'remap_nearest_timed')
+        else:
+            _check(lib.remap_nearest(
+                _ptr(src_xyz), n_src, _ptr(dst_xyz), n_dst, _ptr(out),
+                _ptr(ws), nbytes.value, stream), 'remap_nearest')
+        if timing is not None:
+            t1.record()
+            t1.synchronize()
+            timing['ms'] = t0.elapsed_time(t1)
+            if phases:
+                timing['sort_ms'], timing['pyramid_ms'], \
+                    timing['walk_ms'] = (float(v) for v in ms)
+        # the workspace's memory returns to torch's allocator, which keeps it
+        # for this stream: later work on the stream is ordered behind the walk
+        del ws
+    return out

@@ -152,8 +152,11 @@ class Remapper:
         (``LatLon2DGridDescriptor``) and an MPAS cell mesh, a lat-lon grid or
         another such grid, either way: ESMF's first-order conservative map,
         the cell overlaps clipped on the GPU.  ``bilinear`` / ``neareststod``
-        also go towards a 2-D grid (its cell centres).  The file is
-        written to
+        also go towards a 2-D grid (its cell centres).  ``neareststod`` from
+        an MPAS mesh (cells, edges or vertices) to anything is ESMF's exact
+        nearest-point search, run on the GPU
+        (:func:`pyremap_amd.weights.nearest_weights`); from a rectangular
+        grid it is the nearest centre per axis.  The file is written to
         ``map_filename`` (default name as in ``setup.py:29-42``).
         """
         from pyremap_amd.remapper.setup import _setup_remapper

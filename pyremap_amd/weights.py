@@ -21,7 +21,8 @@ axes the common methods have closed forms:
   at either pole by a node that stands for the mean of the adjacent row.
   Reproduces the outputs the reference's tests store (ESMF weights) to the
   rounding of those files.
-* ``neareststod`` -- nearest source centre per axis.
+* ``neareststod`` -- between rectangular grids, and from one towards points:
+  the nearest source centre per axis (a closed form, not ESMF's search).
 
 * ``bilinear`` FROM an MPAS mesh (its cells, edges or vertices) -- linear
   interpolation on the triangles of the dual mesh, located and weighted along
@@ -48,6 +49,14 @@ axes the common methods have closed forms:
   every grid cell the great-circle polygon of its four corners
   (``remap_overlap_grids``).  ``bilinear`` and ``neareststod`` go TOWARDS
   such a grid (its cell centres are points for the source), not from it.
+* ``neareststod`` FROM an MPAS mesh (its cells, edges or vertices, given by
+  a mesh file or by ``lat=`` / ``lon=``) towards anything
+  (:func:`nearest_weights`) -- ESMF's search: every destination point takes
+  the source point closest in 3-D Cartesian distance on the unit sphere with
+  weight 1, the lowest source index on a tie, no point left unmapped.  The
+  search is exact and runs on the GPU (``remap_nearest``,
+  ``pyremap_amd/csrc/remap_nearest.hip``); it takes plain coordinate arrays,
+  so sources of any other kind go through it when called directly.
 
 The result is a :class:`pyremap_amd.io.mapfile.MappingFile` with exactly the
 schema ESMF writes (1-based ``row``/``col``, Fortran-ordered grid dims), so it
@@ -958,6 +967,56 @@ def conserve_grid(src_descriptor, dst_descriptor, device=None, timing=None):
                        S, frac_b)
 
 
+def nearest_weights(src_lat, src_lon, dst_lat, dst_lon, src_dims, dst_dims,
+                    device=None, timing=None):
+    """
+    ESMF's ``neareststod`` between two sets of points given by latitude /
+    longitude in radians (1-D, finite): every destination point takes the
+    source point closest in 3-D Cartesian distance on the unit sphere with
+    weight 1, on a tie the lowest source index; every point is mapped
+    (``frac_b`` = 1).  The unit vectors are made here (:func:`_unit`); the
+    search is :func:`pyremap_amd.engine.nearest_points` on the GPU, exact in
+    fp64: the minimum of ``(dx*dx + dy*dy) + dz*dz`` over ALL sources.
+    ``src_dims`` / ``dst_dims``: the mapping file's Fortran-ordered grid
+    dims.  ``timing``: passed on to the engine call.
+    """
+    from pyremap_amd import engine
+    arrays = []
+    for name, a in (('src_lat', src_lat), ('src_lon', src_lon),
+                    ('dst_lat', dst_lat), ('dst_lon', dst_lon)):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.ndim != 1:
+            raise ValueError(f'{name}: expected a 1-D array, not one of '
+                             f'shape {a.shape}')
+        if not np.isfinite(a).all():
+            raise ValueError(f'{name} holds NaN or Inf: neareststod needs '
+                             f'finite coordinates')
+        arrays.append(a)
+    src_lat, src_lon, dst_lat, dst_lon = arrays
+    if src_lat.shape != src_lon.shape or dst_lat.shape != dst_lon.shape:
+        raise ValueError('latitudes and longitudes of one side differ in '
+                         'length')
+    n_a, n_b = len(src_lat), len(dst_lat)
+    if n_a < 1:
+        raise ValueError('neareststod needs at least one source point')
+    if n_a > np.iinfo(np.int32).max:
+        raise ValueError(f'{n_a} source points: the mapping file\'s col is '
+                         f'int32')
+    torch = engine.require_gpu()
+    if device is None:
+        device = f'cuda:{torch.cuda.current_device()}'
+    src = torch.from_numpy(np.ascontiguousarray(_unit(src_lat, src_lon)))
+    dst = torch.from_numpy(np.ascontiguousarray(
+        _unit(dst_lat, dst_lon).reshape(-1, 3)))
+    nearest = engine.nearest_points(src.to(device), dst.to(device),
+                                    timing=timing).cpu().numpy()
+    return MappingFile(n_a, n_b, np.asarray(src_dims, dtype=np.int32),
+                       np.asarray(dst_dims, dtype=np.int32),
+                       np.arange(1, n_b + 1, dtype=np.int32),
+                       (nearest + 1).astype(np.int32), np.ones(n_b),
+                       np.ones(n_b))
+
+
 def _cell_centres(descriptor):
     """(lat, lon) in radians of every cell centre of a rectangular grid, in
     C order, and its Fortran-ordered dims."""
@@ -993,6 +1052,10 @@ def build_weights(src_descriptor, dst_descriptor, method='conserve'):
     an MPAS cell mesh, a lat-lon grid or another 2-D grid
     (:func:`conserve_grid`, on the GPU).  ``bilinear`` / ``neareststod``
     towards a 2-D lat-lon grid take its cell centres as points.
+    ``neareststod`` from an MPAS mesh (cells, edges or vertices; its
+    coordinates are enough, no mesh file is needed) towards any destination
+    is ESMF's exact search (:func:`nearest_weights`, on the GPU); from a
+    rectangular grid it stays the nearest centre per axis.
     """
     if method not in METHODS:
         raise ValueError(f'method {method!r}: expected one of {METHODS}')
@@ -1013,6 +1076,18 @@ def build_weights(src_descriptor, dst_descriptor, method='conserve'):
                     isinstance(grid, LatLonGridDescriptor):
                 return conserve_mesh_latlon(mesh, grid, mesh_is_src)
     points = _points(dst_descriptor)
+    if isinstance(src_descriptor, MpasMeshDescriptor) and \
+            method == 'neareststod':
+        src = _points(src_descriptor)
+        if src is None:
+            raise ValueError(
+                'neareststod from an MPAS mesh needs its coordinates: give '
+                'the descriptor a mesh file or lat= / lon=, not a size alone')
+        if points is not None:
+            lat, lon, dims = points[0], points[1], [len(points[0])]
+        else:
+            lat, lon, dims = _cell_centres(dst_descriptor)
+        return nearest_weights(src[0], src[1], lat, lon, [len(src[0])], dims)
     if isinstance(src_descriptor, MpasMeshDescriptor):
         if points is not None:
             return _from_cell_mesh(src_descriptor, points[0], points[1],
