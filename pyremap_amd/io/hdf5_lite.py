@@ -8,11 +8,18 @@ Supported (HDF5 File Format Specification 3.0): superblock v0-v3; object
 headers v1 and v2 with continuation blocks; old-style groups (symbol table:
 v1 B-tree + local heap) and new-style groups (compact link messages or dense
 storage: fractal heap + v2 B-tree); datasets with compact, contiguous or
-chunked (v1 B-tree index; v4 single-chunk / implicit / fixed-array indexes)
-layout; deflate, shuffle and fletcher32 filters; fixed-point, floating-point,
-fixed and variable-length string, enum (as its integer base), object-reference
-and variable-length-sequence datatypes; attributes in the header or in dense
-storage; the global heap.  Anything else raises ``NotImplementedError`` with
+chunked (v1 B-tree index; v4 single-chunk / implicit / fixed-array /
+extensible-array indexes, the last being what a dataset with ONE unlimited
+axis gets from ``libver='latest'`` writers: header, index block, data blocks
+addressed from the index block and from super blocks -- not the paged data
+blocks beyond 131060 chunks, nor paged fixed arrays, nor the v2 B-tree index
+of datasets with several unlimited axes) layout; deflate, shuffle and
+fletcher32 filters; fixed-point, floating-point, fixed and variable-length
+string, enum (as its integer base), object-reference and
+variable-length-sequence datatypes; attributes in the header or in dense
+storage; the global heap.  ``Dataset.storage()`` tells how a dataset is laid
+out and filtered without reading it.  Anything else raises
+``NotImplementedError`` with
 the name of the feature.
 """
 import mmap
@@ -848,10 +855,38 @@ class Dataset(_Object):
                     idx = np.unravel_index(i, grid)
                     offs = tuple(int(a) * c for a, c in zip(idx, cdims))
                     chunks.append((offs, caddr, size, mask))
+            elif index == 4:                     # extensible array
+                params = tuple(mm[p:p + 5])
+                address = f.addr(p + 5)
+                grid = [-(-s // c) for s, c in zip(shape, cdims)]
+                # the array runs along the one unlimited axis: that axis
+                # varies slowest in the element order
+                axes = list(range(rank))
+                grow = [i for i, m in enumerate(self.maxshape or ())
+                        if m == (1 << (8 * f.L)) - 1]
+                if len(grow) == 1:
+                    axes.insert(0, axes.pop(grow[0]))
+                order = [grid[a] for a in axes]
+                total = int(np.prod(grid, dtype=np.int64))
+                entries = []
+                if address is not None:
+                    entries = self._extensible_array(address, params, total,
+                                                     nbytes, bool(filters))
+                for i, (caddr, size, mask) in enumerate(entries):
+                    if caddr is None:
+                        continue
+                    idx = np.unravel_index(i, order)
+                    offs = [0] * rank
+                    for a, j in zip(axes, idx):
+                        offs[a] = int(j) * cdims[a]
+                    chunks.append((tuple(offs), caddr, size, mask))
+            elif index == 5:
+                raise NotImplementedError(
+                    f'v2 B-tree chunk index (chunk index type 5: two or '
+                    f'more unlimited axes) on {self.name}')
             else:
                 raise NotImplementedError(
-                    f'chunk index type {index} (extensible array / v2 '
-                    f'B-tree) on {self.name}')
+                    f'chunk index type {index} on {self.name}')
         out = self._filled(count).reshape(shape)
         for offs, address, size, mask in chunks:
             blob = mm[address:address + size]
@@ -879,7 +914,8 @@ class Dataset(_Object):
         p = data + 6 + f.O
         page = 1 << page_bits
         if nent > page:
-            raise NotImplementedError('paged fixed-array chunk index')
+            raise NotImplementedError(
+                f'paged fixed-array chunk index on {self.name}')
         out = []
         for i in range(min(nent, total)):
             q = p + i * entry_size
@@ -892,6 +928,121 @@ class Dataset(_Object):
                 size, mask = nbytes, 0
             out.append((caddr, size, mask))
         return out
+
+    def _extensible_array(self, address, params, total, nbytes, filtered):
+        """
+        The first ``total`` elements ``(chunk address or None, stored bytes,
+        filter mask)`` of an extensible-array chunk index (layout version 4,
+        index type 4; HDF5 File Format Specification 3.0, VII.D).  Elements
+        0 .. n-1 sit in the index block itself; the rest in data blocks that
+        double in size every second "super block": the data blocks of the
+        first few super blocks are addressed from the index block, those of
+        the later ones from a super block of their own.
+        """
+        f = self.file
+        O, L = f.O, f.L
+        f._check(address, b'EAHD', 'extensible array header')
+        client = f.mm[address + 5]
+        esize = f.mm[address + 6]
+        max_bits, n_index, dblk_min, sblk_min_ptrs, page_bits = \
+            tuple(f.mm[address + 7:address + 12])
+        if (max_bits, n_index, sblk_min_ptrs, dblk_min, page_bits) != \
+                tuple(params) or client != (1 if filtered else 0):
+            raise ValueError(f'{f.filename}: extensible array header of '
+                             f'{self.name} disagrees with its layout '
+                             f'message')
+        iblock = f.addr(address + 12 + 6 * L)
+        if iblock is None:
+            return []
+        off_size = (max_bits + 7) // 8
+        out = []
+
+        def elements(p, n):
+            for i in range(min(n, total - len(out))):
+                q = p + i * esize
+                caddr = f.addr(q)
+                if filtered:
+                    w = esize - O - 4
+                    out.append((caddr, f.uint(q + O, w),
+                                f.uint(q + O + w, 4)))
+                else:
+                    out.append((caddr, nbytes, 0))
+
+        def data_block(addr, n):
+            if n > (1 << page_bits):
+                raise NotImplementedError(
+                    f'paged extensible-array data block (a chunk index of '
+                    f'more than {len(out)} chunks) on {self.name}')
+            if addr is None:
+                for _ in range(min(n, total - len(out))):
+                    out.append((None, 0, 0))
+                return
+            f._check(addr, b'EADB', 'extensible array data block')
+            if f.addr(addr + 6) != address:
+                raise ValueError(f'{f.filename}: extensible array data '
+                                 f'block at {addr:#x} belongs to another '
+                                 f'array')
+            elements(addr + 6 + O + off_size, n)
+
+        f._check(iblock, b'EAIB', 'extensible array index block')
+        p = iblock + 6 + O
+        elements(p, n_index)
+        p += n_index * esize
+        # super block s: 2^(s//2) data blocks of 2^((s+1)//2) * dblk_min
+        # elements; the first 2*log2(sblk_min_ptrs) of them have no block
+        # of their own, their data blocks hang off the index block
+        n_super = 1 + max_bits - (dblk_min.bit_length() - 1)
+        direct = 2 * (sblk_min_ptrs.bit_length() - 1)
+        s = 0
+        while len(out) < total and s < n_super:
+            ndblks = 1 << (s // 2)
+            nelmts = (1 << ((s + 1) // 2)) * dblk_min
+            if s < direct:
+                for _ in range(ndblks):
+                    if len(out) < total:
+                        data_block(f.addr(p), nelmts)
+                    p += O
+            else:
+                sblock = f.addr(p)
+                p += O
+                if sblock is None:
+                    for _ in range(min(ndblks * nelmts, total - len(out))):
+                        out.append((None, 0, 0))
+                else:
+                    f._check(sblock, b'EASB',
+                             'extensible array super block')
+                    # (no page bitmaps before the addresses: data_block
+                    # refuses paged blocks)
+                    q = sblock + 6 + O + off_size
+                    for i in range(ndblks):
+                        if len(out) < total:
+                            data_block(f.addr(q + i * O), nelmts)
+            s += 1
+        return out
+
+    def storage(self):
+        """
+        How the values are stored: ``{'layout': 'compact' | 'contiguous' |
+        'chunked', 'chunks': shape or None, 'filters': [(id, client
+        values)]}`` (no data is read).
+        """
+        f = self.file
+        mm = f.mm
+        pos, _ = self._find(MSG_LAYOUT)
+        version, cls = mm[pos], mm[pos + 1]
+        chunks = None
+        if cls == 2 and version == 3:
+            rank = mm[pos + 2] - 1
+            chunks = tuple(f.uint(pos + 3 + f.O + 4 * i, 4)
+                           for i in range(rank))
+        elif cls == 2 and version >= 4:
+            rank = mm[pos + 3] - 1
+            enc = mm[pos + 4]
+            chunks = tuple(f.uint(pos + 5 + enc * i, enc)
+                           for i in range(rank))
+        return {'layout': {0: 'compact', 1: 'contiguous',
+                           2: 'chunked'}.get(cls, f'class {cls}'),
+                'chunks': chunks, 'filters': self._filters()}
 
     def _filled(self, count):
         typ = self.type

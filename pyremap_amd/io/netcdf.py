@@ -185,6 +185,7 @@ def _open_hdf5(filename, mask_and_scale, variables=None, lazy_bytes=None):
                     OrderedDict(var.attrs),
                     lambda n=name: _read_hdf5_variable(filename, n),
                     mask_and_scale)
+                enc.update(var.encoding)
                 ds[name] = da
                 ds.variables[name].encoding = enc
                 continue
@@ -195,6 +196,8 @@ def _open_hdf5(filename, mask_and_scale, variables=None, lazy_bytes=None):
             attrs, enc = OrderedDict(var.attrs), {}
             if mask_and_scale:
                 data, attrs, enc = _decode(data, attrs)
+            # how the file stores it, under xarray's names
+            enc.update(var.encoding)
             da = xr_lite.DataArray(data, dims=var.dims, name=name,
                                    attrs=attrs)
             da.encoding = enc
@@ -207,14 +210,23 @@ def _open_hdf5(filename, mask_and_scale, variables=None, lazy_bytes=None):
 
 
 def write_netcdf(ds, filename, format='NETCDF3_64BIT', fillvalues=None,
-                 unlimited_dims=None):
+                 unlimited_dims=None, encoding=None):
     """
     Write a Dataset with netCDF4-style fill values (reference
     ``utility.write_netcdf``): numeric variables holding NaNs get
     ``_FillValue`` = the default fill of their dtype and have their NaNs
     stored as that value; all other variables get no ``_FillValue``.
+
+    ``encoding`` (NetCDF-4 only): variable name -> ``{'zlib', 'complevel',
+    'shuffle', 'chunksizes'}`` as xarray spells them.  Nothing is taken from
+    the variables' own ``.encoding``: without this argument no variable is
+    compressed, and only those along an unlimited dimension are chunked.
     """
     nc4 = format in ('NETCDF4', 'NETCDF4_CLASSIC')
+    if encoding and not nc4:
+        raise ValueError(
+            f'encoding (compression, chunking) needs a NetCDF-4 format: '
+            f'{format!r} stores variables contiguously and unfiltered')
     if not nc4 and format not in netcdf3.FORMATS:
         raise NotImplementedError(
             f'format {format!r}: expected NETCDF4, NETCDF4_CLASSIC or one '
@@ -309,7 +321,8 @@ def write_netcdf(ds, filename, format='NETCDF3_64BIT', fillvalues=None,
                       nan_fill={v.name: v.nan_fill for v in out_vars
                                 if v.nan_fill is not None},
                       auto_fill={v.name: v.auto_fill for v in out_vars
-                                 if v.auto_fill is not None})
+                                 if v.auto_fill is not None},
+                      encoding=encoding)
         return
     netcdf3.write(filename, dimensions, out_vars, attrs=attrs,
                   version=version)

@@ -61,6 +61,19 @@ class Variable:
     def read(self):
         return self._dataset.read()
 
+    @property
+    def encoding(self):
+        """How the variable is stored, under xarray's names: ``contiguous``,
+        ``chunksizes``, ``zlib``, ``complevel``, ``shuffle``."""
+        store = self._dataset.storage()
+        filters = dict((fid, cd) for fid, cd in store['filters'])
+        deflate = filters.get(1)
+        return {'contiguous': store['layout'] != 'chunked',
+                'chunksizes': store['chunks'],
+                'zlib': deflate is not None,
+                'complevel': int(deflate[0]) if deflate else 0,
+                'shuffle': 2 in filters}
+
 
 class NetCDF4File:
     """``dimensions`` (name -> size), ``unlimited`` (names), ``variables``

@@ -70,6 +70,13 @@ def _remap_file(remapper, in_filename, out_filename, variable_list,
             raise ValueError(f'variables {missing} are not in {in_filename}')
         ds = ds.drop_vars([v for v in ds.data_vars
                            if v not in variable_list])
+    in_filters = {}
+    for name, var in ds.variables.items():
+        enc = getattr(var, 'encoding', None) or {}
+        if enc.get('zlib') or enc.get('shuffle'):
+            in_filters[name] = {'zlib': bool(enc.get('zlib')),
+                                'complevel': int(enc.get('complevel', 0)),
+                                'shuffle': bool(enc.get('shuffle'))}
     if replace_mpas_fill and isinstance(remapper.src_descriptor,
                                         MpasMeshDescriptor):
         # `ncremap -P mpas` without -C: MPAS's missing value gets the role
@@ -107,8 +114,14 @@ def _remap_file(remapper, in_filename, out_filename, variable_list,
         fmt = 'NETCDF3_64BIT_DATA'
     if group is not None and remapper._matrix.rank != group[1]:
         return                       # rank `src` writes
+    # as NCO does: the record dimensions stay record dimensions, and every
+    # variable keeps the deflate level and shuffle flag it came with (not
+    # the chunk shape: a remapped variable has another shape)
+    filters = {name: enc for name, enc in in_filters.items()
+               if name in ds_out.variables} if fmt == 'NETCDF4' else {}
     write_netcdf(ds_out, out_filename, format=fmt,
-                 unlimited_dims=encoding.get('unlimited_dims', []))
+                 unlimited_dims=encoding.get('unlimited_dims', []),
+                 encoding=filters or None)
     if logger is not None:
         logger.info(f'remapped {in_filename} -> {out_filename} with '
                     f'{remapper.map_filename} ({len(list(ds_out.data_vars))} '
