@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define REMAP_ABI_VERSION 25
+#define REMAP_ABI_VERSION 26
 
 /* The library is built with -fvisibility=hidden: the entry points declared
  * here, and nothing else, are its dynamic symbols. */
@@ -1122,6 +1122,77 @@ int remap_nearest_timed(const double *src_xyz, int64_t n_src,
                         int32_t *nearest_out, void *workspace,
                         size_t workspace_bytes, float *phase_ms_out,
                         void *stream);
+
+/*
+ * ---------------------------------------------------------------------------
+ * Point location in spherical triangles: the search behind `bilinear` maps
+ * from an MPAS mesh (the triangles of its dual mesh).  xyz (n_nodes, 3) fp64,
+ * tri (n_tri, 3) int32 node ids (0-based), points (n_pts, 3) fp64, all C
+ * order; nodes and points are unit vectors to within 1e-6; tol >= 0.  With
+ *     cross(u, v) = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x)
+ *     dot(u, v)   = (u.x*v.x + u.y*v.y) + u.z*v.z
+ * in IEEE fp64 in that order, no contraction, for the triangle t = (a, b, c)
+ * and the point q
+ *     D = dot(a, cross(b, c)),  s = -1 if D < 0, else +1
+ *     w0 = s*dot(q, cross(b, c)),  w1 = s*dot(q, cross(c, a)),
+ *     w2 = s*dot(q, cross(a, b)),  tot = (w0 + w1) + w2
+ *     holds(q, t)  iff  tot > 0 and every w_k >= -tol*tot
+ * A triangle with D == 0, D not finite or a node id outside [0, n_nodes)
+ * holds nothing and is never dereferenced.  found_out[q] is the LOWEST t that
+ * holds q, or -1; weights_out[q] are the winner's S_k = v_k / ((v0 + v1) +
+ * v2) with v_k = w_k > 0 ? w_k : 0.0, zeros where found_out[q] is -1.  Exact:
+ * a pure function of the inputs, whatever the triangles' orientation, order
+ * or sizes (a variable-resolution mesh, overlapping triangles, duplicates).
+ *
+ * The triangles are sorted by the Morton code of their centroids (rocPRIM
+ * radix sort), a tree of axis-aligned boxes is built over the sorted array
+ * (8 triangles a leaf, 4 nodes a node) and walked depth first by one lane
+ * per point.  A triangle's box is the box of its corners widened by a margin
+ * of its own that covers the sphere's bulge over the flat triangle, the 1e-6
+ * and tol (pyremap_amd/csrc/remap_locate.hip has the derivation): a triangle
+ * is skipped only where holds() rejects the point.  No atomics: two calls
+ * give identical bytes.  Everything is asynchronous on `stream`, nothing is
+ * read back; the workspace depends on (n_nodes, n_tri, n_pts) alone.  Inputs
+ * outside the unit-vector contract give an unspecified result; the call
+ * still ends and stays inside its arrays.
+ *
+ *   REMAP_ERR_ARG        a NULL array, n_nodes < 1, n_tri < 1, n_tri >
+ *                        2^31 - 1, n_pts < 0, tol < 0 or NaN
+ *   REMAP_ERR_WORKSPACE  workspace_bytes below remap_locate_workspace()'s
+ *   n_pts == 0           REMAP_OK, nothing is launched
+ * ---------------------------------------------------------------------------
+ */
+/*
+ * Launches nothing and touches no device memory (rocPRIM is asked for its
+ * sort buffer, as in remap_nearest_workspace: call it with the device current
+ * that remap_locate() will run on).
+ */
+REMAP_API
+int remap_locate_workspace(int64_t n_nodes, int64_t n_tri, int64_t n_pts,
+                           size_t *bytes_out);
+
+/*
+ *   xyz, tri, points, found_out, weights_out, workspace (device);  found_out
+ *   one int32 and weights_out three doubles per point.
+ */
+REMAP_API
+int remap_locate(const double *xyz, int64_t n_nodes, const int32_t *tri,
+                 int64_t n_tri, const double *points, int64_t n_pts,
+                 double tol, int32_t *found_out, double *weights_out,
+                 void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * remap_locate() for measurements: the same launches with events between the
+ * phases.  This one WAITS for the last event, then writes phase_ms_out[0..2]
+ * (host): milliseconds of keys + sort, of normals + boxes, and of the walk.
+ * (With n_pts == 0 the first two phases still run.)
+ */
+REMAP_API
+int remap_locate_timed(const double *xyz, int64_t n_nodes, const int32_t *tri,
+                       int64_t n_tri, const double *points, int64_t n_pts,
+                       double tol, int32_t *found_out, double *weights_out,
+                       void *workspace, size_t workspace_bytes,
+                       float *phase_ms_out, void *stream);
 
 #ifdef __cplusplus
 }

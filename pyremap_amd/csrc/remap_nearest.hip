@@ -51,23 +51,18 @@
 #include <rocprim/rocprim.hpp>
 
 #include "remap_common.h"
+#include "remap_tree.h"
 
 namespace remap {
 namespace {
 
-constexpr size_t kAlign = 256;
-constexpr int kLeaf = 8;       // sorted points a leaf
-constexpr int kFan = 4;        // nodes below a node
 constexpr int kWalkBlock = 64;
-// n_src <= 2^31 - 1: 2^28 leaves, a quarter as many nodes a level above
-constexpr int kMaxLevels = 15;
+// (kLeaf sorted points a leaf, kFan nodes below a node: remap_tree.h)
 // the walk steps into one child and stacks at most kFan - 1 a level above
 // level 0, so that bounds the stack whatever the points are.  The launch
 // sizes the LDS by the tree at hand (8 bytes an entry and lane): the fewer
 // levels, the more walking waves fit beside each other in a CU
 constexpr int stack_depth(int levels) { return (kFan - 1) * (levels - 1); }
-constexpr uint32_t kNodeBits = 28;
-constexpr uint32_t kNodeMask = (1u << kNodeBits) - 1u;
 constexpr uint32_t kNone = 0xffffffffu;   // no node (levels end at 14)
 // one walk launch: its block count stays far below the grid limit
 constexpr int64_t kWalkChunk = int64_t(1) << 30;
@@ -75,15 +70,6 @@ constexpr int64_t kWalkChunk = int64_t(1) << 30;
 static_assert(kFan == 4, "nearest_walk sorts four children by hand");
 static_assert(stack_depth(kMaxLevels) * kWalkBlock * 8 <= 64 * 1024,
               "the walk's stack must fit in a workgroup's LDS");
-
-size_t align_up(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
-
-// level l holds count[l] nodes, its boxes (6 doubles each) from node first[l]
-struct Tree {
-    int32_t levels;
-    int64_t count[kMaxLevels];
-    int64_t first[kMaxLevels];
-};
 
 struct Layout {
     Tree tree;
@@ -94,20 +80,7 @@ struct Layout {
 int make_layout(int64_t n_src, Layout *lay)
 {
     const size_t n = static_cast<size_t>(n_src);
-    Tree &t = lay->tree;
-    int64_t c = (n_src + kLeaf - 1) / kLeaf, nodes = 0;
-    t.levels = 0;
-    for (;;) {
-        t.count[t.levels] = c;
-        t.first[t.levels] = nodes;
-        nodes += c;
-        ++t.levels;
-        if (c == 1)
-            break;
-        c = (c + kFan - 1) / kFan;
-    }
-    for (int l = t.levels; l < kMaxLevels; ++l)
-        t.count[l] = t.first[l] = 0;
+    const int64_t nodes = make_tree(n_src, &lay->tree);
     size_t sort_bytes = 0;
     REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
         nullptr, sort_bytes, static_cast<const uint64_t *>(nullptr),
@@ -127,26 +100,6 @@ int make_layout(int64_t n_src, Layout *lay)
     return REMAP_OK;
 }
 
-// every third bit of the result holds a bit of v (21 of them)
-__device__ inline uint64_t spread3(uint64_t v)
-{
-    v &= 0x1fffffull;
-    v = (v | v << 32) & 0x1f00000000ffffull;
-    v = (v | v << 16) & 0x1f0000ff0000ffull;
-    v = (v | v << 8) & 0x100f00f00f00f00full;
-    v = (v | v << 4) & 0x10c30c30c30c30c3ull;
-    v = (v | v << 2) & 0x1249249249249249ull;
-    return v;
-}
-
-__device__ inline uint64_t quantise(double x)
-{
-    const double q = (x + 1.0) * 1048576.0;   // [-1, 1] -> [0, 2^21]
-    if (!(q > 0.0))
-        return 0;
-    return q >= 2097151.0 ? 2097151ull : static_cast<uint64_t>(q);
-}
-
 __global__ __launch_bounds__(kBlock) void morton_keys(
     int64_t n, const double *__restrict__ xyz, uint64_t *__restrict__ keys,
     uint32_t *__restrict__ idx)
@@ -154,9 +107,7 @@ __global__ __launch_bounds__(kBlock) void morton_keys(
     const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (k >= n)
         return;
-    keys[k] = spread3(quantise(xyz[3 * k])) << 2 |
-              spread3(quantise(xyz[3 * k + 1])) << 1 |
-              spread3(quantise(xyz[3 * k + 2]));
+    keys[k] = morton_key(xyz[3 * k], xyz[3 * k + 1], xyz[3 * k + 2]);
     idx[k] = static_cast<uint32_t>(k);
 }
 
@@ -203,33 +154,7 @@ __global__ __launch_bounds__(kBlock) void leaf_boxes(
     }
 }
 
-// one lane per node of a level >= 1, the level below it complete
-__global__ __launch_bounds__(kBlock) void upper_boxes(
-    int64_t n_nodes, int64_t n_below, const double *__restrict__ below,
-    double *__restrict__ boxes)
-{
-    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (k >= n_nodes)
-        return;
-    const int64_t c0 = k * kFan;
-    const int64_t c1 = c0 + kFan < n_below ? c0 + kFan : n_below;
-    double b[6];
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-        b[a] = below[c0 * 6 + a];
-    for (int64_t c = c0 + 1; c < c1; ++c) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double l = below[c * 6 + a], h = below[c * 6 + 3 + a];
-            b[a] = l < b[a] ? l : b[a];
-            b[3 + a] = h > b[3 + a] ? h : b[3 + a];
-        }
-    }
-    double *o = boxes + k * 6;
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-        o[a] = b[a];
-}
+// (upper_boxes, a node's box over its kFan children: remap_tree.h)
 
 // the least d2 any point inside the box can have (see the file's head)
 __device__ inline double box_bound(const double *__restrict__ b, double px,
@@ -356,11 +281,6 @@ __global__ __launch_bounds__(kWalkBlock) void nearest_walk(
         }
     }
     nearest[w] = static_cast<int32_t>(best_i);
-}
-
-uint32_t blocks(int64_t n, int per)
-{
-    return static_cast<uint32_t>((n + per - 1) / per);
 }
 
 int check_args(const double *src_xyz, int64_t n_src, const double *dst_xyz,

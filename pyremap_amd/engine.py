@@ -51,7 +51,7 @@ CELL_MAX_RUN = 4
 DTYPE_F64 = 0
 DTYPE_F32 = 1
 
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 #: readable pad entries kept behind col/val (remap_csr.csr_pad)
 CSR_PAD = 8
@@ -80,6 +80,7 @@ EXPORTS = (
     'remap_overlap_meshes_sizes', 'remap_overlap_meshes',
     'remap_overlap_grids_sizes', 'remap_overlap_grids',
     'remap_nearest_workspace', 'remap_nearest', 'remap_nearest_timed',
+    'remap_locate_workspace', 'remap_locate', 'remap_locate_timed',
 )
 
 
@@ -466,6 +467,21 @@ def load_library():
     lib.remap_nearest_timed.restype = ctypes.c_int
     lib.remap_nearest_timed.argtypes = [
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
+    lib.remap_locate_workspace.restype = ctypes.c_int
+    lib.remap_locate_workspace.argtypes = [
+        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+        ctypes.POINTER(ctypes.c_size_t)]
+    lib.remap_locate.restype = ctypes.c_int
+    lib.remap_locate.argtypes = [
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.remap_locate_timed.restype = ctypes.c_int
+    lib.remap_locate_timed.argtypes = [
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
         ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
     if lib.remap_abi_version() != ABI_VERSION:
@@ -2424,3 +2440,89 @@ def nearest_points(src_xyz, dst_xyz, timing=None, phases=False):
         # for this stream: later work on the stream is ordered behind the walk
         del ws
     return out
+
+
+# ---------------------------------------------------------------------------
+# the triangle that holds every point (bilinear from an MPAS mesh)
+# ---------------------------------------------------------------------------
+
+def locate_in_triangles(xyz, tri, points, tol=1e-12, timing=None,
+                        phases=False):
+    """
+    For every point the lowest-numbered spherical triangle that holds it and
+    the weights of its three corners, through ``remap_locate``
+    (``include/remap_hip.h`` has the definition): ``xyz (n_nodes, 3)`` and
+    ``points (n_pts, 3)`` are contiguous fp64 tensors, ``tri (n_tri, 3)`` a
+    contiguous int32 tensor of node ids, all on one HIP device; nodes and
+    points are unit vectors.  Returns ``(found int32 (n_pts,), weights fp64
+    (n_pts, 3))`` on that device: ``found`` is -1, and the weights zero, where
+    no triangle holds the point.  Exact in fp64 (the barycentric coordinates
+    of the point's central projection, a corner accepted down to ``-tol``);
+    two calls give identical bytes.  Asynchronous on the current stream.
+
+    ``timing``: a dict that receives the GPU ``ms`` of the call (events on
+    the stream).  With ``phases=True`` (measurements only: the library then
+    waits for the walk before it returns) the call goes through
+    ``remap_locate_timed`` and the dict also receives ``sort_ms``,
+    ``setup_ms`` and ``walk_ms``.
+    """
+    torch = require_gpu()
+    lib = load_library()
+    for name, t, dtype in (('xyz', xyz, torch.float64),
+                           ('tri', tri, torch.int32),
+                           ('points', points, torch.float64)):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or \
+                t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
+            kind = 'int32' if dtype == torch.int32 else 'float64'
+            raise ValueError(
+                f'{name}: expected a contiguous (n, 3) {kind} tensor on a '
+                f'HIP device')
+    if not (xyz.device == tri.device == points.device):
+        raise ValueError(
+            f'xyz on {xyz.device}, tri on {tri.device}, points on '
+            f'{points.device}: expected one device')
+    n_nodes, n_tri, n_pts = xyz.shape[0], tri.shape[0], points.shape[0]
+    if n_tri < 1 or n_nodes < 1:
+        raise ValueError('locate_in_triangles needs at least one triangle '
+                         'and one node')
+    tol = float(tol)
+    if not tol >= 0.0:
+        raise ValueError(f'tol {tol}: expected a number >= 0')
+    if phases and timing is None:
+        raise ValueError('phases=True needs a timing dict to fill')
+    dev = xyz.device
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        nbytes = ctypes.c_size_t()
+        _check(lib.remap_locate_workspace(n_nodes, n_tri, n_pts,
+                                          ctypes.byref(nbytes)),
+               'remap_locate_workspace')
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        found = torch.empty(n_pts, dtype=torch.int32, device=dev)
+        weights = torch.empty((n_pts, 3), dtype=torch.float64, device=dev)
+        if timing is not None:
+            t0 = torch.cuda.Event(enable_timing=True)
+            t1 = torch.cuda.Event(enable_timing=True)
+            t0.record()
+        if phases:
+            ms = (ctypes.c_float * 3)()
+            _check(lib.remap_locate_timed(
+                _ptr(xyz), n_nodes, _ptr(tri), n_tri, _ptr(points), n_pts,
+                tol, _ptr(found), _ptr(weights), _ptr(ws), nbytes.value, ms,
+                stream), 'remap_locate_timed')
+        else:
+            _check(lib.remap_locate(
+                _ptr(xyz), n_nodes, _ptr(tri), n_tri, _ptr(points), n_pts,
+                tol, _ptr(found), _ptr(weights), _ptr(ws), nbytes.value,
+                stream), 'remap_locate')
+        if timing is not None:
+            t1.record()
+            t1.synchronize()
+            timing['ms'] = t0.elapsed_time(t1)
+            if phases:
+                timing['sort_ms'], timing['setup_ms'], \
+                    timing['walk_ms'] = (float(v) for v in ms)
+        # (as in nearest_points: torch's allocator keeps the workspace for
+        # this stream, so later work is ordered behind the walk)
+        del ws
+    return found, weights

@@ -144,8 +144,10 @@ class Remapper:
         form: ``conserve`` / ``bilinear`` / ``neareststod`` between two
         lat-lon grids, or two grids of one projection, and ``bilinear`` from
         an MPAS mesh (cells, edges or vertices, given by its mesh file) to
-        anything -- ESMF's weights, reproduced (:mod:`pyremap_amd.weights`) --
-        and ``conserve`` between an MPAS cell mesh (given by its mesh file)
+        anything -- ESMF's weights, reproduced (:mod:`pyremap_amd.weights`;
+        the triangle that holds each destination point is searched on the GPU
+        where one is present,
+        :func:`pyremap_amd.weights.bilinear_mesh_weights`) -- and ``conserve`` between an MPAS cell mesh (given by its mesh file)
         and a lat-lon grid, either way, or between two MPAS cell meshes
         (``src_from_mpas`` / ``dst_from_mpas``), and between a grid given by
         2-D latitude / longitude arrays with their corners

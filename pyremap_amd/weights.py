@@ -30,7 +30,11 @@ axes the common methods have closed forms:
   rule (:func:`clip_ears`): reproduces the outputs the reference's tests store
   for ``test_mpas_{cell,edge,vertex}_to_latlon`` and
   ``test_mpas_cell_to_stereographic`` to rounding, the unmapped cells
-  included.
+  included.  Where a GPU is present the triangles are searched there
+  (:func:`bilinear_mesh_weights`: ``remap_locate``,
+  ``pyremap_amd/csrc/remap_locate.hip``, the lowest-numbered triangle that
+  holds the point, exact in fp64); without one the numpy search
+  (:func:`locate_in_triangles`) does the same on the host.
 * ``conserve`` between an MPAS cell mesh (given by its mesh file) and a
   lat-lon grid, either way (:func:`conserve_mesh_latlon`) -- ESMF's
   first-order conservative map: every cell a spherical polygon with
@@ -495,8 +499,26 @@ def _from_cell_mesh(src_descriptor, plat, plon, dst_dims, method):
             f'from an MPAS mesh only bilinear has a closed form here, not '
             f'{method!r} (conservative weights need polygon clipping: ESMF / '
             f'MOAB)')
+    if _gpu_present():
+        return bilinear_mesh_weights(src_descriptor, plat, plon, dst_dims)
     xyz, tri = _dual_triangles(src_descriptor)
     found, w = locate_in_triangles(xyz, tri, _unit(plat, plon))
+    return _triangle_mapping(xyz, tri, found, w, len(plat), dst_dims)
+
+
+def _gpu_present():
+    """Whether a HIP device is visible (the library is then required: with a
+    device and no library the engine call raises, it does not fall back)."""
+    try:
+        import torch
+    except ImportError:
+        return False
+    return torch.cuda.is_available()
+
+
+def _triangle_mapping(xyz, tri, found, w, n_b, dst_dims):
+    """The mapping file of a point location: three entries per mapped point,
+    sorted by (row, col); ``frac_b`` 1 where a triangle holds the point."""
     hit = np.nonzero(found >= 0)[0]
     row = np.repeat(hit, 3)
     col = tri[found[hit]].reshape(-1)
@@ -504,10 +526,48 @@ def _from_cell_mesh(src_descriptor, plat, plon, dst_dims, method):
     order = np.lexsort((col, row))
     frac_b = (found >= 0).astype(np.float64)
     return MappingFile(
-        len(xyz), len(plat), np.array([len(xyz)], dtype=np.int32),
+        len(xyz), n_b, np.array([len(xyz)], dtype=np.int32),
         np.asarray(dst_dims, dtype=np.int32),
         (row[order] + 1).astype(np.int32), (col[order] + 1).astype(np.int32),
         S[order], frac_b)
+
+
+def bilinear_mesh_weights(src_descriptor, plat, plon, dst_dims, device=None,
+                          timing=None):
+    """
+    ``bilinear`` from the cells, edges or vertices of an MPAS mesh (given by
+    its mesh file) towards the points ``plat`` / ``plon`` (radians, 1-D),
+    located on the GPU: the triangles of the dual mesh
+    (:func:`_dual_triangles`), then
+    :func:`pyremap_amd.engine.locate_in_triangles` -- every point takes the
+    lowest-numbered triangle that holds its central projection and the
+    barycentric weights of its corners, exact in fp64 -- then the same
+    mapping file :func:`locate_in_triangles` leads to on the host: three
+    entries per mapped point, points no triangle holds unmapped with
+    ``frac_b`` = 0.  ``dst_dims``: the mapping file's Fortran-ordered grid
+    dims.  ``timing``: passed on to the engine call.
+    """
+    from pyremap_amd import engine
+    xyz, tri = _dual_triangles(src_descriptor)
+    if len(tri) < 1:
+        raise ValueError('the mesh has no complete dual triangle: nothing '
+                         'to interpolate on')
+    if len(xyz) > np.iinfo(np.int32).max:
+        raise ValueError(f'{len(xyz)} source points: the mapping file\'s '
+                         f'col is int32')
+    plat = np.ascontiguousarray(plat, dtype=np.float64).reshape(-1)
+    plon = np.ascontiguousarray(plon, dtype=np.float64).reshape(-1)
+    torch = engine.require_gpu()
+    if device is None:
+        device = f'cuda:{torch.cuda.current_device()}'
+    found, w = engine.locate_in_triangles(
+        torch.from_numpy(np.ascontiguousarray(xyz)).to(device),
+        torch.from_numpy(np.ascontiguousarray(tri, dtype=np.int32))
+        .to(device),
+        torch.from_numpy(np.ascontiguousarray(_unit(plat, plon))).to(device),
+        timing=timing)
+    return _triangle_mapping(xyz, tri, found.cpu().numpy(), w.cpu().numpy(),
+                             len(plat), dst_dims)
 
 
 
@@ -1055,7 +1115,10 @@ def build_weights(src_descriptor, dst_descriptor, method='conserve'):
     ``neareststod`` from an MPAS mesh (cells, edges or vertices; its
     coordinates are enough, no mesh file is needed) towards any destination
     is ESMF's exact search (:func:`nearest_weights`, on the GPU); from a
-    rectangular grid it stays the nearest centre per axis.
+    rectangular grid it stays the nearest centre per axis.  ``bilinear``
+    from an MPAS mesh (given by its mesh file) locates the destination
+    points in the triangles of the dual mesh on the GPU where one is present
+    (:func:`bilinear_mesh_weights`), with numpy on the host otherwise.
     """
     if method not in METHODS:
         raise ValueError(f'method {method!r}: expected one of {METHODS}')
