@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define REMAP_ABI_VERSION 26
+#define REMAP_ABI_VERSION 27
 
 /* The library is built with -fvisibility=hidden: the entry points declared
  * here, and nothing else, are its dynamic symbols. */
@@ -1193,6 +1193,89 @@ int remap_locate_timed(const double *xyz, int64_t n_nodes, const int32_t *tri,
                        double tol, int32_t *found_out, double *weights_out,
                        void *workspace, size_t workspace_bytes,
                        float *phase_ms_out, void *stream);
+
+/*
+ * ---------------------------------------------------------------------------
+ * Point location in the quads between four neighbouring cell centres: the
+ * search behind `bilinear` maps from a grid given by 2-D latitude /
+ * longitude arrays.  nodes (ny, nx, 3) fp64 unit vectors of the centres (C
+ * order), ny >= 2, nx >= 2; periodic 0 or 1 (with 1 column nx-1 closes onto
+ * column 0); points (n_pts, 3) fp64; nodes and points are unit vectors to
+ * within 1e-6; tol >= 0.  nqx = nx - 1 + periodic, and quad k = j*nqx + i has
+ * the corners p0 = (j, i), p1 = (j, i1), p2 = (j+1, i1), p3 = (j+1, i),
+ * i1 = (i+1) % nx.  With cross and dot as above, in IEEE fp64 in that order,
+ * no contraction, component by component
+ *     c0 = 0.25*(((p0+p1)+p2)+p3)      c1 = 0.25*(((p1-p0)+p2)-p3)
+ *     c2 = 0.25*(((p2-p0)-p1)+p3)      c3 = 0.25*(((p0-p1)+p2)-p3)
+ * and Newton on c0 + s*c1 + t*c2 + s*t*c3 = r*q from s = t = 0, r = 1, at
+ * most 12 steps, each
+ *     F = (((c0 + s*c1) + t*c2) + (s*t)*c3) - r*q
+ *     a = c1 + t*c3,  b = c2 + s*c3,  bq = cross(b, q),  det = -dot(a, bq)
+ *     d0 = dot(F, bq)/det,  d1 = dot(a, cross(F, q))/det,
+ *     d2 = -dot(a, cross(b, F))/det;   s += d0, t += d1, r += d2
+ *     !(|s| <= 50) or !(|t| <= 50): the quad holds nothing
+ *     an earlier step had max(|d0|, |d1|) <= 1e-8: the solve is done (this
+ *     step was the polish); otherwise such a step asks for exactly one more
+ * (not done after 12 steps: the quad holds nothing),
+ *     holds(q, k)  iff  done, |s| <= 1 + tol, |t| <= 1 + tol and r > 0.
+ * A quad with a non-finite corner holds nothing.  found_out[q] is the LOWEST
+ * k that holds q, or -1; weights_out[q] are, with s and t clipped to [-1, 1],
+ * 0.25*(1-s)*(1-t), 0.25*(1+s)*(1-t), 0.25*(1+s)*(1+t), 0.25*(1-s)*(1+t) for
+ * p0..p3, zeros where found_out[q] is -1.  Exact: a pure function of the
+ * inputs, whatever the grid's orientation or refinement, overlapping and
+ * collapsed quads included.
+ *
+ * The quads are sorted by the Morton code of c0 (rocPRIM radix sort), a tree
+ * of axis-aligned boxes is built over the sorted array (8 quads a leaf, 4
+ * nodes a node) and walked depth first by one lane per point.  A quad's box
+ * is the box of its corners widened by a margin of its own that covers the
+ * sphere's bulge over the patch, the 1e-6 and tol; a quad too flat or folded
+ * for that bound is tested against every point
+ * (pyremap_amd/csrc/remap_quads.hip has the derivation): a quad is skipped
+ * only where holds() rejects the point.  No atomics: two calls give identical
+ * bytes.  Everything is asynchronous on `stream`, nothing is read back; the
+ * workspace depends on (ny, nx, periodic, n_pts) alone.  Inputs outside the
+ * unit-vector contract give an unspecified result; the call still ends and
+ * stays inside its arrays.
+ *
+ *   REMAP_ERR_ARG        a NULL array, ny < 2, nx < 2, more than 2^31 - 1
+ *                        quads, periodic not 0 or 1, n_pts < 0, tol < 0 or
+ *                        NaN
+ *   REMAP_ERR_WORKSPACE  workspace_bytes below remap_quads_workspace()'s
+ *   n_pts == 0           REMAP_OK, nothing is launched
+ * ---------------------------------------------------------------------------
+ */
+/*
+ * Launches nothing and touches no device memory (rocPRIM is asked for its
+ * sort buffer: call it with the device current that remap_quads() will run
+ * on).
+ */
+REMAP_API
+int remap_quads_workspace(int64_t ny, int64_t nx, int32_t periodic,
+                          int64_t n_pts, size_t *bytes_out);
+
+/*
+ *   nodes, points, found_out, weights_out, workspace (device);  found_out
+ *   one int32 and weights_out four doubles per point.
+ */
+REMAP_API
+int remap_quads(const double *nodes, int64_t ny, int64_t nx, int32_t periodic,
+                const double *points, int64_t n_pts, double tol,
+                int32_t *found_out, double *weights_out, void *workspace,
+                size_t workspace_bytes, void *stream);
+
+/*
+ * remap_quads() for measurements: the same launches with events between the
+ * phases.  This one WAITS for the last event, then writes phase_ms_out[0..2]
+ * (host): milliseconds of keys + sort, of coefficients + boxes, and of the
+ * walk.  (With n_pts == 0 the first two phases still run.)
+ */
+REMAP_API
+int remap_quads_timed(const double *nodes, int64_t ny, int64_t nx,
+                      int32_t periodic, const double *points, int64_t n_pts,
+                      double tol, int32_t *found_out, double *weights_out,
+                      void *workspace, size_t workspace_bytes,
+                      float *phase_ms_out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -51,7 +51,7 @@ CELL_MAX_RUN = 4
 DTYPE_F64 = 0
 DTYPE_F32 = 1
 
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 #: readable pad entries kept behind col/val (remap_csr.csr_pad)
 CSR_PAD = 8
@@ -81,6 +81,7 @@ EXPORTS = (
     'remap_overlap_grids_sizes', 'remap_overlap_grids',
     'remap_nearest_workspace', 'remap_nearest', 'remap_nearest_timed',
     'remap_locate_workspace', 'remap_locate', 'remap_locate_timed',
+    'remap_quads_workspace', 'remap_quads', 'remap_quads_timed',
 )
 
 
@@ -481,6 +482,21 @@ def load_library():
     lib.remap_locate_timed.restype = ctypes.c_int
     lib.remap_locate_timed.argtypes = [
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
+    lib.remap_quads_workspace.restype = ctypes.c_int
+    lib.remap_quads_workspace.argtypes = [
+        ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+        ctypes.POINTER(ctypes.c_size_t)]
+    lib.remap_quads.restype = ctypes.c_int
+    lib.remap_quads.argtypes = [
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.remap_quads_timed.restype = ctypes.c_int
+    lib.remap_quads_timed.argtypes = [
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
         ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
@@ -2515,6 +2531,97 @@ def locate_in_triangles(xyz, tri, points, tol=1e-12, timing=None,
                 _ptr(xyz), n_nodes, _ptr(tri), n_tri, _ptr(points), n_pts,
                 tol, _ptr(found), _ptr(weights), _ptr(ws), nbytes.value,
                 stream), 'remap_locate')
+        if timing is not None:
+            t1.record()
+            t1.synchronize()
+            timing['ms'] = t0.elapsed_time(t1)
+            if phases:
+                timing['sort_ms'], timing['setup_ms'], \
+                    timing['walk_ms'] = (float(v) for v in ms)
+        # (as in nearest_points: torch's allocator keeps the workspace for
+        # this stream, so later work is ordered behind the walk)
+        del ws
+    return found, weights
+
+
+# ---------------------------------------------------------------------------
+# the quad of four cell centres that holds every point (bilinear from a grid
+# given by 2-D latitude / longitude arrays)
+# ---------------------------------------------------------------------------
+
+def locate_in_quads(nodes, points, periodic=False, tol=1e-10, timing=None,
+                    phases=False):
+    """
+    For every point the lowest-numbered quad of four neighbouring cell
+    centres whose bilinear patch holds it, and the patch's weights of the
+    four corners, through ``remap_quads`` (``include/remap_hip.h`` has the
+    definition): ``nodes (ny, nx, 3)`` and ``points (n_pts, 3)`` are
+    contiguous fp64 tensors of unit vectors on one HIP device, ``ny >= 2``
+    and ``nx >= 2``; with ``periodic`` column ``nx - 1`` closes onto column
+    0.  Quad ``k = j * nqx + i`` (``nqx = nx - 1 + periodic``) has the corners
+    ``(j, i)``, ``(j, i1)``, ``(j + 1, i1)``, ``(j + 1, i)`` with ``i1 = (i +
+    1) % nx``, the order of the weights.  Returns ``(found int32 (n_pts,),
+    weights fp64 (n_pts, 4))`` on that device: ``found`` is -1, and the
+    weights zero, where no quad holds the point.  Exact in fp64 (a Newton
+    solve per point and quad with a stopping rule of its own, the patch
+    coordinates accepted up to ``1 + tol``); two calls give identical bytes.
+    Asynchronous on the current stream.
+
+    ``timing``: a dict that receives the GPU ``ms`` of the call (events on
+    the stream).  With ``phases=True`` (measurements only: the library then
+    waits for the walk before it returns) the call goes through
+    ``remap_quads_timed`` and the dict also receives ``sort_ms``,
+    ``setup_ms`` and ``walk_ms``.
+    """
+    torch = require_gpu()
+    lib = load_library()
+    for name, t, dim in (('nodes', nodes, 3), ('points', points, 2)):
+        if not torch.is_tensor(t) or not t.is_cuda or \
+                t.dtype != torch.float64 or t.dim() != dim or \
+                t.shape[-1] != 3 or not t.is_contiguous():
+            shape = '(ny, nx, 3)' if dim == 3 else '(n, 3)'
+            raise ValueError(
+                f'{name}: expected a contiguous {shape} float64 tensor on a '
+                f'HIP device')
+    if nodes.device != points.device:
+        raise ValueError(
+            f'nodes on {nodes.device}, points on {points.device}: expected '
+            f'one device')
+    ny, nx, n_pts = nodes.shape[0], nodes.shape[1], points.shape[0]
+    if ny < 2 or nx < 2:
+        raise ValueError(f'locate_in_quads needs at least 2 x 2 nodes, not '
+                         f'{ny} x {nx}')
+    periodic = 1 if periodic else 0
+    tol = float(tol)
+    if not tol >= 0.0:
+        raise ValueError(f'tol {tol}: expected a number >= 0')
+    if phases and timing is None:
+        raise ValueError('phases=True needs a timing dict to fill')
+    dev = nodes.device
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        nbytes = ctypes.c_size_t()
+        _check(lib.remap_quads_workspace(ny, nx, periodic, n_pts,
+                                         ctypes.byref(nbytes)),
+               'remap_quads_workspace')
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        found = torch.empty(n_pts, dtype=torch.int32, device=dev)
+        weights = torch.empty((n_pts, 4), dtype=torch.float64, device=dev)
+        if timing is not None:
+            t0 = torch.cuda.Event(enable_timing=True)
+            t1 = torch.cuda.Event(enable_timing=True)
+            t0.record()
+        if phases:
+            ms = (ctypes.c_float * 3)()
+            _check(lib.remap_quads_timed(
+                _ptr(nodes), ny, nx, periodic, _ptr(points), n_pts, tol,
+                _ptr(found), _ptr(weights), _ptr(ws), nbytes.value, ms,
+                stream), 'remap_quads_timed')
+        else:
+            _check(lib.remap_quads(
+                _ptr(nodes), ny, nx, periodic, _ptr(points), n_pts, tol,
+                _ptr(found), _ptr(weights), _ptr(ws), nbytes.value, stream),
+                'remap_quads')
         if timing is not None:
             t1.record()
             t1.synchronize()

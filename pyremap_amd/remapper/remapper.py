@@ -154,7 +154,13 @@ class Remapper:
         (``LatLon2DGridDescriptor``) and an MPAS cell mesh, a lat-lon grid or
         another such grid, either way: ESMF's first-order conservative map,
         the cell overlaps clipped on the GPU.  ``bilinear`` / ``neareststod``
-        also go towards a 2-D grid (its cell centres).  ``neareststod`` from
+        also go towards a 2-D grid (its cell centres), and FROM one towards
+        anything: its centres are enough, a grid read from a file without
+        corner arrays will do (:func:`pyremap_amd.weights.make_weights`;
+        ``bilinear`` on the quads between four neighbouring centres, the quad
+        that holds each point searched on the GPU where one is present,
+        :func:`pyremap_amd.weights.bilinear_grid_weights`, without pole
+        caps; ``neareststod`` the exact search below).  ``neareststod`` from
         an MPAS mesh (cells, edges or vertices) to anything is ESMF's exact
         nearest-point search, run on the GPU
         (:func:`pyremap_amd.weights.nearest_weights`); from a rectangular
@@ -171,7 +177,9 @@ class Remapper:
                 "bilinear maps from an MPAS mesh and conserve maps between an "
                 "MPAS cell mesh and a lat-lon grid or another MPAS cell "
                 "mesh, or between a 2-D lat-lon grid (its corner arrays) and "
-                "an MPAS cell mesh, a lat-lon grid or another 2-D grid")
+                "an MPAS cell mesh, a lat-lon grid or another 2-D grid, and "
+                "bilinear / neareststod maps from a 2-D lat-lon grid (its "
+                "cell centres) to anything")
         _setup_remapper(self)
         from pyremap_amd.weights import write_weights
         if logger is not None:

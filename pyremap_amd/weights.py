@@ -52,7 +52,16 @@ axes the common methods have closed forms:
   or another such grid, either way (:func:`conserve_grid`) -- the same map,
   every grid cell the great-circle polygon of its four corners
   (``remap_overlap_grids``).  ``bilinear`` and ``neareststod`` go TOWARDS
-  such a grid (its cell centres are points for the source), not from it.
+  such a grid (its cell centres are points for the source) through
+  :func:`build_weights`; FROM it they go through :func:`make_weights`
+  (:func:`build_weights` itself keeps its ``TypeError`` for them).
+* ``bilinear`` FROM a 2-D lat-lon grid (its centres are enough, no corner
+  arrays) towards anything (:func:`bilinear_grid_weights`) -- ESMF's
+  construction as for tensor grids, the quad of four neighbouring centres
+  that holds each point found by an exact search: on the GPU where one is
+  present (``remap_quads``, ``pyremap_amd/csrc/remap_quads.hip``), with numpy
+  (:func:`locate_in_quads`) otherwise, the same bytes.  No pole caps.
+  ``neareststod`` from such a grid is :func:`nearest_weights` on its centres.
 * ``neareststod`` FROM an MPAS mesh (its cells, edges or vertices, given by
   a mesh file or by ``lat=`` / ``lon=``) towards anything
   (:func:`nearest_weights`) -- ESMF's search: every destination point takes
@@ -797,6 +806,266 @@ def bilinear_3d(src_descriptor, plat, plon, tol=1e-10, chunk=1 << 20):
 
 
 # ---------------------------------------------------------------------------
+# bilinear from a grid given by 2-D latitude / longitude arrays: the same
+# quads and patches, but no per-axis bracket says which quad holds a point --
+# an exact search (remap_quads on the GPU, locate_in_quads on the host)
+# ---------------------------------------------------------------------------
+
+def _cross3(u, v):
+    return np.stack([u[:, 1] * v[:, 2] - u[:, 2] * v[:, 1],
+                     u[:, 2] * v[:, 0] - u[:, 0] * v[:, 2],
+                     u[:, 0] * v[:, 1] - u[:, 1] * v[:, 0]], axis=1)
+
+
+def _dot3(u, v):
+    return (u[:, 0] * v[:, 0] + u[:, 1] * v[:, 1]) + u[:, 2] * v[:, 2]
+
+
+def _quad_corner_ids(ny, nx, periodic, k=None):
+    """The flat node ids ``(len(k), 4)`` of the corners p0..p3 of the quads
+    ``k`` (all of them by default): quad ``k = j * nqx + i`` with ``nqx = nx
+    - 1 + periodic`` has ``(j, i)``, ``(j, i1)``, ``(j + 1, i1)``, ``(j + 1,
+    i)``, ``i1 = (i + 1) % nx``."""
+    nqx = nx - 1 + (1 if periodic else 0)
+    if k is None:
+        k = np.arange((ny - 1) * nqx, dtype=np.int64)
+    j, i = np.divmod(np.asarray(k, dtype=np.int64), nqx)
+    i1 = (i + 1) % nx
+    return np.stack([j * nx + i, j * nx + i1, (j + 1) * nx + i1,
+                     (j + 1) * nx + i], axis=1)
+
+
+def _quad_patches(nodes, periodic):
+    """Per quad: the patch coefficients ``c0..c3`` of ``X(s, t) = c0 + s c1 +
+    t c2 + s t c3``, each ``(n_quads, 3)``, its corners ``(n_quads, 4, 3)``
+    and whether all four are finite."""
+    ny, nx = nodes.shape[:2]
+    P = nodes.reshape(-1, 3)[_quad_corner_ids(ny, nx, periodic)]
+    p0, p1, p2, p3 = P[:, 0], P[:, 1], P[:, 2], P[:, 3]
+    with np.errstate(all='ignore'):
+        c0 = 0.25 * (((p0 + p1) + p2) + p3)
+        c1 = 0.25 * (((p1 - p0) + p2) - p3)
+        c2 = 0.25 * (((p2 - p0) - p1) + p3)
+        c3 = 0.25 * (((p0 - p1) + p2) - p3)
+    return (c0, c1, c2, c3), P, np.isfinite(P).all(axis=(1, 2))
+
+
+def _quad_boxes(coef, P, finite, tol):
+    """``(lo, hi)``, each ``(n_quads, 3)``: a box per quad that holds every
+    point the quad holds -- its corners' box widened by the quad's own margin
+    ``d^2/2 + 2 d (2 tol + tol^2) + 1e-5`` (``d`` its diameter), everything
+    for a quad too flat or folded for that bound, nothing for one with a
+    non-finite corner (``pyremap_amd/csrc/remap_quads.hip`` has the
+    derivation; the kernel prunes with the same boxes)."""
+    c0, c1, c2, c3 = coef
+    n = len(P)
+    lo = np.full((n, 3), np.inf)
+    hi = np.full((n, 3), -np.inf)
+    with np.errstate(all='ignore'):
+        d2 = np.zeros(n)
+        for u, v in ((0, 1), (1, 2), (2, 3), (3, 0), (0, 2), (1, 3)):
+            d2 = np.fmax(d2, ((P[:, u] - P[:, v]) ** 2).sum(axis=1))
+        m = 0.5 * d2 + 2.0 * np.sqrt(d2) * (2.0 * tol + tol * tol) + 1e-5
+        # the shape test: the patch's normal keeps its side of the ray on the
+        # square |s|, |t| <= L, well enough for Cramer's rule
+        L = 1.25 + tol
+        n12 = _cross3(c1, c2)
+        D0, D1 = _dot3(c0, n12), _dot3(c0, _cross3(c1, c3))
+        D2, D3 = _dot3(c0, _cross3(c3, c2)), _dot3(c3, n12)
+        g = np.stack([(D0 - L * D1 - L * D2) - L * L * D3,
+                      (D0 + L * D1 - L * D2) + L * L * D3,
+                      (D0 + L * D1 + L * D2) - L * L * D3,
+                      (D0 - L * D1 + L * D2) + L * L * D3], axis=1)
+        one_side = (g > 0.0).all(axis=1) | (g < 0.0).all(axis=1)
+        l3 = L * np.sqrt(_dot3(c3, c3))
+        A = np.sqrt(_dot3(c1, c1)) + l3
+        B = np.sqrt(_dot3(c2, c2)) + l3
+        trusted = one_side & (m < 1.0) & \
+            (np.abs(g).min(axis=1) * 1e3 >= A * B * (1.0 + 1e-6))
+    ok = finite & trusted
+    lo[ok] = P[ok].min(axis=1) - m[ok, None]
+    hi[ok] = P[ok].max(axis=1) + m[ok, None]
+    rest = finite & ~trusted
+    lo[rest] = -np.inf
+    hi[rest] = np.inf
+    return lo, hi
+
+
+def _newton_quads(c0, c1, c2, c3, q):
+    """The Newton solve of :func:`locate_in_quads` on pairs of a patch and a
+    point, each pair on its own: ``(done, s, t, r)``."""
+    n = len(q)
+    s = np.zeros(n)
+    t = np.zeros(n)
+    r = np.ones(n)
+    done = np.zeros(n, dtype=bool)
+    polish = np.zeros(n, dtype=bool)
+    act = np.arange(n)
+    with np.errstate(all='ignore'):
+        for _ in range(12):
+            if not len(act):
+                break
+            C0, C1, C2, C3, Q = c0[act], c1[act], c2[act], c3[act], q[act]
+            sa, ta, ra = s[act], t[act], r[act]
+            F = (((C0 + sa[:, None] * C1) + ta[:, None] * C2) +
+                 (sa * ta)[:, None] * C3) - ra[:, None] * Q
+            a = C1 + ta[:, None] * C3
+            b = C2 + sa[:, None] * C3
+            bq = _cross3(b, Q)
+            det = -_dot3(a, bq)
+            d0 = _dot3(F, bq) / det
+            d1 = _dot3(a, _cross3(F, Q)) / det
+            d2 = -_dot3(a, _cross3(b, F)) / det
+            sa, ta, ra = sa + d0, ta + d1, ra + d2
+            s[act], t[act], r[act] = sa, ta, ra
+            near = (np.abs(sa) <= 50.0) & (np.abs(ta) <= 50.0)
+            finished = near & polish[act]
+            done[act[finished]] = True
+            polish[act] = (np.abs(d0) <= 1e-8) & (np.abs(d1) <= 1e-8)
+            act = act[near & ~finished]
+    return done, s, t, r
+
+
+def locate_in_quads(nodes, points, periodic=False, tol=1e-10,
+                    pairs=1 << 22):
+    """
+    For every unit vector in ``points (n, 3)`` the quad of four neighbouring
+    ``nodes (ny, nx, 3)`` (unit vectors of cell centres; with ``periodic``
+    column ``nx - 1`` closes onto column 0) whose bilinear patch the ray from
+    the sphere's centre through the point meets, and the patch's weights of
+    its corners: the numpy statement of ``remap_quads``
+    (``pyremap_amd/csrc/remap_quads.hip`` has the definition) for machines
+    without a GPU, the same result byte for byte.
+
+    Quad ``k = j * nqx + i`` (``nqx = nx - 1 + periodic``) has the corners
+    ``p0 = (j, i)``, ``p1 = (j, i1)``, ``p2 = (j + 1, i1)``, ``p3 = (j + 1,
+    i)``, ``i1 = (i + 1) % nx``, joined by straight lines in 3-D.  Newton on
+    ``X(s, t) = r q`` from ``s = t = 0``, ``r = 1`` runs per point and per
+    quad, at most 12 steps: a step with ``max(|d0|, |d1|) <= 1e-8`` asks for
+    exactly one more (unlike :func:`_solve_quads`, whose ``last`` flag looks
+    at the whole batch), an iterate beyond ``|s|, |t| <= 50`` gives up.  A
+    quad holds the point iff the solve finished with ``|s|, |t| <= 1 + tol``
+    and ``r > 0`` (the near side of the sphere); the LOWEST such quad wins.
+
+    Returns ``(found int32 (n,), weights (n, 4))``: -1 and zeros where no
+    quad holds the point.  Works in chunks of about ``pairs`` (point, quad)
+    pairs, over the quads whose box (:func:`_quad_boxes`) holds the point.
+    """
+    nodes = np.ascontiguousarray(nodes, dtype=np.float64)
+    points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    if nodes.ndim != 3 or nodes.shape[2] != 3 or nodes.shape[0] < 2 or \
+            nodes.shape[1] < 2:
+        raise ValueError(f'nodes of shape {nodes.shape}: expected (ny, nx, '
+                         f'3) with ny >= 2 and nx >= 2')
+    tol = float(tol)
+    if not tol >= 0.0:
+        raise ValueError(f'tol {tol}: expected a number >= 0')
+    coef, P, finite = _quad_patches(nodes, periodic)
+    lo, hi = _quad_boxes(coef, P, finite, tol)
+    n_quads, n = len(P), len(points)
+    found = np.full(n, -1, dtype=np.int32)
+    weights = np.zeros((n, 4))
+    chunk = max(1, pairs // n_quads)
+    lim = 1.0 + tol
+    for at in range(0, n, chunk):
+        q = points[at:at + chunk]
+        with np.errstate(invalid='ignore'):
+            inside = ((q[:, None, :] >= lo[None]) &
+                      (q[:, None, :] <= hi[None])).all(axis=2)
+        qi, ki = np.nonzero(inside)
+        done, s, t, r = _newton_quads(coef[0][ki], coef[1][ki], coef[2][ki],
+                                      coef[3][ki], q[qi])
+        with np.errstate(invalid='ignore'):
+            holds = done & (np.abs(s) <= lim) & (np.abs(t) <= lim) & (r > 0.0)
+        qi, ki, s, t = qi[holds], ki[holds], s[holds], t[holds]
+        best = np.full(len(q), n_quads, dtype=np.int64)
+        np.minimum.at(best, qi, ki)
+        win = ki == best[qi]                       # one pair per held point
+        qi, s, t = qi[win], np.clip(s[win], -1.0, 1.0), \
+            np.clip(t[win], -1.0, 1.0)
+        found[at + qi] = ki[win]
+        weights[at + qi] = np.stack(
+            [0.25 * (1.0 - s) * (1.0 - t), 0.25 * (1.0 + s) * (1.0 - t),
+             0.25 * (1.0 + s) * (1.0 + t), 0.25 * (1.0 - s) * (1.0 + t)],
+            axis=1)
+    return found, weights
+
+
+def _quad_mapping(found, w, ny, nx, periodic, n_b, dst_dims):
+    """The mapping file of a point location in quads: four entries per
+    mapped point, those with ``S == 0`` dropped, merged and sorted by (row,
+    col); ``frac_b`` 1 where a quad holds the point."""
+    found = np.asarray(found, dtype=np.int64)
+    hit = np.nonzero(found >= 0)[0]
+    row = np.repeat(hit, 4)
+    col = _quad_corner_ids(ny, nx, periodic, found[hit]).reshape(-1)
+    S = np.asarray(w)[hit].reshape(-1)
+    keep = S != 0.0
+    row, col, S = _merged(row[keep], col[keep], S[keep])
+    return MappingFile(
+        ny * nx, n_b, np.array([nx, ny], dtype=np.int32),
+        np.asarray(dst_dims, dtype=np.int32), (row + 1).astype(np.int32),
+        (col + 1).astype(np.int32), S, (found >= 0).astype(np.float64))
+
+
+def _grid_2d_centres(descriptor):
+    """(lat, lon) in radians, both ``(ny, nx)``, of a 2-D lat-lon grid."""
+    scale = 1.0 if 'rad' in descriptor.units else np.pi / 180.0
+    lat = np.asarray(descriptor.lat, dtype=np.float64) * scale
+    lon = np.asarray(descriptor.lon, dtype=np.float64) * scale
+    if lat.ndim != 2 or lat.shape != lon.shape:
+        raise ValueError(f'a 2-D lat-lon grid needs 2-D lat and lon arrays '
+                         f'of one shape, not {lat.shape} and {lon.shape}')
+    return lat, lon
+
+
+def bilinear_grid_weights(src_descriptor, plat, plon, dst_dims, device=None,
+                          timing=None):
+    """
+    ``bilinear`` from a grid given by 2-D latitude / longitude arrays
+    (``LatLon2DGridDescriptor``; its corner arrays are not needed) towards
+    the points ``plat`` / ``plon`` (radians, 1-D): ESMF's construction as in
+    :func:`bilinear_3d` -- the nodes are the grid's cell centres, every point
+    is located in a quad of four neighbouring centres joined by straight
+    lines in 3-D and takes the patch's bilinear weights -- with the quad
+    found by an exact search, since no per-axis bracket exists on a
+    curvilinear grid: :func:`pyremap_amd.engine.locate_in_quads` on the GPU
+    where one is present, :func:`locate_in_quads` on the host otherwise, the
+    same bytes either way.  A grid that is not ``regional`` closes in its
+    second dimension (column ``nx - 1`` onto column 0).  No pole caps are
+    made and no tripolar seam is stitched: points beyond the first or last
+    row of a grid that is not regional, like points outside a regional one,
+    stay unmapped with ``frac_b`` = 0.  ``dst_dims``: the mapping file's
+    Fortran-ordered grid dims.  ``timing``: passed on to the engine call.
+    """
+    lat, lon = _grid_2d_centres(src_descriptor)
+    ny, nx = lat.shape
+    if ny < 2 or nx < 2:
+        raise ValueError(f'bilinear from a 2-D grid needs at least 2 x 2 '
+                         f'cell centres, not {ny} x {nx}')
+    if ny * nx > np.iinfo(np.int32).max:
+        raise ValueError(f'{ny * nx} source cells: the mapping file\'s col '
+                         f'is int32')
+    periodic = not src_descriptor.regional
+    nodes = np.ascontiguousarray(_unit(lat, lon))
+    plat = np.ascontiguousarray(plat, dtype=np.float64).reshape(-1)
+    plon = np.ascontiguousarray(plon, dtype=np.float64).reshape(-1)
+    q = np.ascontiguousarray(_unit(plat, plon))
+    if _gpu_present():
+        from pyremap_amd import engine
+        torch = engine.require_gpu()
+        if device is None:
+            device = f'cuda:{torch.cuda.current_device()}'
+        found, w = engine.locate_in_quads(
+            torch.from_numpy(nodes).to(device),
+            torch.from_numpy(q).to(device), periodic=periodic, timing=timing)
+        found, w = found.cpu().numpy(), w.cpu().numpy()
+    else:
+        found, w = locate_in_quads(nodes, q, periodic=periodic)
+    return _quad_mapping(found, w, ny, nx, periodic, len(plat), dst_dims)
+
+
+# ---------------------------------------------------------------------------
 # conserve between an MPAS cell mesh and a lat-lon grid: polygon clipping on
 # the GPU
 # ---------------------------------------------------------------------------
@@ -1216,11 +1485,54 @@ def build_weights(src_descriptor, dst_descriptor, method='conserve'):
         (row + 1).astype(np.int32), (col + 1).astype(np.int32), S, frac_b)
 
 
+def make_weights(src_descriptor, dst_descriptor, method='conserve'):
+    """
+    The mapping between any pair of descriptors this module serves, as a
+    :class:`MappingFile`: :func:`build_weights`, plus ``bilinear`` and
+    ``neareststod`` FROM a grid given by 2-D latitude / longitude arrays
+    (``LatLon2DGridDescriptor``) towards anything -- a point collection, the
+    positions of an MPAS mesh, or the cell centres of any grid.  The source's
+    corner arrays are not needed for these two methods, its centres are.
+
+    * ``bilinear``: :func:`bilinear_grid_weights` -- the quads between four
+      neighbouring centres, searched on the GPU where one is present and
+      with numpy otherwise; no pole caps.
+    * ``neareststod``: :func:`nearest_weights` with the grid's centres --
+      ESMF's exact search, which needs the GPU, as from an MPAS mesh.
+
+    Two entry points because :func:`build_weights` keeps its behaviour to
+    the letter, a ``TypeError`` for these pairs included: callers and tests
+    rely on it as the statement of what the closed forms and the earlier
+    searches serve.  :func:`write_weights`, and through it
+    ``Remapper(map_tool='analytic').build_map()``, come here.
+    """
+    if method not in METHODS:
+        raise ValueError(f'method {method!r}: expected one of {METHODS}')
+    if not isinstance(src_descriptor, LatLon2DGridDescriptor) or \
+            method == 'conserve':
+        return build_weights(src_descriptor, dst_descriptor, method)
+    points = _points(dst_descriptor)
+    if points is not None:
+        plat, plon, dims = points[0], points[1], [len(points[0])]
+    elif isinstance(dst_descriptor, MpasMeshDescriptor):
+        raise ValueError(
+            'towards an MPAS mesh its coordinates are needed: give the '
+            'descriptor a mesh file or lat= / lon=, not a size alone')
+    else:
+        plat, plon, dims = _cell_centres(dst_descriptor)
+    if method == 'bilinear':
+        return bilinear_grid_weights(src_descriptor, plat, plon, dims)
+    lat, lon = _grid_2d_centres(src_descriptor)
+    return nearest_weights(lat.reshape(-1), lon.reshape(-1), plat, plon,
+                           [lat.shape[1], lat.shape[0]], dims)
+
+
 def write_weights(filename, src_descriptor, dst_descriptor,
                   method='conserve'):
-    """Build the weights and write them as a mapping file."""
+    """Build the weights (:func:`make_weights`) and write them as a mapping
+    file."""
     from pyremap_amd.io.mapfile import write_mapping
-    m = build_weights(src_descriptor, dst_descriptor, method)
+    m = make_weights(src_descriptor, dst_descriptor, method)
     write_mapping(filename, m.n_a, m.n_b, m.src_grid_dims, m.dst_grid_dims,
                   m.row, m.col, m.S, m.frac_b,
                   attrs={'map_method': method,
