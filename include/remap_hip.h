@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define REMAP_ABI_VERSION 27
+#define REMAP_ABI_VERSION 28
 
 /* The library is built with -fvisibility=hidden: the entry points declared
  * here, and nothing else, are its dynamic symbols. */
@@ -990,6 +990,83 @@ int remap_overlap_meshes(const remap_overlap_mesh *a,
                          double *frac_b_out, double *a_area_out,
                          double *b_area_out, int64_t *n_entries_out,
                          void *stream);
+
+/*
+ * ---------------------------------------------------------------------------
+ * Conservative overlaps between two polygon soups whose cells come in convex
+ * PIECES (the cells of an MPAS vertex mesh beside a land mask are concave;
+ * any cell can be handed over as triangles).  Each side is a mesh of pieces
+ * and, per piece, the cell it belongs to.  The geometry, the candidate
+ * search (bucket raster sized to b), the clip and the error bits are those
+ * of remap_overlap_meshes applied to the pieces: every piece of b must be
+ * convex (REMAP_OVERLAP_ERR_CONVEX), pieces of a are subjects.  The outputs
+ * are in CELLS: A(dst cell, src cell) is the sum of the areas of its piece
+ * pairs, added in ascending (dst piece, src piece) order; a cell's area is
+ * the sum of its pieces' areas in piece order; the sliver rule (A > 1e-14 x
+ * area(dst cell)) applies to the merged sum; frac_b = min(sum of the
+ * entries / area, 1) in entry order; entries sorted by (dst, src), unique.
+ * No floating-point atomics: two calls give bitwise-identical outputs, and
+ * with parent == NULL on both sides every output has the bytes
+ * remap_overlap_meshes gives.
+ *
+ * REMAP_ERR_ARG: a parent array that decreases, leaves [0, n_parents) or
+ * skips a cell (a cell without a piece), n_parents > 2^31 - 1, n_parents
+ * that cannot match the pieces.  Host read-backs: those of
+ * remap_overlap_meshes, one for the parents' check (none with NULL parents)
+ * and one for the entry count behind the merge.
+ * ---------------------------------------------------------------------------
+ */
+/* (a struct tag, not a typedef: the name is also the call's) */
+struct remap_overlap_pieces {
+    remap_overlap_mesh mesh;    /* the PIECES, as cells of a mesh            */
+    int64_t n_parents;          /* cells the pieces belong to                */
+    const int32_t *parent;      /* (device) mesh.n_cells, 0-based, non-
+                                   decreasing; NULL: piece k is cell k       */
+};
+
+/*
+ *   counter (device) 4 x int64 of scratch;  n_pairs_out (host) candidate
+ *   piece pairs;  workspace_bytes_out (host) what remap_overlap_pieces()
+ *   needs.
+ */
+REMAP_API
+int remap_overlap_pieces_sizes(const struct remap_overlap_pieces *a,
+                               const struct remap_overlap_pieces *b, int64_t *counter,
+                               int64_t *n_pairs_out,
+                               size_t *workspace_bytes_out, void *stream);
+
+/*
+ *   dst_out, src_out, area_out (device) n_pairs capacity each, the first
+ *   *n_entries_out meaningful, indices of CELLS;  frac_b_out (device) one per
+ *   destination cell;  a_area_out (device) a->n_parents, b_area_out (device)
+ *   b->n_parents: the cells' areas;  n_entries_out (host) one int64.
+ */
+REMAP_API
+int remap_overlap_pieces(const struct remap_overlap_pieces *a,
+                         const struct remap_overlap_pieces *b, int32_t dst_is_b,
+                         int64_t n_pairs, void *workspace,
+                         size_t workspace_bytes, int32_t *dst_out,
+                         int32_t *src_out, double *area_out,
+                         double *frac_b_out, double *a_area_out,
+                         double *b_area_out, int64_t *n_entries_out,
+                         void *stream);
+
+/*
+ * The same call for measurements: phase_ms_out (host) receives 5 floats, the
+ * GPU milliseconds of the cell preparation, the candidate pairs, the clip
+ * (with its compaction), the sort and the merge (with frac_b), from events
+ * on `stream`; it synchronises the stream before it returns.
+ */
+REMAP_API
+int remap_overlap_pieces_timed(const struct remap_overlap_pieces *a,
+                               const struct remap_overlap_pieces *b,
+                               int32_t dst_is_b, int64_t n_pairs,
+                               void *workspace, size_t workspace_bytes,
+                               int32_t *dst_out, int32_t *src_out,
+                               double *area_out, double *frac_b_out,
+                               double *a_area_out, double *b_area_out,
+                               int64_t *n_entries_out, float *phase_ms_out,
+                               void *stream);
 
 /*
  * ---------------------------------------------------------------------------

@@ -36,13 +36,21 @@
 // come from the buckets the cells' boxes share, and clip_pairs_poly clips a
 // cell of one mesh by a (convex) cell of the other.
 //
+// Cells that come in convex pieces (remap_overlap_pieces, behind the mesh
+// path: the concave cells of an MPAS vertex mesh as triangles) go through the
+// mesh path piece by piece up to clip_pairs_poly; the piece pairs are then
+// re-keyed to their cells, sorted, and merge_runs adds every run of equal
+// keys up in a fixed order before the sliver rule is applied to the sum.
+//
 // With a structured 2-D grid given by its corner arrays on one side or both
 // (remap_overlap_grids, at the end) the grid's cells are prepared straight
 // from the corners, candidates come from a pyramid of bounding caps over
 // the grid's own index space, and clip_pairs_poly and everything behind it
 // are the mesh path's.  Host read-backs: one in remap_overlap_latlon, two in
 // remap_overlap_meshes, one in remap_overlap_grids (the entry count with
-// every error bit, before the sort); each _sizes call reads its count back.
+// every error bit, before the sort), remap_overlap_meshes' two and up to two
+// more in remap_overlap_pieces (the parents' check, the entry count behind
+// the merge); each _sizes call reads its count back.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -1372,14 +1380,19 @@ void describe(const char *name, int err, char *out, size_t size)
     }
 }
 
-int meshes_fail(int err_a, int err_b, int err_p)
+int meshes_fail(const char *who, int err_a, int err_b, int err_p)
 {
     char text[3][192];
     describe("a", err_a, text[0], sizeof(text[0]));
     describe("b", err_b, text[1], sizeof(text[1]));
     describe(nullptr, err_p, text[2], sizeof(text[2]));
-    return fail(REMAP_ERR_UNSUPPORTED, "remap_overlap_meshes: %s%s%s", text[0],
-                text[1], text[2]);
+    // (remap_overlap_pieces names the bit as well)
+    const bool pieces = strcmp(who, "remap_overlap_meshes") != 0;
+    return fail(REMAP_ERR_UNSUPPORTED, "%s: %s%s%s%s", who, text[0], text[1],
+                text[2],
+                pieces && ((err_a | err_b) & REMAP_OVERLAP_ERR_CONVEX)
+                    ? "(REMAP_OVERLAP_ERR_CONVEX)"
+                    : "");
 }
 
 // one mesh's prepared cells in the workspace
@@ -1497,7 +1510,7 @@ int mesh_var_layout(int64_t n_akeys, int64_t n_bkeys, int64_t n_pairs,
     return REMAP_OK;
 }
 
-int meshes_sizes(const remap_overlap_mesh *mesh_a,
+int meshes_sizes(const char *who, const remap_overlap_mesh *mesh_a,
                  const remap_overlap_mesh *mesh_b, int64_t *counter,
                  int64_t *n_pairs_out, size_t *bytes_out, hipStream_t stream)
 {
@@ -1508,7 +1521,7 @@ int meshes_sizes(const remap_overlap_mesh *mesh_a,
     if (rc != REMAP_OK)
         return rc;
     if (!counter || !n_pairs_out || !bytes_out)
-        return fail(REMAP_ERR_ARG, "remap_overlap_meshes_sizes: NULL output");
+        return fail(REMAP_ERR_ARG, "%s_sizes: NULL output", who);
     bucket_raster(B.n_cells, &A, &B);
     const int64_t n_buckets = A.n_lat * A.n_lon;
     // the histogram of b's cells over the buckets, and the raster
@@ -1553,7 +1566,7 @@ int meshes_sizes(const remap_overlap_mesh *mesh_a,
     const int err_a = static_cast<int>(got[3] & 0xffffffff);
     const int err_b = static_cast<int>((got[3] >> 32) & 0xffffffff);
     if (err_a || err_b)
-        return meshes_fail(err_a, err_b, 0);
+        return meshes_fail(who, err_a, err_b, 0);
     MeshLayout lay;
     rc = mesh_fixed_layout(A, B, &lay);
     if (rc == REMAP_OK)
@@ -1678,35 +1691,46 @@ int sort_and_sum(int64_t n_dst, int64_t n_entries, int64_t n_pairs,
     return REMAP_OK;
 }
 
-int meshes(const remap_overlap_mesh *mesh_a, const remap_overlap_mesh *mesh_b,
-           int32_t dst_is_b, int64_t n_pairs, void *workspace,
-           size_t workspace_bytes, int32_t *dst_out, int32_t *src_out,
-           double *area_out, double *frac_b_out, double *a_area_out,
-           double *b_area_out, int64_t *n_entries_out, hipStream_t stream)
-{
+// what the front of remap_overlap_meshes leaves behind for the clip
+struct MeshRun {
     Geom A, B;
+    MeshLayout lay;
+    Side sa, sb;
+    PairWork work;
+    int64_t *back;
+};
+
+// Everything in front of clip_pairs_poly: both meshes prepared against b's
+// bucket raster (their polygons' areas into a_area / b_area), read-back 1,
+// the bucket lists and the unique candidate pairs a << 32 | b in R->work.cand.
+// `who` names the entry point in messages; ev (6 events or NULL) receives
+// the phase marks [0] start, [1] cells prepared, [2] pairs listed.
+int mesh_front(const char *who, const remap_overlap_mesh *mesh_a,
+               const remap_overlap_mesh *mesh_b, int64_t n_pairs,
+               void *workspace, size_t workspace_bytes, double *a_area,
+               double *b_area, bool have_outputs, hipStream_t stream,
+               hipEvent_t *ev, MeshRun *R)
+{
+    Geom &A = R->A, &B = R->B;
     int rc = check_mesh(mesh_a, "a", &A);
     if (rc == REMAP_OK)
         rc = check_mesh(mesh_b, "b", &B);
     if (rc != REMAP_OK)
         return rc;
     if (n_pairs < 0 || n_pairs >= (int64_t(1) << 32) - 1)
-        return fail(REMAP_ERR_UNSUPPORTED,
-                    "remap_overlap_meshes: %lld candidate pairs",
+        return fail(REMAP_ERR_UNSUPPORTED, "%s: %lld candidate pairs", who,
                     static_cast<long long>(n_pairs));
-    if (!frac_b_out || !a_area_out || !b_area_out || !n_entries_out ||
-        (n_pairs > 0 && (!dst_out || !src_out || !area_out)))
-        return fail(REMAP_ERR_ARG, "remap_overlap_meshes: NULL output");
+    if (!have_outputs)
+        return fail(REMAP_ERR_ARG, "%s: NULL output", who);
     bucket_raster(B.n_cells, &A, &B);
     const int64_t n_buckets = A.n_lat * A.n_lon;
-    MeshLayout lay;
+    MeshLayout &lay = R->lay;
     rc = mesh_fixed_layout(A, B, &lay);
     if (rc != REMAP_OK)
         return rc;
     if (!workspace || workspace_bytes < lay.fixed)
         return fail(REMAP_ERR_WORKSPACE,
-                    "remap_overlap_meshes: workspace of %zu bytes, need at "
-                    "least %zu",
+                    "%s: workspace of %zu bytes, need at least %zu", who,
                     workspace_bytes, lay.fixed);
     char *ws = static_cast<char *>(workspace);
     double *lat_c = reinterpret_cast<double *>(ws + lay.lat_c);
@@ -1715,23 +1739,30 @@ int meshes(const remap_overlap_mesh *mesh_a, const remap_overlap_mesh *mesh_b,
     int64_t *back = reinterpret_cast<int64_t *>(ws + lay.back);
     int32_t *status_ab = reinterpret_cast<int32_t *>(back + 2);
     int32_t *status = reinterpret_cast<int32_t *>(back + 5);
-    const Side sa = side_at(ws, lay.a), sb = side_at(ws, lay.b);
+    R->back = back;
+    R->sa = side_at(ws, lay.a);
+    R->sb = side_at(ws, lay.b);
+    const Side &sa = R->sa, &sb = R->sb;
     A.lat_c = B.lat_c = lat_c;
     A.lon_c = B.lon_c = lon_c;
 
+    if (ev)
+        REMAP_HIP_CHECK(hipEventRecord(ev[0], stream));
     REMAP_HIP_CHECK(hipMemsetAsync(back, 0, kBackWords * 8, stream));
     hipLaunchKernelGGL(bucket_edges, dim3(blocks(A.n_lon + 1, kBlock)),
                        dim3(kBlock), 0, stream, A.n_lat, A.n_lon, lat_c,
                        lon_c);
     REMAP_HIP_CHECK(hipGetLastError());
     void *temp0 = ws + lay.temp0;
-    rc = prep_side(B, true, sb, b_area_out, temp0, lay.temp0_bytes, back,
+    rc = prep_side(B, true, sb, b_area, temp0, lay.temp0_bytes, back,
                    status_ab + 1, stream);
     if (rc == REMAP_OK)
-        rc = prep_side(A, false, sa, a_area_out, temp0, lay.temp0_bytes,
+        rc = prep_side(A, false, sa, a_area, temp0, lay.temp0_bytes,
                        back + 1, status_ab, stream);
     if (rc != REMAP_OK)
         return rc;
+    if (ev)
+        REMAP_HIP_CHECK(hipEventRecord(ev[1], stream));
     // read-back 1: the bucket keys of both meshes, the cells' error bits
     int64_t got[3];
     REMAP_HIP_CHECK(hipMemcpyAsync(got, back, sizeof(got),
@@ -1741,20 +1772,19 @@ int meshes(const remap_overlap_mesh *mesh_a, const remap_overlap_mesh *mesh_b,
     const int err_a = static_cast<int>(got[2] & 0xffffffff);
     const int err_b = static_cast<int>((got[2] >> 32) & 0xffffffff);
     if (err_a || err_b)
-        return meshes_fail(err_a, err_b, 0);
+        return meshes_fail(who, err_a, err_b, 0);
     if (n_bkeys >= (int64_t(1) << 32) - 1 || n_akeys >= (int64_t(1) << 32) - 1)
-        return fail(REMAP_ERR_UNSUPPORTED,
-                    "remap_overlap_meshes: %lld / %lld bucket keys",
+        return fail(REMAP_ERR_UNSUPPORTED, "%s: %lld / %lld bucket keys", who,
                     static_cast<long long>(n_akeys),
                     static_cast<long long>(n_bkeys));
     if (n_pairs > 0 && n_akeys == 0)
-        return meshes_fail(0, 0, REMAP_OVERLAP_ERR_CAPACITY);
+        return meshes_fail(who, 0, 0, REMAP_OVERLAP_ERR_CAPACITY);
     rc = mesh_var_layout(n_akeys, n_bkeys, n_pairs, &lay);
     if (rc != REMAP_OK)
         return rc;
     if (workspace_bytes < lay.total)
         return fail(REMAP_ERR_WORKSPACE,
-                    "remap_overlap_meshes: workspace of %zu bytes, need %zu",
+                    "%s: workspace of %zu bytes, need %zu", who,
                     workspace_bytes, lay.total);
     uint64_t *bkeys = reinterpret_cast<uint64_t *>(ws + lay.bkeys);
     uint64_t *bkeys_s = reinterpret_cast<uint64_t *>(ws + lay.bkeys_s);
@@ -1805,9 +1835,8 @@ int meshes(const remap_overlap_mesh *mesh_a, const remap_overlap_mesh *mesh_b,
                            bkeys_s, n_pairs, cand, status);
         REMAP_HIP_CHECK(hipGetLastError());
     }
-    const bool dst_is_a = dst_is_b == 0;
-    const PairWork work = {cand, cand_s, parea, area_c, head, slot, n_unique,
-                           n_kept, status, temp, lay.temp_bytes};
+    R->work = {cand, cand_s, parea, area_c, head, slot, n_unique,
+               n_kept, status, temp, lay.temp_bytes};
     if (n_pairs > 0) {
         size_t tb = lay.temp_bytes;
         REMAP_HIP_CHECK((rocprim::radix_sort_keys(
@@ -1820,24 +1849,491 @@ int meshes(const remap_overlap_mesh *mesh_a, const remap_overlap_mesh *mesh_b,
             temp, tb, static_cast<const uint64_t *>(cand_s), cand, n_unique,
             static_cast<size_t>(n_pairs), rocprim::equal_to<uint64_t>(),
             stream)));
-        rc = clip_and_keep(A, sa, B, sb, dst_is_a, n_pairs, work, a_area_out,
-                           b_area_out, stream);
+    }
+    if (ev)
+        REMAP_HIP_CHECK(hipEventRecord(ev[2], stream));
+    return REMAP_OK;
+}
+
+int meshes(const remap_overlap_mesh *mesh_a, const remap_overlap_mesh *mesh_b,
+           int32_t dst_is_b, int64_t n_pairs, void *workspace,
+           size_t workspace_bytes, int32_t *dst_out, int32_t *src_out,
+           double *area_out, double *frac_b_out, double *a_area_out,
+           double *b_area_out, int64_t *n_entries_out, hipStream_t stream)
+{
+    static const char who[] = "remap_overlap_meshes";
+    const bool have_outputs =
+        frac_b_out && a_area_out && b_area_out && n_entries_out &&
+        (n_pairs <= 0 || (dst_out && src_out && area_out));
+    MeshRun R;
+    int rc = mesh_front(who, mesh_a, mesh_b, n_pairs, workspace,
+                        workspace_bytes, a_area_out, b_area_out, have_outputs,
+                        stream, nullptr, &R);
+    if (rc != REMAP_OK)
+        return rc;
+    const bool dst_is_a = dst_is_b == 0;
+    if (n_pairs > 0) {
+        rc = clip_and_keep(R.A, R.sa, R.B, R.sb, dst_is_a, n_pairs, R.work,
+                           a_area_out, b_area_out, stream);
         if (rc != REMAP_OK)
             return rc;
     }
     // read-back 2: how many entries to sort, the pairs' error bits
     int64_t kept[2];
-    REMAP_HIP_CHECK(hipMemcpyAsync(kept, n_kept, 16, hipMemcpyDeviceToHost,
-                                   stream));
+    REMAP_HIP_CHECK(hipMemcpyAsync(kept, R.work.n_kept, 16,
+                                   hipMemcpyDeviceToHost, stream));
     REMAP_HIP_CHECK(hipStreamSynchronize(stream));
     const int64_t n_entries = kept[0];
     if (const int err = static_cast<int>(kept[1] & 0xffffffff))
-        return meshes_fail(0, 0, err);
+        return meshes_fail(who, 0, 0, err);
     *n_entries_out = n_entries;
-    return sort_and_sum(dst_is_a ? A.n_cells : B.n_cells, n_entries, n_pairs,
-                        work, dst_out, src_out, area_out,
+    return sort_and_sum(dst_is_a ? R.A.n_cells : R.B.n_cells, n_entries,
+                        n_pairs, R.work, dst_out, src_out, area_out,
                         dst_is_a ? a_area_out : b_area_out, frac_b_out,
                         stream);
+}
+
+// ---------------------------------------------------------------------------
+// cells in convex pieces (remap_overlap_pieces): each side's mesh holds the
+// PIECES of its cells, parent[k] the cell piece k belongs to (non-decreasing,
+// every cell at least one piece; NULL: piece k is cell k).  Everything up to
+// clip_pairs_poly is remap_overlap_meshes on the pieces; behind it
+//   check_parents  one lane per piece: parent in range, never decreasing,
+//                  never skipping a cell
+//   parent_areas   one lane per cell: its pieces' areas summed in piece order
+//   flag / scan / scatter_parents  the piece pairs with A > 0 re-keyed
+//                  (dst cell, src cell), with their own position and their
+//                  (dst piece, src piece) key beside them
+//   radix sort     (dst cell << 32 | src cell, position)
+//   merge_runs     one lane per sorted entry, the first of each run of equal
+//                  keys walks it (runs are 1 to 4 long where a few cells are
+//                  split in two or three): the areas added in ascending
+//                  (dst piece, src piece) order, whatever order the sort left
+//                  them in; kept when the SUM > kSliver * area(dst cell)
+//   scan / scatter_entries  the kept runs, already sorted and unique
+//   -- read-back 3: the entry count --
+//   dst_sums as above over the cells
+// With identity parents a run is one piece pair, its sum that pair's area
+// and the sliver test the one flag_kept makes: the bytes of
+// remap_overlap_meshes.
+// ---------------------------------------------------------------------------
+
+// (the struct shares its name with the entry point: the tag names it)
+using PiecesArg = struct ::remap_overlap_pieces;
+
+// argument error bits of check_parents (beside the REMAP_OVERLAP_ERR_* bits
+// of the two sides)
+constexpr int kErrParentOrder = 1 << 8;
+constexpr int kErrParentEmpty = 1 << 9;
+
+__global__ __launch_bounds__(kBlock) void check_parents(
+    int64_t n_pieces, int64_t n_parents, const int32_t *__restrict__ parent,
+    int32_t *__restrict__ status)
+{
+    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (k >= n_pieces)
+        return;
+    const int64_t p = parent[k];
+    const int64_t prev = k > 0 ? parent[k - 1] : -1;
+    if (p < 0 || p >= n_parents || p < prev)
+        atomicOr(status, kErrParentOrder);
+    else if (p > prev + 1 || (k == n_pieces - 1 && p != n_parents - 1))
+        atomicOr(status, kErrParentEmpty);
+}
+
+// the first piece of cell c (parent is non-decreasing); NULL: c itself
+__device__ inline int64_t first_piece(const int32_t *parent, int64_t n_pieces,
+                                      int64_t c)
+{
+    if (!parent)
+        return c;
+    int64_t lo = 0, hi = n_pieces;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (parent[mid] < c)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kBlock) void parent_areas(
+    int64_t n_pieces, int64_t n_parents, const int32_t *__restrict__ parent,
+    const double *__restrict__ piece_area, double *__restrict__ area)
+{
+    const int64_t c = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (c >= n_parents)
+        return;
+    int64_t k = first_piece(parent, n_pieces, c);
+    double s = 0.0;
+    if (!parent) {
+        s = k < n_pieces ? piece_area[k] : 0.0;
+    } else {
+        for (; k < n_pieces && parent[k] == c; ++k)
+            s += piece_area[k];
+    }
+    area[c] = s;
+}
+
+__global__ __launch_bounds__(kBlock) void flag_positive(
+    int64_t n_pairs, int64_t n_a, int64_t n_b,
+    const uint64_t *__restrict__ keys, const double *__restrict__ area,
+    uint32_t *__restrict__ head)
+{
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n_pairs)
+        return;
+    const uint64_t key = keys[p];
+    const bool in = (key >> 32) < static_cast<uint64_t>(n_a) &&
+                    (key & kLow) < static_cast<uint64_t>(n_b);
+    head[p] = in && area[p] > 0.0 ? 1u : 0u;   // (past the unique pairs: ~0)
+}
+
+__global__ __launch_bounds__(kBlock) void scatter_parents(
+    int64_t n_pairs, bool dst_is_a, const uint64_t *__restrict__ keys,
+    const double *__restrict__ area, const uint32_t *__restrict__ head,
+    const uint32_t *__restrict__ slot, const int32_t *__restrict__ parent_a,
+    const int32_t *__restrict__ parent_b, uint64_t *__restrict__ keys_out,
+    uint32_t *__restrict__ at_out, double *__restrict__ area_out,
+    uint64_t *__restrict__ pieces_out, int64_t *__restrict__ n_kept)
+{
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n_pairs)
+        return;
+    if (p == n_pairs - 1)
+        *n_kept = static_cast<int64_t>(slot[p]) + head[p];
+    if (!head[p])
+        return;
+    const uint64_t a = keys[p] >> 32, b = keys[p] & kLow;
+    const uint64_t ca = parent_a ? static_cast<uint64_t>(parent_a[a]) : a;
+    const uint64_t cb = parent_b ? static_cast<uint64_t>(parent_b[b]) : b;
+    const uint32_t s = slot[p];
+    keys_out[s] = dst_is_a ? ca << 32 | cb : cb << 32 | ca;
+    pieces_out[s] = dst_is_a ? a << 32 | b : b << 32 | a;
+    at_out[s] = s;
+    area_out[s] = area[p];
+}
+
+__global__ __launch_bounds__(kBlock) void merge_runs(
+    int64_t n, const uint64_t *__restrict__ keys,
+    const uint32_t *__restrict__ at, const double *__restrict__ area,
+    const uint64_t *__restrict__ pieces, const double *__restrict__ dst_area,
+    double *__restrict__ sums, uint32_t *__restrict__ head)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n)
+        return;
+    const uint64_t key = keys[i];
+    if (i > 0 && keys[i - 1] == key) {
+        head[i] = 0u;
+        return;
+    }
+    int64_t end = i + 1;
+    while (end < n && keys[end] == key)
+        ++end;
+    double s = area[at[i]];
+    if (end > i + 1) {
+        // selection by the piece keys (unique within a run): the order of the
+        // additions does not lean on what the sort does with equal keys
+        s = 0.0;
+        bool any = false;
+        uint64_t last = 0;
+        for (int64_t step = i; step < end; ++step) {
+            uint64_t next = ~uint64_t(0);
+            double a = 0.0;
+            for (int64_t j = i; j < end; ++j) {
+                const uint32_t q = at[j];
+                const uint64_t k = pieces[q];
+                if ((!any || k > last) && k <= next) {
+                    next = k;
+                    a = area[q];
+                }
+            }
+            s += a;
+            last = next;
+            any = true;
+        }
+    }
+    sums[i] = s;
+    head[i] = s > kSliver * dst_area[key >> 32] ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(kBlock) void scatter_entries(
+    int64_t n, const uint64_t *__restrict__ keys,
+    const double *__restrict__ sums, const uint32_t *__restrict__ head,
+    const uint32_t *__restrict__ slot, int32_t *__restrict__ dst,
+    int32_t *__restrict__ src, double *__restrict__ area,
+    int64_t *__restrict__ n_entries)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n)
+        return;
+    if (i == n - 1)
+        *n_entries = static_cast<int64_t>(slot[i]) + head[i];
+    if (!head[i])
+        return;
+    const uint32_t s = slot[i];
+    dst[s] = static_cast<int32_t>(keys[i] >> 32);
+    src[s] = static_cast<int32_t>(keys[i] & kLow);
+    area[s] = sums[i];
+}
+
+// what remap_overlap_pieces keeps in FRONT of the workspace of the mesh
+// path: the pieces' own areas and the buffers of the merge
+struct PiecesLayout {
+    size_t a_area, b_area, at_c, at_s, pieces_c, back, temp, total;
+    size_t temp_bytes;
+};
+
+int pieces_layout(int64_t n_a, int64_t n_b, int64_t n_pairs, PiecesLayout *L)
+{
+    const size_t n = static_cast<size_t>(n_pairs > 0 ? n_pairs : 1);
+    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
+        nullptr, L->temp_bytes, static_cast<const uint64_t *>(nullptr),
+        static_cast<uint64_t *>(nullptr),
+        static_cast<const uint32_t *>(nullptr),
+        static_cast<uint32_t *>(nullptr), n, 0u, 64u)));
+    size_t off = 0;
+    L->a_area = take(&off, static_cast<size_t>(n_a > 0 ? n_a : 1) * 8);
+    L->b_area = take(&off, static_cast<size_t>(n_b > 0 ? n_b : 1) * 8);
+    L->at_c = take(&off, n * 4);
+    L->at_s = take(&off, n * 4);
+    L->pieces_c = take(&off, n * 8);
+    // [0] the entry count, [1] the parents' error bits: a low, b high
+    L->back = take(&off, 16);
+    L->temp = take(&off, L->temp_bytes);
+    L->total = off;
+    return REMAP_OK;
+}
+
+int check_pieces(const PiecesArg *p, const char *name)
+{
+    if (!p)
+        return fail(REMAP_ERR_ARG, "remap_overlap_pieces: NULL side %s", name);
+    if (p->n_parents < 0 || p->n_parents >= (int64_t(1) << 31))
+        return fail(REMAP_ERR_ARG,
+                    "remap_overlap_pieces: n_parents %lld of side %s (0 to "
+                    "2^31 - 1)",
+                    static_cast<long long>(p->n_parents), name);
+    // every cell has a piece and every piece a cell
+    if (p->mesh.n_cells >= 0 &&
+        (p->parent ? p->n_parents > p->mesh.n_cells ||
+                         (p->n_parents == 0) != (p->mesh.n_cells == 0)
+                   : p->n_parents != p->mesh.n_cells))
+        return fail(REMAP_ERR_ARG,
+                    "remap_overlap_pieces: side %s has %lld cells for %lld "
+                    "pieces%s (a cell without a piece, or pieces without a "
+                    "cell)",
+                    name, static_cast<long long>(p->n_parents),
+                    static_cast<long long>(p->mesh.n_cells),
+                    p->parent ? "" : " and no parent array");
+    return REMAP_OK;
+}
+
+int pieces_sizes(const PiecesArg *a, const PiecesArg *b,
+                 int64_t *counter, int64_t *n_pairs_out, size_t *bytes_out,
+                 hipStream_t stream)
+{
+    int rc = check_pieces(a, "a");
+    if (rc == REMAP_OK)
+        rc = check_pieces(b, "b");
+    if (rc == REMAP_OK)
+        rc = meshes_sizes("remap_overlap_pieces", &a->mesh, &b->mesh, counter,
+                          n_pairs_out, bytes_out, stream);
+    if (rc != REMAP_OK)
+        return rc;
+    PiecesLayout X;
+    rc = pieces_layout(a->mesh.n_cells, b->mesh.n_cells, *n_pairs_out, &X);
+    if (rc != REMAP_OK)
+        return rc;
+    *bytes_out += X.total;
+    return REMAP_OK;
+}
+
+// ev (6 events, or NULL) marks the phases: cell preparation, candidate pairs,
+// clip (with its compaction), sort, merge (with frac_b)
+int pieces(const PiecesArg *pa, const PiecesArg *pb,
+           int32_t dst_is_b, int64_t n_pairs, void *workspace,
+           size_t workspace_bytes, int32_t *dst_out, int32_t *src_out,
+           double *area_out, double *frac_b_out, double *a_area_out,
+           double *b_area_out, int64_t *n_entries_out, hipStream_t stream,
+           hipEvent_t *ev)
+{
+    static const char who[] = "remap_overlap_pieces";
+    int rc = check_pieces(pa, "a");
+    if (rc == REMAP_OK)
+        rc = check_pieces(pb, "b");
+    if (rc != REMAP_OK)
+        return rc;
+    const bool have_outputs =
+        frac_b_out && a_area_out && b_area_out && n_entries_out &&
+        (n_pairs <= 0 || (dst_out && src_out && area_out));
+    const int64_t n_a = pa->mesh.n_cells, n_b = pb->mesh.n_cells;
+    PiecesLayout X;
+    rc = pieces_layout(n_a, n_b, n_pairs, &X);
+    if (rc != REMAP_OK)
+        return rc;
+    if (!workspace || workspace_bytes < X.total)
+        return fail(REMAP_ERR_WORKSPACE,
+                    "%s: workspace of %zu bytes, need more than %zu", who,
+                    workspace_bytes, X.total);
+    char *ws = static_cast<char *>(workspace);
+    double *piece_area_a = reinterpret_cast<double *>(ws + X.a_area);
+    double *piece_area_b = reinterpret_cast<double *>(ws + X.b_area);
+    uint32_t *at_c = reinterpret_cast<uint32_t *>(ws + X.at_c);
+    uint32_t *at_s = reinterpret_cast<uint32_t *>(ws + X.at_s);
+    uint64_t *pieces_c = reinterpret_cast<uint64_t *>(ws + X.pieces_c);
+    int64_t *back = reinterpret_cast<int64_t *>(ws + X.back);
+    int32_t *status_ab = reinterpret_cast<int32_t *>(back + 1);
+
+    REMAP_HIP_CHECK(hipMemsetAsync(back, 0, 16, stream));
+    // the parents first (a read-back of their own, none with identity
+    // parents): an argument error comes before any geometry
+    if ((pa->parent && n_a > 0) || (pb->parent && n_b > 0)) {
+        if (pa->parent && n_a > 0)
+            hipLaunchKernelGGL(check_parents, dim3(blocks(n_a, kBlock)),
+                               dim3(kBlock), 0, stream, n_a, pa->n_parents,
+                               pa->parent, status_ab);
+        if (pb->parent && n_b > 0)
+            hipLaunchKernelGGL(check_parents, dim3(blocks(n_b, kBlock)),
+                               dim3(kBlock), 0, stream, n_b, pb->n_parents,
+                               pb->parent, status_ab + 1);
+        REMAP_HIP_CHECK(hipGetLastError());
+        int32_t bad[2];
+        REMAP_HIP_CHECK(hipMemcpyAsync(bad, status_ab, 8,
+                                       hipMemcpyDeviceToHost, stream));
+        REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+        if (bad[0] || bad[1])
+            return fail(REMAP_ERR_ARG, "%s: parent of side %s %s", who,
+                        bad[0] ? "a" : "b",
+                        ((bad[0] ? bad[0] : bad[1]) & kErrParentOrder)
+                            ? "decreases or is outside [0, n_parents)"
+                            : "skips a cell: a cell without a piece");
+    }
+    MeshRun R;
+    rc = mesh_front(who, &pa->mesh, &pb->mesh, n_pairs, ws + X.total,
+                    workspace_bytes - X.total, piece_area_a, piece_area_b,
+                    have_outputs, stream, ev, &R);
+    if (rc != REMAP_OK)
+        return rc;
+    if (pa->n_parents > 0)
+        hipLaunchKernelGGL(parent_areas, dim3(blocks(pa->n_parents, kBlock)),
+                           dim3(kBlock), 0, stream, n_a, pa->n_parents,
+                           pa->parent, piece_area_a, a_area_out);
+    if (pb->n_parents > 0)
+        hipLaunchKernelGGL(parent_areas, dim3(blocks(pb->n_parents, kBlock)),
+                           dim3(kBlock), 0, stream, n_b, pb->n_parents,
+                           pb->parent, piece_area_b, b_area_out);
+    REMAP_HIP_CHECK(hipGetLastError());
+    const bool dst_is_a = dst_is_b == 0;
+    const PairWork &w = R.work;
+    if (n_pairs > 0) {
+        hipLaunchKernelGGL(clip_pairs_poly, dim3(blocks(n_pairs, kClipBlock)),
+                           dim3(kClipBlock), 0, stream, n_a, R.A.max_edges,
+                           n_b, R.B.max_edges, n_pairs, w.n_unique, w.cand,
+                           R.sa.xyz, R.sa.nv, R.sa.centre, R.sa.radius,
+                           R.sb.xyz, R.sb.nv, R.sb.centre, R.sb.radius,
+                           w.parea, w.status);
+        REMAP_HIP_CHECK(hipGetLastError());
+        const uint32_t nb = blocks(n_pairs, kBlock);
+        hipLaunchKernelGGL(flag_positive, dim3(nb), dim3(kBlock), 0, stream,
+                           n_pairs, n_a, n_b, w.cand, w.parea, w.head);
+        REMAP_HIP_CHECK(hipGetLastError());
+        size_t tb = w.temp_bytes;
+        REMAP_HIP_CHECK((rocprim::exclusive_scan(
+            w.temp, tb, static_cast<const uint32_t *>(w.head), w.slot, 0u,
+            static_cast<size_t>(n_pairs), rocprim::plus<uint32_t>(), stream)));
+        hipLaunchKernelGGL(scatter_parents, dim3(nb), dim3(kBlock), 0, stream,
+                           n_pairs, dst_is_a, w.cand, w.parea, w.head, w.slot,
+                           pa->parent, pb->parent, w.cand_s, at_c, w.area_c,
+                           pieces_c, w.n_kept);
+        REMAP_HIP_CHECK(hipGetLastError());
+    }
+    if (ev)
+        REMAP_HIP_CHECK(hipEventRecord(ev[3], stream));
+    // read-back 2: how many piece pairs to sort, the pairs' error bits
+    int64_t kept[2];
+    REMAP_HIP_CHECK(hipMemcpyAsync(kept, w.n_kept, 16, hipMemcpyDeviceToHost,
+                                   stream));
+    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+    const int64_t n_kept = kept[0];
+    if (const int err = static_cast<int>(kept[1] & 0xffffffff))
+        return meshes_fail(who, 0, 0, err);
+    const double *dst_area = dst_is_a ? a_area_out : b_area_out;
+    const int64_t n_dst = dst_is_a ? pa->n_parents : pb->n_parents;
+    if (n_kept > 0) {
+        // (w.cand is the sort's key output, w.parea the runs' sums)
+        size_t tb = X.temp_bytes;
+        REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
+            ws + X.temp, tb, static_cast<const uint64_t *>(w.cand_s), w.cand,
+            static_cast<const uint32_t *>(at_c), at_s,
+            static_cast<size_t>(n_kept), 0u, 64u, stream)));
+    }
+    if (ev)
+        REMAP_HIP_CHECK(hipEventRecord(ev[4], stream));
+    int64_t n_entries = 0;
+    if (n_kept > 0) {
+        const uint32_t nb = blocks(n_kept, kBlock);
+        hipLaunchKernelGGL(merge_runs, dim3(nb), dim3(kBlock), 0, stream,
+                           n_kept, w.cand, at_s, w.area_c, pieces_c, dst_area,
+                           w.parea, w.head);
+        REMAP_HIP_CHECK(hipGetLastError());
+        size_t tb = w.temp_bytes;
+        REMAP_HIP_CHECK((rocprim::exclusive_scan(
+            w.temp, tb, static_cast<const uint32_t *>(w.head), w.slot, 0u,
+            static_cast<size_t>(n_kept), rocprim::plus<uint32_t>(), stream)));
+        hipLaunchKernelGGL(scatter_entries, dim3(nb), dim3(kBlock), 0, stream,
+                           n_kept, w.cand, w.parea, w.head, w.slot, dst_out,
+                           src_out, area_out, back);
+        REMAP_HIP_CHECK(hipGetLastError());
+        // read-back 3: the entries the sliver rule left
+        REMAP_HIP_CHECK(hipMemcpyAsync(&n_entries, back, 8,
+                                       hipMemcpyDeviceToHost, stream));
+        REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+    }
+    *n_entries_out = n_entries;
+    if (n_dst > 0) {
+        hipLaunchKernelGGL(dst_sums, dim3(blocks(n_dst, kBlock)), dim3(kBlock),
+                           0, stream, n_dst, back, dst_out, area_out, dst_area,
+                           frac_b_out);
+        REMAP_HIP_CHECK(hipGetLastError());
+    }
+    if (ev)
+        REMAP_HIP_CHECK(hipEventRecord(ev[5], stream));
+    return REMAP_OK;
+}
+
+int pieces_timed(const PiecesArg *pa,
+                 const PiecesArg *pb, int32_t dst_is_b,
+                 int64_t n_pairs, void *workspace, size_t workspace_bytes,
+                 int32_t *dst_out, int32_t *src_out, double *area_out,
+                 double *frac_b_out, double *a_area_out, double *b_area_out,
+                 int64_t *n_entries_out, float *phase_ms, hipStream_t stream)
+{
+    if (!phase_ms)
+        return fail(REMAP_ERR_ARG, "remap_overlap_pieces_timed: NULL phase_ms");
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipError_t err = hipSuccess;
+    for (int k = 0; k < 6 && err == hipSuccess; ++k)
+        err = hipEventCreate(&ev[k]);
+    int rc = REMAP_OK;
+    if (err == hipSuccess) {
+        rc = pieces(pa, pb, dst_is_b, n_pairs, workspace, workspace_bytes,
+                    dst_out, src_out, area_out, frac_b_out, a_area_out,
+                    b_area_out, n_entries_out, stream, ev);
+        if (rc == REMAP_OK)
+            err = hipEventSynchronize(ev[5]);
+        for (int k = 0; k < 5 && rc == REMAP_OK && err == hipSuccess; ++k)
+            err = hipEventElapsedTime(&phase_ms[k], ev[k], ev[k + 1]);
+    }
+    for (int k = 0; k < 6; ++k)
+        if (ev[k])
+            (void)hipEventDestroy(ev[k]);
+    if (rc != REMAP_OK)
+        return rc;
+    REMAP_HIP_CHECK(err);
+    return REMAP_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -2492,7 +2988,8 @@ int remap_overlap_meshes_sizes(const remap_overlap_mesh *a,
                                int64_t *n_pairs_out,
                                size_t *workspace_bytes_out, void *stream)
 {
-    return remap::meshes_sizes(a, b, counter, n_pairs_out, workspace_bytes_out,
+    return remap::meshes_sizes("remap_overlap_meshes", a, b, counter,
+                               n_pairs_out, workspace_bytes_out,
                                static_cast<hipStream_t>(stream));
 }
 
@@ -2509,6 +3006,48 @@ int remap_overlap_meshes(const remap_overlap_mesh *a,
                          dst_out, src_out, area_out, frac_b_out, a_area_out,
                          b_area_out, n_entries_out,
                          static_cast<hipStream_t>(stream));
+}
+
+int remap_overlap_pieces_sizes(const struct remap_overlap_pieces *a,
+                               const struct remap_overlap_pieces *b, int64_t *counter,
+                               int64_t *n_pairs_out,
+                               size_t *workspace_bytes_out, void *stream)
+{
+    return remap::pieces_sizes(a, b, counter, n_pairs_out,
+                               workspace_bytes_out,
+                               static_cast<hipStream_t>(stream));
+}
+
+int remap_overlap_pieces(const struct remap_overlap_pieces *a,
+                         const struct remap_overlap_pieces *b, int32_t dst_is_b,
+                         int64_t n_pairs, void *workspace,
+                         size_t workspace_bytes, int32_t *dst_out,
+                         int32_t *src_out, double *area_out,
+                         double *frac_b_out, double *a_area_out,
+                         double *b_area_out, int64_t *n_entries_out,
+                         void *stream)
+{
+    return remap::pieces(a, b, dst_is_b, n_pairs, workspace, workspace_bytes,
+                         dst_out, src_out, area_out, frac_b_out, a_area_out,
+                         b_area_out, n_entries_out,
+                         static_cast<hipStream_t>(stream), nullptr);
+}
+
+int remap_overlap_pieces_timed(const struct remap_overlap_pieces *a,
+                               const struct remap_overlap_pieces *b,
+                               int32_t dst_is_b, int64_t n_pairs,
+                               void *workspace, size_t workspace_bytes,
+                               int32_t *dst_out, int32_t *src_out,
+                               double *area_out, double *frac_b_out,
+                               double *a_area_out, double *b_area_out,
+                               int64_t *n_entries_out, float *phase_ms_out,
+                               void *stream)
+{
+    return remap::pieces_timed(a, b, dst_is_b, n_pairs, workspace,
+                               workspace_bytes, dst_out, src_out, area_out,
+                               frac_b_out, a_area_out, b_area_out,
+                               n_entries_out, phase_ms_out,
+                               static_cast<hipStream_t>(stream));
 }
 
 int remap_overlap_grids_sizes(const remap_overlap_side *a,

@@ -51,7 +51,7 @@ CELL_MAX_RUN = 4
 DTYPE_F64 = 0
 DTYPE_F32 = 1
 
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 #: readable pad entries kept behind col/val (remap_csr.csr_pad)
 CSR_PAD = 8
@@ -78,6 +78,8 @@ EXPORTS = (
     'remap_clock_probe',
     'remap_overlap_latlon_sizes', 'remap_overlap_latlon',
     'remap_overlap_meshes_sizes', 'remap_overlap_meshes',
+    'remap_overlap_pieces_sizes', 'remap_overlap_pieces',
+    'remap_overlap_pieces_timed',
     'remap_overlap_grids_sizes', 'remap_overlap_grids',
     'remap_nearest_workspace', 'remap_nearest', 'remap_nearest_timed',
     'remap_locate_workspace', 'remap_locate', 'remap_locate_timed',
@@ -274,6 +276,12 @@ class _OverlapMesh(ctypes.Structure):  # struct remap_overlap_mesh
                 ('lon_vertex', ctypes.c_void_p)]
 
 
+class _OverlapPieces(ctypes.Structure):  # struct remap_overlap_pieces
+    _fields_ = [('mesh', _OverlapMesh),
+                ('n_parents', ctypes.c_int64),
+                ('parent', ctypes.c_void_p)]
+
+
 class _OverlapGrid(ctypes.Structure):  # struct remap_overlap_grid
     _fields_ = [('ny', ctypes.c_int64),
                 ('nx', ctypes.c_int64),
@@ -446,6 +454,25 @@ def load_library():
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
         ctypes.c_void_p]
+    lib.remap_overlap_pieces_sizes.restype = ctypes.c_int
+    lib.remap_overlap_pieces_sizes.argtypes = [
+        ctypes.POINTER(_OverlapPieces), ctypes.POINTER(_OverlapPieces),
+        ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
+        ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
+    lib.remap_overlap_pieces.restype = ctypes.c_int
+    lib.remap_overlap_pieces.argtypes = [
+        ctypes.POINTER(_OverlapPieces), ctypes.POINTER(_OverlapPieces),
+        ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
+        ctypes.c_void_p]
+    lib.remap_overlap_pieces_timed.restype = ctypes.c_int
+    lib.remap_overlap_pieces_timed.argtypes = [
+        ctypes.POINTER(_OverlapPieces), ctypes.POINTER(_OverlapPieces),
+        ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
+        ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
     lib.remap_overlap_grids_sizes.restype = ctypes.c_int
     lib.remap_overlap_grids_sizes.argtypes = [
         ctypes.POINTER(_OverlapSide), ctypes.POINTER(_OverlapSide),
@@ -2292,6 +2319,117 @@ def overlap_meshes(mesh_a, mesh_b, dst_is_b, timing=None):
             t1.synchronize()
             timing['n_pairs'] = n
             timing['ms'] = t0.elapsed_time(t1)
+        del ws
+        m = n_entries.value
+    return (dst[:m], src[:m], A[:m], frac_b[:n_dst], a_area[:n_a],
+            b_area[:n_b])
+
+
+# ---------------------------------------------------------------------------
+# conservative overlaps between cells that come in convex pieces
+# ---------------------------------------------------------------------------
+
+#: the phases ``remap_overlap_pieces_timed`` reports, in order
+PIECES_PHASES = ('prep_ms', 'pairs_ms', 'clip_ms', 'sort_ms', 'merge_ms')
+
+
+def overlap_pieces(pieces_a, pieces_b, dst_is_b, timing=None):
+    """
+    The overlap areas between the cells of two polygon soups, each cell given
+    as one or more convex pieces, through ``remap_overlap_pieces``
+    (``include/remap_hip.h``).  A side is ``(verticesOnCell 1-based,
+    nEdgesOnCell, latVertex, lonVertex, parent, n_parents)``: the first four
+    describe the PIECES as :func:`overlap_meshes` takes a mesh, ``parent``
+    (int32, 0-based, non-decreasing, every cell at least once) says which
+    cell a piece belongs to -- ``None``: piece k is cell k, and ``n_parents``
+    is the number of pieces.  Side a's pieces are clipped by side b's, which
+    must be convex.
+
+    Returns ``(dst, src, A, frac_b, a_area, b_area)`` as
+    :func:`overlap_meshes` does, in cells: the areas of the piece pairs of a
+    pair of cells added in ascending (dst piece, src piece) order.  With
+    ``parent=None`` on both sides the bytes are those of
+    :func:`overlap_meshes`.  ``timing``: a dict that receives ``n_pairs``
+    (candidate piece pairs), the GPU ``ms`` of the call and its phases
+    (:data:`PIECES_PHASES`, the merge ``merge_ms``) from
+    ``remap_overlap_pieces_timed``.
+
+    A ``parent`` that decreases, leaves ``[0, n_parents)`` or skips a cell is
+    a ``ValueError`` (the library's ``REMAP_ERR_ARG``).
+    """
+    torch = require_gpu()
+    lib = load_library()
+    dev = pieces_a[0].device
+    keep = []
+
+    def side(p):
+        voc = p[0].to(torch.int32).contiguous()
+        noc = p[1].to(torch.int32).contiguous()
+        lat_v = p[2].to(torch.float64).contiguous()
+        lon_v = p[3].to(torch.float64).contiguous()
+        keep.extend((voc, noc, lat_v, lon_v))
+        parent, n_parents = p[4], int(p[5])
+        ptr = None
+        if parent is not None:
+            parent = parent.to(device=dev, dtype=torch.int32).contiguous()
+            if parent.numel() != voc.shape[0]:
+                raise ValueError(
+                    f'overlap_pieces: {parent.numel()} parents for '
+                    f'{voc.shape[0]} pieces')
+            keep.append(parent)
+            ptr = parent.data_ptr()
+        mesh = _OverlapMesh(voc.shape[0], lat_v.numel(), voc.shape[1], 0,
+                            voc.data_ptr(), noc.data_ptr(), lat_v.data_ptr(),
+                            lon_v.data_ptr())
+        return _OverlapPieces(mesh, n_parents, ptr)
+
+    def check(rc, what):
+        if rc == -1:     # REMAP_ERR_ARG
+            raise ValueError(
+                f'{what}: ' +
+                lib.remap_last_error().decode('utf-8', 'replace'))
+        _check(rc, what)
+    ga, gb = side(pieces_a), side(pieces_b)
+    n_a, n_b = ga.n_parents, gb.n_parents
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        counter = torch.zeros(4, dtype=torch.int64, device=dev)
+        n_pairs = ctypes.c_int64()
+        nbytes = ctypes.c_size_t()
+        check(lib.remap_overlap_pieces_sizes(
+            ctypes.byref(ga), ctypes.byref(gb), _ptr(counter),
+            ctypes.byref(n_pairs), ctypes.byref(nbytes), stream),
+            'remap_overlap_pieces_sizes')
+        n = n_pairs.value
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        dst = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        src = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        A = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        # (never empty: the C side wants every output pointer)
+        a_area = torch.empty(max(n_a, 1), dtype=torch.float64, device=dev)
+        b_area = torch.empty(max(n_b, 1), dtype=torch.float64, device=dev)
+        n_dst = n_b if dst_is_b else n_a
+        frac_b = torch.empty(max(n_dst, 1), dtype=torch.float64, device=dev)
+        n_entries = ctypes.c_int64()
+        args = (ctypes.byref(ga), ctypes.byref(gb), 1 if dst_is_b else 0, n,
+                _ptr(ws), nbytes.value, _ptr(dst), _ptr(src), _ptr(A),
+                _ptr(frac_b), _ptr(a_area), _ptr(b_area),
+                ctypes.byref(n_entries))
+        if timing is None:
+            check(lib.remap_overlap_pieces(*args, stream),
+                  'remap_overlap_pieces')
+        else:
+            phases = (ctypes.c_float * len(PIECES_PHASES))()
+            t0 = torch.cuda.Event(enable_timing=True)
+            t1 = torch.cuda.Event(enable_timing=True)
+            t0.record()
+            check(lib.remap_overlap_pieces_timed(*args, phases, stream),
+                  'remap_overlap_pieces_timed')
+            t1.record()
+            t1.synchronize()
+            timing['n_pairs'] = n
+            timing['ms'] = t0.elapsed_time(t1)
+            timing.update(zip(PIECES_PHASES, (float(x) for x in phases)))
         del ws
         m = n_entries.value
     return (dst[:m], src[:m], A[:m], frac_b[:n_dst], a_area[:n_a],

@@ -166,6 +166,14 @@ class Remapper:
         (:func:`pyremap_amd.weights.nearest_weights`); from a rectangular
         grid it is the nearest centre per axis.  The file is written to
         ``map_filename`` (default name as in ``setup.py:29-42``).
+        ``conserve`` also serves MPAS edge and vertex meshes (given by their
+        mesh files: the cells the reference writes to SCRIP for them, concave
+        ones beside a land mask cut into triangles) against anything that
+        has cells, and a projection grid (its corners projected to latitude
+        / longitude) against an MPAS cell mesh, a lat-lon grid, a 2-D grid
+        or a grid of another projection
+        (:func:`pyremap_amd.weights.conserve_polygons`,
+        :func:`pyremap_amd.weights.conserve_grid`).
         """
         from pyremap_amd.remapper.setup import _setup_remapper
         if self.map_tool != 'analytic':
@@ -179,7 +187,9 @@ class Remapper:
                 "mesh, or between a 2-D lat-lon grid (its corner arrays) and "
                 "an MPAS cell mesh, a lat-lon grid or another 2-D grid, and "
                 "bilinear / neareststod maps from a 2-D lat-lon grid (its "
-                "cell centres) to anything")
+                "cell centres) to anything, and conserve maps with an MPAS "
+                "edge or vertex mesh (its mesh file) or a projection grid "
+                "on either side")
         _setup_remapper(self)
         from pyremap_amd.weights import write_weights
         if logger is not None:

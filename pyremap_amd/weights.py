@@ -55,6 +55,18 @@ axes the common methods have closed forms:
   such a grid (its cell centres are points for the source) through
   :func:`build_weights`; FROM it they go through :func:`make_weights`
   (:func:`build_weights` itself keeps its ``TypeError`` for them).
+* ``conserve`` with the cells of an MPAS EDGE or VERTEX mesh (given by its
+  mesh file) on either side, against anything that has cells
+  (:func:`conserve_polygons`) -- the cells the reference writes to SCRIP for
+  these meshes (:func:`cell_polygons`); beside a land mask a vertex's cell is
+  concave, so cells that fail the clipper's convexity test are cut into
+  triangles on the host (:func:`convex_pieces`) and the GPU adds the pieces'
+  overlaps up per pair of cells (``remap_overlap_pieces``).  A projection
+  grid takes part in ``conserve`` through its projected corners: against an
+  MPAS cell mesh, a lat-lon grid, a 2-D grid or a grid of another projection
+  it goes through :func:`conserve_grid` (:func:`projected_grid`); two grids
+  of one projection keep the planar closed form.  These pairs are routed by
+  :func:`make_weights`; :func:`build_weights` keeps its errors for them.
 * ``bilinear`` FROM a 2-D lat-lon grid (its centres are enough, no corner
   arrays) towards anything (:func:`bilinear_grid_weights`) -- ESMF's
   construction as for tensor grids, the quad of four neighbouring centres
@@ -81,7 +93,9 @@ from pyremap_amd.descriptor import (
     LatLon2DGridDescriptor,
     LatLonGridDescriptor,
     MpasCellMeshDescriptor,
+    MpasEdgeMeshDescriptor,
     MpasMeshDescriptor,
+    MpasVertexMeshDescriptor,
     PointCollectionDescriptor,
     ProjectionGridDescriptor,
 )
@@ -1296,6 +1310,437 @@ def conserve_grid(src_descriptor, dst_descriptor, device=None, timing=None):
                        S, frac_b)
 
 
+# ---------------------------------------------------------------------------
+# conserve between any two descriptors that have cells: MPAS edge and vertex
+# meshes (their cells can be concave beside a land mask) and projection grids
+# ---------------------------------------------------------------------------
+
+#: kConvexTol of remap_overlap.hip: a corner may lie this far (x the cell's
+#: longest edge) on the wrong side of another edge's great circle
+CONVEX_TOL = 1e-9
+
+_EDGE_VARIABLES = ('cellsOnEdge', 'verticesOnEdge', 'latCell', 'lonCell',
+                   'latVertex', 'lonVertex')
+_VERTEX_VARIABLES = ('edgesOnVertex', 'cellsOnVertex', 'latVertex',
+                     'lonVertex', 'latEdge', 'lonEdge', 'latCell', 'lonCell')
+
+
+def _unit_poles(lat, lon):
+    """Unit vectors as remap_overlap.hip makes them: latitudes at +-pi/2 are
+    exactly the poles, whatever the longitude."""
+    lat, lon = np.broadcast_arrays(np.asarray(lat, dtype=np.float64),
+                                   np.asarray(lon, dtype=np.float64))
+    p = _unit(lat, lon)
+    p[lat >= 0.5 * np.pi] = (0.0, 0.0, 1.0)
+    p[lat <= -0.5 * np.pi] = (0.0, 0.0, -1.0)
+    return p
+
+
+def _tidy_ring(ids):
+    """One ring of node ids: consecutive equal corners dropped, cyclically,
+    and spikes removed -- a run a, b, a loses b and one a -- until neither
+    is left."""
+    ring = list(ids)
+    changed = True
+    while changed and len(ring) > 1:
+        changed = False
+        for k in range(len(ring)):
+            if ring[k] == ring[k - 1]:
+                del ring[k]
+                changed = True
+                break
+            if len(ring) > 2 and ring[k - 2] == ring[k]:
+                # (k - 1 is the spike's tip; drop it and this copy of a)
+                for j in sorted((k % len(ring), (k - 1) % len(ring)),
+                                reverse=True):
+                    del ring[j]
+                changed = True
+                break
+    return ring
+
+
+def _tidy_rings(ids):
+    """:func:`_tidy_ring` for every row of ``ids`` (n, width), 0-based:
+    ``(voc (n, width) 1-based and padded with 0, noc)``.  Rows of distinct
+    ids, all there are away from a mesh's boundary, stay as they are."""
+    ids = np.asarray(ids, dtype=np.int64)
+    n, width = ids.shape
+    voc = (ids + 1).astype(np.int32)
+    noc = np.full(n, width, dtype=np.int32)
+    ordered = np.sort(ids, axis=1)
+    for r in np.nonzero((np.diff(ordered, axis=1) == 0).any(axis=1))[0]:
+        ring = _tidy_ring(ids[r])
+        voc[r] = 0
+        voc[r, :len(ring)] = np.asarray(ring, dtype=np.int64) + 1
+        noc[r] = len(ring)
+    return voc, noc
+
+
+def _quad_soup(lat, lon):
+    """The cells of a grid given by its (ny + 1, nx + 1) corner arrays as
+    four-corner polygons: cell j * nx + i through the corners (j, i),
+    (j, i + 1), (j + 1, i + 1), (j + 1, i)."""
+    ny, nx = lat.shape[0] - 1, lat.shape[1] - 1
+    j, i = (x.reshape(-1) for x in np.meshgrid(np.arange(ny), np.arange(nx),
+                                               indexing='ij'))
+    first = j * (nx + 1) + i
+    voc = np.stack([first, first + 1, first + nx + 2, first + nx + 1],
+                   axis=1) + 1
+    return (voc.astype(np.int32), np.full(ny * nx, 4, dtype=np.int32),
+            np.ascontiguousarray(lat.reshape(-1)),
+            np.ascontiguousarray(lon.reshape(-1)))
+
+
+def _projected_corners(descriptor):
+    """(lat, lon) in radians, (ny + 1, nx + 1), of a projection grid's cell
+    corners."""
+    lat, lon = descriptor.project_to_lat_lon(
+        *np.meshgrid(descriptor.x_corner, descriptor.y_corner))
+    if lat is None:
+        raise ValueError('the projection grid has no usable projection')
+    return np.radians(lat), np.radians(lon)
+
+
+def cell_polygons(descriptor):
+    """
+    The cells of a descriptor as polygons: ``(verticesOnCell (n, width)
+    1-based, nEdgesOnCell, lat, lon)`` as :func:`mesh_polygons` gives them
+    for an MPAS cell mesh, ``lat`` / ``lon`` (radians) the coordinates of the
+    nodes the indices point to.
+
+    * MPAS cell mesh: :func:`mesh_polygons`.
+    * MPAS edge mesh: the quadrilateral cellsOnEdge[0], verticesOnEdge[0],
+      cellsOnEdge[1], verticesOnEdge[1] around every edge, the vertex that
+      follows in place of a cell that is missing (nodes: cells, then
+      vertices).
+    * MPAS vertex mesh (``vertexDegree`` 3): edge k, cell k alternating for
+      k = 0, 1, 2 around every vertex, the vertex itself in place of an edge
+      or a cell that is missing (nodes: vertices, then edges, then cells).
+      Beside a land mask these cells are kites (one cell left) or hexagons
+      with a reflex corner at the vertex (two cells left): CONCAVE.
+      These corner orders are the ones the reference writes to SCRIP for the
+      two kinds of mesh.
+    * a lat-lon grid, a 2-D lat-lon grid with its corner arrays, a
+      projection grid (its ``x_corner`` / ``y_corner`` mesh through
+      ``project_to_lat_lon``): one quadrilateral per cell (C order) through
+      the corners (j, i), (j, i + 1), (j + 1, i + 1), (j + 1, i).
+
+    Consecutive equal corners are dropped, cyclically, and so are spikes (a
+    corner run a, b, a, which the fall-back leaves when an edge exists but
+    neither of its cells does, loses b and one a).
+    """
+    if isinstance(descriptor, ProjectionGridDescriptor):
+        return _quad_soup(*_projected_corners(descriptor))
+    if isinstance(descriptor, (LatLonGridDescriptor, LatLon2DGridDescriptor)):
+        return _quad_soup(*grid_corners(descriptor))
+    if not isinstance(descriptor, MpasMeshDescriptor):
+        raise ValueError(
+            f'a {type(descriptor).__name__} has no cells: conserve needs '
+            f'cells on both sides')
+    if descriptor._dim == 'nCells':
+        return mesh_polygons(descriptor)
+    if getattr(descriptor, 'filename', None) is None:
+        raise ValueError(
+            'conservative weights with an MPAS mesh need its mesh file '
+            '(cell polygons): construct the descriptor with filename=')
+    from pyremap_amd.io.netcdf import open_dataset
+    wanted = _EDGE_VARIABLES if descriptor._dim == 'nEdges' \
+        else _VERTEX_VARIABLES
+    ds = open_dataset(descriptor.filename)
+    missing = [v for v in wanted if v not in ds]
+    if missing:
+        raise ValueError(
+            f'{descriptor.filename}: conservative weights with its '
+            f'{descriptor._dim[1:].lower()} need the mesh variables '
+            f'{list(wanted)}; missing {missing}')
+
+    def coords(*names):
+        return np.concatenate([np.asarray(ds[v].values, dtype=np.float64)
+                               for v in names])
+
+    def members(name, width, count, offset, fallback):
+        # 0-based node ids; `fallback` where the mesh has no such member
+        m = np.asarray(ds[name].values, dtype=np.int64)
+        if m.ndim != 2 or m.shape[1] != width:
+            raise ValueError(
+                f'{descriptor.filename}: {name} of shape {m.shape}, '
+                f'expected (n, {width})' +
+                (': a vertexDegree of 3 is needed' if width == 3 else ''))
+        return np.where((m > 0) & (m <= count), m - 1 + offset, fallback)
+    n_cells = len(ds['latCell'].values)
+    n_vertices = len(ds['latVertex'].values)
+    if descriptor._dim == 'nEdges':
+        voe = np.asarray(ds['verticesOnEdge'].values, dtype=np.int64)
+        if voe.ndim != 2 or voe.shape[1] != 2 or voe.min() < 1 or \
+                voe.max() > n_vertices:
+            raise ValueError(f'{descriptor.filename}: verticesOnEdge must '
+                             f'name two vertices per edge')
+        vertex = voe - 1 + n_cells
+        cell = members('cellsOnEdge', 2, n_cells, 0, vertex)
+        ids = np.stack([cell[:, 0], vertex[:, 0], cell[:, 1], vertex[:, 1]],
+                       axis=1)
+        lat, lon = coords('latCell', 'latVertex'), \
+            coords('lonCell', 'lonVertex')
+    else:
+        n_edges = len(ds['latEdge'].values)
+        own = np.arange(n_vertices)[:, None]
+        edge = members('edgesOnVertex', 3, n_edges, n_vertices, own)
+        cell = members('cellsOnVertex', 3, n_cells, n_vertices + n_edges,
+                       own)
+        ids = np.stack([edge, cell], axis=2).reshape(n_vertices, 6)
+        lat = coords('latVertex', 'latEdge', 'latCell')
+        lon = coords('lonVertex', 'lonEdge', 'lonCell')
+    voc, noc = _tidy_rings(ids)
+    return voc, noc, lat, lon
+
+
+def _fan_areas(v):
+    """Signed areas of the polygons v (m, n, 3): the fan of Van
+    Oosterom-Strackee triangles from corner 0 (remap_overlap.hip's)."""
+    a, b, c = v[:, :1], v[:, 1:-1], v[:, 2:]
+    num = (a * np.cross(b - a, c - a)).sum(axis=-1)
+    den = 1.0 + (a * b).sum(axis=-1) + (b * c).sum(axis=-1) + \
+        (c * a).sum(axis=-1)
+    return (2.0 * np.arctan2(num, den)).sum(axis=-1)
+
+
+def _rings_convex(v):
+    """remap_overlap.hip's ``convex_cell`` for the rings v (m, n, 3), each
+    counter-clockwise and free of repeated corners: every corner on the left
+    of every edge's great circle, within CONVEX_TOL x the longest edge."""
+    n = v.shape[1]
+    nxt = np.roll(v, -1, axis=1)
+    length = np.sqrt(((nxt - v) ** 2).sum(axis=-1)).max(axis=1)
+    normal = np.cross(v, nxt)
+    lim = -CONVEX_TOL * length[:, None] * np.sqrt((normal ** 2).sum(axis=-1))
+    side = np.einsum('mei,mki->mek', normal, v)
+    e = np.arange(n)
+    other = (e[None, :] != e[:, None]) & (e[None, :] != (e[:, None] + 1) % n)
+    return ~((side < lim[:, :, None]) & other[None]).any(axis=(1, 2))
+
+
+def _prepared_ring(p):
+    """A ring of unit vectors as the device prepares it: consecutive equal
+    points dropped (cyclically), turned counter-clockwise."""
+    keep = np.any(p != np.roll(p, 1, axis=0), axis=1)
+    keep_ids = np.nonzero(keep)[0] if keep.any() else np.arange(1)
+    p = p[keep_ids]
+    if len(p) >= 3 and _fan_areas(p[None])[0] < 0.0:
+        p, keep_ids = p[::-1], keep_ids[::-1]
+    return p, keep_ids
+
+
+def cells_convex(xyz, poly, count):
+    """Whether each cell passes the clipper's convexity test
+    (``convex_cell`` of remap_overlap.hip, the same formula and tolerance,
+    restated on the host).  ``poly`` (n, width): 0-based node ids into
+    ``xyz``, the first ``count[i]`` of row i valid."""
+    poly = np.asarray(poly, dtype=np.int64)
+    count = np.asarray(count, dtype=np.int64)
+    ok = np.ones(len(poly), dtype=bool)
+    for n in np.unique(count):
+        rows = np.nonzero(count == n)[0]
+        if n < 3:
+            ok[rows] = False
+            continue
+        v = xyz[poly[rows, :n]]
+        repeat = (v == np.roll(v, 1, axis=1)).all(axis=-1).any(axis=1)
+        flip = _fan_areas(v) < 0.0
+        v[flip] = v[flip, ::-1]
+        good = _rings_convex(v)
+        for k in np.nonzero(repeat)[0]:
+            p, _ = _prepared_ring(xyz[poly[rows[k], :n]])
+            good[k] = len(p) >= 3 and bool(_rings_convex(p[None])[0])
+        ok[rows] = good
+    return ok
+
+
+#: a corner is collinear with its neighbours when the triangle of the three
+#: holds less than this share of the cell's area: a cell of n corners loses
+#: at most n times as much to the corners dropped and the ears not emitted,
+#: 5e-15 for n = 10, inside the 1e-14 to which the pieces add up to the cell
+_FLAT_SHARE = 5e-16
+#: slack of the test "no other corner inside the ear", x the length of the
+#: edge's normal: the rounding of three unit vectors' products
+_INSIDE_EPS = 8 * np.finfo(np.float64).eps
+
+
+def _ear_triangles(p):
+    """A simple polygon p (n, 3), counter-clockwise, as triangles of corner
+    numbers: corners collinear with their neighbours are dropped, then ears
+    are cut off -- a convex corner with no other corner of the polygon inside
+    its triangle -- the lowest such corner first; collinear triples are
+    never emitted.
+
+    Collinear is measured by area (``_FLAT_SHARE``), not by ``CONVEX_TOL``:
+    the triangles must add up to the polygon's own area, and on the QU240
+    vertex mesh 407 cells have a corner that is straight to 1e-9 of an edge
+    but holds up to 7e-10 of the cell's area behind it."""
+    tiny = _FLAT_SHARE * abs(_fan_areas(p[None])[0])
+
+    def area(a, b, c):
+        return _fan_areas(p[[a, b, c]][None])[0]
+
+    def left(a, b, c):
+        # (c's distance to the left of the great circle a -> b, the slack)
+        normal = np.cross(p[a], p[b])
+        return float(normal @ p[c]), \
+            _INSIDE_EPS * float(np.sqrt(normal @ normal))
+
+    ring = list(range(len(p)))
+    out = []
+    while len(ring) >= 3:
+        m = len(ring)
+        size = [area(ring[k - 1], ring[k], ring[(k + 1) % m])
+                for k in range(m)]
+        flat = [k for k in range(m) if abs(size[k]) <= tiny]
+        if flat:
+            del ring[flat[0]]
+            continue
+        if m == 3:
+            out.append(tuple(ring))
+            break
+        ear = None
+        for k in range(m):
+            if size[k] <= tiny:
+                continue
+            a, b, c = ring[k - 1], ring[k], ring[(k + 1) % m]
+            inside = False
+            for q in ring:
+                if q in (a, b, c):
+                    continue
+                sides = [left(*edge, q) for edge in ((a, b), (b, c), (c, a))]
+                if all(d >= -lim for d, lim in sides):
+                    inside = True
+                    break
+            if not inside:
+                ear = k
+                break
+        if ear is None:
+            raise ValueError('a cell is no simple polygon: it has no ear')
+        out.append((ring[ear - 1], ring[ear], ring[(ear + 1) % m]))
+        del ring[ear]
+    return out
+
+
+def convex_pieces(xyz, poly, count):
+    """
+    The cells as convex pieces for ``remap_overlap_pieces``: a cell that
+    passes the clipper's convexity test (:func:`cells_convex`) stays whole, a
+    cell that fails it is cut into triangles by ear clipping with a true ear
+    test (:func:`_ear_triangles`; :func:`clip_ears` is ESMF's rule for
+    convex cells).  Only corners collinear to rounding are dropped: the
+    pieces' areas add up to the cell's.
+
+    ``xyz`` (nodes, 3) unit vectors, ``poly`` (n, width) 0-based node ids,
+    the first ``count[i]`` of row i valid, either orientation.  Returns
+    ``(voc, noc, parent)``: the pieces as ``verticesOnCell`` (1-based) and
+    ``nEdgesOnCell``, and the 0-based cell of every piece, non-decreasing.
+    On the host: a few per cent of a vertex mesh's cells need it.
+    """
+    poly = np.asarray(poly, dtype=np.int64)
+    count = np.asarray(count, dtype=np.int64)
+    n = len(poly)
+    whole = cells_convex(xyz, poly, count)
+    cut = {}
+    for c in np.nonzero(~whole)[0]:
+        ids = poly[c, :count[c]]
+        p, kept = _prepared_ring(xyz[ids])
+        if len(p) < 3:
+            cut[c] = None       # (left whole: the device names the error)
+            continue
+        cut[c] = [[ids[kept[k]] for k in tri] for tri in _ear_triangles(p)]
+    per_cell = np.ones(n, dtype=np.int64)
+    for c, tris in cut.items():
+        if tris:
+            per_cell[c] = len(tris)
+    first = np.cumsum(per_cell) - per_cell
+    parent = np.repeat(np.arange(n, dtype=np.int32), per_cell)
+    width = max(poly.shape[1] if n else 3, 3)
+    voc = np.zeros((len(parent), width), dtype=np.int32)
+    noc = np.zeros(len(parent), dtype=np.int32)
+    voc[first, :poly.shape[1]] = np.where(
+        np.arange(poly.shape[1])[None, :] < count[:, None], poly + 1, 0)
+    noc[first] = count
+    for c, tris in cut.items():
+        if not tris:
+            continue
+        rows = slice(first[c], first[c] + len(tris))
+        voc[rows] = 0
+        voc[rows, :3] = np.asarray(tris, dtype=np.int64) + 1
+        noc[rows] = 3
+    return voc, noc, parent
+
+
+def _polygon_side(descriptor):
+    """(pieces for engine.overlap_pieces as numpy arrays, cells,
+    Fortran-ordered dims) of one side of :func:`conserve_polygons`."""
+    voc, noc, lat, lon = cell_polygons(descriptor)
+    n = len(noc)
+    if isinstance(descriptor, MpasMeshDescriptor):
+        dims = [n]
+    else:
+        ny, nx = descriptor.dim_sizes
+        dims = [nx, ny]
+    pvoc, pnoc, parent = convex_pieces(_unit_poles(lat, lon),
+                                       voc.astype(np.int64) - 1, noc)
+    return [pvoc, pnoc, lat, lon, None if len(parent) == n else parent,
+            n], n, dims
+
+
+def conserve_polygons(src_descriptor, dst_descriptor, device=None,
+                      timing=None):
+    """
+    First-order conservative weights between any two descriptors that have
+    cells (:func:`cell_polygons`), the cells of MPAS edge and vertex meshes
+    included, ESMF's ``destarea`` normalisation as in
+    :func:`conserve_mesh_latlon`.  Cells that are not convex are handed over
+    as triangles (:func:`convex_pieces`); the overlaps come from the GPU
+    (:func:`pyremap_amd.engine.overlap_pieces`), which adds the pieces'
+    overlaps up per pair of cells: the side with more pieces is clipped by
+    the other (the source on a tie).
+    """
+    from pyremap_amd import engine
+    src, n_src, src_dims = _polygon_side(src_descriptor)
+    dst, n_dst, dst_dims = _polygon_side(dst_descriptor)
+    torch = engine.require_gpu()
+    if device is None:
+        device = f'cuda:{torch.cuda.current_device()}'
+
+    def dev(side):
+        return [x if x is None or isinstance(x, int) else
+                torch.from_numpy(np.ascontiguousarray(x)).to(device)
+                for x in side]
+    src_is_a = len(src[1]) >= len(dst[1])
+    side_a, side_b = (src, dst) if src_is_a else (dst, src)
+    row, col, A, frac_b, a_area, b_area = engine.overlap_pieces(
+        dev(side_a), dev(side_b), dst_is_b=src_is_a, timing=timing)
+    row = row.cpu().numpy()
+    col = col.cpu().numpy()
+    A = A.cpu().numpy()
+    frac_b = frac_b.cpu().numpy()
+    dst_area = (b_area if src_is_a else a_area).cpu().numpy()
+    S = A / dst_area[row]
+    return MappingFile(n_src, n_dst, np.array(src_dims, dtype=np.int32),
+                       np.array(dst_dims, dtype=np.int32),
+                       (row + 1).astype(np.int32), (col + 1).astype(np.int32),
+                       S, frac_b)
+
+
+def projected_grid(descriptor):
+    """A projection grid as a 2-D lat-lon grid with its cells' corners
+    projected to latitude / longitude (what :func:`conserve_grid` takes)."""
+    lat, lon = descriptor.project_to_lat_lon(
+        *np.meshgrid(descriptor.x, descriptor.y))
+    lat_corner, lon_corner = descriptor.project_to_lat_lon(
+        *np.meshgrid(descriptor.x_corner, descriptor.y_corner))
+    if lat is None or lat_corner is None:
+        raise ValueError('the projection grid has no usable projection')
+    return LatLon2DGridDescriptor.create(
+        lat, lon, lat_corner=lat_corner, lon_corner=lon_corner,
+        mesh_name=f'{descriptor.mesh_name}_corners')
+
+
 def nearest_weights(src_lat, src_lon, dst_lat, dst_lon, src_dims, dst_dims,
                     device=None, timing=None):
     """
@@ -1485,6 +1930,31 @@ def build_weights(src_descriptor, dst_descriptor, method='conserve'):
         (row + 1).astype(np.int32), (col + 1).astype(np.int32), S, frac_b)
 
 
+def _same_projection(a, b):
+    pa, pb = a.projection, b.projection
+    return pa is pb or getattr(pa, 'srs', pa) == getattr(pb, 'srs', pb)
+
+
+def _make_conserve(src_descriptor, dst_descriptor):
+    """``conserve`` of :func:`make_weights`: the pairs with an MPAS edge or
+    vertex mesh (its file) or a projection grid on one side, everything else
+    to :func:`build_weights`."""
+    pair = (src_descriptor, dst_descriptor)
+    if any(isinstance(d, (MpasEdgeMeshDescriptor, MpasVertexMeshDescriptor))
+           and getattr(d, 'filename', None) is not None for d in pair):
+        return conserve_polygons(src_descriptor, dst_descriptor)
+    stereo = [isinstance(d, ProjectionGridDescriptor) for d in pair]
+    if any(stereo) and not (all(stereo) and _same_projection(*pair)):
+        other = pair[1] if stereo[0] else pair[0]
+        if all(stereo) or isinstance(
+                other, (LatLonGridDescriptor, LatLon2DGridDescriptor)) or (
+                isinstance(other, MpasCellMeshDescriptor) and
+                getattr(other, 'filename', None) is not None):
+            return conserve_grid(*(projected_grid(d) if p else d
+                                   for d, p in zip(pair, stereo)))
+    return build_weights(src_descriptor, dst_descriptor, 'conserve')
+
+
 def make_weights(src_descriptor, dst_descriptor, method='conserve'):
     """
     The mapping between any pair of descriptors this module serves, as a
@@ -1500,6 +1970,15 @@ def make_weights(src_descriptor, dst_descriptor, method='conserve'):
     * ``neareststod``: :func:`nearest_weights` with the grid's centres --
       ESMF's exact search, which needs the GPU, as from an MPAS mesh.
 
+    ``conserve`` with an MPAS edge or vertex mesh (its mesh file) on either
+    side goes to :func:`conserve_polygons`; a projection grid paired with an
+    MPAS cell mesh (its file), a lat-lon grid, a 2-D grid or a grid of
+    ANOTHER projection goes to :func:`conserve_grid` with its projected
+    corners (:func:`projected_grid`); two grids of one projection keep
+    their planar closed form, and every other pair is
+    :func:`build_weights`'.  These need the GPU, as the other clipped maps
+    do.
+
     Two entry points because :func:`build_weights` keeps its behaviour to
     the letter, a ``TypeError`` for these pairs included: callers and tests
     rely on it as the statement of what the closed forms and the earlier
@@ -1508,8 +1987,9 @@ def make_weights(src_descriptor, dst_descriptor, method='conserve'):
     """
     if method not in METHODS:
         raise ValueError(f'method {method!r}: expected one of {METHODS}')
-    if not isinstance(src_descriptor, LatLon2DGridDescriptor) or \
-            method == 'conserve':
+    if method == 'conserve':
+        return _make_conserve(src_descriptor, dst_descriptor)
+    if not isinstance(src_descriptor, LatLon2DGridDescriptor):
         return build_weights(src_descriptor, dst_descriptor, method)
     points = _points(dst_descriptor)
     if points is not None:

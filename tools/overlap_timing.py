@@ -22,6 +22,22 @@ process the same grid written as a four-vertex MPAS mesh through
 remap_overlap_meshes, the two routes alternating, ``--repeat`` warm calls
 each (for latlon also remap_overlap_latlon on the same mesh and grid).
 
+    python tools/overlap_timing.py --vertices 153:latlon:0.5,153:cells:100
+
+--vertices times remap_overlap_pieces on the cells around the VERTICES of the
+icosahedral mesh n (derived from verticesOnCell) with a land mask removed, so
+that concave cells occur and are cut into triangles on the host
+(weights.convex_pieces): against the global r degree lat-lon grid as a quad
+soup (``latlon:r``) or against the cells of the icosahedral mesh n2
+(``cells:n2``), ``--repeat`` warm calls, the medians of the call and of its
+phases (prep, pairs, clip, sort, merge) and the share of the merge.
+
+    python tools/overlap_timing.py --meshes 153:100 --pieces
+
+--pieces (with --meshes) times remap_overlap_pieces with NULL parents beside
+remap_overlap_meshes on the same pair in the same process, the two calls
+alternating, ``--repeat`` warm calls each: minimum, median and maximum.
+
 One JSON line per size: cells, grid cells, candidates, entries, ms.
 """
 import argparse
@@ -45,8 +61,18 @@ def main():
                     help='n1:n2,... icosahedral mesh pairs (mesh <-> mesh)')
     ap.add_argument('--grids', default=None,
                     help='n:arctic:km or n:latlon:deg,... (mesh <-> 2-D grid)')
+    ap.add_argument('--vertices', default=None,
+                    help='n:latlon:deg or n:cells:n2,... (vertex cells, in '
+                         'pieces)')
+    ap.add_argument('--pieces', action='store_true',
+                    help='with --meshes: remap_overlap_pieces with NULL '
+                         'parents beside remap_overlap_meshes')
     ap.add_argument('--repeat', type=int, default=5)
     args = ap.parse_args()
+    if args.vertices:
+        return time_vertices(args.vertices, args.repeat)
+    if args.meshes and args.pieces:
+        return time_identity(args.meshes, args.repeat)
     if args.meshes:
         return time_meshes(args.meshes, args.sample)
     if args.grids:
@@ -156,6 +182,214 @@ def time_meshes(pairs, sample):
             'sample_max_dS': float(err.max()),
             'sum_A_minus_4pi': float(A.sum() - 4 * np.pi),
             'mesh_gen_s': round(gen_s, 1)}), flush=True)
+
+
+def _spread(ms):
+    ms = sorted(ms)
+    return {'min': round(ms[0], 3), 'median': round(ms[len(ms) // 2], 3),
+            'max': round(ms[-1], 3)}
+
+
+def time_identity(pairs, repeat):
+    """remap_overlap_meshes and remap_overlap_pieces with NULL parents on
+    one pair of meshes, alternating."""
+    import torch
+    from pyremap_amd import engine, synthetic
+    engine.require_gpu()
+    dev = 'cuda:0'
+    for item in pairs.split(','):
+        n1, n2 = (int(x) for x in item.split(':'))
+        meshes = [synthetic.icosahedral_mesh(n) for n in (n1, n2)]
+        arrays = [[torch.from_numpy(np.ascontiguousarray(m[k])).to(dev)
+                   for k in ('verticesOnCell', 'nEdgesOnCell', 'latVertex',
+                             'lonVertex')] for m in meshes]
+        sides = [a + [None, int(a[1].numel())] for a in arrays]
+        runs = {'meshes': [], 'pieces': []}
+        outs = {}
+        for _ in range(repeat + 1):
+            for name in runs:
+                timing = {}
+                if name == 'meshes':
+                    out = engine.overlap_meshes(*arrays, dst_is_b=True,
+                                                timing=timing)
+                else:
+                    out = engine.overlap_pieces(*sides, dst_is_b=True,
+                                                timing=timing)
+                torch.cuda.synchronize()
+                runs[name].append(timing)
+                outs[name] = [x.cpu().numpy() for x in out]
+                del out
+        same = all(np.array_equal(x.view(np.uint8), y.view(np.uint8))
+                   for x, y in zip(outs['meshes'], outs['pieces']))
+        row = {'mesh_a_cells': int(sides[0][5]),
+               'mesh_b_cells': int(sides[1][5]),
+               'candidates': int(runs['meshes'][-1]['n_pairs']),
+               'entries': int(len(outs['meshes'][0])), 'same_bytes': same}
+        for name, t in runs.items():
+            row[name] = dict(_spread([x['ms'] for x in t[1:]]),
+                             ms_first=round(t[0]['ms'], 3))
+        row['pieces_phases_median'] = {
+            k: _spread([x[k] for x in runs['pieces'][1:]])['median']
+            for k in engine.PIECES_PHASES}
+        print(json.dumps(row), flush=True)
+
+
+def vertex_cells(m):
+    """The cells around the vertices of a mesh of ``icosahedral_mesh`` (a
+    land mask may have removed cells), derived from verticesOnCell: the
+    a point on each of the vertex's edges and the centres of its cells in
+    turn, the vertex itself where the mesh ends -- (voc 1-based (nVertices, 8),
+    noc, lat, lon), nodes: vertices, edge midpoints, cell centres."""
+    from pyremap_amd.weights import _unit
+    voc = np.asarray(m['verticesOnCell'], dtype=np.int64) - 1
+    noc = np.asarray(m['nEdgesOnCell'], dtype=np.int64)
+    n_v, n_c = len(m['latVertex']), len(noc)
+    cell, k = np.nonzero(np.arange(voc.shape[1])[None, :] < noc[:, None])
+    v = voc[cell, k]
+    q = voc[cell, (k + 1) % noc[cell]]        # next corner of the cell
+    p = voc[cell, (k - 1) % noc[cell]]        # the one before
+    # the edges' midpoints as nodes
+    pairs = np.minimum(v, q) * n_v + np.maximum(v, q)
+    edges, edge_vq = np.unique(pairs, return_inverse=True)
+    edge_pv = np.searchsorted(edges, np.minimum(v, p) * n_v +
+                              np.maximum(v, p))
+    xyz_v = _unit(np.asarray(m['latVertex']), np.asarray(m['lonVertex']))
+    centre = np.zeros((n_c, 3))
+    np.add.at(centre, cell, xyz_v[v])
+    centre /= np.linalg.norm(centre, axis=1)[:, None]
+    # an edge between two cells: the point midway between their centres, so
+    # that a whole cell is a triangle with collinear edge points, as on a
+    # Voronoi mesh; an edge of the coast: midway between its vertices
+    sides = np.bincount(edge_vq, minlength=len(edges))
+    between = np.zeros((len(edges), 3))
+    np.add.at(between, edge_vq, centre[cell])
+    mid = np.where((sides == 2)[:, None], between,
+                   xyz_v[edges // n_v] + xyz_v[edges % n_v])
+    nodes = np.concatenate([xyz_v, mid, centre])
+    nodes /= np.linalg.norm(nodes, axis=1)[:, None]
+    lat = np.arcsin(np.clip(nodes[:, 2], -1.0, 1.0))
+    lon = np.arctan2(nodes[:, 1], nodes[:, 0])
+    # up to three corners (cell, position) per vertex
+    by_v = np.argsort(v, kind='stable')
+    deg = np.bincount(v, minlength=n_v)
+    assert deg.max() <= 3
+    first = np.cumsum(deg) - deg
+    slot = np.arange(len(v)) - first[v[by_v]]
+    corner = np.full((n_v, 3), -1, dtype=np.int64)
+    corner[v[by_v], slot] = by_v
+    has = corner >= 0
+    cq = np.where(has, q[corner], -1)
+    cp = np.where(has, p[corner], -2)
+    # succ[i] = the corner j of the same vertex whose cell follows i's
+    # counter-clockwise: q_j == p_i
+    match = has[:, :, None] & has[:, None, :] & \
+        (cp[:, :, None] == cq[:, None, :])
+    succ = np.where(match.any(axis=2), match.argmax(axis=2), -1)
+    pred = match.any(axis=1)              # j has a predecessor
+    closed = (deg == 3) & pred.all(axis=1)
+    start = np.where(closed, 0, np.where(has & ~pred, np.arange(3)[None, :],
+                                         9).min(axis=1))
+    used = deg > 0
+    assert (start[used] < 3).all()
+    ring = np.zeros((n_v, 8), dtype=np.int64)
+    count = np.zeros(n_v, dtype=np.int64)
+    rows = np.nonzero(used)[0]
+    ring[rows, 0] = rows                   # the vertex, dropped when closed
+    cur = start.copy()
+    alive = used.copy()
+    for step in range(3):
+        r = np.nonzero(alive)[0]
+        c = corner[r, cur[r]]
+        if step == 0:
+            ring[r, 1] = n_v + edge_vq[c]
+            count[r] = 2
+        ring[r, 2 + 2 * step] = n_v + len(edges) + cell[c]
+        ring[r, 3 + 2 * step] = n_v + edge_pv[c]
+        count[r] = 4 + 2 * step
+        nxt = succ[r, cur[r]]
+        alive[r] = nxt >= 0
+        cur[r] = np.maximum(nxt, 0)
+        alive &= count < 2 * deg + 2
+    # a closed ring: no vertex, and its last edge is its first
+    out = np.zeros((n_v, 8), dtype=np.int32)
+    rc = np.nonzero(closed)[0]
+    out[rc, :6] = ring[rc, 1:7] + 1
+    ro = np.nonzero(used & ~closed)[0]
+    out[ro] = np.where(np.arange(8)[None, :] < count[ro, None],
+                       ring[ro] + 1, 0)
+    noc_out = np.where(closed, 6, count).astype(np.int32)
+    return out[used], noc_out[used], lat, lon
+
+
+def _land(lat, lon):
+    return (np.abs(lat - np.radians(20.0)) < np.radians(25.0)) & \
+        (np.abs(lon - np.radians(100.0)) < np.radians(40.0))
+
+
+def time_vertices(cases, repeat):
+    import torch
+    from pyremap_amd import engine, synthetic, weights
+    from pyremap_amd.descriptor import get_lat_lon_descriptor
+    engine.require_gpu()
+    dev = 'cuda:0'
+
+    def side(arrays, parent, n):
+        return [torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                for a in arrays] + [
+            None if parent is None else torch.from_numpy(parent).to(dev), n]
+    for item in cases.split(','):
+        n, kind, res = item.split(':')
+        n = int(n)
+        t0 = time.time()
+        voc, noc, lat, lon = vertex_cells(synthetic.icosahedral_mesh(n, _land))
+        gen_s = time.time() - t0
+        t0 = time.time()
+        xyz = weights._unit_poles(lat, lon)
+        concave = int((~weights.cells_convex(xyz, voc.astype(np.int64) - 1,
+                                             noc)).sum())
+        pvoc, pnoc, parent = weights.convex_pieces(
+            xyz, voc.astype(np.int64) - 1, noc)
+        split_s = time.time() - t0
+        vertex = side((pvoc, pnoc, lat, lon), parent, len(noc))
+        if kind == 'latlon':
+            other = weights.cell_polygons(get_lat_lon_descriptor(
+                float(res), float(res)))
+        else:
+            m = synthetic.icosahedral_mesh(int(res))
+            other = [m[k] for k in ('verticesOnCell', 'nEdgesOnCell',
+                                    'latVertex', 'lonVertex')]
+        other = side(other, None, len(other[1]))
+        vertex_is_a = len(pnoc) >= other[5]
+        a, b = (vertex, other) if vertex_is_a else (other, vertex)
+        runs = []
+        for _ in range(repeat + 1):
+            timing = {}
+            out = engine.overlap_pieces(a, b, dst_is_b=True, timing=timing)
+            torch.cuda.synchronize()
+            runs.append(timing)
+        A = out[2].cpu().numpy()
+        a_area = out[4].cpu().numpy()
+        src = out[1].cpu().numpy()
+        given = np.bincount(src, weights=A, minlength=len(a_area))
+        row = {'vertex_cells': int(len(noc)), 'concave': concave,
+               'pieces': int(len(pnoc)), 'other': f'{kind} {res}',
+               'other_cells': int(other[5]),
+               'clipped': 'vertex cells' if vertex_is_a else 'other',
+               'candidates': int(runs[-1]['n_pairs']),
+               'entries': int(len(A)),
+               'ms_first': round(runs[0]['ms'], 3),
+               'ms': _spread([x['ms'] for x in runs[1:]]),
+               'host_cells_s': round(gen_s, 1),
+               'host_split_s': round(split_s, 1)}
+        for k in engine.PIECES_PHASES:
+            row[k] = _spread([x[k] for x in runs[1:]])['median']
+        row['merge_share'] = round(row['merge_ms'] / sum(
+            row[k] for k in engine.PIECES_PHASES), 4)
+        if kind == 'latlon' or vertex_is_a:
+            # (a global b: every cell of a is shared out whole)
+            row['max_sum_A_over_area_minus_1'] = float(
+                np.abs(given / a_area - 1.0).max())
+        print(json.dumps(row), flush=True)
 
 
 def time_grids(cases, sample, repeat):
