@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define REMAP_ABI_VERSION 28
+#define REMAP_ABI_VERSION 29
 
 /* The library is built with -fvisibility=hidden: the entry points declared
  * here, and nothing else, are its dynamic symbols. */
@@ -1353,6 +1353,62 @@ int remap_quads_timed(const double *nodes, int64_t ny, int64_t nx,
                       double tol, int32_t *found_out, double *weights_out,
                       void *workspace, size_t workspace_bytes,
                       float *phase_ms_out, void *stream);
+
+/*
+ * ---------------------------------------------------------------------------
+ * Cells widened about their centres: the reference's expand_dist /
+ * expand_factor, applied to the DESTINATION cells of a smoothed `conserve`
+ * map before their overlaps are taken.  centre_lat / centre_lon (n_cells),
+ * corner_lat / corner_lon (n_cells, width) row-major, radians; the first
+ * count[i] slots of row i are corners, 0 <= count[i] <= width.  dist (metres)
+ * and factor are read at [i * stride], stride 0 (one value for every cell)
+ * or 1 (a value per cell).  All fp64, IEEE, no contraction, on WGS84
+ * (a = 6378137 m, 1/f = 298.257223563, b = a (1 - f), e2 = f (2 - f),
+ * e'2 = e2 / (1 - e2)) at height 0:
+ *     ecef(lat, lon) = (N cos lat cos lon, N cos lat sin lon,
+ *                       N (1 - e2) sin lat),  N = a / sqrt(1 - e2 sin^2 lat)
+ *     c = ecef(centre), p = ecef(corner), v = p - c, d = |v|
+ *     t = c + ((factor * d + dist) / d) * v
+ *     out_lon = atan2(t.y, t.x), out_lat = the geodetic latitude of t, its
+ *     height dropped: th = atan2(a t.z, b q) with q = sqrt(t.x^2 + t.y^2),
+ *     then THREE times  lat = atan2(t.z + e'2 b sin^3 th, q - e2 a cos^3 th),
+ *     th = atan2(b sin lat, a cos lat)  (Bowring's iteration, a fixed count)
+ * with three rules:
+ *     A  a latitude >= pi/2 or <= -pi/2, of a corner or a centre, is the
+ *        pole itself: ecef = (0, 0, +-b) whatever the longitude, so the two
+ *        pole corners of a polar lat-lon cell come out as one point, bit for
+ *        bit.  Such a corner crosses the pole when the expansion exceeds
+ *        the cell.
+ *     B  a corner with d == 0 (it IS the centre: the fixed point) is copied.
+ *     C  slots k >= count[i] are copied.
+ * One lane per slot; no LDS, no atomics on floating-point data: a pure
+ * function of the inputs, and equal inputs give equal bits.
+ *
+ * status: two int32 on the device, the call's scratch.  The call WAITS for
+ * its kernel on `stream`, reads them back and returns REMAP_ERR_ARG with a
+ * message naming the bits below and the lowest offending cell when an input
+ * is bad (out_lat / out_lon then hold copies at the offending slots).
+ *
+ *   REMAP_ERR_ARG   a NULL array, n_cells < 0 or > 2^31 - 1, width < 1, a
+ *                   stride other than 0 or 1, more than 2^31 - 1 blocks of
+ *                   256 slots; or an error bit
+ *   n_cells == 0    REMAP_OK, nothing is launched (dist, factor and status
+ *                   must still be given)
+ * ---------------------------------------------------------------------------
+ */
+#define REMAP_EXPAND_ERR_COUNT 1  /* a count[i] outside [0, width]          */
+#define REMAP_EXPAND_ERR_FINITE 2 /* NaN or Inf in a centre, a slot, dist or
+                                     factor                                 */
+#define REMAP_EXPAND_ERR_RADIUS 4 /* factor * d + dist <= 0 where d > 0     */
+
+REMAP_API
+int remap_expand_cells(int64_t n_cells, int32_t width,
+                       const double *centre_lat, const double *centre_lon,
+                       const double *corner_lat, const double *corner_lon,
+                       const int32_t *count, const double *dist,
+                       int32_t dist_stride, const double *factor,
+                       int32_t factor_stride, double *out_lat,
+                       double *out_lon, int32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

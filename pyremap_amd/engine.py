@@ -51,7 +51,7 @@ CELL_MAX_RUN = 4
 DTYPE_F64 = 0
 DTYPE_F32 = 1
 
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 #: readable pad entries kept behind col/val (remap_csr.csr_pad)
 CSR_PAD = 8
@@ -84,6 +84,7 @@ EXPORTS = (
     'remap_nearest_workspace', 'remap_nearest', 'remap_nearest_timed',
     'remap_locate_workspace', 'remap_locate', 'remap_locate_timed',
     'remap_quads_workspace', 'remap_quads', 'remap_quads_timed',
+    'remap_expand_cells',
 )
 
 
@@ -527,6 +528,12 @@ def load_library():
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
         ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
+    lib.remap_expand_cells.restype = ctypes.c_int
+    lib.remap_expand_cells.argtypes = [
+        ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     if lib.remap_abi_version() != ABI_VERSION:
         raise EngineError(
             f'{path} has ABI {lib.remap_abi_version()}, expected '
@@ -2771,3 +2778,92 @@ def locate_in_quads(nodes, points, periodic=False, tol=1e-10, timing=None,
         # this stream, so later work is ordered behind the walk)
         del ws
     return found, weights
+
+
+# ---------------------------------------------------------------------------
+# cells widened about their centres (expand_dist / expand_factor)
+# ---------------------------------------------------------------------------
+
+def expand_cells(centre_lat, centre_lon, corner_lat, corner_lon, count,
+                 expand_dist=None, expand_factor=None, timing=None):
+    """
+    The corners of every cell moved away from the cell's centre, through
+    ``remap_expand_cells`` (``include/remap_hip.h`` has the definition and
+    its three rules; :func:`pyremap_amd.weights.expand_cells` is the same
+    statement in numpy): ``centre_lat`` / ``centre_lon`` ``(n,)``,
+    ``corner_lat`` / ``corner_lon`` ``(n, width)`` fp64 tensors in radians
+    and ``count (n,)`` integers, all on one HIP device.  ``expand_dist``
+    (metres; ``None``: 0) and ``expand_factor`` (``None``: 1) are numbers or
+    ``(n,)`` arrays / tensors, one value per cell.
+
+    Returns ``(lat, lon)``, two new ``(n, width)`` fp64 tensors on that
+    device; slots beyond ``count[i]`` hold copies.  Runs on the current
+    stream and waits for it (the status is read back).  ``n = 0`` is legal.
+    A NaN, a count outside ``[0, width]`` or a corner whose new distance
+    ``factor * d + dist`` is not positive is a ``ValueError`` that names the
+    first such cell (the library's ``REMAP_ERR_ARG``).  ``timing``: a dict
+    that receives the GPU ``ms`` of the call (events on the stream).
+    """
+    torch = require_gpu()
+    lib = load_library()
+    if not torch.is_tensor(corner_lat) or not corner_lat.is_cuda or \
+            corner_lat.dim() != 2 or corner_lat.shape[1] < 1:
+        raise ValueError('corner_lat: expected an (n, width) tensor on a HIP '
+                         'device, width >= 1')
+    dev = corner_lat.device
+    n, width = corner_lat.shape
+
+    def f64(name, t, shape):
+        if not torch.is_tensor(t) or t.device != dev or \
+                tuple(t.shape) != shape:
+            raise ValueError(
+                f'{name}: expected a tensor of shape {shape} on {dev}')
+        return t.to(torch.float64).contiguous()
+
+    def per_cell(name, value, default):
+        if value is None:
+            value = default
+        if not torch.is_tensor(value):
+            value = torch.as_tensor(np.asarray(value, dtype=np.float64))
+        value = value.to(device=dev, dtype=torch.float64).contiguous()
+        if value.dim() == 0:
+            return value.reshape(1), 0
+        if tuple(value.shape) != (n,):
+            raise ValueError(
+                f'{name} of shape {tuple(value.shape)}: expected a number '
+                f'or one value for each of the {n} cells')
+        # (a one-cell array has one value either way)
+        return (value, 1) if n > 0 else (value.new_zeros(1), 0)
+    corner_lat = f64('corner_lat', corner_lat, (n, width))
+    corner_lon = f64('corner_lon', corner_lon, (n, width))
+    centre_lat = f64('centre_lat', centre_lat, (n,))
+    centre_lon = f64('centre_lon', centre_lon, (n,))
+    if not torch.is_tensor(count) or count.device != dev or \
+            tuple(count.shape) != (n,) or count.dtype.is_floating_point:
+        raise ValueError(f'count: expected {n} integers on {dev}')
+    count = count.to(torch.int32).contiguous()
+    dist, dist_stride = per_cell('expand_dist', expand_dist, 0.0)
+    factor, factor_stride = per_cell('expand_factor', expand_factor, 1.0)
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        out_lat = torch.empty_like(corner_lat)
+        out_lon = torch.empty_like(corner_lon)
+        status = torch.zeros(2, dtype=torch.int32, device=dev)
+        if timing is not None:
+            t0 = torch.cuda.Event(enable_timing=True)
+            t1 = torch.cuda.Event(enable_timing=True)
+            t0.record()
+        rc = lib.remap_expand_cells(
+            n, width, _ptr(centre_lat), _ptr(centre_lon), _ptr(corner_lat),
+            _ptr(corner_lon), _ptr(count), _ptr(dist), dist_stride,
+            _ptr(factor), factor_stride, _ptr(out_lat), _ptr(out_lon),
+            _ptr(status), stream)
+        if rc == -1:     # REMAP_ERR_ARG
+            raise ValueError(
+                lib.remap_last_error().decode('utf-8', 'replace'))
+        _check(rc, 'remap_expand_cells')
+        if timing is not None:
+            t1.record()
+            t1.synchronize()
+            timing['ms'] = t0.elapsed_time(t1)
+    return out_lat, out_lon

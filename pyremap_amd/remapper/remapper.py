@@ -174,6 +174,15 @@ class Remapper:
         or a grid of another projection
         (:func:`pyremap_amd.weights.conserve_polygons`,
         :func:`pyremap_amd.weights.conserve_grid`).
+        ``expand_dist`` (metres) and ``expand_factor``, the reference's
+        attributes (a number or one value per destination cell each), widen
+        every DESTINATION cell about its centre before a ``conserve`` map is
+        made: the cell then averages the source over a larger footprint (a
+        smoothed map; :func:`pyremap_amd.weights.expand_cells` has the
+        definition, the corners are moved on the GPU).  It holds for every
+        destination that has cells; the file records the two values.
+        ``bilinear`` and ``neareststod`` maps do not depend on destination
+        corners and stay as they are, as in the reference.
         """
         from pyremap_amd.remapper.setup import _setup_remapper
         if self.map_tool != 'analytic':
@@ -189,14 +198,21 @@ class Remapper:
                 "bilinear / neareststod maps from a 2-D lat-lon grid (its "
                 "cell centres) to anything, and conserve maps with an MPAS "
                 "edge or vertex mesh (its mesh file) or a projection grid "
-                "on either side")
+                "on either side; expand_dist / expand_factor smooth the "
+                "conserve maps")
         _setup_remapper(self)
         from pyremap_amd.weights import write_weights
         if logger is not None:
             logger.info(f'analytic {self.method} weights -> '
                         f'{self.map_filename}')
-        write_weights(self.map_filename, self.src_descriptor,
-                      self.dst_descriptor, self.method)
+        if self.expand_dist is None and self.expand_factor is None:
+            write_weights(self.map_filename, self.src_descriptor,
+                          self.dst_descriptor, self.method)
+        else:
+            write_weights(self.map_filename, self.src_descriptor,
+                          self.dst_descriptor, self.method,
+                          expand_dist=self.expand_dist,
+                          expand_factor=self.expand_factor)
         self._ds_map = None
         self._matrix = None
 

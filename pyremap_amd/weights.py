@@ -1672,6 +1672,178 @@ def convex_pieces(xyz, poly, count):
     return voc, noc, parent
 
 
+# ---------------------------------------------------------------------------
+# smoothed conserve maps: destination cells widened about their centres
+# (the reference's expand_dist / expand_factor, descriptor/utility.py
+# ::expand_scrip)
+# ---------------------------------------------------------------------------
+
+#: WGS84, as EPSG:4979 / 4978 have it
+WGS84_A = 6378137.0
+WGS84_F = 1.0 / 298.257223563
+#: steps of Bowring's latitude iteration, in numpy and in the kernel: one is
+#: the closed formula (up to 1.9e-10 rad off the converged foot point at
+#: factor 3, 500 km), two are converged to rounding, the third is margin
+EXPAND_STEPS = 3
+
+
+def _ecef(lat, lon):
+    """WGS84 geodetic (radians, height 0) -> ECEF metres, (..., 3).  Rule A:
+    a latitude at or beyond +-pi/2 is the pole itself, (0, 0, +-b), whatever
+    the longitude."""
+    b = WGS84_A * (1.0 - WGS84_F)
+    e2 = WGS84_F * (2.0 - WGS84_F)
+    s, c = np.sin(lat), np.cos(lat)
+    n = WGS84_A / np.sqrt(1.0 - e2 * s * s)
+    p = np.stack([n * c * np.cos(lon), n * c * np.sin(lon),
+                  n * (1.0 - e2) * s], axis=-1)
+    p[lat >= 0.5 * np.pi] = (0.0, 0.0, b)
+    p[lat <= -0.5 * np.pi] = (0.0, 0.0, -b)
+    return p
+
+
+def _per_cell(name, value, default, n):
+    value = np.asarray(default if value is None else value, dtype=np.float64)
+    if value.ndim == 0:
+        value = np.full(n, float(value))
+    if value.shape != (n,):
+        raise ValueError(
+            f'{name} of shape {value.shape}: expected a number or one value '
+            f'for each of the {n} cells')
+    if not np.isfinite(value).all():
+        raise ValueError(f'{name} holds NaN or Inf')
+    return value
+
+
+def expand_cells(centre_lat, centre_lon, corner_lat, corner_lon, count,
+                 expand_dist=None, expand_factor=None):
+    """
+    The reference's ``expand_scrip`` as one numpy statement, the definition
+    ``remap_expand_cells`` (the GPU kernel) is tested against: every cell's
+    corners moved away from the cell's centre.  ``centre_lat`` /
+    ``centre_lon`` ``(n,)`` and ``corner_lat`` / ``corner_lon``
+    ``(n, width)`` in radians, the first ``count[i]`` slots of row i valid;
+    ``expand_dist`` in metres (``None``: 0) and ``expand_factor`` (``None``:
+    1) a number or an ``(n,)`` array each.  Returns ``(lat, lon)``,
+    ``(n, width)``.
+
+    Per valid corner, in fp64: centre c and corner p go to ECEF on WGS84 at
+    height 0, ``d = |p - c|``, the target is ``t = c + ((factor * d + dist)
+    / d) * (p - c)``, and the result is the geodetic latitude and longitude
+    of t with its height dropped -- the reference's EPSG:4979 -> 4978 round
+    trip.  The latitude is the CONVERGED foot point on the ellipsoid:
+    ``EXPAND_STEPS`` steps of Bowring's iteration, a fixed count.
+
+    Three rules the reference does not state:
+
+    A. a corner (or centre) with ``|lat| >= pi/2`` is the exact pole, ECEF
+       ``(0, 0, +-b)`` whatever its longitude, as the overlap kernels make it
+       ``(0, 0, +-1)``: the two pole corners of a polar lat-lon cell differ
+       in longitude only and must come out as ONE point, bit for bit, or the
+       expanded cell is no simple polygon.  Such a corner crosses the pole
+       once the expansion exceeds the cell; the cell then holds the pole.
+    B. a corner equal to its centre (``d == 0``) stays where it is: it is the
+       fixed point of the expansion (the reference writes 0/0 = NaN).  The
+       vertex itself is a corner of a vertex cell beside a land mask.
+    C. slots beyond ``count[i]`` come back unchanged.
+
+    ``ValueError``: a non-finite input, an array whose length is not n, a
+    count outside ``[0, width]``, or a cell with ``factor * d + dist <= 0``
+    for a corner with ``d > 0`` (the first such cell is named).
+    """
+    corner_lat = np.asarray(corner_lat, dtype=np.float64)
+    corner_lon = np.asarray(corner_lon, dtype=np.float64)
+    if corner_lat.ndim != 2 or corner_lat.shape != corner_lon.shape:
+        raise ValueError(
+            f'corners of shapes {corner_lat.shape} and {corner_lon.shape}: '
+            f'expected two (n, width) arrays')
+    n, width = corner_lat.shape
+    centre_lat = np.asarray(centre_lat, dtype=np.float64)
+    centre_lon = np.asarray(centre_lon, dtype=np.float64)
+    count = np.asarray(count)
+    for name, a in (('centre_lat', centre_lat), ('centre_lon', centre_lon),
+                    ('count', count)):
+        if a.shape != (n,):
+            raise ValueError(f'{name} of shape {a.shape}: expected one value '
+                             f'for each of the {n} cells')
+    for name, a in (('centre_lat', centre_lat), ('centre_lon', centre_lon),
+                    ('corner_lat', corner_lat), ('corner_lon', corner_lon)):
+        if not np.isfinite(a).all():
+            raise ValueError(f'{name} holds NaN or Inf')
+    if n and (count.min() < 0 or count.max() > width):
+        raise ValueError(f'count outside [0, {width}]')
+    dist = _per_cell('expand_dist', expand_dist, 0.0, n)
+    factor = _per_cell('expand_factor', expand_factor, 1.0, n)
+    a, b = WGS84_A, WGS84_A * (1.0 - WGS84_F)
+    e2 = WGS84_F * (2.0 - WGS84_F)
+    ep2 = e2 / (1.0 - e2)
+    c = _ecef(centre_lat, centre_lon)[:, None, :]
+    v = _ecef(corner_lat, corner_lon) - c
+    d = np.sqrt(v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1] +
+                v[..., 2] * v[..., 2])
+    moves = (np.arange(width)[None, :] < count[:, None]) & (d > 0.0)
+    r = factor[:, None] * d + dist[:, None]
+    bad = moves & ~(r > 0.0)
+    if bad.any():
+        cell = int(np.nonzero(bad.any(axis=1))[0][0])
+        raise ValueError(
+            f'cell {cell}: expand_factor * d + expand_dist <= 0 for a corner '
+            f'at d = {d[cell][bad[cell]][0]:.6g} m from the centre')
+    with np.errstate(divide='ignore', invalid='ignore'):
+        g = r / d
+    g[~moves] = 1.0
+    t = c + g[..., None] * v
+    q = np.sqrt(t[..., 0] * t[..., 0] + t[..., 1] * t[..., 1])
+    z = t[..., 2]
+    th = np.arctan2(a * z, b * q)
+    for _ in range(EXPAND_STEPS):
+        s, co = np.sin(th), np.cos(th)
+        lat = np.arctan2(z + ep2 * b * (s * s * s), q - e2 * a * (co * co * co))
+        th = np.arctan2(b * np.sin(lat), a * np.cos(lat))
+    lon = np.arctan2(t[..., 1], t[..., 0])
+    return np.where(moves, lat, corner_lat), np.where(moves, lon, corner_lon)
+
+
+def _expanded_side(descriptor, expand_dist, expand_factor, device):
+    """The destination side of a smoothed :func:`conserve_polygons`: the
+    cells of :func:`cell_polygons` about the centres the reference writes as
+    ``grid_center_*``, widened on the GPU
+    (:func:`pyremap_amd.engine.expand_cells`) into a soup in which every
+    cell owns its nodes -- node ``i * width + k`` is corner k of cell i --
+    then cut into convex pieces as :func:`_polygon_side` does."""
+    from pyremap_amd import engine
+    voc, noc, lat, lon = cell_polygons(descriptor)
+    n, width = voc.shape
+    if isinstance(descriptor, MpasMeshDescriptor):
+        centres = _points(descriptor)
+        if centres is None:
+            raise ValueError(
+                'expanding the cells of an MPAS mesh needs their centres: '
+                'give the descriptor a mesh file')
+        dims = [n]
+    else:
+        centres = _cell_centres(descriptor)[:2]
+        ny, nx = descriptor.dim_sizes
+        dims = [nx, ny]
+    valid = np.arange(width)[None, :] < noc[:, None]
+    ids = np.where(valid, voc.astype(np.int64) - 1, 0)
+    torch = engine.require_gpu()
+
+    def dev(x, dtype=np.float64):
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=dtype)) \
+            .to(device)
+    out_lat, out_lon = engine.expand_cells(
+        dev(centres[0]), dev(centres[1]), dev(np.where(valid, lat[ids], 0.0)),
+        dev(np.where(valid, lon[ids], 0.0)), dev(noc, np.int32),
+        expand_dist, expand_factor)
+    lat = out_lat.cpu().numpy().reshape(-1)
+    lon = out_lon.cpu().numpy().reshape(-1)
+    own = np.arange(n * width, dtype=np.int64).reshape(n, width)
+    pvoc, pnoc, parent = convex_pieces(_unit_poles(lat, lon), own, noc)
+    return [pvoc, pnoc, lat, lon, None if len(parent) == n else parent,
+            n], n, dims
+
+
 def _polygon_side(descriptor):
     """(pieces for engine.overlap_pieces as numpy arrays, cells,
     Fortran-ordered dims) of one side of :func:`conserve_polygons`."""
@@ -1689,7 +1861,7 @@ def _polygon_side(descriptor):
 
 
 def conserve_polygons(src_descriptor, dst_descriptor, device=None,
-                      timing=None):
+                      timing=None, expand_dist=None, expand_factor=None):
     """
     First-order conservative weights between any two descriptors that have
     cells (:func:`cell_polygons`), the cells of MPAS edge and vertex meshes
@@ -1699,13 +1871,27 @@ def conserve_polygons(src_descriptor, dst_descriptor, device=None,
     (:func:`pyremap_amd.engine.overlap_pieces`), which adds the pieces'
     overlaps up per pair of cells: the side with more pieces is clipped by
     the other (the source on a tie).
+
+    ``expand_dist`` (metres) / ``expand_factor``, a number or one value per
+    destination cell each: with either one given (``None`` for the other is
+    0 m / 1) the DESTINATION cells are widened about their centres first
+    (:func:`expand_cells` has the definition; the kernel is
+    :func:`pyremap_amd.engine.expand_cells`), so that a destination cell
+    averages the source over a larger footprint -- the reference's smoothed
+    maps.  The source is never expanded; ``S = A / area(expanded cell)``.
+    The widened cells overlap each other, which the clipper does not mind.
     """
     from pyremap_amd import engine
     src, n_src, src_dims = _polygon_side(src_descriptor)
-    dst, n_dst, dst_dims = _polygon_side(dst_descriptor)
+    expand = expand_dist is not None or expand_factor is not None
+    if not expand:
+        dst, n_dst, dst_dims = _polygon_side(dst_descriptor)
     torch = engine.require_gpu()
     if device is None:
         device = f'cuda:{torch.cuda.current_device()}'
+    if expand:
+        dst, n_dst, dst_dims = _expanded_side(dst_descriptor, expand_dist,
+                                              expand_factor, device)
 
     def dev(side):
         return [x if x is None or isinstance(x, int) else
@@ -1955,7 +2141,8 @@ def _make_conserve(src_descriptor, dst_descriptor):
     return build_weights(src_descriptor, dst_descriptor, 'conserve')
 
 
-def make_weights(src_descriptor, dst_descriptor, method='conserve'):
+def make_weights(src_descriptor, dst_descriptor, method='conserve',
+                 expand_dist=None, expand_factor=None):
     """
     The mapping between any pair of descriptors this module serves, as a
     :class:`MappingFile`: :func:`build_weights`, plus ``bilinear`` and
@@ -1984,9 +2171,25 @@ def make_weights(src_descriptor, dst_descriptor, method='conserve'):
     rely on it as the statement of what the closed forms and the earlier
     searches serve.  :func:`write_weights`, and through it
     ``Remapper(map_tool='analytic').build_map()``, come here.
+
+    ``expand_dist`` (metres) / ``expand_factor`` (a number or one value per
+    destination cell each) are the reference's: they widen every DESTINATION
+    cell about its centre before the weights are made.  With ``conserve``
+    and either one given, the map is the smoothed one of
+    :func:`conserve_polygons`, for every destination that has cells and
+    whatever the source -- the lat-lon and same-projection pairs, which
+    otherwise keep their closed forms, included.  ``bilinear`` and
+    ``neareststod`` accept the two values and change nothing, as in the
+    reference: destination corners play no part in them.  With both ``None``
+    every call made is the one made without them.
     """
     if method not in METHODS:
         raise ValueError(f'method {method!r}: expected one of {METHODS}')
+    if method == 'conserve' and not (expand_dist is None and
+                                     expand_factor is None):
+        return conserve_polygons(src_descriptor, dst_descriptor,
+                                 expand_dist=expand_dist,
+                                 expand_factor=expand_factor)
     if method == 'conserve':
         return _make_conserve(src_descriptor, dst_descriptor)
     if not isinstance(src_descriptor, LatLon2DGridDescriptor):
@@ -2007,17 +2210,32 @@ def make_weights(src_descriptor, dst_descriptor, method='conserve'):
                            [lat.shape[1], lat.shape[0]], dims)
 
 
+def _expand_attr(value, default):
+    """What the mapping file says about expand_dist / expand_factor."""
+    value = np.asarray(default if value is None else value)
+    return float(value) if value.ndim == 0 else 'per cell'
+
+
 def write_weights(filename, src_descriptor, dst_descriptor,
-                  method='conserve'):
+                  method='conserve', expand_dist=None, expand_factor=None):
     """Build the weights (:func:`make_weights`) and write them as a mapping
-    file."""
+    file.  With ``expand_dist`` or ``expand_factor`` given (see
+    :func:`make_weights`; they shape ``conserve`` maps only) the file
+    records both as global attributes of these names, ``'per cell'`` for an
+    array."""
     from pyremap_amd.io.mapfile import write_mapping
-    m = make_weights(src_descriptor, dst_descriptor, method)
+    attrs = {'map_method': method,
+             'weight_generator': 'pyremap_amd.weights (analytic)',
+             'normalization': 'destarea',
+             'domain_a': str(src_descriptor.mesh_name),
+             'domain_b': str(dst_descriptor.mesh_name)}
+    if expand_dist is None and expand_factor is None:
+        m = make_weights(src_descriptor, dst_descriptor, method)
+    else:
+        m = make_weights(src_descriptor, dst_descriptor, method,
+                         expand_dist=expand_dist, expand_factor=expand_factor)
+        attrs['expand_dist'] = _expand_attr(expand_dist, 0.0)
+        attrs['expand_factor'] = _expand_attr(expand_factor, 1.0)
     write_mapping(filename, m.n_a, m.n_b, m.src_grid_dims, m.dst_grid_dims,
-                  m.row, m.col, m.S, m.frac_b,
-                  attrs={'map_method': method,
-                         'weight_generator': 'pyremap_amd.weights (analytic)',
-                         'normalization': 'destarea',
-                         'domain_a': str(src_descriptor.mesh_name),
-                         'domain_b': str(dst_descriptor.mesh_name)})
+                  m.row, m.col, m.S, m.frac_b, attrs=attrs)
     return m

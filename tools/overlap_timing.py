@@ -38,6 +38,18 @@ phases (prep, pairs, clip, sort, merge) and the share of the merge.
 remap_overlap_meshes on the same pair in the same process, the two calls
 alternating, ``--repeat`` warm calls each: minimum, median and maximum.
 
+    python tools/overlap_timing.py --expand 1.5:2e5 [--sizes 153:0.5,608:0]
+
+--expand FACTOR:DIST times the smoothed maps (expand_factor : expand_dist in
+metres).  Per ``n:r`` of --sizes, first remap_expand_cells alone on the corner
+slots of the icosahedral mesh n about its cell centres, ``--repeat`` warm
+calls, with the numpy statement (weights.expand_cells) once on the same
+arrays beside it; then, unless r is 0, the whole build mesh n -> global r
+degree lat-lon grid as weights.conserve_polygons makes it, with and without
+the expansion of the grid's cells: the kernel, the download and the convexity
+test on the host, remap_overlap_pieces (``--repeat`` warm calls, medians) and
+the candidate pairs and entries of either map.
+
 One JSON line per size: cells, grid cells, candidates, entries, ms.
 """
 import argparse
@@ -67,8 +79,13 @@ def main():
     ap.add_argument('--pieces', action='store_true',
                     help='with --meshes: remap_overlap_pieces with NULL '
                          'parents beside remap_overlap_meshes')
+    ap.add_argument('--expand', default=None,
+                    help='FACTOR:DIST (metres): remap_expand_cells alone and '
+                         'the build mesh -> lat-lon with and without it')
     ap.add_argument('--repeat', type=int, default=5)
     args = ap.parse_args()
+    if args.expand:
+        return time_expand(args.sizes, args.expand, args.repeat)
     if args.vertices:
         return time_vertices(args.vertices, args.repeat)
     if args.meshes and args.pieces:
@@ -390,6 +407,105 @@ def time_vertices(cases, repeat):
             row['max_sum_A_over_area_minus_1'] = float(
                 np.abs(given / a_area - 1.0).max())
         print(json.dumps(row), flush=True)
+
+
+def time_expand(sizes, expand, repeat):
+    import torch
+    from pyremap_amd import engine, synthetic, weights
+    from pyremap_amd.descriptor import get_lat_lon_descriptor
+    engine.require_gpu()
+    dev = 'cuda:0'
+    factor, dist = (float(x) for x in expand.split(':'))
+
+    def to_dev(a, dtype=np.float64):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
+
+    def corners(voc, noc, lat, lon):
+        valid = np.arange(voc.shape[1])[None, :] < noc[:, None]
+        ids = np.where(valid, voc.astype(np.int64) - 1, 0)
+        return np.where(valid, lat[ids], 0.0), np.where(valid, lon[ids], 0.0)
+
+    def kernel(args):
+        runs = []
+        for _ in range(repeat + 1):
+            timing = {}
+            out = engine.expand_cells(*args, expand_dist=dist,
+                                      expand_factor=factor, timing=timing)
+            runs.append(timing['ms'])
+        return out, runs
+    for item in sizes.split(','):
+        n, res = item.split(':')
+        n, res = int(n), float(res)
+        m = synthetic.icosahedral_mesh(n)
+        mesh = [m[k] for k in ('verticesOnCell', 'nEdgesOnCell', 'latVertex',
+                               'lonVertex')]
+        host = (m['latCell'], m['lonCell']) + corners(*mesh) + (mesh[1],)
+        args = [to_dev(x) for x in host[:4]] + [to_dev(host[4], np.int32)]
+        out, runs = kernel(args)
+        t0 = time.time()
+        want = weights.expand_cells(*host, expand_dist=dist,
+                                    expand_factor=factor)
+        numpy_s = time.time() - t0
+        row = {'mesh_cells': int(len(mesh[1])),
+               'slots': int(host[2].size), 'factor': factor, 'dist_m': dist,
+               'kernel_ms_first': round(runs[0], 3),
+               'kernel_ms': _spread(runs[1:]),
+               'numpy_s': round(numpy_s, 3),
+               'max_dlat': float(np.abs(out[0].cpu().numpy()
+                                        - want[0]).max())}
+        del out, want, args
+        print(json.dumps(row), flush=True)
+        if res == 0:
+            continue
+        grid = get_lat_lon_descriptor(res, res)
+        gvoc, gnoc, glat, glon = weights.cell_polygons(grid)
+        clat, clon, _ = weights._cell_centres(grid)
+        n_grid = len(gnoc)
+        src = [to_dev(a, a.dtype) for a in mesh] + [None, len(mesh[1])]
+        for wide in (False, True):
+            t0 = time.time()
+            if wide:
+                cells = [to_dev(clat), to_dev(clon)] + \
+                    [to_dev(x) for x in corners(gvoc, gnoc, glat, glon)] + \
+                    [to_dev(gnoc, np.int32)]
+                out, runs = kernel(cells)
+                lat, lon = (x.cpu().numpy().reshape(-1) for x in out)
+                poly = np.arange(n_grid * 4, dtype=np.int64).reshape(-1, 4)
+            else:
+                lat, lon, poly, runs = glat, glon, gvoc.astype(np.int64) - 1, \
+                    [0.0, 0.0]
+            t1 = time.time()
+            pvoc, pnoc, parent = weights.convex_pieces(
+                weights._unit_poles(lat, lon), poly, gnoc)
+            host_s = time.time() - t1
+            dst = [to_dev(a, a.dtype) for a in (pvoc, pnoc, lat, lon)] + \
+                [None if len(parent) == n_grid else to_dev(parent, np.int32),
+                 n_grid]
+            src_is_a = len(mesh[1]) >= len(pnoc)
+            a, b = (src, dst) if src_is_a else (dst, src)
+            timings = []
+            for _ in range(repeat + 1):
+                timing = {}
+                ov = engine.overlap_pieces(a, b, dst_is_b=src_is_a,
+                                           timing=timing)
+                torch.cuda.synchronize()
+                timings.append(timing)
+            entries = int(len(ov[0]))
+            del ov
+            print(json.dumps({
+                'mesh_cells': int(len(mesh[1])), 'grid': f'{res}deg',
+                'grid_cells': int(n_grid), 'expanded': wide,
+                'factor': factor if wide else None,
+                'dist_m': dist if wide else None,
+                'pieces': int(len(pnoc)),
+                'candidates': int(timings[-1]['n_pairs']),
+                'entries': entries,
+                'expand_kernel_ms': _spread(runs[1:])['median'],
+                'host_convex_s': round(host_s, 2),
+                'overlap_ms_first': round(timings[0]['ms'], 3),
+                'overlap_ms': _spread([x['ms'] for x in timings[1:]]),
+                'build_first_call_s': round(time.time() - t0, 2)}),
+                flush=True)
 
 
 def time_grids(cases, sample, repeat):
