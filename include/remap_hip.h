@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define REMAP_ABI_VERSION 29
+#define REMAP_ABI_VERSION 30
 
 /* The library is built with -fvisibility=hidden: the entry points declared
  * here, and nothing else, are its dynamic symbols. */
@@ -1409,6 +1409,77 @@ int remap_expand_cells(int64_t n_cells, int32_t width,
                        int32_t dist_stride, const double *factor,
                        int32_t factor_stride, double *out_lat,
                        double *out_lon, int32_t *status, void *stream);
+
+/*
+ * ---------------------------------------------------------------------------
+ * What a complete mapping file says about its grids beyond the weights
+ * (remap_geometry.hip): cell areas (area_a, area_b) and the fraction of every
+ * source cell that takes part in the map (frac_a).
+ *
+ * remap_cell_areas: the area in steradians of every cell given in SCRIP
+ * layout -- corner_lat / corner_lon (n_cells, width) row-major, radians, the
+ * first count[i] slots of row i valid, 0 <= count[i] <= width -- as the
+ * great-circle polygon of those corners.  Corners become unit vectors (a
+ * latitude >= pi/2 or <= -pi/2 is the pole itself, whatever the longitude),
+ * consecutive equal corners are dropped, the copies of corner 0 that close
+ * the ring are dropped, and the area is
+ *     | sum_k t(p_0, p_k, p_k+1) |,
+ *     t(a, b, c) = 2 atan2(a . ((b - a) x (c - a)), 1 + a.b + b.c + c.a)
+ * added in ascending k: the ring, the fan and the triangle of the overlap
+ * calls' cell preparation (one device function serves both), so an MPAS
+ * cell has the same bits here as in their a_area_out / b_area_out.  The sum
+ * is signed, the absolute value is taken last: clockwise rings and concave
+ * cells come out right.  Fewer than 3 corners left: 0.
+ *
+ * status: two int32 on the device, the call's scratch.  The call WAITS for
+ * its kernel on `stream` and reads them back.
+ *
+ *   REMAP_ERR_ARG          a NULL array, n_cells < 0 or > 2^31 - 1, width <
+ *                          1, or a count[i] outside [0, width] (the message
+ *                          names the lowest such cell; its area_out is 0)
+ *   REMAP_ERR_UNSUPPORTED  width > REMAP_CELL_AREAS_MAX_WIDTH
+ *   n_cells == 0           REMAP_OK, nothing is launched (status must still
+ *                          be given)
+ * ---------------------------------------------------------------------------
+ */
+#define REMAP_CELL_AREAS_MAX_WIDTH 32
+
+REMAP_API
+int remap_cell_areas(int64_t n_cells, int32_t width, const double *corner_lat,
+                     const double *corner_lon, const int32_t *count,
+                     double *area_out, int32_t *status, void *stream);
+
+/*
+ * remap_column_fractions: out[j] (n_cols) = the sum of value[k] over the
+ * entries with col[k] - index_base == j, added in ASCENDING k starting from
+ * +0.0 -- numpy's bincount(col, weights=value) on the same entry order, bit
+ * for bit -- then, for a column that has entries, divided by denom[j] when
+ * denom is not NULL and replaced by 1 when clamp != 0 and it exceeds 1.  A
+ * column without entries is +0.0.  With value = the overlap areas A (or
+ * S * area_b[row]), denom = area_a and clamp = 1 this is ESMF's frac_a.
+ *
+ * No floating-point atomics: the entries are regrouped by column with a
+ * stable radix sort (rocPRIM radix_sort_pairs, as remap_csr_from_coo; equal
+ * keys keep their input order) and one lane adds one column up in that
+ * order, so two calls give the same bytes.  A long column is added by its
+ * one lane, serially.  Entries whose column is outside [0, n_cols) are left
+ * out and counted in *bad_out (device, int64); nothing synchronises.
+ *
+ *   REMAP_ERR_ARG          a NULL array that is needed, a negative size
+ *   REMAP_ERR_UNSUPPORTED  n_cols >= 2^31 or n_entries >= 2^32 - 1
+ *   REMAP_ERR_WORKSPACE    workspace_bytes below
+ *                          remap_column_fractions_workspace()'s answer
+ */
+REMAP_API
+int remap_column_fractions_workspace(int64_t n_entries, size_t *bytes_out);
+
+REMAP_API
+int remap_column_fractions(int64_t n_entries, int64_t n_cols,
+                           const int32_t *col, int32_t index_base,
+                           const double *value, const double *denom,
+                           int32_t clamp, double *out, int64_t *bad_out,
+                           void *workspace, size_t workspace_bytes,
+                           void *stream);
 
 #ifdef __cplusplus
 }

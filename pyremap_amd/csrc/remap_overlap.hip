@@ -59,6 +59,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "remap_common.h"
+#include "remap_sphere.h"
 
 namespace remap {
 namespace {
@@ -83,50 +84,9 @@ constexpr double kMinCos = 0.1;
 constexpr double kSliver = 1e-14;
 // slack of the boxes, radians (rounding of the corners' lat / lon)
 constexpr double kBoxEps = 1e-9;
-constexpr double kPi = 3.14159265358979323846;
-constexpr double kHalfPi = 0.5 * kPi;
-constexpr double kTwoPi = 2.0 * kPi;
 
 constexpr size_t kAlign = 256;
 size_t align_up(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
-
-struct V3 {
-    double x, y, z;
-};
-
-__device__ inline V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ inline double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ inline V3 cross(V3 a, V3 b)
-{
-    return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z,
-            a.x * b.y - a.y * b.x};
-}
-__device__ inline V3 normalized(V3 a)
-{
-    const double r = sqrt(dot(a, a));
-    return {a.x / r, a.y / r, a.z / r};
-}
-
-// a pole is exactly (0, 0, +-1): every corner at +-90 deg is the same point
-__device__ inline V3 unit_latlon(double lat, double lon)
-{
-    if (lat >= kHalfPi)
-        return {0.0, 0.0, 1.0};
-    if (lat <= -kHalfPi)
-        return {0.0, 0.0, -1.0};
-    const double c = cos(lat);
-    return {c * cos(lon), c * sin(lon), sin(lat)};
-}
-
-// signed area of the spherical triangle (a, b, c) (Van Oosterom-Strackee;
-// the triple product from the edge vectors at a keeps its relative accuracy
-// for small triangles)
-__device__ inline double tri_area(V3 a, V3 b, V3 c)
-{
-    const double num = dot(a, cross(sub(b, a), sub(c, a)));
-    const double den = 1.0 + dot(a, b) + dot(b, c) + dot(c, a);
-    return 2.0 * atan2(num, den);
-}
 
 // the lat-lon cell with 0-based index g = j * n_lon + i, corners SW, SE, NE,
 // NW (swapped to SW, NW, NE, SE when exactly one axis descends, so that the

@@ -58,9 +58,15 @@ class MeshDescriptor:
         self.logger = None
 
     def to_scrip(self, scrip_filename, expand_dist=None, expand_factor=None):
-        raise NotImplementedError(
-            'SCRIP files feed ESMF/MOAB weight generation, which is outside '
-            'the scope of pyremap_amd (it applies existing weights)')
+        """Write this descriptor's SCRIP file (every reference descriptor's
+        ``to_scrip``): :func:`pyremap_amd.scrip.write_scrip`.  With
+        ``expand_dist`` (metres) or ``expand_factor`` given, a number or one
+        value per cell each, the corners are moved away from the cells'
+        centres first.  A ``ValueError`` names what the descriptor lacks
+        (``filename``, ``mesh_name``, ...)."""
+        from pyremap_amd.scrip import write_scrip
+        write_scrip(self, scrip_filename, expand_dist=expand_dist,
+                    expand_factor=expand_factor)
 
     def write_netcdf(self, ds, filename):
         """``mesh_descriptor.py:93-112``: write ``ds`` in this descriptor's

@@ -51,7 +51,7 @@ CELL_MAX_RUN = 4
 DTYPE_F64 = 0
 DTYPE_F32 = 1
 
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 #: readable pad entries kept behind col/val (remap_csr.csr_pad)
 CSR_PAD = 8
@@ -85,6 +85,8 @@ EXPORTS = (
     'remap_locate_workspace', 'remap_locate', 'remap_locate_timed',
     'remap_quads_workspace', 'remap_quads', 'remap_quads_timed',
     'remap_expand_cells',
+    'remap_cell_areas', 'remap_column_fractions_workspace',
+    'remap_column_fractions',
 )
 
 
@@ -534,6 +536,18 @@ def load_library():
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.remap_cell_areas.restype = ctypes.c_int
+    lib.remap_cell_areas.argtypes = [
+        ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.remap_column_fractions_workspace.restype = ctypes.c_int
+    lib.remap_column_fractions_workspace.argtypes = [
+        ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]
+    lib.remap_column_fractions.restype = ctypes.c_int
+    lib.remap_column_fractions.argtypes = [
+        ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
     if lib.remap_abi_version() != ABI_VERSION:
         raise EngineError(
             f'{path} has ABI {lib.remap_abi_version()}, expected '
@@ -2867,3 +2881,129 @@ def expand_cells(centre_lat, centre_lon, corner_lat, corner_lon, count,
             t1.synchronize()
             timing['ms'] = t0.elapsed_time(t1)
     return out_lat, out_lon
+
+
+# ---------------------------------------------------------------------------
+# what a complete mapping file says about its grids: areas and frac_a
+# ---------------------------------------------------------------------------
+
+#: REMAP_CELL_AREAS_MAX_WIDTH
+CELL_AREAS_MAX_WIDTH = 32
+
+
+def cell_areas(corner_lat, corner_lon, count, timing=None):
+    """
+    The area in steradians of every cell given in SCRIP layout, through
+    ``remap_cell_areas`` (``include/remap_hip.h`` has the definition;
+    :func:`pyremap_amd.weights.cell_areas` is the same statement in numpy):
+    ``corner_lat`` / ``corner_lon`` ``(n, width)`` fp64 tensors in radians
+    and ``count (n,)`` integers on one HIP device, the first ``count[i]``
+    corners of row i the cell's great-circle polygon.  Returns a new ``(n,)``
+    fp64 tensor.  Runs on the current stream and waits for it.  A count
+    outside ``[0, width]`` is a ``ValueError`` that names the first such
+    cell (the library's ``REMAP_ERR_ARG``).  ``timing``: a dict that
+    receives the GPU ``ms`` of the call.
+    """
+    torch = require_gpu()
+    lib = load_library()
+    if not torch.is_tensor(corner_lat) or not corner_lat.is_cuda or \
+            corner_lat.dim() != 2 or corner_lat.shape[1] < 1:
+        raise ValueError('corner_lat: expected an (n, width) tensor on a HIP '
+                         'device, width >= 1')
+    dev = corner_lat.device
+    n, width = corner_lat.shape
+    if not torch.is_tensor(corner_lon) or corner_lon.device != dev or \
+            tuple(corner_lon.shape) != (n, width):
+        raise ValueError(f'corner_lon: expected a tensor of shape '
+                         f'{(n, width)} on {dev}')
+    if not torch.is_tensor(count) or count.device != dev or \
+            tuple(count.shape) != (n,) or count.dtype.is_floating_point:
+        raise ValueError(f'count: expected {n} integers on {dev}')
+    corner_lat = corner_lat.to(torch.float64).contiguous()
+    corner_lon = corner_lon.to(torch.float64).contiguous()
+    count = count.to(torch.int32).contiguous()
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        area = torch.empty(n, dtype=torch.float64, device=dev)
+        status = torch.zeros(2, dtype=torch.int32, device=dev)
+        if timing is not None:
+            t0 = torch.cuda.Event(enable_timing=True)
+            t1 = torch.cuda.Event(enable_timing=True)
+            t0.record()
+        rc = lib.remap_cell_areas(n, width, _ptr(corner_lat),
+                                  _ptr(corner_lon), _ptr(count), _ptr(area),
+                                  _ptr(status), stream)
+        if rc == -1:     # REMAP_ERR_ARG
+            raise ValueError(
+                lib.remap_last_error().decode('utf-8', 'replace'))
+        _check(rc, 'remap_cell_areas')
+        if timing is not None:
+            t1.record()
+            t1.synchronize()
+            timing['ms'] = t0.elapsed_time(t1)
+    return area
+
+
+def column_fractions(col, value, n_cols, denom=None, clamp=False,
+                     index_base=0, timing=None):
+    """
+    ``out[j] = sum of value[k] over col[k] - index_base == j``, added in
+    ascending k -- ``np.bincount(col, weights=value, minlength=n_cols)``, bit
+    for bit -- then divided by ``denom[j]`` when ``denom`` is given and cut
+    to at most 1 when ``clamp`` is set; a column without entries is 0.
+    Through ``remap_column_fractions`` (``include/remap_hip.h``;
+    :func:`pyremap_amd.weights.column_fractions` is the numpy statement):
+    ``col`` integers and ``value`` fp64, 1-D tensors of one length on one
+    HIP device, ``denom`` ``(n_cols,)`` fp64 there.  Returns a new
+    ``(n_cols,)`` fp64 tensor; two calls give the same bytes.  An entry whose
+    column is outside ``[0, n_cols)`` is a ``ValueError`` (the count is read
+    back, which waits for the stream).  ``timing``: a dict that receives the
+    GPU ``ms`` of the call.
+    """
+    torch = require_gpu()
+    lib = load_library()
+    if not torch.is_tensor(value) or not value.is_cuda or value.dim() != 1:
+        raise ValueError('value: expected a 1-D tensor on a HIP device')
+    dev = value.device
+    n = value.shape[0]
+    n_cols = int(n_cols)
+    if not torch.is_tensor(col) or col.device != dev or \
+            tuple(col.shape) != (n,) or col.dtype.is_floating_point:
+        raise ValueError(f'col: expected {n} integers on {dev}')
+    if n and (int(col.max()) > 2 ** 31 - 1 or int(col.min()) < -2 ** 31):
+        raise ValueError('col: beyond int32')
+    if denom is not None and (
+            not torch.is_tensor(denom) or denom.device != dev or
+            tuple(denom.shape) != (n_cols,)):
+        raise ValueError(f'denom: expected a tensor of shape ({n_cols},) on '
+                         f'{dev}')
+    col = col.to(torch.int32).contiguous()
+    value = value.to(torch.float64).contiguous()
+    if denom is not None:
+        denom = denom.to(torch.float64).contiguous()
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        need = ctypes.c_size_t(0)
+        _check(lib.remap_column_fractions_workspace(n, ctypes.byref(need)),
+               'remap_column_fractions_workspace')
+        workspace = torch.empty(max(need.value, 1), dtype=torch.uint8,
+                                device=dev)
+        out = torch.empty(n_cols, dtype=torch.float64, device=dev)
+        bad = torch.zeros(1, dtype=torch.int64, device=dev)
+        if timing is not None:
+            t0 = torch.cuda.Event(enable_timing=True)
+            t1 = torch.cuda.Event(enable_timing=True)
+            t0.record()
+        _check(lib.remap_column_fractions(
+            n, n_cols, _ptr(col), int(index_base), _ptr(value), _ptr(denom),
+            1 if clamp else 0, _ptr(out), _ptr(bad), _ptr(workspace),
+            need.value, stream), 'remap_column_fractions')
+        if timing is not None:
+            t1.record()
+            t1.synchronize()
+            timing['ms'] = t0.elapsed_time(t1)
+        n_bad = int(bad.item())
+    if n_bad:
+        raise ValueError(f'{n_bad} entries name a column outside '
+                         f'[0, {n_cols})')
+    return out

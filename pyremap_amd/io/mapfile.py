@@ -19,6 +19,26 @@ import numpy as np
 
 REQUIRED = ('src_grid_dims', 'dst_grid_dims', 'col', 'row', 'S', 'frac_b')
 
+#: what ESMF's files say about the two grids beyond the weights, optional
+#: here: name -> (dims, dtype, units).  Centres and corners in degrees, the
+#: corners (n, nv) with the last one repeated where a cell has fewer; areas
+#: in steradians; frac_a the covered fraction of every source cell.
+GEOMETRY = OrderedDict([
+    ('yc_a', (('n_a',), np.float64, 'degrees')),
+    ('yc_b', (('n_b',), np.float64, 'degrees')),
+    ('xc_a', (('n_a',), np.float64, 'degrees')),
+    ('xc_b', (('n_b',), np.float64, 'degrees')),
+    ('yv_a', (('n_a', 'nv_a'), np.float64, 'degrees')),
+    ('xv_a', (('n_a', 'nv_a'), np.float64, 'degrees')),
+    ('yv_b', (('n_b', 'nv_b'), np.float64, 'degrees')),
+    ('xv_b', (('n_b', 'nv_b'), np.float64, 'degrees')),
+    ('mask_a', (('n_a',), np.int32, 'unitless')),
+    ('mask_b', (('n_b',), np.int32, 'unitless')),
+    ('area_a', (('n_a',), np.float64, 'square radians')),
+    ('area_b', (('n_b',), np.float64, 'square radians')),
+    ('frac_a', (('n_a',), np.float64, 'unitless')),
+])
+
 
 def _native(a):
     a = np.asarray(a)
@@ -26,10 +46,19 @@ def _native(a):
 
 
 class MappingFile:
-    """The members of a mapping file that the remapping path consumes."""
+    """The members of a mapping file that the remapping path consumes, and
+    -- optional, ``None`` where a file or a caller has none -- the ones of
+    :data:`GEOMETRY`, which it does not."""
 
     def __init__(self, n_a, n_b, src_grid_dims, dst_grid_dims, row, col, S,
-                 frac_b):
+                 frac_b, **geometry):
+        unknown = sorted(set(geometry) - set(GEOMETRY))
+        if unknown:
+            raise TypeError(f'unknown mapping-file members {unknown}')
+        for name, (_, dtype, _) in GEOMETRY.items():
+            value = geometry.get(name)
+            setattr(self, name, None if value is None else
+                    np.ascontiguousarray(value, dtype=dtype))
         self.n_a = int(n_a)
         self.n_b = int(n_b)
         #: as stored in the file: Fortran order
@@ -52,6 +81,12 @@ class MappingFile:
     @property
     def n_s(self):
         return int(self.S.shape[0])
+
+    @property
+    def geometry(self):
+        """The members of :data:`GEOMETRY` that are set, by name."""
+        return OrderedDict((k, getattr(self, k)) for k in GEOMETRY
+                           if getattr(self, k) is not None)
 
 
 def _magic(filename):
@@ -83,8 +118,9 @@ def _read_npz(filename):
             n_a = int(z['n_a'])
         else:
             n_a = int(np.prod(z['src_grid_dims']))
+        extra = {k: z[k] for k in GEOMETRY if k in z}
         return MappingFile(n_a, n_b, z['src_grid_dims'], z['dst_grid_dims'],
-                           z['row'], z['col'], z['S'], z['frac_b'])
+                           z['row'], z['col'], z['S'], z['frac_b'], **extra)
 
 
 def _read_netcdf3(filename):
@@ -97,9 +133,13 @@ def _read_netcdf3(filename):
     for dim in ('n_a', 'n_b'):
         if dim not in nc.dimensions:
             raise ValueError(f'{filename}: missing dimension {dim}')
+    extra = {k: _native(nc.variables[k].data) for k in GEOMETRY
+             if k in nc.variables}
     return MappingFile(nc.dimensions['n_a'], nc.dimensions['n_b'],
                        get['src_grid_dims'], get['dst_grid_dims'],
-                       get['row'], get['col'], get['S'], get['frac_b'])
+                       get['row'], get['col'], get['S'], get['frac_b'],
+                       **_whole(extra, nc.dimensions['n_a'],
+                                nc.dimensions['n_b']))
 
 
 def _read_hdf5(filename):
@@ -115,12 +155,54 @@ def _read_hdf5(filename):
         n_a = nc.dimensions.get('n_a')
         if n_a is None:
             n_a = int(np.prod(get['src_grid_dims']))
+        extra = {k: _native(nc.variables[k].read()) for k in GEOMETRY
+                 if k in nc.variables}
     return MappingFile(n_a, n_b, get['src_grid_dims'], get['dst_grid_dims'],
-                       get['row'], get['col'], get['S'], get['frac_b'])
+                       get['row'], get['col'], get['S'], get['frac_b'],
+                       **_whole(extra, n_a, n_b))
+
+
+def _whole(extra, n_a, n_b):
+    """The optional members a file holds with the expected leading length
+    (a file of another writer may carry them under other shapes: those are
+    left out rather than refused, the remapping path does not need them)."""
+    size = {'n_a': int(n_a), 'n_b': int(n_b)}
+    return {k: v for k, v in extra.items()
+            if v.ndim == len(GEOMETRY[k][0]) and
+            v.shape[0] == size[GEOMETRY[k][0][0]]}
+
+
+def _checked_geometry(geometry, n_a, n_b):
+    """``geometry`` (a mapping or a :class:`MappingFile`) as name -> array in
+    the order, dtypes and shapes of :data:`GEOMETRY`; the corner arrays of
+    one side go together."""
+    if isinstance(geometry, MappingFile):
+        geometry = geometry.geometry
+    unknown = sorted(set(geometry) - set(GEOMETRY))
+    if unknown:
+        raise ValueError(f'unknown mapping-file members {unknown}')
+    size = {'n_a': int(n_a), 'n_b': int(n_b)}
+    out = OrderedDict()
+    for name, (dims, dtype, _) in GEOMETRY.items():
+        if geometry.get(name) is None:
+            continue
+        value = np.ascontiguousarray(geometry[name], dtype=dtype)
+        if value.ndim != len(dims) or value.shape[0] != size[dims[0]]:
+            raise ValueError(
+                f'{name} of shape {value.shape}: expected '
+                f'({", ".join(dims)}) with {dims[0]} = {size[dims[0]]}')
+        out[name] = value
+    for side in 'ab':
+        pair = [out.get(f'{v}v_{side}') for v in 'xy']
+        if (pair[0] is None) != (pair[1] is None) or (
+                pair[0] is not None and pair[0].shape != pair[1].shape):
+            raise ValueError(f'xv_{side} and yv_{side} go together, with '
+                             f'one shape')
+    return out
 
 
 def write_mapping(filename, n_a, n_b, src_grid_dims, dst_grid_dims, row, col,
-                  S, frac_b, attrs=None, format=None):
+                  S, frac_b, attrs=None, format=None, geometry=None):
     """
     Write a mapping file with the schema of SURVEY.md Appendix A.
     ``*.npz`` -> numpy archive; otherwise ``format`` is ``'NETCDF4'`` (what
@@ -129,6 +211,13 @@ def write_mapping(filename, n_a, n_b, src_grid_dims, dst_grid_dims, row, col,
     64-bit-data flavour when a variable outgrows 4 GiB.
     ``src_grid_dims`` / ``dst_grid_dims`` are in FILE (Fortran) order and
     ``row`` / ``col`` are 1-based, exactly as ESMF writes them.
+
+    ``geometry``: a mapping (or a :class:`MappingFile`) with any of the
+    members of :data:`GEOMETRY` -- ``area_a, area_b, frac_a, xc_*, yc_*,
+    xv_*, yv_*, mask_*`` -- written under ESMF's names, dimensions (``nv_a``,
+    ``nv_b`` for the corners) and ``units`` attributes.  Without it the file
+    is, byte for byte, the one this function has always written (an
+    ``area_a`` of zeros keeps ``n_a`` a used dimension).
     """
     row = np.asarray(row, dtype=np.int32)
     col = np.asarray(col, dtype=np.int32)
@@ -136,10 +225,11 @@ def write_mapping(filename, n_a, n_b, src_grid_dims, dst_grid_dims, row, col,
     frac_b = np.asarray(frac_b, dtype=np.float64)
     src_grid_dims = np.asarray(src_grid_dims, dtype=np.int32)
     dst_grid_dims = np.asarray(dst_grid_dims, dtype=np.int32)
+    extra = _checked_geometry(geometry, n_a, n_b) if geometry else {}
     if filename.endswith('.npz'):
         np.savez(filename, n_a=np.int64(n_a), n_b=np.int64(n_b),
                  src_grid_dims=src_grid_dims, dst_grid_dims=dst_grid_dims,
-                 row=row, col=col, S=S, frac_b=frac_b)
+                 row=row, col=col, S=S, frac_b=frac_b, **extra)
         return
     from pyremap_amd.io import netcdf3
     dims = OrderedDict([
@@ -153,19 +243,28 @@ def write_mapping(filename, n_a, n_b, src_grid_dims, dst_grid_dims, row, col,
         ('row', ('n_s',), row),
         ('S', ('n_s',), S),
         ('frac_b', ('n_b',), frac_b),
-        # keeps n_a a used dimension, as in ESMF files
-        ('area_a', ('n_a',), np.zeros(int(n_a))),
     ]
+    var_attrs = {}
+    if 'area_a' not in extra:
+        # keeps n_a a used dimension, as in ESMF files
+        variables.append(('area_a', ('n_a',), np.zeros(int(n_a))))
+    for name, value in extra.items():
+        if value.ndim == 2:
+            dims[GEOMETRY[name][0][1]] = int(value.shape[1])
+        variables.append((name, GEOMETRY[name][0], value))
+        var_attrs[name] = {'units': GEOMETRY[name][2]}
     if format is None:
         big = max(v[2].nbytes for v in variables) >= (1 << 32) - 4
         format = 'NETCDF3_64BIT_DATA' if big else 'NETCDF3_64BIT'
     if format in ('NETCDF4', 'NETCDF4_CLASSIC'):
         from pyremap_amd.io.hdf5_write import write_netcdf4
-        write_netcdf4(filename, dims, [v + ({},) for v in variables],
+        write_netcdf4(filename, dims,
+                      [v + (var_attrs.get(v[0], {}),) for v in variables],
                       attrs=attrs or {})
         return
     if format not in netcdf3.FORMATS:
         raise ValueError(f'unknown mapping-file format {format!r}')
     netcdf3.write(filename, dims,
-                  [netcdf3.Variable(*v) for v in variables],
+                  [netcdf3.Variable(*v, attrs=var_attrs.get(v[0]))
+                   for v in variables],
                   attrs=attrs or {}, version=netcdf3.FORMATS[format])

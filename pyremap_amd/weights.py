@@ -86,6 +86,23 @@ axes the common methods have closed forms:
 The result is a :class:`pyremap_amd.io.mapfile.MappingFile` with exactly the
 schema ESMF writes (1-based ``row``/``col``, Fortran-ordered grid dims), so it
 goes through the same ``_load_mapping`` as any other mapping file.
+
+The maps of :func:`make_weights` are COMPLETE (:func:`complete_mapping`):
+beside the weights they carry what ESMF's files say about the two grids --
+``xc, yc, xv, yv`` (degrees) and ``mask`` from the one statement of a
+descriptor's SCRIP geometry (:func:`pyremap_amd.scrip.scrip_geometry`, which
+also feeds every descriptor's ``to_scrip``), ``area_a`` / ``area_b`` in
+steradians and ``frac_a``.  On the GPU conserve paths the areas are the
+overlap call's own and ``frac_a`` the overlap areas added up per source cell
+in entry order, over ``area_a``, at most 1 (``remap_column_fractions``);
+everywhere else the areas are the great-circle polygons of the SCRIP corners
+(``remap_cell_areas``; :func:`cell_areas` and :func:`column_fractions` are
+the numpy statements, used where there is no GPU), ``frac_a`` of a
+closed-form ``conserve`` pair the column sums of ``S * area_b[row]`` and of
+``bilinear`` / ``neareststod`` 0, as ESMF's format documents.  With
+``expand_dist`` / ``expand_factor`` the destination's corners and ``area_b``
+are the widened ones.  No ESMF-written file pins these variables; the
+identities of tests/test_gpu_geometry.py do.
 """
 import numpy as np
 
@@ -1156,6 +1173,9 @@ def conserve_mesh_latlon(mesh_descriptor, grid_descriptor, mesh_is_src=True,
     dst, src, A, frac_b, mesh_area, grid_area = engine.overlap_latlon(
         dev(voc), dev(noc), dev(lat_v), dev(lon_v), dev(lat_e), dev(lon_e),
         slack, dst_is_mesh=not mesh_is_src, timing=timing)
+    src_area = mesh_area if mesh_is_src else grid_area
+    frac_a = engine.column_fractions(src, A, len(src_area), denom=src_area,
+                                     clamp=True).cpu().numpy()
     dst = dst.cpu().numpy()
     src = src.cpu().numpy()
     A = A.cpu().numpy()
@@ -1171,7 +1191,8 @@ def conserve_mesh_latlon(mesh_descriptor, grid_descriptor, mesh_is_src=True,
         n_a, n_b, src_dims, dst_dims = n_grid, n_mesh, grid_dims, mesh_dims
     return MappingFile(n_a, n_b, src_dims, dst_dims,
                        (dst + 1).astype(np.int32), (src + 1).astype(np.int32),
-                       S, frac_b)
+                       S, frac_b, area_a=src_area.cpu().numpy(),
+                       area_b=dst_area, frac_a=frac_a)
 
 
 def conserve_mesh_mesh(src_descriptor, dst_descriptor, device=None,
@@ -1200,6 +1221,10 @@ def conserve_mesh_mesh(src_descriptor, dst_descriptor, device=None,
     mesh_a, mesh_b = (src, dst) if src_is_a else (dst, src)
     row, col, A, frac_b, a_area, b_area = engine.overlap_meshes(
         dev(mesh_a), dev(mesh_b), dst_is_b=src_is_a, timing=timing)
+    src_area = a_area if src_is_a else b_area
+    frac_a = engine.column_fractions(col, A, len(src_area), denom=src_area,
+                                     clamp=True).cpu().numpy()
+    src_area = src_area.cpu().numpy()
     row = row.cpu().numpy()
     col = col.cpu().numpy()
     A = A.cpu().numpy()
@@ -1209,7 +1234,8 @@ def conserve_mesh_mesh(src_descriptor, dst_descriptor, device=None,
     return MappingFile(n_src, n_dst, np.array([n_src], dtype=np.int32),
                        np.array([n_dst], dtype=np.int32),
                        (row + 1).astype(np.int32), (col + 1).astype(np.int32),
-                       S, frac_b)
+                       S, frac_b, area_a=src_area, area_b=dst_area,
+                       frac_a=frac_a)
 
 
 # ---------------------------------------------------------------------------
@@ -1298,6 +1324,10 @@ def conserve_grid(src_descriptor, dst_descriptor, device=None, timing=None):
     side_a, side_b = (src, dst) if src_is_a else (dst, src)
     row, col, A, frac_b, a_area, b_area = engine.overlap_grids(
         dev(side_a), dev(side_b), dst_is_b=src_is_a, timing=timing)
+    src_area = a_area if src_is_a else b_area
+    frac_a = engine.column_fractions(col, A, len(src_area), denom=src_area,
+                                     clamp=True).cpu().numpy()
+    src_area = src_area.cpu().numpy()
     row = row.cpu().numpy()
     col = col.cpu().numpy()
     A = A.cpu().numpy()
@@ -1307,7 +1337,8 @@ def conserve_grid(src_descriptor, dst_descriptor, device=None, timing=None):
     return MappingFile(n_src, n_dst, np.array(src_dims, dtype=np.int32),
                        np.array(dst_dims, dtype=np.int32),
                        (row + 1).astype(np.int32), (col + 1).astype(np.int32),
-                       S, frac_b)
+                       S, frac_b, area_a=src_area, area_b=dst_area,
+                       frac_a=frac_a)
 
 
 # ---------------------------------------------------------------------------
@@ -1401,44 +1432,14 @@ def _projected_corners(descriptor):
     return np.radians(lat), np.radians(lon)
 
 
-def cell_polygons(descriptor):
+def cell_rings(descriptor):
     """
-    The cells of a descriptor as polygons: ``(verticesOnCell (n, width)
-    1-based, nEdgesOnCell, lat, lon)`` as :func:`mesh_polygons` gives them
-    for an MPAS cell mesh, ``lat`` / ``lon`` (radians) the coordinates of the
-    nodes the indices point to.
-
-    * MPAS cell mesh: :func:`mesh_polygons`.
-    * MPAS edge mesh: the quadrilateral cellsOnEdge[0], verticesOnEdge[0],
-      cellsOnEdge[1], verticesOnEdge[1] around every edge, the vertex that
-      follows in place of a cell that is missing (nodes: cells, then
-      vertices).
-    * MPAS vertex mesh (``vertexDegree`` 3): edge k, cell k alternating for
-      k = 0, 1, 2 around every vertex, the vertex itself in place of an edge
-      or a cell that is missing (nodes: vertices, then edges, then cells).
-      Beside a land mask these cells are kites (one cell left) or hexagons
-      with a reflex corner at the vertex (two cells left): CONCAVE.
-      These corner orders are the ones the reference writes to SCRIP for the
-      two kinds of mesh.
-    * a lat-lon grid, a 2-D lat-lon grid with its corner arrays, a
-      projection grid (its ``x_corner`` / ``y_corner`` mesh through
-      ``project_to_lat_lon``): one quadrilateral per cell (C order) through
-      the corners (j, i), (j, i + 1), (j + 1, i + 1), (j + 1, i).
-
-    Consecutive equal corners are dropped, cyclically, and so are spikes (a
-    corner run a, b, a, which the fall-back leaves when an edge exists but
-    neither of its cells does, loses b and one a).
+    The cells of an MPAS edge or vertex mesh exactly as the reference writes
+    them to SCRIP, repeated corners and all: ``(ids (n, width) 0-based,
+    lat, lon)``, ``lat`` / ``lon`` (radians) the coordinates of the nodes
+    the ids point to.  :func:`cell_polygons` has the corner orders and
+    tidies these rings for the clipper.
     """
-    if isinstance(descriptor, ProjectionGridDescriptor):
-        return _quad_soup(*_projected_corners(descriptor))
-    if isinstance(descriptor, (LatLonGridDescriptor, LatLon2DGridDescriptor)):
-        return _quad_soup(*grid_corners(descriptor))
-    if not isinstance(descriptor, MpasMeshDescriptor):
-        raise ValueError(
-            f'a {type(descriptor).__name__} has no cells: conserve needs '
-            f'cells on both sides')
-    if descriptor._dim == 'nCells':
-        return mesh_polygons(descriptor)
     if getattr(descriptor, 'filename', None) is None:
         raise ValueError(
             'conservative weights with an MPAS mesh need its mesh file '
@@ -1490,6 +1491,48 @@ def cell_polygons(descriptor):
         ids = np.stack([edge, cell], axis=2).reshape(n_vertices, 6)
         lat = coords('latVertex', 'latEdge', 'latCell')
         lon = coords('lonVertex', 'lonEdge', 'lonCell')
+    return ids, lat, lon
+
+
+def cell_polygons(descriptor):
+    """
+    The cells of a descriptor as polygons: ``(verticesOnCell (n, width)
+    1-based, nEdgesOnCell, lat, lon)`` as :func:`mesh_polygons` gives them
+    for an MPAS cell mesh, ``lat`` / ``lon`` (radians) the coordinates of the
+    nodes the indices point to.
+
+    * MPAS cell mesh: :func:`mesh_polygons`.
+    * MPAS edge mesh: the quadrilateral cellsOnEdge[0], verticesOnEdge[0],
+      cellsOnEdge[1], verticesOnEdge[1] around every edge, the vertex that
+      follows in place of a cell that is missing (nodes: cells, then
+      vertices).
+    * MPAS vertex mesh (``vertexDegree`` 3): edge k, cell k alternating for
+      k = 0, 1, 2 around every vertex, the vertex itself in place of an edge
+      or a cell that is missing (nodes: vertices, then edges, then cells).
+      Beside a land mask these cells are kites (one cell left) or hexagons
+      with a reflex corner at the vertex (two cells left): CONCAVE.
+      These corner orders are the ones the reference writes to SCRIP for the
+      two kinds of mesh.
+    * a lat-lon grid, a 2-D lat-lon grid with its corner arrays, a
+      projection grid (its ``x_corner`` / ``y_corner`` mesh through
+      ``project_to_lat_lon``): one quadrilateral per cell (C order) through
+      the corners (j, i), (j, i + 1), (j + 1, i + 1), (j + 1, i).
+
+    Consecutive equal corners are dropped, cyclically, and so are spikes (a
+    corner run a, b, a, which the fall-back leaves when an edge exists but
+    neither of its cells does, loses b and one a).
+    """
+    if isinstance(descriptor, ProjectionGridDescriptor):
+        return _quad_soup(*_projected_corners(descriptor))
+    if isinstance(descriptor, (LatLonGridDescriptor, LatLon2DGridDescriptor)):
+        return _quad_soup(*grid_corners(descriptor))
+    if not isinstance(descriptor, MpasMeshDescriptor):
+        raise ValueError(
+            f'a {type(descriptor).__name__} has no cells: conserve needs '
+            f'cells on both sides')
+    if descriptor._dim == 'nCells':
+        return mesh_polygons(descriptor)
+    ids, lat, lon = cell_rings(descriptor)
     voc, noc = _tidy_rings(ids)
     return voc, noc, lat, lon
 
@@ -1901,6 +1944,10 @@ def conserve_polygons(src_descriptor, dst_descriptor, device=None,
     side_a, side_b = (src, dst) if src_is_a else (dst, src)
     row, col, A, frac_b, a_area, b_area = engine.overlap_pieces(
         dev(side_a), dev(side_b), dst_is_b=src_is_a, timing=timing)
+    src_area = a_area if src_is_a else b_area
+    frac_a = engine.column_fractions(col, A, len(src_area), denom=src_area,
+                                     clamp=True).cpu().numpy()
+    src_area = src_area.cpu().numpy()
     row = row.cpu().numpy()
     col = col.cpu().numpy()
     A = A.cpu().numpy()
@@ -1910,7 +1957,8 @@ def conserve_polygons(src_descriptor, dst_descriptor, device=None,
     return MappingFile(n_src, n_dst, np.array(src_dims, dtype=np.int32),
                        np.array(dst_dims, dtype=np.int32),
                        (row + 1).astype(np.int32), (col + 1).astype(np.int32),
-                       S, frac_b)
+                       S, frac_b, area_a=src_area, area_b=dst_area,
+                       frac_a=frac_a)
 
 
 def projected_grid(descriptor):
@@ -2116,6 +2164,193 @@ def build_weights(src_descriptor, dst_descriptor, method='conserve'):
         (row + 1).astype(np.int32), (col + 1).astype(np.int32), S, frac_b)
 
 
+# ---------------------------------------------------------------------------
+# what a complete mapping file says about its grids: areas, frac_a, corners
+# ---------------------------------------------------------------------------
+
+def cell_areas(corner_lat, corner_lon, count):
+    """
+    The numpy statement of ``remap_cell_areas`` (the GPU kernel is tested
+    against it): the area in steradians of every cell given in SCRIP layout,
+    ``corner_lat`` / ``corner_lon`` ``(n, width)`` in radians, the first
+    ``count[i]`` corners of row i the cell's great-circle polygon.  The
+    signed fan of Van Oosterom-Strackee triangles from corner 0
+    (:func:`_fan_areas`, remap_overlap.hip's ``tri_area``), then the
+    absolute value: clockwise rings and concave cells come out right.  A
+    repeated corner adds a triangle of area exactly 0, so slots beyond
+    ``count[i]`` are read as copies of the last valid corner (SCRIP's own
+    padding) and a cell with fewer than 3 distinct corners has area 0.
+    ``ValueError``: a count outside ``[0, width]``.
+    """
+    corner_lat = np.asarray(corner_lat, dtype=np.float64)
+    corner_lon = np.asarray(corner_lon, dtype=np.float64)
+    if corner_lat.ndim != 2 or corner_lat.shape != corner_lon.shape:
+        raise ValueError(
+            f'corners of shapes {corner_lat.shape} and {corner_lon.shape}: '
+            f'expected two (n, width) arrays')
+    n, width = corner_lat.shape
+    count = np.asarray(count, dtype=np.int64)
+    if count.shape != (n,):
+        raise ValueError(f'count of shape {count.shape}: expected one value '
+                         f'for each of the {n} cells')
+    if n and (count.min() < 0 or count.max() > width):
+        raise ValueError(f'count outside [0, {width}]')
+    if n == 0 or width < 3:
+        return np.zeros(n)
+    k = np.minimum(np.arange(width)[None, :],
+                   np.maximum(count, 1)[:, None] - 1)
+    v = _unit_poles(np.take_along_axis(corner_lat, k, axis=1),
+                    np.take_along_axis(corner_lon, k, axis=1))
+    return np.where(count >= 3, np.abs(_fan_areas(v)), 0.0)
+
+
+def column_fractions(col, value, n_cols, denom=None, clamp=False):
+    """
+    The numpy statement of ``remap_column_fractions``: ``out[j]`` = the sum
+    of ``value[k]`` over ``col[k] == j`` (0-based), added in ascending k from
+    +0.0 -- ``np.bincount`` -- then, for a column that has entries, divided
+    by ``denom[j]`` when ``denom`` is given and cut to at most 1 when
+    ``clamp`` is set.  A column without entries is 0.  With ``value`` the
+    overlap areas, ``denom = area_a`` and ``clamp`` this is ESMF's
+    ``frac_a``.
+    """
+    col = np.asarray(col, dtype=np.int64)
+    value = np.asarray(value, dtype=np.float64)
+    n_cols = int(n_cols)
+    if col.shape != value.shape or col.ndim != 1:
+        raise ValueError('col and value: expected two 1-D arrays of one '
+                         'length')
+    if len(col) and (col.min() < 0 or col.max() >= n_cols):
+        raise ValueError(f'an entry names a column outside [0, {n_cols})')
+    out = np.bincount(col, weights=value, minlength=n_cols)
+    has = np.bincount(col, minlength=n_cols) > 0
+    if denom is not None:
+        denom = np.asarray(denom, dtype=np.float64)
+        if denom.shape != (n_cols,):
+            raise ValueError(f'denom of shape {denom.shape}: expected '
+                             f'({n_cols},)')
+        with np.errstate(divide='ignore', invalid='ignore'):
+            out = np.where(has, out / denom, out)
+    if clamp:
+        out = np.where(out > 1.0, 1.0, out)
+    return out
+
+
+def _areas_of(corner_lat, corner_lon, count, device=None):
+    """:func:`cell_areas` of corners in radians, on the GPU where one is
+    present (``remap_cell_areas``), with numpy otherwise."""
+    if not _gpu_present():
+        return cell_areas(corner_lat, corner_lon, count)
+    from pyremap_amd import engine
+    torch = engine.require_gpu()
+    if device is None:
+        device = f'cuda:{torch.cuda.current_device()}'
+
+    def dev(x, dtype=np.float64):
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=dtype)) \
+            .to(device)
+    return engine.cell_areas(dev(corner_lat), dev(corner_lon),
+                             dev(count, np.int32)).cpu().numpy()
+
+
+def _side_geometry(descriptor, expand_dist=None, expand_factor=None):
+    """:func:`pyremap_amd.scrip.scrip_geometry` of one side of a map.  An
+    MPAS mesh given without its file is a set of points where it has
+    coordinates (as a point collection: the point four times, area 0); a
+    mesh given by its size alone, or a projection grid without a usable
+    projection, has no geometry to state: None."""
+    from pyremap_amd.scrip import scrip_geometry
+    if isinstance(descriptor, MpasMeshDescriptor) and \
+            getattr(descriptor, 'filename', None) is None:
+        points = _points(descriptor)
+        if points is None:
+            return None
+        return scrip_geometry(PointCollectionDescriptor(
+            points[0], points[1], descriptor.mesh_name, units='radians'))
+    if isinstance(descriptor, ProjectionGridDescriptor) and \
+            'lat' not in (descriptor.coords or {}):
+        return None
+    return scrip_geometry(descriptor, expand_dist, expand_factor, area=False)
+
+
+def _fractions_of(col, value, n_cols, denom, device=None):
+    """``frac_a``: :func:`column_fractions` with the clamp on, on the GPU
+    where one is present (``remap_column_fractions``: the same bytes)."""
+    if not _gpu_present():
+        return column_fractions(col, value, n_cols, denom=denom, clamp=True)
+    from pyremap_amd import engine
+    torch = engine.require_gpu()
+    if device is None:
+        device = f'cuda:{torch.cuda.current_device()}'
+
+    def dev(x, dtype):
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=dtype)) \
+            .to(device)
+    return engine.column_fractions(
+        dev(col, np.int64), dev(value, np.float64), n_cols,
+        denom=dev(denom, np.float64), clamp=True).cpu().numpy()
+
+
+def complete_mapping(m, src_descriptor, dst_descriptor, method='conserve',
+                     expand_dist=None, expand_factor=None):
+    """
+    Fill the members of ``m`` (a :class:`MappingFile`) that ESMF's files
+    carry beyond the weights and that are still ``None``: ``xc, yc, xv, yv``
+    (degrees) and ``mask`` (ones) of both grids from
+    :func:`pyremap_amd.scrip.scrip_geometry` -- with ``conserve`` and
+    ``expand_dist`` / ``expand_factor`` given, the destination's widened
+    corners --, ``area_a`` / ``area_b`` (steradians) as the great-circle
+    polygons of those corners (``remap_cell_areas`` on the GPU where one is
+    present, :func:`cell_areas` otherwise; 0 for a point collection), and
+    ``frac_a``: for ``conserve`` the clamped column sums of ``S *
+    area_b[row]`` over ``area_a`` (``remap_column_fractions`` on the GPU
+    where one is present, :func:`column_fractions` otherwise), for
+    ``bilinear`` and ``neareststod`` 0, as ESMF's format documents.  The
+    GPU conserve paths set ``area_a``, ``area_b`` (the overlap call's own)
+    and ``frac_a`` (``remap_column_fractions`` of the overlap areas)
+    themselves; those are kept.  A side without geometry
+    (:func:`_side_geometry`) keeps ``None``, and ``frac_a`` with it.
+    Returns ``m``.
+    """
+    for side, descriptor, n in (('a', src_descriptor, m.n_a),
+                                ('b', dst_descriptor, m.n_b)):
+        kw = {}
+        if side == 'b' and method == 'conserve':
+            kw = {'expand_dist': expand_dist, 'expand_factor': expand_factor}
+        g = _side_geometry(descriptor, **kw)
+        if g is None:
+            continue
+        if len(g['grid_center_lat']) != n:
+            raise ValueError(
+                f'the {type(descriptor).__name__} has '
+                f'{len(g["grid_center_lat"])} cells, the map n_{side} = {n}')
+        to_deg = 180.0 / np.pi if 'rad' in g['units'] else 1.0
+        to_rad = 1.0 if 'rad' in g['units'] else np.pi / 180.0
+        for name, key in (('yc', 'grid_center_lat'), ('xc', 'grid_center_lon'),
+                          ('yv', 'grid_corner_lat'),
+                          ('xv', 'grid_corner_lon')):
+            if getattr(m, f'{name}_{side}') is None:
+                setattr(m, f'{name}_{side}', np.ascontiguousarray(
+                    g[key] * to_deg))
+        if getattr(m, f'mask_{side}') is None:
+            setattr(m, f'mask_{side}', g['grid_imask'])
+        if getattr(m, f'area_{side}') is None:
+            setattr(m, f'area_{side}', _areas_of(
+                g['grid_corner_lat'] * to_rad, g['grid_corner_lon'] * to_rad,
+                g['count']))
+    if m.area_a is None or m.area_b is None:
+        return m
+    if m.frac_a is None:
+        if method == 'conserve':
+            row = m.row.astype(np.int64) - 1
+            m.frac_a = _fractions_of(
+                m.col.astype(np.int64) - 1, m.S * m.area_b[row], m.n_a,
+                m.area_a)
+        else:
+            m.frac_a = np.zeros(m.n_a)
+    return m
+
+
 def _same_projection(a, b):
     pa, pb = a.projection, b.projection
     return pa is pb or getattr(pa, 'srs', pa) == getattr(pb, 'srs', pb)
@@ -2183,6 +2418,18 @@ def make_weights(src_descriptor, dst_descriptor, method='conserve',
     reference: destination corners play no part in them.  With both ``None``
     every call made is the one made without them.
     """
+    m = _make_weights(src_descriptor, dst_descriptor, method, expand_dist,
+                      expand_factor)
+    if not isinstance(m, MappingFile):
+        return m      # (a caller's stand-in for a routed call: as it is)
+    return complete_mapping(m, src_descriptor, dst_descriptor, method,
+                            expand_dist, expand_factor)
+
+
+def _make_weights(src_descriptor, dst_descriptor, method, expand_dist,
+                  expand_factor):
+    """The weights of :func:`make_weights`, before the grids' geometry is
+    added."""
     if method not in METHODS:
         raise ValueError(f'method {method!r}: expected one of {METHODS}')
     if method == 'conserve' and not (expand_dist is None and
@@ -2237,5 +2484,6 @@ def write_weights(filename, src_descriptor, dst_descriptor,
         attrs['expand_dist'] = _expand_attr(expand_dist, 0.0)
         attrs['expand_factor'] = _expand_attr(expand_factor, 1.0)
     write_mapping(filename, m.n_a, m.n_b, m.src_grid_dims, m.dst_grid_dims,
-                  m.row, m.col, m.S, m.frac_b, attrs=attrs)
+                  m.row, m.col, m.S, m.frac_b, attrs=attrs,
+                  geometry=m.geometry or None)
     return m
