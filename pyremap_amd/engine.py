@@ -15,6 +15,7 @@ PyTorch is used for device memory, streams and (in ``parallel.py``)
 fallback: without the library or without a GPU every compute entry point
 raises.
 """
+import contextlib
 import ctypes
 import os
 
@@ -584,6 +585,24 @@ def _stream_ptr(device):
 
 def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+@contextlib.contextmanager
+def _gpu_ms(torch, timing):
+    """``timing['ms']``: the GPU time of the body, between an event recorded
+    on the current stream on entry and one recorded on exit, which is waited
+    for.  With ``timing`` None nothing is done at all: no event, no wait.  An
+    exception of the body passes through and ``timing`` is not filled."""
+    if timing is None:
+        yield
+        return
+    t0 = torch.cuda.Event(enable_timing=True)
+    t1 = torch.cuda.Event(enable_timing=True)
+    t0.record()
+    yield
+    t1.record()
+    t1.synchronize()
+    timing['ms'] = t0.elapsed_time(t1)
 
 
 # ---------------------------------------------------------------------------
@@ -2193,6 +2212,97 @@ def stream_copy(dst, src):
 
 
 # ---------------------------------------------------------------------------
+# conservative overlaps: what the four remap_overlap_* calls share
+# ---------------------------------------------------------------------------
+
+def _mesh_struct(torch, arrays, keep):
+    """The ``remap_overlap_mesh`` of ``(verticesOnCell, nEdgesOnCell,
+    latVertex, lonVertex)``; the converted tensors its pointers look into
+    join ``keep``, which has to outlive the call."""
+    voc = arrays[0].to(torch.int32).contiguous()
+    noc = arrays[1].to(torch.int32).contiguous()
+    lat_v = arrays[2].to(torch.float64).contiguous()
+    lon_v = arrays[3].to(torch.float64).contiguous()
+    keep.extend((voc, noc, lat_v, lon_v))
+    return _OverlapMesh(voc.shape[0], lat_v.numel(), voc.shape[1], 0,
+                        voc.data_ptr(), noc.data_ptr(), lat_v.data_ptr(),
+                        lon_v.data_ptr())
+
+
+def _overlap(kind, dev, sides, n_a, n_b, flag, n_dst, timing, counter_words=0,
+             b_padded=True, arg_errors=False, phases=()):
+    """
+    ``remap_overlap_<kind>_sizes``, the workspace and the outputs, then
+    ``remap_overlap_<kind>`` on the current stream of ``dev``: ``sides`` are
+    the call's leading structs (one geometry, or sides a and b, of ``n_a``
+    and ``n_b`` cells; the caller keeps the tensors behind them alive),
+    ``flag`` its direction argument and ``n_dst`` the number of destination
+    cells that follows from it.  ``counter_words``: the int64 words of the
+    counter ``_sizes`` takes (0: it takes none).  ``b_padded=False``: the
+    b-area array has exactly ``n_b`` elements.  ``arg_errors``: the library's
+    ``REMAP_ERR_ARG`` is a ``ValueError``.  ``phases``: with ``timing`` the
+    call goes through ``remap_overlap_<kind>_timed``, which reports these.
+
+    Returns ``(dst, src, A, frac_b, a_area, b_area)`` cut to their lengths;
+    ``timing`` receives ``n_pairs``, ``ms`` and the phases.
+    """
+    torch = _torch()
+    lib = load_library()
+    what = f'remap_overlap_{kind}'
+
+    def check(rc, name):
+        if arg_errors and rc == -1:     # REMAP_ERR_ARG
+            raise ValueError(
+                f'{name}: ' +
+                lib.remap_last_error().decode('utf-8', 'replace'))
+        _check(rc, name)
+
+    def empty(n, dtype=torch.float64):
+        # (never empty: the C side wants every output pointer, even for a
+        # mesh without cells)
+        return torch.empty(max(n, 1), dtype=dtype, device=dev)
+    sides = [ctypes.byref(s) for s in sides]
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        counter = []
+        if counter_words:
+            words = torch.zeros(counter_words, dtype=torch.int64, device=dev)
+            counter = [_ptr(words)]
+        n_pairs = ctypes.c_int64()
+        nbytes = ctypes.c_size_t()
+        check(getattr(lib, what + '_sizes')(
+            *sides, *counter, ctypes.byref(n_pairs), ctypes.byref(nbytes),
+            stream), what + '_sizes')
+        n = n_pairs.value
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        dst, src, A = empty(n, torch.int32), empty(n, torch.int32), empty(n)
+        a_area = empty(n_a)
+        b_area = empty(n_b) if b_padded else \
+            torch.empty(n_b, dtype=torch.float64, device=dev)
+        frac_b = empty(n_dst)
+        n_entries = ctypes.c_int64()
+        args = (*sides, 1 if flag else 0, n, _ptr(ws), nbytes.value,
+                _ptr(dst), _ptr(src), _ptr(A), _ptr(frac_b), _ptr(a_area),
+                _ptr(b_area), ctypes.byref(n_entries))
+        if phases and timing is not None:
+            what += '_timed'
+            ms = (ctypes.c_float * len(phases))()
+            args += (ms,)
+        with _gpu_ms(torch, timing):
+            check(getattr(lib, what)(*args, stream), what)
+        if timing is not None:
+            timing['n_pairs'] = n
+            if phases:
+                timing.update(zip(phases, (float(x) for x in ms)))
+        # (as in nearest_points: torch's allocator keeps the workspace for
+        # this stream, so later work is ordered behind the call)
+        del ws
+        m = n_entries.value
+    return (dst[:m], src[:m], A[:m], frac_b[:n_dst], a_area[:n_a],
+            b_area[:n_b])
+
+
+# ---------------------------------------------------------------------------
 # conservative overlaps: MPAS cell mesh <-> lat-lon grid
 # ---------------------------------------------------------------------------
 
@@ -2215,7 +2325,6 @@ def overlap_latlon(vertices_on_cell, n_edges_on_cell, lat_vertex, lon_vertex,
     overlap call (events on the stream).
     """
     torch = require_gpu()
-    lib = load_library()
     dev = vertices_on_cell.device
     voc = vertices_on_cell.to(torch.int32).contiguous()
     noc = n_edges_on_cell.to(torch.int32).contiguous()
@@ -2229,50 +2338,16 @@ def overlap_latlon(vertices_on_cell, n_edges_on_cell, lat_vertex, lon_vertex,
                         float(lat_slack), voc.data_ptr(), noc.data_ptr(),
                         lat_v.data_ptr(), lon_v.data_ptr(), lat_c.data_ptr(),
                         lon_c.data_ptr())
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        counter = torch.zeros(2, dtype=torch.int64, device=dev)
-        n_pairs = ctypes.c_int64()
-        nbytes = ctypes.c_size_t()
-        _check(lib.remap_overlap_latlon_sizes(
-            ctypes.byref(geom), _ptr(counter), ctypes.byref(n_pairs),
-            ctypes.byref(nbytes), stream), 'remap_overlap_latlon_sizes')
-        n = n_pairs.value
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        dst = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        src = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        A = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
-        # (never empty: the C side wants every output pointer, even for a
-        # mesh without cells)
-        mesh_area = torch.empty(max(n_cells, 1), dtype=torch.float64,
-                                device=dev)
-        grid_area = torch.empty(n_lat * n_lon, dtype=torch.float64,
-                                device=dev)
-        n_dst = n_cells if dst_is_mesh else n_lat * n_lon
-        frac_b = torch.empty(max(n_dst, 1), dtype=torch.float64, device=dev)
-        n_entries = ctypes.c_int64()
-        if timing is not None:
-            t0 = torch.cuda.Event(enable_timing=True)
-            t1 = torch.cuda.Event(enable_timing=True)
-            t0.record()
-        _check(lib.remap_overlap_latlon(
-            ctypes.byref(geom), 1 if dst_is_mesh else 0, n, _ptr(ws),
-            nbytes.value, _ptr(dst), _ptr(src), _ptr(A), _ptr(frac_b),
-            _ptr(mesh_area), _ptr(grid_area), ctypes.byref(n_entries),
-            stream), 'remap_overlap_latlon')
-        if timing is not None:
-            t1.record()
-            t1.synchronize()
-            timing['n_pairs'] = n
-            timing['ms'] = t0.elapsed_time(t1)
-        del ws
-        m = n_entries.value
-    return (dst[:m], src[:m], A[:m], frac_b[:n_dst], mesh_area[:n_cells],
-            grid_area)
+    n_grid = n_lat * n_lon
+    return _overlap('latlon', dev, (geom,), n_cells, n_grid, dst_is_mesh,
+                    n_cells if dst_is_mesh else n_grid, timing,
+                    counter_words=2, b_padded=False)
 
 
 # ---------------------------------------------------------------------------
 # conservative overlaps: MPAS cell mesh <-> MPAS cell mesh
+# (overlap_meshes, like overlap_pieces and overlap_grids below, builds its two
+# side structs and leaves the rest to _overlap)
 # ---------------------------------------------------------------------------
 
 def overlap_meshes(mesh_a, mesh_b, dst_is_b, timing=None):
@@ -2291,59 +2366,12 @@ def overlap_meshes(mesh_a, mesh_b, dst_is_b, timing=None):
     call (events on the stream).
     """
     torch = require_gpu()
-    lib = load_library()
-    dev = mesh_a[0].device
     keep = []
-
-    def geom(mesh):
-        voc = mesh[0].to(torch.int32).contiguous()
-        noc = mesh[1].to(torch.int32).contiguous()
-        lat_v = mesh[2].to(torch.float64).contiguous()
-        lon_v = mesh[3].to(torch.float64).contiguous()
-        keep.extend((voc, noc, lat_v, lon_v))
-        return _OverlapMesh(voc.shape[0], lat_v.numel(), voc.shape[1], 0,
-                            voc.data_ptr(), noc.data_ptr(), lat_v.data_ptr(),
-                            lon_v.data_ptr())
-    ga, gb = geom(mesh_a), geom(mesh_b)
+    ga = _mesh_struct(torch, mesh_a, keep)
+    gb = _mesh_struct(torch, mesh_b, keep)
     n_a, n_b = ga.n_cells, gb.n_cells
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        counter = torch.zeros(4, dtype=torch.int64, device=dev)
-        n_pairs = ctypes.c_int64()
-        nbytes = ctypes.c_size_t()
-        _check(lib.remap_overlap_meshes_sizes(
-            ctypes.byref(ga), ctypes.byref(gb), _ptr(counter),
-            ctypes.byref(n_pairs), ctypes.byref(nbytes), stream),
-            'remap_overlap_meshes_sizes')
-        n = n_pairs.value
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        dst = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        src = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        A = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
-        # (never empty: the C side wants every output pointer)
-        a_area = torch.empty(max(n_a, 1), dtype=torch.float64, device=dev)
-        b_area = torch.empty(max(n_b, 1), dtype=torch.float64, device=dev)
-        n_dst = n_b if dst_is_b else n_a
-        frac_b = torch.empty(max(n_dst, 1), dtype=torch.float64, device=dev)
-        n_entries = ctypes.c_int64()
-        if timing is not None:
-            t0 = torch.cuda.Event(enable_timing=True)
-            t1 = torch.cuda.Event(enable_timing=True)
-            t0.record()
-        _check(lib.remap_overlap_meshes(
-            ctypes.byref(ga), ctypes.byref(gb), 1 if dst_is_b else 0, n,
-            _ptr(ws), nbytes.value, _ptr(dst), _ptr(src), _ptr(A),
-            _ptr(frac_b), _ptr(a_area), _ptr(b_area), ctypes.byref(n_entries),
-            stream), 'remap_overlap_meshes')
-        if timing is not None:
-            t1.record()
-            t1.synchronize()
-            timing['n_pairs'] = n
-            timing['ms'] = t0.elapsed_time(t1)
-        del ws
-        m = n_entries.value
-    return (dst[:m], src[:m], A[:m], frac_b[:n_dst], a_area[:n_a],
-            b_area[:n_b])
+    return _overlap('meshes', mesh_a[0].device, (ga, gb), n_a, n_b, dst_is_b,
+                    n_b if dst_is_b else n_a, timing, counter_words=4)
 
 
 # ---------------------------------------------------------------------------
@@ -2379,82 +2407,27 @@ def overlap_pieces(pieces_a, pieces_b, dst_is_b, timing=None):
     a ``ValueError`` (the library's ``REMAP_ERR_ARG``).
     """
     torch = require_gpu()
-    lib = load_library()
     dev = pieces_a[0].device
     keep = []
 
     def side(p):
-        voc = p[0].to(torch.int32).contiguous()
-        noc = p[1].to(torch.int32).contiguous()
-        lat_v = p[2].to(torch.float64).contiguous()
-        lon_v = p[3].to(torch.float64).contiguous()
-        keep.extend((voc, noc, lat_v, lon_v))
+        mesh = _mesh_struct(torch, p, keep)
         parent, n_parents = p[4], int(p[5])
         ptr = None
         if parent is not None:
             parent = parent.to(device=dev, dtype=torch.int32).contiguous()
-            if parent.numel() != voc.shape[0]:
+            if parent.numel() != mesh.n_cells:
                 raise ValueError(
                     f'overlap_pieces: {parent.numel()} parents for '
-                    f'{voc.shape[0]} pieces')
+                    f'{mesh.n_cells} pieces')
             keep.append(parent)
             ptr = parent.data_ptr()
-        mesh = _OverlapMesh(voc.shape[0], lat_v.numel(), voc.shape[1], 0,
-                            voc.data_ptr(), noc.data_ptr(), lat_v.data_ptr(),
-                            lon_v.data_ptr())
         return _OverlapPieces(mesh, n_parents, ptr)
-
-    def check(rc, what):
-        if rc == -1:     # REMAP_ERR_ARG
-            raise ValueError(
-                f'{what}: ' +
-                lib.remap_last_error().decode('utf-8', 'replace'))
-        _check(rc, what)
     ga, gb = side(pieces_a), side(pieces_b)
     n_a, n_b = ga.n_parents, gb.n_parents
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        counter = torch.zeros(4, dtype=torch.int64, device=dev)
-        n_pairs = ctypes.c_int64()
-        nbytes = ctypes.c_size_t()
-        check(lib.remap_overlap_pieces_sizes(
-            ctypes.byref(ga), ctypes.byref(gb), _ptr(counter),
-            ctypes.byref(n_pairs), ctypes.byref(nbytes), stream),
-            'remap_overlap_pieces_sizes')
-        n = n_pairs.value
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        dst = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        src = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        A = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
-        # (never empty: the C side wants every output pointer)
-        a_area = torch.empty(max(n_a, 1), dtype=torch.float64, device=dev)
-        b_area = torch.empty(max(n_b, 1), dtype=torch.float64, device=dev)
-        n_dst = n_b if dst_is_b else n_a
-        frac_b = torch.empty(max(n_dst, 1), dtype=torch.float64, device=dev)
-        n_entries = ctypes.c_int64()
-        args = (ctypes.byref(ga), ctypes.byref(gb), 1 if dst_is_b else 0, n,
-                _ptr(ws), nbytes.value, _ptr(dst), _ptr(src), _ptr(A),
-                _ptr(frac_b), _ptr(a_area), _ptr(b_area),
-                ctypes.byref(n_entries))
-        if timing is None:
-            check(lib.remap_overlap_pieces(*args, stream),
-                  'remap_overlap_pieces')
-        else:
-            phases = (ctypes.c_float * len(PIECES_PHASES))()
-            t0 = torch.cuda.Event(enable_timing=True)
-            t1 = torch.cuda.Event(enable_timing=True)
-            t0.record()
-            check(lib.remap_overlap_pieces_timed(*args, phases, stream),
-                  'remap_overlap_pieces_timed')
-            t1.record()
-            t1.synchronize()
-            timing['n_pairs'] = n
-            timing['ms'] = t0.elapsed_time(t1)
-            timing.update(zip(PIECES_PHASES, (float(x) for x in phases)))
-        del ws
-        m = n_entries.value
-    return (dst[:m], src[:m], A[:m], frac_b[:n_dst], a_area[:n_a],
-            b_area[:n_b])
+    return _overlap('pieces', dev, (ga, gb), n_a, n_b, dst_is_b,
+                    n_b if dst_is_b else n_a, timing, counter_words=4,
+                    arg_errors=True, phases=PIECES_PHASES)
 
 
 # ---------------------------------------------------------------------------
@@ -2478,8 +2451,6 @@ def overlap_grids(side_a, side_b, dst_is_b, timing=None):
     and the GPU ``ms`` of the overlap call (events on the stream).
     """
     torch = require_gpu()
-    lib = load_library()
-    dev = side_a[0].device
     keep = []
 
     def side(arrays):
@@ -2496,52 +2467,12 @@ def overlap_grids(side_a, side_b, dst_is_b, timing=None):
                              lat.data_ptr(), lon.data_ptr())
             keep.extend((lat, lon, g))
             return _OverlapSide(None, ctypes.pointer(g)), int(g.ny * g.nx)
-        voc = arrays[0].to(torch.int32).contiguous()
-        noc = arrays[1].to(torch.int32).contiguous()
-        lat_v = arrays[2].to(torch.float64).contiguous()
-        lon_v = arrays[3].to(torch.float64).contiguous()
-        m = _OverlapMesh(voc.shape[0], lat_v.numel(), voc.shape[1], 0,
-                         voc.data_ptr(), noc.data_ptr(), lat_v.data_ptr(),
-                         lon_v.data_ptr())
-        keep.extend((voc, noc, lat_v, lon_v, m))
+        m = _mesh_struct(torch, arrays, keep)
+        keep.append(m)
         return _OverlapSide(ctypes.pointer(m), None), int(m.n_cells)
     (ga, n_a), (gb, n_b) = side(side_a), side(side_b)
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        n_pairs = ctypes.c_int64()
-        nbytes = ctypes.c_size_t()
-        _check(lib.remap_overlap_grids_sizes(
-            ctypes.byref(ga), ctypes.byref(gb), ctypes.byref(n_pairs),
-            ctypes.byref(nbytes), stream), 'remap_overlap_grids_sizes')
-        n = n_pairs.value
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        dst = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        src = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        A = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
-        # (never empty: the C side wants every output pointer)
-        a_area = torch.empty(max(n_a, 1), dtype=torch.float64, device=dev)
-        b_area = torch.empty(max(n_b, 1), dtype=torch.float64, device=dev)
-        n_dst = n_b if dst_is_b else n_a
-        frac_b = torch.empty(max(n_dst, 1), dtype=torch.float64, device=dev)
-        n_entries = ctypes.c_int64()
-        if timing is not None:
-            t0 = torch.cuda.Event(enable_timing=True)
-            t1 = torch.cuda.Event(enable_timing=True)
-            t0.record()
-        _check(lib.remap_overlap_grids(
-            ctypes.byref(ga), ctypes.byref(gb), 1 if dst_is_b else 0, n,
-            _ptr(ws), nbytes.value, _ptr(dst), _ptr(src), _ptr(A),
-            _ptr(frac_b), _ptr(a_area), _ptr(b_area), ctypes.byref(n_entries),
-            stream), 'remap_overlap_grids')
-        if timing is not None:
-            t1.record()
-            t1.synchronize()
-            timing['n_pairs'] = n
-            timing['ms'] = t0.elapsed_time(t1)
-        del ws
-        m = n_entries.value
-    return (dst[:m], src[:m], A[:m], frac_b[:n_dst], a_area[:n_a],
-            b_area[:n_b])
+    return _overlap('grids', side_a[0].device, (ga, gb), n_a, n_b, dst_is_b,
+                    n_b if dst_is_b else n_a, timing)
 
 
 # ---------------------------------------------------------------------------
@@ -2591,26 +2522,20 @@ def nearest_points(src_xyz, dst_xyz, timing=None, phases=False):
                'remap_nearest_workspace')
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
         out = torch.empty(n_dst, dtype=torch.int32, device=dev)
-        if timing is not None:
-            t0 = torch.cuda.Event(enable_timing=True)
-            t1 = torch.cuda.Event(enable_timing=True)
-            t0.record()
-        if phases:
-            ms = (ctypes.c_float * 3)()
-            _check(lib.remap_nearest_timed(
-                _ptr(src_xyz), n_src, _ptr(dst_xyz), n_dst, _ptr(out),
-                _ptr(ws), nbytes.value, ms, stream), 'remap_nearest_timed')
-        else:
-            _check(lib.remap_nearest(
-                _ptr(src_xyz), n_src, _ptr(dst_xyz), n_dst, _ptr(out),
-                _ptr(ws), nbytes.value, stream), 'remap_nearest')
-        if timing is not None:
-            t1.record()
-            t1.synchronize()
-            timing['ms'] = t0.elapsed_time(t1)
+        with _gpu_ms(torch, timing):
             if phases:
-                timing['sort_ms'], timing['pyramid_ms'], \
-                    timing['walk_ms'] = (float(v) for v in ms)
+                ms = (ctypes.c_float * 3)()
+                _check(lib.remap_nearest_timed(
+                    _ptr(src_xyz), n_src, _ptr(dst_xyz), n_dst, _ptr(out),
+                    _ptr(ws), nbytes.value, ms, stream),
+                    'remap_nearest_timed')
+            else:
+                _check(lib.remap_nearest(
+                    _ptr(src_xyz), n_src, _ptr(dst_xyz), n_dst, _ptr(out),
+                    _ptr(ws), nbytes.value, stream), 'remap_nearest')
+        if phases:
+            timing['sort_ms'], timing['pyramid_ms'], \
+                timing['walk_ms'] = (float(v) for v in ms)
         # the workspace's memory returns to torch's allocator, which keeps it
         # for this stream: later work on the stream is ordered behind the walk
         del ws
@@ -2675,28 +2600,21 @@ def locate_in_triangles(xyz, tri, points, tol=1e-12, timing=None,
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
         found = torch.empty(n_pts, dtype=torch.int32, device=dev)
         weights = torch.empty((n_pts, 3), dtype=torch.float64, device=dev)
-        if timing is not None:
-            t0 = torch.cuda.Event(enable_timing=True)
-            t1 = torch.cuda.Event(enable_timing=True)
-            t0.record()
-        if phases:
-            ms = (ctypes.c_float * 3)()
-            _check(lib.remap_locate_timed(
-                _ptr(xyz), n_nodes, _ptr(tri), n_tri, _ptr(points), n_pts,
-                tol, _ptr(found), _ptr(weights), _ptr(ws), nbytes.value, ms,
-                stream), 'remap_locate_timed')
-        else:
-            _check(lib.remap_locate(
-                _ptr(xyz), n_nodes, _ptr(tri), n_tri, _ptr(points), n_pts,
-                tol, _ptr(found), _ptr(weights), _ptr(ws), nbytes.value,
-                stream), 'remap_locate')
-        if timing is not None:
-            t1.record()
-            t1.synchronize()
-            timing['ms'] = t0.elapsed_time(t1)
+        with _gpu_ms(torch, timing):
             if phases:
-                timing['sort_ms'], timing['setup_ms'], \
-                    timing['walk_ms'] = (float(v) for v in ms)
+                ms = (ctypes.c_float * 3)()
+                _check(lib.remap_locate_timed(
+                    _ptr(xyz), n_nodes, _ptr(tri), n_tri, _ptr(points),
+                    n_pts, tol, _ptr(found), _ptr(weights), _ptr(ws),
+                    nbytes.value, ms, stream), 'remap_locate_timed')
+            else:
+                _check(lib.remap_locate(
+                    _ptr(xyz), n_nodes, _ptr(tri), n_tri, _ptr(points),
+                    n_pts, tol, _ptr(found), _ptr(weights), _ptr(ws),
+                    nbytes.value, stream), 'remap_locate')
+        if phases:
+            timing['sort_ms'], timing['setup_ms'], \
+                timing['walk_ms'] = (float(v) for v in ms)
         # (as in nearest_points: torch's allocator keeps the workspace for
         # this stream, so later work is ordered behind the walk)
         del ws
@@ -2766,28 +2684,21 @@ def locate_in_quads(nodes, points, periodic=False, tol=1e-10, timing=None,
         ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
         found = torch.empty(n_pts, dtype=torch.int32, device=dev)
         weights = torch.empty((n_pts, 4), dtype=torch.float64, device=dev)
-        if timing is not None:
-            t0 = torch.cuda.Event(enable_timing=True)
-            t1 = torch.cuda.Event(enable_timing=True)
-            t0.record()
-        if phases:
-            ms = (ctypes.c_float * 3)()
-            _check(lib.remap_quads_timed(
-                _ptr(nodes), ny, nx, periodic, _ptr(points), n_pts, tol,
-                _ptr(found), _ptr(weights), _ptr(ws), nbytes.value, ms,
-                stream), 'remap_quads_timed')
-        else:
-            _check(lib.remap_quads(
-                _ptr(nodes), ny, nx, periodic, _ptr(points), n_pts, tol,
-                _ptr(found), _ptr(weights), _ptr(ws), nbytes.value, stream),
-                'remap_quads')
-        if timing is not None:
-            t1.record()
-            t1.synchronize()
-            timing['ms'] = t0.elapsed_time(t1)
+        with _gpu_ms(torch, timing):
             if phases:
-                timing['sort_ms'], timing['setup_ms'], \
-                    timing['walk_ms'] = (float(v) for v in ms)
+                ms = (ctypes.c_float * 3)()
+                _check(lib.remap_quads_timed(
+                    _ptr(nodes), ny, nx, periodic, _ptr(points), n_pts, tol,
+                    _ptr(found), _ptr(weights), _ptr(ws), nbytes.value, ms,
+                    stream), 'remap_quads_timed')
+            else:
+                _check(lib.remap_quads(
+                    _ptr(nodes), ny, nx, periodic, _ptr(points), n_pts, tol,
+                    _ptr(found), _ptr(weights), _ptr(ws), nbytes.value,
+                    stream), 'remap_quads')
+        if phases:
+            timing['sort_ms'], timing['setup_ms'], \
+                timing['walk_ms'] = (float(v) for v in ms)
         # (as in nearest_points: torch's allocator keeps the workspace for
         # this stream, so later work is ordered behind the walk)
         del ws
@@ -2863,23 +2774,16 @@ def expand_cells(centre_lat, centre_lon, corner_lat, corner_lon, count,
         out_lat = torch.empty_like(corner_lat)
         out_lon = torch.empty_like(corner_lon)
         status = torch.zeros(2, dtype=torch.int32, device=dev)
-        if timing is not None:
-            t0 = torch.cuda.Event(enable_timing=True)
-            t1 = torch.cuda.Event(enable_timing=True)
-            t0.record()
-        rc = lib.remap_expand_cells(
-            n, width, _ptr(centre_lat), _ptr(centre_lon), _ptr(corner_lat),
-            _ptr(corner_lon), _ptr(count), _ptr(dist), dist_stride,
-            _ptr(factor), factor_stride, _ptr(out_lat), _ptr(out_lon),
-            _ptr(status), stream)
-        if rc == -1:     # REMAP_ERR_ARG
-            raise ValueError(
-                lib.remap_last_error().decode('utf-8', 'replace'))
-        _check(rc, 'remap_expand_cells')
-        if timing is not None:
-            t1.record()
-            t1.synchronize()
-            timing['ms'] = t0.elapsed_time(t1)
+        with _gpu_ms(torch, timing):
+            rc = lib.remap_expand_cells(
+                n, width, _ptr(centre_lat), _ptr(centre_lon),
+                _ptr(corner_lat), _ptr(corner_lon), _ptr(count), _ptr(dist),
+                dist_stride, _ptr(factor), factor_stride, _ptr(out_lat),
+                _ptr(out_lon), _ptr(status), stream)
+            if rc == -1:     # REMAP_ERR_ARG
+                raise ValueError(
+                    lib.remap_last_error().decode('utf-8', 'replace'))
+            _check(rc, 'remap_expand_cells')
     return out_lat, out_lon
 
 
@@ -2926,21 +2830,14 @@ def cell_areas(corner_lat, corner_lon, count, timing=None):
         stream = _stream_ptr(dev)
         area = torch.empty(n, dtype=torch.float64, device=dev)
         status = torch.zeros(2, dtype=torch.int32, device=dev)
-        if timing is not None:
-            t0 = torch.cuda.Event(enable_timing=True)
-            t1 = torch.cuda.Event(enable_timing=True)
-            t0.record()
-        rc = lib.remap_cell_areas(n, width, _ptr(corner_lat),
-                                  _ptr(corner_lon), _ptr(count), _ptr(area),
-                                  _ptr(status), stream)
-        if rc == -1:     # REMAP_ERR_ARG
-            raise ValueError(
-                lib.remap_last_error().decode('utf-8', 'replace'))
-        _check(rc, 'remap_cell_areas')
-        if timing is not None:
-            t1.record()
-            t1.synchronize()
-            timing['ms'] = t0.elapsed_time(t1)
+        with _gpu_ms(torch, timing):
+            rc = lib.remap_cell_areas(n, width, _ptr(corner_lat),
+                                      _ptr(corner_lon), _ptr(count),
+                                      _ptr(area), _ptr(status), stream)
+            if rc == -1:     # REMAP_ERR_ARG
+                raise ValueError(
+                    lib.remap_last_error().decode('utf-8', 'replace'))
+            _check(rc, 'remap_cell_areas')
     return area
 
 
@@ -2990,18 +2887,12 @@ def column_fractions(col, value, n_cols, denom=None, clamp=False,
                                 device=dev)
         out = torch.empty(n_cols, dtype=torch.float64, device=dev)
         bad = torch.zeros(1, dtype=torch.int64, device=dev)
-        if timing is not None:
-            t0 = torch.cuda.Event(enable_timing=True)
-            t1 = torch.cuda.Event(enable_timing=True)
-            t0.record()
-        _check(lib.remap_column_fractions(
-            n, n_cols, _ptr(col), int(index_base), _ptr(value), _ptr(denom),
-            1 if clamp else 0, _ptr(out), _ptr(bad), _ptr(workspace),
-            need.value, stream), 'remap_column_fractions')
-        if timing is not None:
-            t1.record()
-            t1.synchronize()
-            timing['ms'] = t0.elapsed_time(t1)
+        with _gpu_ms(torch, timing):
+            _check(lib.remap_column_fractions(
+                n, n_cols, _ptr(col), int(index_base), _ptr(value),
+                _ptr(denom), 1 if clamp else 0, _ptr(out), _ptr(bad),
+                _ptr(workspace), need.value, stream),
+                'remap_column_fractions')
         n_bad = int(bad.item())
     if n_bad:
         raise ValueError(f'{n_bad} entries name a column outside '

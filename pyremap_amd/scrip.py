@@ -162,16 +162,13 @@ def expanded_corners(centre_lat, centre_lon, corner_lat, corner_lon, count,
                                     corner_lon, count, expand_dist,
                                     expand_factor)
     from pyremap_amd import engine
-    torch = engine.require_gpu()
-    if device is None:
-        device = f'cuda:{torch.cuda.current_device()}'
-
-    def dev(x, dtype=np.float64):
-        return torch.from_numpy(np.ascontiguousarray(x, dtype=dtype)) \
-            .to(device)
+    engine.require_gpu()
+    device = weights._device(device)
     lat, lon = engine.expand_cells(
-        dev(centre_lat), dev(centre_lon), dev(corner_lat), dev(corner_lon),
-        dev(count, np.int32), expand_dist, expand_factor)
+        *(weights._to_device(x, device, np.float64) for x in (
+            centre_lat, centre_lon, corner_lat, corner_lon)),
+        weights._to_device(count, device, np.int32), expand_dist,
+        expand_factor)
     return lat.cpu().numpy(), lon.cpu().numpy()
 
 

@@ -556,6 +556,21 @@ def _gpu_present():
     return torch.cuda.is_available()
 
 
+def _device(device=None):
+    """``device``, or the current HIP device where it is None."""
+    if device is None:
+        import torch
+        device = f'cuda:{torch.cuda.current_device()}'
+    return device
+
+
+def _to_device(x, device, dtype=None):
+    """The array ``x`` (as ``dtype`` where one is given), contiguous, as a
+    tensor on ``device``."""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=dtype)).to(device)
+
+
 def _triangle_mapping(xyz, tri, found, w, n_b, dst_dims):
     """The mapping file of a point location: three entries per mapped point,
     sorted by (row, col); ``frac_b`` 1 where a triangle holds the point."""
@@ -597,15 +612,11 @@ def bilinear_mesh_weights(src_descriptor, plat, plon, dst_dims, device=None,
                          f'col is int32')
     plat = np.ascontiguousarray(plat, dtype=np.float64).reshape(-1)
     plon = np.ascontiguousarray(plon, dtype=np.float64).reshape(-1)
-    torch = engine.require_gpu()
-    if device is None:
-        device = f'cuda:{torch.cuda.current_device()}'
+    engine.require_gpu()
+    device = _device(device)
     found, w = engine.locate_in_triangles(
-        torch.from_numpy(np.ascontiguousarray(xyz)).to(device),
-        torch.from_numpy(np.ascontiguousarray(tri, dtype=np.int32))
-        .to(device),
-        torch.from_numpy(np.ascontiguousarray(_unit(plat, plon))).to(device),
-        timing=timing)
+        _to_device(xyz, device), _to_device(tri, device, np.int32),
+        _to_device(_unit(plat, plon), device), timing=timing)
     return _triangle_mapping(xyz, tri, found.cpu().numpy(), w.cpu().numpy(),
                              len(plat), dst_dims)
 
@@ -1084,12 +1095,11 @@ def bilinear_grid_weights(src_descriptor, plat, plon, dst_dims, device=None,
     q = np.ascontiguousarray(_unit(plat, plon))
     if _gpu_present():
         from pyremap_amd import engine
-        torch = engine.require_gpu()
-        if device is None:
-            device = f'cuda:{torch.cuda.current_device()}'
+        engine.require_gpu()
+        device = _device(device)
         found, w = engine.locate_in_quads(
-            torch.from_numpy(nodes).to(device),
-            torch.from_numpy(q).to(device), periodic=periodic, timing=timing)
+            _to_device(nodes, device), _to_device(q, device),
+            periodic=periodic, timing=timing)
         found, w = found.cpu().numpy(), w.cpu().numpy()
     else:
         found, w = locate_in_quads(nodes, q, periodic=periodic)
@@ -1149,6 +1159,29 @@ def latlon_corners(descriptor):
     return lat_e, lon_e, float(bulge.max(initial=0.0))
 
 
+def _conserve_mapping(overlaps, src_is_a, n_src, n_dst, src_dims, dst_dims):
+    """The mapping file of a conserve map from what an ``engine.overlap_*``
+    call returns, ``(row, col, A, frac_b, a_area, b_area)`` on the device
+    (0-based; side a is the source when ``src_is_a``): ``S = A /
+    dst_area[row]``, 1-based int32 ``row`` / ``col``, the areas of both
+    sides and ``frac_a``, the clamped column sums of ``A`` over the source's
+    areas (:func:`pyremap_amd.engine.column_fractions`, while everything is
+    still on the device).  ``src_dims`` / ``dst_dims``: Fortran-ordered."""
+    from pyremap_amd import engine
+    row, col, A, frac_b, a_area, b_area = overlaps
+    src_area, dst_area = (a_area, b_area) if src_is_a else (b_area, a_area)
+    frac_a = engine.column_fractions(col, A, len(src_area), denom=src_area,
+                                     clamp=True).cpu().numpy()
+    row, col, A, frac_b, src_area, dst_area = (
+        x.cpu().numpy() for x in (row, col, A, frac_b, src_area, dst_area))
+    S = A / dst_area[row]
+    return MappingFile(n_src, n_dst, np.array(src_dims, dtype=np.int32),
+                       np.array(dst_dims, dtype=np.int32),
+                       (row + 1).astype(np.int32), (col + 1).astype(np.int32),
+                       S, frac_b, area_a=src_area, area_b=dst_area,
+                       frac_a=frac_a)
+
+
 def conserve_mesh_latlon(mesh_descriptor, grid_descriptor, mesh_is_src=True,
                          device=None, timing=None):
     """
@@ -1162,37 +1195,22 @@ def conserve_mesh_latlon(mesh_descriptor, grid_descriptor, mesh_is_src=True,
     (:func:`pyremap_amd.engine.overlap_latlon`).
     """
     from pyremap_amd import engine
-    torch = engine.require_gpu()
+    engine.require_gpu()
     voc, noc, lat_v, lon_v = mesh_polygons(mesh_descriptor)
     lat_e, lon_e, slack = latlon_corners(grid_descriptor)
-    if device is None:
-        device = f'cuda:{torch.cuda.current_device()}'
-
-    def dev(a):
-        return torch.from_numpy(np.ascontiguousarray(a)).to(device)
-    dst, src, A, frac_b, mesh_area, grid_area = engine.overlap_latlon(
-        dev(voc), dev(noc), dev(lat_v), dev(lon_v), dev(lat_e), dev(lon_e),
+    device = _device(device)
+    # the mesh is side a, the grid side b
+    overlaps = engine.overlap_latlon(
+        *(_to_device(a, device) for a in (voc, noc, lat_v, lon_v, lat_e,
+                                          lon_e)),
         slack, dst_is_mesh=not mesh_is_src, timing=timing)
-    src_area = mesh_area if mesh_is_src else grid_area
-    frac_a = engine.column_fractions(src, A, len(src_area), denom=src_area,
-                                     clamp=True).cpu().numpy()
-    dst = dst.cpu().numpy()
-    src = src.cpu().numpy()
-    A = A.cpu().numpy()
-    frac_b = frac_b.cpu().numpy()
-    dst_area = (grid_area if mesh_is_src else mesh_area).cpu().numpy()
-    S = A / dst_area[dst]
-    n_mesh, n_grid = len(noc), (len(lat_e) - 1) * (len(lon_e) - 1)
-    mesh_dims = np.array([n_mesh], dtype=np.int32)
-    grid_dims = np.array([len(lon_e) - 1, len(lat_e) - 1], dtype=np.int32)
-    if mesh_is_src:
-        n_a, n_b, src_dims, dst_dims = n_mesh, n_grid, mesh_dims, grid_dims
-    else:
-        n_a, n_b, src_dims, dst_dims = n_grid, n_mesh, grid_dims, mesh_dims
-    return MappingFile(n_a, n_b, src_dims, dst_dims,
-                       (dst + 1).astype(np.int32), (src + 1).astype(np.int32),
-                       S, frac_b, area_a=src_area.cpu().numpy(),
-                       area_b=dst_area, frac_a=frac_a)
+    mesh = len(noc), [len(noc)]
+    grid = ((len(lat_e) - 1) * (len(lon_e) - 1),
+            [len(lon_e) - 1, len(lat_e) - 1])
+    (n_src, src_dims), (n_dst, dst_dims) = (mesh, grid) if mesh_is_src else \
+        (grid, mesh)
+    return _conserve_mapping(overlaps, mesh_is_src, n_src, n_dst, src_dims,
+                             dst_dims)
 
 
 def conserve_mesh_mesh(src_descriptor, dst_descriptor, device=None,
@@ -1207,35 +1225,19 @@ def conserve_mesh_mesh(src_descriptor, dst_descriptor, device=None,
     same overlap areas, transposed.
     """
     from pyremap_amd import engine
-    torch = engine.require_gpu()
+    engine.require_gpu()
     src = mesh_polygons(src_descriptor)
     dst = mesh_polygons(dst_descriptor)
-    if device is None:
-        device = f'cuda:{torch.cuda.current_device()}'
-
-    def dev(arrays):
-        return [torch.from_numpy(np.ascontiguousarray(a)).to(device)
-                for a in arrays]
+    device = _device(device)
     n_src, n_dst = len(src[1]), len(dst[1])
     src_is_a = n_src >= n_dst
     mesh_a, mesh_b = (src, dst) if src_is_a else (dst, src)
-    row, col, A, frac_b, a_area, b_area = engine.overlap_meshes(
-        dev(mesh_a), dev(mesh_b), dst_is_b=src_is_a, timing=timing)
-    src_area = a_area if src_is_a else b_area
-    frac_a = engine.column_fractions(col, A, len(src_area), denom=src_area,
-                                     clamp=True).cpu().numpy()
-    src_area = src_area.cpu().numpy()
-    row = row.cpu().numpy()
-    col = col.cpu().numpy()
-    A = A.cpu().numpy()
-    frac_b = frac_b.cpu().numpy()
-    dst_area = (b_area if src_is_a else a_area).cpu().numpy()
-    S = A / dst_area[row]
-    return MappingFile(n_src, n_dst, np.array([n_src], dtype=np.int32),
-                       np.array([n_dst], dtype=np.int32),
-                       (row + 1).astype(np.int32), (col + 1).astype(np.int32),
-                       S, frac_b, area_a=src_area, area_b=dst_area,
-                       frac_a=frac_a)
+    overlaps = engine.overlap_meshes(
+        [_to_device(a, device) for a in mesh_a],
+        [_to_device(a, device) for a in mesh_b], dst_is_b=src_is_a,
+        timing=timing)
+    return _conserve_mapping(overlaps, src_is_a, n_src, n_dst, [n_src],
+                             [n_dst])
 
 
 # ---------------------------------------------------------------------------
@@ -1313,32 +1315,16 @@ def conserve_grid(src_descriptor, dst_descriptor, device=None, timing=None):
         raise ValueError(f'{_GRID_PAIRS}; neither side is one')
     src, n_src, src_dims = _grid_side(src_descriptor)
     dst, n_dst, dst_dims = _grid_side(dst_descriptor)
-    torch = engine.require_gpu()
-    if device is None:
-        device = f'cuda:{torch.cuda.current_device()}'
-
-    def dev(arrays):
-        return [torch.from_numpy(np.ascontiguousarray(a)).to(device)
-                for a in arrays]
+    engine.require_gpu()
+    device = _device(device)
     src_is_a = n_src >= n_dst
     side_a, side_b = (src, dst) if src_is_a else (dst, src)
-    row, col, A, frac_b, a_area, b_area = engine.overlap_grids(
-        dev(side_a), dev(side_b), dst_is_b=src_is_a, timing=timing)
-    src_area = a_area if src_is_a else b_area
-    frac_a = engine.column_fractions(col, A, len(src_area), denom=src_area,
-                                     clamp=True).cpu().numpy()
-    src_area = src_area.cpu().numpy()
-    row = row.cpu().numpy()
-    col = col.cpu().numpy()
-    A = A.cpu().numpy()
-    frac_b = frac_b.cpu().numpy()
-    dst_area = (b_area if src_is_a else a_area).cpu().numpy()
-    S = A / dst_area[row]
-    return MappingFile(n_src, n_dst, np.array(src_dims, dtype=np.int32),
-                       np.array(dst_dims, dtype=np.int32),
-                       (row + 1).astype(np.int32), (col + 1).astype(np.int32),
-                       S, frac_b, area_a=src_area, area_b=dst_area,
-                       frac_a=frac_a)
+    overlaps = engine.overlap_grids(
+        [_to_device(a, device) for a in side_a],
+        [_to_device(a, device) for a in side_b], dst_is_b=src_is_a,
+        timing=timing)
+    return _conserve_mapping(overlaps, src_is_a, n_src, n_dst, src_dims,
+                             dst_dims)
 
 
 # ---------------------------------------------------------------------------
@@ -1863,44 +1849,42 @@ def _expanded_side(descriptor, expand_dist, expand_factor, device):
             raise ValueError(
                 'expanding the cells of an MPAS mesh needs their centres: '
                 'give the descriptor a mesh file')
-        dims = [n]
     else:
         centres = _cell_centres(descriptor)[:2]
-        ny, nx = descriptor.dim_sizes
-        dims = [nx, ny]
     valid = np.arange(width)[None, :] < noc[:, None]
     ids = np.where(valid, voc.astype(np.int64) - 1, 0)
-    torch = engine.require_gpu()
-
-    def dev(x, dtype=np.float64):
-        return torch.from_numpy(np.ascontiguousarray(x, dtype=dtype)) \
-            .to(device)
+    engine.require_gpu()
     out_lat, out_lon = engine.expand_cells(
-        dev(centres[0]), dev(centres[1]), dev(np.where(valid, lat[ids], 0.0)),
-        dev(np.where(valid, lon[ids], 0.0)), dev(noc, np.int32),
-        expand_dist, expand_factor)
+        *(_to_device(x, device, np.float64) for x in (
+            centres[0], centres[1], np.where(valid, lat[ids], 0.0),
+            np.where(valid, lon[ids], 0.0))),
+        _to_device(noc, device, np.int32), expand_dist, expand_factor)
     lat = out_lat.cpu().numpy().reshape(-1)
     lon = out_lon.cpu().numpy().reshape(-1)
     own = np.arange(n * width, dtype=np.int64).reshape(n, width)
-    pvoc, pnoc, parent = convex_pieces(_unit_poles(lat, lon), own, noc)
-    return [pvoc, pnoc, lat, lon, None if len(parent) == n else parent,
-            n], n, dims
+    return _pieces_side(descriptor, own, noc, lat, lon)
 
 
-def _polygon_side(descriptor):
+def _pieces_side(descriptor, poly, noc, lat, lon):
     """(pieces for engine.overlap_pieces as numpy arrays, cells,
-    Fortran-ordered dims) of one side of :func:`conserve_polygons`."""
-    voc, noc, lat, lon = cell_polygons(descriptor)
+    Fortran-ordered dims) of the cells ``poly`` (0-based ids of the nodes
+    ``lat`` / ``lon``, ``noc`` per cell) of ``descriptor``, cut into convex
+    pieces (:func:`convex_pieces`)."""
     n = len(noc)
     if isinstance(descriptor, MpasMeshDescriptor):
         dims = [n]
     else:
         ny, nx = descriptor.dim_sizes
         dims = [nx, ny]
-    pvoc, pnoc, parent = convex_pieces(_unit_poles(lat, lon),
-                                       voc.astype(np.int64) - 1, noc)
+    pvoc, pnoc, parent = convex_pieces(_unit_poles(lat, lon), poly, noc)
     return [pvoc, pnoc, lat, lon, None if len(parent) == n else parent,
             n], n, dims
+
+
+def _polygon_side(descriptor):
+    """:func:`_pieces_side` of one side of :func:`conserve_polygons`."""
+    voc, noc, lat, lon = cell_polygons(descriptor)
+    return _pieces_side(descriptor, voc.astype(np.int64) - 1, noc, lat, lon)
 
 
 def conserve_polygons(src_descriptor, dst_descriptor, device=None,
@@ -1929,36 +1913,21 @@ def conserve_polygons(src_descriptor, dst_descriptor, device=None,
     expand = expand_dist is not None or expand_factor is not None
     if not expand:
         dst, n_dst, dst_dims = _polygon_side(dst_descriptor)
-    torch = engine.require_gpu()
-    if device is None:
-        device = f'cuda:{torch.cuda.current_device()}'
+    engine.require_gpu()
+    device = _device(device)
     if expand:
         dst, n_dst, dst_dims = _expanded_side(dst_descriptor, expand_dist,
                                               expand_factor, device)
 
-    def dev(side):
+    def on_device(side):
         return [x if x is None or isinstance(x, int) else
-                torch.from_numpy(np.ascontiguousarray(x)).to(device)
-                for x in side]
+                _to_device(x, device) for x in side]
     src_is_a = len(src[1]) >= len(dst[1])
     side_a, side_b = (src, dst) if src_is_a else (dst, src)
-    row, col, A, frac_b, a_area, b_area = engine.overlap_pieces(
-        dev(side_a), dev(side_b), dst_is_b=src_is_a, timing=timing)
-    src_area = a_area if src_is_a else b_area
-    frac_a = engine.column_fractions(col, A, len(src_area), denom=src_area,
-                                     clamp=True).cpu().numpy()
-    src_area = src_area.cpu().numpy()
-    row = row.cpu().numpy()
-    col = col.cpu().numpy()
-    A = A.cpu().numpy()
-    frac_b = frac_b.cpu().numpy()
-    dst_area = (b_area if src_is_a else a_area).cpu().numpy()
-    S = A / dst_area[row]
-    return MappingFile(n_src, n_dst, np.array(src_dims, dtype=np.int32),
-                       np.array(dst_dims, dtype=np.int32),
-                       (row + 1).astype(np.int32), (col + 1).astype(np.int32),
-                       S, frac_b, area_a=src_area, area_b=dst_area,
-                       frac_a=frac_a)
+    overlaps = engine.overlap_pieces(on_device(side_a), on_device(side_b),
+                                     dst_is_b=src_is_a, timing=timing)
+    return _conserve_mapping(overlaps, src_is_a, n_src, n_dst, src_dims,
+                             dst_dims)
 
 
 def projected_grid(descriptor):
@@ -2010,14 +1979,12 @@ def nearest_weights(src_lat, src_lon, dst_lat, dst_lon, src_dims, dst_dims,
     if n_a > np.iinfo(np.int32).max:
         raise ValueError(f'{n_a} source points: the mapping file\'s col is '
                          f'int32')
-    torch = engine.require_gpu()
-    if device is None:
-        device = f'cuda:{torch.cuda.current_device()}'
-    src = torch.from_numpy(np.ascontiguousarray(_unit(src_lat, src_lon)))
-    dst = torch.from_numpy(np.ascontiguousarray(
-        _unit(dst_lat, dst_lon).reshape(-1, 3)))
-    nearest = engine.nearest_points(src.to(device), dst.to(device),
-                                    timing=timing).cpu().numpy()
+    engine.require_gpu()
+    device = _device(device)
+    nearest = engine.nearest_points(
+        _to_device(_unit(src_lat, src_lon), device),
+        _to_device(_unit(dst_lat, dst_lon).reshape(-1, 3), device),
+        timing=timing).cpu().numpy()
     return MappingFile(n_a, n_b, np.asarray(src_dims, dtype=np.int32),
                        np.asarray(dst_dims, dtype=np.int32),
                        np.arange(1, n_b + 1, dtype=np.int32),
@@ -2242,15 +2209,12 @@ def _areas_of(corner_lat, corner_lon, count, device=None):
     if not _gpu_present():
         return cell_areas(corner_lat, corner_lon, count)
     from pyremap_amd import engine
-    torch = engine.require_gpu()
-    if device is None:
-        device = f'cuda:{torch.cuda.current_device()}'
-
-    def dev(x, dtype=np.float64):
-        return torch.from_numpy(np.ascontiguousarray(x, dtype=dtype)) \
-            .to(device)
-    return engine.cell_areas(dev(corner_lat), dev(corner_lon),
-                             dev(count, np.int32)).cpu().numpy()
+    engine.require_gpu()
+    device = _device(device)
+    return engine.cell_areas(
+        _to_device(corner_lat, device, np.float64),
+        _to_device(corner_lon, device, np.float64),
+        _to_device(count, device, np.int32)).cpu().numpy()
 
 
 def _side_geometry(descriptor, expand_dist=None, expand_factor=None):
@@ -2279,16 +2243,12 @@ def _fractions_of(col, value, n_cols, denom, device=None):
     if not _gpu_present():
         return column_fractions(col, value, n_cols, denom=denom, clamp=True)
     from pyremap_amd import engine
-    torch = engine.require_gpu()
-    if device is None:
-        device = f'cuda:{torch.cuda.current_device()}'
-
-    def dev(x, dtype):
-        return torch.from_numpy(np.ascontiguousarray(x, dtype=dtype)) \
-            .to(device)
+    engine.require_gpu()
+    device = _device(device)
     return engine.column_fractions(
-        dev(col, np.int64), dev(value, np.float64), n_cols,
-        denom=dev(denom, np.float64), clamp=True).cpu().numpy()
+        _to_device(col, device, np.int64),
+        _to_device(value, device, np.float64), n_cols,
+        denom=_to_device(denom, device, np.float64), clamp=True).cpu().numpy()
 
 
 def complete_mapping(m, src_descriptor, dst_descriptor, method='conserve',
