@@ -1878,6 +1878,45 @@ def in_place_addressable(shape, remap_axes):
     return axes == list(range(lead, lead + len(axes)))
 
 
+def check_field_extents(n_a, n_b, n_b_global, dst_grid_dims, shape,
+                        remap_axes):
+    """
+    The contract between a field and a mapping, stated once: the axes
+    ``remap_axes`` of a field of shape ``shape`` hold exactly ``n_a`` source
+    cells, and ``dst_grid_dims`` (C order; ``None``: flat rows) holds exactly
+    ``n_b`` cells.  A row shard (``n_b != n_b_global``) answers with its flat
+    slab of rows, so its ``dst_grid_dims`` -- the grid of the WHOLE mapping --
+    is not compared.  Raises ``ValueError``; returns ``(axes, dst_shape)``:
+    the axes made non-negative and the destination dims of the result.
+
+    Everything behind this check addresses raw pointers with ``n_a`` and
+    ``n_b``: every route to a launch or a 2-D copy calls it before its first
+    allocation, stream wait, thread, copy or launch.
+    """
+    # (plain loops: this runs in front of every launch, microseconds count)
+    ndim = len(shape)
+    axes = [int(a) % ndim for a in remap_axes]
+    n_src = 1
+    for ax in axes:
+        n_src *= int(shape[ax])
+    if n_src != n_a:
+        raise ValueError(
+            f'the remapped axes hold {n_src} source cells but the mapping '
+            f'has n_a = {n_a}')
+    # rows stay flat for a shard (its rows are no whole grid) and when the
+    # caller names no destination grid
+    if dst_grid_dims is None or n_b != n_b_global:
+        return axes, [int(n_b)]
+    dst_shape = [int(d) for d in dst_grid_dims]
+    n_dst = 1
+    for d in dst_shape:
+        n_dst *= d
+    if n_dst != n_b:
+        raise ValueError(f'dst_grid_dims {dst_shape} do not hold n_b = '
+                         f'{n_b} cells')
+    return axes, dst_shape
+
+
 def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
                  want_mask=False, flags=0, tune=None, out=None, gate=None,
                  gate_value=0, mask_out=None):
@@ -1903,14 +1942,11 @@ def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
         return plan.remap_tensor(dst_grid_dims, field, remap_axes, mode,
                                  threshold=threshold, want_mask=want_mask,
                                  flags=flags)
-    remap_axes = [int(a) % field.ndim for a in remap_axes]
+    remap_axes, dst_shape = check_field_extents(
+        plan.n_a, plan.n_b, plan.n_b_global, dst_grid_dims, field.shape,
+        remap_axes)
     ndim = field.ndim
     extra_axes = [ax for ax in range(ndim) if ax not in remap_axes]
-    n_src = _prod(field.shape[ax] for ax in remap_axes)
-    if n_src != plan.n_a:
-        raise ValueError(
-            f'the remapped axes hold {n_src} source cells but the mapping '
-            f'has n_a = {plan.n_a}')
     if field.dtype not in (torch.float64, torch.float32):
         # scipy upcasts everything else to float64 before the product
         field = field.to(torch.float64)
@@ -1922,14 +1958,6 @@ def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
     n_batch = _prod(lead_shape)
     k_inner = _prod(tail_shape)
     direct = in_place_addressable(field.shape, remap_axes)
-    sharded = plan.n_b != plan.n_b_global
-    # rows stay flat for a shard (its rows are no whole grid) and when the
-    # caller names no destination grid
-    dst_shape = [plan.n_b] if sharded or dst_grid_dims is None \
-        else [int(d) for d in dst_grid_dims]
-    if not sharded and _prod(dst_shape) != plan.n_b:
-        raise ValueError(f'dst_grid_dims {dst_shape} do not hold n_b = '
-                         f'{plan.n_b} cells')
     out_shape = lead_shape + dst_shape + tail_shape
     if out is not None:
         # the kernel writes through out.data_ptr(): anything but a float64,
@@ -2007,7 +2035,8 @@ def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
     # general axis order (or a very short contiguous run): one device
     # transpose to (n_a, K), the kernel, one transpose back
     K = _prod(field.shape[ax] for ax in extra_axes)
-    X = field.permute(remap_axes + extra_axes).reshape(n_src, K).contiguous()
+    X = field.permute(remap_axes + extra_axes).reshape(plan.n_a, K)\
+        .contiguous()
     Y = torch.empty((plan.n_b, K), dtype=torch.float64, device=field.device)
     mask = torch.empty((plan.n_b, K), dtype=torch.uint8,
                        device=field.device) if want_mask else None
@@ -2092,6 +2121,10 @@ def remap_tensor_auto_mode(plan, dst_grid_dims, field, remap_axes, threshold,
     whose masked branch has two forms), nothing synchronises.
     """
     torch = _torch()
+    # (before the scan below is enqueued: remap_tensor would say the same,
+    # but only after it)
+    check_field_extents(plan.n_a, plan.n_b, plan.n_b_global, dst_grid_dims,
+                        field.shape, remap_axes)
     if hasattr(plan, 'shards'):
         if out is not None or flag is not None:
             raise ValueError("out / flag address ONE device's launch; not "
@@ -2150,6 +2183,12 @@ def gather_rows(field, axis, rows, out=None):
     the library's ``remap_gather_rows``: the packed source buffer
     ``X[ucols]`` a row shard's GPU receives.  ``rows``: int32 device tensor.
     Asynchronous on torch's current stream.
+
+    Every listed row must lie below ``field.shape[axis]``: the kernel reads
+    ``field`` at each of them and has no bound, and reading ``rows`` back to
+    compare would synchronise the stream.  The callers check the field's
+    extent against the mapping the rows come from
+    (:func:`check_field_extents`) before they get here.
     """
     torch = _torch()
     lib = load_library()

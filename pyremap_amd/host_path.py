@@ -19,6 +19,7 @@ What this module is about is everything AROUND the 0.4 ms kernel:
 * nothing blocks until the caller asks for the data: a Dataset's variables
   are all enqueued before the first result is awaited.
 """
+import ctypes
 import os
 import queue
 import threading
@@ -68,30 +69,48 @@ N_UPLOADERS = 1
 PANEL_COLUMNS = 128
 PANEL_MIN = 3
 
+#: the handle of :func:`_hip`: ``None`` = not looked for yet, ``False`` = no
+#: runtime could be loaded
 _hip_runtime = [None]
+
+#: sonames tried after torch's own copy: the name a process that runs torch
+#: has already loaded, then the versioned ones of a system ROCm
+_HIP_SONAMES = ('libamdhip64.so', 'libamdhip64.so.7', 'libamdhip64.so.6',
+                'libamdhip64.so.5')
 
 
 def _hip():
     """The HIP runtime torch itself uses (2-D copies: torch's strided
     ``copy_`` between host and device goes through a host-side contiguous
-    copy at 4-5 GB/s)."""
+    copy at 4-5 GB/s), resolved once: torch's lib directory (the wheels
+    carry their own), then the sonames of a system ROCm that torch was built
+    against.  ``None`` when none of them loads -- the column-panel route
+    then declines and the plain form answers."""
     if _hip_runtime[0] is None:
-        import ctypes
         torch = engine._torch()
-        lib = ctypes.CDLL(os.path.join(os.path.dirname(torch.__file__),
-                                       'lib', 'libamdhip64.so'))
-        lib.hipMemcpy2DAsync.restype = ctypes.c_int
-        lib.hipMemcpy2DAsync.argtypes = [
-            ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
-            ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int,
-            ctypes.c_void_p]
-        _hip_runtime[0] = lib
-    return _hip_runtime[0]
+        names = (os.path.join(os.path.dirname(torch.__file__), 'lib',
+                              'libamdhip64.so'),) + _HIP_SONAMES
+        _hip_runtime[0] = False
+        for name in names:
+            try:
+                lib = ctypes.CDLL(name)
+                lib.hipMemcpy2DAsync.restype = ctypes.c_int
+            except (OSError, AttributeError):
+                continue
+            lib.hipMemcpy2DAsync.argtypes = [
+                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                ctypes.c_int, ctypes.c_void_p]
+            _hip_runtime[0] = lib
+            break
+        else:
+            _log_once('hip', 'no HIP runtime could be loaded for 2-D '
+                      'copies; (n_a, K) host arrays take the plain form')
+    return _hip_runtime[0] or None
 
 
 def _copy_2d(dst_ptr, dst_pitch, src_ptr, src_pitch, width, height, kind,
              stream):
-    import ctypes
     rc = _hip().hipMemcpy2DAsync(dst_ptr, dst_pitch, src_ptr, src_pitch,
                                  width, height, kind,
                                  ctypes.c_void_p(stream.cuda_stream))
@@ -349,11 +368,10 @@ def remap_host_batch(plan, dst_grid_dims, arrays, remap_axes, *, mode,
     if mode == 'auto' and threshold is None:
         raise ValueError('the masked branch needs a threshold')
     V, nd = len(arrays), len(shape)
-    axes = [int(a) % nd for a in remap_axes]
+    axes, dst_shape = engine.check_field_extents(
+        plan.n_a, plan.n_b, plan.n_b_global, dst_grid_dims, shape,
+        remap_axes)
     lead = min(axes)
-    dst_shape = [int(d) for d in dst_grid_dims] \
-        if dst_grid_dims is not None and plan.n_b == plan.n_b_global \
-        else [plan.n_b]
     out_shape = [V] + list(shape[:lead]) + dst_shape + \
         [int(shape[ax]) for ax in range(lead, nd) if ax not in axes]
     stacked_axes = [a + 1 for a in axes]
@@ -389,7 +407,8 @@ def remap_host_batch(plan, dst_grid_dims, arrays, remap_axes, *, mode,
                 except BaseException as exc:   # noqa: BLE001 - handed over
                     arrivals.put(exc)
 
-            feeder = threading.Thread(target=uploader, daemon=True)
+            feeder = threading.Thread(target=uploader, daemon=True,
+                                      name='pyremap_amd.batch_uploader')
             feeder.start()
             for k in range(n_sub):
                 lo, hi = bounds[k], bounds[k + 1]
@@ -468,7 +487,11 @@ def remap_host_array(plan, dst_grid_dims, values, remap_axes, *, mode,
     torch = engine.require_gpu()
     device = plan.device
     values = _as_uploadable(values)
-    remap_axes = [int(a) % values.ndim for a in remap_axes]
+    # every route below -- and the pinned result -- is sized from n_a, n_b
+    # and the other dims: a field that does not match the mapping stops here
+    remap_axes, dst_shape = engine.check_field_extents(
+        plan.n_a, plan.n_b, plan.n_b_global, dst_grid_dims, values.shape,
+        remap_axes)
     lead = min(remap_axes)
     n_batch = _prod(values.shape[:lead])
     in_place = engine.in_place_addressable(values.shape, remap_axes)
@@ -483,9 +506,6 @@ def remap_host_array(plan, dst_grid_dims, values, remap_axes, *, mode,
     up, down = _side_streams(device)
     main = torch.cuda.current_stream(device)
     host = torch.from_numpy(values)
-    dst_shape = [int(d) for d in dst_grid_dims] \
-        if dst_grid_dims is not None and plan.n_b == plan.n_b_global \
-        else [plan.n_b]
     # (remap_numpy.py:280-295: the destination dims take the place of the
     # first source axis, every other non-source dim keeps its order -- also
     # the ones BETWEEN two source axes)
@@ -568,8 +588,8 @@ def _enqueue(plan, dst_grid_dims, values, host, remap_axes, lead, n_batch,
         values.nbytes >= 4 * CHUNK_BYTES and values.flags.c_contiguous and \
         out_h.is_pinned() and (mask_h is None or mask_h.is_pinned())
     if panels:
-        got = _panel_pipeline(plan, values, out_h, mask_h, mode, thr, flags,
-                              up, down, main)
+        got = _panel_pipeline(plan, values, remap_axes, out_h, mask_h, mode,
+                              thr, flags, up, down, main)
         if got is not None:
             done, recheck = got
             return Pending(done, out_h, mask_h, (pin_o, pin_m),
@@ -578,8 +598,8 @@ def _enqueue(plan, dst_grid_dims, values, host, remap_axes, lead, n_batch,
     x_d = torch.empty(values.shape, dtype=host.dtype, device=device) \
         if single or banded else None
     if banded:
-        done = _banded_pipeline(plan, values, host, x_d, out_h, mask_h,
-                                mode, thr, flags, up, down, main)
+        done = _banded_pipeline(plan, values, remap_axes, host, x_d, out_h,
+                                mask_h, mode, thr, flags, up, down, main)
         if done is not None:
             return Pending(done, out_h, mask_h, (pin_o, pin_m))
     if single:
@@ -701,7 +721,8 @@ def _enqueue(plan, dst_grid_dims, values, host, remap_axes, lead, n_batch,
         except BaseException as exc:   # noqa: BLE001 - handed over
             arrivals[k].put(exc)
 
-    feeders = [threading.Thread(target=uploader, args=(k,), daemon=True)
+    feeders = [threading.Thread(target=uploader, args=(k,), daemon=True,
+                                name=f'pyremap_amd.ring_uploader_{k}')
                for k in range(n_up)]
     for f in feeders:
         f.start()
@@ -751,8 +772,8 @@ def _enqueue(plan, dst_grid_dims, values, host, remap_axes, lead, n_batch,
     return Pending(finished, out_h, mask_h, (pin_o, pin_m))
 
 
-def _panel_pipeline(plan, values, out_h, mask_h, mode, thr, flags, up, down,
-                    main):
+def _panel_pipeline(plan, values, remap_axes, out_h, mask_h, mode, thr,
+                    flags, up, down, main):
     """
     A host field whose source axes lead -- ``(n_a, K)``, what the reference
     flattens every field to (``remap_numpy.py:254-256``) -- in COLUMN PANELS:
@@ -769,17 +790,28 @@ def _panel_pipeline(plan, values, out_h, mask_h, mode, thr, flags, up, down,
     remapped in the frac_b mode while a device scan of each looks for NaNs;
     the returned ``recheck`` reads the scans' flag when the result is asked
     for and, should it be set, remaps the (still resident) panels again in
-    the masked mode.  Returns ``(event, recheck)`` or ``None`` to decline.
+    the masked mode.  Returns ``(event, recheck)`` or ``None`` to decline:
+    too few panels, no HIP runtime for the 2-D copies (:func:`_hip`), or
+    panels -- source, result and mask stay resident until the result is
+    asked for -- beyond ``DEVICE_FRACTION`` of the free device memory.
+
+    The caller has checked the field against the mapping
+    (``engine.check_field_extents``); K is the product of the dims behind
+    the (leading) source axes.
     """
     torch = engine._torch()
     device = plan.device
     n_a, n_b = plan.n_a, plan.n_b
-    K = values.size // n_a
+    K = _prod(values.shape[len(remap_axes):])
     kp = PANEL_COLUMNS
     n_p = (K + kp - 1) // kp
-    if n_p < PANEL_MIN:
+    if n_p < PANEL_MIN or _hip() is None:
         return None
     esize = values.dtype.itemsize
+    need = n_p * kp * (n_a * esize + n_b * (9 if mask_h is not None else 8))
+    free, _ = torch.cuda.mem_get_info(device)
+    if need > DEVICE_FRACTION * free:
+        return None
     tdtype = torch.from_numpy(values.reshape(-1)[:0]).dtype
     bounds = [(p * kp, min((p + 1) * kp, K)) for p in range(n_p)]
     x_p = torch.empty((n_p, n_a, kp), dtype=tdtype, device=device)
@@ -826,7 +858,8 @@ def _panel_pipeline(plan, values, out_h, mask_h, mode, thr, flags, up, down,
             _copy_2d(mask_h.data_ptr() + c0, K, m_p[p].data_ptr(), kp,
                      c1 - c0, n_b, 2, down)
 
-    feeder = threading.Thread(target=uploader, daemon=True)
+    feeder = threading.Thread(target=uploader, daemon=True,
+                              name='pyremap_amd.panel_uploader')
     feeder.start()
     finished = None
     try:
@@ -887,8 +920,8 @@ def _panel_pipeline(plan, values, out_h, mask_h, mode, thr, flags, up, down,
     return finished, recheck
 
 
-def _banded_pipeline(plan, values, host, x_d, out_h, mask_h, mode, thr,
-                     flags, up, down, main):
+def _banded_pipeline(plan, values, remap_axes, host, x_d, out_h, mask_h, mode,
+                     thr, flags, up, down, main):
     """
     A field whose source axes lead -- ``(n_a, K)``, rows contiguous on both
     sides -- with the mode known: X goes up in row chunks, and a block of
@@ -903,7 +936,9 @@ def _banded_pipeline(plan, values, host, x_d, out_h, mask_h, mode, thr,
     torch = engine._torch()
     device = plan.device
     n_a, n_b = plan.n_a, plan.n_b
-    K = values.size // n_a
+    # (the field matches the mapping: engine.check_field_extents in
+    # remap_host_array; the source axes lead)
+    K = _prod(values.shape[len(remap_axes):])
     if K < 33:
         return None        # the wave-per-row kernels serve partial row ranges
     xh = host.reshape(n_a, K)
@@ -949,7 +984,8 @@ def _banded_pipeline(plan, values, host, x_d, out_h, mask_h, mode, thr,
         except BaseException as exc:   # noqa: BLE001 - handed over
             arrivals.put(exc)
 
-    feeder = threading.Thread(target=uploader, daemon=True)
+    feeder = threading.Thread(target=uploader, daemon=True,
+                              name='pyremap_amd.banded_uploader')
     feeder.start()
     have = 0
     finished = None

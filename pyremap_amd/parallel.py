@@ -300,6 +300,15 @@ class ShardedRemap:
         return packed_fraction(self.packed_counts(), self._full.n_a)
 
     # -- the exchange ---------------------------------------------------------
+    def _check_source(self, shape, remap_axes, dst_grid_dims=None):
+        """A field of ``shape`` against the WHOLE mapping
+        (``engine.check_field_extents``)."""
+        from pyremap_amd import engine
+        full = self._full
+        return engine.check_field_extents(full.n_a, full.n_b,
+                                          full.n_b_global, dst_grid_dims,
+                                          shape, remap_axes)
+
     def _packed_shape(self, shape, axis, n):
         shape = list(shape)
         shape[axis] = int(n)
@@ -320,10 +329,17 @@ class ShardedRemap:
         broadcast), each rank gathers its own rows.  ``how='auto'``:
         ``self.exchange``.  With ``async_op`` returns ``(packed, works)``:
         wait on ``works`` before the first launch that reads ``packed``.
+
+        ``shape[axis]`` must be the mapping's ``n_a`` (``ValueError``
+        otherwise, on every rank, before anything is gathered or sent):
+        ``ucols`` index the rows of a whole source field.
         """
         from pyremap_amd import engine
         torch = _torch()
         import torch.distributed as dist
+        if field is not None:
+            shape, dtype = tuple(field.shape), field.dtype
+        self._check_source(shape, [axis])
         if how == 'auto':
             how = self.exchange
         if how not in self._logged:
@@ -335,8 +351,6 @@ class ShardedRemap:
                 '(this rank reads %.1f %% of the source rows)', self.rank,
                 self.world_size, how, 100.0 * int(self.ucols.shape[0]) /
                 max(self._full.n_a, 1))
-        if field is not None:
-            shape, dtype = tuple(field.shape), field.dtype
         axis = int(axis) % len(shape)
         if self.world_size == 1:
             packed = engine.gather_rows(field, axis, self.ucols)
@@ -378,6 +392,8 @@ class ShardedRemap:
         """
         from pyremap_amd import engine
         results = []
+        for x in batches:      # all of them, before the first exchange
+            self._check_source(tuple(x.shape), [0])
 
         def start(x):
             return self.distribute(x, src=src, axis=0, how=how,
@@ -430,6 +446,12 @@ class ShardedRemap:
         import torch.distributed as dist
         if field is not None:
             shape, dtype = tuple(field.shape), field.dtype
+        # on every rank, before the scan, the exchange and the launch
+        self._check_source(shape, remap_axes, dst_grid_dims)
+        if field is not None and self.rank == src:
+            # (a host tensor, or one on another GPU: the scan, the gather
+            # and the launch all address it from the plan's device)
+            field = field.to(self.plan.device)
         like = field if field is not None and self.rank == src else \
             torch.empty(shape, dtype=dtype, device='meta')
         # (a rank that only knows the shape goes through the same view
@@ -555,15 +577,14 @@ class MultiDeviceRemap:
         """
         from pyremap_amd import engine
         torch = _torch()
+        # before the field moves, is flattened or any shard launches
+        engine.check_field_extents(self.n_a, self.n_b, self.n_b_global,
+                                   dst_grid_dims, field.shape, remap_axes)
         field = field.to(self.device)
         if field.dtype not in (torch.float64, torch.float32):
             field = field.to(torch.float64)
         x3, lead_shape, tail_shape, unpermute = _flatten_source_axes(
             field, remap_axes)
-        if x3.shape[1] != self.n_a:
-            raise ValueError(
-                f'the remapped axes hold {x3.shape[1]} source cells but the '
-                f'mapping has n_a = {self.n_a}')
         n_batch, inner = int(x3.shape[0]), int(x3.shape[2])
         if _gate is not None:
             # remap_numpy.py:201-204 decided on the device, ONCE for the
