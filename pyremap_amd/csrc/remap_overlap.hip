@@ -1,58 +1,60 @@
-// remap_overlap.hip -- first-order conservative overlaps between an MPAS cell
-// mesh and a lat-lon grid (what ESMF_RegridWeightGen --method conserve
-// computes for pyremap's MPAS <-> lat-lon maps).
+// remap_overlap.hip -- first-order conservative overlaps on the sphere (what
+// ESMF_RegridWeightGen --method conserve computes), four routes to one back
+// end:
+//   remap_overlap_latlon   an MPAS cell mesh and a lat-lon grid
+//   remap_overlap_meshes   two MPAS cell meshes
+//   remap_overlap_pieces   cells that come in convex pieces
+//   remap_overlap_grids    a structured 2-D grid on one side or both
 //
 // Geometry (ESMF's convention): every cell is a spherical polygon with
 // great-circle edges, lat-lon cells included -- their "lat lines" are the
 // great-circle arcs between their corners.  Corners at a pole coincide, so
 // the polar rows' cells are triangles (a repeated corner is a zero-length
 // edge, which clips nothing and adds no area).  A_ij = spherical area of
-// (mesh cell n lat-lon cell); polygon areas come from the same formula.
+// (cell i n cell j); polygon areas come from the same formula.
 //
-// Pipeline (all on the caller's stream, fp64 throughout, no float atomics):
+// Every route (all on the caller's stream, fp64 throughout, no float
+// atomics) prepares the cells of side a (the subject) and side b (the
+// clipper), lists candidate pairs a << 32 | b, clips, and hands over to the
+// shared back end:
 //   cell_prep      one lane per mesh cell: vertices -> unit xyz (consecutive
 //                  duplicates dropped, turned counter-clockwise seen from
 //                  outside), the cell's own area, its centre and its
 //                  (lat, lon) box -- latitude extrema of the great-circle
 //                  arcs included, the poles' cells reaching +-90 deg over the
-//                  whole circle -- as rows and column ranges of the grid
-//   grid_area      one lane per lat-lon cell: its area
-//   exclusive scan rocPRIM over the candidate counts
-//   fill_pairs     one lane per mesh cell: key = mesh << 32 | grid cell
-//   clip_pairs     one lane per candidate: gnomonic projection about the
-//                  mesh cell's centre (great circles -> straight lines),
-//                  Sutherland-Hodgman of the mesh polygon by the lat-lon
-//                  cell's four edges in that plane, area of the result from
-//                  its 3-D vertices (fan of Van Oosterom-Strackee triangles)
-//   flag / scan / scatter  keep A_ij > kSliver * A_dst; re-key (dst, src)
-//   radix sort     rocPRIM radix_sort_pairs on (dst << 32 | src, A)
-//   dst_sums       one lane per destination cell: its entries summed in that
-//                  order -> frac_b = min(sum / A_dst, 1)
-// The polygons being clipped live in per-lane LDS slots (runtime-indexed
-// private arrays would go to scratch on gfx950).
-//
-// Between two MPAS meshes (remap_overlap_meshes, further down) the same
-// cell preparation runs against a raster of lat-lon buckets, candidate pairs
-// come from the buckets the cells' boxes share, and clip_pairs_poly clips a
-// cell of one mesh by a (convex) cell of the other.
-//
-// Cells that come in convex pieces (remap_overlap_pieces, behind the mesh
-// path: the concave cells of an MPAS vertex mesh as triangles) go through the
-// mesh path piece by piece up to clip_pairs_poly; the piece pairs are then
-// re-keyed to their cells, sorted, and merge_runs adds every run of equal
+//                  whole circle -- as rows and column ranges of a lat-lon
+//                  grid (the grid itself, or a raster of buckets)
+//   candidates     per route: the boxes (latlon), buckets the boxes share
+//                  (meshes, pieces), a pyramid of bounding caps (grids)
+//   the clip       Tangent / load_ring / clip_edge: gnomonic projection about
+//                  the subject's centre (great circles -> straight lines),
+//                  Sutherland-Hodgman by the clipper's edges in that plane;
+//                  clip_pairs (the four edges of a lat-lon cell, the area
+//                  from the vertices lifted to the sphere) and
+//                  clip_pairs_poly (a convex cell's edges, the area in the
+//                  plane) are its two kernels.  The polygons being clipped
+//                  live in per-lane LDS slots (runtime-indexed private
+//                  arrays would go to scratch on gfx950)
+//   keep_pairs     flag / scan / scatter: keep A_ij > kSliver * A_dst, re-key
+//                  (dst, src)
+//   sort_and_sum   rocPRIM radix_sort_pairs on (dst << 32 | src, A);
+//                  dst_sums, one lane per destination cell: its entries
+//                  summed in that order -> frac_b = min(sum / A_dst, 1)
+// remap_overlap_pieces leaves the back end after the clip: the piece pairs
+// are re-keyed to their cells, sorted, and merge_runs adds every run of equal
 // keys up in a fixed order before the sliver rule is applied to the sum.
 //
-// With a structured 2-D grid given by its corner arrays on one side or both
-// (remap_overlap_grids, at the end) the grid's cells are prepared straight
-// from the corners, candidates come from a pyramid of bounding caps over
-// the grid's own index space, and clip_pairs_poly and everything behind it
-// are the mesh path's.  Host read-backs: one in remap_overlap_latlon, two in
-// remap_overlap_meshes, one in remap_overlap_grids (the entry count with
-// every error bit, before the sort), remap_overlap_meshes' two and up to two
-// more in remap_overlap_pieces (the parents' check, the entry count behind
-// the merge); each _sizes call reads its count back.
+// The host side is written with a few helpers (launch, at, read_back, the
+// typed rocPRIM calls), one Route table per entry point that turns the error
+// bits into text (route_fail), and take() for every workspace layout.
+// Host read-backs: one in remap_overlap_latlon, two in remap_overlap_meshes,
+// one in remap_overlap_grids (the entry count with every error bit, before
+// the sort), remap_overlap_meshes' two and up to two more in
+// remap_overlap_pieces (the parents' check, the entry count behind the
+// merge); each _sizes call reads its count back.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <string.h>
 
@@ -87,6 +89,134 @@ constexpr double kBoxEps = 1e-9;
 
 constexpr size_t kAlign = 256;
 size_t align_up(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
+
+uint32_t blocks(int64_t n, int per) { return static_cast<uint32_t>((n + per - 1) / per); }
+// (no buffer and no rocPRIM call is sized 0)
+size_t at_least_one(int64_t n) { return static_cast<size_t>(n > 0 ? n : 1); }
+
+#define REMAP_TRY(expr)                                         \
+    do {                                                        \
+        const int rc__ = (expr);                                \
+        if (rc__ != REMAP_OK)                                   \
+            return rc__;                                        \
+    } while (0)
+
+// ---------------------------------------------------------------------------
+// host helpers: every launch, rocPRIM call, workspace pointer and read-back
+// of this file goes through these (each returns REMAP_OK or what fail() gave)
+// ---------------------------------------------------------------------------
+
+// one lane per item in blocks of `block`; nothing to launch for no items
+template <class... P, class... A>
+int launch(void (*kernel)(P...), int64_t n_items, int block,
+           hipStream_t stream, A... args)
+{
+    if (n_items <= 0)
+        return REMAP_OK;
+    hipLaunchKernelGGL(kernel, dim3(blocks(n_items, block)), dim3(block), 0,
+                       stream, static_cast<P>(args)...);
+    REMAP_HIP_CHECK(hipGetLastError());
+    return REMAP_OK;
+}
+
+template <class T>
+T *at(char *ws, size_t off)
+{
+    return reinterpret_cast<T *>(ws + off);
+}
+
+// a word of a counter block as what a kernel writes there
+template <class T, class U>
+T *as(U *word)
+{
+    return reinterpret_cast<T *>(word);
+}
+
+// bytes from the device, waited for
+int read_back(void *dst, const void *src, size_t bytes, hipStream_t stream)
+{
+    REMAP_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost,
+                                   stream));
+    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+    return REMAP_OK;
+}
+
+// rocPRIM, typed; *_temp: the bytes of temporary storage n items need
+template <class T>
+int exclusive_scan(void *temp, size_t temp_bytes, const T *in, T *out,
+                   int64_t n, hipStream_t stream)
+{
+    REMAP_HIP_CHECK((rocprim::exclusive_scan(temp, temp_bytes, in, out, T(0),
+                                             static_cast<size_t>(n),
+                                             rocprim::plus<T>(), stream)));
+    return REMAP_OK;
+}
+
+template <class T>
+int scan_temp(size_t n, size_t *bytes)
+{
+    REMAP_HIP_CHECK((rocprim::exclusive_scan(
+        nullptr, *bytes, static_cast<const T *>(nullptr),
+        static_cast<T *>(nullptr), T(0), n, rocprim::plus<T>())));
+    return REMAP_OK;
+}
+
+int radix_sort_keys(void *temp, size_t temp_bytes, const uint64_t *in,
+                    uint64_t *out, int64_t n, hipStream_t stream)
+{
+    REMAP_HIP_CHECK((rocprim::radix_sort_keys(temp, temp_bytes, in, out,
+                                              static_cast<size_t>(n), 0u, 64u,
+                                              stream)));
+    return REMAP_OK;
+}
+
+int sort_keys_temp(size_t n, size_t *bytes)
+{
+    REMAP_HIP_CHECK((rocprim::radix_sort_keys(
+        nullptr, *bytes, static_cast<const uint64_t *>(nullptr),
+        static_cast<uint64_t *>(nullptr), n, 0u, 64u)));
+    return REMAP_OK;
+}
+
+// V: double (areas) or uint32_t (positions)
+template <class V>
+int radix_sort_pairs(void *temp, size_t temp_bytes, const uint64_t *keys_in,
+                     uint64_t *keys_out, const V *in, V *out, int64_t n,
+                     hipStream_t stream)
+{
+    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
+        temp, temp_bytes, keys_in, keys_out, in, out, static_cast<size_t>(n),
+        0u, 64u, stream)));
+    return REMAP_OK;
+}
+
+template <class V>
+int sort_pairs_temp(size_t n, size_t *bytes)
+{
+    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
+        nullptr, *bytes, static_cast<const uint64_t *>(nullptr),
+        static_cast<uint64_t *>(nullptr), static_cast<const V *>(nullptr),
+        static_cast<V *>(nullptr), n, 0u, 64u)));
+    return REMAP_OK;
+}
+
+int unique(void *temp, size_t temp_bytes, const uint64_t *in, uint64_t *out,
+           uint64_t *n_unique, int64_t n, hipStream_t stream)
+{
+    REMAP_HIP_CHECK((rocprim::unique(temp, temp_bytes, in, out, n_unique,
+                                     static_cast<size_t>(n),
+                                     rocprim::equal_to<uint64_t>(), stream)));
+    return REMAP_OK;
+}
+
+int unique_temp(size_t n, size_t *bytes)
+{
+    REMAP_HIP_CHECK((rocprim::unique(
+        nullptr, *bytes, static_cast<const uint64_t *>(nullptr),
+        static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr),
+        n)));
+    return REMAP_OK;
+}
 
 // the lat-lon cell with 0-based index g = j * n_lon + i, corners SW, SE, NE,
 // NW (swapped to SW, NW, NE, SE when exactly one axis descends, so that the
@@ -437,14 +567,100 @@ __global__ __launch_bounds__(kBlock) void fill_pairs(
     }
 }
 
-// one lane per candidate pair: the overlap area
+// ---------------------------------------------------------------------------
+// the clip both clip kernels share: a polygon in the gnomonic plane of a
+// centre, in one lane's LDS ring [buffer][vertex][lane] (ping-pong), cut by
+// one directed edge at a time
+// ---------------------------------------------------------------------------
+
+// the tangent plane at a centre: great circles are straight lines in it
+struct Tangent {
+    V3 cc, e1, e2;
+    // (x, y) of p in the plane and t, the cosine of its angle to the centre
+    // (the projection reaches t >= kMinCos)
+    __device__ void project(V3 p, double *x, double *y, double *t) const
+    {
+        *t = dot(p, cc);
+        *x = dot(p, e1) / *t;
+        *y = dot(p, e2) / *t;
+    }
+};
+
+__device__ inline Tangent tangent_at(V3 cc)
+{
+    const V3 ref = fabs(cc.z) < 0.9 ? V3{0.0, 0.0, 1.0} : V3{1.0, 0.0, 0.0};
+    const V3 e1 = normalized(cross(ref, cc));
+    return {cc, e1, cross(cc, e1)};
+}
+
+// the subject: a prepared cell's nv vertices (v: its row of cell_xyz) into
+// buffer 0 of the ring; false when one is beyond the projection's reach
+template <int kCap>
+__device__ inline bool load_ring(const Tangent &T, const double *v, int nv,
+                                 double (&px)[2][kCap][kClipBlock],
+                                 double (&py)[2][kCap][kClipBlock], int lane)
+{
+    bool bad = false;
+    for (int k = 0; k < kMaxEdges; ++k) {
+        if (k < nv) {
+            double x, y, t;
+            T.project({v[3 * k], v[3 * k + 1], v[3 * k + 2]}, &x, &y, &t);
+            bad |= !(t >= kMinCos);
+            px[0][k][lane] = x;
+            py[0][k][lane] = y;
+        }
+    }
+    return !bad;
+}
+
+// One Sutherland-Hodgman pass: the n vertices of buffer cur against the
+// half-plane left of the edge from (ax, ay) along (dx, dy), into the other
+// buffer.  Returns the new count m; no slot at or past kCap is written, and
+// m > kCap is the caller's kErrClip.
+template <int kCap>
+__device__ inline int clip_edge(double (&px)[2][kCap][kClipBlock],
+                                double (&py)[2][kCap][kClipBlock], int lane,
+                                int cur, int n, double ax, double ay,
+                                double dx, double dy)
+{
+    const int nxt = cur ^ 1;
+    int m = 0;
+    double sx = px[cur][n - 1][lane], sy = py[cur][n - 1][lane];
+    double ss = dx * (sy - ay) - dy * (sx - ax);
+    for (int k = 0; k < n; ++k) {
+        const double ex = px[cur][k][lane], ey = py[cur][k][lane];
+        const double se = dx * (ey - ay) - dy * (ex - ax);
+        if ((se >= 0.0) != (ss >= 0.0)) {
+            if (m < kCap) {
+                const double t = ss / (ss - se);
+                px[nxt][m][lane] = sx + t * (ex - sx);
+                py[nxt][m][lane] = sy + t * (ey - sy);
+            }
+            ++m;
+        }
+        if (se >= 0.0) {
+            if (m < kCap) {
+                px[nxt][m][lane] = ex;
+                py[nxt][m][lane] = ey;
+            }
+            ++m;
+        }
+        sx = ex;
+        sy = ey;
+        ss = se;
+    }
+    return m;
+}
+
+// one lane per candidate pair mesh cell << 32 | lat-lon cell: the mesh cell's
+// polygon cut by the lat-lon cell's four edges, the area of the result from
+// its vertices lifted back to the sphere (a fan of tri_area)
 __global__ __launch_bounds__(kClipBlock) void clip_pairs(
     Geom G, bool swap, int64_t n_pairs, const uint64_t *__restrict__ keys,
     const double *__restrict__ cell_xyz, const int32_t *__restrict__ cell_nv,
     const double *__restrict__ cell_centre, double *__restrict__ area,
     int32_t *__restrict__ status)
 {
-    // the polygon being clipped, ping-pong: [buffer][vertex][lane]
     __shared__ double px[2][kMaxOut][kClipBlock];
     __shared__ double py[2][kMaxOut][kClipBlock];
     const int lane = threadIdx.x;
@@ -460,31 +676,16 @@ __global__ __launch_bounds__(kClipBlock) void clip_pairs(
         return;
     }
     const int nv = cell_nv[c];
-    const V3 cc = {cell_centre[c * 3], cell_centre[c * 3 + 1],
-                   cell_centre[c * 3 + 2]};
-    // tangent-plane basis at the centre
-    const V3 ref = fabs(cc.z) < 0.9 ? V3{0.0, 0.0, 1.0} : V3{1.0, 0.0, 0.0};
-    const V3 e1 = normalized(cross(ref, cc));
-    const V3 e2 = cross(cc, e1);
-    bool bad = false;
-    for (int k = 0; k < kMaxEdges; ++k) {
-        if (k < nv) {
-            const double *v = cell_xyz + (c * G.max_edges + k) * 3;
-            const V3 q = {v[0], v[1], v[2]};
-            const double t = dot(q, cc);
-            bad |= !(t >= kMinCos);
-            px[0][k][lane] = dot(q, e1) / t;
-            py[0][k][lane] = dot(q, e2) / t;
-        }
-    }
+    const Tangent T = tangent_at({cell_centre[c * 3], cell_centre[c * 3 + 1],
+                                  cell_centre[c * 3 + 2]});
+    bool bad = !load_ring(T, cell_xyz + c * G.max_edges * 3, nv, px, py, lane);
     const Quad quad = grid_cell(G.lat_c, G.lon_c, G.n_lon, g, swap);
     double qx[4], qy[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const double t = dot(quad.p[k], cc);
+        double t;
+        T.project(quad.p[k], &qx[k], &qy[k], &t);
         bad |= !(t >= kMinCos);
-        qx[k] = dot(quad.p[k], e1) / t;
-        qy[k] = dot(quad.p[k], e2) / t;
     }
     if (bad) {
         atomicOr(status, REMAP_OVERLAP_ERR_HEMISPHERE);
@@ -498,42 +699,17 @@ __global__ __launch_bounds__(kClipBlock) void clip_pairs(
         const double dx = qx[(e + 1) & 3] - ax, dy = qy[(e + 1) & 3] - ay;
         if (n == 0 || (dx == 0.0 && dy == 0.0))
             continue;    // (a repeated pole corner: no edge)
-        const int nxt = cur ^ 1;
-        int m = 0;
-        double sx = px[cur][n - 1][lane], sy = py[cur][n - 1][lane];
-        double ss = dx * (sy - ay) - dy * (sx - ax);
-        for (int k = 0; k < n; ++k) {
-            const double ex = px[cur][k][lane], ey = py[cur][k][lane];
-            const double se = dx * (ey - ay) - dy * (ex - ax);
-            if ((se >= 0.0) != (ss >= 0.0)) {
-                if (m < kMaxOut) {
-                    const double t = ss / (ss - se);
-                    px[nxt][m][lane] = sx + t * (ex - sx);
-                    py[nxt][m][lane] = sy + t * (ey - sy);
-                }
-                ++m;
-            }
-            if (se >= 0.0) {
-                if (m < kMaxOut) {
-                    px[nxt][m][lane] = ex;
-                    py[nxt][m][lane] = ey;
-                }
-                ++m;
-            }
-            sx = ex;
-            sy = ey;
-            ss = se;
-        }
-        if (m > kMaxOut) {
+        n = clip_edge(px, py, lane, cur, n, ax, ay, dx, dy);
+        if (n > kMaxOut) {
             atomicOr(status, kErrClip);
             area[p] = 0.0;
             return;
         }
-        n = m;
-        cur = nxt;
+        cur ^= 1;
     }
     double a = 0.0;
     if (n >= 3) {
+        const V3 cc = T.cc, e1 = T.e1, e2 = T.e2;
         auto lift = [&](int k) {
             const double x = px[cur][k][lane], y = py[cur][k][lane];
             return normalized(V3{cc.x + x * e1.x + y * e2.x,
@@ -627,49 +803,257 @@ __global__ __launch_bounds__(kBlock) void dst_sums(
     frac_b[d] = f < 1.0 ? f : 1.0;
 }
 
-struct Layout {
-    size_t xyz, nv, centre, boxes, counts, offs, keys, parea, head, slot,
-        keys_c, area_c, keys_s, n_kept, status, temp, total;
+// ---------------------------------------------------------------------------
+// what the four routes share on the host: the error bits as text, the
+// workspace of one side's prepared cells and of the pairs, and the back end
+// behind the clip (keep_pairs, the one read-back of the count, sort_and_sum)
+// ---------------------------------------------------------------------------
+
+// a route's entry point and its words for the error bits, in the order of
+// kErrBits (a side's text is cut at `room`, as snprintf always cut it)
+constexpr int kErrBits[6] = {REMAP_OVERLAP_ERR_EDGES, REMAP_OVERLAP_ERR_VERTEX,
+                             REMAP_OVERLAP_ERR_CONVEX,
+                             REMAP_OVERLAP_ERR_HEMISPHERE, kErrClip,
+                             REMAP_OVERLAP_ERR_CAPACITY};
+struct Route {
+    const char *who;
+    const char *side;    // what a side is called, before its name
+    size_t room;
+    bool name_convex;    // "(REMAP_OVERLAP_ERR_CONVEX)" behind everything
+    const char *bit[6];
+};
+
+const Route kLatlon = {
+    "remap_overlap_latlon", "", kErrorBufferSize, false,
+    {"a cell has more edges than this build serves "
+     "(REMAP_OVERLAP_MAX_EDGES); ",
+     "a cell has fewer than 3 distinct vertices or a vertex index out of "
+     "range; ",
+     "",
+     "a candidate pair has a vertex outside the tangent hemisphere of the "
+     "mesh cell's centre; ",
+     "a clipped polygon outgrew its REMAP_OVERLAP_MAX_EDGES + 4 vertices "
+     "(mesh vertices on a lat-lon edge); ",
+     "more candidate pairs than n_pairs (a stale "
+     "remap_overlap_latlon_sizes)"}};
+
+const Route kMeshes = {
+    "remap_overlap_meshes", "mesh ", 192, false,
+    {"a cell has more edges than this build serves "
+     "(REMAP_OVERLAP_MAX_EDGES); ",
+     "a cell has fewer than 3 distinct vertices or a vertex index out of "
+     "range; ",
+     "a cell is not convex (mesh b's cells clip); ",
+     "a candidate pair has a vertex outside the tangent hemisphere of the "
+     "mesh a cell's centre; ",
+     "a clipped polygon outgrew its 2 x REMAP_OVERLAP_MAX_EDGES vertices; ",
+     "the candidate pairs differ from n_pairs (a stale "
+     "remap_overlap_meshes_sizes); "}};
+
+// (the pieces are meshes; remap_overlap_pieces names the convexity bit)
+const Route kPieces = {"remap_overlap_pieces", kMeshes.side, kMeshes.room, true,
+                       {kMeshes.bit[0], kMeshes.bit[1], kMeshes.bit[2],
+                        kMeshes.bit[3], kMeshes.bit[4], kMeshes.bit[5]}};
+
+const Route kGrids = {
+    "remap_overlap_grids", "side ", 256, false,
+    {"a cell has more edges than this build serves "
+     "(REMAP_OVERLAP_ERR_EDGES); ",
+     "a cell has fewer than 3 distinct corners or a vertex index out of "
+     "range (REMAP_OVERLAP_ERR_VERTEX); ",
+     "a cell is not convex and side b's cells clip "
+     "(REMAP_OVERLAP_ERR_CONVEX); ",
+     "a candidate pair has a vertex outside the tangent hemisphere of the "
+     "side a cell's centre (REMAP_OVERLAP_ERR_HEMISPHERE); ",
+     "a clipped polygon outgrew its 2 x REMAP_OVERLAP_MAX_EDGES vertices; ",
+     "the candidate pairs differ from n_pairs, a stale "
+     "remap_overlap_grids_sizes (REMAP_OVERLAP_ERR_CAPACITY); "}};
+
+// the error bits of one side, or of the pairs (name NULL), as text
+void describe(const Route &R, const char *name, int err, char *out)
+{
+    out[0] = '\0';
+    if (!err)
+        return;
+    size_t n = name ? snprintf(out, R.room, "%s%s: ", R.side, name) : 0;
+    for (int k = 0; k < 6 && n < R.room; ++k)
+        if (err & kErrBits[k])
+            n += snprintf(out + n, R.room - n, "%s", R.bit[k]);
+}
+
+int route_fail(const Route &R, int err_a, int err_b, int err_p)
+{
+    char text[3][kErrorBufferSize];
+    describe(R, "a", err_a, text[0]);
+    describe(R, "b", err_b, text[1]);
+    describe(R, nullptr, err_p, text[2]);
+    return fail(REMAP_ERR_UNSUPPORTED, "%s: %s%s%s%s", R.who, text[0], text[1],
+                text[2],
+                R.name_convex && ((err_a | err_b) & REMAP_OVERLAP_ERR_CONVEX)
+                    ? "(REMAP_OVERLAP_ERR_CONVEX)"
+                    : "");
+}
+
+// what every run writes (dst / src / area may be NULL with no pairs)
+struct Outputs {
+    int32_t *dst, *src;
+    double *area, *frac_b, *a_area, *b_area;
+    int64_t *n_entries;
+};
+
+int check_call(const char *who, int64_t n_pairs, const Outputs &out)
+{
+    if (n_pairs < 0 || n_pairs >= (int64_t(1) << 32) - 1)
+        return fail(REMAP_ERR_UNSUPPORTED, "%s: %lld candidate pairs", who,
+                    static_cast<long long>(n_pairs));
+    if (!out.frac_b || !out.a_area || !out.b_area || !out.n_entries ||
+        (n_pairs > 0 && (!out.dst || !out.src || !out.area)))
+        return fail(REMAP_ERR_ARG, "%s: NULL output", who);
+    return REMAP_OK;
+}
+
+size_t take(size_t *off, size_t bytes)
+{
+    const size_t at = *off;
+    *off += align_up(bytes);
+    return at;
+}
+
+// one side's prepared cells in the workspace (radius: the mesh and grid
+// routes' cell_shape; the lat-lon route takes none)
+struct SideLayout {
+    size_t xyz, nv, centre, radius, boxes, counts, offs;
+};
+
+SideLayout side_layout(const Geom &G, bool radius, size_t *off)
+{
+    const size_t c = at_least_one(G.n_cells);
+    SideLayout s;
+    s.xyz = take(off, c * G.max_edges * 3 * 8);
+    s.nv = take(off, c * 4);
+    s.centre = take(off, c * 3 * 8);
+    s.radius = radius ? take(off, c * 8) : 0;
+    s.boxes = take(off, c * sizeof(Box));
+    s.counts = take(off, c * 8);
+    s.offs = take(off, c * 8);
+    return s;
+}
+
+struct Side {
+    double *xyz, *centre, *radius;
+    int32_t *nv;
+    Box *boxes;
+    uint64_t *counts, *offs;
+};
+
+Side side_at(char *ws, const SideLayout &s)
+{
+    return {at<double>(ws, s.xyz), at<double>(ws, s.centre),
+            at<double>(ws, s.radius), at<int32_t>(ws, s.nv),
+            at<Box>(ws, s.boxes), at<uint64_t>(ws, s.counts),
+            at<uint64_t>(ws, s.offs)};
+}
+
+// the buffers of the pairs (n_pairs each) from the clip on
+struct PairLayout {
+    size_t cand, cand_s, parea, area_c, head, slot;
+};
+
+PairLayout pair_layout(size_t n, size_t *off)
+{
+    PairLayout p;
+    // candidates (the mesh routes: then the unique pairs); then the sorted
+    // entry keys
+    p.cand = take(off, n * 8);
+    // (the mesh route: sorted candidates;) the kept entries' keys
+    p.cand_s = take(off, n * 8);
+    p.parea = take(off, n * 8);
+    p.area_c = take(off, n * 8);
+    p.head = take(off, n * 4);
+    p.slot = take(off, n * 4);
+    return p;
+}
+
+struct PairWork {
+    uint64_t *cand, *cand_s;   // the pairs a << 32 | b; the kept entries' keys
+    double *parea, *area_c;
+    uint32_t *head, *slot;
+    uint64_t *n_unique;        // (the lat-lon route has none)
+    int64_t *n_kept;           // the error bits of the pairs in the word behind
+    int32_t *status;
+    void *temp;
     size_t temp_bytes;
 };
 
-int make_layout(int64_t n_cells, int32_t max_edges, int64_t n_pairs,
-                Layout *lay)
+PairWork pair_work(char *ws, const PairLayout &p, int64_t *counts, void *temp,
+                   size_t temp_bytes)
 {
-    const size_t c = static_cast<size_t>(n_cells > 0 ? n_cells : 1);
-    const size_t n = static_cast<size_t>(n_pairs > 0 ? n_pairs : 1);
+    // counts: [0] unique pairs, [1] entries, [2] the pairs' error bits
+    return {at<uint64_t>(ws, p.cand), at<uint64_t>(ws, p.cand_s),
+            at<double>(ws, p.parea), at<double>(ws, p.area_c),
+            at<uint32_t>(ws, p.head), at<uint32_t>(ws, p.slot),
+            as<uint64_t>(counts), counts + 1,
+            as<int32_t>(counts + 2), temp, temp_bytes};
+}
+
+// flag / scan / scatter over the clipped pairs in w.cand / w.parea: the
+// entries with A > kSliver * A_dst re-keyed (dst, src) in w.cand_s /
+// w.area_c, their number in *w.n_kept
+int keep_pairs(int64_t n_pairs, int64_t n_a, int64_t n_b, bool dst_is_a,
+               const PairWork &w, const double *a_area, const double *b_area,
+               hipStream_t stream)
+{
+    REMAP_TRY(launch(flag_kept, n_pairs, kBlock, stream, n_pairs, n_a, n_b,
+                     dst_is_a, w.cand, w.parea, a_area, b_area, w.head));
+    if (n_pairs > 0)
+        REMAP_TRY(exclusive_scan(w.temp, w.temp_bytes, w.head, w.slot, n_pairs,
+                                 stream));
+    return launch(scatter_kept, n_pairs, kBlock, stream, n_pairs, dst_is_a,
+                  w.cand, w.parea, w.head, w.slot, w.cand_s, w.area_c,
+                  w.n_kept);
+}
+
+// the kept entries sorted by (dst, src) into the outputs, frac_b of every
+// destination cell (w.cand is the sort's key output)
+int sort_and_sum(int64_t n_dst, int64_t n_entries, int64_t n_pairs,
+                 const PairWork &w, const Outputs &out, const double *dst_area,
+                 hipStream_t stream)
+{
+    if (n_entries > 0)
+        REMAP_TRY(radix_sort_pairs(w.temp, w.temp_bytes, w.cand_s, w.cand,
+                                   w.area_c, out.area, n_entries, stream));
+    REMAP_TRY(launch(split_keys, n_entries, kBlock, stream, w.n_kept, n_pairs,
+                     w.cand, out.dst, out.src));
+    return launch(dst_sums, n_dst, kBlock, stream, n_dst, w.n_kept, out.dst,
+                  out.area, dst_area, out.frac_b);
+}
+
+// ---------------------------------------------------------------------------
+// an MPAS mesh and a lat-lon grid (remap_overlap_latlon): the mesh is side a
+// ---------------------------------------------------------------------------
+
+struct Layout {
+    SideLayout cells;
+    PairLayout pairs;
+    // the entry count and the error bits side by side (behind a word that is
+    // not used: pair_work's n_unique): one read-back
+    size_t counts, temp, total;
+    size_t temp_bytes;
+};
+
+int make_layout(const Geom &G, int64_t n_pairs, Layout *lay)
+{
+    const size_t c = at_least_one(G.n_cells), n = at_least_one(n_pairs);
     size_t scan_c = 0, scan_n = 0, sort_n = 0;
-    REMAP_HIP_CHECK((rocprim::exclusive_scan(
-        nullptr, scan_c, static_cast<const uint64_t *>(nullptr),
-        static_cast<uint64_t *>(nullptr), uint64_t(0), c,
-        rocprim::plus<uint64_t>())));
-    REMAP_HIP_CHECK((rocprim::exclusive_scan(
-        nullptr, scan_n, static_cast<const uint32_t *>(nullptr),
-        static_cast<uint32_t *>(nullptr), 0u, n, rocprim::plus<uint32_t>())));
-    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-        nullptr, sort_n, static_cast<const uint64_t *>(nullptr),
-        static_cast<uint64_t *>(nullptr), static_cast<const double *>(nullptr),
-        static_cast<double *>(nullptr), n, 0u, 64u)));
-    size_t t = scan_c > scan_n ? scan_c : scan_n;
-    lay->temp_bytes = t > sort_n ? t : sort_n;
+    REMAP_TRY(scan_temp<uint64_t>(c, &scan_c));
+    REMAP_TRY(scan_temp<uint32_t>(n, &scan_n));
+    REMAP_TRY(sort_pairs_temp<double>(n, &sort_n));
+    lay->temp_bytes = std::max({scan_c, scan_n, sort_n});
     size_t off = 0;
-    lay->xyz = off;    off += align_up(c * max_edges * 3 * 8);
-    lay->nv = off;     off += align_up(c * 4);
-    lay->centre = off; off += align_up(c * 3 * 8);
-    lay->boxes = off;  off += align_up(c * sizeof(Box));
-    lay->counts = off; off += align_up(c * 8);
-    lay->offs = off;   off += align_up(c * 8);
-    lay->keys = off;   off += align_up(n * 8);
-    lay->parea = off;  off += align_up(n * 8);
-    lay->head = off;   off += align_up(n * 4);
-    lay->slot = off;   off += align_up(n * 4);
-    lay->keys_c = off; off += align_up(n * 8);
-    lay->area_c = off; off += align_up(n * 8);
-    lay->keys_s = off; off += align_up(n * 8);
-    // the entry count and the error bits side by side: one read-back
-    lay->n_kept = off; off += align_up(16);
-    lay->status = lay->n_kept + 8;
-    lay->temp = off;   off += align_up(lay->temp_bytes);
+    lay->cells = side_layout(G, false, &off);
+    lay->pairs = pair_layout(n, &off);
+    lay->counts = take(&off, 24);
+    lay->temp = take(&off, lay->temp_bytes);
     lay->total = off;
     return REMAP_OK;
 }
@@ -713,37 +1097,27 @@ int axis_swap(const Geom &G, hipStream_t stream, bool *swap)
                                    hipMemcpyDeviceToHost, stream));
     REMAP_HIP_CHECK(hipMemcpyAsync(&ends[2], G.lon_c, 8, hipMemcpyDeviceToHost,
                                    stream));
-    REMAP_HIP_CHECK(hipMemcpyAsync(&ends[3], G.lon_c + G.n_lon, 8,
-                                   hipMemcpyDeviceToHost, stream));
-    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+    REMAP_TRY(read_back(&ends[3], G.lon_c + G.n_lon, 8, stream));
     *swap = (ends[1] < ends[0]) != (ends[3] < ends[2]);
     return REMAP_OK;
 }
-
-uint32_t blocks(int64_t n, int per) { return static_cast<uint32_t>((n + per - 1) / per); }
 
 int overlap_sizes(const remap_overlap_geom *geom, int64_t *counter,
                   int64_t *n_pairs_out, size_t *bytes_out, hipStream_t stream)
 {
     Geom G;
-    int rc = check_geom(geom, &G);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(check_geom(geom, &G));
     if (!counter || !n_pairs_out || !bytes_out)
         return fail(REMAP_ERR_ARG, "remap_overlap_latlon_sizes: NULL output");
     REMAP_HIP_CHECK(hipMemsetAsync(counter, 0, 2 * sizeof(int64_t), stream));
-    if (G.n_cells > 0) {
-        hipLaunchKernelGGL(cell_prep, dim3(blocks(G.n_cells, kPrepBlock)),
-                           dim3(kPrepBlock), 0, stream, G, nullptr, nullptr,
-                           nullptr, nullptr, nullptr, nullptr,
-                           reinterpret_cast<unsigned long long *>(counter),
-                           reinterpret_cast<int32_t *>(counter + 1));
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
+    // (count only: the total in counter[0], the error bits in counter[1])
+    REMAP_TRY(launch(cell_prep, G.n_cells, kPrepBlock, stream, G, nullptr,
+                     nullptr, nullptr, nullptr, nullptr, nullptr,
+                     as<unsigned long long>(counter),
+                     as<int32_t>(counter + 1)));
     int64_t got[2];
-    REMAP_HIP_CHECK(hipMemcpyAsync(got, counter, sizeof(got),
-                                   hipMemcpyDeviceToHost, stream));
-    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+    REMAP_TRY(read_back(got, counter, sizeof(got), stream));
+    // (its own punctuation, not kLatlon's)
     if (int err = static_cast<int>(got[1] & 0xffffffff))
         return fail(REMAP_ERR_UNSUPPORTED,
                     "remap_overlap_latlon: %s%s",
@@ -756,9 +1130,7 @@ int overlap_sizes(const remap_overlap_geom *geom, int64_t *counter,
                           "vertex index out of range"
                         : "");
     Layout lay;
-    rc = make_layout(G.n_cells, G.max_edges, got[0], &lay);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(make_layout(G, got[0], &lay));
     *n_pairs_out = got[0];
     *bytes_out = lay.total;
     return REMAP_OK;
@@ -766,141 +1138,48 @@ int overlap_sizes(const remap_overlap_geom *geom, int64_t *counter,
 
 int overlap(const remap_overlap_geom *geom, int32_t dst_is_mesh,
             int64_t n_pairs, void *workspace, size_t workspace_bytes,
-            int32_t *dst_out, int32_t *src_out, double *area_out,
-            double *frac_b_out, double *mesh_area_out, double *grid_area_out,
-            int64_t *n_entries_out, hipStream_t stream)
+            const Outputs &out, hipStream_t stream)
 {
     Geom G;
-    int rc = check_geom(geom, &G);
-    if (rc != REMAP_OK)
-        return rc;
-    if (n_pairs < 0 || n_pairs >= (int64_t(1) << 32) - 1)
-        return fail(REMAP_ERR_UNSUPPORTED,
-                    "remap_overlap_latlon: %lld candidate pairs",
-                    static_cast<long long>(n_pairs));
-    if (!frac_b_out || !mesh_area_out || !grid_area_out || !n_entries_out ||
-        (n_pairs > 0 && (!dst_out || !src_out || !area_out)))
-        return fail(REMAP_ERR_ARG, "remap_overlap_latlon: NULL output");
+    REMAP_TRY(check_geom(geom, &G));
+    REMAP_TRY(check_call(kLatlon.who, n_pairs, out));
     Layout lay;
-    rc = make_layout(G.n_cells, G.max_edges, n_pairs, &lay);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(make_layout(G, n_pairs, &lay));
     if (!workspace || workspace_bytes < lay.total)
         return fail(REMAP_ERR_WORKSPACE,
                     "remap_overlap_latlon: workspace of %zu bytes, need %zu",
                     workspace_bytes, lay.total);
     bool swap = false;
-    rc = axis_swap(G, stream, &swap);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(axis_swap(G, stream, &swap));
     char *ws = static_cast<char *>(workspace);
-    double *cell_xyz = reinterpret_cast<double *>(ws + lay.xyz);
-    int32_t *cell_nv = reinterpret_cast<int32_t *>(ws + lay.nv);
-    double *centre = reinterpret_cast<double *>(ws + lay.centre);
-    Box *boxes = reinterpret_cast<Box *>(ws + lay.boxes);
-    uint64_t *counts = reinterpret_cast<uint64_t *>(ws + lay.counts);
-    uint64_t *offs = reinterpret_cast<uint64_t *>(ws + lay.offs);
-    uint64_t *keys = reinterpret_cast<uint64_t *>(ws + lay.keys);
-    double *parea = reinterpret_cast<double *>(ws + lay.parea);
-    uint32_t *head = reinterpret_cast<uint32_t *>(ws + lay.head);
-    uint32_t *slot = reinterpret_cast<uint32_t *>(ws + lay.slot);
-    uint64_t *keys_c = reinterpret_cast<uint64_t *>(ws + lay.keys_c);
-    double *area_c = reinterpret_cast<double *>(ws + lay.area_c);
-    uint64_t *keys_s = reinterpret_cast<uint64_t *>(ws + lay.keys_s);
-    int64_t *n_kept = reinterpret_cast<int64_t *>(ws + lay.n_kept);
-    int32_t *status = reinterpret_cast<int32_t *>(ws + lay.status);
-    void *temp = ws + lay.temp;
+    const Side s = side_at(ws, lay.cells);
+    int64_t *counts = at<int64_t>(ws, lay.counts);
+    const PairWork w = pair_work(ws, lay.pairs, counts, ws + lay.temp,
+                                 lay.temp_bytes);
     const int64_t n_grid = G.n_lat * G.n_lon;
-    const int64_t n_dst = dst_is_mesh ? G.n_cells : n_grid;
-    double *dst_area = dst_is_mesh ? mesh_area_out : grid_area_out;
 
-    REMAP_HIP_CHECK(hipMemsetAsync(n_kept, 0, 16, stream));
-    hipLaunchKernelGGL(grid_area, dim3(blocks(n_grid, kBlock)), dim3(kBlock),
-                       0, stream, G, swap, grid_area_out);
-    REMAP_HIP_CHECK(hipGetLastError());
-    if (G.n_cells > 0) {
-        hipLaunchKernelGGL(cell_prep, dim3(blocks(G.n_cells, kPrepBlock)),
-                           dim3(kPrepBlock), 0, stream, G, cell_xyz, cell_nv,
-                           centre, mesh_area_out, boxes, counts, nullptr,
-                           status);
-        REMAP_HIP_CHECK(hipGetLastError());
-        size_t tb = lay.temp_bytes;
-        REMAP_HIP_CHECK((rocprim::exclusive_scan(
-            temp, tb, static_cast<const uint64_t *>(counts), offs,
-            uint64_t(0), static_cast<size_t>(G.n_cells),
-            rocprim::plus<uint64_t>(), stream)));
-        hipLaunchKernelGGL(fill_pairs<false>, dim3(blocks(G.n_cells, kBlock)),
-                           dim3(kBlock), 0, stream, G, boxes, offs, n_pairs,
-                           keys, status);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
-    if (n_pairs > 0) {
-        hipLaunchKernelGGL(clip_pairs, dim3(blocks(n_pairs, kClipBlock)),
-                           dim3(kClipBlock), 0, stream, G, swap, n_pairs, keys,
-                           cell_xyz, cell_nv, centre, parea, status);
-        REMAP_HIP_CHECK(hipGetLastError());
-        const uint32_t nb = blocks(n_pairs, kBlock);
-        hipLaunchKernelGGL(flag_kept, dim3(nb), dim3(kBlock), 0, stream,
-                           n_pairs, G.n_cells, n_grid, dst_is_mesh != 0, keys,
-                           parea, mesh_area_out, grid_area_out, head);
-        REMAP_HIP_CHECK(hipGetLastError());
-        size_t tb = lay.temp_bytes;
-        REMAP_HIP_CHECK((rocprim::exclusive_scan(
-            temp, tb, static_cast<const uint32_t *>(head), slot, 0u,
-            static_cast<size_t>(n_pairs), rocprim::plus<uint32_t>(), stream)));
-        hipLaunchKernelGGL(scatter_kept, dim3(nb), dim3(kBlock), 0, stream,
-                           n_pairs, dst_is_mesh != 0, keys, parea, head, slot,
-                           keys_c, area_c, n_kept);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
-    // the one read-back: how many entries to sort
+    REMAP_HIP_CHECK(hipMemsetAsync(counts, 0, 24, stream));
+    REMAP_TRY(launch(grid_area, n_grid, kBlock, stream, G, swap, out.b_area));
+    REMAP_TRY(launch(cell_prep, G.n_cells, kPrepBlock, stream, G, s.xyz, s.nv,
+                     s.centre, out.a_area, s.boxes, s.counts, nullptr,
+                     w.status));
+    if (G.n_cells > 0)
+        REMAP_TRY(exclusive_scan(w.temp, w.temp_bytes, s.counts, s.offs,
+                                 G.n_cells, stream));
+    REMAP_TRY(launch(fill_pairs<false>, G.n_cells, kBlock, stream, G, s.boxes,
+                     s.offs, n_pairs, w.cand, w.status));
+    REMAP_TRY(launch(clip_pairs, n_pairs, kClipBlock, stream, G, swap, n_pairs,
+                     w.cand, s.xyz, s.nv, s.centre, w.parea, w.status));
+    REMAP_TRY(keep_pairs(n_pairs, G.n_cells, n_grid, dst_is_mesh != 0, w,
+                         out.a_area, out.b_area, stream));
+    // the one read-back: how many entries to sort, the error bits
     int64_t back[2];
-    REMAP_HIP_CHECK(hipMemcpyAsync(back, n_kept, 16, hipMemcpyDeviceToHost,
-                                   stream));
-    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
-    const int64_t n_entries = back[0];
-    const int err = static_cast<int>(back[1] & 0xffffffff);
-    if (err)
-        return fail(REMAP_ERR_UNSUPPORTED, "remap_overlap_latlon: %s%s%s%s%s",
-                    (err & REMAP_OVERLAP_ERR_EDGES)
-                        ? "a cell has more edges than this build serves "
-                          "(REMAP_OVERLAP_MAX_EDGES); "
-                        : "",
-                    (err & REMAP_OVERLAP_ERR_VERTEX)
-                        ? "a cell has fewer than 3 distinct vertices or a "
-                          "vertex index out of range; "
-                        : "",
-                    (err & REMAP_OVERLAP_ERR_HEMISPHERE)
-                        ? "a candidate pair has a vertex outside the "
-                          "tangent hemisphere of the mesh cell's centre; "
-                        : "",
-                    (err & kErrClip)
-                        ? "a clipped polygon outgrew its REMAP_OVERLAP_MAX_EDGES "
-                          "+ 4 vertices (mesh vertices on a lat-lon edge); "
-                        : "",
-                    (err & REMAP_OVERLAP_ERR_CAPACITY)
-                        ? "more candidate pairs than n_pairs (a stale "
-                          "remap_overlap_latlon_sizes)"
-                        : "");
-    *n_entries_out = n_entries;
-    if (n_entries > 0) {
-        size_t tb = lay.temp_bytes;
-        REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-            temp, tb, static_cast<const uint64_t *>(keys_c), keys_s,
-            static_cast<const double *>(area_c), area_out,
-            static_cast<size_t>(n_entries), 0u, 64u, stream)));
-        hipLaunchKernelGGL(split_keys, dim3(blocks(n_entries, kBlock)),
-                           dim3(kBlock), 0, stream, n_kept, n_pairs, keys_s,
-                           dst_out, src_out);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
-    if (n_dst > 0) {
-        hipLaunchKernelGGL(dst_sums, dim3(blocks(n_dst, kBlock)), dim3(kBlock),
-                           0, stream, n_dst, n_kept, dst_out, area_out,
-                           dst_area, frac_b_out);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
-    return REMAP_OK;
+    REMAP_TRY(read_back(back, w.n_kept, 16, stream));
+    if (const int err = static_cast<int>(back[1] & 0xffffffff))
+        return route_fail(kLatlon, 0, 0, err);
+    *out.n_entries = back[0];
+    return sort_and_sum(dst_is_mesh ? G.n_cells : n_grid, back[0], n_pairs, w,
+                        out, dst_is_mesh ? out.a_area : out.b_area, stream);
 }
 
 
@@ -922,8 +1201,8 @@ int overlap(const remap_overlap_geom *geom, int32_t dst_is_mesh,
 //                  bucket the two boxes share)
 //   clip_pairs_poly  one lane per unique pair: a's polygon by b's edges in
 //                  the gnomonic plane of a's centre
-//   flag / scan / scatter, radix sort, dst_sums as above, a in the "mesh"
-//   and b in the "grid" half of the keys (dst_is_b only re-keys)
+//   keep_pairs, the read-back of the count, sort_and_sum as above
+//   (dst_is_b only re-keys)
 // ---------------------------------------------------------------------------
 
 // one clip by an edge of a convex clipper adds at most one vertex
@@ -1122,7 +1401,7 @@ __global__ __launch_bounds__(kBlock) void expand_pairs(
 }
 
 // one lane per unique candidate pair a << 32 | b: the area of a's polygon
-// clipped by b's (convex) in the gnomonic plane of a's centre; lanes past
+// cut by b's edges (b convex) in the tangent plane of a's centre; lanes past
 // the unique count (their keys ~0) write 0
 __global__ __launch_bounds__(kClipBlock) void clip_pairs_poly(
     int64_t n_a, int32_t max_edges_a, int64_t n_b, int32_t max_edges_b,
@@ -1134,7 +1413,6 @@ __global__ __launch_bounds__(kClipBlock) void clip_pairs_poly(
     const double *__restrict__ radius_b, double *__restrict__ area,
     int32_t *__restrict__ status)
 {
-    // the polygon being clipped, ping-pong: [buffer][vertex][lane]
     __shared__ double px[2][kMaxOutPoly][kClipBlock];
     __shared__ double py[2][kMaxOutPoly][kClipBlock];
     const int lane = threadIdx.x;
@@ -1163,81 +1441,34 @@ __global__ __launch_bounds__(kClipBlock) void clip_pairs_poly(
         area[p] = 0.0;
         return;
     }
-    // tangent-plane basis at a's centre
-    const V3 ref = fabs(ca.z) < 0.9 ? V3{0.0, 0.0, 1.0} : V3{1.0, 0.0, 0.0};
-    const V3 e1 = normalized(cross(ref, ca));
-    const V3 e2 = cross(ca, e1);
+    const Tangent T = tangent_at(ca);
     const int na = nv_a[a], nb = nv_b[b];
-    const double *vb = xyz_b + b * max_edges_b * 3;
-    bool bad = false;
-    for (int k = 0; k < kMaxEdges; ++k) {
-        if (k < na) {
-            const double *v = xyz_a + (a * max_edges_a + k) * 3;
-            const V3 q = {v[0], v[1], v[2]};
-            const double t = dot(q, ca);
-            bad |= !(t >= kMinCos);
-            px[0][k][lane] = dot(q, e1) / t;
-            py[0][k][lane] = dot(q, e2) / t;
-        }
-    }
-    for (int k = 0; k < nb; ++k) {
-        const V3 q = {vb[3 * k], vb[3 * k + 1], vb[3 * k + 2]};
-        bad |= !(dot(q, ca) >= kMinCos);
-    }
+    const CellRing vb = {xyz_b + b * max_edges_b * 3};
+    bool bad = !load_ring(T, xyz_a + a * max_edges_a * 3, na, px, py, lane);
+    for (int k = 0; k < nb; ++k)
+        bad |= !(dot(vb[k], ca) >= kMinCos);
     if (bad) {
         atomicOr(status, REMAP_OVERLAP_ERR_HEMISPHERE);
         area[p] = 0.0;
         return;
     }
-    auto project = [&](int k, double *x, double *y) {
-        const V3 q = {vb[3 * k], vb[3 * k + 1], vb[3 * k + 2]};
-        const double t = dot(q, ca);
-        *x = dot(q, e1) / t;
-        *y = dot(q, e2) / t;
-    };
-    double fx, fy;
-    project(0, &fx, &fy);
+    double fx, fy, t;
+    T.project(vb[0], &fx, &fy, &t);
     double ax = fx, ay = fy;
     int n = na, cur = 0;
     for (int e = 0; e < nb && n > 0; ++e) {
         double bx = fx, by = fy;
         if (e + 1 < nb)
-            project(e + 1, &bx, &by);
+            T.project(vb[e + 1], &bx, &by, &t);
         const double dx = bx - ax, dy = by - ay;
         if (dx != 0.0 || dy != 0.0) {
-            const int nxt = cur ^ 1;
-            int m = 0;
-            double sx = px[cur][n - 1][lane], sy = py[cur][n - 1][lane];
-            double ss = dx * (sy - ay) - dy * (sx - ax);
-            for (int k = 0; k < n; ++k) {
-                const double ex = px[cur][k][lane], ey = py[cur][k][lane];
-                const double se = dx * (ey - ay) - dy * (ex - ax);
-                if ((se >= 0.0) != (ss >= 0.0)) {
-                    if (m < kMaxOutPoly) {
-                        const double t = ss / (ss - se);
-                        px[nxt][m][lane] = sx + t * (ex - sx);
-                        py[nxt][m][lane] = sy + t * (ey - sy);
-                    }
-                    ++m;
-                }
-                if (se >= 0.0) {
-                    if (m < kMaxOutPoly) {
-                        px[nxt][m][lane] = ex;
-                        py[nxt][m][lane] = ey;
-                    }
-                    ++m;
-                }
-                sx = ex;
-                sy = ey;
-                ss = se;
-            }
-            if (m > kMaxOutPoly) {
+            n = clip_edge(px, py, lane, cur, n, ax, ay, dx, dy);
+            if (n > kMaxOutPoly) {
                 atomicOr(status, kErrClip);
                 area[p] = 0.0;
                 return;
             }
-            n = m;
-            cur = nxt;
+            cur ^= 1;
         }
         ax = bx;
         ay = by;
@@ -1306,68 +1537,15 @@ void bucket_raster(int64_t n_b, Geom *A, Geom *B)
     A->n_lon = B->n_lon = 2 * n_lat;
 }
 
-// the error bits of one mesh, or of the pairs (name NULL), as text
-void describe(const char *name, int err, char *out, size_t size)
-{
-    out[0] = '\0';
-    if (!err)
-        return;
-    snprintf(out, size, "%s%s%s%s%s%s%s%s", name ? "mesh " : "",
-             name ? name : "", name ? ": " : "",
-             (err & REMAP_OVERLAP_ERR_EDGES)
-                 ? "a cell has more edges than this build serves "
-                   "(REMAP_OVERLAP_MAX_EDGES); "
-                 : "",
-             (err & REMAP_OVERLAP_ERR_VERTEX)
-                 ? "a cell has fewer than 3 distinct vertices or a vertex "
-                   "index out of range; "
-                 : "",
-             (err & REMAP_OVERLAP_ERR_CONVEX)
-                 ? "a cell is not convex (mesh b's cells clip); "
-                 : "",
-             (err & REMAP_OVERLAP_ERR_HEMISPHERE)
-                 ? "a candidate pair has a vertex outside the tangent "
-                   "hemisphere of the mesh a cell's centre; "
-                 : "",
-             (err & kErrClip)
-                 ? "a clipped polygon outgrew its 2 x REMAP_OVERLAP_MAX_EDGES "
-                   "vertices; "
-                 : "");
-    if (err & REMAP_OVERLAP_ERR_CAPACITY) {
-        const size_t n = strlen(out);
-        snprintf(out + n, size - n, "the candidate pairs differ from n_pairs "
-                                    "(a stale remap_overlap_meshes_sizes); ");
-    }
-}
-
-int meshes_fail(const char *who, int err_a, int err_b, int err_p)
-{
-    char text[3][192];
-    describe("a", err_a, text[0], sizeof(text[0]));
-    describe("b", err_b, text[1], sizeof(text[1]));
-    describe(nullptr, err_p, text[2], sizeof(text[2]));
-    // (remap_overlap_pieces names the bit as well)
-    const bool pieces = strcmp(who, "remap_overlap_meshes") != 0;
-    return fail(REMAP_ERR_UNSUPPORTED, "%s: %s%s%s%s", who, text[0], text[1],
-                text[2],
-                pieces && ((err_a | err_b) & REMAP_OVERLAP_ERR_CONVEX)
-                    ? "(REMAP_OVERLAP_ERR_CONVEX)"
-                    : "");
-}
-
-// one mesh's prepared cells in the workspace
-struct SideLayout {
-    size_t xyz, nv, centre, radius, boxes, counts, offs;
-};
-
 struct MeshLayout {
     // known from the sizes of the meshes
     size_t lat_c, lon_c, start, back, temp0, fixed;
     SideLayout a, b;
     size_t temp0_bytes;
     // known from the bucket key counts (the first read-back)
-    size_t bkeys, bkeys_s, akeys, pcnt, poff, cand, cand_s, parea, area_c,
-        head, slot, temp, total;
+    size_t bkeys, bkeys_s, akeys, pcnt, poff;
+    PairLayout pairs;
+    size_t temp, total;
     size_t temp_bytes;
 };
 
@@ -1376,45 +1554,18 @@ struct MeshLayout {
 // pairs' error bits
 constexpr int kBackWords = 6;
 
-size_t take(size_t *off, size_t bytes)
-{
-    const size_t at = *off;
-    *off += align_up(bytes);
-    return at;
-}
-
-SideLayout side_layout(const Geom &G, size_t *off)
-{
-    const size_t c = static_cast<size_t>(G.n_cells > 0 ? G.n_cells : 1);
-    SideLayout s;
-    s.xyz = take(off, c * G.max_edges * 3 * 8);
-    s.nv = take(off, c * 4);
-    s.centre = take(off, c * 3 * 8);
-    s.radius = take(off, c * 8);
-    s.boxes = take(off, c * sizeof(Box));
-    s.counts = take(off, c * 8);
-    s.offs = take(off, c * 8);
-    return s;
-}
-
 int mesh_fixed_layout(const Geom &A, const Geom &B, MeshLayout *L)
 {
-    const size_t nc = static_cast<size_t>(
-        (A.n_cells > B.n_cells ? A.n_cells : B.n_cells) > 0
-            ? (A.n_cells > B.n_cells ? A.n_cells : B.n_cells)
-            : 1);
-    REMAP_HIP_CHECK((rocprim::exclusive_scan(
-        nullptr, L->temp0_bytes, static_cast<const uint64_t *>(nullptr),
-        static_cast<uint64_t *>(nullptr), uint64_t(0), nc,
-        rocprim::plus<uint64_t>())));
+    REMAP_TRY(scan_temp<uint64_t>(
+        at_least_one(std::max(A.n_cells, B.n_cells)), &L->temp0_bytes));
     const size_t n_buckets = static_cast<size_t>(A.n_lat * A.n_lon);
     size_t off = 0;
     L->lat_c = take(&off, (A.n_lat + 1) * 8);
     L->lon_c = take(&off, (A.n_lon + 1) * 8);
     L->start = take(&off, (n_buckets + 1) * 4);
     L->back = take(&off, kBackWords * 8);
-    L->a = side_layout(A, &off);
-    L->b = side_layout(B, &off);
+    L->a = side_layout(A, true, &off);
+    L->b = side_layout(B, true, &off);
     L->temp0 = take(&off, L->temp0_bytes);
     L->fixed = off;
     return REMAP_OK;
@@ -1423,137 +1574,84 @@ int mesh_fixed_layout(const Geom &A, const Geom &B, MeshLayout *L)
 int mesh_var_layout(int64_t n_akeys, int64_t n_bkeys, int64_t n_pairs,
                     MeshLayout *L)
 {
-    const size_t na = static_cast<size_t>(n_akeys > 0 ? n_akeys : 1);
-    const size_t nb = static_cast<size_t>(n_bkeys > 0 ? n_bkeys : 1);
-    const size_t n = static_cast<size_t>(n_pairs > 0 ? n_pairs : 1);
+    const size_t na = at_least_one(n_akeys), nb = at_least_one(n_bkeys);
+    const size_t n = at_least_one(n_pairs);
     size_t t[6];
-    REMAP_HIP_CHECK((rocprim::radix_sort_keys(
-        nullptr, t[0], static_cast<const uint64_t *>(nullptr),
-        static_cast<uint64_t *>(nullptr), nb, 0u, 64u)));
-    REMAP_HIP_CHECK((rocprim::exclusive_scan(
-        nullptr, t[1], static_cast<const uint64_t *>(nullptr),
-        static_cast<uint64_t *>(nullptr), uint64_t(0), na,
-        rocprim::plus<uint64_t>())));
-    REMAP_HIP_CHECK((rocprim::radix_sort_keys(
-        nullptr, t[2], static_cast<const uint64_t *>(nullptr),
-        static_cast<uint64_t *>(nullptr), n, 0u, 64u)));
-    REMAP_HIP_CHECK((rocprim::unique(
-        nullptr, t[3], static_cast<const uint64_t *>(nullptr),
-        static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr),
-        n)));
-    REMAP_HIP_CHECK((rocprim::exclusive_scan(
-        nullptr, t[4], static_cast<const uint32_t *>(nullptr),
-        static_cast<uint32_t *>(nullptr), 0u, n, rocprim::plus<uint32_t>())));
-    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-        nullptr, t[5], static_cast<const uint64_t *>(nullptr),
-        static_cast<uint64_t *>(nullptr), static_cast<const double *>(nullptr),
-        static_cast<double *>(nullptr), n, 0u, 64u)));
-    L->temp_bytes = 0;
-    for (size_t b : t)
-        L->temp_bytes = b > L->temp_bytes ? b : L->temp_bytes;
+    REMAP_TRY(sort_keys_temp(nb, &t[0]));
+    REMAP_TRY(scan_temp<uint64_t>(na, &t[1]));
+    REMAP_TRY(sort_keys_temp(n, &t[2]));
+    REMAP_TRY(unique_temp(n, &t[3]));
+    REMAP_TRY(scan_temp<uint32_t>(n, &t[4]));
+    REMAP_TRY(sort_pairs_temp<double>(n, &t[5]));
+    L->temp_bytes = *std::max_element(t, t + 6);
     size_t off = L->fixed;
     L->bkeys = take(&off, nb * 8);
     L->bkeys_s = take(&off, nb * 8);
     L->akeys = take(&off, na * 8);
     L->pcnt = take(&off, na * 8);
     L->poff = take(&off, na * 8);
-    // candidates; then the unique pairs; then the sorted entry keys
-    L->cand = take(&off, n * 8);
-    // sorted candidates; then the kept entries' keys
-    L->cand_s = take(&off, n * 8);
-    L->parea = take(&off, n * 8);
-    L->area_c = take(&off, n * 8);
-    L->head = take(&off, n * 4);
-    L->slot = take(&off, n * 4);
+    L->pairs = pair_layout(n, &off);
     L->temp = take(&off, L->temp_bytes);
     L->total = off;
     return REMAP_OK;
 }
 
-int meshes_sizes(const char *who, const remap_overlap_mesh *mesh_a,
+// the count pass: mesh b's cells into the histogram of the buckets, mesh a's
+// sums over it; counter[0] candidates, [1] a's keys, [2] b's keys, [3] the
+// error bits of a (low half) and b (high half), read back into got
+int count_meshes(const Geom &A, const Geom &B, uint32_t *hist, double *lat_c,
+                 double *lon_c, int64_t *counter, int64_t *got,
+                 hipStream_t stream)
+{
+    REMAP_HIP_CHECK(hipMemsetAsync(counter, 0, 4 * sizeof(int64_t), stream));
+    REMAP_HIP_CHECK(hipMemsetAsync(hist, 0, A.n_lat * A.n_lon * 4, stream));
+    REMAP_TRY(launch(bucket_edges, A.n_lon + 1, kBlock, stream, A.n_lat,
+                     A.n_lon, lat_c, lon_c));
+    unsigned long long *cnt = as<unsigned long long>(counter);
+    int32_t *status = as<int32_t>(counter + 3);
+    REMAP_TRY(launch(mesh_count, B.n_cells, kPrepBlock, stream, B, true, hist,
+                     cnt + 2, cnt, status + 1));
+    REMAP_TRY(launch(mesh_count, A.n_cells, kPrepBlock, stream, A, false, hist,
+                     cnt + 1, cnt, status));
+    return read_back(got, counter, 4 * sizeof(int64_t), stream);
+}
+
+int meshes_sizes(const Route &R, const remap_overlap_mesh *mesh_a,
                  const remap_overlap_mesh *mesh_b, int64_t *counter,
                  int64_t *n_pairs_out, size_t *bytes_out, hipStream_t stream)
 {
     Geom A, B;
-    int rc = check_mesh(mesh_a, "a", &A);
-    if (rc == REMAP_OK)
-        rc = check_mesh(mesh_b, "b", &B);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(check_mesh(mesh_a, "a", &A));
+    REMAP_TRY(check_mesh(mesh_b, "b", &B));
     if (!counter || !n_pairs_out || !bytes_out)
-        return fail(REMAP_ERR_ARG, "%s_sizes: NULL output", who);
+        return fail(REMAP_ERR_ARG, "%s_sizes: NULL output", R.who);
     bucket_raster(B.n_cells, &A, &B);
-    const int64_t n_buckets = A.n_lat * A.n_lon;
     // the histogram of b's cells over the buckets, and the raster
-    const size_t hist_bytes = align_up(n_buckets * 4);
-    const size_t bytes = hist_bytes + align_up((A.n_lat + 1) * 8) +
-                         align_up((A.n_lon + 1) * 8);
+    size_t bytes = 0;
+    const size_t at_hist = take(&bytes, A.n_lat * A.n_lon * 4);
+    const size_t at_lat = take(&bytes, (A.n_lat + 1) * 8);
+    const size_t at_lon = take(&bytes, (A.n_lon + 1) * 8);
     char *buf = nullptr;
     REMAP_HIP_CHECK(hipMalloc(&buf, bytes));
-    uint32_t *hist = reinterpret_cast<uint32_t *>(buf);
-    double *lat_c = reinterpret_cast<double *>(buf + hist_bytes);
-    double *lon_c = lat_c + align_up((A.n_lat + 1) * 8) / 8;
-    A.lat_c = B.lat_c = lat_c;
-    A.lon_c = B.lon_c = lon_c;
+    A.lat_c = B.lat_c = at<double>(buf, at_lat);
+    A.lon_c = B.lon_c = at<double>(buf, at_lon);
     int64_t got[4];
-    hipError_t err = hipMemsetAsync(counter, 0, 4 * sizeof(int64_t), stream);
-    if (err == hipSuccess)
-        err = hipMemsetAsync(hist, 0, n_buckets * 4, stream);
-    if (err == hipSuccess) {
-        hipLaunchKernelGGL(bucket_edges, dim3(blocks(A.n_lon + 1, kBlock)),
-                           dim3(kBlock), 0, stream, A.n_lat, A.n_lon, lat_c,
-                           lon_c);
-        unsigned long long *cnt = reinterpret_cast<unsigned long long *>(counter);
-        int32_t *status = reinterpret_cast<int32_t *>(counter + 3);
-        if (B.n_cells > 0)
-            hipLaunchKernelGGL(mesh_count, dim3(blocks(B.n_cells, kPrepBlock)),
-                               dim3(kPrepBlock), 0, stream, B, true, hist,
-                               cnt + 2, cnt, status + 1);
-        if (A.n_cells > 0)
-            hipLaunchKernelGGL(mesh_count, dim3(blocks(A.n_cells, kPrepBlock)),
-                               dim3(kPrepBlock), 0, stream, A, false, hist,
-                               cnt + 1, cnt, status);
-        err = hipGetLastError();
-    }
-    if (err == hipSuccess)
-        err = hipMemcpyAsync(got, counter, sizeof(got), hipMemcpyDeviceToHost,
-                             stream);
-    if (err == hipSuccess)
-        err = hipStreamSynchronize(stream);
+    const int rc = count_meshes(A, B, at<uint32_t>(buf, at_hist),
+                                at<double>(buf, at_lat),
+                                at<double>(buf, at_lon), counter, got, stream);
     const hipError_t freed = hipFree(buf);
-    REMAP_HIP_CHECK(err);
+    REMAP_TRY(rc);
     REMAP_HIP_CHECK(freed);
     const int err_a = static_cast<int>(got[3] & 0xffffffff);
     const int err_b = static_cast<int>((got[3] >> 32) & 0xffffffff);
     if (err_a || err_b)
-        return meshes_fail(who, err_a, err_b, 0);
+        return route_fail(R, err_a, err_b, 0);
     MeshLayout lay;
-    rc = mesh_fixed_layout(A, B, &lay);
-    if (rc == REMAP_OK)
-        rc = mesh_var_layout(got[1], got[2], got[0], &lay);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(mesh_fixed_layout(A, B, &lay));
+    REMAP_TRY(mesh_var_layout(got[1], got[2], got[0], &lay));
     *n_pairs_out = got[0];
     *bytes_out = lay.total;
     return REMAP_OK;
-}
-
-struct Side {
-    double *xyz, *centre, *radius;
-    int32_t *nv;
-    Box *boxes;
-    uint64_t *counts, *offs;
-};
-
-Side side_at(char *ws, const SideLayout &s)
-{
-    return {reinterpret_cast<double *>(ws + s.xyz),
-            reinterpret_cast<double *>(ws + s.centre),
-            reinterpret_cast<double *>(ws + s.radius),
-            reinterpret_cast<int32_t *>(ws + s.nv),
-            reinterpret_cast<Box *>(ws + s.boxes),
-            reinterpret_cast<uint64_t *>(ws + s.counts),
-            reinterpret_cast<uint64_t *>(ws + s.offs)};
 }
 
 // cell_prep, cell_shape, the scan of the bucket counts and its total
@@ -1563,92 +1661,26 @@ int prep_side(const Geom &G, bool clipper, const Side &s, double *area,
 {
     if (G.n_cells <= 0)
         return REMAP_OK;
-    hipLaunchKernelGGL(cell_prep, dim3(blocks(G.n_cells, kPrepBlock)),
-                       dim3(kPrepBlock), 0, stream, G, s.xyz, s.nv, s.centre,
-                       area, s.boxes, s.counts, nullptr, status);
-    REMAP_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(cell_shape, dim3(blocks(G.n_cells, kBlock)),
-                       dim3(kBlock), 0, stream, G.n_cells, G.max_edges,
-                       clipper, s.xyz, s.nv, s.centre, s.radius, status);
-    REMAP_HIP_CHECK(hipGetLastError());
-    size_t tb = temp_bytes;
-    REMAP_HIP_CHECK((rocprim::exclusive_scan(
-        temp, tb, static_cast<const uint64_t *>(s.counts), s.offs,
-        uint64_t(0), static_cast<size_t>(G.n_cells),
-        rocprim::plus<uint64_t>(), stream)));
-    hipLaunchKernelGGL(scan_total, dim3(1), dim3(kWave), 0, stream, G.n_cells,
-                       s.counts, s.offs, total);
-    REMAP_HIP_CHECK(hipGetLastError());
-    return REMAP_OK;
+    REMAP_TRY(launch(cell_prep, G.n_cells, kPrepBlock, stream, G, s.xyz, s.nv,
+                     s.centre, area, s.boxes, s.counts, nullptr, status));
+    REMAP_TRY(launch(cell_shape, G.n_cells, kBlock, stream, G.n_cells,
+                     G.max_edges, clipper, s.xyz, s.nv, s.centre, s.radius,
+                     status));
+    REMAP_TRY(exclusive_scan(temp, temp_bytes, s.counts, s.offs, G.n_cells,
+                             stream));
+    return launch(scan_total, 1, kWave, stream, G.n_cells, s.counts, s.offs,
+                  total);
 }
-
-// the buffers of the pairs (n_pairs each) behind clip_pairs_poly
-struct PairWork {
-    uint64_t *cand, *cand_s;   // the pairs a << 32 | b; the kept entries' keys
-    double *parea, *area_c;
-    uint32_t *head, *slot;
-    uint64_t *n_unique;
-    int64_t *n_kept;
-    int32_t *status;
-    void *temp;
-    size_t temp_bytes;
-};
 
 // clip_pairs_poly over the pairs in w.cand (the first *w.n_unique of
-// n_pairs), then flag / scan / scatter: the kept entries re-keyed
-// (dst, src) in w.cand_s / w.area_c, their number in *w.n_kept
-int clip_and_keep(const Geom &A, const Side &sa, const Geom &B, const Side &sb,
-                  bool dst_is_a, int64_t n_pairs, const PairWork &w,
-                  const double *a_area, const double *b_area,
-                  hipStream_t stream)
+// n_pairs): their areas in w.parea
+int clip_poly(const Geom &A, const Side &sa, const Geom &B, const Side &sb,
+              int64_t n_pairs, const PairWork &w, hipStream_t stream)
 {
-    hipLaunchKernelGGL(clip_pairs_poly, dim3(blocks(n_pairs, kClipBlock)),
-                       dim3(kClipBlock), 0, stream, A.n_cells, A.max_edges,
-                       B.n_cells, B.max_edges, n_pairs, w.n_unique, w.cand,
-                       sa.xyz, sa.nv, sa.centre, sa.radius, sb.xyz, sb.nv,
-                       sb.centre, sb.radius, w.parea, w.status);
-    REMAP_HIP_CHECK(hipGetLastError());
-    const uint32_t nb = blocks(n_pairs, kBlock);
-    hipLaunchKernelGGL(flag_kept, dim3(nb), dim3(kBlock), 0, stream, n_pairs,
-                       A.n_cells, B.n_cells, dst_is_a, w.cand, w.parea, a_area,
-                       b_area, w.head);
-    REMAP_HIP_CHECK(hipGetLastError());
-    size_t tb = w.temp_bytes;
-    REMAP_HIP_CHECK((rocprim::exclusive_scan(
-        w.temp, tb, static_cast<const uint32_t *>(w.head), w.slot, 0u,
-        static_cast<size_t>(n_pairs), rocprim::plus<uint32_t>(), stream)));
-    hipLaunchKernelGGL(scatter_kept, dim3(nb), dim3(kBlock), 0, stream,
-                       n_pairs, dst_is_a, w.cand, w.parea, w.head, w.slot,
-                       w.cand_s, w.area_c, w.n_kept);
-    REMAP_HIP_CHECK(hipGetLastError());
-    return REMAP_OK;
-}
-
-// the kept entries sorted by (dst, src) into the outputs, frac_b of every
-// destination cell (w.cand is the sort's key output)
-int sort_and_sum(int64_t n_dst, int64_t n_entries, int64_t n_pairs,
-                 const PairWork &w, int32_t *dst_out, int32_t *src_out,
-                 double *area_out, const double *dst_area, double *frac_b_out,
-                 hipStream_t stream)
-{
-    if (n_entries > 0) {
-        size_t tb = w.temp_bytes;
-        REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-            w.temp, tb, static_cast<const uint64_t *>(w.cand_s), w.cand,
-            static_cast<const double *>(w.area_c), area_out,
-            static_cast<size_t>(n_entries), 0u, 64u, stream)));
-        hipLaunchKernelGGL(split_keys, dim3(blocks(n_entries, kBlock)),
-                           dim3(kBlock), 0, stream, w.n_kept, n_pairs, w.cand,
-                           dst_out, src_out);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
-    if (n_dst > 0) {
-        hipLaunchKernelGGL(dst_sums, dim3(blocks(n_dst, kBlock)), dim3(kBlock),
-                           0, stream, n_dst, w.n_kept, dst_out, area_out,
-                           dst_area, frac_b_out);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
-    return REMAP_OK;
+    return launch(clip_pairs_poly, n_pairs, kClipBlock, stream, A.n_cells,
+                  A.max_edges, B.n_cells, B.max_edges, n_pairs, w.n_unique,
+                  w.cand, sa.xyz, sa.nv, sa.centre, sa.radius, sb.xyz, sb.nv,
+                  sb.centre, sb.radius, w.parea, w.status);
 }
 
 // what the front of remap_overlap_meshes leaves behind for the clip
@@ -1663,42 +1695,33 @@ struct MeshRun {
 // Everything in front of clip_pairs_poly: both meshes prepared against b's
 // bucket raster (their polygons' areas into a_area / b_area), read-back 1,
 // the bucket lists and the unique candidate pairs a << 32 | b in R->work.cand.
-// `who` names the entry point in messages; ev (6 events or NULL) receives
-// the phase marks [0] start, [1] cells prepared, [2] pairs listed.
-int mesh_front(const char *who, const remap_overlap_mesh *mesh_a,
+// ev (6 events or NULL) receives the phase marks [0] start, [1] cells
+// prepared, [2] pairs listed.
+int mesh_front(const Route &route, const remap_overlap_mesh *mesh_a,
                const remap_overlap_mesh *mesh_b, int64_t n_pairs,
-               void *workspace, size_t workspace_bytes, double *a_area,
-               double *b_area, bool have_outputs, hipStream_t stream,
+               void *workspace, size_t workspace_bytes, const Outputs &out,
+               double *a_area, double *b_area, hipStream_t stream,
                hipEvent_t *ev, MeshRun *R)
 {
+    const char *who = route.who;
     Geom &A = R->A, &B = R->B;
-    int rc = check_mesh(mesh_a, "a", &A);
-    if (rc == REMAP_OK)
-        rc = check_mesh(mesh_b, "b", &B);
-    if (rc != REMAP_OK)
-        return rc;
-    if (n_pairs < 0 || n_pairs >= (int64_t(1) << 32) - 1)
-        return fail(REMAP_ERR_UNSUPPORTED, "%s: %lld candidate pairs", who,
-                    static_cast<long long>(n_pairs));
-    if (!have_outputs)
-        return fail(REMAP_ERR_ARG, "%s: NULL output", who);
+    REMAP_TRY(check_mesh(mesh_a, "a", &A));
+    REMAP_TRY(check_mesh(mesh_b, "b", &B));
+    REMAP_TRY(check_call(who, n_pairs, out));
     bucket_raster(B.n_cells, &A, &B);
     const int64_t n_buckets = A.n_lat * A.n_lon;
     MeshLayout &lay = R->lay;
-    rc = mesh_fixed_layout(A, B, &lay);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(mesh_fixed_layout(A, B, &lay));
     if (!workspace || workspace_bytes < lay.fixed)
         return fail(REMAP_ERR_WORKSPACE,
                     "%s: workspace of %zu bytes, need at least %zu", who,
                     workspace_bytes, lay.fixed);
     char *ws = static_cast<char *>(workspace);
-    double *lat_c = reinterpret_cast<double *>(ws + lay.lat_c);
-    double *lon_c = reinterpret_cast<double *>(ws + lay.lon_c);
-    uint32_t *start = reinterpret_cast<uint32_t *>(ws + lay.start);
-    int64_t *back = reinterpret_cast<int64_t *>(ws + lay.back);
-    int32_t *status_ab = reinterpret_cast<int32_t *>(back + 2);
-    int32_t *status = reinterpret_cast<int32_t *>(back + 5);
+    double *lat_c = at<double>(ws, lay.lat_c);
+    double *lon_c = at<double>(ws, lay.lon_c);
+    uint32_t *start = at<uint32_t>(ws, lay.start);
+    int64_t *back = at<int64_t>(ws, lay.back);
+    int32_t *status_ab = as<int32_t>(back + 2);
     R->back = back;
     R->sa = side_at(ws, lay.a);
     R->sb = side_at(ws, lay.b);
@@ -1709,106 +1732,71 @@ int mesh_front(const char *who, const remap_overlap_mesh *mesh_a,
     if (ev)
         REMAP_HIP_CHECK(hipEventRecord(ev[0], stream));
     REMAP_HIP_CHECK(hipMemsetAsync(back, 0, kBackWords * 8, stream));
-    hipLaunchKernelGGL(bucket_edges, dim3(blocks(A.n_lon + 1, kBlock)),
-                       dim3(kBlock), 0, stream, A.n_lat, A.n_lon, lat_c,
-                       lon_c);
-    REMAP_HIP_CHECK(hipGetLastError());
+    REMAP_TRY(launch(bucket_edges, A.n_lon + 1, kBlock, stream, A.n_lat,
+                     A.n_lon, lat_c, lon_c));
     void *temp0 = ws + lay.temp0;
-    rc = prep_side(B, true, sb, b_area, temp0, lay.temp0_bytes, back,
-                   status_ab + 1, stream);
-    if (rc == REMAP_OK)
-        rc = prep_side(A, false, sa, a_area, temp0, lay.temp0_bytes,
-                       back + 1, status_ab, stream);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(prep_side(B, true, sb, b_area, temp0, lay.temp0_bytes, back,
+                        status_ab + 1, stream));
+    REMAP_TRY(prep_side(A, false, sa, a_area, temp0, lay.temp0_bytes,
+                        back + 1, status_ab, stream));
     if (ev)
         REMAP_HIP_CHECK(hipEventRecord(ev[1], stream));
     // read-back 1: the bucket keys of both meshes, the cells' error bits
     int64_t got[3];
-    REMAP_HIP_CHECK(hipMemcpyAsync(got, back, sizeof(got),
-                                   hipMemcpyDeviceToHost, stream));
-    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+    REMAP_TRY(read_back(got, back, sizeof(got), stream));
     const int64_t n_bkeys = got[0], n_akeys = got[1];
     const int err_a = static_cast<int>(got[2] & 0xffffffff);
     const int err_b = static_cast<int>((got[2] >> 32) & 0xffffffff);
     if (err_a || err_b)
-        return meshes_fail(who, err_a, err_b, 0);
+        return route_fail(route, err_a, err_b, 0);
     if (n_bkeys >= (int64_t(1) << 32) - 1 || n_akeys >= (int64_t(1) << 32) - 1)
         return fail(REMAP_ERR_UNSUPPORTED, "%s: %lld / %lld bucket keys", who,
                     static_cast<long long>(n_akeys),
                     static_cast<long long>(n_bkeys));
     if (n_pairs > 0 && n_akeys == 0)
-        return meshes_fail(who, 0, 0, REMAP_OVERLAP_ERR_CAPACITY);
-    rc = mesh_var_layout(n_akeys, n_bkeys, n_pairs, &lay);
-    if (rc != REMAP_OK)
-        return rc;
+        return route_fail(route, 0, 0, REMAP_OVERLAP_ERR_CAPACITY);
+    REMAP_TRY(mesh_var_layout(n_akeys, n_bkeys, n_pairs, &lay));
     if (workspace_bytes < lay.total)
         return fail(REMAP_ERR_WORKSPACE,
                     "%s: workspace of %zu bytes, need %zu", who,
                     workspace_bytes, lay.total);
-    uint64_t *bkeys = reinterpret_cast<uint64_t *>(ws + lay.bkeys);
-    uint64_t *bkeys_s = reinterpret_cast<uint64_t *>(ws + lay.bkeys_s);
-    uint64_t *akeys = reinterpret_cast<uint64_t *>(ws + lay.akeys);
-    uint64_t *pcnt = reinterpret_cast<uint64_t *>(ws + lay.pcnt);
-    uint64_t *poff = reinterpret_cast<uint64_t *>(ws + lay.poff);
-    uint64_t *cand = reinterpret_cast<uint64_t *>(ws + lay.cand);
-    uint64_t *cand_s = reinterpret_cast<uint64_t *>(ws + lay.cand_s);
-    double *parea = reinterpret_cast<double *>(ws + lay.parea);
-    double *area_c = reinterpret_cast<double *>(ws + lay.area_c);
-    uint32_t *head = reinterpret_cast<uint32_t *>(ws + lay.head);
-    uint32_t *slot = reinterpret_cast<uint32_t *>(ws + lay.slot);
-    uint64_t *n_unique = reinterpret_cast<uint64_t *>(back + 3);
-    int64_t *n_kept = back + 4;
+    uint64_t *bkeys = at<uint64_t>(ws, lay.bkeys);
+    uint64_t *bkeys_s = at<uint64_t>(ws, lay.bkeys_s);
+    uint64_t *akeys = at<uint64_t>(ws, lay.akeys);
+    uint64_t *pcnt = at<uint64_t>(ws, lay.pcnt);
+    uint64_t *poff = at<uint64_t>(ws, lay.poff);
     void *temp = ws + lay.temp;
+    R->work = pair_work(ws, lay.pairs, back + 3, temp, lay.temp_bytes);
+    const PairWork &w = R->work;
 
     // b's bucket lists
     if (n_bkeys > 0) {
-        hipLaunchKernelGGL(fill_pairs<true>, dim3(blocks(B.n_cells, kBlock)),
-                           dim3(kBlock), 0, stream, B, sb.boxes, sb.offs,
-                           n_bkeys, bkeys, status);
-        REMAP_HIP_CHECK(hipGetLastError());
-        size_t tb = lay.temp_bytes;
-        REMAP_HIP_CHECK((rocprim::radix_sort_keys(
-            temp, tb, static_cast<const uint64_t *>(bkeys), bkeys_s,
-            static_cast<size_t>(n_bkeys), 0u, 64u, stream)));
+        REMAP_TRY(launch(fill_pairs<true>, B.n_cells, kBlock, stream, B,
+                         sb.boxes, sb.offs, n_bkeys, bkeys, w.status));
+        REMAP_TRY(radix_sort_keys(temp, lay.temp_bytes, bkeys, bkeys_s,
+                                  n_bkeys, stream));
     }
-    hipLaunchKernelGGL(bucket_starts, dim3(blocks(n_buckets + 1, kBlock)),
-                       dim3(kBlock), 0, stream, n_buckets, n_bkeys, bkeys_s,
-                       start);
-    REMAP_HIP_CHECK(hipGetLastError());
+    REMAP_TRY(launch(bucket_starts, n_buckets + 1, kBlock, stream, n_buckets,
+                     n_bkeys, bkeys_s, start));
     // a's (cell, bucket) keys, expanded to (a, b) candidates
     if (n_akeys > 0) {
-        const uint32_t nb = blocks(n_akeys, kBlock);
-        hipLaunchKernelGGL(fill_pairs<false>, dim3(blocks(A.n_cells, kBlock)),
-                           dim3(kBlock), 0, stream, A, sa.boxes, sa.offs,
-                           n_akeys, akeys, status);
-        REMAP_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(pair_counts, dim3(nb), dim3(kBlock), 0, stream,
-                           n_akeys, n_buckets, akeys, start, pcnt);
-        REMAP_HIP_CHECK(hipGetLastError());
-        size_t tb = lay.temp_bytes;
-        REMAP_HIP_CHECK((rocprim::exclusive_scan(
-            temp, tb, static_cast<const uint64_t *>(pcnt), poff, uint64_t(0),
-            static_cast<size_t>(n_akeys), rocprim::plus<uint64_t>(), stream)));
-        hipLaunchKernelGGL(expand_pairs, dim3(nb), dim3(kBlock), 0, stream,
-                           n_akeys, n_buckets, akeys, pcnt, poff, start,
-                           bkeys_s, n_pairs, cand, status);
-        REMAP_HIP_CHECK(hipGetLastError());
+        REMAP_TRY(launch(fill_pairs<false>, A.n_cells, kBlock, stream, A,
+                         sa.boxes, sa.offs, n_akeys, akeys, w.status));
+        REMAP_TRY(launch(pair_counts, n_akeys, kBlock, stream, n_akeys,
+                         n_buckets, akeys, start, pcnt));
+        REMAP_TRY(exclusive_scan(temp, lay.temp_bytes, pcnt, poff, n_akeys,
+                                 stream));
+        REMAP_TRY(launch(expand_pairs, n_akeys, kBlock, stream, n_akeys,
+                         n_buckets, akeys, pcnt, poff, start, bkeys_s, n_pairs,
+                         w.cand, w.status));
     }
-    R->work = {cand, cand_s, parea, area_c, head, slot, n_unique,
-               n_kept, status, temp, lay.temp_bytes};
     if (n_pairs > 0) {
-        size_t tb = lay.temp_bytes;
-        REMAP_HIP_CHECK((rocprim::radix_sort_keys(
-            temp, tb, static_cast<const uint64_t *>(cand), cand_s,
-            static_cast<size_t>(n_pairs), 0u, 64u, stream)));
+        REMAP_TRY(radix_sort_keys(temp, lay.temp_bytes, w.cand, w.cand_s,
+                                  n_pairs, stream));
         // the unique pairs into cand, the rest of it ~0 (no pair)
-        REMAP_HIP_CHECK(hipMemsetAsync(cand, 0xff, n_pairs * 8, stream));
-        tb = lay.temp_bytes;
-        REMAP_HIP_CHECK((rocprim::unique(
-            temp, tb, static_cast<const uint64_t *>(cand_s), cand, n_unique,
-            static_cast<size_t>(n_pairs), rocprim::equal_to<uint64_t>(),
-            stream)));
+        REMAP_HIP_CHECK(hipMemsetAsync(w.cand, 0xff, n_pairs * 8, stream));
+        REMAP_TRY(unique(temp, lay.temp_bytes, w.cand_s, w.cand, w.n_unique,
+                         n_pairs, stream));
     }
     if (ev)
         REMAP_HIP_CHECK(hipEventRecord(ev[2], stream));
@@ -1817,39 +1805,24 @@ int mesh_front(const char *who, const remap_overlap_mesh *mesh_a,
 
 int meshes(const remap_overlap_mesh *mesh_a, const remap_overlap_mesh *mesh_b,
            int32_t dst_is_b, int64_t n_pairs, void *workspace,
-           size_t workspace_bytes, int32_t *dst_out, int32_t *src_out,
-           double *area_out, double *frac_b_out, double *a_area_out,
-           double *b_area_out, int64_t *n_entries_out, hipStream_t stream)
+           size_t workspace_bytes, const Outputs &out, hipStream_t stream)
 {
-    static const char who[] = "remap_overlap_meshes";
-    const bool have_outputs =
-        frac_b_out && a_area_out && b_area_out && n_entries_out &&
-        (n_pairs <= 0 || (dst_out && src_out && area_out));
     MeshRun R;
-    int rc = mesh_front(who, mesh_a, mesh_b, n_pairs, workspace,
-                        workspace_bytes, a_area_out, b_area_out, have_outputs,
-                        stream, nullptr, &R);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(mesh_front(kMeshes, mesh_a, mesh_b, n_pairs, workspace,
+                         workspace_bytes, out, out.a_area, out.b_area, stream,
+                         nullptr, &R));
     const bool dst_is_a = dst_is_b == 0;
-    if (n_pairs > 0) {
-        rc = clip_and_keep(R.A, R.sa, R.B, R.sb, dst_is_a, n_pairs, R.work,
-                           a_area_out, b_area_out, stream);
-        if (rc != REMAP_OK)
-            return rc;
-    }
+    REMAP_TRY(clip_poly(R.A, R.sa, R.B, R.sb, n_pairs, R.work, stream));
+    REMAP_TRY(keep_pairs(n_pairs, R.A.n_cells, R.B.n_cells, dst_is_a, R.work,
+                         out.a_area, out.b_area, stream));
     // read-back 2: how many entries to sort, the pairs' error bits
     int64_t kept[2];
-    REMAP_HIP_CHECK(hipMemcpyAsync(kept, R.work.n_kept, 16,
-                                   hipMemcpyDeviceToHost, stream));
-    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
-    const int64_t n_entries = kept[0];
+    REMAP_TRY(read_back(kept, R.work.n_kept, 16, stream));
     if (const int err = static_cast<int>(kept[1] & 0xffffffff))
-        return meshes_fail(who, 0, 0, err);
-    *n_entries_out = n_entries;
-    return sort_and_sum(dst_is_a ? R.A.n_cells : R.B.n_cells, n_entries,
-                        n_pairs, R.work, dst_out, src_out, area_out,
-                        dst_is_a ? a_area_out : b_area_out, frac_b_out,
+        return route_fail(kMeshes, 0, 0, err);
+    *out.n_entries = kept[0];
+    return sort_and_sum(dst_is_a ? R.A.n_cells : R.B.n_cells, kept[0], n_pairs,
+                        R.work, out, dst_is_a ? out.a_area : out.b_area,
                         stream);
 }
 
@@ -2048,15 +2021,11 @@ struct PiecesLayout {
 
 int pieces_layout(int64_t n_a, int64_t n_b, int64_t n_pairs, PiecesLayout *L)
 {
-    const size_t n = static_cast<size_t>(n_pairs > 0 ? n_pairs : 1);
-    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-        nullptr, L->temp_bytes, static_cast<const uint64_t *>(nullptr),
-        static_cast<uint64_t *>(nullptr),
-        static_cast<const uint32_t *>(nullptr),
-        static_cast<uint32_t *>(nullptr), n, 0u, 64u)));
+    const size_t n = at_least_one(n_pairs);
+    REMAP_TRY(sort_pairs_temp<uint32_t>(n, &L->temp_bytes));
     size_t off = 0;
-    L->a_area = take(&off, static_cast<size_t>(n_a > 0 ? n_a : 1) * 8);
-    L->b_area = take(&off, static_cast<size_t>(n_b > 0 ? n_b : 1) * 8);
+    L->a_area = take(&off, at_least_one(n_a) * 8);
+    L->b_area = take(&off, at_least_one(n_b) * 8);
     L->at_c = take(&off, n * 4);
     L->at_s = take(&off, n * 4);
     L->pieces_c = take(&off, n * 8);
@@ -2095,75 +2064,52 @@ int pieces_sizes(const PiecesArg *a, const PiecesArg *b,
                  int64_t *counter, int64_t *n_pairs_out, size_t *bytes_out,
                  hipStream_t stream)
 {
-    int rc = check_pieces(a, "a");
-    if (rc == REMAP_OK)
-        rc = check_pieces(b, "b");
-    if (rc == REMAP_OK)
-        rc = meshes_sizes("remap_overlap_pieces", &a->mesh, &b->mesh, counter,
-                          n_pairs_out, bytes_out, stream);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(check_pieces(a, "a"));
+    REMAP_TRY(check_pieces(b, "b"));
+    REMAP_TRY(meshes_sizes(kPieces, &a->mesh, &b->mesh, counter, n_pairs_out,
+                           bytes_out, stream));
     PiecesLayout X;
-    rc = pieces_layout(a->mesh.n_cells, b->mesh.n_cells, *n_pairs_out, &X);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(pieces_layout(a->mesh.n_cells, b->mesh.n_cells, *n_pairs_out,
+                            &X));
     *bytes_out += X.total;
     return REMAP_OK;
 }
 
 // ev (6 events, or NULL) marks the phases: cell preparation, candidate pairs,
 // clip (with its compaction), sort, merge (with frac_b)
-int pieces(const PiecesArg *pa, const PiecesArg *pb,
-           int32_t dst_is_b, int64_t n_pairs, void *workspace,
-           size_t workspace_bytes, int32_t *dst_out, int32_t *src_out,
-           double *area_out, double *frac_b_out, double *a_area_out,
-           double *b_area_out, int64_t *n_entries_out, hipStream_t stream,
-           hipEvent_t *ev)
+int pieces(const PiecesArg *pa, const PiecesArg *pb, int32_t dst_is_b,
+           int64_t n_pairs, void *workspace, size_t workspace_bytes,
+           const Outputs &out, hipStream_t stream, hipEvent_t *ev)
 {
-    static const char who[] = "remap_overlap_pieces";
-    int rc = check_pieces(pa, "a");
-    if (rc == REMAP_OK)
-        rc = check_pieces(pb, "b");
-    if (rc != REMAP_OK)
-        return rc;
-    const bool have_outputs =
-        frac_b_out && a_area_out && b_area_out && n_entries_out &&
-        (n_pairs <= 0 || (dst_out && src_out && area_out));
+    const char *who = kPieces.who;
+    REMAP_TRY(check_pieces(pa, "a"));
+    REMAP_TRY(check_pieces(pb, "b"));
     const int64_t n_a = pa->mesh.n_cells, n_b = pb->mesh.n_cells;
     PiecesLayout X;
-    rc = pieces_layout(n_a, n_b, n_pairs, &X);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(pieces_layout(n_a, n_b, n_pairs, &X));
     if (!workspace || workspace_bytes < X.total)
         return fail(REMAP_ERR_WORKSPACE,
                     "%s: workspace of %zu bytes, need more than %zu", who,
                     workspace_bytes, X.total);
     char *ws = static_cast<char *>(workspace);
-    double *piece_area_a = reinterpret_cast<double *>(ws + X.a_area);
-    double *piece_area_b = reinterpret_cast<double *>(ws + X.b_area);
-    uint32_t *at_c = reinterpret_cast<uint32_t *>(ws + X.at_c);
-    uint32_t *at_s = reinterpret_cast<uint32_t *>(ws + X.at_s);
-    uint64_t *pieces_c = reinterpret_cast<uint64_t *>(ws + X.pieces_c);
-    int64_t *back = reinterpret_cast<int64_t *>(ws + X.back);
-    int32_t *status_ab = reinterpret_cast<int32_t *>(back + 1);
+    double *piece_area_a = at<double>(ws, X.a_area);
+    double *piece_area_b = at<double>(ws, X.b_area);
+    uint32_t *at_c = at<uint32_t>(ws, X.at_c);
+    uint32_t *at_s = at<uint32_t>(ws, X.at_s);
+    uint64_t *pieces_c = at<uint64_t>(ws, X.pieces_c);
+    int64_t *back = at<int64_t>(ws, X.back);
+    int32_t *status_ab = as<int32_t>(back + 1);
 
     REMAP_HIP_CHECK(hipMemsetAsync(back, 0, 16, stream));
     // the parents first (a read-back of their own, none with identity
     // parents): an argument error comes before any geometry
     if ((pa->parent && n_a > 0) || (pb->parent && n_b > 0)) {
-        if (pa->parent && n_a > 0)
-            hipLaunchKernelGGL(check_parents, dim3(blocks(n_a, kBlock)),
-                               dim3(kBlock), 0, stream, n_a, pa->n_parents,
-                               pa->parent, status_ab);
-        if (pb->parent && n_b > 0)
-            hipLaunchKernelGGL(check_parents, dim3(blocks(n_b, kBlock)),
-                               dim3(kBlock), 0, stream, n_b, pb->n_parents,
-                               pb->parent, status_ab + 1);
-        REMAP_HIP_CHECK(hipGetLastError());
+        REMAP_TRY(launch(check_parents, pa->parent ? n_a : 0, kBlock, stream,
+                         n_a, pa->n_parents, pa->parent, status_ab));
+        REMAP_TRY(launch(check_parents, pb->parent ? n_b : 0, kBlock, stream,
+                         n_b, pb->n_parents, pb->parent, status_ab + 1));
         int32_t bad[2];
-        REMAP_HIP_CHECK(hipMemcpyAsync(bad, status_ab, 8,
-                                       hipMemcpyDeviceToHost, stream));
-        REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+        REMAP_TRY(read_back(bad, status_ab, 8, stream));
         if (bad[0] || bad[1])
             return fail(REMAP_ERR_ARG, "%s: parent of side %s %s", who,
                         bad[0] ? "a" : "b",
@@ -2172,104 +2118,65 @@ int pieces(const PiecesArg *pa, const PiecesArg *pb,
                             : "skips a cell: a cell without a piece");
     }
     MeshRun R;
-    rc = mesh_front(who, &pa->mesh, &pb->mesh, n_pairs, ws + X.total,
-                    workspace_bytes - X.total, piece_area_a, piece_area_b,
-                    have_outputs, stream, ev, &R);
-    if (rc != REMAP_OK)
-        return rc;
-    if (pa->n_parents > 0)
-        hipLaunchKernelGGL(parent_areas, dim3(blocks(pa->n_parents, kBlock)),
-                           dim3(kBlock), 0, stream, n_a, pa->n_parents,
-                           pa->parent, piece_area_a, a_area_out);
-    if (pb->n_parents > 0)
-        hipLaunchKernelGGL(parent_areas, dim3(blocks(pb->n_parents, kBlock)),
-                           dim3(kBlock), 0, stream, n_b, pb->n_parents,
-                           pb->parent, piece_area_b, b_area_out);
-    REMAP_HIP_CHECK(hipGetLastError());
+    REMAP_TRY(mesh_front(kPieces, &pa->mesh, &pb->mesh, n_pairs, ws + X.total,
+                         workspace_bytes - X.total, out, piece_area_a,
+                         piece_area_b, stream, ev, &R));
+    REMAP_TRY(launch(parent_areas, pa->n_parents, kBlock, stream, n_a,
+                     pa->n_parents, pa->parent, piece_area_a, out.a_area));
+    REMAP_TRY(launch(parent_areas, pb->n_parents, kBlock, stream, n_b,
+                     pb->n_parents, pb->parent, piece_area_b, out.b_area));
     const bool dst_is_a = dst_is_b == 0;
     const PairWork &w = R.work;
+    REMAP_TRY(clip_poly(R.A, R.sa, R.B, R.sb, n_pairs, w, stream));
     if (n_pairs > 0) {
-        hipLaunchKernelGGL(clip_pairs_poly, dim3(blocks(n_pairs, kClipBlock)),
-                           dim3(kClipBlock), 0, stream, n_a, R.A.max_edges,
-                           n_b, R.B.max_edges, n_pairs, w.n_unique, w.cand,
-                           R.sa.xyz, R.sa.nv, R.sa.centre, R.sa.radius,
-                           R.sb.xyz, R.sb.nv, R.sb.centre, R.sb.radius,
-                           w.parea, w.status);
-        REMAP_HIP_CHECK(hipGetLastError());
-        const uint32_t nb = blocks(n_pairs, kBlock);
-        hipLaunchKernelGGL(flag_positive, dim3(nb), dim3(kBlock), 0, stream,
-                           n_pairs, n_a, n_b, w.cand, w.parea, w.head);
-        REMAP_HIP_CHECK(hipGetLastError());
-        size_t tb = w.temp_bytes;
-        REMAP_HIP_CHECK((rocprim::exclusive_scan(
-            w.temp, tb, static_cast<const uint32_t *>(w.head), w.slot, 0u,
-            static_cast<size_t>(n_pairs), rocprim::plus<uint32_t>(), stream)));
-        hipLaunchKernelGGL(scatter_parents, dim3(nb), dim3(kBlock), 0, stream,
-                           n_pairs, dst_is_a, w.cand, w.parea, w.head, w.slot,
-                           pa->parent, pb->parent, w.cand_s, at_c, w.area_c,
-                           pieces_c, w.n_kept);
-        REMAP_HIP_CHECK(hipGetLastError());
+        REMAP_TRY(launch(flag_positive, n_pairs, kBlock, stream, n_pairs, n_a,
+                         n_b, w.cand, w.parea, w.head));
+        REMAP_TRY(exclusive_scan(w.temp, w.temp_bytes, w.head, w.slot, n_pairs,
+                                 stream));
+        REMAP_TRY(launch(scatter_parents, n_pairs, kBlock, stream, n_pairs,
+                         dst_is_a, w.cand, w.parea, w.head, w.slot, pa->parent,
+                         pb->parent, w.cand_s, at_c, w.area_c, pieces_c,
+                         w.n_kept));
     }
     if (ev)
         REMAP_HIP_CHECK(hipEventRecord(ev[3], stream));
     // read-back 2: how many piece pairs to sort, the pairs' error bits
     int64_t kept[2];
-    REMAP_HIP_CHECK(hipMemcpyAsync(kept, w.n_kept, 16, hipMemcpyDeviceToHost,
-                                   stream));
-    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+    REMAP_TRY(read_back(kept, w.n_kept, 16, stream));
     const int64_t n_kept = kept[0];
     if (const int err = static_cast<int>(kept[1] & 0xffffffff))
-        return meshes_fail(who, 0, 0, err);
-    const double *dst_area = dst_is_a ? a_area_out : b_area_out;
+        return route_fail(kPieces, 0, 0, err);
+    const double *dst_area = dst_is_a ? out.a_area : out.b_area;
     const int64_t n_dst = dst_is_a ? pa->n_parents : pb->n_parents;
-    if (n_kept > 0) {
-        // (w.cand is the sort's key output, w.parea the runs' sums)
-        size_t tb = X.temp_bytes;
-        REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-            ws + X.temp, tb, static_cast<const uint64_t *>(w.cand_s), w.cand,
-            static_cast<const uint32_t *>(at_c), at_s,
-            static_cast<size_t>(n_kept), 0u, 64u, stream)));
-    }
+    // (w.cand is the sort's key output, w.parea the runs' sums)
+    if (n_kept > 0)
+        REMAP_TRY(radix_sort_pairs(ws + X.temp, X.temp_bytes, w.cand_s, w.cand,
+                                   at_c, at_s, n_kept, stream));
     if (ev)
         REMAP_HIP_CHECK(hipEventRecord(ev[4], stream));
     int64_t n_entries = 0;
     if (n_kept > 0) {
-        const uint32_t nb = blocks(n_kept, kBlock);
-        hipLaunchKernelGGL(merge_runs, dim3(nb), dim3(kBlock), 0, stream,
-                           n_kept, w.cand, at_s, w.area_c, pieces_c, dst_area,
-                           w.parea, w.head);
-        REMAP_HIP_CHECK(hipGetLastError());
-        size_t tb = w.temp_bytes;
-        REMAP_HIP_CHECK((rocprim::exclusive_scan(
-            w.temp, tb, static_cast<const uint32_t *>(w.head), w.slot, 0u,
-            static_cast<size_t>(n_kept), rocprim::plus<uint32_t>(), stream)));
-        hipLaunchKernelGGL(scatter_entries, dim3(nb), dim3(kBlock), 0, stream,
-                           n_kept, w.cand, w.parea, w.head, w.slot, dst_out,
-                           src_out, area_out, back);
-        REMAP_HIP_CHECK(hipGetLastError());
+        REMAP_TRY(launch(merge_runs, n_kept, kBlock, stream, n_kept, w.cand,
+                         at_s, w.area_c, pieces_c, dst_area, w.parea, w.head));
+        REMAP_TRY(exclusive_scan(w.temp, w.temp_bytes, w.head, w.slot, n_kept,
+                                 stream));
+        REMAP_TRY(launch(scatter_entries, n_kept, kBlock, stream, n_kept,
+                         w.cand, w.parea, w.head, w.slot, out.dst, out.src,
+                         out.area, back));
         // read-back 3: the entries the sliver rule left
-        REMAP_HIP_CHECK(hipMemcpyAsync(&n_entries, back, 8,
-                                       hipMemcpyDeviceToHost, stream));
-        REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+        REMAP_TRY(read_back(&n_entries, back, 8, stream));
     }
-    *n_entries_out = n_entries;
-    if (n_dst > 0) {
-        hipLaunchKernelGGL(dst_sums, dim3(blocks(n_dst, kBlock)), dim3(kBlock),
-                           0, stream, n_dst, back, dst_out, area_out, dst_area,
-                           frac_b_out);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
+    *out.n_entries = n_entries;
+    REMAP_TRY(launch(dst_sums, n_dst, kBlock, stream, n_dst, back, out.dst,
+                     out.area, dst_area, out.frac_b));
     if (ev)
         REMAP_HIP_CHECK(hipEventRecord(ev[5], stream));
     return REMAP_OK;
 }
 
-int pieces_timed(const PiecesArg *pa,
-                 const PiecesArg *pb, int32_t dst_is_b,
+int pieces_timed(const PiecesArg *pa, const PiecesArg *pb, int32_t dst_is_b,
                  int64_t n_pairs, void *workspace, size_t workspace_bytes,
-                 int32_t *dst_out, int32_t *src_out, double *area_out,
-                 double *frac_b_out, double *a_area_out, double *b_area_out,
-                 int64_t *n_entries_out, float *phase_ms, hipStream_t stream)
+                 const Outputs &out, float *phase_ms, hipStream_t stream)
 {
     if (!phase_ms)
         return fail(REMAP_ERR_ARG, "remap_overlap_pieces_timed: NULL phase_ms");
@@ -2279,9 +2186,8 @@ int pieces_timed(const PiecesArg *pa,
         err = hipEventCreate(&ev[k]);
     int rc = REMAP_OK;
     if (err == hipSuccess) {
-        rc = pieces(pa, pb, dst_is_b, n_pairs, workspace, workspace_bytes,
-                    dst_out, src_out, area_out, frac_b_out, a_area_out,
-                    b_area_out, n_entries_out, stream, ev);
+        rc = pieces(pa, pb, dst_is_b, n_pairs, workspace, workspace_bytes, out,
+                    stream, ev);
         if (rc == REMAP_OK)
             err = hipEventSynchronize(ev[5]);
         for (int k = 0; k < 5 && rc == REMAP_OK && err == hipSuccess; ++k)
@@ -2319,7 +2225,7 @@ int pieces_timed(const PiecesArg *pa,
 //                  node is a candidate.  Count pass, exclusive scan, fill
 //                  pass with the same walk: keys a << 32 | b whichever side
 //                  walked, unique, in a fixed order
-//   clip_pairs_poly, flag / scan / scatter, radix sort, dst_sums as above
+//   clip_pairs_poly, keep_pairs, sort_and_sum as above
 // The pyramid is the grid side's; when both sides are grids it is b's (the
 // clipper, the side with fewer cells: the side with more cells has the
 // lanes).  Nothing but the corner arrays is needed: a pole inside the grid,
@@ -2612,52 +2518,6 @@ int check_side(const remap_overlap_side *s, const char *name, GridSide *out)
     return REMAP_OK;
 }
 
-// the error bits of one side, or of the pairs (name NULL), as text, the
-// bits' names included
-void describe_side(const char *name, int err, char *out, size_t size)
-{
-    out[0] = '\0';
-    if (!err)
-        return;
-    snprintf(out, size, "%s%s%s%s%s%s%s%s%s", name ? "side " : "",
-             name ? name : "", name ? ": " : "",
-             (err & REMAP_OVERLAP_ERR_EDGES)
-                 ? "a cell has more edges than this build serves "
-                   "(REMAP_OVERLAP_ERR_EDGES); "
-                 : "",
-             (err & REMAP_OVERLAP_ERR_VERTEX)
-                 ? "a cell has fewer than 3 distinct corners or a vertex "
-                   "index out of range (REMAP_OVERLAP_ERR_VERTEX); "
-                 : "",
-             (err & REMAP_OVERLAP_ERR_CONVEX)
-                 ? "a cell is not convex and side b's cells clip "
-                   "(REMAP_OVERLAP_ERR_CONVEX); "
-                 : "",
-             (err & REMAP_OVERLAP_ERR_HEMISPHERE)
-                 ? "a candidate pair has a vertex outside the tangent "
-                   "hemisphere of the side a cell's centre "
-                   "(REMAP_OVERLAP_ERR_HEMISPHERE); "
-                 : "",
-             (err & kErrClip)
-                 ? "a clipped polygon outgrew its 2 x REMAP_OVERLAP_MAX_EDGES "
-                   "vertices; "
-                 : "",
-             (err & REMAP_OVERLAP_ERR_CAPACITY)
-                 ? "the candidate pairs differ from n_pairs, a stale "
-                   "remap_overlap_grids_sizes (REMAP_OVERLAP_ERR_CAPACITY); "
-                 : "");
-}
-
-int grids_fail(int err_a, int err_b, int err_p)
-{
-    char text[3][256];
-    describe_side("a", err_a, text[0], sizeof(text[0]));
-    describe_side("b", err_b, text[1], sizeof(text[1]));
-    describe_side(nullptr, err_p, text[2], sizeof(text[2]));
-    return fail(REMAP_ERR_UNSUPPORTED, "remap_overlap_grids: %s%s%s", text[0],
-                text[1], text[2]);
-}
-
 // the workspace in front of the pairs: the mesh path's (a raster of one
 // bucket, both sides, the read-back words) and the pyramid
 struct GridLayout {
@@ -2669,9 +2529,7 @@ struct GridLayout {
 
 int grid_fixed_layout(const GridSide &A, const GridSide &B, GridLayout *L)
 {
-    const int rc = mesh_fixed_layout(A.G, B.G, &L->m);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(mesh_fixed_layout(A.G, B.G, &L->m));
     L->index = B.is_grid ? &B : &A;
     L->walker = B.is_grid ? &A : &B;
     const GridGeom &Q = L->index->Q;
@@ -2685,15 +2543,11 @@ int grid_fixed_layout(const GridSide &A, const GridSide &B, GridLayout *L)
 int prep_grid_side(const GridSide &S, bool clipper, const Side &s,
                    double *area, int32_t *status, hipStream_t stream)
 {
-    hipLaunchKernelGGL(quad_prep, dim3(blocks(S.G.n_cells, kPrepBlock)),
-                       dim3(kPrepBlock), 0, stream, S.Q, s.xyz, s.nv, s.centre,
-                       area, status);
-    REMAP_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(cell_shape, dim3(blocks(S.G.n_cells, kBlock)),
-                       dim3(kBlock), 0, stream, S.G.n_cells, S.G.max_edges,
-                       clipper, s.xyz, s.nv, s.centre, s.radius, status);
-    REMAP_HIP_CHECK(hipGetLastError());
-    return REMAP_OK;
+    REMAP_TRY(launch(quad_prep, S.G.n_cells, kPrepBlock, stream, S.Q, s.xyz,
+                     s.nv, s.centre, area, status));
+    return launch(cell_shape, S.G.n_cells, kBlock, stream, S.G.n_cells,
+                  S.G.max_edges, clipper, s.xyz, s.nv, s.centre, s.radius,
+                  status);
 }
 
 // both sides prepared, the pyramid, the count pass and its scan: the number
@@ -2704,60 +2558,47 @@ int grid_candidates(GridSide &A, GridSide &B, const GridLayout &L, char *ws,
                     hipStream_t stream)
 {
     const MeshLayout &lay = L.m;
-    double *lat_c = reinterpret_cast<double *>(ws + lay.lat_c);
-    double *lon_c = reinterpret_cast<double *>(ws + lay.lon_c);
-    int64_t *back = reinterpret_cast<int64_t *>(ws + lay.back);
-    int32_t *status_ab = reinterpret_cast<int32_t *>(back + 2);
+    double *lat_c = at<double>(ws, lay.lat_c);
+    double *lon_c = at<double>(ws, lay.lon_c);
+    int64_t *back = at<int64_t>(ws, lay.back);
+    int32_t *status_ab = as<int32_t>(back + 2);
     void *temp0 = ws + lay.temp0;
     A.G.lat_c = B.G.lat_c = lat_c;
     A.G.lon_c = B.G.lon_c = lon_c;
     REMAP_HIP_CHECK(hipMemsetAsync(back, 0, kBackWords * 8, stream));
-    hipLaunchKernelGGL(bucket_edges, dim3(1), dim3(kBlock), 0, stream,
-                       int64_t(1), int64_t(1), lat_c, lon_c);
-    REMAP_HIP_CHECK(hipGetLastError());
+    REMAP_TRY(launch(bucket_edges, 1, kBlock, stream, 1, 1, lat_c, lon_c));
     for (int k = 0; k < 2; ++k) {
         const GridSide &S = k ? A : B;
         const Side s = side_at(ws, k ? lay.a : lay.b);
         double *area = k ? a_area : b_area;
         int32_t *status = k ? status_ab : status_ab + 1;
-        const int rc = S.is_grid
-            ? prep_grid_side(S, k == 0, s, area, status, stream)
-            : prep_side(S.G, k == 0, s, area, temp0, lay.temp0_bytes,
-                        back + k, status, stream);
-        if (rc != REMAP_OK)
-            return rc;
+        REMAP_TRY(S.is_grid
+                      ? prep_grid_side(S, k == 0, s, area, status, stream)
+                      : prep_side(S.G, k == 0, s, area, temp0,
+                                  lay.temp0_bytes, back + k, status, stream));
     }
     const Side si = side_at(ws, L.index == &A ? lay.a : lay.b);
     const Side sw = side_at(ws, L.walker == &A ? lay.a : lay.b);
     const GridGeom &Q = L.index->Q;
-    int64_t *first = reinterpret_cast<int64_t *>(ws + L.first);
+    int64_t *first = at<int64_t>(ws, L.first);
     const Pyramid P = {L.levels, Q.ny, Q.nx, si.centre, si.radius,
-                       reinterpret_cast<double *>(ws + L.nodes), first};
+                       at<double>(ws, L.nodes), first};
     *pyramid = P;
-    hipLaunchKernelGGL(pyramid_table, dim3(1), dim3(kWave), 0, stream, Q.ny,
-                       Q.nx, L.levels, first);
-    REMAP_HIP_CHECK(hipGetLastError());
-    for (int l = 1; l < L.levels; ++l) {
-        const int64_t n = level_dim(Q.ny, l) * level_dim(Q.nx, l);
-        hipLaunchKernelGGL(pyramid_level, dim3(blocks(n, kBlock)),
-                           dim3(kBlock), 0, stream, P, l);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
+    REMAP_TRY(launch(pyramid_table, 1, kWave, stream, Q.ny, Q.nx, L.levels,
+                     first));
+    for (int l = 1; l < L.levels; ++l)
+        REMAP_TRY(launch(pyramid_level,
+                         level_dim(Q.ny, l) * level_dim(Q.nx, l), kBlock,
+                         stream, P, l));
     const int64_t n_w = L.walker->G.n_cells;
     if (n_w > 0) {
-        hipLaunchKernelGGL(pyramid_walk<false>, dim3(blocks(n_w, kWalkBlock)),
-                           dim3(kWalkBlock), 0, stream, P, n_w, sw.centre,
-                           sw.radius, sw.nv, L.walker == &A, sw.counts,
-                           nullptr, int64_t(0), nullptr, status_ab);
-        REMAP_HIP_CHECK(hipGetLastError());
-        size_t tb = lay.temp0_bytes;
-        REMAP_HIP_CHECK((rocprim::exclusive_scan(
-            temp0, tb, static_cast<const uint64_t *>(sw.counts), sw.offs,
-            uint64_t(0), static_cast<size_t>(n_w), rocprim::plus<uint64_t>(),
-            stream)));
-        hipLaunchKernelGGL(scan_total, dim3(1), dim3(kWave), 0, stream, n_w,
-                           sw.counts, sw.offs, back + 3);
-        REMAP_HIP_CHECK(hipGetLastError());
+        REMAP_TRY(launch(pyramid_walk<false>, n_w, kWalkBlock, stream, P, n_w,
+                         sw.centre, sw.radius, sw.nv, L.walker == &A,
+                         sw.counts, nullptr, 0, nullptr, status_ab));
+        REMAP_TRY(exclusive_scan(temp0, lay.temp0_bytes, sw.counts, sw.offs,
+                                 n_w, stream));
+        REMAP_TRY(launch(scan_total, 1, kWave, stream, n_w, sw.counts, sw.offs,
+                         back + 3));
     }
     return REMAP_OK;
 }
@@ -2765,11 +2606,8 @@ int grid_candidates(GridSide &A, GridSide &B, const GridLayout &L, char *ws,
 int check_sides(const remap_overlap_side *a, const remap_overlap_side *b,
                 GridSide *A, GridSide *B)
 {
-    int rc = check_side(a, "a", A);
-    if (rc == REMAP_OK)
-        rc = check_side(b, "b", B);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(check_side(a, "a", A));
+    REMAP_TRY(check_side(b, "b", B));
     if (!A->is_grid && !B->is_grid)
         return fail(REMAP_ERR_ARG, "remap_overlap_grids: neither side is a "
                                    "grid (two meshes: remap_overlap_meshes)");
@@ -2781,52 +2619,38 @@ int grids_sizes(const remap_overlap_side *side_a,
                 size_t *bytes_out, hipStream_t stream)
 {
     GridSide A, B;
-    int rc = check_sides(side_a, side_b, &A, &B);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(check_sides(side_a, side_b, &A, &B));
     if (!n_pairs_out || !bytes_out)
         return fail(REMAP_ERR_ARG, "remap_overlap_grids_sizes: NULL output");
     GridLayout L;
-    rc = grid_fixed_layout(A, B, &L);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(grid_fixed_layout(A, B, &L));
     // the count pass needs both sides prepared: in memory of its own, with
     // the two area arrays behind it
-    const size_t na = static_cast<size_t>(A.G.n_cells > 0 ? A.G.n_cells : 1);
-    const size_t nb = static_cast<size_t>(B.G.n_cells > 0 ? B.G.n_cells : 1);
     size_t bytes = L.m.fixed;
-    const size_t at_a = take(&bytes, na * 8), at_b = take(&bytes, nb * 8);
+    const size_t at_a = take(&bytes, at_least_one(A.G.n_cells) * 8);
+    const size_t at_b = take(&bytes, at_least_one(B.G.n_cells) * 8);
     char *buf = nullptr;
     REMAP_HIP_CHECK(hipMalloc(&buf, bytes));
     Pyramid P;
     int64_t got[2] = {0, 0};
-    rc = grid_candidates(A, B, L, buf, reinterpret_cast<double *>(buf + at_a),
-                         reinterpret_cast<double *>(buf + at_b), &P, stream);
-    hipError_t err = hipSuccess;
-    if (rc == REMAP_OK) {
-        err = hipMemcpyAsync(got, buf + L.m.back + 16, sizeof(got),
-                             hipMemcpyDeviceToHost, stream);
-        if (err == hipSuccess)
-            err = hipStreamSynchronize(stream);
-    } else {
+    int rc = grid_candidates(A, B, L, buf, at<double>(buf, at_a),
+                             at<double>(buf, at_b), &P, stream);
+    if (rc == REMAP_OK)
+        rc = read_back(got, buf + L.m.back + 16, sizeof(got), stream);
+    else
         (void)hipStreamSynchronize(stream);
-    }
     const hipError_t freed = hipFree(buf);
-    if (rc != REMAP_OK)
-        return rc;
-    REMAP_HIP_CHECK(err);
+    REMAP_TRY(rc);
     REMAP_HIP_CHECK(freed);
     const int err_a = static_cast<int>(got[0] & 0xffffffff);
     const int err_b = static_cast<int>((got[0] >> 32) & 0xffffffff);
     if (err_a || err_b)
-        return grids_fail(err_a, err_b, 0);
+        return route_fail(kGrids, err_a, err_b, 0);
     if (got[1] >= (int64_t(1) << 32) - 1)
         return fail(REMAP_ERR_UNSUPPORTED,
                     "remap_overlap_grids: %lld candidate pairs",
                     static_cast<long long>(got[1]));
-    rc = mesh_var_layout(0, 0, got[1], &L.m);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(mesh_var_layout(0, 0, got[1], &L.m));
     *n_pairs_out = got[1];
     *bytes_out = L.m.total;
     return REMAP_OK;
@@ -2834,27 +2658,14 @@ int grids_sizes(const remap_overlap_side *side_a,
 
 int grids(const remap_overlap_side *side_a, const remap_overlap_side *side_b,
           int32_t dst_is_b, int64_t n_pairs, void *workspace,
-          size_t workspace_bytes, int32_t *dst_out, int32_t *src_out,
-          double *area_out, double *frac_b_out, double *a_area_out,
-          double *b_area_out, int64_t *n_entries_out, hipStream_t stream)
+          size_t workspace_bytes, const Outputs &out, hipStream_t stream)
 {
     GridSide A, B;
-    int rc = check_sides(side_a, side_b, &A, &B);
-    if (rc != REMAP_OK)
-        return rc;
-    if (n_pairs < 0 || n_pairs >= (int64_t(1) << 32) - 1)
-        return fail(REMAP_ERR_UNSUPPORTED,
-                    "remap_overlap_grids: %lld candidate pairs",
-                    static_cast<long long>(n_pairs));
-    if (!frac_b_out || !a_area_out || !b_area_out || !n_entries_out ||
-        (n_pairs > 0 && (!dst_out || !src_out || !area_out)))
-        return fail(REMAP_ERR_ARG, "remap_overlap_grids: NULL output");
+    REMAP_TRY(check_sides(side_a, side_b, &A, &B));
+    REMAP_TRY(check_call(kGrids.who, n_pairs, out));
     GridLayout L;
-    rc = grid_fixed_layout(A, B, &L);
-    if (rc == REMAP_OK)
-        rc = mesh_var_layout(0, 0, n_pairs, &L.m);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(grid_fixed_layout(A, B, &L));
+    REMAP_TRY(mesh_var_layout(0, 0, n_pairs, &L.m));
     const MeshLayout &lay = L.m;
     if (!workspace || workspace_bytes < lay.total)
         return fail(REMAP_ERR_WORKSPACE,
@@ -2862,57 +2673,36 @@ int grids(const remap_overlap_side *side_a, const remap_overlap_side *side_b,
                     workspace_bytes, lay.total);
     char *ws = static_cast<char *>(workspace);
     Pyramid P;
-    rc = grid_candidates(A, B, L, ws, a_area_out, b_area_out, &P, stream);
-    if (rc != REMAP_OK)
-        return rc;
-    int64_t *back = reinterpret_cast<int64_t *>(ws + lay.back);
+    REMAP_TRY(grid_candidates(A, B, L, ws, out.a_area, out.b_area, &P,
+                              stream));
+    int64_t *back = at<int64_t>(ws, lay.back);
     const Side sa = side_at(ws, lay.a), sb = side_at(ws, lay.b);
     const Side sw = L.walker == &A ? sa : sb;
-    const PairWork work = {reinterpret_cast<uint64_t *>(ws + lay.cand),
-                           reinterpret_cast<uint64_t *>(ws + lay.cand_s),
-                           reinterpret_cast<double *>(ws + lay.parea),
-                           reinterpret_cast<double *>(ws + lay.area_c),
-                           reinterpret_cast<uint32_t *>(ws + lay.head),
-                           reinterpret_cast<uint32_t *>(ws + lay.slot),
-                           reinterpret_cast<uint64_t *>(back + 3),
-                           back + 4,
-                           reinterpret_cast<int32_t *>(back + 5),
-                           ws + lay.temp,
-                           lay.temp_bytes};
+    const PairWork work = pair_work(ws, lay.pairs, back + 3, ws + lay.temp,
+                                    lay.temp_bytes);
     const bool dst_is_a = dst_is_b == 0;
     const int64_t n_w = L.walker->G.n_cells;
-    if (n_w > 0) {
-        // (with n_pairs 0 it only checks that there are none)
-        hipLaunchKernelGGL(pyramid_walk<true>, dim3(blocks(n_w, kWalkBlock)),
-                           dim3(kWalkBlock), 0, stream, P, n_w, sw.centre,
-                           sw.radius, sw.nv, L.walker == &A, sw.counts,
-                           sw.offs, n_pairs, work.cand, work.status);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
-    if (n_pairs > 0) {
-        rc = clip_and_keep(A.G, sa, B.G, sb, dst_is_a, n_pairs, work,
-                           a_area_out, b_area_out, stream);
-        if (rc != REMAP_OK)
-            return rc;
-    }
+    // (with n_pairs 0 it only checks that there are none)
+    REMAP_TRY(launch(pyramid_walk<true>, n_w, kWalkBlock, stream, P, n_w,
+                     sw.centre, sw.radius, sw.nv, L.walker == &A, sw.counts,
+                     sw.offs, n_pairs, work.cand, work.status));
+    REMAP_TRY(clip_poly(A.G, sa, B.G, sb, n_pairs, work, stream));
+    REMAP_TRY(keep_pairs(n_pairs, A.G.n_cells, B.G.n_cells, dst_is_a, work,
+                         out.a_area, out.b_area, stream));
     // the one read-back: the sides' error bits, the candidates, how many
     // entries to sort, the pairs' error bits
     int64_t got[4];
-    REMAP_HIP_CHECK(hipMemcpyAsync(got, back + 2, sizeof(got),
-                                   hipMemcpyDeviceToHost, stream));
-    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+    REMAP_TRY(read_back(got, back + 2, sizeof(got), stream));
     const int err_a = static_cast<int>(got[0] & 0xffffffff);
     const int err_b = static_cast<int>((got[0] >> 32) & 0xffffffff);
     int err_p = static_cast<int>(got[3] & 0xffffffff);
     if (got[1] != n_pairs)
         err_p |= REMAP_OVERLAP_ERR_CAPACITY;
     if (err_a || err_b || err_p)
-        return grids_fail(err_a, err_b, err_p);
-    *n_entries_out = got[2];
+        return route_fail(kGrids, err_a, err_b, err_p);
+    *out.n_entries = got[2];
     return sort_and_sum(dst_is_a ? A.G.n_cells : B.G.n_cells, got[2], n_pairs,
-                        work, dst_out, src_out, area_out,
-                        dst_is_a ? a_area_out : b_area_out, frac_b_out,
-                        stream);
+                        work, out, dst_is_a ? out.a_area : out.b_area, stream);
 }
 
 }  // namespace
@@ -2929,6 +2719,7 @@ int remap_overlap_latlon_sizes(const remap_overlap_geom *geom,
                                 static_cast<hipStream_t>(stream));
 }
 
+// (the mesh is side a, the grid side b)
 int remap_overlap_latlon(const remap_overlap_geom *geom, int32_t dst_is_mesh,
                          int64_t n_pairs, void *workspace,
                          size_t workspace_bytes, int32_t *dst_out,
@@ -2938,9 +2729,10 @@ int remap_overlap_latlon(const remap_overlap_geom *geom, int32_t dst_is_mesh,
                          void *stream)
 {
     return remap::overlap(geom, dst_is_mesh, n_pairs, workspace,
-                          workspace_bytes, dst_out, src_out, area_out,
-                          frac_b_out, mesh_area_out, grid_area_out,
-                          n_entries_out, static_cast<hipStream_t>(stream));
+                          workspace_bytes,
+                          {dst_out, src_out, area_out, frac_b_out,
+                           mesh_area_out, grid_area_out, n_entries_out},
+                          static_cast<hipStream_t>(stream));
 }
 
 int remap_overlap_meshes_sizes(const remap_overlap_mesh *a,
@@ -2948,8 +2740,8 @@ int remap_overlap_meshes_sizes(const remap_overlap_mesh *a,
                                int64_t *n_pairs_out,
                                size_t *workspace_bytes_out, void *stream)
 {
-    return remap::meshes_sizes("remap_overlap_meshes", a, b, counter,
-                               n_pairs_out, workspace_bytes_out,
+    return remap::meshes_sizes(remap::kMeshes, a, b, counter, n_pairs_out,
+                               workspace_bytes_out,
                                static_cast<hipStream_t>(stream));
 }
 
@@ -2963,8 +2755,8 @@ int remap_overlap_meshes(const remap_overlap_mesh *a,
                          void *stream)
 {
     return remap::meshes(a, b, dst_is_b, n_pairs, workspace, workspace_bytes,
-                         dst_out, src_out, area_out, frac_b_out, a_area_out,
-                         b_area_out, n_entries_out,
+                         {dst_out, src_out, area_out, frac_b_out, a_area_out,
+                          b_area_out, n_entries_out},
                          static_cast<hipStream_t>(stream));
 }
 
@@ -2988,8 +2780,8 @@ int remap_overlap_pieces(const struct remap_overlap_pieces *a,
                          void *stream)
 {
     return remap::pieces(a, b, dst_is_b, n_pairs, workspace, workspace_bytes,
-                         dst_out, src_out, area_out, frac_b_out, a_area_out,
-                         b_area_out, n_entries_out,
+                         {dst_out, src_out, area_out, frac_b_out, a_area_out,
+                          b_area_out, n_entries_out},
                          static_cast<hipStream_t>(stream), nullptr);
 }
 
@@ -3004,10 +2796,10 @@ int remap_overlap_pieces_timed(const struct remap_overlap_pieces *a,
                                void *stream)
 {
     return remap::pieces_timed(a, b, dst_is_b, n_pairs, workspace,
-                               workspace_bytes, dst_out, src_out, area_out,
-                               frac_b_out, a_area_out, b_area_out,
-                               n_entries_out, phase_ms_out,
-                               static_cast<hipStream_t>(stream));
+                               workspace_bytes,
+                               {dst_out, src_out, area_out, frac_b_out,
+                                a_area_out, b_area_out, n_entries_out},
+                               phase_ms_out, static_cast<hipStream_t>(stream));
 }
 
 int remap_overlap_grids_sizes(const remap_overlap_side *a,
@@ -3029,8 +2821,8 @@ int remap_overlap_grids(const remap_overlap_side *a,
                         void *stream)
 {
     return remap::grids(a, b, dst_is_b, n_pairs, workspace, workspace_bytes,
-                        dst_out, src_out, area_out, frac_b_out, a_area_out,
-                        b_area_out, n_entries_out,
+                        {dst_out, src_out, area_out, frac_b_out, a_area_out,
+                         b_area_out, n_entries_out},
                         static_cast<hipStream_t>(stream));
 }
 
