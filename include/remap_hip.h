@@ -55,7 +55,7 @@
 extern "C" {
 #endif
 
-#define REMAP_ABI_VERSION 30
+#define REMAP_ABI_VERSION 31
 
 /* The library is built with -fvisibility=hidden: the entry points declared
  * here, and nothing else, are its dynamic symbols. */
@@ -1480,6 +1480,126 @@ int remap_column_fractions(int64_t n_entries, int64_t n_cols,
                            int32_t clamp, double *out, int64_t *bad_out,
                            void *workspace, size_t workspace_bytes,
                            void *stream);
+
+/*
+ * ---------------------------------------------------------------------------
+ * Second-order conservative maps (conserve2nd) from the first-order overlaps
+ * ---------------------------------------------------------------------------
+ * Everything on the unit sphere, cells great-circle polygons as in the
+ * overlap calls.  The first moment M(P) = integral over P of r dA of a
+ * polygon with corners p_0 .. p_n-1 (counter-clockwise, closed cyclically) is
+ *     M = 1/2 sum_k theta_k n_k,   n_k = (p_k x p_k+1) / |p_k x p_k+1|,
+ *     theta_k = atan2(|p_k x p_k+1|, p_k . p_k+1),
+ * added in ascending k, p_k x p_k+1 evaluated as p_k x (p_k+1 - p_k); an
+ * edge with p_k == p_k+1 adds nothing.  A source cell j has area A_j, moment
+ * M_j, mean position M_j / A_j (NOT normalised) and centroid M_j / |M_j|.
+ * The map's triples are (i, j, A_ij / A_i) for every first-order entry and,
+ * where cell j has a gradient, (i, k, G_jk . d_ij) for k = j and j's edge
+ * neighbours, d_ij = (M_ij - A_ij M_j / A_j) / A_i.  The G of a cell sum to
+ * 0, so the rows keep their first-order sums; sum_i M_ij = M_j, so
+ * sum_i A_i S_ik = A_k for every fully covered source cell.  This is ESMF's
+ * conserve2nd in structure, not in bytes.  All calls: fp64, on the caller's
+ * stream, no floating-point atomics (two calls give the same bytes).
+ *
+ * remap_cell_moments: moment_out (n_cells x 3) of cells in SCRIP layout, the
+ * arguments, the ring (consecutive equal corners and closing copies dropped)
+ * and the errors of remap_cell_areas.  A clockwise ring (its moment points
+ * away from the sum of its corners) is negated at the end; fewer than 3
+ * distinct corners: 0.  status: two int32 on the device; the call WAITS.
+ *
+ * remap_overlap_moments: moment_out (n_entries x 3), M_ij of source cell
+ * src[e] n destination cell dst[e] (0-based, as the overlap calls return
+ * them), both sides in SCRIP layout (width <= REMAP_OVERLAP_MAX_EDGES each,
+ * REMAP_ERR_UNSUPPORTED otherwise).  The source cell is clipped by the
+ * destination cell's edges in the gnomonic plane of the source cell's centre
+ * (the normalised sum of its corners): the ring loading and the edge clip of
+ * remap_overlap_meshes; the clipped corners are lifted back to unit vectors.
+ * A clip that leaves fewer than 3 corners gives area[e] * src_moment[j] /
+ * src_area[j] (no correction).  Destination cells must be convex
+ * (REMAP_OVERLAP_ERR_CONVEX) and every corner of a pair within acos(0.1) of
+ * the source cell's centre (REMAP_OVERLAP_ERR_HEMISPHERE): both
+ * REMAP_ERR_UNSUPPORTED.  An entry outside its side, a count outside
+ * [0, width]: REMAP_ERR_ARG.  workspace: remap_overlap_moments_workspace()
+ * bytes (the prepared rings).  status: two int32 on the device; the call
+ * WAITS twice (the source's counts, then everything else).
+ *
+ * remap_gradient_stencils: nbr (n_cells x width, -1 = no cell across edge
+ * (corner t, corner t + 1)), count = nEdgesOnCell, centroid (n_cells x 3,
+ * unit).  A cell has a gradient (has_out = 1) when count >= 3, every edge has
+ * a neighbour and the polygon N of the neighbours' centroids, in edge order,
+ * has an area A_N != 0.  With nu_t / theta_t the unit normal / the arc
+ * between neighbours t and t + 1 (cyclic) and e_t = -1/2 theta_t nu_t / A_N
+ * (A_N SIGNED: a clockwise N gives what its reversal gives), coef_out
+ * (n_cells x (width + 1) x 3) holds at slot 1 + t  e_t-1 + e_t  and at slot 0
+ * -2 sum_t e_t, each made tangential: G - (G . c_j) c_j.  A cell without a
+ * gradient has all 0.  width <= REMAP_OVERLAP_MAX_EDGES.  status as above;
+ * the call WAITS.  REMAP_ERR_ARG: a count outside [0, width], a neighbour >=
+ * n_cells.
+ *
+ * remap_conserve2nd_sizes: *capacity_out = the number of triples (1 per
+ * entry, + 1 + count[j] where has[j]), read back (the call WAITS), and the
+ * workspace bytes of the assembly.  counters: two int64 on the device.
+ *
+ * remap_conserve2nd_assemble: triples in emission order (entry order; the
+ * first-order term, the cell itself, the neighbours in edge order), the dot
+ * product as (gx*dx + gy*dy) + gz*dz; keys row << 32 | col with the emission
+ * position as value, stable radix sort, equal keys added in emission order,
+ * zero sums kept.  row_out / col_out (0-based) / s_out hold `capacity`
+ * slots, the first *n_out (host; the one read-back, the call WAITS) are the
+ * map sorted by (row, col), unique.  REMAP_ERR_ARG: an index outside its
+ * side, a capacity that is not remap_conserve2nd_sizes' for these arrays.
+ * ---------------------------------------------------------------------------
+ */
+REMAP_API
+int remap_cell_moments(int64_t n_cells, int32_t width,
+                       const double *corner_lat, const double *corner_lon,
+                       const int32_t *count, double *moment_out,
+                       int32_t *status, void *stream);
+
+REMAP_API
+int remap_overlap_moments_workspace(int64_t n_src, int32_t width_src,
+                                    int64_t n_dst, int32_t width_dst,
+                                    size_t *bytes_out);
+
+REMAP_API
+int remap_overlap_moments(int64_t n_entries, const int32_t *dst,
+                          const int32_t *src, const double *area,
+                          int64_t n_src, int32_t width_src,
+                          const double *src_lat, const double *src_lon,
+                          const int32_t *src_count, const double *src_area,
+                          const double *src_moment, int64_t n_dst,
+                          int32_t width_dst, const double *dst_lat,
+                          const double *dst_lon, const int32_t *dst_count,
+                          double *moment_out, int32_t *status,
+                          void *workspace, size_t workspace_bytes,
+                          void *stream);
+
+REMAP_API
+int remap_gradient_stencils(int64_t n_cells, int32_t width,
+                            const int32_t *nbr, const int32_t *count,
+                            const double *centroid, double *coef_out,
+                            int32_t *has_out, int32_t *status, void *stream);
+
+REMAP_API
+int remap_conserve2nd_sizes(int64_t n_entries, const int32_t *src,
+                            int64_t n_src, int32_t width,
+                            const int32_t *count, const int32_t *has,
+                            int64_t *counters, int64_t *capacity_out,
+                            size_t *workspace_bytes_out, void *stream);
+
+REMAP_API
+int remap_conserve2nd_assemble(int64_t n_entries, const int32_t *dst,
+                               const int32_t *src, const double *area,
+                               const double *moment, int64_t n_src,
+                               int32_t width, const int32_t *nbr,
+                               const int32_t *count, const double *coef,
+                               const int32_t *has, const double *src_area,
+                               const double *src_moment, int64_t n_dst,
+                               const double *dst_area, int64_t capacity,
+                               void *workspace, size_t workspace_bytes,
+                               int32_t *row_out, int32_t *col_out,
+                               double *s_out, int64_t *counters,
+                               int64_t *n_out, void *stream);
 
 #ifdef __cplusplus
 }

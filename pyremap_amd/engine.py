@@ -52,7 +52,7 @@ CELL_MAX_RUN = 4
 DTYPE_F64 = 0
 DTYPE_F32 = 1
 
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 #: readable pad entries kept behind col/val (remap_csr.csr_pad)
 CSR_PAD = 8
@@ -88,6 +88,9 @@ EXPORTS = (
     'remap_expand_cells',
     'remap_cell_areas', 'remap_column_fractions_workspace',
     'remap_column_fractions',
+    'remap_cell_moments', 'remap_overlap_moments_workspace',
+    'remap_overlap_moments', 'remap_gradient_stencils',
+    'remap_conserve2nd_sizes', 'remap_conserve2nd_assemble',
 )
 
 
@@ -549,6 +552,36 @@ def load_library():
         ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    lib.remap_cell_moments.restype = ctypes.c_int
+    lib.remap_cell_moments.argtypes = lib.remap_cell_areas.argtypes
+    lib.remap_overlap_moments_workspace.restype = ctypes.c_int
+    lib.remap_overlap_moments_workspace.argtypes = [
+        ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+        ctypes.POINTER(ctypes.c_size_t)]
+    lib.remap_overlap_moments.restype = ctypes.c_int
+    lib.remap_overlap_moments.argtypes = [ctypes.c_int64] + \
+        [ctypes.c_void_p] * 3 + \
+        [ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 5 + \
+        [ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 3 + \
+        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+         ctypes.c_void_p]
+    lib.remap_gradient_stencils.restype = ctypes.c_int
+    lib.remap_gradient_stencils.argtypes = [
+        ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 7
+    lib.remap_conserve2nd_sizes.restype = ctypes.c_int
+    lib.remap_conserve2nd_sizes.argtypes = [
+        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_size_t),
+        ctypes.c_void_p]
+    lib.remap_conserve2nd_assemble.restype = ctypes.c_int
+    lib.remap_conserve2nd_assemble.argtypes = [ctypes.c_int64] + \
+        [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_int32] + \
+        [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.c_void_p,
+                                 ctypes.c_int64, ctypes.c_void_p,
+                                 ctypes.c_size_t] + \
+        [ctypes.c_void_p] * 4 + [ctypes.POINTER(ctypes.c_int64),
+                                 ctypes.c_void_p]
     if lib.remap_abi_version() != ABI_VERSION:
         raise EngineError(
             f'{path} has ABI {lib.remap_abi_version()}, expected '
@@ -2937,3 +2970,240 @@ def column_fractions(col, value, n_cols, denom=None, clamp=False,
         raise ValueError(f'{n_bad} entries name a column outside '
                          f'[0, {n_cols})')
     return out
+
+
+# ---------------------------------------------------------------------------
+# second-order conservative maps: moments, gradient stencils, the assembly
+# ---------------------------------------------------------------------------
+
+#: REMAP_OVERLAP_MAX_EDGES
+OVERLAP_MAX_EDGES = 10
+
+
+def _scrip_cells(torch, name, corner_lat, corner_lon, count, dev=None):
+    """``(lat, lon, count)`` of one side in SCRIP layout, checked the way
+    :func:`cell_areas` checks its own and made fp64 / int32, contiguous."""
+    if not torch.is_tensor(corner_lat) or not corner_lat.is_cuda or \
+            corner_lat.dim() != 2 or corner_lat.shape[1] < 1 or \
+            (dev is not None and corner_lat.device != dev):
+        raise ValueError(
+            f'{name}corner_lat: expected an (n, width) tensor on '
+            f'{"a HIP device" if dev is None else dev}, width >= 1')
+    dev = corner_lat.device
+    n, width = corner_lat.shape
+    if not torch.is_tensor(corner_lon) or corner_lon.device != dev or \
+            tuple(corner_lon.shape) != (n, width):
+        raise ValueError(f'{name}corner_lon: expected a tensor of shape '
+                         f'{(n, width)} on {dev}')
+    if not torch.is_tensor(count) or count.device != dev or \
+            tuple(count.shape) != (n,) or count.dtype.is_floating_point:
+        raise ValueError(f'{name}count: expected {n} integers on {dev}')
+    return (corner_lat.to(torch.float64).contiguous(),
+            corner_lon.to(torch.float64).contiguous(),
+            count.to(torch.int32).contiguous())
+
+
+def _f64(torch, name, t, shape, dev):
+    if not torch.is_tensor(t) or t.device != dev or \
+            tuple(t.shape) != shape or not t.dtype.is_floating_point:
+        raise ValueError(f'{name}: expected a floating-point tensor of shape '
+                         f'{shape} on {dev}')
+    return t.to(torch.float64).contiguous()
+
+
+def _i32(torch, name, t, shape, dev):
+    if not torch.is_tensor(t) or t.device != dev or \
+            tuple(t.shape) != shape or t.dtype.is_floating_point:
+        raise ValueError(f'{name}: expected integers of shape {shape} on '
+                         f'{dev}')
+    return t.to(torch.int32).contiguous()
+
+
+def _checked(lib, rc, what):
+    if rc == -1:     # REMAP_ERR_ARG
+        raise ValueError(lib.remap_last_error().decode('utf-8', 'replace'))
+    _check(rc, what)
+
+
+def cell_moments(corner_lat, corner_lon, count, timing=None):
+    """
+    The first moment ``M = integral of r dA`` (unit sphere) of every cell
+    given in SCRIP layout, through ``remap_cell_moments``
+    (``include/remap_hip.h`` has the definition;
+    :func:`pyremap_amd.weights.cell_moments` is the same statement in
+    numpy): the arguments and the errors of :func:`cell_areas`.  Returns a
+    new ``(n, 3)`` fp64 tensor.  Runs on the current stream and waits for
+    it.  ``timing``: a dict that receives the GPU ``ms`` of the call.
+    """
+    torch = require_gpu()
+    lib = load_library()
+    corner_lat, corner_lon, count = _scrip_cells(torch, '', corner_lat,
+                                                 corner_lon, count)
+    dev = corner_lat.device
+    n, width = corner_lat.shape
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        moment = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        status = torch.zeros(2, dtype=torch.int32, device=dev)
+        with _gpu_ms(torch, timing):
+            _checked(lib, lib.remap_cell_moments(
+                n, width, _ptr(corner_lat), _ptr(corner_lon), _ptr(count),
+                _ptr(moment), _ptr(status), stream), 'remap_cell_moments')
+    return moment
+
+
+def overlap_moments(dst, src, area, src_cells, src_area, src_moment,
+                    dst_cells, timing=None):
+    """
+    ``M_ij``, the first moment of (source cell ``src[e]`` n destination cell
+    ``dst[e]``) for every first-order entry, through
+    ``remap_overlap_moments`` (``include/remap_hip.h``): ``dst`` / ``src``
+    0-based integers and ``area`` (``A_ij``) as an ``overlap_*`` call returns
+    them, ``src_cells`` / ``dst_cells`` the two sides as ``(corner_lat,
+    corner_lon, count)`` in SCRIP layout (radians, width at most
+    ``OVERLAP_MAX_EDGES``: an :class:`EngineError` otherwise), ``src_area``
+    ``(n_src,)`` and ``src_moment`` ``(n_src, 3)``; everything on one HIP
+    device.  An entry whose clip leaves fewer than 3 corners gets ``A_ij *
+    M_j / A_j``.  Returns a new ``(n_entries, 3)`` fp64 tensor.  Runs on the
+    current stream and waits for it.  ``ValueError``: a wrong shape, dtype
+    or device, an entry outside its side, a count outside ``[0, width]``.
+    """
+    torch = require_gpu()
+    lib = load_library()
+    s_lat, s_lon, s_count = _scrip_cells(torch, 'source ', *src_cells)
+    dev = s_lat.device
+    d_lat, d_lon, d_count = _scrip_cells(torch, 'destination ', *dst_cells,
+                                         dev=dev)
+    n_src, w_src = s_lat.shape
+    n_dst, w_dst = d_lat.shape
+    if not torch.is_tensor(area) or area.dim() != 1:
+        raise ValueError('area: expected a 1-D tensor')
+    n = area.shape[0]
+    area = _f64(torch, 'area', area, (n,), dev)
+    dst = _i32(torch, 'dst', dst, (n,), dev)
+    src = _i32(torch, 'src', src, (n,), dev)
+    src_area = _f64(torch, 'src_area', src_area, (n_src,), dev)
+    src_moment = _f64(torch, 'src_moment', src_moment, (n_src, 3), dev)
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        need = ctypes.c_size_t(0)
+        _checked(lib, lib.remap_overlap_moments_workspace(
+            n_src, w_src, n_dst, w_dst, ctypes.byref(need)),
+            'remap_overlap_moments_workspace')
+        workspace = torch.empty(max(need.value, 1), dtype=torch.uint8,
+                                device=dev)
+        moment = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        status = torch.zeros(2, dtype=torch.int32, device=dev)
+        with _gpu_ms(torch, timing):
+            _checked(lib, lib.remap_overlap_moments(
+                n, _ptr(dst), _ptr(src), _ptr(area), n_src, w_src,
+                _ptr(s_lat), _ptr(s_lon), _ptr(s_count), _ptr(src_area),
+                _ptr(src_moment), n_dst, w_dst, _ptr(d_lat), _ptr(d_lon),
+                _ptr(d_count), _ptr(moment), _ptr(status), _ptr(workspace),
+                need.value, stream), 'remap_overlap_moments')
+        del workspace
+    return moment
+
+
+def gradient_stencils(nbr, count, centroid, timing=None):
+    """
+    The gradient coefficients of every cell over its edge neighbours,
+    through ``remap_gradient_stencils`` (``include/remap_hip.h``;
+    :func:`pyremap_amd.weights.gradient_stencils` is the numpy statement):
+    ``nbr`` ``(n, width)`` integers (-1: no cell across that edge),
+    ``count`` ``(n,)`` integers and ``centroid`` ``(n, 3)`` unit vectors on
+    one HIP device, width at most ``OVERLAP_MAX_EDGES``.  Returns ``(coef
+    (n, width + 1, 3) fp64, has (n,) int32)``: slot 0 the cell itself, slot
+    ``1 + t`` neighbour ``t``; all 0 where ``has`` is 0.  Runs on the
+    current stream and waits for it.
+    """
+    torch = require_gpu()
+    lib = load_library()
+    if not torch.is_tensor(nbr) or not nbr.is_cuda or nbr.dim() != 2 or \
+            nbr.shape[1] < 1 or nbr.dtype.is_floating_point:
+        raise ValueError('nbr: expected (n, width) integers on a HIP '
+                         'device, width >= 1')
+    dev = nbr.device
+    n, width = nbr.shape
+    nbr = nbr.to(torch.int32).contiguous()
+    count = _i32(torch, 'count', count, (n,), dev)
+    centroid = _f64(torch, 'centroid', centroid, (n, 3), dev)
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        coef = torch.empty((n, width + 1, 3), dtype=torch.float64,
+                           device=dev)
+        has = torch.empty(n, dtype=torch.int32, device=dev)
+        status = torch.zeros(2, dtype=torch.int32, device=dev)
+        with _gpu_ms(torch, timing):
+            _checked(lib, lib.remap_gradient_stencils(
+                n, width, _ptr(nbr), _ptr(count), _ptr(centroid), _ptr(coef),
+                _ptr(has), _ptr(status), stream), 'remap_gradient_stencils')
+    return coef, has
+
+
+def conserve2nd_assemble(dst, src, area, moment, nbr, count, coef, has,
+                         src_area, src_moment, dst_area, timing=None):
+    """
+    The second-order map from its pieces, through
+    ``remap_conserve2nd_sizes`` / ``remap_conserve2nd_assemble``
+    (``include/remap_hip.h``; :func:`pyremap_amd.weights.second_order_entries`
+    is the numpy statement): the first-order entries ``dst`` / ``src`` /
+    ``area`` with their moments ``(n_entries, 3)``, the source's ``nbr (n_src,
+    width)``, ``count``, ``coef (n_src, width + 1, 3)`` and ``has``,
+    ``src_area``, ``src_moment (n_src, 3)`` and ``dst_area (n_dst,)``, all on
+    one HIP device.  Returns ``(row, col, S)``, new tensors (int32 0-based,
+    fp64) sorted by ``(row, col)`` and unique; zero sums are kept.  Two
+    calls give the same bytes.  Runs on the current stream and waits for it
+    twice (the triple count, the entry count).  ``timing`` receives the GPU
+    ``ms`` of the assembly call.
+    """
+    torch = require_gpu()
+    lib = load_library()
+    if not torch.is_tensor(area) or not area.is_cuda or area.dim() != 1:
+        raise ValueError('area: expected a 1-D tensor on a HIP device')
+    dev = area.device
+    n = area.shape[0]
+    if not torch.is_tensor(nbr) or nbr.dim() != 2 or nbr.shape[1] < 1:
+        raise ValueError('nbr: expected (n_src, width) integers, width >= 1')
+    n_src, width = nbr.shape
+    if not torch.is_tensor(dst_area) or dst_area.dim() != 1:
+        raise ValueError('dst_area: expected a 1-D tensor')
+    n_dst = dst_area.shape[0]
+    area = _f64(torch, 'area', area, (n,), dev)
+    dst = _i32(torch, 'dst', dst, (n,), dev)
+    src = _i32(torch, 'src', src, (n,), dev)
+    moment = _f64(torch, 'moment', moment, (n, 3), dev)
+    nbr = _i32(torch, 'nbr', nbr, (n_src, width), dev)
+    count = _i32(torch, 'count', count, (n_src,), dev)
+    coef = _f64(torch, 'coef', coef, (n_src, width + 1, 3), dev)
+    has = _i32(torch, 'has', has, (n_src,), dev)
+    src_area = _f64(torch, 'src_area', src_area, (n_src,), dev)
+    src_moment = _f64(torch, 'src_moment', src_moment, (n_src, 3), dev)
+    dst_area = _f64(torch, 'dst_area', dst_area, (n_dst,), dev)
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        counters = torch.zeros(2, dtype=torch.int64, device=dev)
+        capacity = ctypes.c_int64(0)
+        need = ctypes.c_size_t(0)
+        _checked(lib, lib.remap_conserve2nd_sizes(
+            n, _ptr(src), n_src, width, _ptr(count), _ptr(has),
+            _ptr(counters), ctypes.byref(capacity), ctypes.byref(need),
+            stream), 'remap_conserve2nd_sizes')
+        cap = capacity.value
+        workspace = torch.empty(max(need.value, 1), dtype=torch.uint8,
+                                device=dev)
+        row = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        col = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
+        S = torch.empty(max(cap, 1), dtype=torch.float64, device=dev)
+        n_out = ctypes.c_int64(0)
+        with _gpu_ms(torch, timing):
+            _checked(lib, lib.remap_conserve2nd_assemble(
+                n, _ptr(dst), _ptr(src), _ptr(area), _ptr(moment), n_src,
+                width, _ptr(nbr), _ptr(count), _ptr(coef), _ptr(has),
+                _ptr(src_area), _ptr(src_moment), n_dst, _ptr(dst_area), cap,
+                _ptr(workspace), need.value, _ptr(row), _ptr(col), _ptr(S),
+                _ptr(counters), ctypes.byref(n_out), stream),
+                'remap_conserve2nd_assemble')
+        del workspace
+    k = n_out.value
+    return row[:k], col[:k], S[:k]

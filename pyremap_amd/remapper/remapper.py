@@ -183,6 +183,13 @@ class Remapper:
         destination that has cells; the file records the two values.
         ``bilinear`` and ``neareststod`` maps do not depend on destination
         corners and stay as they are, as in the reference.
+        ``conserve2nd`` is the second-order conservative map from an MPAS
+        cell mesh (given by its mesh file) to a lat-lon grid, another MPAS
+        cell mesh or a 2-D grid with its corners: the first-order overlaps
+        plus a gradient of the source over each cell's edge neighbours,
+        moments, stencils and assembly on the GPU
+        (:func:`pyremap_amd.weights.conserve2nd`); it is not smoothed
+        (``expand_dist`` / ``expand_factor`` raise).
         """
         from pyremap_amd.remapper.setup import _setup_remapper
         if self.map_tool != 'analytic':
@@ -199,7 +206,9 @@ class Remapper:
                 "cell centres) to anything, and conserve maps with an MPAS "
                 "edge or vertex mesh (its mesh file) or a projection grid "
                 "on either side; expand_dist / expand_factor smooth the "
-                "conserve maps")
+                "conserve maps; conserve2nd maps from an MPAS cell mesh (its "
+                "mesh file) to a lat-lon grid, an MPAS cell mesh or a 2-D "
+                "lat-lon grid")
         _setup_remapper(self)
         from pyremap_amd.weights import write_weights
         if logger is not None:

@@ -18,7 +18,8 @@ from pyremap_amd.descriptor import (
 
 _TOOL_PREFIX = {'esmf': 'esmf', 'moab': 'mbtr', 'analytic': 'analytic'}
 _METHOD_SUFFIX = {'conserve': 'aave', 'bilinear': 'bilin',
-                  'neareststod': 'neareststod'}
+                  'neareststod': 'neareststod',
+                  'conserve2nd': 'conserve2nd'}
 
 
 def _setup_remapper(remapper):

@@ -1194,6 +1194,14 @@ def conserve_mesh_latlon(mesh_descriptor, grid_descriptor, mesh_is_src=True,
     ``frac_b = 0``.  The overlaps come from the GPU
     (:func:`pyremap_amd.engine.overlap_latlon`).
     """
+    return _conserve_mapping(*_overlaps_mesh_latlon(
+        mesh_descriptor, grid_descriptor, mesh_is_src, device, timing))
+
+
+def _overlaps_mesh_latlon(mesh_descriptor, grid_descriptor, mesh_is_src,
+                          device, timing):
+    """The arguments of :func:`_conserve_mapping` for
+    :func:`conserve_mesh_latlon`: the overlap call's answer and the sizes."""
     from pyremap_amd import engine
     engine.require_gpu()
     voc, noc, lat_v, lon_v = mesh_polygons(mesh_descriptor)
@@ -1209,8 +1217,7 @@ def conserve_mesh_latlon(mesh_descriptor, grid_descriptor, mesh_is_src=True,
             [len(lon_e) - 1, len(lat_e) - 1])
     (n_src, src_dims), (n_dst, dst_dims) = (mesh, grid) if mesh_is_src else \
         (grid, mesh)
-    return _conserve_mapping(overlaps, mesh_is_src, n_src, n_dst, src_dims,
-                             dst_dims)
+    return overlaps, mesh_is_src, n_src, n_dst, src_dims, dst_dims
 
 
 def conserve_mesh_mesh(src_descriptor, dst_descriptor, device=None,
@@ -1224,6 +1231,13 @@ def conserve_mesh_mesh(src_descriptor, dst_descriptor, device=None,
     whose cells must be convex.  The maps of the two directions hold the
     same overlap areas, transposed.
     """
+    return _conserve_mapping(*_overlaps_mesh_mesh(
+        src_descriptor, dst_descriptor, device, timing))
+
+
+def _overlaps_mesh_mesh(src_descriptor, dst_descriptor, device, timing):
+    """The arguments of :func:`_conserve_mapping` for
+    :func:`conserve_mesh_mesh`."""
     from pyremap_amd import engine
     engine.require_gpu()
     src = mesh_polygons(src_descriptor)
@@ -1236,8 +1250,7 @@ def conserve_mesh_mesh(src_descriptor, dst_descriptor, device=None,
         [_to_device(a, device) for a in mesh_a],
         [_to_device(a, device) for a in mesh_b], dst_is_b=src_is_a,
         timing=timing)
-    return _conserve_mapping(overlaps, src_is_a, n_src, n_dst, [n_src],
-                             [n_dst])
+    return overlaps, src_is_a, n_src, n_dst, [n_src], [n_dst]
 
 
 # ---------------------------------------------------------------------------
@@ -1309,6 +1322,12 @@ def conserve_grid(src_descriptor, dst_descriptor, device=None, timing=None):
     clipped by those of the other, whose cells must be convex.  The maps of
     the two directions hold the same overlap areas, transposed.
     """
+    return _conserve_mapping(*_overlaps_grid(
+        src_descriptor, dst_descriptor, device, timing))
+
+
+def _overlaps_grid(src_descriptor, dst_descriptor, device, timing):
+    """The arguments of :func:`_conserve_mapping` for :func:`conserve_grid`."""
     from pyremap_amd import engine
     if not any(isinstance(d, LatLon2DGridDescriptor)
                for d in (src_descriptor, dst_descriptor)):
@@ -1323,8 +1342,7 @@ def conserve_grid(src_descriptor, dst_descriptor, device=None, timing=None):
         [_to_device(a, device) for a in side_a],
         [_to_device(a, device) for a in side_b], dst_is_b=src_is_a,
         timing=timing)
-    return _conserve_mapping(overlaps, src_is_a, n_src, n_dst, src_dims,
-                             dst_dims)
+    return overlaps, src_is_a, n_src, n_dst, src_dims, dst_dims
 
 
 # ---------------------------------------------------------------------------
@@ -2311,6 +2329,330 @@ def complete_mapping(m, src_descriptor, dst_descriptor, method='conserve',
     return m
 
 
+# ---------------------------------------------------------------------------
+# second-order conservative maps (conserve2nd) from an MPAS cell mesh
+# ---------------------------------------------------------------------------
+
+_CONSERVE2ND_PAIRS = (
+    'conserve2nd is served from an MPAS cell mesh given by its mesh file '
+    '(MpasCellMeshDescriptor with filename=) to a lat-lon grid '
+    '(LatLonGridDescriptor), another MPAS cell mesh given by its mesh file, '
+    'or a 2-D lat-lon grid with its corner arrays (LatLon2DGridDescriptor), '
+    'without expand_dist / expand_factor')
+
+
+def _ring_moments(v):
+    """The first moments ``(m, 3)`` of the rings ``v (m, n, 3)`` of unit
+    vectors, closed cyclically: ``1/2 sum_k theta_k n_k`` added in ascending
+    k, ``p_k x p_k+1`` evaluated as ``p_k x (p_k+1 - p_k)`` (the products are
+    of the size of the edge), an edge with ``p_k == p_k+1`` skipped -- so
+    repeated and closing corners change nothing.  A clockwise ring (its
+    moment points away from the sum of its corners) is negated at the end;
+    fewer than 3 edges of non-zero length: 0."""
+    v = np.asarray(v, dtype=np.float64)
+    m = np.zeros((v.shape[0], 3))
+    edges = np.zeros(v.shape[0], dtype=np.int64)
+    n = v.shape[1]
+    for k in range(n):
+        p, q = v[:, k], v[:, (k + 1) % n]
+        c = np.cross(p, q - p)
+        s = np.sqrt(c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1] + c[:, 2] * c[:, 2])
+        d = p[:, 0] * q[:, 0] + p[:, 1] * q[:, 1] + p[:, 2] * q[:, 2]
+        real = s > 0.0
+        with np.errstate(divide='ignore', invalid='ignore'):
+            h = 0.5 * np.arctan2(s, d) / s
+        m[real] += h[real, None] * c[real]
+        edges += real
+    m[(m * v.sum(axis=1)).sum(axis=1) < 0.0] *= -1.0
+    m[edges < 3] = 0.0
+    return m
+
+
+def polygon_moment(p):
+    """``M(P) = integral over P of r dA`` of one great-circle polygon on the
+    unit sphere, ``p (n, 3)`` its corners as unit vectors in either
+    orientation (:func:`_ring_moments`).  Exact: ``M = 1/2 sum_k theta_k
+    n_k`` with ``n_k`` the unit normal of edge k's great circle and
+    ``theta_k`` its arc."""
+    p = np.asarray(p, dtype=np.float64).reshape(-1, 3)
+    if len(p) < 3:
+        return np.zeros(3)
+    return _ring_moments(p[None])[0]
+
+
+def cell_moments(corner_lat, corner_lon, count):
+    """
+    The numpy statement of ``remap_cell_moments`` (the GPU kernel is tested
+    against it): :func:`polygon_moment` of every cell given in SCRIP layout,
+    the arguments of :func:`cell_areas`; ``(n, 3)``.  Slots beyond
+    ``count[i]`` are read as copies of the last valid corner, which add
+    nothing.
+    """
+    corner_lat = np.asarray(corner_lat, dtype=np.float64)
+    corner_lon = np.asarray(corner_lon, dtype=np.float64)
+    if corner_lat.ndim != 2 or corner_lat.shape != corner_lon.shape:
+        raise ValueError(
+            f'corners of shapes {corner_lat.shape} and {corner_lon.shape}: '
+            f'expected two (n, width) arrays')
+    n, width = corner_lat.shape
+    count = np.asarray(count, dtype=np.int64)
+    if count.shape != (n,):
+        raise ValueError(f'count of shape {count.shape}: expected one value '
+                         f'for each of the {n} cells')
+    if n and (count.min() < 0 or count.max() > width):
+        raise ValueError(f'count outside [0, {width}]')
+    if n == 0 or width < 3:
+        return np.zeros((n, 3))
+    k = np.minimum(np.arange(width)[None, :],
+                   np.maximum(count, 1)[:, None] - 1)
+    v = _unit_poles(np.take_along_axis(corner_lat, k, axis=1),
+                    np.take_along_axis(corner_lon, k, axis=1))
+    return np.where((count >= 3)[:, None], _ring_moments(v), 0.0)
+
+
+def cell_neighbours(voc, noc):
+    """
+    The cell across every edge of every cell: ``nbr (n, width)`` int32,
+    0-based, ``nbr[j, k]`` the cell that shares the edge (corner k, corner
+    k + 1) of ``verticesOnCell`` row j (cyclic within ``nEdgesOnCell[j]``),
+    -1 where no cell does (a coast, the rim of a regional mesh) and in the
+    slots beyond ``noc[j]``.  Found by matching the edge keys (min vertex,
+    max vertex); ``cellsOnCell`` is not needed.
+    """
+    voc = np.asarray(voc, dtype=np.int64)
+    noc = np.asarray(noc, dtype=np.int64)
+    n, width = voc.shape
+    k = np.arange(width)[None, :]
+    valid = k < noc[:, None]
+    nxt = np.take_along_axis(voc, (k + 1) % np.maximum(noc, 1)[:, None],
+                             axis=1)
+    lo, hi = np.minimum(voc, nxt), np.maximum(voc, nxt)
+    valid &= lo != hi
+    key = lo * (int(voc.max(initial=0)) + 1) + hi
+    cell = np.broadcast_to(np.arange(n)[:, None], voc.shape)
+    at = np.nonzero(valid.reshape(-1))[0]
+    order = at[np.argsort(key.reshape(-1)[at], kind='stable')]
+    keys = key.reshape(-1)[order]
+    pair = np.nonzero(keys[:-1] == keys[1:])[0]
+    nbr = np.full(n * width, -1, dtype=np.int32)
+    nbr[order[pair]] = cell.reshape(-1)[order[pair + 1]]
+    nbr[order[pair + 1]] = cell.reshape(-1)[order[pair]]
+    return nbr.reshape(n, width)
+
+
+def gradient_stencils(nbr, count, centroid):
+    """
+    The numpy statement of ``remap_gradient_stencils``: ``(coef (n, width +
+    1, 3), has (n,) int32)``.  Cell j has a gradient when ``count[j] >= 3``,
+    every one of its edges has a neighbour and the polygon N of the
+    neighbours' centroids (``centroid (n, 3)``, unit), in edge order, has an
+    area ``A_N != 0`` (the signed fan of :func:`_fan_areas`).  Green's
+    theorem with the trapezoid rule over N, minus the cell's own value:
+    ``g_j = sum_t e_t [(f_t - f_j) + (f_t+1 - f_j)]``, ``e_t = -1/2 theta_t
+    nu_t / A_N`` with ``nu_t`` / ``theta_t`` the unit normal / the arc from
+    neighbour t to t + 1 (cyclic).  ``A_N`` keeps its sign: a clockwise N
+    changes the sign of every ``nu_t`` and of ``A_N``, so ``e_t`` is what the
+    reversed order gives.  Slot ``1 + t`` holds ``e_t-1 + e_t``, slot 0 ``-2
+    sum_t e_t``, each made tangential at the cell's centroid: ``G - (G . c_j)
+    c_j``.  Without a gradient: all 0, ``has = 0``.
+    """
+    nbr = np.asarray(nbr, dtype=np.int64)
+    count = np.asarray(count, dtype=np.int64)
+    centroid = np.asarray(centroid, dtype=np.float64)
+    n, width = nbr.shape
+    coef = np.zeros((n, width + 1, 3))
+    if n == 0:
+        return coef, np.zeros(0, dtype=np.int32)
+    k = np.arange(width)[None, :]
+    valid = k < count[:, None]
+    ok = (count >= 3) & ((nbr >= 0) | ~valid).all(axis=1)
+    last = np.maximum(count, 1)[:, None] - 1
+    ring = centroid[np.where(valid & (nbr >= 0), nbr, 0)]
+    padded = np.take_along_axis(ring, np.minimum(k, last)[:, :, None], axis=1)
+    with np.errstate(invalid='ignore'):
+        an = _fan_areas(padded) if width >= 3 else np.zeros(n)
+    has = ok & (an != 0.0) & np.isfinite(an)
+    e = np.zeros((n, width, 3))
+    for t in range(width):
+        a = ring[:, t]
+        b = np.take_along_axis(
+            ring, ((t + 1) % np.maximum(count, 1))[:, None, None], axis=1)[:, 0]
+        c = np.cross(a, b - a)
+        s = np.sqrt(c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1] + c[:, 2] * c[:, 2])
+        d = a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1] + a[:, 2] * b[:, 2]
+        real = has & (t < count) & (s > 0.0)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            h = -0.5 * np.arctan2(s, d) / (s * an)
+        e[real, t] = h[real, None] * c[real]
+    total = np.zeros((n, 3))
+    for t in range(width):
+        prev = np.take_along_axis(
+            e, ((t - 1) % np.maximum(count, 1))[:, None, None], axis=1)[:, 0]
+        coef[:, 1 + t] = np.where((t < count)[:, None], prev + e[:, t], 0.0)
+        total = total + e[:, t]
+    coef[:, 0] = -2.0 * total
+    c = centroid[:, None, :]
+    along = (coef[..., 0] * c[..., 0] + coef[..., 1] * c[..., 1]) + \
+        coef[..., 2] * c[..., 2]
+    coef = coef - along[..., None] * c
+    coef[~has] = 0.0
+    return coef, has.astype(np.int32)
+
+
+def second_order_entries(dst, src, area, moment, nbr, count, coef, has,
+                         src_area, src_moment, dst_area):
+    """
+    The numpy statement of ``remap_conserve2nd_assemble``: the second-order
+    map ``(row, col, S)`` (0-based, sorted by (row, col), unique, zero sums
+    kept) from the first-order entries ``dst`` / ``src`` / ``area`` (``A_ij``)
+    with their overlap moments ``moment (n_entries, 3)``.  Entry (i, j)
+    emits ``(i, j, A_ij / A_i)`` and, where ``has[j]``, ``(i, k, G_jk .
+    d_ij)`` for k = j (``coef[j, 0]``) and j's neighbours in edge order,
+    ``d_ij = (M_ij - A_ij (M_j / A_j)) / A_i`` (never a division by
+    ``A_ij``), the dot product as ``(gx*dx + gy*dy) + gz*dz``.  Triples with
+    equal (i, k) are added in emission order.
+    """
+    dst = np.asarray(dst, dtype=np.int64)
+    src = np.asarray(src, dtype=np.int64)
+    area = np.asarray(area, dtype=np.float64)
+    moment = np.asarray(moment, dtype=np.float64)
+    nbr = np.asarray(nbr, dtype=np.int64)
+    count = np.asarray(count, dtype=np.int64)
+    has = np.asarray(has) != 0
+    src_area = np.asarray(src_area, dtype=np.float64)
+    width = nbr.shape[1]
+    ai = np.asarray(dst_area, dtype=np.float64)[dst]
+    with np.errstate(divide='ignore', invalid='ignore'):
+        mean = np.where((src_area > 0.0)[:, None],
+                        np.asarray(src_moment) / src_area[:, None], 0.0)
+    d = (moment - area[:, None] * mean[src]) / ai[:, None]
+    n_triples = 1 + np.where(has[src], 1 + count[src], 0)
+    off = np.cumsum(n_triples) - n_triples
+    pos, row, col, val = [off], [dst], [src], [area / ai]
+    for k in range(width + 1):
+        e = np.nonzero(has[src] & (k - 1 < count[src]))[0]
+        j = src[e]
+        g = coef[j, k]
+        pos.append(off[e] + 1 + k)
+        row.append(dst[e])
+        col.append(j if k == 0 else nbr[j, k - 1])
+        val.append((g[:, 0] * d[e, 0] + g[:, 1] * d[e, 1]) + g[:, 2] * d[e, 2])
+    pos, row, col, val = (np.concatenate(x) for x in (pos, row, col, val))
+    emission = np.argsort(pos, kind='stable')
+    row, col, val = row[emission], col[emission], val[emission]
+    key = row << 32 | col
+    order = np.argsort(key, kind='stable')
+    key, val = key[order], val[order]
+    head = np.ones(len(key), dtype=bool)
+    head[1:] = key[1:] != key[:-1]
+    run = np.cumsum(head) - 1
+    S = np.bincount(run, weights=val, minlength=int(head.sum()))
+    return ((key[head] >> 32).astype(np.int32),
+            (key[head] & 0xffffffff).astype(np.int32), S)
+
+
+def conserve2nd(src_descriptor, dst_descriptor, device=None, timing=None):
+    """
+    Second-order conservative weights from an MPAS cell mesh (its mesh file)
+    to a lat-lon grid, another MPAS cell mesh (its file) or a 2-D lat-lon
+    grid with its corner arrays; any other pair is a
+    ``NotImplementedError``.  ESMF's ``conserve2nd`` in structure -- the
+    first-order map plus a gradient of the source by Green's theorem over
+    the centroids of each cell's edge neighbours, applied to the offset of
+    every overlap's centroid from its source cell's -- not in bytes:
+
+    1. the first-order overlaps ``A_ij`` through the pair's own route
+       (:func:`conserve_mesh_latlon`, :func:`conserve_mesh_mesh`,
+       :func:`conserve_grid`), with its sliver rule and its ``frac_b``;
+    2. both sides' corners from :func:`pyremap_amd.scrip.scrip_geometry`;
+    3. on the GPU: the source cells' moments
+       (:func:`pyremap_amd.engine.cell_moments`), the gradient stencils over
+       :func:`cell_neighbours` (:func:`pyremap_amd.engine.gradient_stencils`),
+       the overlaps' moments (:func:`pyremap_amd.engine.overlap_moments`)
+       and the assembly (:func:`pyremap_amd.engine.conserve2nd_assemble`);
+    4. a :class:`MappingFile` whose ``area_a``, ``area_b``, ``frac_a`` and
+       ``frac_b`` are the first-order map's.
+
+    Rows keep their first-order sums (the coefficients of a cell sum to 0)
+    and ``sum_i A_i S_ik = A_k`` for every fully covered source cell.  A
+    cell with an edge that has no neighbour (a coast) stays first-order.
+    ``timing``: a dict that receives the GPU ``ms`` of the steps
+    (``overlap_ms``, ``cell_moments_ms``, ``stencils_ms``,
+    ``overlap_moments_ms``, ``assemble_ms``).
+    """
+    def mesh_file(d):
+        return isinstance(d, MpasCellMeshDescriptor) and \
+            getattr(d, 'filename', None) is not None
+    if not mesh_file(src_descriptor) or not (
+            mesh_file(dst_descriptor) or isinstance(
+                dst_descriptor, (LatLonGridDescriptor,
+                                 LatLon2DGridDescriptor))):
+        raise NotImplementedError(
+            f'{_CONSERVE2ND_PAIRS}; not from a '
+            f'{type(src_descriptor).__name__} to a '
+            f'{type(dst_descriptor).__name__}')
+    from pyremap_amd import engine
+    from pyremap_amd.scrip import scrip_geometry
+    torch = engine.require_gpu()
+    device = _device(device)
+    steps = {} if timing is None else timing
+
+    def timed(name):
+        if timing is None:
+            return None
+        steps[name] = {}
+        return steps[name]
+
+    if isinstance(dst_descriptor, LatLonGridDescriptor):
+        first = _overlaps_mesh_latlon(src_descriptor, dst_descriptor, True,
+                                      device, timed('overlap_ms'))
+    elif isinstance(dst_descriptor, LatLon2DGridDescriptor):
+        first = _overlaps_grid(src_descriptor, dst_descriptor, device,
+                               timed('overlap_ms'))
+    else:
+        first = _overlaps_mesh_mesh(src_descriptor, dst_descriptor, device,
+                                    timed('overlap_ms'))
+    overlaps, src_is_a, n_src, n_dst, src_dims, dst_dims = first
+    row, col, A, _, a_area, b_area = overlaps
+    src_area, dst_area = (a_area, b_area) if src_is_a else (b_area, a_area)
+
+    def cells(descriptor):
+        g = scrip_geometry(descriptor, area=False)
+        to_rad = 1.0 if 'rad' in g['units'] else np.pi / 180.0
+        return (_to_device(g['grid_corner_lat'] * to_rad, device, np.float64),
+                _to_device(g['grid_corner_lon'] * to_rad, device, np.float64),
+                _to_device(g['count'], device, np.int32))
+    src_cells, dst_cells = cells(src_descriptor), cells(dst_descriptor)
+    voc, noc, _, _ = mesh_polygons(src_descriptor)
+    nbr = _to_device(cell_neighbours(voc, noc), device, np.int32)
+
+    src_moment = engine.cell_moments(*src_cells,
+                                     timing=timed('cell_moments_ms'))
+    length = torch.linalg.vector_norm(src_moment, dim=1, keepdim=True)
+    centroid = torch.where(length > 0.0, src_moment / length,
+                           torch.zeros_like(src_moment))
+    coef, has = engine.gradient_stencils(nbr, src_cells[2], centroid,
+                                         timing=timed('stencils_ms'))
+    moment = engine.overlap_moments(row, col, A, src_cells, src_area,
+                                    src_moment, dst_cells,
+                                    timing=timed('overlap_moments_ms'))
+    row2, col2, S = engine.conserve2nd_assemble(
+        row, col, A, moment, nbr, src_cells[2], coef, has, src_area,
+        src_moment, dst_area, timing=timed('assemble_ms'))
+    m = _conserve_mapping(overlaps, src_is_a, n_src, n_dst, src_dims,
+                          dst_dims)
+    if timing is not None:
+        for name, value in list(steps.items()):
+            if isinstance(value, dict):
+                steps[name] = value.get('ms')
+    return MappingFile(
+        n_src, n_dst, m.src_grid_dims.astype(np.int32),
+        m.dst_grid_dims.astype(np.int32),
+        (row2.cpu().numpy() + 1).astype(np.int32),
+        (col2.cpu().numpy() + 1).astype(np.int32), S.cpu().numpy(), m.frac_b,
+        area_a=m.area_a, area_b=m.area_b, frac_a=m.frac_a)
+
+
 def _same_projection(a, b):
     pa, pb = a.projection, b.projection
     return pa is pb or getattr(pa, 'srs', pa) == getattr(pb, 'srs', pb)
@@ -2377,6 +2719,13 @@ def make_weights(src_descriptor, dst_descriptor, method='conserve',
     ``neareststod`` accept the two values and change nothing, as in the
     reference: destination corners play no part in them.  With both ``None``
     every call made is the one made without them.
+
+    ``method='conserve2nd'`` (not one of ``METHODS``: :func:`build_weights`
+    does not know it) is :func:`conserve2nd`, the second-order conservative
+    map from an MPAS cell mesh (its file) to a lat-lon grid, an MPAS cell
+    mesh or a 2-D grid with corners; other pairs and ``expand_dist`` /
+    ``expand_factor`` raise ``NotImplementedError``.  Its ``frac_a`` is the
+    first-order map's and is kept.
     """
     m = _make_weights(src_descriptor, dst_descriptor, method, expand_dist,
                       expand_factor)
@@ -2390,6 +2739,12 @@ def _make_weights(src_descriptor, dst_descriptor, method, expand_dist,
                   expand_factor):
     """The weights of :func:`make_weights`, before the grids' geometry is
     added."""
+    if method == 'conserve2nd':
+        if not (expand_dist is None and expand_factor is None):
+            raise NotImplementedError(
+                f'{_CONSERVE2ND_PAIRS}: smoothed second-order maps are not '
+                f'served')
+        return conserve2nd(src_descriptor, dst_descriptor)
     if method not in METHODS:
         raise ValueError(f'method {method!r}: expected one of {METHODS}')
     if method == 'conserve' and not (expand_dist is None and
