@@ -1601,6 +1601,111 @@ int remap_conserve2nd_assemble(int64_t n_entries, const int32_t *dst,
                                double *s_out, int64_t *counters,
                                int64_t *n_out, void *stream);
 
+/*
+ * ---------------------------------------------------------------------------
+ * Patch-recovery maps (patch) on the triangles remap_locate searches
+ * ---------------------------------------------------------------------------
+ * ESMF's patch interpolation in structure, not in bytes: a least-squares
+ * quadratic per node over its one-ring, and per destination point the blend
+ * of its triangle's three quadratics by the located weights, written as a
+ * map row.  xyz (n_nodes x 3, unit), tri (n_tri x 3 node ids) and points
+ * (n_pts x 3, unit) as remap_locate takes them, found / w as it returns them.
+ * Additions of ABI 31: no existing call changes.
+ *
+ * Rings.  ring[v] (REMAP_PATCH_MAX_RING wide) holds the distinct nodes that
+ * share a triangle with v, v itself left out, ascending, padded with -1;
+ * count[v] is their true number, of which the lowest REMAP_PATCH_MAX_RING are
+ * kept.  (The six directed pairs (a, b) of every triangle keyed a << 32 | b,
+ * rocPRIM's radix sort, the heads of the runs ranked by a scan and segmented
+ * per node.)
+ *
+ * Fits.  The members of node v are v, then ring[v].  The frame at c = xyz[v]:
+ * ref = z if |c_z| < 0.9, else x; e1 = normalize(ref x c); e2 = c x e1.
+ * Member r has t = r . c, x = (r . e1) / t, y = (r . e2) / t; h = the largest
+ * sqrt(x^2 + y^2) of the members; phi = (1, x/h, y/h, (x/h)^2, (x/h)(y/h),
+ * (y/h)^2); N = sum phi phi^T, the members added in order.  v HAS A PATCH
+ * when it has at least 6 members, count[v] <= REMAP_PATCH_MAX_RING (and is
+ * the number of ring slots filled), every member has t > 0.5, everything is
+ * finite and the unpivoted Cholesky N = L L^T (row by row) has every pivot
+ * d_k > 1e-8 N_kk.  fit[v] (REMAP_PATCH_FIT_WIDTH = 22 doubles) is h followed
+ * by the upper triangle of N^-1 = M^T M, M = L^-1, row-major; without a patch
+ * fit[v] = 0 and has[v] = 0.
+ *
+ * Rows.  A point p with found[p] = f >= 0 in triangle (v0, v1, v2) gets the
+ * bilinear row (v_t, w[p][t]) bit for bit when one of the three nodes has no
+ * patch or p . xyz[v_t] <= 0.5 for some t.  Otherwise, for t = 0, 1, 2: with
+ * phi_p the basis at p's scaled coordinates in v_t's frame and g = N^-1
+ * phi_p, member k of v_t receives w[p][t] * (phi_k . g).  Triples with the
+ * same column are added in emission order (t ascending, members in order)
+ * and the row is written sorted by column, zero sums kept.  Because every
+ * member list is ascending once v_t is put in its place, the row is ONE
+ * three-way merge of the lists: no per-lane list, no sort.  found[p] = -1:
+ * no row.
+ *
+ * remap_node_rings: ring_out (n_nodes x 16) and count_out (n_nodes) from tri.
+ * workspace: remap_node_rings_workspace() bytes.  status: one int32 on the
+ * device; the call WAITS (REMAP_ERR_ARG: a triangle names a node outside
+ * [0, n_nodes)).  n_tri < 2^32 / 6.
+ *
+ * remap_patch_fits: fit_out (n_nodes x 22) and has_out (n_nodes), one lane
+ * per node.  status as above; the call WAITS (REMAP_ERR_ARG: a ring entry
+ * outside [-1, n_nodes)).
+ *
+ * remap_patch_sizes: offsets_out (n_pts + 1 int64 on the device): the
+ * exclusive scan of every row's number of distinct columns, offsets_out[n_pts]
+ * = *total_out (host; the one read-back, the call WAITS).  workspace:
+ * remap_patch_sizes_workspace() bytes.
+ *
+ * remap_patch_rows: row p into row_out / col_out (0-based) / s_out at
+ * [offsets[p], offsets[p + 1]); capacity = the slots of the three arrays =
+ * offsets[n_pts].  The output is sorted by (row, col), unique.  Nothing is
+ * written outside a row's own slots.  status as above; the call WAITS.
+ * REMAP_ERR_ARG: a node or triangle id outside its side, offsets that are not
+ * remap_patch_sizes' for these arrays.
+ *
+ * All calls: fp64, on the caller's stream, no floating-point atomics (two
+ * calls give the same bytes).
+ * ---------------------------------------------------------------------------
+ */
+#define REMAP_PATCH_MAX_RING 16
+#define REMAP_PATCH_FIT_WIDTH 22
+
+REMAP_API
+int remap_node_rings_workspace(int64_t n_tri, int64_t n_nodes,
+                               size_t *bytes_out);
+
+REMAP_API
+int remap_node_rings(int64_t n_tri, const int32_t *tri, int64_t n_nodes,
+                     int32_t *ring_out, int32_t *count_out, int32_t *status,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
+REMAP_API
+int remap_patch_fits(int64_t n_nodes, const double *xyz, const int32_t *ring,
+                     const int32_t *count, double *fit_out, int32_t *has_out,
+                     int32_t *status, void *stream);
+
+REMAP_API
+int remap_patch_sizes_workspace(int64_t n_pts, size_t *bytes_out);
+
+REMAP_API
+int remap_patch_sizes(int64_t n_nodes, const double *xyz, int64_t n_tri,
+                      const int32_t *tri, const int32_t *ring,
+                      const int32_t *count, const int32_t *has, int64_t n_pts,
+                      const int32_t *found, const double *points,
+                      int64_t *offsets_out, int64_t *total_out,
+                      int32_t *status, void *workspace,
+                      size_t workspace_bytes, void *stream);
+
+REMAP_API
+int remap_patch_rows(int64_t n_nodes, const double *xyz, int64_t n_tri,
+                     const int32_t *tri, const int32_t *ring,
+                     const int32_t *count, const double *fit,
+                     const int32_t *has, int64_t n_pts, const int32_t *found,
+                     const double *w, const double *points,
+                     const int64_t *offsets, int64_t capacity,
+                     int32_t *row_out, int32_t *col_out, double *s_out,
+                     int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

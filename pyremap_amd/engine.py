@@ -91,6 +91,8 @@ EXPORTS = (
     'remap_cell_moments', 'remap_overlap_moments_workspace',
     'remap_overlap_moments', 'remap_gradient_stencils',
     'remap_conserve2nd_sizes', 'remap_conserve2nd_assemble',
+    'remap_node_rings_workspace', 'remap_node_rings', 'remap_patch_fits',
+    'remap_patch_sizes_workspace', 'remap_patch_sizes', 'remap_patch_rows',
 )
 
 
@@ -582,6 +584,30 @@ def load_library():
                                  ctypes.c_size_t] + \
         [ctypes.c_void_p] * 4 + [ctypes.POINTER(ctypes.c_int64),
                                  ctypes.c_void_p]
+    lib.remap_node_rings_workspace.restype = ctypes.c_int
+    lib.remap_node_rings_workspace.argtypes = [
+        ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]
+    lib.remap_node_rings.restype = ctypes.c_int
+    lib.remap_node_rings.argtypes = [
+        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+        ctypes.c_void_p]
+    lib.remap_patch_fits.restype = ctypes.c_int
+    lib.remap_patch_fits.argtypes = [ctypes.c_int64] + [ctypes.c_void_p] * 7
+    lib.remap_patch_sizes_workspace.restype = ctypes.c_int
+    lib.remap_patch_sizes_workspace.argtypes = [
+        ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]
+    lib.remap_patch_sizes.restype = ctypes.c_int
+    lib.remap_patch_sizes.argtypes = [
+        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] + \
+        [ctypes.c_void_p] * 4 + [ctypes.c_int64] + [ctypes.c_void_p] * 3 + \
+        [ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p, ctypes.c_void_p,
+         ctypes.c_size_t, ctypes.c_void_p]
+    lib.remap_patch_rows.restype = ctypes.c_int
+    lib.remap_patch_rows.argtypes = [
+        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] + \
+        [ctypes.c_void_p] * 5 + [ctypes.c_int64] + [ctypes.c_void_p] * 4 + \
+        [ctypes.c_int64] + [ctypes.c_void_p] * 5
     if lib.remap_abi_version() != ABI_VERSION:
         raise EngineError(
             f'{path} has ABI {lib.remap_abi_version()}, expected '
@@ -3207,3 +3233,183 @@ def conserve2nd_assemble(dst, src, area, moment, nbr, count, coef, has,
         del workspace
     k = n_out.value
     return row[:k], col[:k], S[:k]
+
+
+# ---------------------------------------------------------------------------
+# patch-recovery maps: one-rings, a quadratic per node, the rows
+# ---------------------------------------------------------------------------
+
+#: REMAP_PATCH_MAX_RING, REMAP_PATCH_FIT_WIDTH
+PATCH_MAX_RING = 16
+PATCH_FIT_WIDTH = 22
+
+
+def _patch_args(torch, specs):
+    """Every ``(name, tensor, dtype, trailing shape)`` of ``specs`` is a
+    contiguous tensor of that dtype and shape ``(n,) + trailing`` on one HIP
+    device, or a ``ValueError`` that names the argument.  Returns the
+    device."""
+    for name, t, dtype, tail in specs:
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or \
+                t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail or \
+                not t.is_contiguous():
+            kind = 'int32' if dtype == torch.int32 else 'float64'
+            shape = '(n, ' + ', '.join(str(k) for k in tail) + ')' \
+                if tail else '(n,)'
+            raise ValueError(
+                f'{name}: expected a contiguous {shape} {kind} tensor on a '
+                f'HIP device')
+    devices = {t.device for _, t, _, _ in specs}
+    if len(devices) != 1:
+        where = ', '.join(f'{name} on {t.device}' for name, t, _, _ in specs)
+        raise ValueError(f'{where}: expected one device')
+    return specs[0][1].device
+
+
+def _same_length(specs):
+    """Every ``(name, tensor, n, of)`` has ``n`` rows (one per ``of``)."""
+    for name, t, n, of in specs:
+        if t.shape[0] != n:
+            raise ValueError(f'{name}: {t.shape[0]} rows, expected one for '
+                             f'each of the {n} {of}')
+
+
+def node_rings(tri, n_nodes, timing=None):
+    """
+    The one-ring of every node of the triangles ``tri (n_tri, 3)`` (a
+    contiguous int32 tensor of node ids below ``n_nodes`` on a HIP device),
+    through ``remap_node_rings`` (``include/remap_hip.h`` has the
+    definition; :func:`pyremap_amd.weights.node_rings` is the numpy
+    statement).  Returns ``(ring int32 (n_nodes, PATCH_MAX_RING), count
+    int32 (n_nodes,))``: the distinct nodes that share a triangle with each
+    node, ascending, padded with -1, and their true number (of which the
+    lowest ``PATCH_MAX_RING`` are kept).  Two calls give identical bytes.
+    Runs on the current stream and waits for it.  ``ValueError``: a triangle
+    names a node outside ``[0, n_nodes)``.  ``timing``: a dict that receives
+    the GPU ``ms`` of the call.
+    """
+    torch = require_gpu()
+    lib = load_library()
+    dev = _patch_args(torch, (('tri', tri, torch.int32, (3,)),))
+    n_nodes = int(n_nodes)
+    if n_nodes < 1:
+        raise ValueError(f'n_nodes {n_nodes}: expected at least one node')
+    n_tri = tri.shape[0]
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        need = ctypes.c_size_t(0)
+        _checked(lib, lib.remap_node_rings_workspace(
+            n_tri, n_nodes, ctypes.byref(need)), 'remap_node_rings_workspace')
+        workspace = torch.empty(max(need.value, 1), dtype=torch.uint8,
+                                device=dev)
+        ring = torch.empty((n_nodes, PATCH_MAX_RING), dtype=torch.int32,
+                           device=dev)
+        count = torch.empty(n_nodes, dtype=torch.int32, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        with _gpu_ms(torch, timing):
+            _checked(lib, lib.remap_node_rings(
+                n_tri, _ptr(tri), n_nodes, _ptr(ring), _ptr(count),
+                _ptr(status), _ptr(workspace), need.value, stream),
+                'remap_node_rings')
+        del workspace
+    return ring, count
+
+
+def patch_fits(xyz, ring, count, timing=None):
+    """
+    The least-squares quadratic of every node over itself and its ring,
+    through ``remap_patch_fits`` (``include/remap_hip.h``;
+    :func:`pyremap_amd.weights.patch_fits` is the numpy statement): ``xyz
+    (n, 3)`` fp64 unit vectors, ``ring (n, PATCH_MAX_RING)`` and ``count
+    (n,)`` int32 as :func:`node_rings` returns them, contiguous, on one HIP
+    device.  Returns ``(fit fp64 (n, PATCH_FIT_WIDTH), has int32 (n,))``:
+    the scale ``h`` and the upper triangle of ``N^-1`` where the node has a
+    patch, zeros where ``has`` is 0.  Runs on the current stream and waits
+    for it.  ``timing``: a dict that receives the GPU ``ms`` of the call.
+    """
+    torch = require_gpu()
+    lib = load_library()
+    dev = _patch_args(torch, (
+        ('xyz', xyz, torch.float64, (3,)),
+        ('ring', ring, torch.int32, (PATCH_MAX_RING,)),
+        ('count', count, torch.int32, ())))
+    n = xyz.shape[0]
+    if n < 1:
+        raise ValueError('patch_fits needs at least one node')
+    _same_length((('ring', ring, n, 'nodes'), ('count', count, n, 'nodes')))
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        fit = torch.empty((n, PATCH_FIT_WIDTH), dtype=torch.float64,
+                          device=dev)
+        has = torch.empty(n, dtype=torch.int32, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        with _gpu_ms(torch, timing):
+            _checked(lib, lib.remap_patch_fits(
+                n, _ptr(xyz), _ptr(ring), _ptr(count), _ptr(fit), _ptr(has),
+                _ptr(status), stream), 'remap_patch_fits')
+    return fit, has
+
+
+def patch_rows(xyz, tri, ring, count, fit, has, found, w, points,
+               timing=None):
+    """
+    The patch map's rows, through ``remap_patch_sizes`` /
+    ``remap_patch_rows`` (``include/remap_hip.h``;
+    :func:`pyremap_amd.weights.patch_entries` is the numpy statement):
+    ``xyz``, ``tri`` and ``points`` as :func:`locate_in_triangles` takes
+    them, ``found (n_pts,)`` / ``w (n_pts, 3)`` as it returns them, ``ring``
+    / ``count`` of :func:`node_rings` and ``fit`` / ``has`` of
+    :func:`patch_fits`; contiguous fp64 / int32 tensors on one HIP device.
+    Returns ``(row, col, S)``, new tensors (int32 0-based, fp64) sorted by
+    ``(row, col)`` and unique; zero sums are kept; a point with ``found =
+    -1`` has no row.  A point whose triangle touches a node without a patch
+    keeps its three located weights, bit for bit.  Two calls give the same
+    bytes.  Runs on the current stream and waits for it twice (the entry
+    count, the status).  ``timing`` receives the GPU ``ms`` of both passes.
+    """
+    torch = require_gpu()
+    lib = load_library()
+    dev = _patch_args(torch, (
+        ('xyz', xyz, torch.float64, (3,)),
+        ('tri', tri, torch.int32, (3,)),
+        ('ring', ring, torch.int32, (PATCH_MAX_RING,)),
+        ('count', count, torch.int32, ()),
+        ('fit', fit, torch.float64, (PATCH_FIT_WIDTH,)),
+        ('has', has, torch.int32, ()),
+        ('found', found, torch.int32, ()),
+        ('w', w, torch.float64, (3,)),
+        ('points', points, torch.float64, (3,))))
+    n, n_tri, n_pts = xyz.shape[0], tri.shape[0], points.shape[0]
+    if n < 1:
+        raise ValueError('patch_rows needs at least one node')
+    _same_length((('ring', ring, n, 'nodes'), ('count', count, n, 'nodes'),
+                  ('fit', fit, n, 'nodes'), ('has', has, n, 'nodes'),
+                  ('found', found, n_pts, 'points'),
+                  ('w', w, n_pts, 'points')))
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        need = ctypes.c_size_t(0)
+        _checked(lib, lib.remap_patch_sizes_workspace(
+            n_pts, ctypes.byref(need)), 'remap_patch_sizes_workspace')
+        workspace = torch.empty(max(need.value, 1), dtype=torch.uint8,
+                                device=dev)
+        offsets = torch.empty(n_pts + 1, dtype=torch.int64, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        total = ctypes.c_int64(0)
+        with _gpu_ms(torch, timing):
+            _checked(lib, lib.remap_patch_sizes(
+                n, _ptr(xyz), n_tri, _ptr(tri), _ptr(ring), _ptr(count),
+                _ptr(has), n_pts, _ptr(found), _ptr(points), _ptr(offsets),
+                ctypes.byref(total), _ptr(status), _ptr(workspace),
+                need.value, stream), 'remap_patch_sizes')
+            cap = total.value
+            row = torch.empty(cap, dtype=torch.int32, device=dev)
+            col = torch.empty(cap, dtype=torch.int32, device=dev)
+            S = torch.empty(cap, dtype=torch.float64, device=dev)
+            _checked(lib, lib.remap_patch_rows(
+                n, _ptr(xyz), n_tri, _ptr(tri), _ptr(ring), _ptr(count),
+                _ptr(fit), _ptr(has), n_pts, _ptr(found), _ptr(w),
+                _ptr(points), _ptr(offsets), cap, _ptr(row), _ptr(col),
+                _ptr(S), _ptr(status), stream), 'remap_patch_rows')
+        del workspace
+    return row, col, S

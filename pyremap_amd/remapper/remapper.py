@@ -190,6 +190,13 @@ class Remapper:
         moments, stencils and assembly on the GPU
         (:func:`pyremap_amd.weights.conserve2nd`); it is not smoothed
         (``expand_dist`` / ``expand_factor`` raise).
+        ``patch`` is the patch-recovery interpolation from an MPAS mesh
+        (cells, edges or vertices, given by its mesh file) to anything
+        ``bilinear`` from such a mesh reaches, point collections included:
+        a least-squares quadratic per node over its one-ring, blended by the
+        bilinear weights, third-order where ``bilinear`` is second-order;
+        rings, fits and rows on the GPU
+        (:func:`pyremap_amd.weights.patch_mesh_weights`).
         """
         from pyremap_amd.remapper.setup import _setup_remapper
         if self.map_tool != 'analytic':
@@ -208,7 +215,8 @@ class Remapper:
                 "on either side; expand_dist / expand_factor smooth the "
                 "conserve maps; conserve2nd maps from an MPAS cell mesh (its "
                 "mesh file) to a lat-lon grid, an MPAS cell mesh or a 2-D "
-                "lat-lon grid")
+                "lat-lon grid; patch maps from an MPAS mesh (its mesh file) "
+                "to anything bilinear from it reaches")
         _setup_remapper(self)
         from pyremap_amd.weights import write_weights
         if logger is not None:

@@ -19,7 +19,7 @@ from pyremap_amd.descriptor import (
 _TOOL_PREFIX = {'esmf': 'esmf', 'moab': 'mbtr', 'analytic': 'analytic'}
 _METHOD_SUFFIX = {'conserve': 'aave', 'bilinear': 'bilin',
                   'neareststod': 'neareststod',
-                  'conserve2nd': 'conserve2nd'}
+                  'conserve2nd': 'conserve2nd', 'patch': 'patch'}
 
 
 def _setup_remapper(remapper):
@@ -50,7 +50,7 @@ def _setup_remapper(remapper):
             f'Unexpected map_tool {map_tool}. Valid '
             f'values are "esmf" or "moab".')
     if isinstance(dst_descriptor, PointCollectionDescriptor) and \
-            method not in ('bilinear', 'neareststod'):
+            method not in ('bilinear', 'neareststod', 'patch'):
         raise ValueError(
             f'method {method} not supported for destination '
             f'grid of type PointCollectionDescriptor.')

@@ -82,6 +82,15 @@ axes the common methods have closed forms:
   search is exact and runs on the GPU (``remap_nearest``,
   ``pyremap_amd/csrc/remap_nearest.hip``); it takes plain coordinate arrays,
   so sources of any other kind go through it when called directly.
+* ``patch`` FROM an MPAS mesh (its cells, edges or vertices, given by its
+  mesh file) towards anything ``bilinear`` from such a mesh reaches
+  (:func:`patch_mesh_weights`, through :func:`make_weights` only) -- ESMF's
+  patch recovery in structure, not in bytes: a least-squares quadratic per
+  node of the dual mesh over its one-ring, and per destination point the
+  blend of its triangle's three quadratics by the bilinear weights;
+  third-order where ``bilinear`` is second-order.  Rings, fits and rows run
+  on the GPU (``pyremap_amd/csrc/remap_patch.hip``); :func:`node_rings`,
+  :func:`patch_fits` and :func:`patch_entries` are the numpy statements.
 
 The result is a :class:`pyremap_amd.io.mapfile.MappingFile` with exactly the
 schema ESMF writes (1-based ``row``/``col``, Fortran-ordered grid dims), so it
@@ -2653,6 +2662,294 @@ def conserve2nd(src_descriptor, dst_descriptor, device=None, timing=None):
         area_a=m.area_a, area_b=m.area_b, frac_a=m.frac_a)
 
 
+# ---------------------------------------------------------------------------
+# patch-recovery maps (patch) from an MPAS mesh
+# ---------------------------------------------------------------------------
+
+#: REMAP_PATCH_MAX_RING
+PATCH_MAX_RING = 16
+#: a member, or a point, must lie within 60 degrees of a patch's node
+PATCH_MIN_COS = 0.5
+#: a Cholesky pivot below this share of its diagonal entry: no patch
+PATCH_PIVOT = 1e-8
+
+_PATCH_SOURCES = (
+    'patch is served from an MPAS cell, edge or vertex mesh given by its '
+    'mesh file (filename=)')
+
+
+def node_rings(tri, n_nodes):
+    """
+    The numpy statement of ``remap_node_rings``: ``(ring (n_nodes,
+    PATCH_MAX_RING) int32, count (n_nodes,) int32)``.  ``ring[v]`` holds the
+    distinct nodes that share a triangle of ``tri (nt, 3)`` with v, v itself
+    left out, in ascending order and padded with -1; ``count[v]`` is their
+    true number, of which the lowest ``PATCH_MAX_RING`` are kept.
+    """
+    tri = np.asarray(tri, dtype=np.int64).reshape(-1, 3)
+    n_nodes = int(n_nodes)
+    if len(tri) and (tri.min() < 0 or tri.max() >= n_nodes):
+        raise ValueError(f'tri: a node outside [0, {n_nodes})')
+    a = tri[:, [0, 0, 1, 1, 2, 2]].reshape(-1)
+    b = tri[:, [1, 2, 0, 2, 0, 1]].reshape(-1)
+    key = np.unique((a << 32 | b)[a != b])
+    a, b = key >> 32, key & 0xffffffff
+    count = np.bincount(a, minlength=n_nodes)
+    slot = np.arange(len(a)) - (np.cumsum(count) - count)[a]
+    ring = np.full((n_nodes, PATCH_MAX_RING), -1, dtype=np.int32)
+    kept = slot < PATCH_MAX_RING
+    ring[a[kept], slot[kept]] = b[kept]
+    return ring, count.astype(np.int32)
+
+
+def _patch_frames(c):
+    """``(e1, e2)`` of the tangent planes at the unit vectors ``c (n, 3)``:
+    ``tangent_at`` of ``remap_clip.h``."""
+    ref = np.where((np.abs(c[:, 2]) < 0.9)[:, None], [[0.0, 0.0, 1.0]],
+                   [[1.0, 0.0, 0.0]])
+    e1 = np.cross(ref, c)
+    e1 = e1 / np.sqrt((e1 * e1).sum(axis=1))[:, None]
+    return e1, np.cross(c, e1)
+
+
+def _patch_project(r, c, e1, e2):
+    """``(x, y, t)`` of ``r`` in the gnomonic plane at ``c``: ``t = r . c``,
+    ``x = (r . e1) / t``, ``y = (r . e2) / t`` (arrays that broadcast)."""
+    t = (r * c).sum(axis=-1)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return (r * e1).sum(axis=-1) / t, (r * e2).sum(axis=-1) / t, t
+
+
+def _patch_basis(x, y):
+    """phi = (1, x, y, x^2, xy, y^2) along a new last axis."""
+    return np.stack([np.ones_like(x), x, y, x * x, x * y, y * y], axis=-1)
+
+
+_PATCH_UPPER = np.triu_indices(6)
+
+
+def patch_fits(xyz, ring, count):
+    """
+    The numpy statement of ``remap_patch_fits``: ``(fit (n, 22) fp64, has
+    (n,) int32)``, the least-squares quadratic of every node over itself and
+    its ring (:func:`node_rings`).  The members of node v are v, then
+    ``ring[v]``; member r has the gnomonic coordinates ``x = (r . e1) / (r .
+    c)``, ``y = (r . e2) / (r . c)`` in the frame of ``c = xyz[v]``
+    (``tangent_at``), scaled by ``h``, the largest ``sqrt(x^2 + y^2)`` of
+    the members; ``N = sum phi phi^T`` over the members' ``phi = (1, x, y,
+    x^2, xy, y^2)``.  v has a patch when it has at least 6 members,
+    ``count[v] <= PATCH_MAX_RING``, every member has ``r . c >
+    PATCH_MIN_COS``, everything is finite and the unpivoted Cholesky of N has
+    every pivot ``d_k > PATCH_PIVOT * N_kk``.  ``fit[v]`` is then ``h``
+    followed by the upper triangle of ``N^-1`` (row-major, from the inverse
+    of the Cholesky factor); without a patch it is 0 and ``has[v] = 0``.
+    """
+    xyz = np.asarray(xyz, dtype=np.float64)
+    ring = np.asarray(ring, dtype=np.int64)
+    count = np.asarray(count, dtype=np.int64)
+    n = len(xyz)
+    if ring.shape != (n, PATCH_MAX_RING) or count.shape != (n,):
+        raise ValueError(
+            f'ring of shape {ring.shape}, count of shape {count.shape}: '
+            f'expected ({n}, {PATCH_MAX_RING}) and ({n},)')
+    fit = np.zeros((n, 22))
+    if n == 0:
+        return fit, np.zeros(0, dtype=np.int32)
+    members = np.concatenate([np.arange(n)[:, None], ring], axis=1)
+    valid = (members >= 0) & (members < n)
+    e1, e2 = _patch_frames(xyz)
+    x, y, t = _patch_project(xyz[np.where(valid, members, 0)], xyz[:, None],
+                             e1[:, None], e2[:, None])
+    ok = (valid.sum(axis=1) >= 6) & (count <= PATCH_MAX_RING) & \
+        (count == valid[:, 1:].sum(axis=1)) & \
+        np.where(valid, t > PATCH_MIN_COS, True).all(axis=1)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        h = np.sqrt(np.where(valid, x * x + y * y, 0.0)).max(axis=1)
+        ok &= np.isfinite(h) & (h > 0.0)
+        phi = np.where(valid[..., None],
+                       _patch_basis(x / h[:, None], y / h[:, None]), 0.0)
+        N = np.zeros((n, 6, 6))
+        for m in range(phi.shape[1]):       # members in order, as one lane
+            N += phi[:, m, :, None] * phi[:, m, None, :]
+        # unpivoted Cholesky N = L L^T, row by row
+        L = np.zeros((n, 6, 6))
+        for k in range(6):
+            d = N[:, k, k].copy()
+            for j in range(k):
+                d -= L[:, k, j] * L[:, k, j]
+            ok &= np.isfinite(d) & (d > PATCH_PIVOT * N[:, k, k])
+            L[:, k, k] = np.sqrt(np.where(ok, d, 1.0))
+            for i in range(k + 1, 6):
+                s = N[:, i, k].copy()
+                for j in range(k):
+                    s -= L[:, i, j] * L[:, k, j]
+                L[:, i, k] = s / L[:, k, k]
+        # M = L^-1 by forward substitution, N^-1 = M^T M
+        M = np.zeros((n, 6, 6))
+        for k in range(6):
+            M[:, k, k] = 1.0 / L[:, k, k]
+            for i in range(k + 1, 6):
+                s = np.zeros(n)
+                for j in range(k, i):
+                    s -= L[:, i, j] * M[:, j, k]
+                M[:, i, k] = s / L[:, i, i]
+        inv = np.zeros((n, 6, 6))
+        for m in range(6):
+            inv += M[:, m, :, None] * M[:, m, None, :]
+    ok &= np.isfinite(inv).all(axis=(1, 2))
+    fit[:, 0] = h
+    fit[:, 1:] = inv[:, _PATCH_UPPER[0], _PATCH_UPPER[1]]
+    fit[~ok] = 0.0
+    return fit, ok.astype(np.int32)
+
+
+def patch_entries(xyz, tri, ring, count, fit, has, found, w, points):
+    """
+    The numpy statement of ``remap_patch_sizes`` / ``remap_patch_rows``: the
+    map ``(row, col, S)`` (0-based int32, fp64; sorted by (row, col), unique,
+    zero sums kept) of the points located in ``tri`` (``found`` the triangle
+    or -1, ``w (n_pts, 3)`` its corners' weights, as
+    :func:`locate_in_triangles` returns them).  A point in triangle ``(v0,
+    v1, v2)`` gets the bilinear row ``(v_t, w_t)`` as it is when one of the
+    three nodes has no patch (:func:`patch_fits`) or ``p . xyz[v_t] <=
+    PATCH_MIN_COS`` for one of them.  Otherwise, for t = 0, 1, 2: with
+    ``phi_p`` the basis at p's scaled gnomonic coordinates in v_t's frame and
+    ``g = N^-1 phi_p``, every member k of v_t (v_t, then its ring) receives
+    ``w_t * (phi_k . g)``; triples with the same column are added in
+    emission order (t ascending, members in order).  Points with ``found =
+    -1`` get no row.
+    """
+    xyz = np.asarray(xyz, dtype=np.float64)
+    tri = np.asarray(tri, dtype=np.int64).reshape(-1, 3)
+    ring = np.asarray(ring, dtype=np.int64)
+    has = np.asarray(has) != 0
+    fit = np.asarray(fit, dtype=np.float64)
+    found = np.asarray(found, dtype=np.int64)
+    w = np.asarray(w, dtype=np.float64)
+    points = np.asarray(points, dtype=np.float64)
+    hit = np.nonzero(found >= 0)[0]
+    v = tri[found[hit]]                                   # (m, 3)
+    p = points[hit]
+    near = ((p[:, None, :] * xyz[v]).sum(axis=-1) > PATCH_MIN_COS).all(axis=1)
+    full = has[v].all(axis=1) & near
+    # the bilinear rows, as they are
+    fb = hit[~full]
+    rows = [np.repeat(fb, 3)]
+    cols = [v[~full].reshape(-1)]
+    vals = [w[fb].reshape(-1)]
+    # the patch rows: (m, 3, 17) triples in emission order
+    pt, vp, pp = hit[full], v[full], p[full]
+    if len(pt):
+        c = xyz[vp]                                        # (m, 3, 3)
+        e1, e2 = _patch_frames(c.reshape(-1, 3))
+        e1, e2 = e1.reshape(c.shape), e2.reshape(c.shape)
+        h = fit[vp, 0]
+        inv = np.zeros(vp.shape + (6, 6))
+        inv[..., _PATCH_UPPER[0], _PATCH_UPPER[1]] = fit[vp, 1:]
+        inv[..., _PATCH_UPPER[1], _PATCH_UPPER[0]] = fit[vp, 1:]
+        x, y, _ = _patch_project(pp[:, None, :], c, e1, e2)
+        g = (inv * _patch_basis(x / h, y / h)[..., None, :]).sum(axis=-1)
+        members = np.concatenate([vp[..., None], ring[vp]], axis=-1)
+        valid = members >= 0
+        r = xyz[np.where(valid, members, 0)]               # (m, 3, 17, 3)
+        x, y, _ = _patch_project(r, c[:, :, None], e1[:, :, None],
+                                 e2[:, :, None])
+        phi = _patch_basis(x / h[..., None], y / h[..., None])
+        val = w[pt][:, :, None] * (phi * g[:, :, None, :]).sum(axis=-1)
+        rows.append(np.broadcast_to(pt[:, None, None], members.shape)[valid])
+        cols.append(members[valid])
+        vals.append(val[valid])
+    row, col, val = (np.concatenate(a) for a in (rows, cols, vals))
+    key = row << 32 | col
+    order = np.argsort(key, kind='stable')
+    key, val = key[order], val[order]
+    head = np.ones(len(key), dtype=bool)
+    head[1:] = key[1:] != key[:-1]
+    S = np.zeros(int(head.sum()))
+    np.add.at(S, np.cumsum(head) - 1, val)
+    # (a run of one keeps its bits, -0.0 included)
+    single = head & np.append(head[1:], True)
+    S[(np.cumsum(head) - 1)[single]] = val[single]
+    return ((key[head] >> 32).astype(np.int32),
+            (key[head] & 0xffffffff).astype(np.int32), S)
+
+
+def patch_mesh_weights(src_descriptor, plat, plon, dst_dims, device=None,
+                       timing=None):
+    """
+    ``patch`` from the cells, edges or vertices of an MPAS mesh (given by its
+    mesh file) towards the points ``plat`` / ``plon`` (radians, 1-D): ESMF's
+    patch recovery in structure, not in bytes.  The triangles of the dual
+    mesh (:func:`_dual_triangles`) and the point location of ``bilinear``
+    (:func:`pyremap_amd.engine.locate_in_triangles`), then on the GPU the
+    one-rings (:func:`pyremap_amd.engine.node_rings`), a least-squares
+    quadratic per node (:func:`pyremap_amd.engine.patch_fits`) and the rows
+    (:func:`pyremap_amd.engine.patch_rows`): every point takes the blend of
+    its triangle's three quadratics by the bilinear weights, 12 entries a
+    row on a hexagonal mesh; a triangle that touches a node without a full
+    ring (a coast) keeps the bilinear row.  :func:`node_rings`,
+    :func:`patch_fits` and :func:`patch_entries` are the numpy statements.
+    Points no triangle holds are unmapped, ``frac_b`` = 0.  Needs the GPU.
+    ``timing``: a dict that receives ``locate_ms``, ``rings_ms``, ``fits_ms``
+    and ``rows_ms``.
+    """
+    from pyremap_amd import engine
+    xyz, tri = _dual_triangles(src_descriptor)
+    if len(tri) < 1:
+        raise ValueError('the mesh has no complete dual triangle: nothing '
+                         'to interpolate on')
+    if len(xyz) > np.iinfo(np.int32).max:
+        raise ValueError(f'{len(xyz)} source points: the mapping file\'s '
+                         f'col is int32')
+    plat = np.ascontiguousarray(plat, dtype=np.float64).reshape(-1)
+    plon = np.ascontiguousarray(plon, dtype=np.float64).reshape(-1)
+    engine.require_gpu()
+    device = _device(device)
+    steps = {name: ({} if timing is not None else None)
+             for name in ('locate_ms', 'rings_ms', 'fits_ms', 'rows_ms')}
+    d_xyz = _to_device(xyz, device)
+    d_tri = _to_device(tri, device, np.int32)
+    d_points = _to_device(_unit(plat, plon), device)
+    found, w = engine.locate_in_triangles(d_xyz, d_tri, d_points,
+                                          timing=steps['locate_ms'])
+    ring, count = engine.node_rings(d_tri, len(xyz),
+                                    timing=steps['rings_ms'])
+    fit, has = engine.patch_fits(d_xyz, ring, count,
+                                 timing=steps['fits_ms'])
+    row, col, S = engine.patch_rows(d_xyz, d_tri, ring, count, fit, has,
+                                    found, w, d_points,
+                                    timing=steps['rows_ms'])
+    if timing is not None:
+        for name, value in steps.items():
+            timing[name] = value.get('ms')
+    frac_b = (found >= 0).to(d_points.dtype).cpu().numpy()
+    return MappingFile(
+        len(xyz), len(plat), np.array([len(xyz)], dtype=np.int32),
+        np.asarray(dst_dims, dtype=np.int32),
+        (row.cpu().numpy() + 1).astype(np.int32),
+        (col.cpu().numpy() + 1).astype(np.int32), S.cpu().numpy(), frac_b)
+
+
+def _make_patch(src_descriptor, dst_descriptor):
+    """``patch`` of :func:`make_weights`: the destinations ``bilinear`` from
+    an MPAS mesh has."""
+    if not (isinstance(src_descriptor, MpasMeshDescriptor) and
+            getattr(src_descriptor, 'filename', None) is not None):
+        raise ValueError(
+            f'method \'patch\' from a {type(src_descriptor).__name__}: for '
+            f'this source expected one of {METHODS}; {_PATCH_SOURCES}')
+    points = _points(dst_descriptor)
+    if points is not None:
+        plat, plon, dims = points[0], points[1], [len(points[0])]
+    elif isinstance(dst_descriptor, MpasMeshDescriptor):
+        raise ValueError(
+            'towards an MPAS mesh its coordinates are needed: give the '
+            'descriptor a mesh file or lat= / lon=, not a size alone')
+    else:
+        plat, plon, dims = _cell_centres(dst_descriptor)
+    return patch_mesh_weights(src_descriptor, plat, plon, dims)
+
+
 def _same_projection(a, b):
     pa, pb = a.projection, b.projection
     return pa is pb or getattr(pa, 'srs', pa) == getattr(pb, 'srs', pb)
@@ -2726,6 +3023,13 @@ def make_weights(src_descriptor, dst_descriptor, method='conserve',
     mesh or a 2-D grid with corners; other pairs and ``expand_dist`` /
     ``expand_factor`` raise ``NotImplementedError``.  Its ``frac_a`` is the
     first-order map's and is kept.
+
+    ``method='patch'`` (not one of ``METHODS`` either) is
+    :func:`patch_mesh_weights`, the patch-recovery interpolation from an
+    MPAS cell, edge or vertex mesh given by its mesh file towards the
+    destinations ``bilinear`` from such a mesh has; ``expand_dist`` /
+    ``expand_factor`` change nothing.  Any other source is a ``ValueError``.
+    It needs the GPU.
     """
     m = _make_weights(src_descriptor, dst_descriptor, method, expand_dist,
                       expand_factor)
@@ -2745,6 +3049,8 @@ def _make_weights(src_descriptor, dst_descriptor, method, expand_dist,
                 f'{_CONSERVE2ND_PAIRS}: smoothed second-order maps are not '
                 f'served')
         return conserve2nd(src_descriptor, dst_descriptor)
+    if method == 'patch':
+        return _make_patch(src_descriptor, dst_descriptor)
     if method not in METHODS:
         raise ValueError(f'method {method!r}: expected one of {METHODS}')
     if method == 'conserve' and not (expand_dist is None and
