@@ -1627,9 +1627,12 @@ int remap_conserve2nd_assemble(int64_t n_entries, const int32_t *dst,
  * when it has at least 6 members, count[v] <= REMAP_PATCH_MAX_RING (and is
  * the number of ring slots filled), every member has t > 0.5, everything is
  * finite and the unpivoted Cholesky N = L L^T (row by row) has every pivot
- * d_k > 1e-8 N_kk.  fit[v] (REMAP_PATCH_FIT_WIDTH = 22 doubles) is h followed
+ * d_k > 1e-2 N_kk.  fit[v] (REMAP_PATCH_FIT_WIDTH = 22 doubles) is h followed
  * by the upper triangle of N^-1 = M^T M, M = L^-1, row-major; without a patch
- * fit[v] = 0 and has[v] = 0.
+ * fit[v] = 0 and has[v] = 0.  (The pivot share was 1e-8 when ABI 31 came; it
+ * admitted fits singular to eight digits on the duals of edge and vertex
+ * meshes.  No signature or layout changed, so the ABI number stays; no node
+ * of a cell mesh changes, their smallest share is 0.19.)
  *
  * Rows.  A point p with found[p] = f >= 0 in triangle (v0, v1, v2) gets the
  * bilinear row (v_t, w[p][t]) bit for bit when one of the three nodes has no

@@ -46,7 +46,9 @@ constexpr int kRing = REMAP_PATCH_MAX_RING;
 constexpr int kFit = REMAP_PATCH_FIT_WIDTH;    // h, 21 of N^-1
 constexpr int kMinMembers = 6;
 constexpr double kPatchMinCos = 0.5;
-constexpr double kPivot = 1e-8;
+// (1e-8 admitted fits singular to eight digits on edge and vertex meshes:
+// DESIGN section 18 has the sweep)
+constexpr double kPivot = 1e-2;
 // status bits: a node id outside [0, n_nodes) (tri, ring); a triangle id
 // outside [-1, n_tri) (found); offsets that are not remap_patch_sizes' for
 // these arrays

@@ -2670,8 +2670,9 @@ def conserve2nd(src_descriptor, dst_descriptor, device=None, timing=None):
 PATCH_MAX_RING = 16
 #: a member, or a point, must lie within 60 degrees of a patch's node
 PATCH_MIN_COS = 0.5
-#: a Cholesky pivot below this share of its diagonal entry: no patch
-PATCH_PIVOT = 1e-8
+#: a Cholesky pivot at or below this share of its diagonal entry: no patch
+#: (1e-8 before; DESIGN section 18 has the sweep that chose 1e-2)
+PATCH_PIVOT = 1e-2
 
 _PATCH_SOURCES = (
     'patch is served from an MPAS cell, edge or vertex mesh given by its '

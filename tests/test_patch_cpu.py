@@ -4,7 +4,8 @@ numpy statements of the three steps -- rings, fits, rows
 (pyremap_amd.weights.node_rings / patch_fits / patch_entries) -- held to the
 counts, identities and convergence the scheme was chosen for (DESIGN section
 18), on icosahedral meshes (plain and under a land mask) and the QU240
-fixture; degenerate inputs; the dispatch; the ABI names.
+fixture (the triangles of its cells, and the ear-clipped duals of its edges
+and vertices); degenerate inputs; the dispatch; the ABI names.
 
 The field is f = a . r, the points 4 000 normalised normal deviates; errors
 are the root mean square and the maximum over the mapped points against f at
@@ -18,6 +19,18 @@ issue's):
   n = 8, land    2.61e-4 / 1.77e-3  0.148   (bound 0.3), max 2.18e-3 / 4.35e-3
   QU240          3.17e-5 / 1.06e-4  0.300   (bound 0.5), max 2.380e-4 /
                  2.394e-4 = 0.994 (bound 1.05)
+  QU240 edges    2.63e-5 / 5.30e-5  0.496   (bound 0.6), max 1.526e-4 /
+                 1.679e-4 = 0.909 (bound 1.05)
+  QU240 vertices 4.27e-5 / 8.47e-5  0.504   (bound 0.6), max 2.358e-4 /
+                 2.384e-4 = 0.989 (bound 1.05)
+
+The duals of the edge and vertex meshes are what the pivot rule is for: rings
+of 2 to 10 nodes, often on or near one conic.  With PATCH_PIVOT = 1e-2 the
+largest |N^-1| of a node with a patch is 87 (edges) and 100 (vertices) and
+the absolute weights of a row sum to at most 2.403 and 2.363; with the 1e-8
+the scheme came with they were 2.1e6 / 8.8e8 and 2.72 / 110.6, and rows
+missed a sum of 1 by 1.1e-12 / 1.3e-11.  The bounds (1000 and 4) sit a decade
+above the first pair and decades below the second.
 """
 import functools
 import os
@@ -41,11 +54,18 @@ def points():
 @functools.lru_cache(maxsize=None)
 def triangles(which, masked=False):
     """(xyz, tri) of icosahedral ``which`` (triangles from cellsOnVertex), or
-    of the QU240 fixture's cells (``which='qu240'``)."""
+    of the QU240 fixture's cells (``which='qu240'``), edges
+    (``'qu240-edge'``) or vertices (``'qu240-vertex'``)."""
     from pyremap_amd import MpasCellMeshDescriptor, weights
     if which == 'qu240':
         return weights._dual_triangles(
             MpasCellMeshDescriptor(QU240, mesh_name='oQU240'))
+    if which in ('qu240-edge', 'qu240-vertex'):
+        from test_nearest_cpu import qu240
+        xyz, tri = weights._dual_triangles(qu240(which[6:]))
+        xyz.setflags(write=False)
+        tri.setflags(write=False)
+        return xyz, tri
     m = mesh(which, masked)
     coc = m['cellsOnVertex'].astype(np.int64)
     return weights._unit(m['latCell'], m['lonCell']), \
@@ -67,6 +87,7 @@ def figures(xyz, tri, found, w, row, col, S, pts):
         row_sum=np.abs(np.bincount(row, weights=S, minlength=len(pts))[hit] -
                        1.0).max(),
         per_row_max=int(per_row.max()), per_row_mean=per_row[hit].mean(),
+        sum_abs=np.bincount(row, weights=np.abs(S), minlength=len(pts)).max(),
         l2=np.sqrt((ep * ep).mean()), l2_bilinear=np.sqrt((eb * eb).mean()),
         max=np.abs(ep).max(), max_bilinear=np.abs(eb).max())
 
@@ -204,8 +225,129 @@ def test_statement_on_qu240():
     assert s['max'] <= 1.05 * s['max_bilinear']
 
 
+DUALS = {
+    # nodes, triangles, widest ring, mapped of the 4 000 points
+    'qu240-edge': (22403, 42990, 9, 2735),
+    'qu240-vertex': (15211, 28606, 10, 2741),
+}
+
+
+def inverse_scale(s):
+    """max |N^-1| of every node (0 without a patch)."""
+    return np.abs(s['fit'][:, 1:]).max(axis=1)
+
+
+@pytest.mark.parametrize('which', sorted(DUALS))
+def test_statement_on_the_duals_of_edges_and_vertices(which):
+    s = statement(which)
+    nodes, ntri, widest, mapped = DUALS[which]
+    worst = inverse_scale(s).max()
+    print(which, 'patches', int(s['has'].sum()), 'max |N^-1| =', worst,
+          'max |row sum - 1| =', s['row_sum'], 'max sum |S| =', s['sum_abs'],
+          'L2 ratio', s['l2'] / s['l2_bilinear'], 'max ratio',
+          s['max'] / s['max_bilinear'])
+    assert s['row_sum'] <= 1e-13
+    assert worst <= 1000.0
+    assert s['sum_abs'] <= 4.0
+    check_rows(s)
+    assert s['unmapped_entries'] == 0
+    assert len(s['xyz']) == nodes and len(s['tri']) == ntri
+    assert s['count'].max() == widest and s['mapped'] == mapped
+    assert 12 < s['per_row_max'] <= 3 * 17
+    assert s['l2'] <= 0.6 * s['l2_bilinear']
+    assert s['max'] <= 1.05 * s['max_bilinear']
+
+
+def normal_matrices(xyz, ring, nodes):
+    """N of ``nodes`` in long double, from positions, frames and h rebuilt in
+    long double: the statement's definition, none of its arithmetic."""
+    LD = np.longdouble
+    r = xyz.astype(LD)
+    members = np.concatenate([nodes[:, None], ring[nodes].astype(np.int64)],
+                             axis=1)
+    valid = members >= 0
+    c = r[nodes]
+    ref = np.where((np.abs(xyz[nodes, 2]) < 0.9)[:, None], [[0.0, 0.0, 1.0]],
+                   [[1.0, 0.0, 0.0]]).astype(LD)
+    e1 = np.cross(ref, c)
+    e1 /= np.sqrt((e1 * e1).sum(axis=1))[:, None]
+    e2 = np.cross(c, e1)
+    m = r[np.where(valid, members, 0)]
+    t = (m * c[:, None]).sum(axis=-1)
+    x = (m * e1[:, None]).sum(axis=-1) / t
+    y = (m * e2[:, None]).sum(axis=-1) / t
+    h = np.sqrt(np.where(valid, x * x + y * y, LD(0))).max(axis=1)
+    x, y = x / h[:, None], y / h[:, None]
+    phi = np.where(valid[..., None], np.stack(
+        [np.ones_like(x), x, y, x * x, x * y, y * y], axis=-1), LD(0))
+    N = (phi[:, :, :, None] * phi[:, :, None, :]).sum(axis=1)
+    return N, h, (np.where(valid, t, LD(1)) > 0.5).all(axis=1)
+
+
+def pivot_ratios(which):
+    """The smallest Cholesky pivot ratio d_k / N_kk, in long double, of every
+    node that the other rules of patch_fits leave (members, ring width, the
+    60 degree rule)."""
+    from pyremap_amd.weights import PATCH_MAX_RING
+    s = statement(which)
+    nodes = np.nonzero((s['count'] >= 5) &
+                       (s['count'] <= PATCH_MAX_RING))[0]
+    N, _, near = normal_matrices(s['xyz'], s['ring'], nodes)
+    N = N[near]
+    L = np.zeros_like(N)
+    ratio = np.full(len(N), np.inf, dtype=np.longdouble)
+    for k in range(6):
+        d = N[:, k, k] - (L[:, k, :k] ** 2).sum(axis=1)
+        ratio = np.minimum(ratio, d / N[:, k, k])
+        L[:, k, k] = np.sqrt(np.where(d > 0, d, 1))
+        for i in range(k + 1, 6):
+            L[:, i, k] = (N[:, i, k] - (L[:, i, :k] * L[:, k, :k]).sum(
+                axis=1)) / L[:, k, k]
+    return nodes[near], ratio
+
+
+@pytest.mark.parametrize('which', ['qu240', 'qu240-edge', 'qu240-vertex'])
+def test_no_pivot_ratio_lies_near_the_threshold(which):
+    """A ``has`` decision must not depend on the rounding of one fp64
+    evaluation: no node within a factor 1.25 of PATCH_PIVOT, and the decision
+    of the statement is the long-double one."""
+    from pyremap_amd.weights import PATCH_PIVOT
+    assert PATCH_PIVOT == 1e-2
+    nodes, ratio = pivot_ratios(which)
+    below, above = ratio[ratio <= PATCH_PIVOT], ratio[ratio > PATCH_PIVOT]
+    print(which, len(nodes), 'nodes;', len(below), 'below the threshold, the '
+          'largest', below.max() if len(below) else None, '; the smallest '
+          'above', above.min())
+    assert not ((ratio >= PATCH_PIVOT / 1.25) &
+                (ratio <= PATCH_PIVOT * 1.25)).any()
+    has = statement(which)['has']
+    assert np.array_equal(np.nonzero(has)[0], nodes[ratio > PATCH_PIVOT])
+
+
+@pytest.mark.parametrize('which', sorted(DUALS))
+def test_fits_of_the_duals_against_an_independent_inverse(which):
+    """``fit`` against numpy.linalg.inv of N rebuilt in long double (and
+    rounded once to fp64 for LAPACK): within 1e-10 x max |N^-1| of the node,
+    the bound tests/test_gpu_patch.py holds the kernel to."""
+    s = statement(which)
+    nodes = np.nonzero(s['has'])[0]
+    N, h, near = normal_matrices(s['xyz'], s['ring'], nodes)
+    assert near.all()
+    want = np.linalg.inv(N.astype(np.float64))
+    iu = np.triu_indices(6)
+    scale = inverse_scale(s)[nodes]
+    diff = np.abs(s['fit'][nodes, 1:] - want[:, iu[0], iu[1]]).max(axis=1)
+    dh = np.abs(s['fit'][nodes, 0] - h.astype(np.float64)).max()
+    print(which, len(nodes), 'fits: max |d N^-1| / max |N^-1| =',
+          (diff / scale).max(), 'max |dh| =', dh)
+    assert (diff <= 1e-10 * scale).all()
+    assert dh <= 1e-15
+
+
 @pytest.mark.parametrize('which, masked', [(8, False), (8, True),
-                                           ('qu240', False)])
+                                           ('qu240', False),
+                                           ('qu240-edge', False),
+                                           ('qu240-vertex', False)])
 def test_a_constant_comes_back(which, masked):
     s = statement(which, masked)
     got = np.bincount(s['row'], weights=s['S'] * 3.25,
@@ -277,6 +419,77 @@ def test_a_ring_of_more_than_sixteen_has_no_patch():
     row, col, S = patch_entries(xyz, tri, ring, count, fit, has, found, w,
                                 pts)
     assert len(S) == 21 and np.array_equal(row, np.repeat(np.arange(7), 3))
+
+
+def two_ring_fan(n):
+    """A hub (node 0), an inner ring of n nodes at 0.10 rad (1 .. n) and an
+    outer ring of 2 n nodes at 0.20 rad: the hub's ring is the n inner nodes,
+    an inner node's the hub, two inner and three outer nodes."""
+    from pyremap_amd.weights import _unit
+    xyz = np.concatenate([_unit(np.array(0.3), np.array(0.7))[None],
+                          small_circle(n, 0.10), small_circle(2 * n, 0.20)])
+    tri = []
+    for i in range(n):
+        a, b = 1 + i, 1 + (i + 1) % n
+        o0, o1, o2 = (1 + n + (2 * i + k) % (2 * n) for k in range(3))
+        tri += [[0, a, b], [a, o0, o1], [a, o1, b], [b, o1, o2]]
+    return xyz, np.array(tri)
+
+
+def fan_points(count=200):
+    """Points inside the hub's triangles of :func:`two_ring_fan` (n >= 15:
+    the inner polygon's apothem is 0.0978)."""
+    rng = np.random.default_rng(11)
+    return np.concatenate([
+        small_circle(1, r, phase=t) for r, t in
+        zip(rng.uniform(0.005, 0.09, count),
+            rng.uniform(0.0, 2.0 * np.pi, count))])
+
+
+@functools.lru_cache(maxsize=None)
+def fan_statement(n):
+    """The numpy statement on :func:`two_ring_fan` and :func:`fan_points`."""
+    from pyremap_amd import weights
+    xyz, tri = two_ring_fan(n)
+    pts = fan_points()
+    ring, count = weights.node_rings(tri, len(xyz))
+    fit, has = weights.patch_fits(xyz, ring, count)
+    found, w = weights.locate_in_triangles(xyz, tri, pts)
+    row, col, S = weights.patch_entries(xyz, tri, ring, count, fit, has,
+                                        found, w, pts)
+    out = dict(xyz=xyz, tri=tri, pts=pts, ring=ring, count=count, fit=fit,
+               has=has, found=found, w=w, row=row, col=col, S=S)
+    out.update(figures(xyz, tri, found, w, row, col, S, pts))
+    return out
+
+
+@pytest.mark.parametrize('n', [15, 16, 17])
+def test_a_two_ring_fan_walks_a_full_member_list(n):
+    """The hub of n = 16 has the widest ring that is served: 17 members in
+    one list of the merge, rows of 17 + 5 entries."""
+    s = fan_statement(n)
+    count, has = s['count'], s['has']
+    assert (s['found'] >= 0).all() and (s['found'] % 4 == 0).all()
+    assert count[0] == n and (count[1:n + 1] == 6).all()
+    assert set(count[n + 1:]) == {3, 4}
+    assert has[0] == (n <= 16) and not has[n + 1:].any()
+    per_row = np.bincount(s['row'], minlength=200)
+    print(n, 'max |N^-1| =', np.abs(s['fit'][:, 1:]).max(), 'row sum',
+          s['row_sum'], 'entries a row', set(per_row), 'sum |S|',
+          s['sum_abs'])
+    assert has[1:n + 1].all()
+    assert s['row_sum'] <= 1e-13
+    if n <= 16:
+        assert (per_row == n + 6).all()
+        assert np.abs(s['fit'][:, 1:]).max() <= 100.0
+        assert s['sum_abs'] <= 4.0
+        assert s['l2'] < s['l2_bilinear']
+    else:
+        assert (s['fit'][0] == 0.0).all() and (per_row == 3).all()
+        rows = s['S'].reshape(200, 3)
+        order = np.argsort(s['tri'][s['found']], axis=1)
+        assert rows.tobytes() == np.take_along_axis(
+            s['w'], order, axis=1).tobytes()
 
 
 def test_a_tetrahedron_falls_back_everywhere():
