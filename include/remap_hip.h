@@ -1202,6 +1202,45 @@ int remap_nearest_timed(const double *src_xyz, int64_t n_src,
 
 /*
  * ---------------------------------------------------------------------------
+ * The k nearest source points of every destination point: the search behind
+ * ESMF's `--extrap_method neareststod | nearestidavg`.  Inputs and d2 as for
+ * remap_nearest() above.  Row i of idx_out / d2_out, both (n_dst, k) in C
+ * order, holds the min(k, n_src) sources that come first in (d2(i, j), j)
+ * lexicographic order, ascending: 0-based index and d2.  The slots behind
+ * them (k > n_src) hold index -1 and d2 = +inf.  Exact, a pure function of
+ * the inputs; k = 1 gives remap_nearest()'s indices.
+ *
+ * The same sort and tree; the walk keeps each lane's k best in LDS beside
+ * its stack and skips a box only when its bound is STRICTLY greater than the
+ * k-th best d2 so far (never while fewer than k are held).  No atomics: two
+ * calls give identical bytes.  Asynchronous on `stream`, nothing is read
+ * back; the workspace is remap_nearest()'s, whatever k.
+ *
+ *   REMAP_ERR_ARG        a NULL array, n_src < 1, n_dst < 0, n_src > 2^31 - 1,
+ *                        k outside 1 .. REMAP_NEAREST_K_MAX
+ *   REMAP_ERR_WORKSPACE  workspace_bytes below remap_nearest_k_workspace()'s
+ *   n_dst == 0           REMAP_OK, nothing is launched
+ * ---------------------------------------------------------------------------
+ */
+#define REMAP_NEAREST_K_MAX 16
+
+/* (as remap_nearest_workspace: call it with the device current that
+ * remap_nearest_k() will run on) */
+REMAP_API
+int remap_nearest_k_workspace(int64_t n_src, int64_t n_dst, int32_t k,
+                              size_t *bytes_out);
+
+/*
+ *   src_xyz, dst_xyz, idx_out, d2_out, workspace (device)
+ */
+REMAP_API
+int remap_nearest_k(const double *src_xyz, int64_t n_src,
+                    const double *dst_xyz, int64_t n_dst, int32_t k,
+                    int32_t *idx_out, double *d2_out, void *workspace,
+                    size_t workspace_bytes, void *stream);
+
+/*
+ * ---------------------------------------------------------------------------
  * Point location in spherical triangles: the search behind `bilinear` maps
  * from an MPAS mesh (the triangles of its dual mesh).  xyz (n_nodes, 3) fp64,
  * tri (n_tri, 3) int32 node ids (0-based), points (n_pts, 3) fp64, all C

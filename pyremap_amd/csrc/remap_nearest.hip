@@ -42,6 +42,33 @@
 // the leaf size, the fan-out nor the sort: only the speed does.  The stack
 // keeps a node's bound as a float rounded DOWN (<= the bound): the test at
 // the pop prunes a little less than the fp64 bound would, never more.
+//
+// The k nearest (remap_nearest_k, 1 <= k <= REMAP_NEAREST_K_MAX).  Row i of
+// the output holds the min(k, n_src) sources that come first in (d2(i, j), j)
+// lexicographic order, ascending; the slots behind them hold index -1 and
+// d2 = +inf.  k = 1 is remap_nearest's answer.  Everything before the walk
+// is shared (build_tree); nearest_k_walk is nearest_walk with "best" read as
+// "k-th best":
+//   * beside the stack a lane keeps its k best in LDS, [entry][lane], d2
+//     (fp64) then index (int32), ascending in (d2, index).  Every slot starts
+//     as (+inf, 0xffffffff), which sorts behind any source (an index is at
+//     most 2^31 - 2) and IS the padding of the definition, so "the list is
+//     full" needs no counter: until k sources are in, the k-th best d2 is
+//     +inf and no bound exceeds it.
+//   * the k-th best (d2, index) -- the last slot -- is mirrored in registers.
+//     A source enters when it is lexicographically below it: it is put in
+//     its place, the slots behind it move one down and the last drops out.
+//   * a node is dropped only when its bound is STRICTLY greater than the
+//     k-th best d2.  fl(bound) <= fl(d2(s)) for every s in the box (above),
+//     so a dropped box holds only sources with d2 > the k-th best d2 at that
+//     moment, and the k-th best only ever decreases: none of them belongs to
+//     the final k.  A box whose bound EQUALS the k-th best d2 may hold a
+//     source of that d2 with a lower index, so it is kept.  The final list
+//     is therefore the k smallest of ALL (d2, j) pairs, whatever the
+//     traversal order, the leaf size, the fan-out and the sort.
+//   * the 64 lists of a block leave through LDS: the block's part of the
+//     (n_dst, k) row-major outputs is contiguous, and lane t stores its
+//     elements t, t + 64, ...
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -70,6 +97,11 @@ constexpr int64_t kWalkChunk = int64_t(1) << 30;
 static_assert(kFan == 4, "nearest_walk sorts four children by hand");
 static_assert(stack_depth(kMaxLevels) * kWalkBlock * 8 <= 64 * 1024,
               "the walk's stack must fit in a workgroup's LDS");
+// nearest_k_walk's list beside the stack: 12 bytes an entry and lane
+constexpr size_t list_bytes(int k) { return size_t(k) * kWalkBlock * 12; }
+static_assert(stack_depth(kMaxLevels) * kWalkBlock * 8 +
+                      list_bytes(REMAP_NEAREST_K_MAX) <= 64 * 1024,
+              "the k-walk's stack and list must fit in a workgroup's LDS");
 
 struct Layout {
     Tree tree;
@@ -283,6 +315,150 @@ __global__ __launch_bounds__(kWalkBlock) void nearest_walk(
     nearest[w] = static_cast<int32_t>(best_i);
 }
 
+// (d, i) before (dq, iq) in the order of the definition
+__device__ inline bool comes_first(double d, uint32_t i, double dq,
+                                   uint32_t iq)
+{
+    return d < dq || (d == dq && i < iq);
+}
+
+// one lane per destination point: its k nearest (see the file's head).  The
+// LDS holds the lists' d2 (k entries a lane), their indices, then the stack
+// as in nearest_walk.
+__global__ __launch_bounds__(kWalkBlock) void nearest_k_walk(
+    Tree T, int64_t n_src, const double *__restrict__ sorted,
+    const uint32_t *__restrict__ orig, const double *__restrict__ boxes,
+    int64_t n_dst, const double *__restrict__ dst, int k,
+    int32_t *__restrict__ idx_out, double *__restrict__ d2_out)
+{
+    extern __shared__ double list_lds[];
+    double (*list_d)[kWalkBlock] =
+        reinterpret_cast<double (*)[kWalkBlock]>(list_lds);
+    uint32_t *words = reinterpret_cast<uint32_t *>(list_lds + k * kWalkBlock);
+    uint32_t (*list_i)[kWalkBlock] =
+        reinterpret_cast<uint32_t (*)[kWalkBlock]>(words);
+    uint32_t (*stack_node)[kWalkBlock] =
+        reinterpret_cast<uint32_t (*)[kWalkBlock]>(words + k * kWalkBlock);
+    float (*stack_bound)[kWalkBlock] = reinterpret_cast<float (*)[kWalkBlock]>(
+        words + (k + stack_depth(T.levels)) * kWalkBlock);
+    const int lane = threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * kWalkBlock;
+    const int64_t w = base + lane;
+    if (w < n_dst) {
+        const double px = dst[3 * w], py = dst[3 * w + 1], pz = dst[3 * w + 2];
+        for (int q = 0; q < k; ++q) {
+            list_d[q][lane] = __builtin_huge_val();
+            list_i[q][lane] = 0xffffffffu;
+        }
+        // the k-th best so far: the list's last slot
+        double kth = __builtin_huge_val();
+        uint32_t kth_i = 0xffffffffu;
+        int top = 0;
+        uint32_t cur = static_cast<uint32_t>(T.levels - 1) << kNodeBits;
+        bool have = true;
+        for (;;) {
+            if (!have) {
+                if (top == 0)
+                    break;
+                --top;
+                // (the float is at most the node's bound: the file's head)
+                if (static_cast<double>(stack_bound[top][lane]) > kth)
+                    continue;
+                cur = stack_node[top][lane];
+            }
+            have = false;
+            const int l = static_cast<int>(cur >> kNodeBits);
+            const int64_t node = cur & kNodeMask;
+            if (l == 0) {
+                const int64_t p0 = node * kLeaf;
+                const int64_t p1 = p0 + kLeaf < n_src ? p0 + kLeaf : n_src;
+                for (int64_t p = p0; p < p1; ++p) {
+                    const double dx = sorted[3 * p] - px;
+                    const double dy = sorted[3 * p + 1] - py;
+                    const double dz = sorted[3 * p + 2] - pz;
+                    const double d = (dx * dx + dy * dy) + dz * dz;
+                    const uint32_t i = orig[p];
+                    if (!comes_first(d, i, kth, kth_i))
+                        continue;
+                    // into its place; the last slot drops out
+                    int q = k - 1;
+                    while (q > 0) {
+                        const double dq = list_d[q - 1][lane];
+                        const uint32_t iq = list_i[q - 1][lane];
+                        if (!comes_first(d, i, dq, iq))
+                            break;
+                        list_d[q][lane] = dq;
+                        list_i[q][lane] = iq;
+                        --q;
+                    }
+                    list_d[q][lane] = d;
+                    list_i[q][lane] = i;
+                    kth = list_d[k - 1][lane];
+                    kth_i = list_i[k - 1][lane];
+                }
+                continue;
+            }
+            const int64_t n_below = T.count[l - 1];
+            const double *below = boxes + T.first[l - 1] * 6;
+            const int64_t c0 = node * kFan;
+            const uint32_t tag = static_cast<uint32_t>(l - 1) << kNodeBits;
+            // a child is kept when its bound does not exceed the k-th best;
+            // one that is dropped, or that the level does not hold, sorts
+            // last
+            double b[kFan];
+            uint32_t kn[kFan];
+#pragma unroll
+            for (int q = 0; q < kFan; ++q) {
+                const int64_t c = c0 + q;
+                b[q] = __builtin_huge_val();
+                kn[q] = kNone;
+                if (c < n_below) {
+                    const double bound = box_bound(below + c * 6, px, py, pz);
+                    if (bound <= kth) {
+                        b[q] = bound;
+                        kn[q] = tag | static_cast<uint32_t>(c);
+                    }
+                }
+            }
+            order2(b[0], kn[0], b[1], kn[1]);
+            order2(b[2], kn[2], b[3], kn[3]);
+            order2(b[0], kn[0], b[2], kn[2]);
+            order2(b[1], kn[1], b[3], kn[3]);
+            order2(b[1], kn[1], b[2], kn[2]);
+            // (as in nearest_walk: the tests are on kn, not on the position)
+            int first = kFan;
+#pragma unroll
+            for (int q = kFan - 1; q >= 0; --q)
+                if (kn[q] != kNone)
+                    first = q;
+#pragma unroll
+            for (int q = kFan - 1; q >= 0; --q) {
+                if (kn[q] == kNone)
+                    continue;
+                if (q == first) {
+                    cur = kn[q];
+                    have = true;
+                } else {
+                    stack_node[top][lane] = kn[q];
+                    stack_bound[top][lane] = __double2float_rd(b[q]);
+                    ++top;
+                }
+            }
+        }
+    }
+    // every lane of the block is here: the lists leave as whole rows, element
+    // e of the block's part is slot e % k of lane e / k
+    __syncthreads();
+    const int64_t rest = n_dst - base;
+    const int rows = rest < kWalkBlock ? static_cast<int>(rest) : kWalkBlock;
+    const int64_t out = base * k;
+    for (int e = lane; e < rows * k; e += kWalkBlock) {
+        const int r = e / k, s = e - r * k;
+        idx_out[out + e] = static_cast<int32_t>(list_i[s][r]);
+        d2_out[out + e] = list_d[s][r];
+    }
+}
+
 int check_args(const double *src_xyz, int64_t n_src, const double *dst_xyz,
                int64_t n_dst, const int32_t *nearest_out)
 {
@@ -296,10 +472,18 @@ int check_args(const double *src_xyz, int64_t n_src, const double *dst_xyz,
     return REMAP_OK;
 }
 
-// the three phases; ev (NULL, or 4 events) is recorded around them
-int run(const Layout &lay, const double *src_xyz, int64_t n_src,
-        const double *dst_xyz, int64_t n_dst, int32_t *nearest_out,
-        void *workspace, hipStream_t stream, hipEvent_t *ev)
+// what a walk reads in the workspace once build_tree() has run
+struct Built {
+    const double *sorted;
+    const uint32_t *orig;
+    const double *boxes;
+};
+
+// the two phases before a walk: sort and boxes; ev (NULL, or at least 3
+// events) is recorded around them
+int build_tree(const Layout &lay, const double *src_xyz, int64_t n_src,
+               void *workspace, hipStream_t stream, hipEvent_t *ev,
+               Built *built)
 {
     char *ws = static_cast<char *>(workspace);
     uint64_t *keys_in = reinterpret_cast<uint64_t *>(ws + lay.keys_in);
@@ -309,6 +493,9 @@ int run(const Layout &lay, const double *src_xyz, int64_t n_src,
     double *sorted = reinterpret_cast<double *>(ws + lay.xyz);
     double *boxes = reinterpret_cast<double *>(ws + lay.boxes);
     const Tree &T = lay.tree;
+    built->sorted = sorted;
+    built->orig = idx_out;
+    built->boxes = boxes;
 
     if (ev)
         REMAP_HIP_CHECK(hipEventRecord(ev[0], stream));
@@ -339,17 +526,54 @@ int run(const Layout &lay, const double *src_xyz, int64_t n_src,
     }
     if (ev)
         REMAP_HIP_CHECK(hipEventRecord(ev[2], stream));
+    return REMAP_OK;
+}
+
+// the three phases; ev (NULL, or 4 events) is recorded around them
+int run(const Layout &lay, const double *src_xyz, int64_t n_src,
+        const double *dst_xyz, int64_t n_dst, int32_t *nearest_out,
+        void *workspace, hipStream_t stream, hipEvent_t *ev)
+{
+    Built t;
+    const int rc = build_tree(lay, src_xyz, n_src, workspace, stream, ev, &t);
+    if (rc != REMAP_OK)
+        return rc;
+    const Tree &T = lay.tree;
     const size_t lds = size_t(stack_depth(T.levels)) * kWalkBlock * 8;
     for (int64_t at = 0; at < n_dst; at += kWalkChunk) {
         const int64_t m = n_dst - at < kWalkChunk ? n_dst - at : kWalkChunk;
         const dim3 grid(blocks(m, kWalkBlock)), block(kWalkBlock);
         hipLaunchKernelGGL(nearest_walk, grid, block, lds, stream, T, n_src,
-                           sorted, idx_out, boxes, m, dst_xyz + 3 * at,
+                           t.sorted, t.orig, t.boxes, m, dst_xyz + 3 * at,
                            nearest_out + at);
         REMAP_HIP_CHECK(hipGetLastError());
     }
     if (ev)
         REMAP_HIP_CHECK(hipEventRecord(ev[3], stream));
+    return REMAP_OK;
+}
+
+// sort, boxes, then the k-walk
+int run_k(const Layout &lay, const double *src_xyz, int64_t n_src,
+          const double *dst_xyz, int64_t n_dst, int k, int32_t *idx_out,
+          double *d2_out, void *workspace, hipStream_t stream)
+{
+    Built t;
+    const int rc = build_tree(lay, src_xyz, n_src, workspace, stream, nullptr,
+                              &t);
+    if (rc != REMAP_OK)
+        return rc;
+    const Tree &T = lay.tree;
+    const size_t lds = list_bytes(k) +
+        size_t(stack_depth(T.levels)) * kWalkBlock * 8;
+    for (int64_t at = 0; at < n_dst; at += kWalkChunk) {
+        const int64_t m = n_dst - at < kWalkChunk ? n_dst - at : kWalkChunk;
+        const dim3 grid(blocks(m, kWalkBlock)), block(kWalkBlock);
+        hipLaunchKernelGGL(nearest_k_walk, grid, block, lds, stream, T, n_src,
+                           t.sorted, t.orig, t.boxes, m, dst_xyz + 3 * at, k,
+                           idx_out + at * k, d2_out + at * k);
+        REMAP_HIP_CHECK(hipGetLastError());
+    }
     return REMAP_OK;
 }
 
@@ -409,9 +633,66 @@ int nearest(const double *src_xyz, int64_t n_src, const double *dst_xyz,
     return REMAP_OK;
 }
 
+int nearest_k_workspace(int64_t n_src, int64_t n_dst, int32_t k,
+                        size_t *bytes_out)
+{
+    if (!bytes_out || n_src < 1 || n_dst < 0 || n_src > INT32_MAX || k < 1 ||
+        k > REMAP_NEAREST_K_MAX)
+        return fail(REMAP_ERR_ARG, "remap_nearest_k_workspace: bad args");
+    Layout lay;
+    const int rc = make_layout(n_src, &lay);
+    if (rc != REMAP_OK)
+        return rc;
+    *bytes_out = lay.total;
+    return REMAP_OK;
+}
+
+int nearest_k(const double *src_xyz, int64_t n_src, const double *dst_xyz,
+              int64_t n_dst, int32_t k, int32_t *idx_out, double *d2_out,
+              void *workspace, size_t workspace_bytes, hipStream_t stream)
+{
+    if (n_src < 1 || n_dst < 0 || n_src > INT32_MAX || k < 1 ||
+        k > REMAP_NEAREST_K_MAX)
+        return fail(REMAP_ERR_ARG,
+                    "remap_nearest_k: n_src %lld (1 .. 2^31 - 1), n_dst %lld "
+                    "(>= 0), k %d (1 .. %d)", static_cast<long long>(n_src),
+                    static_cast<long long>(n_dst), static_cast<int>(k),
+                    REMAP_NEAREST_K_MAX);
+    if (!src_xyz || (n_dst > 0 && (!dst_xyz || !idx_out || !d2_out)))
+        return fail(REMAP_ERR_ARG, "remap_nearest_k: NULL array");
+    Layout lay;
+    const int rc = make_layout(n_src, &lay);
+    if (rc != REMAP_OK)
+        return rc;
+    if (!workspace || workspace_bytes < lay.total)
+        return fail(REMAP_ERR_WORKSPACE,
+                    "remap_nearest_k: workspace of %zu bytes, need %zu",
+                    workspace_bytes, lay.total);
+    if (n_dst == 0)
+        return REMAP_OK;
+    return run_k(lay, src_xyz, n_src, dst_xyz, n_dst, k, idx_out, d2_out,
+                 workspace, stream);
+}
+
 }  // namespace remap
 
 extern "C" {
+
+int remap_nearest_k_workspace(int64_t n_src, int64_t n_dst, int32_t k,
+                              size_t *bytes_out)
+{
+    return remap::nearest_k_workspace(n_src, n_dst, k, bytes_out);
+}
+
+int remap_nearest_k(const double *src_xyz, int64_t n_src,
+                    const double *dst_xyz, int64_t n_dst, int32_t k,
+                    int32_t *idx_out, double *d2_out, void *workspace,
+                    size_t workspace_bytes, void *stream)
+{
+    return remap::nearest_k(src_xyz, n_src, dst_xyz, n_dst, k, idx_out,
+                            d2_out, workspace, workspace_bytes,
+                            static_cast<hipStream_t>(stream));
+}
 
 int remap_nearest_workspace(int64_t n_src, int64_t n_dst, size_t *bytes_out)
 {

@@ -17,6 +17,7 @@ raises.
 """
 import contextlib
 import ctypes
+import numbers
 import os
 
 import numpy as np
@@ -54,6 +55,8 @@ DTYPE_F32 = 1
 
 ABI_VERSION = 31
 
+#: the largest k of nearest_k_points (REMAP_NEAREST_K_MAX)
+NEAREST_K_MAX = 16
 #: readable pad entries kept behind col/val (remap_csr.csr_pad)
 CSR_PAD = 8
 #: LDS a workgroup of the lanes-across-rows kernel may take (kPatchLdsMax)
@@ -83,6 +86,7 @@ EXPORTS = (
     'remap_overlap_pieces_timed',
     'remap_overlap_grids_sizes', 'remap_overlap_grids',
     'remap_nearest_workspace', 'remap_nearest', 'remap_nearest_timed',
+    'remap_nearest_k_workspace', 'remap_nearest_k',
     'remap_locate_workspace', 'remap_locate', 'remap_locate_timed',
     'remap_quads_workspace', 'remap_quads', 'remap_quads_timed',
     'remap_expand_cells',
@@ -506,6 +510,15 @@ def load_library():
         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
         ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
+    lib.remap_nearest_k_workspace.restype = ctypes.c_int
+    lib.remap_nearest_k_workspace.argtypes = [
+        ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+        ctypes.POINTER(ctypes.c_size_t)]
+    lib.remap_nearest_k.restype = ctypes.c_int
+    lib.remap_nearest_k.argtypes = [
+        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+        ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_size_t, ctypes.c_void_p]
     lib.remap_locate_workspace.restype = ctypes.c_int
     lib.remap_locate_workspace.argtypes = [
         ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
@@ -2638,6 +2651,60 @@ def nearest_points(src_xyz, dst_xyz, timing=None, phases=False):
         # for this stream: later work on the stream is ordered behind the walk
         del ws
     return out
+
+
+def nearest_k_points(src_xyz, dst_xyz, k, timing=None):
+    """
+    The ``k`` nearest source points of every destination point, through
+    ``remap_nearest_k`` (``include/remap_hip.h``): ``(idx, d2)``, an
+    ``int32`` and a ``float64`` tensor of shape ``(n_dst, k)``.  Row ``i``
+    holds the ``min(k, n_src)`` sources that come first in ``(d2, index)``
+    order, ascending, with ``d2`` as in :func:`nearest_points`; the slots
+    behind them hold index -1 and ``d2`` = +inf.  The tensors are as for
+    :func:`nearest_points`, ``k`` is 1 .. ``NEAREST_K_MAX``; exact, two calls
+    give identical bytes, ``k = 1`` gives :func:`nearest_points`' indices.
+    Asynchronous on the current stream.  ``timing``: a dict that receives
+    the GPU ``ms`` of the call.
+    """
+    torch = require_gpu()
+    lib = load_library()
+    for name, t in (('src_xyz', src_xyz), ('dst_xyz', dst_xyz)):
+        if not torch.is_tensor(t) or not t.is_cuda or \
+                t.dtype != torch.float64 or t.dim() != 2 or \
+                t.shape[1] != 3 or not t.is_contiguous():
+            raise ValueError(
+                f'{name}: expected a contiguous (n, 3) float64 tensor on a '
+                f'HIP device')
+    if src_xyz.device != dst_xyz.device:
+        raise ValueError(
+            f'src_xyz on {src_xyz.device}, dst_xyz on {dst_xyz.device}: '
+            f'expected one device')
+    n_src, n_dst = src_xyz.shape[0], dst_xyz.shape[0]
+    if n_src < 1:
+        raise ValueError('nearest_k_points needs at least one source point')
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or \
+            not 1 <= k <= NEAREST_K_MAX:
+        raise ValueError(f'k = {k!r}: expected an integer from 1 to '
+                         f'{NEAREST_K_MAX}')
+    k = int(k)
+    dev = src_xyz.device
+    with torch.cuda.device(dev):
+        stream = _stream_ptr(dev)
+        nbytes = ctypes.c_size_t()
+        _check(lib.remap_nearest_k_workspace(n_src, n_dst, k,
+                                             ctypes.byref(nbytes)),
+               'remap_nearest_k_workspace')
+        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        idx = torch.empty((n_dst, k), dtype=torch.int32, device=dev)
+        d2 = torch.empty((n_dst, k), dtype=torch.float64, device=dev)
+        with _gpu_ms(torch, timing):
+            _check(lib.remap_nearest_k(
+                _ptr(src_xyz), n_src, _ptr(dst_xyz), n_dst, k, _ptr(idx),
+                _ptr(d2), _ptr(ws), nbytes.value, stream), 'remap_nearest_k')
+        # (as in nearest_points: torch's allocator keeps the workspace for
+        # this stream)
+        del ws
+    return idx, d2
 
 
 # ---------------------------------------------------------------------------

@@ -60,6 +60,12 @@ class Remapper:
         self.use_tmp = use_tmp
         self.expand_dist = None
         self.expand_factor = None
+        #: ESMF's --extrap_method ('neareststod' | 'nearestidavg'),
+        #: --extrap_num_src_pnts and --extrap_dist_exponent for the analytic
+        #: bilinear and patch maps (build_map)
+        self.extrap_method = None
+        self.extrap_num_src_pnts = 8
+        self.extrap_dist_exponent = 2.0
         self.src_scrip_filename = 'src_mesh.nc'
         self.dst_scrip_filename = 'dst_mesh.nc'
         self.format = 'NETCDF3_64BIT_DATA'
@@ -197,6 +203,17 @@ class Remapper:
         bilinear weights, third-order where ``bilinear`` is second-order;
         rings, fits and rows on the GPU
         (:func:`pyremap_amd.weights.patch_mesh_weights`).
+        ``extrap_method`` (``'neareststod'`` or ``'nearestidavg'``, ESMF's
+        ``--extrap_method``; set after construction, default ``None``) fills
+        the destination points a ``bilinear`` or ``patch`` map leaves
+        unmapped -- land, the rim of a regional source -- from the nearest
+        source point, or from the inverse-distance average of the
+        ``extrap_num_src_pnts`` (default 8, at most 16) nearest with the
+        exponent ``extrap_dist_exponent`` (default 2.0): an exact k-nearest
+        search over all source points, on the GPU where one is present
+        (:func:`pyremap_amd.weights.extrapolate`).  Every destination point
+        is then mapped; the file records the three values.  Other methods
+        with ``extrap_method`` set raise.
         """
         from pyremap_amd.remapper.setup import _setup_remapper
         if self.map_tool != 'analytic':
@@ -222,14 +239,17 @@ class Remapper:
         if logger is not None:
             logger.info(f'analytic {self.method} weights -> '
                         f'{self.map_filename}')
-        if self.expand_dist is None and self.expand_factor is None:
-            write_weights(self.map_filename, self.src_descriptor,
-                          self.dst_descriptor, self.method)
-        else:
-            write_weights(self.map_filename, self.src_descriptor,
-                          self.dst_descriptor, self.method,
-                          expand_dist=self.expand_dist,
-                          expand_factor=self.expand_factor)
+        kw = {}
+        if not (self.expand_dist is None and self.expand_factor is None):
+            kw.update(expand_dist=self.expand_dist,
+                      expand_factor=self.expand_factor)
+        if self.extrap_method is not None:
+            kw['extrap_method'] = self.extrap_method
+            if self.extrap_method == 'nearestidavg':
+                kw['extrap_num_src_pnts'] = self.extrap_num_src_pnts
+                kw['extrap_dist_exponent'] = self.extrap_dist_exponent
+        write_weights(self.map_filename, self.src_descriptor,
+                      self.dst_descriptor, self.method, **kw)
         self._ds_map = None
         self._matrix = None
 

@@ -91,6 +91,14 @@ axes the common methods have closed forms:
   third-order where ``bilinear`` is second-order.  Rings, fits and rows run
   on the GPU (``pyremap_amd/csrc/remap_patch.hip``); :func:`node_rings`,
   :func:`patch_fits` and :func:`patch_entries` are the numpy statements.
+* ``extrap_method`` of :func:`make_weights` (``'neareststod'`` /
+  ``'nearestidavg'``, ESMF's ``--extrap_method``) -- the destination points a
+  ``bilinear`` or ``patch`` map leaves without a row take the nearest source
+  point, or the inverse-distance average of the k <= 16 nearest
+  (:func:`extrapolate`, :func:`extrap_rows`).  The k nearest are searched
+  exactly over ALL source points on the GPU where one is present
+  (``remap_nearest_k``, ``pyremap_amd/csrc/remap_nearest.hip``), by
+  :func:`nearest_k`, the numpy statement, otherwise: the same bytes.
 
 The result is a :class:`pyremap_amd.io.mapfile.MappingFile` with exactly the
 schema ESMF writes (1-based ``row``/``col``, Fortran-ordered grid dims), so it
@@ -2041,6 +2049,232 @@ def _cell_centres(descriptor):
         [lat.shape[1], lat.shape[0]]
 
 
+# ---------------------------------------------------------------------------
+# the k nearest sources, and ESMF's nearest-point extrapolation from them
+# ---------------------------------------------------------------------------
+
+#: the largest k of :func:`nearest_k` (REMAP_NEAREST_K_MAX)
+NEAREST_K_MAX = 16
+EXTRAP_METHODS = ('neareststod', 'nearestidavg')
+#: the methods :func:`make_weights` extrapolates
+EXTRAP_SERVED = ('bilinear', 'patch')
+#: ESMF's defaults of --extrap_num_src_pnts and --extrap_dist_exponent
+EXTRAP_NUM_SRC_PNTS = 8
+EXTRAP_DIST_EXPONENT = 2.0
+
+
+def _check_k(k):
+    if isinstance(k, (bool, np.bool_)) or \
+            not isinstance(k, (int, np.integer)) or \
+            not 1 <= k <= NEAREST_K_MAX:
+        raise ValueError(f'k = {k!r}: expected an integer from 1 to '
+                         f'{NEAREST_K_MAX}')
+    return int(k)
+
+
+def nearest_k(src_xyz, dst_xyz, k, chunk=512):
+    """
+    The numpy statement of ``remap_nearest_k`` (``include/remap_hip.h``,
+    :func:`pyremap_amd.engine.nearest_k_points`): ``(idx int32, d2 float64)``
+    of shape ``(n_dst, k)``.  With ``dx = src[j].x - dst[i].x`` (likewise y,
+    z) and ``d2(i, j) = (dx*dx + dy*dy) + dz*dz`` in fp64 in that order, row
+    ``i`` holds the ``min(k, n_src)`` sources that come first in ``(d2, j)``
+    lexicographic order, ascending; the slots behind them hold index -1 and
+    ``d2`` = +inf.  Brute force over all pairs, ``chunk`` destination points
+    at a time; the GPU walk gives the same bytes.
+    """
+    src = np.ascontiguousarray(src_xyz, dtype=np.float64)
+    dst = np.ascontiguousarray(dst_xyz, dtype=np.float64)
+    for name, a in (('src_xyz', src), ('dst_xyz', dst)):
+        if a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f'{name}: expected an (n, 3) array, not one of '
+                             f'shape {a.shape}')
+    n_src, n_dst = len(src), len(dst)
+    if n_src < 1:
+        raise ValueError('nearest_k needs at least one source point')
+    k = _check_k(k)
+    idx = np.full((n_dst, k), -1, dtype=np.int32)
+    d2 = np.full((n_dst, k), np.inf)
+    m = min(k, n_src)
+    for at in range(0, n_dst, max(int(chunk), 1)):
+        p = dst[at:at + max(int(chunk), 1)]
+        dx = src[None, :, 0] - p[:, None, 0]
+        dy = src[None, :, 1] - p[:, None, 1]
+        dz = src[None, :, 2] - p[:, None, 2]
+        d = (dx * dx + dy * dy) + dz * dz
+        j = np.broadcast_to(np.arange(n_src), d.shape)
+        order = np.lexsort((j, d), axis=-1)[:, :m]
+        idx[at:at + len(p), :m] = order
+        d2[at:at + len(p), :m] = np.take_along_axis(d, order, axis=1)
+    return idx, d2
+
+
+def extrap_rows(idx, d2, method, dist_exponent=EXTRAP_DIST_EXPONENT):
+    """
+    The entries ESMF's nearest-point extrapolation gives the points whose
+    nearest sources are ``idx`` / ``d2`` (:func:`nearest_k`: ``(n, k)``,
+    ascending, -1 / +inf behind the last source): ``(row, col, S)``, 0-based,
+    ``row`` counting the rows of ``idx``, a row's entries in slot order.
+
+    * ``'neareststod'``: the first slot with weight 1.
+    * ``'nearestidavg'``: the inverse-distance average of the valid slots,
+      ``w = 1.0 / d2 ** (0.5 * dist_exponent)`` -- the 3-D Cartesian distance
+      to the power ``dist_exponent`` --, ``S = w / w.sum()``.  A row whose
+      first ``d2`` is 0 (a coincident source, the lowest index first) is
+      that one source with weight 1.
+
+    One host function behind the GPU and the numpy path of
+    :func:`extrapolate`: the entries are the same bytes on both.
+    """
+    idx = np.asarray(idx)
+    d2 = np.asarray(d2, dtype=np.float64)
+    if idx.ndim != 2 or idx.shape != d2.shape or idx.shape[1] < 1:
+        raise ValueError(f'idx {idx.shape} and d2 {d2.shape}: expected two '
+                         f'(n, k) arrays, k >= 1')
+    if method not in EXTRAP_METHODS:
+        raise ValueError(f'extrap_method {method!r}: expected one of '
+                         f'{EXTRAP_METHODS}')
+    n = len(idx)
+    if n and (idx[:, 0] < 0).any():
+        raise ValueError('a row without a source: nothing to extrapolate '
+                         'from')
+    if method == 'neareststod':
+        return np.arange(n, dtype=np.int64), idx[:, 0].astype(np.int64), \
+            np.ones(n)
+    p = float(dist_exponent)
+    if not np.isfinite(p) or p < 0.0:
+        raise ValueError(f'dist_exponent {dist_exponent!r}: expected a '
+                         f'finite number >= 0')
+    valid = idx >= 0
+    # a coincident source takes everything
+    valid[:, 1:] &= (d2[:, :1] != 0.0)
+    with np.errstate(divide='ignore', over='ignore'):
+        w = np.where(valid, 1.0 / d2 ** (0.5 * p), 0.0)
+    w[d2[:, 0] == 0.0, 0] = 1.0
+    S = w / w.sum(axis=1, keepdims=True)
+    row = np.broadcast_to(np.arange(n, dtype=np.int64)[:, None], idx.shape)
+    return row[valid], idx[valid].astype(np.int64), S[valid]
+
+
+def extrapolate(m, src_lat, src_lon, dst_lat, dst_lon, method,
+                num_src_pnts=EXTRAP_NUM_SRC_PNTS,
+                dist_exponent=EXTRAP_DIST_EXPONENT, device=None,
+                timing=None):
+    """
+    ``m`` (a :class:`MappingFile`) with its unmapped destination points
+    filled the way ESMF's ``--extrap_method neareststod | nearestidavg``
+    fills them: every destination row WITHOUT an entry is searched against
+    ALL source points (``src_lat`` / ``src_lon``, radians, in the numbering
+    of ``col``; the destination's likewise in the numbering of ``row``) for
+    its nearest (``neareststod``) or its ``num_src_pnts`` nearest
+    (``nearestidavg``, weighted by distance to the power
+    ``-dist_exponent``) in 3-D Cartesian distance on the unit sphere
+    (:func:`extrap_rows`).  Their entries are merged into the map, sorted by
+    (row, col), and ``frac_b`` of those rows becomes 1; rows that had
+    entries keep them to the bit.  With ``neareststod`` the two numbers play
+    no part, as in ESMF.
+
+    Only the unmapped points are searched: on the GPU where one is present
+    (:func:`pyremap_amd.engine.nearest_k_points`), with :func:`nearest_k`
+    otherwise -- the same bytes.  A map that is already complete is
+    returned as it is.  ``timing``: passed on to the engine call.
+    """
+    if method not in EXTRAP_METHODS:
+        raise ValueError(f'extrap_method {method!r}: expected one of '
+                         f'{EXTRAP_METHODS}')
+    k = 1 if method == 'neareststod' else _check_k(num_src_pnts)
+    arrays = []
+    for name, a, n in (('src_lat', src_lat, m.n_a), ('src_lon', src_lon, m.n_a),
+                       ('dst_lat', dst_lat, m.n_b), ('dst_lon', dst_lon, m.n_b)):
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        if len(a) != n:
+            raise ValueError(f'{name} has {len(a)} points, the map {n}')
+        if not np.isfinite(a).all():
+            raise ValueError(f'{name} holds NaN or Inf: the extrapolation '
+                             f'needs finite coordinates')
+        arrays.append(a)
+    src_lat, src_lon, dst_lat, dst_lon = arrays
+    if m.n_a < 1:
+        raise ValueError('the extrapolation needs at least one source point')
+    filled = np.bincount(m.row.astype(np.int64) - 1, minlength=m.n_b) > 0
+    empty = np.nonzero(~filled)[0]
+    if len(empty) == 0:
+        return m
+    src = _unit(src_lat, src_lon)
+    dst = _unit(dst_lat[empty], dst_lon[empty])
+    if _gpu_present():
+        from pyremap_amd import engine
+        device = _device(device)
+        idx, d2 = engine.nearest_k_points(
+            _to_device(src, device), _to_device(dst, device), k,
+            timing=timing)
+        idx, d2 = idx.cpu().numpy(), d2.cpu().numpy()
+    else:
+        idx, d2 = nearest_k(src, dst, k)
+    r, c, S = extrap_rows(idx, d2, method, dist_exponent)
+    row = np.concatenate([m.row, (empty[r] + 1).astype(np.int32)])
+    col = np.concatenate([m.col, (c + 1).astype(np.int32)])
+    S = np.concatenate([m.S, S])
+    order = np.lexsort((col, row))
+    frac_b = m.frac_b.copy()
+    frac_b[empty] = 1.0
+    return MappingFile(m.n_a, m.n_b, m.src_grid_dims, m.dst_grid_dims,
+                       row[order], col[order], S[order], frac_b,
+                       **m.geometry)
+
+
+def _extrap_args(method, extrap_method, num_src_pnts, dist_exponent):
+    """None without extrapolation, else ``(extrap_method, num_src_pnts,
+    dist_exponent)`` of :func:`make_weights`, checked."""
+    if extrap_method is None:
+        if num_src_pnts is not None or dist_exponent is not None:
+            raise ValueError(
+                'extrap_num_src_pnts / extrap_dist_exponent without '
+                f'extrap_method: give one of {EXTRAP_METHODS}')
+        return None
+    if extrap_method not in EXTRAP_METHODS:
+        raise ValueError(
+            f'extrap_method {extrap_method!r}: expected one of '
+            f'{EXTRAP_METHODS} (creep is not built)')
+    if method not in EXTRAP_SERVED:
+        raise ValueError(
+            f'extrap_method with method {method!r}: unmapped points are '
+            f'extrapolated for {EXTRAP_SERVED} maps only')
+    if extrap_method == 'neareststod':
+        return extrap_method, 1, EXTRAP_DIST_EXPONENT
+    k = EXTRAP_NUM_SRC_PNTS if num_src_pnts is None else num_src_pnts
+    if isinstance(k, (bool, np.bool_)) or \
+            not isinstance(k, (int, np.integer)) or \
+            not 1 <= k <= NEAREST_K_MAX:
+        raise ValueError(f'extrap_num_src_pnts {k!r}: expected an integer '
+                         f'from 1 to {NEAREST_K_MAX}')
+    p = EXTRAP_DIST_EXPONENT if dist_exponent is None else dist_exponent
+    try:
+        p = float(p)
+    except (TypeError, ValueError):
+        p = np.nan
+    if not np.isfinite(p) or p < 0.0:
+        raise ValueError(f'extrap_dist_exponent {dist_exponent!r}: expected '
+                         f'a finite number >= 0')
+    return extrap_method, int(k), p
+
+
+def _centres_of(descriptor, side):
+    """(lat, lon) in radians of a side's points in the numbering the map's
+    ``col`` / ``row`` use: a point-like side's positions, a grid's cell
+    centres in C order."""
+    points = _points(descriptor)
+    if points is not None:
+        return points[0], points[1]
+    if isinstance(descriptor, MpasMeshDescriptor):
+        raise ValueError(
+            f'the extrapolation needs the coordinates of the {side} MPAS '
+            f'mesh: give the descriptor a mesh file or lat= / lon=, not a '
+            f'size alone')
+    lat, lon, _ = _cell_centres(descriptor)
+    return lat, lon
+
+
 def build_weights(src_descriptor, dst_descriptor, method='conserve'):
     """
     The mapping between two rectangular grids (lat-lon or on a map
@@ -2977,7 +3211,8 @@ def _make_conserve(src_descriptor, dst_descriptor):
 
 
 def make_weights(src_descriptor, dst_descriptor, method='conserve',
-                 expand_dist=None, expand_factor=None):
+                 expand_dist=None, expand_factor=None, extrap_method=None,
+                 extrap_num_src_pnts=None, extrap_dist_exponent=None):
     """
     The mapping between any pair of descriptors this module serves, as a
     :class:`MappingFile`: :func:`build_weights`, plus ``bilinear`` and
@@ -3031,11 +3266,34 @@ def make_weights(src_descriptor, dst_descriptor, method='conserve',
     destinations ``bilinear`` from such a mesh has; ``expand_dist`` /
     ``expand_factor`` change nothing.  Any other source is a ``ValueError``.
     It needs the GPU.
+
+    ``extrap_method`` (``'neareststod'`` or ``'nearestidavg'``, ESMF's
+    ``--extrap_method``; ``creep`` is not built) fills the destination points
+    a ``bilinear`` or ``patch`` map leaves without a row -- outside the
+    source's triangles or quads: land, the rim of a regional grid -- from
+    the nearest source point, or from the inverse-distance average of the
+    ``extrap_num_src_pnts`` (default 8, at most 16) nearest with the
+    distance to the power ``extrap_dist_exponent`` (default 2.0), over ALL
+    source points (:func:`extrapolate`; on the GPU where one is present).
+    It is served from every source those two methods have; the rows the
+    method mapped keep their bytes and every ``frac_b`` becomes 1.  Any
+    other ``method`` with it, an unknown name, a count outside 1 .. 16, a
+    negative or non-finite exponent, or the two numbers without
+    ``extrap_method`` are a ``ValueError``; with ``'neareststod'`` the two
+    numbers are ignored, as in ESMF.  With ``extrap_method=None`` every call
+    made is the one made without it.
     """
+    extrap = _extrap_args(method, extrap_method, extrap_num_src_pnts,
+                          extrap_dist_exponent)
     m = _make_weights(src_descriptor, dst_descriptor, method, expand_dist,
                       expand_factor)
     if not isinstance(m, MappingFile):
         return m      # (a caller's stand-in for a routed call: as it is)
+    if extrap is not None:
+        src_lat, src_lon = _centres_of(src_descriptor, 'source')
+        dst_lat, dst_lon = _centres_of(dst_descriptor, 'destination')
+        m = extrapolate(m, src_lat, src_lon, dst_lat, dst_lon, extrap[0],
+                        num_src_pnts=extrap[1], dist_exponent=extrap[2])
     return complete_mapping(m, src_descriptor, dst_descriptor, method,
                             expand_dist, expand_factor)
 
@@ -3086,25 +3344,41 @@ def _expand_attr(value, default):
 
 
 def write_weights(filename, src_descriptor, dst_descriptor,
-                  method='conserve', expand_dist=None, expand_factor=None):
+                  method='conserve', expand_dist=None, expand_factor=None,
+                  extrap_method=None, extrap_num_src_pnts=None,
+                  extrap_dist_exponent=None):
     """Build the weights (:func:`make_weights`) and write them as a mapping
     file.  With ``expand_dist`` or ``expand_factor`` given (see
     :func:`make_weights`; they shape ``conserve`` maps only) the file
     records both as global attributes of these names, ``'per cell'`` for an
-    array."""
+    array.  With ``extrap_method`` given (see :func:`make_weights`) it
+    records ``extrap_method``, ``extrap_num_src_pnts`` and
+    ``extrap_dist_exponent`` as used: 1 point and ESMF's default exponent
+    for ``'neareststod'``, where the two numbers play no part."""
     from pyremap_amd.io.mapfile import write_mapping
     attrs = {'map_method': method,
              'weight_generator': 'pyremap_amd.weights (analytic)',
              'normalization': 'destarea',
              'domain_a': str(src_descriptor.mesh_name),
              'domain_b': str(dst_descriptor.mesh_name)}
-    if expand_dist is None and expand_factor is None:
-        m = make_weights(src_descriptor, dst_descriptor, method)
-    else:
-        m = make_weights(src_descriptor, dst_descriptor, method,
-                         expand_dist=expand_dist, expand_factor=expand_factor)
+    kw = {}
+    if not (expand_dist is None and expand_factor is None):
+        kw.update(expand_dist=expand_dist, expand_factor=expand_factor)
         attrs['expand_dist'] = _expand_attr(expand_dist, 0.0)
         attrs['expand_factor'] = _expand_attr(expand_factor, 1.0)
+    if extrap_method is not None:
+        kw['extrap_method'] = extrap_method
+    if extrap_num_src_pnts is not None:
+        kw['extrap_num_src_pnts'] = extrap_num_src_pnts
+    if extrap_dist_exponent is not None:
+        kw['extrap_dist_exponent'] = extrap_dist_exponent
+    m = make_weights(src_descriptor, dst_descriptor, method, **kw)
+    if extrap_method is not None and isinstance(m, MappingFile):
+        _, k, p = _extrap_args(method, extrap_method, extrap_num_src_pnts,
+                               extrap_dist_exponent)
+        attrs['extrap_method'] = str(extrap_method)
+        attrs['extrap_num_src_pnts'] = np.int32(k)
+        attrs['extrap_dist_exponent'] = float(p)
     write_mapping(filename, m.n_a, m.n_b, m.src_grid_dims, m.dst_grid_dims,
                   m.row, m.col, m.S, m.frac_b, attrs=attrs,
                   geometry=m.geometry or None)
