@@ -1748,6 +1748,60 @@ int remap_patch_rows(int64_t n_nodes, const double *xyz, int64_t n_tri,
                      int32_t *row_out, int32_t *col_out, double *s_out,
                      int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Local-bounds limiter (csrc/remap_limit.hip; DESIGN.md section 20;
+ * pyremap_amd.limiter is the same statement in numpy).
+ *
+ * A map with signed weights (conserve2nd, patch, a signed map read from a
+ * file) overshoots at fronts.  This pass runs AFTER an apply launch, on the
+ * same stream and over the same strided layouts, and clamps every
+ * destination value to the bounds of the source values of its own row.  It
+ * re-gathers them from the CSR (rowptr, col); the weights are not read: every
+ * stored entry counts, whatever the sign or size of its weight.
+ *
+ * For destination element (i, b, k), row_begin <= i < row_end, the row's
+ * entries are walked in CSR order with x = (double)X[cell(col), b, k]:
+ *   a NaN x is skipped (+-inf are values like any other);
+ *   the first x that is no NaN sets lo = hi = x; after it
+ *   if (x < lo) lo = x; if (x > hi) hi = x;  -- strict: the first one seen
+ *   wins a tie, so -0.0 against +0.0 is decided by CSR order;
+ *   a row without an entry, or without a value that is no NaN: y stays as it
+ *   is and lo = hi = y; otherwise y = y < lo ? lo : (y > hi ? hi : y) (a NaN
+ *   y stays NaN).
+ * y is written back in place, lo / hi where those pointers are given.
+ * Elements of rows outside [row_begin, row_end) are not written.  Nothing
+ * rounds: comparisons and copies only, the result is defined to the bit.
+ *
+ * X and Y are addressed as in remap_apply_args (x_src_fold included); lo and
+ * hi like Y.  Asynchronous on `stream`; nothing is allocated, freed or
+ * synchronised.  REMAP_ERR_ARG: a NULL array that is needed, a negative
+ * stride or size, a row range outside [0, A.n_rows], an x_dtype that is no
+ * REMAP_DTYPE_*, an x_src_fold that does not divide A.n_cols, more elements
+ * than one launch serves.
+ * ---------------------------------------------------------------------------
+ */
+typedef struct remap_limit_args {
+    remap_csr A;            /* rowptr and col are read; val is not           */
+    int64_t row_begin;      /* rows [row_begin, row_end) of A are limited;   */
+    int64_t row_end;        /* Y / lo / hi are indexed by row                */
+    const void *X;          /* (device) the source field the apply read      */
+    int32_t x_dtype;        /* REMAP_DTYPE_*                                 */
+    int64_t x_row_stride;
+    int64_t x_batch_stride;
+    int64_t x_src_fold;     /* as in remap_apply_args (0: one stride)        */
+    int64_t x_outer_stride;
+    double *Y;              /* (device) what the apply left, limited in place */
+    int64_t y_row_stride;
+    int64_t y_batch_stride;
+    int64_t n_batch;
+    int64_t k_inner;
+    double *lo;             /* (device) optional, addressed like Y           */
+    double *hi;             /* (device) optional, addressed like Y           */
+} remap_limit_args;
+
+REMAP_API int remap_limit_rows(const struct remap_limit_args *args,
+                               void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,7 +97,11 @@ EXPORTS = (
     'remap_conserve2nd_sizes', 'remap_conserve2nd_assemble',
     'remap_node_rings_workspace', 'remap_node_rings', 'remap_patch_fits',
     'remap_patch_sizes_workspace', 'remap_patch_sizes', 'remap_patch_rows',
+    'remap_limit_rows',
 )
+
+#: what ``limiter=`` accepts (remap_tensor, Remapper.limiter)
+LIMITERS = (None, 'clip', 'caas')
 
 
 class _CSR(ctypes.Structure):
@@ -164,6 +168,27 @@ class _ApplyArgs(ctypes.Structure):
         ('share_mask', ctypes.c_void_p),
         ('share_waves', ctypes.c_int32),
         ('share_reserved', ctypes.c_int32),
+    ]
+
+
+class _LimitArgs(ctypes.Structure):     # struct remap_limit_args
+    _fields_ = [
+        ('A', _CSR),
+        ('row_begin', ctypes.c_int64),
+        ('row_end', ctypes.c_int64),
+        ('X', ctypes.c_void_p),
+        ('x_dtype', ctypes.c_int32),
+        ('x_row_stride', ctypes.c_int64),
+        ('x_batch_stride', ctypes.c_int64),
+        ('x_src_fold', ctypes.c_int64),
+        ('x_outer_stride', ctypes.c_int64),
+        ('Y', ctypes.c_void_p),
+        ('y_row_stride', ctypes.c_int64),
+        ('y_batch_stride', ctypes.c_int64),
+        ('n_batch', ctypes.c_int64),
+        ('k_inner', ctypes.c_int64),
+        ('lo', ctypes.c_void_p),
+        ('hi', ctypes.c_void_p),
     ]
 
 
@@ -621,6 +646,9 @@ def load_library():
         ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] + \
         [ctypes.c_void_p] * 5 + [ctypes.c_int64] + [ctypes.c_void_p] * 4 + \
         [ctypes.c_int64] + [ctypes.c_void_p] * 5
+    lib.remap_limit_rows.restype = ctypes.c_int
+    lib.remap_limit_rows.argtypes = [ctypes.POINTER(_LimitArgs),
+                                     ctypes.c_void_p]
     if lib.remap_abi_version() != ABI_VERSION:
         raise EngineError(
             f'{path} has ABI {lib.remap_abi_version()}, expected '
@@ -1927,6 +1955,208 @@ def apply_strided(plan, X, Y, *, n_batch, k_inner, x_row_stride,
                    'remap_apply_f64')
 
 
+def check_limiter(limiter):
+    """``limiter`` is one of ``None | 'clip' | 'caas'``."""
+    if limiter not in LIMITERS:
+        raise ValueError(f"unknown limiter {limiter!r}: expected one of "
+                         f"None, 'clip', 'caas'")
+    return limiter
+
+
+def limit_strided(plan, X, Y, *, n_batch, k_inner, x_row_stride,
+                  x_batch_stride, y_row_stride, y_batch_stride, lo=None,
+                  hi=None, row_begin=0, row_end=None, x_src_fold=0,
+                  x_outer_stride=0):
+    """
+    One asynchronous ``remap_limit_rows`` launch on torch's current stream,
+    after the apply launch that filled ``Y`` from ``X`` with the same strides
+    (in elements): every ``Y[i, b, k]`` of rows ``[row_begin, row_end)`` is
+    clamped, in place, to the bounds of the source values of row ``i``'s
+    stored entries (:mod:`pyremap_amd.limiter` has the semantics).  ``lo`` /
+    ``hi``: optional float64 device tensors addressed like ``Y`` that receive
+    the bounds.
+
+    The pass reads the plan's own CSR (``rowptr``, ``col``), never a
+    schedule: a plan applied as short and long rows (``plan._split``) is
+    limited as the one matrix it is, a row slice over its own rows.
+    """
+    torch = _torch()
+    lib = load_library()
+    if hasattr(plan, 'shards') or not isinstance(plan, RemapPlan):
+        raise NotImplementedError(
+            'the limiter serves one device: not with a multi-device or '
+            'process-group plan')
+    if X.device != plan.device or Y.device != plan.device:
+        raise ValueError('X, Y and the plan must live on the same device')
+    if Y.dtype != torch.float64:
+        raise TypeError('Y must be float64')
+    if X.dtype == torch.float64:
+        x_dtype = DTYPE_F64
+    elif X.dtype == torch.float32:
+        x_dtype = DTYPE_F32
+    else:
+        raise TypeError(f'X must be float64 or float32, not {X.dtype}')
+    for name, t in (('lo', lo), ('hi', hi)):
+        if t is not None and (t.dtype != torch.float64 or
+                              t.device != plan.device):
+            raise TypeError(f'{name} must be a float64 tensor on the plan '
+                            f'device')
+    end = plan.n_b if row_end is None else int(row_end)
+    row_begin = int(row_begin)
+    if not 0 <= row_begin <= end <= plan.n_b:
+        raise ValueError(f'rows [{row_begin}, {end}) are not inside '
+                         f'[0, {plan.n_b}]')
+    # the kernel addresses through raw pointers: the tensors must hold the
+    # last element the strides reach (the checks of apply_strided)
+    for name, t, rows, rs, bs in (('X', X, plan.n_a, x_row_stride,
+                                   x_batch_stride),
+                                  ('Y', Y, plan.n_b, y_row_stride,
+                                   y_batch_stride),
+                                  ('lo', lo, plan.n_b, y_row_stride,
+                                   y_batch_stride),
+                                  ('hi', hi, plan.n_b, y_row_stride,
+                                   y_batch_stride)):
+        if t is None or n_batch <= 0 or k_inner <= 0 or rows <= 0:
+            continue
+        reach = (n_batch - 1) * bs + (rows - 1) * rs + k_inner
+        if name == 'X' and x_src_fold:
+            if x_src_fold < 0 or plan.n_a % x_src_fold or \
+                    x_outer_stride < 0:
+                raise ValueError(f'x_src_fold {x_src_fold} does not divide '
+                                 f'n_a = {plan.n_a}')
+            reach = (n_batch - 1) * bs + \
+                (plan.n_a // x_src_fold - 1) * x_outer_stride + \
+                (x_src_fold - 1) * rs + k_inner
+        if min(rs, bs) < 0 or reach > t.numel():
+            raise ValueError(
+                f'{name} holds {t.numel()} elements; the strides (row {rs}, '
+                f'batch {bs}) reach {reach}')
+    if n_batch < 0 or k_inner < 0:
+        raise ValueError('n_batch and k_inner must not be negative')
+    # (a split plan keeps the whole mapping's CSR beside its two parts)
+    if plan.rowptr is None or plan.col is None or \
+            plan.rowptr.numel() != plan.n_b + 1 or \
+            plan.col.numel() != plan.nnz:
+        raise EngineError('the plan no longer holds its CSR (rowptr, col): '
+                          'the limiter gathers a row\'s sources from it')
+    args = _LimitArgs()
+    args.A.n_rows = plan.n_b
+    args.A.n_cols = plan.n_a
+    args.A.nnz = plan.nnz
+    args.A.rowptr = plan.rowptr.data_ptr()
+    args.A.col = plan.col.data_ptr()
+    args.A.val = plan.val.data_ptr()
+    args.A.max_row_nnz = plan.max_row_nnz
+    args.A.csr_pad = plan.csr_pad
+    args.row_begin = row_begin
+    args.row_end = end
+    args.X = X.data_ptr()
+    args.x_dtype = x_dtype
+    args.x_row_stride = int(x_row_stride)
+    args.x_batch_stride = int(x_batch_stride)
+    args.x_src_fold = int(x_src_fold)
+    args.x_outer_stride = int(x_outer_stride)
+    args.Y = Y.data_ptr()
+    args.y_row_stride = int(y_row_stride)
+    args.y_batch_stride = int(y_batch_stride)
+    args.n_batch = int(n_batch)
+    args.k_inner = int(k_inner)
+    args.lo = lo.data_ptr() if lo is not None else None
+    args.hi = hi.data_ptr() if hi is not None else None
+    stream = ctypes.c_void_p(
+        torch.cuda.current_stream(plan.device).cuda_stream)
+    with torch.cuda.device(plan.device):
+        _check(lib.remap_limit_rows(ctypes.byref(args), stream),
+               'remap_limit_rows')
+
+
+def _caas_mass(Yv, row_weight):
+    """``sum_V w_i y_i`` per column of the ``(n_batch, n_b, k_inner)`` view
+    ``Yv``, V the rows whose value is no NaN."""
+    torch = _torch()
+    w = row_weight.view(1, -1, 1)
+    return torch.where(torch.isnan(Yv), 0.0, w * Yv).sum(dim=1)
+
+
+def _caas_fixup(Yv, M, lo, hi, row_weight):
+    """
+    The second half of "clip and assured sum" (``limiter.caas`` is the
+    statement), in place on the clipped ``(n_batch, n_b, k_inner)`` view
+    ``Yv`` with the bounds ``lo`` / ``hi`` of the same view and ``M`` the
+    mass of the unlimited result (:func:`_caas_mass`, taken before the clip).
+    Device tensor operations, nothing is read back.  Where the bounds cannot
+    hold the mass every value goes to its bound and conservation is not
+    reached.
+    """
+    torch = _torch()
+    w = row_weight.view(1, -1, 1)
+    valid = ~torch.isnan(Yv)
+    Mc = torch.where(valid, w * Yv, 0.0).sum(dim=1)
+    dM = M - Mc
+    up = (dM > 0).unsqueeze(1)
+    cap = torch.where(up, hi - Yv, Yv - lo)
+    bound = torch.where(up, hi, lo)
+    C = torch.where(valid, w * cap, 0.0).sum(dim=1)
+    ok = torch.isfinite(M) & torch.isfinite(Mc) & torch.isfinite(C) & \
+        (C > 0) & (dM != 0)
+    t = torch.where(ok, dM.abs() / C, 0.0)
+    full = (ok & (t >= 1)).unsqueeze(1)
+    step = torch.where(dM > 0, t, -t).unsqueeze(1)
+    new = torch.maximum(torch.minimum(Yv + step * cap, hi), lo)
+    new = torch.where(full, bound, new)
+    Yv.copy_(torch.where(ok.unsqueeze(1) & valid, new, Yv))
+
+
+def _limit_views(t, n_batch, n_b, k_inner, y_row_stride, y_batch_stride):
+    """The ``(n_batch, n_b, k_inner)`` strided view of a result buffer."""
+    return t.as_strided((n_batch, n_b, k_inner),
+                        (y_batch_stride, y_row_stride, 1),
+                        t.storage_offset())
+
+
+def _limit_after_apply(plan, limiter, row_weight, X, Y, **strides):
+    """Clip -- and, for CAAS, hand the clipped mass back -- behind the apply
+    launch that filled the contiguous buffer ``Y``.  CAAS takes two scratch
+    tensors of ``Y``'s size for the bounds."""
+    torch = _torch()
+    if limiter == 'clip':
+        limit_strided(plan, X, Y, **strides)
+        return
+    view = (strides['n_batch'], plan.n_b, strides['k_inner'],
+            strides['y_row_stride'], strides['y_batch_stride'])
+    Yv = _limit_views(Y.view(-1), *view)
+    M = _caas_mass(Yv, row_weight)       # of the unlimited result
+    lo = torch.empty(Y.numel(), dtype=torch.float64, device=Y.device)
+    hi = torch.empty(Y.numel(), dtype=torch.float64, device=Y.device)
+    limit_strided(plan, X, Y, lo=lo, hi=hi, **strides)
+    _caas_fixup(Yv, M, _limit_views(lo, *view), _limit_views(hi, *view),
+                row_weight)
+
+
+def _limiter_arguments(plan, limiter, row_weight):
+    """The checks of ``limiter=`` / ``row_weight=`` in front of any launch;
+    returns the float64 device weights (None unless CAAS)."""
+    check_limiter(limiter)
+    if limiter is None:
+        return None
+    if hasattr(plan, 'shards') or not isinstance(plan, RemapPlan):
+        raise NotImplementedError(
+            'the limiter serves one device: not with a multi-device or '
+            'process-group plan')
+    if limiter != 'caas':
+        return None
+    if row_weight is None:
+        raise ValueError("limiter 'caas' needs row_weight (one weight per "
+                         'destination row: area_b * frac_b)')
+    torch = _torch()
+    w = torch.as_tensor(row_weight).to(device=plan.device,
+                                       dtype=torch.float64).contiguous()
+    if tuple(w.shape) != (plan.n_b,):
+        raise ValueError(f'row_weight of shape {tuple(w.shape)}: expected '
+                         f'({plan.n_b},)')
+    return w
+
+
 def _prod(seq):
     out = 1
     for s in seq:
@@ -1991,7 +2221,7 @@ def check_field_extents(n_a, n_b, n_b_global, dst_grid_dims, shape,
 
 def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
                  want_mask=False, flags=0, tune=None, out=None, gate=None,
-                 gate_value=0, mask_out=None):
+                 gate_value=0, mask_out=None, limiter=None, row_weight=None):
     """
     Device-level ``_remap_numpy_array``: ``field`` is a device tensor whose
     axes ``remap_axes`` hold the source grid; returns the float64 tensor with
@@ -2002,8 +2232,24 @@ def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
     ``dst_grid_dims`` is in C order; for a row shard the leading destination
     dimension is replaced by the shard's row count (the result is the flat
     slab of rows ``[plan.row_offset, plan.row_offset + plan.n_b)``).
+
+    ``limiter`` (``None | 'clip' | 'caas'``; :mod:`pyremap_amd.limiter`):
+    after the apply, on the same stream, every value is clamped to the bounds
+    of the source values of its row's entries (``remap_limit_rows``; whatever
+    the mode left is what is limited, NaN stays NaN); ``'caas'`` then hands
+    the clipped mass back within the bounds so that ``sum_i row_weight[i] *
+    y[i]`` of every column is what it was (``row_weight``: ``n_b`` weights
+    ``>= 0``, ``area_b * frac_b`` for a conservative map).  Where the bounds
+    cannot hold the mass every value ends on its bound and conservation is
+    not reached; nothing reports it.  CAAS takes two scratch tensors of the
+    result's size.  A gated launch is not limited (the limiter needs no
+    gate: ``remap_tensor_auto_mode`` runs it once behind its launches).
     """
     torch = _torch()
+    weight = _limiter_arguments(plan, limiter, row_weight)
+    if limiter is not None and gate is not None:
+        raise ValueError('a gated launch is not limited: run the limiter '
+                         'behind the gated launches')
     if hasattr(plan, 'shards'):
         # a parallel.MultiDeviceRemap standing where the plan stands
         # (Remapper(..., devices=[...])): rows sharded over several GPUs
@@ -2066,6 +2312,12 @@ def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
             y_row_stride=k_inner, y_batch_stride=plan.n_b * k_inner,
             mode=mode, threshold=threshold, mask_out=mask, flags=flags,
             tune=tune, gate=gate, gate_value=gate_value)
+        if limiter is not None:
+            _limit_after_apply(
+                plan, limiter, weight, X, Y, n_batch=n_batch,
+                k_inner=k_inner, x_row_stride=k_inner,
+                x_batch_stride=plan.n_a * k_inner, y_row_stride=k_inner,
+                y_batch_stride=plan.n_b * k_inner)
         return (Y, mask) if want_mask else Y
     if len(remap_axes) == 2 and remap_axes[0] < remap_axes[1] and \
             out is None and gate is None and mask_out is None:
@@ -2099,6 +2351,12 @@ def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
                 threshold=threshold,
                 mask_out=Ml[li] if want_mask else None, flags=flags,
                 tune=tune, x_src_fold=nx, x_outer_stride=M * nx * T)
+            if limiter is not None:
+                _limit_after_apply(
+                    plan, limiter, weight, Xl[li], Yl[li], n_batch=M,
+                    k_inner=T, x_row_stride=T, x_batch_stride=nx * T,
+                    y_row_stride=M * T, y_batch_stride=T, x_src_fold=nx,
+                    x_outer_stride=M * nx * T)
         return (Y, mask) if want_mask else Y
     if gate is not None or mask_out is not None:
         raise ValueError('gated launches and caller-supplied masks need the '
@@ -2116,6 +2374,11 @@ def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
                   x_batch_stride=0, y_row_stride=K, y_batch_stride=0,
                   mode=mode, threshold=threshold, mask_out=mask, flags=flags,
                   tune=tune)
+    if limiter is not None:
+        # (before the transpose back: the kernel's (n_b, K) layout)
+        _limit_after_apply(plan, limiter, weight, X, Y, n_batch=1, k_inner=K,
+                           x_row_stride=K, x_batch_stride=0, y_row_stride=K,
+                           y_batch_stride=0)
     extra_shape = [int(field.shape[ax]) for ax in extra_axes]
     n_dst = len(dst_shape)
     tail = list(range(n_dst, n_dst + len(extra_shape)))
@@ -2184,15 +2447,20 @@ def cell_mask_form(plan):
 
 
 def remap_tensor_auto_mode(plan, dst_grid_dims, field, remap_axes, threshold,
-                           flags=0, out=None, flag=None):
+                           flags=0, out=None, flag=None, limiter=None,
+                           row_weight=None):
     """
     ``_remap_data_array``'s branch (``remap_numpy.py:201-204``) without a
     host round trip: the masked, renormalised result if ``field`` holds a
     NaN, the ``frac_b``-normalised one if not.  One scan, two gated launches
     (the one whose gate is closed does nothing; three on entry-rich mappings,
-    whose masked branch has two forms), nothing synchronises.
+    whose masked branch has two forms), nothing synchronises.  ``limiter`` /
+    ``row_weight`` as in :func:`remap_tensor`: the limiter runs ONCE behind
+    the gated launches, ungated -- it sees ``Y`` as whichever of them left it
+    and needs no mode.
     """
     torch = _torch()
+    weight = _limiter_arguments(plan, limiter, row_weight)
     # (before the scan below is enqueued: remap_tensor would say the same,
     # but only after it)
     check_field_extents(plan.n_a, plan.n_b, plan.n_b_global, dst_grid_dims,
@@ -2209,8 +2477,21 @@ def remap_tensor_auto_mode(plan, dst_grid_dims, field, remap_axes, threshold,
         return remap_tensor(plan, dst_grid_dims, field, remap_axes,
                             MODE_MASKED if masked else MODE_FRACB,
                             threshold=threshold if masked else 0.0,
-                            flags=flags, out=out)
+                            flags=flags, out=out, limiter=limiter,
+                            row_weight=weight)
     X = field.contiguous()
+
+    def limited(Y):
+        if limiter is not None:
+            axes = [int(a) % X.ndim for a in remap_axes]
+            n_batch = _prod(X.shape[:min(axes)])
+            k_inner = _prod(X.shape[min(axes) + len(axes):])
+            _limit_after_apply(
+                plan, limiter, weight, X, Y, n_batch=n_batch,
+                k_inner=k_inner, x_row_stride=k_inner,
+                x_batch_stride=plan.n_a * k_inner, y_row_stride=k_inner,
+                y_batch_stride=plan.n_b * k_inner)
+        return Y
     if flag is None and cell_mask_form(plan):
         # entry-rich mapping: the scan -- told where the cells and the
         # batches of the field are -- also says whether whole cells are
@@ -2237,16 +2518,18 @@ def remap_tensor_auto_mode(plan, dst_grid_dims, field, remap_axes, threshold,
         Y = remap_tensor(plan, dst_grid_dims, X, remap_axes, MODE_MASKED,
                          threshold=threshold, flags=flags, out=Y,
                          gate=kinds[3:], gate_value=3)
-        return remap_tensor(plan, dst_grid_dims, X, remap_axes, MODE_FRACB,
-                            flags=flags, out=Y, gate=kinds, gate_value=0)
+        return limited(remap_tensor(
+            plan, dst_grid_dims, X, remap_axes, MODE_FRACB, flags=flags,
+            out=Y, gate=kinds, gate_value=0))
     if flag is None:
         flag = torch.zeros(1, dtype=torch.int32, device=field.device)
     scan_nan(X, flag)
     Y = remap_tensor(plan, dst_grid_dims, X, remap_axes, MODE_MASKED,
                      threshold=threshold, flags=flags, out=out, gate=flag,
                      gate_value=1)
-    return remap_tensor(plan, dst_grid_dims, X, remap_axes, MODE_FRACB,
-                        flags=flags, out=Y, gate=flag, gate_value=0)
+    return limited(remap_tensor(
+        plan, dst_grid_dims, X, remap_axes, MODE_FRACB, flags=flags, out=Y,
+        gate=flag, gate_value=0))
 
 
 def gather_rows(field, axis, rows, out=None):

@@ -472,7 +472,8 @@ def remap_host_batch(plan, dst_grid_dims, arrays, remap_axes, *, mode,
 
 def remap_host_array(plan, dst_grid_dims, values, remap_axes, *, mode,
                      threshold=None, want_mask=False, flags=0,
-                     host_mask=None, keep_on_device=False):
+                     host_mask=None, keep_on_device=False, limiter=None,
+                     row_weight=None):
     """
     Enqueue the remap of one host array and return a :class:`Pending`
     (``keep_on_device``: an :class:`OnDevice` -- upload and launch are
@@ -483,7 +484,15 @@ def remap_host_array(plan, dst_grid_dims, values, remap_axes, *, mode,
     array holds a NaN, decided on the device (``_remap_data_array``'s rule).
     ``host_mask`` (bool array like ``values``, masked mode only): entries to
     treat as missing, as a ``numpy.ma.MaskedArray`` carries them.
+    ``limiter`` / ``row_weight``: as :func:`pyremap_amd.engine.remap_tensor`
+    takes them.  A limited array takes the whole-array route -- one upload,
+    ``engine.remap_tensor``, one download: the pipelines below launch
+    ``apply_strided`` on panels, bands and chunks themselves and serve
+    ``limiter=None`` only.
     """
+    engine.check_limiter(limiter)
+    limit = {} if limiter is None else {'limiter': limiter,
+                                        'row_weight': row_weight}
     torch = engine.require_gpu()
     device = plan.device
     values = _as_uploadable(values)
@@ -540,14 +549,15 @@ def remap_host_array(plan, dst_grid_dims, values, remap_axes, *, mode,
             x_d.copy_(host, non_blocking=True)
             if mode == 'auto':
                 y_d = engine.remap_tensor_auto_mode(
-                    plan, dst_grid_dims, x_d, remap_axes, thr, flags=flags)
+                    plan, dst_grid_dims, x_d, remap_axes, thr, flags=flags,
+                    **limit)
             else:
                 emode = engine.MODE_MASKED if mode == 'masked' else \
                     engine.MODE_FRACB
                 y_d = engine.remap_tensor(
                     plan, dst_grid_dims, x_d, remap_axes, emode,
                     threshold=thr if emode == engine.MODE_MASKED else 0.0,
-                    flags=flags)
+                    flags=flags, **limit)
             return OnDevice(y_d, out_shape)
     with torch.cuda.device(device):
         out_h, pin_o = _host_buffer(out_shape, torch.float64)
@@ -557,7 +567,7 @@ def remap_host_array(plan, dst_grid_dims, values, remap_axes, *, mode,
             return _enqueue(plan, dst_grid_dims, values, host, remap_axes,
                             lead, n_batch, in_place, mode, thr, want_mask,
                             flags, host_mask, dst_shape, out_shape, out_h,
-                            mask_h, pin_o, pin_m, up, down, main)
+                            mask_h, pin_o, pin_m, up, down, main, limit)
         except BaseException:
             # nothing was handed out: the budget goes back
             _release_pinned(pin_o + pin_m)
@@ -566,8 +576,10 @@ def remap_host_array(plan, dst_grid_dims, values, remap_axes, *, mode,
 
 def _enqueue(plan, dst_grid_dims, values, host, remap_axes, lead, n_batch,
              in_place, mode, thr, want_mask, flags, host_mask, dst_shape,
-             out_shape, out_h, mask_h, pin_o, pin_m, up, down, main):
+             out_shape, out_h, mask_h, pin_o, pin_m, up, down, main,
+             limit=None):
     """The transfers and launches of :func:`remap_host_array`."""
+    limit = limit or {}
     torch = engine._torch()
     device = plan.device
     # a multi-device plan (parallel.MultiDeviceRemap) shards ROWS over its
@@ -575,16 +587,17 @@ def _enqueue(plan, dst_grid_dims, values, host, remap_axes, lead, n_batch,
     # download (the pipelines below drive a single device's launches)
     multi = hasattr(plan, 'shards')
     single = not in_place or host_mask is not None or mode == 'auto' or \
-        n_batch < 2 or multi
-    banded = in_place and host_mask is None and mode != 'auto' and \
-        n_batch == 1 and lead == 0 and not multi and \
+        n_batch < 2 or multi or bool(limit)
+    banded = not limit and in_place and host_mask is None and \
+        mode != 'auto' and n_batch == 1 and lead == 0 and not multi and \
         values.nbytes >= 4 * CHUNK_BYTES and plan.n_b == plan.n_b_global
     # a field whose source axes lead, (n_a, K): column panels, both PCIe
     # directions busy whatever the mesh numbering (mode 'auto' included:
     # frac_b panel by panel, the masked mode over again if a device scan
     # meets a NaN)
-    panels = in_place and host_mask is None and n_batch == 1 and \
-        lead == 0 and not multi and plan.n_b == plan.n_b_global and \
+    panels = not limit and in_place and host_mask is None and \
+        n_batch == 1 and lead == 0 and not multi and \
+        plan.n_b == plan.n_b_global and \
         values.nbytes >= 4 * CHUNK_BYTES and values.flags.c_contiguous and \
         out_h.is_pinned() and (mask_h is None or mask_h.is_pinned())
     if panels:
@@ -623,7 +636,8 @@ def _enqueue(plan, dst_grid_dims, values, host, remap_axes, lead, n_batch,
                 x_d.masked_fill_(poisoned, 0.0)
         if mode == 'auto':
             y_d = engine.remap_tensor_auto_mode(
-                plan, dst_grid_dims, x_d, remap_axes, thr, flags=flags)
+                plan, dst_grid_dims, x_d, remap_axes, thr, flags=flags,
+                **limit)
             m_out = None
         else:
             emode = engine.MODE_MASKED if mode == 'masked' else \
@@ -631,7 +645,7 @@ def _enqueue(plan, dst_grid_dims, values, host, remap_axes, lead, n_batch,
             res = engine.remap_tensor(
                 plan, dst_grid_dims, x_d, remap_axes, emode,
                 threshold=thr if emode == engine.MODE_MASKED else 0.0,
-                want_mask=want_mask, flags=flags)
+                want_mask=want_mask, flags=flags, **limit)
             y_d, m_out = res if want_mask else (res, None)
         if poisoned is not None:
             # every destination cell that touches a poisoned entry is NaN

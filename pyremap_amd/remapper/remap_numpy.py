@@ -65,6 +65,55 @@ class _MapInfo:
         self.src_grid_dims = [int(d) for d in mapping.src_grid_dims[::-1]]
         self.dst_grid_dims = [int(d) for d in mapping.dst_grid_dims[::-1]]
         self.frac_b = mapping.frac_b
+        #: destination cell areas (None: the file has none); with frac_b the
+        #: row weights of the 'caas' limiter
+        self.area_b = getattr(mapping, 'area_b', None)
+        self._row_weight = {}
+
+    def row_weight(self, plan):
+        """``area_b * frac_b`` on ``plan``'s device (the 'caas' limiter's
+        integral), uploaded once per device."""
+        _require_area_b(self)
+        key = str(plan.device)
+        if key not in self._row_weight:
+            torch = engine.require_gpu()
+            w = np.asarray(self.area_b, dtype=np.float64) * \
+                np.asarray(self.frac_b, dtype=np.float64)
+            self._row_weight[key] = torch.from_numpy(w).to(plan.device)
+        return self._row_weight[key]
+
+
+def _require_area_b(info):
+    if info.area_b is None:
+        raise ValueError(
+            "limiter 'caas' restores the area_b * frac_b integral, but the "
+            "mapping file has no variable 'area_b'")
+
+
+def _check_limiter(remapper, limiter=None):
+    """The limiter of one call: the keyword if given, else the Remapper's
+    attribute; one of ``None | 'clip' | 'caas'``."""
+    if limiter is None:
+        limiter = getattr(remapper, 'limiter', None)
+    limiter = engine.check_limiter(limiter)
+    if limiter is not None and (
+            getattr(remapper, '_process_group', None) is not None or
+            len(getattr(remapper, 'devices', None) or ()) > 1):
+        raise NotImplementedError(
+            'the limiter serves one device: not with devices=[...] or a '
+            'process group')
+    return limiter
+
+
+def _limiter_kwargs(remapper, limiter):
+    """What ``engine.remap_tensor`` / ``host_path.remap_host_array`` take for
+    this call's limiter: nothing at all without one."""
+    if limiter is None:
+        return {}
+    if limiter == 'caas':
+        return {'limiter': limiter,
+                'row_weight': remapper._ds_map.row_weight(remapper._matrix)}
+    return {'limiter': limiter}
 
 
 def _remap_numpy(remapper, ds, renormalization_threshold):
@@ -75,7 +124,7 @@ def _remap_numpy(remapper, ds, renormalization_threshold):
     """
     if remapper.map_filename is None:
         raise ValueError('No mapping file has been defined')
-    _load_mapping(remapper)
+    _load_mapping(remapper, limiter=_check_limiter(remapper))
 
     expected = remapper._ds_map.src_grid_dims
     for dim, size in zip(remapper.src_descriptor.dims, expected):
@@ -167,14 +216,22 @@ def _plan_cache_key(remapper):
             tuple(str(d) for d in devices) if devices else None)
 
 
-def _load_mapping(remapper):
+def _load_mapping(remapper, limiter=None):
     """
     Read the mapping file once, validate it against the descriptors and sort
     its triplets into a device-resident CSR (reference ``_load_mapping``
     :72-139; the plan is cached where the reference caches ``_matrix``, and
-    -- per process -- by mapping file, see ``_PLAN_CACHE``).
+    -- per process -- by mapping file, see ``_PLAN_CACHE``).  ``limiter``:
+    the limiter the caller is about to use (default: the Remapper's
+    attribute); ``'caas'`` needs the file's ``area_b`` and raises
+    ``ValueError`` here, before anything is uploaded, if it has none.  The
+    plan and its cache key do not depend on the limiter.
     """
+    if limiter is None:
+        limiter = getattr(remapper, 'limiter', None)
     if remapper._ds_map is not None:
+        if limiter == 'caas':
+            _require_area_b(remapper._ds_map)
         return
     key = _plan_cache_key(remapper)
     if key is not None and key in _PLAN_CACHE:
@@ -182,6 +239,8 @@ def _load_mapping(remapper):
         _PLAN_CACHE[key] = (info, plan, schedule)       # most recent last
         _validate_mapping(info, remapper.src_descriptor,
                           remapper.dst_descriptor)
+        if limiter == 'caas':
+            _require_area_b(info)
         remapper._matrix, remapper.schedule = plan, schedule
         remapper._ds_map = info
         return
@@ -190,6 +249,8 @@ def _load_mapping(remapper):
         mapping = read_mapping(remapper.map_filename)
     info = _MapInfo(mapping)
     _validate_mapping(info, remapper.src_descriptor, remapper.dst_descriptor)
+    if limiter == 'caas':
+        _require_area_b(info)
     # csr_matrix((S, (row - 1, col - 1)), shape=(n_b, n_a)), on the device
     plan = engine.RemapPlan.from_triplets(
         mapping.row, mapping.col, mapping.S, mapping.frac_b, info.n_a,
@@ -337,7 +398,8 @@ def _start_data_array(da, remapper, renormalization_threshold,
         remap_axes,
         mode='fracb' if renormalization_threshold is None else 'auto',
         threshold=renormalization_threshold, flags=remapper.engine_flags,
-        keep_on_device=keep_on_device)
+        keep_on_device=keep_on_device,
+        **_limiter_kwargs(remapper, _check_limiter(remapper)))
     make = _array_class(da).from_dict
     attrs, name = da.attrs, da.name
 
@@ -368,7 +430,9 @@ def _batches(remapper, ds, names):
     """
     plan = getattr(remapper, '_matrix', None)
     if getattr(remapper, '_process_group', None) is not None or \
-            plan is None or hasattr(plan, 'shards'):
+            plan is None or hasattr(plan, 'shards') or \
+            getattr(remapper, 'limiter', None) is not None:
+        # (a limited variable takes the whole-array route, one at a time)
         return {}
     groups = {}
     src_dims = remapper.src_descriptor.dims
@@ -536,7 +600,7 @@ def _collective_array(remapper, values, remap_axes, threshold, mode='auto',
 
 
 def _remap_numpy_array(remapper, in_field, remap_axes,
-                       renormalization_threshold):
+                       renormalization_threshold, limiter=None):
     """
     Remap a single array (reference ``_remap_numpy_array`` :223-297).
 
@@ -551,9 +615,13 @@ def _remap_numpy_array(remapper, in_field, remap_axes,
       device tensor holding NaN where the reference masks; masked mode is
       chosen as ``_remap_data_array`` would (a threshold and at least one
       NaN), nothing leaves the device.
+
+    ``limiter``: this call's limiter (default: the Remapper's attribute).
     """
+    limiter = _check_limiter(remapper, limiter)
     torch = engine.require_gpu()
     plan = remapper._matrix
+    limit = _limiter_kwargs(remapper, limiter)
     dst_grid_dims = remapper._ds_map.dst_grid_dims
     remap_axes = [int(a) for a in remap_axes]
 
@@ -586,11 +654,11 @@ def _remap_numpy_array(remapper, in_field, remap_axes,
         if renormalization_threshold is None:
             return engine.remap_tensor(plan, dst_grid_dims, field,
                                        remap_axes, engine.MODE_FRACB,
-                                       flags=remapper.engine_flags)
+                                       flags=remapper.engine_flags, **limit)
         # NaN scan and both candidate launches stay on the device
         return engine.remap_tensor_auto_mode(
             plan, dst_grid_dims, field, remap_axes,
-            renormalization_threshold, flags=remapper.engine_flags)
+            renormalization_threshold, flags=remapper.engine_flags, **limit)
 
     is_ma = isinstance(in_field, np.ma.MaskedArray)
     masked = is_ma and renormalization_threshold is not None
@@ -611,5 +679,5 @@ def _remap_numpy_array(remapper, in_field, remap_axes,
         mode='masked' if masked else 'fracb',
         threshold=renormalization_threshold if masked else None,
         want_mask=True, flags=remapper.engine_flags,
-        host_mask=host_mask).result()
+        host_mask=host_mask, **limit).result()
     return np.ma.masked_array(out, mask=mask)

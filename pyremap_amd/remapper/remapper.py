@@ -9,6 +9,7 @@ Added on top of the reference surface: ``remap`` / ``remap_file`` aliases
 knobs and :meth:`from_triplets` for mapping data that is already in memory.
 """
 from pyremap_amd.remapper.remap_numpy import (
+    _check_limiter,
     _load_mapping,
     _remap_numpy,
     _remap_numpy_array,
@@ -37,6 +38,12 @@ class Remapper:
         device.  One process per GPU (torchrun): :meth:`use_process_group`.
     engine_flags : int
         ``pyremap_amd.engine.FLAG_*`` bits; 0 = bit-identical to scipy
+    limiter : None, 'clip' or 'caas'
+        set after construction (default ``None``: nothing changes): clamp
+        every remapped value to the bounds of the source values in its row's
+        stencil, and with ``'caas'`` restore the ``area_b * frac_b``
+        integral within those bounds (:mod:`pyremap_amd.limiter`); for the
+        signed ``conserve2nd`` and ``patch`` maps on bounded fields
     """
 
     def __init__(
@@ -66,6 +73,13 @@ class Remapper:
         self.extrap_method = None
         self.extrap_num_src_pnts = 8
         self.extrap_dist_exponent = 2.0
+        #: local-bounds limiter of the apply path (None | 'clip' | 'caas'),
+        #: honoured by remap_array, remap_numpy and ncremap: every remapped
+        #: value is clamped to the bounds of the source values in its row's
+        #: stencil; 'caas' then restores the area_b * frac_b integral
+        #: (pyremap_amd.limiter).  For the signed maps -- conserve2nd, patch
+        #: -- on bounded fields.
+        self.limiter = None
         self.src_scrip_filename = 'src_mesh.nc'
         self.dst_scrip_filename = 'dst_mesh.nc'
         self.format = 'NETCDF3_64BIT_DATA'
@@ -333,17 +347,28 @@ class Remapper:
         """
         return _remap_numpy(self, ds, renormalization_threshold)
 
-    def remap_array(self, field, remap_axes, renormalization_threshold=None):
+    def remap_array(self, field, remap_axes, renormalization_threshold=None,
+                    limiter=None):
         """
         Array-level entry (the reference's private ``_remap_numpy_array``):
         numpy in -> ``numpy.ma.MaskedArray`` out; device tensor in -> device
         tensor out, nothing leaves the GPU.
+
+        ``limiter`` (``'clip'`` or ``'caas'``) overrides the attribute
+        :attr:`limiter` for this call: the result is clamped to the bounds
+        of the source values in every row's stencil, and with ``'caas'`` the
+        ``area_b * frac_b`` integral of the unlimited result is restored
+        within those bounds (the mapping file must hold ``area_b``; where
+        the bounds cannot hold the mass, every value ends on its bound and
+        the integral is not reached).  Host arrays then take the whole-array
+        route: upload, remap, download.
         """
         if self.map_filename is None:
             raise ValueError('No mapping file has been defined')
-        _load_mapping(self)
+        limiter = _check_limiter(self, limiter)
+        _load_mapping(self, limiter=limiter)
         return _remap_numpy_array(self, field, remap_axes,
-                                  renormalization_threshold)
+                                  renormalization_threshold, limiter=limiter)
 
     # pyremap-1.x names used by BASELINE.json's north_star
     remap = remap_numpy
