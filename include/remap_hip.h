@@ -1802,6 +1802,79 @@ typedef struct remap_limit_args {
 REMAP_API int remap_limit_rows(const struct remap_limit_args *args,
                                void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Sub-gridscale fraction weighting (csrc/remap_sgs.hip; DESIGN.md section 21;
+ * pyremap_amd.sgs is the same statement in numpy).
+ *
+ * A field that is a mean over a FRACTION of every source cell (ice thickness
+ * over the ice-covered part, NCO's `ncremap --sgs_frc`) is multiplied by the
+ * fraction before the map and divided by the remapped fraction after it, in
+ * one launch: X is read once, as REMAP_MODE_MASKED reads it, plus a fraction
+ * F that is usually k_inner times smaller.
+ *
+ * For destination element (i, b, k), the entries j of row i are walked in CSR
+ * order.  Three float64 accumulators start at +0.0.
+ *
+ *   x = (double) X[cell(col_j), b, k]
+ *   f = (double) F[cell(col_j), b', k']     (b', k': b, k or 0 where F is broadcast)
+ *   the entry counts iff x is no NaN and f is no NaN      (+-inf, 0 and negative f are values)
+ *   counts:  t = f * x;   num += S_j * t;   den += S_j * f;   valid += S_j
+ *            (every product rounded, every sum rounded: no FMA contraction)
+ *   y = (valid > threshold && den > 0) ? num / den : NaN
+ *
+ * Every NaN written is the quiet NaN 0x7ff8000000000000, also where num / den
+ * is itself a NaN (inf / inf): the bits of Y are defined.
+ *
+ * This is the reference's masked branch (remap_numpy.py:262-266) with in_mask
+ * replaced by a real-valued fraction.  With F == 1 everywhere the result is
+ * byte for byte REMAP_MODE_MASKED at the same threshold; scaling F by a power
+ * of two (without overflow or denormals) keeps the bytes of Y.  A map with
+ * signed weights (conserve2nd, patch) can give den <= 0: y is NaN there.
+ *
+ * X and Y are addressed as in remap_limit_args (x_src_fold included).  F is
+ * addressed like X with strides of its own:
+ *   F[b * f_batch_stride + cell(a) + k * f_inner_stride],
+ *   cell(a) = a * f_row_stride, or with x_src_fold != 0
+ *   (a / x_src_fold) * f_outer_stride + (a % x_src_fold) * f_row_stride.
+ * f_batch_stride == 0 broadcasts over the batches, f_inner_stride (0 or 1)
+ * == 0 over the inner index: a (Time, nCells) fraction for (Time, nCells,
+ * nCategories) fields.
+ *
+ * Elements of rows outside [row_begin, row_end) are not written.
+ * Asynchronous on `stream`; nothing is allocated, freed or synchronised.
+ * REMAP_ERR_ARG: a NULL array that is needed, a negative stride or size, an
+ * f_inner_stride that is neither 0 nor 1, a row range outside [0, A.n_rows],
+ * an x_dtype or f_dtype that is no REMAP_DTYPE_*, an x_src_fold that does not
+ * divide A.n_cols, more elements than one launch serves.
+ * ---------------------------------------------------------------------------
+ */
+typedef struct remap_sgs_args {
+    remap_csr A;            /* rowptr, col and val are all read              */
+    int64_t row_begin;      /* rows [row_begin, row_end) of A are computed;  */
+    int64_t row_end;        /* Y is indexed by row                           */
+    const void *X;          /* (device) source field                         */
+    int32_t x_dtype;        /* REMAP_DTYPE_*                                 */
+    int64_t x_row_stride;
+    int64_t x_batch_stride;
+    int64_t x_src_fold;     /* as in remap_apply_args (0: one stride)        */
+    int64_t x_outer_stride;
+    const void *F;          /* (device) sub-gridscale fraction               */
+    int32_t f_dtype;        /* REMAP_DTYPE_*                                 */
+    int64_t f_row_stride;
+    int64_t f_batch_stride; /* 0: the same fraction in every batch           */
+    int64_t f_inner_stride; /* 1, or 0: the same fraction for every k        */
+    int64_t f_outer_stride; /* with x_src_fold != 0, as x_outer_stride       */
+    double *Y;              /* (device) destination field, float64           */
+    int64_t y_row_stride;
+    int64_t y_batch_stride;
+    int64_t n_batch;
+    int64_t k_inner;
+    double threshold;       /* of `valid`, as REMAP_MODE_MASKED has it       */
+} remap_sgs_args;
+
+REMAP_API int remap_apply_sgs(const struct remap_sgs_args *args,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif

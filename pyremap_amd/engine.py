@@ -97,7 +97,7 @@ EXPORTS = (
     'remap_conserve2nd_sizes', 'remap_conserve2nd_assemble',
     'remap_node_rings_workspace', 'remap_node_rings', 'remap_patch_fits',
     'remap_patch_sizes_workspace', 'remap_patch_sizes', 'remap_patch_rows',
-    'remap_limit_rows',
+    'remap_limit_rows', 'remap_apply_sgs',
 )
 
 #: what ``limiter=`` accepts (remap_tensor, Remapper.limiter)
@@ -189,6 +189,32 @@ class _LimitArgs(ctypes.Structure):     # struct remap_limit_args
         ('k_inner', ctypes.c_int64),
         ('lo', ctypes.c_void_p),
         ('hi', ctypes.c_void_p),
+    ]
+
+
+class _SgsArgs(ctypes.Structure):       # struct remap_sgs_args
+    _fields_ = [
+        ('A', _CSR),
+        ('row_begin', ctypes.c_int64),
+        ('row_end', ctypes.c_int64),
+        ('X', ctypes.c_void_p),
+        ('x_dtype', ctypes.c_int32),
+        ('x_row_stride', ctypes.c_int64),
+        ('x_batch_stride', ctypes.c_int64),
+        ('x_src_fold', ctypes.c_int64),
+        ('x_outer_stride', ctypes.c_int64),
+        ('F', ctypes.c_void_p),
+        ('f_dtype', ctypes.c_int32),
+        ('f_row_stride', ctypes.c_int64),
+        ('f_batch_stride', ctypes.c_int64),
+        ('f_inner_stride', ctypes.c_int64),
+        ('f_outer_stride', ctypes.c_int64),
+        ('Y', ctypes.c_void_p),
+        ('y_row_stride', ctypes.c_int64),
+        ('y_batch_stride', ctypes.c_int64),
+        ('n_batch', ctypes.c_int64),
+        ('k_inner', ctypes.c_int64),
+        ('threshold', ctypes.c_double),
     ]
 
 
@@ -649,6 +675,9 @@ def load_library():
     lib.remap_limit_rows.restype = ctypes.c_int
     lib.remap_limit_rows.argtypes = [ctypes.POINTER(_LimitArgs),
                                      ctypes.c_void_p]
+    lib.remap_apply_sgs.restype = ctypes.c_int
+    lib.remap_apply_sgs.argtypes = [ctypes.POINTER(_SgsArgs),
+                                    ctypes.c_void_p]
     if lib.remap_abi_version() != ABI_VERSION:
         raise EngineError(
             f'{path} has ABI {lib.remap_abi_version()}, expected '
@@ -2157,6 +2186,125 @@ def _limiter_arguments(plan, limiter, row_weight):
     return w
 
 
+def _float_dtype(torch, name, t):
+    if t.dtype == torch.float64:
+        return DTYPE_F64
+    if t.dtype == torch.float32:
+        return DTYPE_F32
+    raise TypeError(f'{name} must be float64 or float32, not {t.dtype}')
+
+
+def sgs_strided(plan, X, F, Y, *, n_batch, k_inner, x_row_stride,
+                x_batch_stride, f_row_stride, f_batch_stride, f_inner_stride,
+                y_row_stride, y_batch_stride, threshold, row_begin=0,
+                row_end=None, x_src_fold=0, x_outer_stride=0,
+                f_outer_stride=0):
+    """
+    One asynchronous ``remap_apply_sgs`` launch on torch's current stream:
+    the sub-gridscale weighted remap of ``X`` by the fraction ``F`` into rows
+    ``[row_begin, row_end)`` of ``Y`` (:mod:`pyremap_amd.sgs` has the
+    semantics; strides in elements).  ``X`` and ``Y`` are addressed as
+    :func:`apply_strided` addresses them, ``F`` like ``X`` with strides of its
+    own: ``f_batch_stride == 0`` broadcasts over the batches,
+    ``f_inner_stride`` (0 or 1) ``== 0`` over the inner index;
+    ``f_outer_stride`` goes with ``x_src_fold``.
+
+    The launch reads the plan's own CSR (``rowptr``, ``col``, ``val``), never
+    a schedule: a plan applied as short and long rows (``plan._split``) is
+    served as the one matrix it is.
+    """
+    torch = _torch()
+    lib = load_library()
+    if hasattr(plan, 'shards') or not isinstance(plan, RemapPlan):
+        raise NotImplementedError(
+            'sub-gridscale weighting serves one device: not with a '
+            'multi-device or process-group plan')
+    for name, t in (('X', X), ('F', F), ('Y', Y)):
+        if t.device != plan.device:
+            raise ValueError('X, F, Y and the plan must live on the same '
+                             'device')
+        if not t.is_contiguous():
+            raise ValueError(f'{name} must be contiguous')
+    if Y.dtype != torch.float64:
+        raise TypeError('Y must be float64')
+    x_dtype = _float_dtype(torch, 'X', X)
+    f_dtype = _float_dtype(torch, 'F', F)
+    end = plan.n_b if row_end is None else int(row_end)
+    row_begin = int(row_begin)
+    if not 0 <= row_begin <= end <= plan.n_b:
+        raise ValueError(f'rows [{row_begin}, {end}) are not inside '
+                         f'[0, {plan.n_b}]')
+    if n_batch < 0 or k_inner < 0:
+        raise ValueError('n_batch and k_inner must not be negative')
+    if f_inner_stride not in (0, 1):
+        raise ValueError(f'f_inner_stride {f_inner_stride}: expected 0 '
+                         f'(broadcast) or 1')
+    if x_src_fold and (x_src_fold < 0 or plan.n_a % x_src_fold or
+                       x_outer_stride < 0 or f_outer_stride < 0):
+        raise ValueError(f'x_src_fold {x_src_fold} does not divide '
+                         f'n_a = {plan.n_a}')
+    # the kernel addresses through raw pointers: the tensors must hold the
+    # last element the strides reach (the checks of apply_strided)
+    for name, t, rows, rs, bs, inner, outer in (
+            ('X', X, plan.n_a, x_row_stride, x_batch_stride, 1,
+             x_outer_stride),
+            ('F', F, plan.n_a, f_row_stride, f_batch_stride, f_inner_stride,
+             f_outer_stride),
+            ('Y', Y, plan.n_b, y_row_stride, y_batch_stride, 1, 0)):
+        if n_batch <= 0 or k_inner <= 0 or rows <= 0:
+            continue
+        reach = (n_batch - 1) * bs + (rows - 1) * rs + \
+            (k_inner - 1) * inner + 1
+        if name != 'Y' and x_src_fold:
+            reach = (n_batch - 1) * bs + \
+                (plan.n_a // x_src_fold - 1) * outer + \
+                (x_src_fold - 1) * rs + (k_inner - 1) * inner + 1
+        if min(rs, bs) < 0 or reach > t.numel():
+            raise ValueError(
+                f'{name} holds {t.numel()} elements; the strides (row {rs}, '
+                f'batch {bs}) reach {reach}')
+    # (a split plan keeps the whole mapping's CSR beside its two parts)
+    if plan.rowptr is None or plan.col is None or plan.val is None or \
+            plan.rowptr.numel() != plan.n_b + 1 or \
+            plan.col.numel() != plan.nnz or plan.val.numel() != plan.nnz:
+        raise EngineError('the plan no longer holds its CSR (rowptr, col, '
+                          'val): the sub-gridscale launch reads it')
+    args = _SgsArgs()
+    args.A.n_rows = plan.n_b
+    args.A.n_cols = plan.n_a
+    args.A.nnz = plan.nnz
+    args.A.rowptr = plan.rowptr.data_ptr()
+    args.A.col = plan.col.data_ptr()
+    args.A.val = plan.val.data_ptr()
+    args.A.max_row_nnz = plan.max_row_nnz
+    args.A.csr_pad = plan.csr_pad
+    args.row_begin = row_begin
+    args.row_end = end
+    args.X = X.data_ptr()
+    args.x_dtype = x_dtype
+    args.x_row_stride = int(x_row_stride)
+    args.x_batch_stride = int(x_batch_stride)
+    args.x_src_fold = int(x_src_fold)
+    args.x_outer_stride = int(x_outer_stride)
+    args.F = F.data_ptr()
+    args.f_dtype = f_dtype
+    args.f_row_stride = int(f_row_stride)
+    args.f_batch_stride = int(f_batch_stride)
+    args.f_inner_stride = int(f_inner_stride)
+    args.f_outer_stride = int(f_outer_stride)
+    args.Y = Y.data_ptr()
+    args.y_row_stride = int(y_row_stride)
+    args.y_batch_stride = int(y_batch_stride)
+    args.n_batch = int(n_batch)
+    args.k_inner = int(k_inner)
+    args.threshold = float(threshold)
+    stream = ctypes.c_void_p(
+        torch.cuda.current_stream(plan.device).cuda_stream)
+    with torch.cuda.device(plan.device):
+        _check(lib.remap_apply_sgs(ctypes.byref(args), stream),
+               'remap_apply_sgs')
+
+
 def _prod(seq):
     out = 1
     for s in seq:
@@ -2392,6 +2540,142 @@ def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
         out.copy_(Y)
         Y = out
     return (Y, back(mask)) if want_mask else Y
+
+
+def _sgs_group(frac, shape, axes):
+    """How the axes ``axes`` of ``frac`` stand against a field of ``shape``:
+    ``(frac, full)`` -- ``full`` if every one has the field's extent, not
+    ``full`` if every one has extent 1; a group that mixes the two is
+    expanded to the field's extents first (one device copy later, when the
+    fraction is made contiguous)."""
+    full = all(int(frac.shape[ax]) == int(shape[ax]) for ax in axes)
+    if full or all(int(frac.shape[ax]) == 1 for ax in axes):
+        return frac, full
+    sizes = [int(shape[ax]) if ax in axes else -1
+             for ax in range(frac.ndim)]
+    return frac.expand(sizes), True
+
+
+def remap_tensor_sgs(plan, dst_grid_dims, field, frac, remap_axes,
+                     threshold=0.0):
+    """
+    :func:`remap_tensor` with sub-gridscale fraction weighting
+    (:mod:`pyremap_amd.sgs`; NCO's ``ncremap --sgs_frc``): ``field`` is a
+    mean over the fraction ``frac`` of every source cell; the result is
+    ``A.(frac * field) / A.frac`` with NaN in either skipped, in ONE launch
+    (``remap_apply_sgs``).  Same result shape and axis order as
+    :func:`remap_tensor`, NaN where ``valid <= threshold`` or the remapped
+    fraction is not positive.
+
+    ``frac`` has ``field``'s number of axes, its remap axes at full extent and
+    every other axis at the field's extent or 1.  Leading and trailing axis
+    groups that are uniformly full or uniformly 1 become strides (a stride of
+    0 broadcasts); a group that mixes the two is expanded once on the device.
+    One device only.
+    """
+    torch = _torch()
+    if hasattr(plan, 'shards') or not isinstance(plan, RemapPlan):
+        raise NotImplementedError(
+            'sub-gridscale weighting serves one device: not with a '
+            'multi-device or process-group plan')
+    remap_axes, dst_shape = check_field_extents(
+        plan.n_a, plan.n_b, plan.n_b_global, dst_grid_dims, field.shape,
+        remap_axes)
+    ndim = field.ndim
+    if frac.ndim != ndim:
+        raise ValueError(f'frac has {frac.ndim} axes, the field {ndim}')
+    if frac.device != field.device:
+        raise ValueError('frac and the field must live on the same device')
+    for ax in range(ndim):
+        want = int(field.shape[ax])
+        if int(frac.shape[ax]) != want and \
+                (ax in remap_axes or int(frac.shape[ax]) != 1):
+            raise ValueError(
+                f'frac of shape {tuple(frac.shape)} against a field of shape '
+                f'{tuple(field.shape)}: axis {ax} must have extent {want}' +
+                ('' if ax in remap_axes else ' or 1'))
+    extra_axes = [ax for ax in range(ndim) if ax not in remap_axes]
+    if field.dtype not in (torch.float64, torch.float32):
+        field = field.to(torch.float64)
+    if frac.dtype not in (torch.float64, torch.float32):
+        frac = frac.to(torch.float64)
+    lead = min(remap_axes)
+    lead_shape = [int(s) for s in field.shape[:lead]]
+    tail_shape = [int(field.shape[ax]) for ax in extra_axes if ax > lead]
+
+    if in_place_addressable(field.shape, remap_axes):
+        n_batch = _prod(lead_shape)
+        k_inner = _prod(tail_shape)
+        X = field.contiguous()
+        frac, lead_full = _sgs_group(frac, X.shape, list(range(lead)))
+        frac, tail_full = _sgs_group(
+            frac, X.shape, list(range(lead + len(remap_axes), ndim)))
+        F = frac.contiguous()
+        kf = k_inner if tail_full else 1
+        Y = torch.empty(lead_shape + dst_shape + tail_shape,
+                        dtype=torch.float64, device=X.device)
+        sgs_strided(
+            plan, X, F, Y, n_batch=n_batch, k_inner=k_inner,
+            x_row_stride=k_inner, x_batch_stride=plan.n_a * k_inner,
+            f_row_stride=kf,
+            f_batch_stride=plan.n_a * kf if lead_full else 0,
+            f_inner_stride=1 if tail_full else 0,
+            y_row_stride=k_inner, y_batch_stride=plan.n_b * k_inner,
+            threshold=threshold)
+        return Y
+    if len(remap_axes) == 2 and remap_axes[0] < remap_axes[1]:
+        # two source axes with other dims between them, as remap_tensor
+        # serves them: the dims between are the batches, a source cell is
+        # addressed through two strides, one launch per index of the dims in
+        # front
+        a0, a1 = remap_axes
+        X = field.contiguous()
+        lead_n = _prod(X.shape[:a0])
+        ny, nx = int(X.shape[a0]), int(X.shape[a1])
+        M = _prod(X.shape[a0 + 1:a1])
+        T = _prod(X.shape[a1 + 1:])
+        between = [int(s) for s in X.shape[a0 + 1:a1]]
+        trailing = [int(s) for s in X.shape[a1 + 1:]]
+        frac, lead_full = _sgs_group(frac, X.shape, list(range(a0)))
+        frac, mid_full = _sgs_group(frac, X.shape, list(range(a0 + 1, a1)))
+        frac, tail_full = _sgs_group(frac, X.shape,
+                                     list(range(a1 + 1, ndim)))
+        F = frac.contiguous()
+        Mf = M if mid_full else 1
+        Tf = T if tail_full else 1
+        Y = torch.empty([int(s) for s in X.shape[:a0]] + dst_shape +
+                        between + trailing, dtype=torch.float64,
+                        device=X.device)
+        Xl = X.reshape(lead_n, ny * M * nx * T)
+        Fl = F.reshape(lead_n if lead_full else 1, ny * Mf * nx * Tf)
+        Yl = Y.reshape(lead_n, _prod(dst_shape) * M * T)
+        for li in range(lead_n):
+            sgs_strided(
+                plan, Xl[li], Fl[li if lead_full else 0], Yl[li], n_batch=M,
+                k_inner=T, x_row_stride=T, x_batch_stride=nx * T,
+                f_row_stride=Tf, f_batch_stride=nx * Tf if mid_full else 0,
+                f_inner_stride=1 if tail_full else 0, y_row_stride=M * T,
+                y_batch_stride=T, threshold=threshold, x_src_fold=nx,
+                x_outer_stride=M * nx * T, f_outer_stride=Mf * nx * Tf)
+        return Y
+    # general axis order: one device transpose to (n_a, K), the kernel, one
+    # transpose back
+    K = _prod(field.shape[ax] for ax in extra_axes)
+    order = remap_axes + extra_axes
+    X = field.permute(order).reshape(plan.n_a, K).contiguous()
+    frac, full = _sgs_group(frac, field.shape, extra_axes)
+    Kf = K if full else 1
+    F = frac.permute(order).reshape(plan.n_a, Kf).contiguous()
+    Y = torch.empty((plan.n_b, K), dtype=torch.float64, device=field.device)
+    sgs_strided(plan, X, F, Y, n_batch=1, k_inner=K, x_row_stride=K,
+                x_batch_stride=0, f_row_stride=Kf, f_batch_stride=0,
+                f_inner_stride=1 if full else 0, y_row_stride=K,
+                y_batch_stride=0, threshold=threshold)
+    extra_shape = [int(field.shape[ax]) for ax in extra_axes]
+    n_dst = len(dst_shape)
+    tail = list(range(n_dst, n_dst + len(extra_shape)))
+    unpermute = tail[:lead] + list(range(n_dst)) + tail[lead:]
+    return Y.reshape(dst_shape + extra_shape).permute(unpermute).contiguous()
 
 
 def scan_nan(x, flag):

@@ -116,6 +116,82 @@ def _limiter_kwargs(remapper, limiter):
     return {'limiter': limiter}
 
 
+def _check_sgs(remapper):
+    """The Remapper's ``sgs_frac`` (None or a variable name) and what it
+    does not go together with."""
+    name = getattr(remapper, 'sgs_frac', None)
+    if name is None:
+        return None
+    if not isinstance(name, str):
+        raise TypeError(f'sgs_frac must be None or a variable name, not '
+                        f'{name!r}')
+    _check_sgs_alone(remapper)
+    return name
+
+
+def _check_sgs_alone(remapper):
+    """What sub-gridscale weighting does not go together with."""
+    if getattr(remapper, 'limiter', None) is not None:
+        raise NotImplementedError(
+            'sgs_frac together with a limiter is not served: one or the '
+            'other')
+    if getattr(remapper, '_process_group', None) is not None or \
+            len(getattr(remapper, 'devices', None) or ()) > 1:
+        raise NotImplementedError(
+            'sgs_frac serves one device: not with devices=[...] or a '
+            'process group')
+
+
+class _SgsFraction:
+    """The fraction variable of one ``remap_numpy`` / ``ncremap`` call
+    (``Remapper.sgs_frac``): read and uploaded once, when the first weighted
+    variable asks for it."""
+
+    def __init__(self, name, da, src_dims):
+        missing = [dim for dim in src_dims if dim not in da.dims]
+        if missing:
+            raise ValueError(
+                f'the sgs_frac variable {name!r} has dims {tuple(da.dims)}: '
+                f'it lacks the source dims {missing}')
+        self.name, self.da = name, da
+        self.dims = list(da.dims)
+        self._device = None
+
+    def weights(self, da):
+        """Is ``da`` weighted?  Every remapped variable whose dims contain
+        all dims of the fraction is; the fraction itself is not."""
+        return da.name != self.name and \
+            all(dim in da.dims for dim in self.dims)
+
+    def on_device(self, plan, dims):
+        """The fraction as a device tensor with one axis per entry of
+        ``dims`` (a weighted variable's), extent 1 where the fraction has no
+        such dim."""
+        torch = engine.require_gpu()
+        if self._device is None:
+            values = host_path._as_uploadable(self.da.values)
+            self._device = torch.from_numpy(values).to(plan.device)
+        have = [dim for dim in dims if dim in self.dims]
+        f = self._device.permute([self.dims.index(dim) for dim in have])
+        for axis, dim in enumerate(dims):
+            if dim not in self.dims:
+                f = f.unsqueeze(axis)
+        return f
+
+
+def _sgs_fraction(remapper, ds):
+    """None without ``Remapper.sgs_frac``; else the fraction variable of
+    ``ds`` (``KeyError`` naming it if ``ds`` has none)."""
+    name = _check_sgs(remapper)
+    if name is None:
+        return None
+    if not _is_dataset(ds) or name not in ds.variables:
+        raise KeyError(
+            f'sgs_frac names the variable {name!r}, which is not in the '
+            f'Dataset')
+    return _SgsFraction(name, ds[name], remapper.src_descriptor.dims)
+
+
 def _remap_numpy(remapper, ds, renormalization_threshold):
     """
     Remap a Dataset or DataArray, possibly masked and renormalized
@@ -124,6 +200,9 @@ def _remap_numpy(remapper, ds, renormalization_threshold):
     """
     if remapper.map_filename is None:
         raise ValueError('No mapping file has been defined')
+    # (before anything is loaded: a refusal or a missing fraction variable
+    # costs nothing)
+    sgs = _sgs_fraction(remapper, ds)
     _load_mapping(remapper, limiter=_check_limiter(remapper))
 
     expected = remapper._ds_map.src_grid_dims
@@ -146,11 +225,13 @@ def _remap_numpy(remapper, ds, renormalization_threshold):
             # variables still on disk (ncremap's streaming path): the result
             # is lazy too -- each variable is read, remapped and handed to the
             # writer in turn, never all of them at once
-            result = _lazy_dataset(remapper, kept, renormalization_threshold)
+            result = _lazy_dataset(remapper, kept, renormalization_threshold,
+                                   sgs=sgs)
         else:
             result = kept.map(
                 _LookAhead(remapper, kept, list(kept.data_vars),
-                           renormalization_threshold), keep_attrs=True)
+                           renormalization_threshold, sgs=sgs),
+                keep_attrs=True)
     else:
         raise TypeError('ds not an xarray Dataset or DataArray.')
 
@@ -325,7 +406,7 @@ def _plan_data_array(da, remapper):
     return remap_axes, dims, coords
 
 
-def _lazy_dataset(remapper, ds, renormalization_threshold):
+def _lazy_dataset(remapper, ds, renormalization_threshold, sgs=None):
     """
     ``ds.map(_remap_data_array, keep_attrs=True)`` for a Dataset whose
     variables are (partly) still on disk: same variables, dims, coordinates
@@ -353,7 +434,7 @@ def _lazy_dataset(remapper, ds, renormalization_threshold):
             def start(da=da):
                 finish = _start_data_array(da, remapper,
                                            renormalization_threshold,
-                                           keep_on_device=True)
+                                           keep_on_device=True, sgs=sgs)
                 return lambda: finish().values
             out = xr_lite.DataArray(
                 xr_lite.LazyValues(shape, np.float64,
@@ -369,18 +450,38 @@ def _lazy_dataset(remapper, ds, renormalization_threshold):
 
 
 def _start_data_array(da, remapper, renormalization_threshold,
-                      keep_on_device=False):
+                      keep_on_device=False, sgs=None):
     """
     Enqueue the remap of one variable -- upload, NaN scan, launch, download,
     none of which waits for the host -- and return the function that waits
     for the data and assembles the result.  ``keep_on_device``: the download
     waits too, until the result is asked for (the streaming file path: the
-    host then holds one result at a time).
+    host then holds one result at a time).  ``sgs``: the call's
+    :class:`_SgsFraction` (``Remapper.sgs_frac``); a variable it weights
+    takes the whole-array route -- upload, ``engine.remap_tensor_sgs``,
+    download.
     """
     plan = _plan_data_array(da, remapper)
     if plan is None:
         return lambda: da  # nothing to remap
     remap_axes, dims, coords = plan
+
+    if sgs is not None and sgs.weights(da):
+        torch = engine.require_gpu()
+        matrix = remapper._matrix
+        values = host_path._as_uploadable(da.values)
+        y_d = engine.remap_tensor_sgs(
+            matrix, remapper._ds_map.dst_grid_dims,
+            torch.from_numpy(values).to(matrix.device),
+            sgs.on_device(matrix, list(da.dims)), remap_axes,
+            threshold=0.0 if renormalization_threshold is None
+            else renormalization_threshold)
+        # (the download waits until the result is asked for)
+        pending = host_path.OnDevice(y_d, tuple(y_d.shape))
+        make = _array_class(da).from_dict
+        attrs, name = da.attrs, da.name
+        return lambda: make({'coords': coords, 'attrs': attrs, 'dims': dims,
+                             'data': pending.result(), 'name': name})
 
     if getattr(remapper, '_process_group', None) is not None:
         data = _collective_array(remapper, da.values, remap_axes,
@@ -431,8 +532,10 @@ def _batches(remapper, ds, names):
     plan = getattr(remapper, '_matrix', None)
     if getattr(remapper, '_process_group', None) is not None or \
             plan is None or hasattr(plan, 'shards') or \
-            getattr(remapper, 'limiter', None) is not None:
-        # (a limited variable takes the whole-array route, one at a time)
+            getattr(remapper, 'limiter', None) is not None or \
+            getattr(remapper, 'sgs_frac', None) is not None:
+        # (a limited or fraction-weighted variable takes the whole-array
+        # route, one at a time)
         return {}
     groups = {}
     src_dims = remapper.src_descriptor.dims
@@ -503,9 +606,9 @@ class _LookAhead:
     (reference: the per-variable loop of ``remap_numpy.py:42-55``).
     """
 
-    def __init__(self, remapper, ds, names, threshold, depth=2):
+    def __init__(self, remapper, ds, names, threshold, depth=2, sgs=None):
         self.remapper, self.ds, self.names = remapper, ds, list(names)
-        self.threshold, self.depth = threshold, depth
+        self.threshold, self.depth, self.sgs = threshold, depth, sgs
         self.started = {}
         self.position = 0
         self.batches = _batches(remapper, ds, self.names)
@@ -522,7 +625,8 @@ class _LookAhead:
                         self.ds, batch, self.remapper, self.threshold))
                 else:
                     self.started[name] = _start_data_array(
-                        self.ds[name], self.remapper, self.threshold)
+                        self.ds[name], self.remapper, self.threshold,
+                        sgs=self.sgs)
             self.position += 1
 
     def __call__(self, da, *unused):
@@ -597,6 +701,47 @@ def _collective_array(remapper, values, remap_axes, threshold, mode='auto',
                                        dtype=torch.float64, mode='raw', **kw)
             y = torch.where(torch.isnan(hit), float('nan'), y)
     return y.cpu().numpy(), mask.cpu().numpy().astype(bool)
+
+
+def _host_values(torch, array, device):
+    """A host array (masked entries as NaN) as a float device tensor."""
+    if isinstance(array, np.ma.MaskedArray):
+        data = np.ma.getdata(array)
+        if data.dtype not in (np.float32, np.float64):
+            data = data.astype(np.float64)
+        array = np.where(np.ma.getmaskarray(array), np.nan, data)
+    return torch.from_numpy(host_path._as_uploadable(array)).to(device)
+
+
+def _remap_array_sgs(remapper, in_field, sgs_frac, remap_axes,
+                     renormalization_threshold):
+    """
+    One array through ``engine.remap_tensor_sgs``: device tensors in, device
+    tensor out (NaN where masked); numpy in, ``numpy.ma.MaskedArray`` out
+    with the mask taken from NaN.  ``None`` threshold means 0.0.
+    """
+    _check_sgs_alone(remapper)
+    torch = engine.require_gpu()
+    plan = remapper._matrix
+    threshold = 0.0 if renormalization_threshold is None else \
+        float(renormalization_threshold)
+    remap_axes = [int(a) for a in remap_axes]
+    on_device = isinstance(in_field, torch.Tensor)
+    if on_device != isinstance(sgs_frac, torch.Tensor):
+        raise TypeError('field and sgs_frac must both be device tensors or '
+                        'both host arrays')
+    if on_device:
+        field, frac = in_field.to(plan.device), sgs_frac.to(plan.device)
+    else:
+        field = _host_values(torch, in_field, plan.device)
+        frac = _host_values(torch, sgs_frac, plan.device)
+    out = engine.remap_tensor_sgs(
+        plan, remapper._ds_map.dst_grid_dims, field, frac, remap_axes,
+        threshold=threshold)
+    if on_device:
+        return out
+    out = out.cpu().numpy()
+    return np.ma.masked_array(out, mask=np.isnan(out))
 
 
 def _remap_numpy_array(remapper, in_field, remap_axes,
