@@ -36,14 +36,18 @@
 #include <cstdint>
 
 #include "remap_common.h"
+#include "rowpass.h"
 
 namespace remap {
 namespace {
 
+using namespace rowpass;
+
+constexpr char kName[] = "remap_limit_rows";
 constexpr int kUnroll = 8;
 constexpr int64_t kRowsFastRun = 4;   // (engine.CELL_MAX_RUN)
 
-struct LimitParams {
+struct LimitParams {                // (rowpass.h: P)
     const int64_t *__restrict__ rowptr;
     const int32_t *__restrict__ col;
     const void *__restrict__ X;
@@ -58,19 +62,15 @@ struct LimitParams {
     int64_t total;                  // n_rows * K
 };
 
-// element offset of source cell a (remap_limit_args.x_src_fold)
-__device__ inline int64_t cell_offset(const LimitParams &p, int32_t a)
+// element offset of source cell a in X
+__device__ inline int64_t x_offset(const LimitParams &p, int32_t a)
 {
-    if (p.src_fold == 0)
-        return static_cast<int64_t>(a) * p.ldx;
-    const uint32_t y = static_cast<uint32_t>(a) / p.src_fold;
-    const uint32_t x = static_cast<uint32_t>(a) - y * p.src_fold;
-    return static_cast<int64_t>(y) * p.src_outer +
-           static_cast<int64_t>(x) * p.ldx;
+    int64_t o[1];
+    cell_offsets(p, a, {p.ldx}, {p.src_outer}, o);
+    return o[0];
 }
 
-// IT: the type the flat index is split in (32 bits where total fits: the
-// 64-bit division is a long instruction sequence)
+// IT: the type the flat index is split in (rowpass::narrow_index)
 template <typename XT, typename IT, bool ROWS_FAST>
 __global__ __launch_bounds__(kBlock) void limit_rowlane(const LimitParams p)
 {
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(kBlock) void limit_rowlane(const LimitParams p)
         }
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u)
-            xs[u] = X[cell_offset(p, c[u])];
+            xs[u] = X[x_offset(p, c[u])];
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) {
             const double x = static_cast<double>(xs[u]);
@@ -145,58 +145,17 @@ __global__ __launch_bounds__(kBlock) void limit_rowlane(const LimitParams p)
 
 // ---------------------------------------------------------------------------
 // rowwave: one wave per (row, chunk of kWave * VEC contiguous columns), lanes
-// across the columns, as spmm_rowwave.h -- for runs of >= kWave columns.  The
-// row is the same in every lane, so the row pointers and the column indices
-// are scalar loads, the loop over the row's entries is wave-uniform and reads
-// exactly the row's entries (no clamped duplicates), UNR source runs in
-// flight at a time; VEC = 2: 16-byte loads and stores of fp64 (even strides
-// and run lengths, aligned pointers).  The waves of a block hold adjacent
-// rows of one chunk (chunk-major work list): they share source cells in L1;
-// blocks are dealt round-robin over the 8 XCDs, so blockIdx % 8 labels the
-// XCD and every label takes a contiguous range of the work list: the rows
-// one L2 sees are neighbours too.  Y, lo and hi are touched once: they are
-// read and written past the caches' keep (non-temporal), as the apply
-// kernels write Y.
+// across the columns, as spmm_rowwave.h -- for runs of >= kWave columns; the
+// work list and VEC are rowpass.h's.  The row is the same in every lane, so
+// the row pointers and the column indices are scalar loads, the loop over the
+// row's entries is wave-uniform and reads exactly the row's entries (no
+// clamped duplicates), UNR source runs in flight at a time.  Y, lo and hi are
+// touched once (load_once, store_once).
 // ---------------------------------------------------------------------------
-template <typename XT, int VEC>
-struct alignas(sizeof(XT) * VEC) Pack {
-    XT v[VEC];
-};
-
 struct Bounds {
     double lo, hi;
     bool has;
 };
-
-typedef double Double2 __attribute__((ext_vector_type(2)));
-
-template <int VEC>
-__device__ inline Pack<double, VEC> load_once(const double *ptr)
-{
-    Pack<double, VEC> out;
-    if constexpr (VEC == 2) {
-        const Double2 t = __builtin_nontemporal_load(
-            reinterpret_cast<const Double2 *>(ptr));
-        out.v[0] = t.x;
-        out.v[1] = t.y;
-    } else {
-        out.v[0] = __builtin_nontemporal_load(ptr);
-    }
-    return out;
-}
-
-template <int VEC>
-__device__ inline void store_once(double *ptr, const Pack<double, VEC> &v)
-{
-    if constexpr (VEC == 2) {
-        Double2 t;
-        t.x = v.v[0];
-        t.y = v.v[1];
-        __builtin_nontemporal_store(t, reinterpret_cast<Double2 *>(ptr));
-    } else {
-        __builtin_nontemporal_store(v.v[0], ptr);
-    }
-}
 
 __device__ inline void widen(Bounds &b, double x)
 {
@@ -222,11 +181,7 @@ __global__ __launch_bounds__(kBlock) void limit_rowwave(const LimitParams p,
 {
     constexpr int UNR = 4;
     const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // physical block -> logical block: a contiguous range for every XCD
-    const int64_t L = (int64_t)(blockIdx.x & (kXcds - 1)) * per_xcd +
-                      (blockIdx.x >> 3);
-    const int64_t w = L * kWavesPerBlock + wave;
+    const int64_t w = rowwave_place(per_xcd);
     if (w >= n_waves)
         return;
     const int64_t cb = w / p.n_rows;            // (batch, chunk), chunk-major
@@ -254,7 +209,7 @@ __global__ __launch_bounds__(kBlock) void limit_rowwave(const LimitParams p,
 #pragma unroll
         for (int u = 0; u < UNR; ++u)
             xs[u] = *reinterpret_cast<const PX *>(
-                X + cell_offset(p, p.col[j + u]));
+                X + x_offset(p, p.col[j + u]));
 #pragma unroll
         for (int u = 0; u < UNR; ++u)
 #pragma unroll
@@ -263,7 +218,7 @@ __global__ __launch_bounds__(kBlock) void limit_rowwave(const LimitParams p,
     }
     for (; j < e; ++j) {
         const PX x = *reinterpret_cast<const PX *>(
-            X + cell_offset(p, p.col[j]));
+            X + x_offset(p, p.col[j]));
 #pragma unroll
         for (int v = 0; v < VEC; ++v)
             widen(bd[v], static_cast<double>(x.v[v]));
@@ -289,51 +244,34 @@ __global__ __launch_bounds__(kBlock) void limit_rowwave(const LimitParams p,
         store_once<VEC>(p.hi + o, hi);
 }
 
-inline bool aligned_to(const void *ptr, size_t bytes)
-{
-    return ptr == nullptr || reinterpret_cast<uintptr_t>(ptr) % bytes == 0;
-}
-
 template <typename XT>
 int launch_rowwave(const LimitParams &p, int64_t n_batch, hipStream_t stream)
 {
-    const bool even = p.k_inner % 2 == 0 && p.ldx % 2 == 0 &&
-                      p.bsx % 2 == 0 && p.ldy % 2 == 0 && p.bsy % 2 == 0 &&
-                      p.src_outer % 2 == 0 &&
-                      aligned_to(p.X, 2 * sizeof(XT)) &&
+    const bool even = even_strides(p) && aligned_to(p.X, 2 * sizeof(XT)) &&
                       aligned_to(p.Y, 16) && aligned_to(p.lo, 16) &&
                       aligned_to(p.hi, 16);
-    const int vec = even ? 2 : 1;
-    const int64_t chunks = (p.k_inner + kWave * vec - 1) / (kWave * vec);
-    // (n_rows * n_batch * k_inner was checked against INT64_MAX / kBlock)
-    const int64_t n_waves = p.n_rows * n_batch * chunks;
-    const int64_t n_blocks = (n_waves + kWavesPerBlock - 1) / kWavesPerBlock;
-    // (whole rounds of the 8 XCDs; the waves past n_waves leave at once)
-    const int64_t per_xcd = (n_blocks + kXcds - 1) / kXcds;
-    if (per_xcd * kXcds > INT32_MAX)
-        return fail(REMAP_ERR_ARG,
-                    "remap_limit_rows: %lld elements are more than one "
-                    "launch serves", (long long)p.total);
-    const dim3 grid(static_cast<unsigned>(per_xcd * kXcds));
+    WaveGrid g;
+    const int rc = rowwave_grid(kName, p, n_batch, even ? 2 : 1, g);
+    if (rc != REMAP_OK)
+        return rc;
     if (even)
-        hipLaunchKernelGGL((limit_rowwave<XT, 2>), grid, dim3(kBlock), 0,
-                           stream, p, n_waves, chunks, per_xcd);
+        hipLaunchKernelGGL((limit_rowwave<XT, 2>), g.grid, dim3(kBlock), 0,
+                           stream, p, g.n_waves, g.chunks, g.per_xcd);
     else
-        hipLaunchKernelGGL((limit_rowwave<XT, 1>), grid, dim3(kBlock), 0,
-                           stream, p, n_waves, chunks, per_xcd);
+        hipLaunchKernelGGL((limit_rowwave<XT, 1>), g.grid, dim3(kBlock), 0,
+                           stream, p, g.n_waves, g.chunks, g.per_xcd);
     return REMAP_OK;
 }
 
 template <typename XT, typename IT>
-void launch_limit(const LimitParams &p, bool rows_fast, unsigned n_blocks,
-                  hipStream_t stream)
+void launch_limit(const LimitParams &p, bool rows_fast, hipStream_t stream)
 {
     if (rows_fast)
-        hipLaunchKernelGGL((limit_rowlane<XT, IT, true>), dim3(n_blocks),
-                           dim3(kBlock), 0, stream, p);
+        hipLaunchKernelGGL((limit_rowlane<XT, IT, true>),
+                           rowlane_grid(p.total), dim3(kBlock), 0, stream, p);
     else
-        hipLaunchKernelGGL((limit_rowlane<XT, IT, false>), dim3(n_blocks),
-                           dim3(kBlock), 0, stream, p);
+        hipLaunchKernelGGL((limit_rowlane<XT, IT, false>),
+                           rowlane_grid(p.total), dim3(kBlock), 0, stream, p);
 }
 
 }  // namespace
@@ -341,81 +279,23 @@ void launch_limit(const LimitParams &p, bool rows_fast, unsigned n_blocks,
 int limit_rows(const remap_limit_args *a, hipStream_t stream)
 {
     if (!a)
-        return fail(REMAP_ERR_ARG, "remap_limit_rows: NULL args");
-    const remap_csr &A = a->A;
-    if (A.n_rows < 0 || A.n_cols < 0 || A.nnz < 0 ||
-        A.n_cols > INT32_MAX || A.n_rows > INT32_MAX)
-        return fail(REMAP_ERR_ARG,
-                    "remap_limit_rows: a (%lld, %lld) matrix of %lld "
-                    "entries: expected sizes in [0, 2^31)",
-                    (long long)A.n_rows, (long long)A.n_cols,
-                    (long long)A.nnz);
-    if (a->row_begin < 0 || a->row_end < a->row_begin ||
-        a->row_end > A.n_rows)
-        return fail(REMAP_ERR_ARG,
-                    "remap_limit_rows: rows [%lld, %lld) are not inside "
-                    "[0, %lld]", (long long)a->row_begin,
-                    (long long)a->row_end, (long long)A.n_rows);
-    if (a->n_batch < 0 || a->k_inner < 0)
-        return fail(REMAP_ERR_ARG,
-                    "remap_limit_rows: n_batch %lld, k_inner %lld: expected "
-                    ">= 0", (long long)a->n_batch, (long long)a->k_inner);
-    if (a->x_dtype != REMAP_DTYPE_F64 && a->x_dtype != REMAP_DTYPE_F32)
-        return fail(REMAP_ERR_ARG, "remap_limit_rows: x_dtype %d is no "
-                                   "REMAP_DTYPE_*", a->x_dtype);
-    if (a->x_row_stride < 0 || a->x_batch_stride < 0 ||
-        a->y_row_stride < 0 || a->y_batch_stride < 0)
-        return fail(REMAP_ERR_ARG, "remap_limit_rows: a negative stride");
-    if (a->x_src_fold < 0 || a->x_src_fold >= (int64_t(1) << 31) ||
-        (a->x_src_fold != 0 &&
-         (a->x_outer_stride < 0 || A.n_cols % a->x_src_fold != 0)))
-        return fail(REMAP_ERR_ARG,
-                    "remap_limit_rows: x_src_fold = %lld does not divide the "
-                    "%lld source cells", (long long)a->x_src_fold,
-                    (long long)A.n_cols);
-    const int64_t n_rows = a->row_end - a->row_begin;
-    if (n_rows == 0 || a->n_batch == 0 || a->k_inner == 0)
-        return REMAP_OK;
-    const int64_t K = a->n_batch > INT32_MAX || a->k_inner > INT32_MAX
-                          ? INT64_MAX : a->n_batch * a->k_inner;
-    if (K > (INT64_MAX / kBlock) / n_rows)
-        return fail(REMAP_ERR_ARG,
-                    "remap_limit_rows: %lld rows of %lld x %lld columns are "
-                    "more than one launch serves", (long long)n_rows,
-                    (long long)a->n_batch, (long long)a->k_inner);
-    if (!A.rowptr || (A.nnz > 0 && !A.col) || !a->X || !a->Y)
-        return fail(REMAP_ERR_ARG,
-                    "remap_limit_rows: NULL rowptr, col, X or Y");
-    const int64_t total = n_rows * K;
-    const int64_t n_blocks = (total + kBlock - 1) / kBlock;
-    if (n_blocks > INT32_MAX)
-        return fail(REMAP_ERR_ARG,
-                    "remap_limit_rows: %lld elements are more than one "
-                    "launch serves", (long long)total);
+        return fail(REMAP_ERR_ARG, "%s: NULL args", kName);
     LimitParams p;
-    p.rowptr = A.rowptr;
-    p.col = A.col;
+    bool empty;
+    const int checked = check_args(kName, *a, p, empty);
+    if (checked != REMAP_OK || empty)
+        return checked;
+    if (!p.rowptr || (a->A.nnz > 0 && !p.col) || !a->X || !a->Y)
+        return fail(REMAP_ERR_ARG, "%s: NULL rowptr, col, X or Y", kName);
     p.X = a->X;
     p.Y = a->Y;
     p.lo = a->lo;
     p.hi = a->hi;
-    p.row_begin = a->row_begin;
-    p.n_rows = n_rows;
-    p.K = K;
-    p.k_inner = a->k_inner;
-    p.ldx = a->x_row_stride;
-    p.bsx = a->x_batch_stride;
-    p.ldy = a->y_row_stride;
-    p.bsy = a->y_batch_stride;
-    p.src_outer = a->x_outer_stride;
-    p.src_fold = static_cast<uint32_t>(a->x_src_fold);
-    p.total = total;
     // short runs in several batches whose rows lie closer than its batches:
     // neighbouring lanes take neighbouring rows
     const bool rows_fast = a->k_inner < kRowsFastRun && a->n_batch > 1 &&
                            a->y_row_stride <= a->y_batch_stride;
-    const bool narrow = total <= static_cast<int64_t>(UINT32_MAX);
-    const unsigned nb = static_cast<unsigned>(n_blocks);
+    const bool narrow = narrow_index(p);
     if (a->k_inner >= kWave) {
         // runs of a wave's width and more: a wave per (row, chunk)
         const int rc = a->x_dtype == REMAP_DTYPE_F64
@@ -425,14 +305,14 @@ int limit_rows(const remap_limit_args *a, hipStream_t stream)
             return rc;
     } else if (a->x_dtype == REMAP_DTYPE_F64) {
         if (narrow)
-            launch_limit<double, uint32_t>(p, rows_fast, nb, stream);
+            launch_limit<double, uint32_t>(p, rows_fast, stream);
         else
-            launch_limit<double, int64_t>(p, rows_fast, nb, stream);
+            launch_limit<double, int64_t>(p, rows_fast, stream);
     } else {
         if (narrow)
-            launch_limit<float, uint32_t>(p, rows_fast, nb, stream);
+            launch_limit<float, uint32_t>(p, rows_fast, stream);
         else
-            launch_limit<float, int64_t>(p, rows_fast, nb, stream);
+            launch_limit<float, int64_t>(p, rows_fast, stream);
     }
     REMAP_HIP_CHECK(hipGetLastError());
     return REMAP_OK;

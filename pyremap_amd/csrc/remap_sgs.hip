@@ -31,13 +31,17 @@
 #include <cstdint>
 
 #include "remap_common.h"
+#include "rowpass.h"
 
 namespace remap {
 namespace {
 
+using namespace rowpass;
+
+constexpr char kName[] = "remap_apply_sgs";
 constexpr int kUnroll = 8;
 
-struct SgsParams {
+struct SgsParams {                  // (rowpass.h: P)
     const int64_t *__restrict__ rowptr;
     const int32_t *__restrict__ col;
     const double *__restrict__ val;
@@ -54,21 +58,14 @@ struct SgsParams {
     double thr;
 };
 
-// element offsets of source cell a in X and in F (remap_sgs_args.x_src_fold)
+// element offsets of source cell a in X and in F, from one split
 __device__ inline void cell_offsets(const SgsParams &p, int32_t a,
                                     int64_t &ox, int64_t &of)
 {
-    if (p.src_fold == 0) {
-        ox = static_cast<int64_t>(a) * p.ldx;
-        of = static_cast<int64_t>(a) * p.ldf;
-        return;
-    }
-    const uint32_t y = static_cast<uint32_t>(a) / p.src_fold;
-    const uint32_t x = static_cast<uint32_t>(a) - y * p.src_fold;
-    ox = static_cast<int64_t>(y) * p.src_outer +
-         static_cast<int64_t>(x) * p.ldx;
-    of = static_cast<int64_t>(y) * p.f_outer +
-         static_cast<int64_t>(x) * p.ldf;
+    int64_t o[2];
+    rowpass::cell_offsets(p, a, {p.ldx, p.ldf}, {p.src_outer, p.f_outer}, o);
+    ox = o[0];
+    of = o[1];
 }
 
 struct Sums {
@@ -96,8 +93,7 @@ __device__ inline double finish(const Sums &s, double thr)
     return (s.valid > thr && s.den > 0.0 && q == q) ? q : __builtin_nan("");
 }
 
-// IT: the type the flat index is split in (32 bits where total fits: the
-// 64-bit division is a long instruction sequence).
+// IT: the type the flat index is split in (rowpass::narrow_index).
 // BATCH_MAJOR (several batches whose rows lie closer than the batches: (Time,
 // nCells[, nCategories])): the lanes run over (row, k) of ONE batch, k
 // fastest -- for k_inner == 1 neighbouring lanes hold neighbouring rows, and
@@ -193,14 +189,12 @@ __global__ __launch_bounds__(kBlock) void sgs_rowlane(const SgsParams p,
 
 // ---------------------------------------------------------------------------
 // rowwave: one wave per (row, chunk of kWave * VEC contiguous columns), lanes
-// across the columns, as limit_rowwave -- for runs of >= kWave columns.  The
-// row is the same in every lane, so the row pointers, the column indices and
-// the weights are scalar loads, the loop over the row's entries is
-// wave-uniform and reads exactly the row's entries, UNR source runs in flight
-// at a time; VEC = 2: 16-byte loads and stores of fp64 (even strides and run
-// lengths, aligned pointers).  The work list is chunk-major and dealt to the
-// XCDs in contiguous ranges, as limit_rowwave's.  Y is written once, past the
-// caches' keep (non-temporal).
+// across the columns, as limit_rowwave -- for runs of >= kWave columns; the
+// work list and VEC are rowpass.h's.  The row is the same in every lane, so
+// the row pointers, the column indices and the weights are scalar loads, the
+// loop over the row's entries is wave-uniform and reads exactly the row's
+// entries, UNR source runs in flight at a time.  Y is written once
+// (store_once).
 //
 // F_UNI (f_inner_stride == 0, the common case: a (Time, nCells) fraction for
 // (Time, nCells, nCategories) fields): the fraction of an entry is the same
@@ -211,26 +205,6 @@ __global__ __launch_bounds__(kBlock) void sgs_rowlane(const SgsParams p,
 // row.  Every lane performs the same additions in the same order either way:
 // the bits do not depend on which loop served an entry.
 // ---------------------------------------------------------------------------
-template <typename T, int VEC>
-struct alignas(sizeof(T) * VEC) Pack {
-    T v[VEC];
-};
-
-typedef double Double2 __attribute__((ext_vector_type(2)));
-
-template <int VEC>
-__device__ inline void store_once(double *ptr, const Pack<double, VEC> &v)
-{
-    if constexpr (VEC == 2) {
-        Double2 t;
-        t.x = v.v[0];
-        t.y = v.v[1];
-        __builtin_nontemporal_store(t, reinterpret_cast<Double2 *>(ptr));
-    } else {
-        __builtin_nontemporal_store(v.v[0], ptr);
-    }
-}
-
 template <typename XT, typename FT, int VEC, bool F_UNI>
 __global__ __launch_bounds__(kBlock) void sgs_rowwave(const SgsParams p,
                                                       const int64_t n_waves,
@@ -239,11 +213,7 @@ __global__ __launch_bounds__(kBlock) void sgs_rowwave(const SgsParams p,
 {
     constexpr int UNR = 4;
     const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // physical block -> logical block: a contiguous range for every XCD
-    const int64_t L = (int64_t)(blockIdx.x & (kXcds - 1)) * per_xcd +
-                      (blockIdx.x >> 3);
-    const int64_t w = L * kWavesPerBlock + wave;
+    const int64_t w = rowwave_place(per_xcd);
     if (w >= n_waves)
         return;
     const int64_t cb = w / p.n_rows;            // (batch, chunk), chunk-major
@@ -349,49 +319,35 @@ __global__ __launch_bounds__(kBlock) void sgs_rowwave(const SgsParams p,
     store_once<VEC>(p.Y + o, y);
 }
 
-inline bool aligned_to(const void *ptr, size_t bytes)
-{
-    return reinterpret_cast<uintptr_t>(ptr) % bytes == 0;
-}
-
 template <typename XT, typename FT>
 int launch_rowwave(const SgsParams &p, int64_t n_batch, hipStream_t stream)
 {
     const bool f_uni = p.isf == 0;
-    const bool even = p.k_inner % 2 == 0 && p.ldx % 2 == 0 &&
-                      p.bsx % 2 == 0 && p.ldy % 2 == 0 && p.bsy % 2 == 0 &&
-                      p.src_outer % 2 == 0 &&
-                      aligned_to(p.X, 2 * sizeof(XT)) &&
+    const bool even = even_strides(p) && aligned_to(p.X, 2 * sizeof(XT)) &&
                       aligned_to(p.Y, 16) &&
                       (f_uni || (p.ldf % 2 == 0 && p.bsf % 2 == 0 &&
                                  p.f_outer % 2 == 0 &&
                                  aligned_to(p.F, 2 * sizeof(FT))));
-    const int vec = even ? 2 : 1;
-    const int64_t chunks = (p.k_inner + kWave * vec - 1) / (kWave * vec);
-    // (n_rows * n_batch * k_inner was checked against INT64_MAX / kBlock)
-    const int64_t n_waves = p.n_rows * n_batch * chunks;
-    const int64_t n_blocks = (n_waves + kWavesPerBlock - 1) / kWavesPerBlock;
-    // (whole rounds of the 8 XCDs; the waves past n_waves leave at once)
-    const int64_t per_xcd = (n_blocks + kXcds - 1) / kXcds;
-    if (per_xcd * kXcds > INT32_MAX)
-        return fail(REMAP_ERR_ARG,
-                    "remap_apply_sgs: %lld elements are more than one "
-                    "launch serves", (long long)p.total);
-    const dim3 grid(static_cast<unsigned>(per_xcd * kXcds));
+    WaveGrid g;
+    const int rc = rowwave_grid(kName, p, n_batch, even ? 2 : 1, g);
+    if (rc != REMAP_OK)
+        return rc;
     if (even && f_uni)
-        hipLaunchKernelGGL((sgs_rowwave<XT, FT, 2, true>), grid, dim3(kBlock),
-                           0, stream, p, n_waves, chunks, per_xcd);
+        hipLaunchKernelGGL((sgs_rowwave<XT, FT, 2, true>), g.grid,
+                           dim3(kBlock), 0, stream, p, g.n_waves, g.chunks,
+                           g.per_xcd);
     else if (even)
-        hipLaunchKernelGGL((sgs_rowwave<XT, FT, 2, false>), grid,
-                           dim3(kBlock), 0, stream, p, n_waves, chunks,
-                           per_xcd);
+        hipLaunchKernelGGL((sgs_rowwave<XT, FT, 2, false>), g.grid,
+                           dim3(kBlock), 0, stream, p, g.n_waves, g.chunks,
+                           g.per_xcd);
     else if (f_uni)
-        hipLaunchKernelGGL((sgs_rowwave<XT, FT, 1, true>), grid, dim3(kBlock),
-                           0, stream, p, n_waves, chunks, per_xcd);
+        hipLaunchKernelGGL((sgs_rowwave<XT, FT, 1, true>), g.grid,
+                           dim3(kBlock), 0, stream, p, g.n_waves, g.chunks,
+                           g.per_xcd);
     else
-        hipLaunchKernelGGL((sgs_rowwave<XT, FT, 1, false>), grid,
-                           dim3(kBlock), 0, stream, p, n_waves, chunks,
-                           per_xcd);
+        hipLaunchKernelGGL((sgs_rowwave<XT, FT, 1, false>), g.grid,
+                           dim3(kBlock), 0, stream, p, g.n_waves, g.chunks,
+                           g.per_xcd);
     return REMAP_OK;
 }
 
@@ -405,8 +361,8 @@ int launch_sgs(const SgsParams &p, int64_t n_batch, bool batch_major,
     SgsParams q = p;
     if (batch_major)                // (a lane per kBatches batches)
         q.total = (n_batch + kBatches - 1) / kBatches * p.n_rows * p.k_inner;
-    const dim3 grid(static_cast<unsigned>((q.total + kBlock - 1) / kBlock));
-    const bool narrow = p.total <= static_cast<int64_t>(UINT32_MAX);
+    const dim3 grid = rowlane_grid(q.total);
+    const bool narrow = narrow_index(p);
     if (narrow && batch_major)
         hipLaunchKernelGGL((sgs_rowlane<XT, FT, uint32_t, true>), grid,
                            dim3(kBlock), 0, stream, q, n_batch);
@@ -427,88 +383,38 @@ int launch_sgs(const SgsParams &p, int64_t n_batch, bool batch_major,
 int apply_sgs(const remap_sgs_args *a, hipStream_t stream)
 {
     if (!a)
-        return fail(REMAP_ERR_ARG, "remap_apply_sgs: NULL args");
-    const remap_csr &A = a->A;
-    if (A.n_rows < 0 || A.n_cols < 0 || A.nnz < 0 ||
-        A.n_cols > INT32_MAX || A.n_rows > INT32_MAX)
-        return fail(REMAP_ERR_ARG,
-                    "remap_apply_sgs: a (%lld, %lld) matrix of %lld "
-                    "entries: expected sizes in [0, 2^31)",
-                    (long long)A.n_rows, (long long)A.n_cols,
-                    (long long)A.nnz);
-    if (a->row_begin < 0 || a->row_end < a->row_begin ||
-        a->row_end > A.n_rows)
-        return fail(REMAP_ERR_ARG,
-                    "remap_apply_sgs: rows [%lld, %lld) are not inside "
-                    "[0, %lld]", (long long)a->row_begin,
-                    (long long)a->row_end, (long long)A.n_rows);
-    if (a->n_batch < 0 || a->k_inner < 0)
-        return fail(REMAP_ERR_ARG,
-                    "remap_apply_sgs: n_batch %lld, k_inner %lld: expected "
-                    ">= 0", (long long)a->n_batch, (long long)a->k_inner);
-    if (a->x_dtype != REMAP_DTYPE_F64 && a->x_dtype != REMAP_DTYPE_F32)
-        return fail(REMAP_ERR_ARG, "remap_apply_sgs: x_dtype %d is no "
-                                   "REMAP_DTYPE_*", a->x_dtype);
+        return fail(REMAP_ERR_ARG, "%s: NULL args", kName);
+    // what the fraction adds to the shared checks
     if (a->f_dtype != REMAP_DTYPE_F64 && a->f_dtype != REMAP_DTYPE_F32)
-        return fail(REMAP_ERR_ARG, "remap_apply_sgs: f_dtype %d is no "
-                                   "REMAP_DTYPE_*", a->f_dtype);
-    if (a->x_row_stride < 0 || a->x_batch_stride < 0 ||
-        a->f_row_stride < 0 || a->f_batch_stride < 0 ||
-        a->y_row_stride < 0 || a->y_batch_stride < 0)
-        return fail(REMAP_ERR_ARG, "remap_apply_sgs: a negative stride");
+        return fail(REMAP_ERR_ARG, "%s: f_dtype %d is no REMAP_DTYPE_*",
+                    kName, a->f_dtype);
+    if (a->f_row_stride < 0 || a->f_batch_stride < 0)
+        return fail(REMAP_ERR_ARG, "%s: a negative stride", kName);
     if (a->f_inner_stride != 0 && a->f_inner_stride != 1)
         return fail(REMAP_ERR_ARG,
-                    "remap_apply_sgs: f_inner_stride %lld: expected 0 "
-                    "(broadcast) or 1", (long long)a->f_inner_stride);
-    if (a->x_src_fold < 0 || a->x_src_fold >= (int64_t(1) << 31) ||
-        (a->x_src_fold != 0 &&
-         (a->x_outer_stride < 0 || a->f_outer_stride < 0 ||
-          A.n_cols % a->x_src_fold != 0)))
+                    "%s: f_inner_stride %lld: expected 0 (broadcast) or 1",
+                    kName, (long long)a->f_inner_stride);
+    if (a->x_src_fold != 0 && a->f_outer_stride < 0)
         return fail(REMAP_ERR_ARG,
-                    "remap_apply_sgs: x_src_fold = %lld does not divide the "
-                    "%lld source cells", (long long)a->x_src_fold,
-                    (long long)A.n_cols);
-    const int64_t n_rows = a->row_end - a->row_begin;
-    if (n_rows == 0 || a->n_batch == 0 || a->k_inner == 0)
-        return REMAP_OK;
-    const int64_t K = a->n_batch > INT32_MAX || a->k_inner > INT32_MAX
-                          ? INT64_MAX : a->n_batch * a->k_inner;
-    if (K > (INT64_MAX / kBlock) / n_rows)
-        return fail(REMAP_ERR_ARG,
-                    "remap_apply_sgs: %lld rows of %lld x %lld columns are "
-                    "more than one launch serves", (long long)n_rows,
-                    (long long)a->n_batch, (long long)a->k_inner);
-    if (!A.rowptr || (A.nnz > 0 && (!A.col || !A.val)) || !a->X || !a->F ||
-        !a->Y)
-        return fail(REMAP_ERR_ARG,
-                    "remap_apply_sgs: NULL rowptr, col, val, X, F or Y");
-    const int64_t total = n_rows * K;
-    if ((total + kBlock - 1) / kBlock > INT32_MAX)
-        return fail(REMAP_ERR_ARG,
-                    "remap_apply_sgs: %lld elements are more than one "
-                    "launch serves", (long long)total);
+                    "%s: x_src_fold = %lld with a negative f_outer_stride",
+                    kName, (long long)a->x_src_fold);
     SgsParams p;
-    p.rowptr = A.rowptr;
-    p.col = A.col;
-    p.val = A.val;
+    bool empty;
+    const int checked = check_args(kName, *a, p, empty);
+    if (checked != REMAP_OK || empty)
+        return checked;
+    if (!p.rowptr || (a->A.nnz > 0 && (!p.col || !a->A.val)) || !a->X ||
+        !a->F || !a->Y)
+        return fail(REMAP_ERR_ARG, "%s: NULL rowptr, col, val, X, F or Y",
+                    kName);
+    p.val = a->A.val;
     p.X = a->X;
     p.F = a->F;
     p.Y = a->Y;
-    p.row_begin = a->row_begin;
-    p.n_rows = n_rows;
-    p.K = K;
-    p.k_inner = a->k_inner;
-    p.ldx = a->x_row_stride;
-    p.bsx = a->x_batch_stride;
-    p.ldy = a->y_row_stride;
-    p.bsy = a->y_batch_stride;
     p.ldf = a->f_row_stride;
     p.bsf = a->f_batch_stride;
     p.isf = a->f_inner_stride;
-    p.src_outer = a->x_outer_stride;
     p.f_outer = a->f_outer_stride;
-    p.src_fold = static_cast<uint32_t>(a->x_src_fold);
-    p.total = total;
     p.thr = a->threshold;
     // several batches whose rows lie closer than the batches: the lanes run
     // over the rows and columns of one batch

@@ -15,6 +15,7 @@ PyTorch is used for device memory, streams and (in ``parallel.py``)
 fallback: without the library or without a GPU every compute entry point
 raises.
 """
+import collections
 import contextlib
 import ctypes
 import numbers
@@ -844,14 +845,7 @@ class RemapPlan:
         if hit is not None and hit[0] == self._sched_version:
             return _ApplyArgs.from_buffer_copy(hit[1])
         args = _ApplyArgs()
-        args.A.n_rows = self.n_b
-        args.A.n_cols = self.n_a
-        args.A.nnz = self.nnz
-        args.A.rowptr = self.rowptr.data_ptr()
-        args.A.col = self.col.data_ptr()
-        args.A.val = self.val.data_ptr()
-        args.A.max_row_nnz = self.max_row_nnz
-        args.A.csr_pad = self.csr_pad
+        args.A = self._csr_struct()
         order = self.row_order
         if whole and cell:
             q = self._runs if cell == 'runs' else \
@@ -1803,6 +1797,78 @@ class RemapPlan:
 # launches
 # ---------------------------------------------------------------------------
 
+def _float_dtype(torch, name, t):
+    if t.dtype == torch.float64:
+        return DTYPE_F64
+    if t.dtype == torch.float32:
+        return DTYPE_F32
+    raise TypeError(f'{name} must be float64 or float32, not {t.dtype}')
+
+
+def _one_device(plan, what):
+    if hasattr(plan, 'shards') or not isinstance(plan, RemapPlan):
+        raise NotImplementedError(
+            f'{what} serves one device: not with a multi-device or '
+            f'process-group plan')
+
+
+def _holds_csr(plan, arrays, why):
+    """The passes beside the apply read the plan's own CSR, never a schedule
+    (a split plan keeps the whole mapping's CSR beside its two parts)."""
+    sizes = {'rowptr': plan.n_b + 1, 'col': plan.nnz, 'val': plan.nnz}
+    for name in arrays:
+        t = getattr(plan, name)
+        if t is None or t.numel() != sizes[name]:
+            raise EngineError(f'the plan no longer holds its CSR '
+                              f'({", ".join(arrays)}): {why}')
+
+
+def _check_fold(n_a, x_src_fold, *outer_strides):
+    if x_src_fold < 0 or n_a % x_src_fold or min(outer_strides) < 0:
+        raise ValueError(f'x_src_fold {x_src_fold} does not divide '
+                         f'n_a = {n_a}')
+
+
+def _check_reach(name, t, rows, row_stride, batch_stride, inner_stride,
+                 n_batch, k_inner, fold=0, outer_stride=0):
+    """The kernels address through raw pointers: ``t`` must hold the last
+    element the strides reach.  ``fold``: two source axes, the last cell is
+    ``(rows / fold - 1, fold - 1)``."""
+    if t is None or n_batch <= 0 or k_inner <= 0 or rows <= 0:
+        return
+    last = (rows - 1) * row_stride
+    if fold:
+        _check_fold(rows, fold, outer_stride)
+        last = (rows // fold - 1) * outer_stride + (fold - 1) * row_stride
+    reach = (n_batch - 1) * batch_stride + last + \
+        (k_inner - 1) * inner_stride + 1
+    if min(row_stride, batch_stride) < 0 or reach > t.numel():
+        raise ValueError(
+            f'{name} holds {t.numel()} elements; the strides (row '
+            f'{row_stride}, batch {batch_stride}) reach {reach}')
+
+
+def _row_range(plan, row_begin, row_end):
+    end = plan.n_b if row_end is None else int(row_end)
+    row_begin = int(row_begin)
+    if not 0 <= row_begin <= end <= plan.n_b:
+        raise ValueError(f'rows [{row_begin}, {end}) are not inside '
+                         f'[0, {plan.n_b}]')
+    return row_begin, end
+
+
+def _launch(torch, plan, fn, name, args, enter=True):
+    """``fn(args, stream)`` on torch's current stream of the plan's device;
+    ``enter``: inside that device's context."""
+    stream = ctypes.c_void_p(
+        torch.cuda.current_stream(plan.device).cuda_stream)
+    if enter:
+        with torch.cuda.device(plan.device):
+            _check(fn(ctypes.byref(args), stream), name)
+    else:
+        _check(fn(ctypes.byref(args), stream), name)
+
+
 def apply_strided(plan, X, Y, *, n_batch, k_inner, x_row_stride,
                   x_batch_stride, y_row_stride, y_batch_stride, mode,
                   threshold=0.0, mask_out=None, flags=0, tune=None,
@@ -1824,36 +1890,12 @@ def apply_strided(plan, X, Y, *, n_batch, k_inner, x_row_stride,
         raise ValueError('X, Y and the plan must live on the same device')
     if Y.dtype != torch.float64:
         raise TypeError('Y must be float64')
-    if X.dtype == torch.float64:
-        x_dtype = DTYPE_F64
-    elif X.dtype == torch.float32:
-        x_dtype = DTYPE_F32
-    else:
-        raise TypeError(f'X must be float64 or float32, not {X.dtype}')
-    # the kernel addresses through raw pointers: the tensors must hold the
-    # last element the strides reach
-    for name, t, rows, rs, bs in (('X', X, plan.n_a, x_row_stride,
-                                   x_batch_stride),
-                                  ('Y', Y, plan.n_b, y_row_stride,
-                                   y_batch_stride),
-                                  ('mask_out', mask_out, plan.n_b,
-                                   y_row_stride, y_batch_stride)):
-        if t is None or n_batch <= 0 or k_inner <= 0 or rows <= 0:
-            continue
-        reach = (n_batch - 1) * bs + (rows - 1) * rs + k_inner
-        if name == 'X' and x_src_fold:
-            # two source axes: the last cell is (n_a / fold - 1, fold - 1)
-            if x_src_fold < 0 or plan.n_a % x_src_fold or \
-                    x_outer_stride < 0:
-                raise ValueError(f'x_src_fold {x_src_fold} does not divide '
-                                 f'n_a = {plan.n_a}')
-            reach = (n_batch - 1) * bs + \
-                (plan.n_a // x_src_fold - 1) * x_outer_stride + \
-                (x_src_fold - 1) * rs + k_inner
-        if min(rs, bs) < 0 or reach > t.numel():
-            raise ValueError(
-                f'{name} holds {t.numel()} elements; the strides (row {rs}, '
-                f'batch {bs}) reach {reach}')
+    x_dtype = _float_dtype(torch, 'X', X)
+    _check_reach('X', X, plan.n_a, x_row_stride, x_batch_stride, 1, n_batch,
+                 k_inner, x_src_fold, x_outer_stride)
+    for name, t in (('Y', Y), ('mask_out', mask_out)):
+        _check_reach(name, t, plan.n_b, y_row_stride, y_batch_stride, 1,
+                     n_batch, k_inner)
     if mask_out is not None and (mask_out.dtype != torch.uint8 or
                                  mask_out.device != plan.device):
         raise TypeError('mask_out must be a uint8 tensor on the plan device')
@@ -1973,15 +2015,10 @@ def apply_strided(plan, X, Y, *, n_batch, k_inner, x_row_stride,
     if tune:
         for i, v in enumerate(tune):
             args.tune[i] = int(v)
-    stream = ctypes.c_void_p(
-        torch.cuda.current_stream(plan.device).cuda_stream)
-    if torch.cuda.current_device() == plan.device.index:
-        _check(lib.remap_apply_f64(ctypes.byref(args), stream),
-               'remap_apply_f64')
-    else:
-        with torch.cuda.device(plan.device):
-            _check(lib.remap_apply_f64(ctypes.byref(args), stream),
-                   'remap_apply_f64')
+    # (this sits in front of every variable of a Dataset: the device context
+    # is entered only where the current device is another)
+    _launch(torch, plan, lib.remap_apply_f64, 'remap_apply_f64', args,
+            enter=torch.cuda.current_device() != plan.device.index)
 
 
 def check_limiter(limiter):
@@ -2011,72 +2048,29 @@ def limit_strided(plan, X, Y, *, n_batch, k_inner, x_row_stride,
     """
     torch = _torch()
     lib = load_library()
-    if hasattr(plan, 'shards') or not isinstance(plan, RemapPlan):
-        raise NotImplementedError(
-            'the limiter serves one device: not with a multi-device or '
-            'process-group plan')
+    _one_device(plan, 'the limiter')
     if X.device != plan.device or Y.device != plan.device:
         raise ValueError('X, Y and the plan must live on the same device')
     if Y.dtype != torch.float64:
         raise TypeError('Y must be float64')
-    if X.dtype == torch.float64:
-        x_dtype = DTYPE_F64
-    elif X.dtype == torch.float32:
-        x_dtype = DTYPE_F32
-    else:
-        raise TypeError(f'X must be float64 or float32, not {X.dtype}')
+    x_dtype = _float_dtype(torch, 'X', X)
     for name, t in (('lo', lo), ('hi', hi)):
         if t is not None and (t.dtype != torch.float64 or
                               t.device != plan.device):
             raise TypeError(f'{name} must be a float64 tensor on the plan '
                             f'device')
-    end = plan.n_b if row_end is None else int(row_end)
-    row_begin = int(row_begin)
-    if not 0 <= row_begin <= end <= plan.n_b:
-        raise ValueError(f'rows [{row_begin}, {end}) are not inside '
-                         f'[0, {plan.n_b}]')
-    # the kernel addresses through raw pointers: the tensors must hold the
-    # last element the strides reach (the checks of apply_strided)
-    for name, t, rows, rs, bs in (('X', X, plan.n_a, x_row_stride,
-                                   x_batch_stride),
-                                  ('Y', Y, plan.n_b, y_row_stride,
-                                   y_batch_stride),
-                                  ('lo', lo, plan.n_b, y_row_stride,
-                                   y_batch_stride),
-                                  ('hi', hi, plan.n_b, y_row_stride,
-                                   y_batch_stride)):
-        if t is None or n_batch <= 0 or k_inner <= 0 or rows <= 0:
-            continue
-        reach = (n_batch - 1) * bs + (rows - 1) * rs + k_inner
-        if name == 'X' and x_src_fold:
-            if x_src_fold < 0 or plan.n_a % x_src_fold or \
-                    x_outer_stride < 0:
-                raise ValueError(f'x_src_fold {x_src_fold} does not divide '
-                                 f'n_a = {plan.n_a}')
-            reach = (n_batch - 1) * bs + \
-                (plan.n_a // x_src_fold - 1) * x_outer_stride + \
-                (x_src_fold - 1) * rs + k_inner
-        if min(rs, bs) < 0 or reach > t.numel():
-            raise ValueError(
-                f'{name} holds {t.numel()} elements; the strides (row {rs}, '
-                f'batch {bs}) reach {reach}')
+    row_begin, end = _row_range(plan, row_begin, row_end)
+    _check_reach('X', X, plan.n_a, x_row_stride, x_batch_stride, 1, n_batch,
+                 k_inner, x_src_fold, x_outer_stride)
+    for name, t in (('Y', Y), ('lo', lo), ('hi', hi)):
+        _check_reach(name, t, plan.n_b, y_row_stride, y_batch_stride, 1,
+                     n_batch, k_inner)
     if n_batch < 0 or k_inner < 0:
         raise ValueError('n_batch and k_inner must not be negative')
-    # (a split plan keeps the whole mapping's CSR beside its two parts)
-    if plan.rowptr is None or plan.col is None or \
-            plan.rowptr.numel() != plan.n_b + 1 or \
-            plan.col.numel() != plan.nnz:
-        raise EngineError('the plan no longer holds its CSR (rowptr, col): '
-                          'the limiter gathers a row\'s sources from it')
+    _holds_csr(plan, ('rowptr', 'col'),
+               "the limiter gathers a row's sources from it")
     args = _LimitArgs()
-    args.A.n_rows = plan.n_b
-    args.A.n_cols = plan.n_a
-    args.A.nnz = plan.nnz
-    args.A.rowptr = plan.rowptr.data_ptr()
-    args.A.col = plan.col.data_ptr()
-    args.A.val = plan.val.data_ptr()
-    args.A.max_row_nnz = plan.max_row_nnz
-    args.A.csr_pad = plan.csr_pad
+    args.A = plan._csr_struct()
     args.row_begin = row_begin
     args.row_end = end
     args.X = X.data_ptr()
@@ -2092,11 +2086,7 @@ def limit_strided(plan, X, Y, *, n_batch, k_inner, x_row_stride,
     args.k_inner = int(k_inner)
     args.lo = lo.data_ptr() if lo is not None else None
     args.hi = hi.data_ptr() if hi is not None else None
-    stream = ctypes.c_void_p(
-        torch.cuda.current_stream(plan.device).cuda_stream)
-    with torch.cuda.device(plan.device):
-        _check(lib.remap_limit_rows(ctypes.byref(args), stream),
-               'remap_limit_rows')
+    _launch(torch, plan, lib.remap_limit_rows, 'remap_limit_rows', args)
 
 
 def _caas_mass(Yv, row_weight):
@@ -2168,10 +2158,7 @@ def _limiter_arguments(plan, limiter, row_weight):
     check_limiter(limiter)
     if limiter is None:
         return None
-    if hasattr(plan, 'shards') or not isinstance(plan, RemapPlan):
-        raise NotImplementedError(
-            'the limiter serves one device: not with a multi-device or '
-            'process-group plan')
+    _one_device(plan, 'the limiter')
     if limiter != 'caas':
         return None
     if row_weight is None:
@@ -2184,14 +2171,6 @@ def _limiter_arguments(plan, limiter, row_weight):
         raise ValueError(f'row_weight of shape {tuple(w.shape)}: expected '
                          f'({plan.n_b},)')
     return w
-
-
-def _float_dtype(torch, name, t):
-    if t.dtype == torch.float64:
-        return DTYPE_F64
-    if t.dtype == torch.float32:
-        return DTYPE_F32
-    raise TypeError(f'{name} must be float64 or float32, not {t.dtype}')
 
 
 def sgs_strided(plan, X, F, Y, *, n_batch, k_inner, x_row_stride,
@@ -2215,10 +2194,7 @@ def sgs_strided(plan, X, F, Y, *, n_batch, k_inner, x_row_stride,
     """
     torch = _torch()
     lib = load_library()
-    if hasattr(plan, 'shards') or not isinstance(plan, RemapPlan):
-        raise NotImplementedError(
-            'sub-gridscale weighting serves one device: not with a '
-            'multi-device or process-group plan')
+    _one_device(plan, 'sub-gridscale weighting')
     for name, t in (('X', X), ('F', F), ('Y', Y)):
         if t.device != plan.device:
             raise ValueError('X, F, Y and the plan must live on the same '
@@ -2229,55 +2205,25 @@ def sgs_strided(plan, X, F, Y, *, n_batch, k_inner, x_row_stride,
         raise TypeError('Y must be float64')
     x_dtype = _float_dtype(torch, 'X', X)
     f_dtype = _float_dtype(torch, 'F', F)
-    end = plan.n_b if row_end is None else int(row_end)
-    row_begin = int(row_begin)
-    if not 0 <= row_begin <= end <= plan.n_b:
-        raise ValueError(f'rows [{row_begin}, {end}) are not inside '
-                         f'[0, {plan.n_b}]')
+    row_begin, end = _row_range(plan, row_begin, row_end)
     if n_batch < 0 or k_inner < 0:
         raise ValueError('n_batch and k_inner must not be negative')
     if f_inner_stride not in (0, 1):
         raise ValueError(f'f_inner_stride {f_inner_stride}: expected 0 '
                          f'(broadcast) or 1')
-    if x_src_fold and (x_src_fold < 0 or plan.n_a % x_src_fold or
-                       x_outer_stride < 0 or f_outer_stride < 0):
-        raise ValueError(f'x_src_fold {x_src_fold} does not divide '
-                         f'n_a = {plan.n_a}')
-    # the kernel addresses through raw pointers: the tensors must hold the
-    # last element the strides reach (the checks of apply_strided)
-    for name, t, rows, rs, bs, inner, outer in (
-            ('X', X, plan.n_a, x_row_stride, x_batch_stride, 1,
-             x_outer_stride),
-            ('F', F, plan.n_a, f_row_stride, f_batch_stride, f_inner_stride,
-             f_outer_stride),
-            ('Y', Y, plan.n_b, y_row_stride, y_batch_stride, 1, 0)):
-        if n_batch <= 0 or k_inner <= 0 or rows <= 0:
-            continue
-        reach = (n_batch - 1) * bs + (rows - 1) * rs + \
-            (k_inner - 1) * inner + 1
-        if name != 'Y' and x_src_fold:
-            reach = (n_batch - 1) * bs + \
-                (plan.n_a // x_src_fold - 1) * outer + \
-                (x_src_fold - 1) * rs + (k_inner - 1) * inner + 1
-        if min(rs, bs) < 0 or reach > t.numel():
-            raise ValueError(
-                f'{name} holds {t.numel()} elements; the strides (row {rs}, '
-                f'batch {bs}) reach {reach}')
-    # (a split plan keeps the whole mapping's CSR beside its two parts)
-    if plan.rowptr is None or plan.col is None or plan.val is None or \
-            plan.rowptr.numel() != plan.n_b + 1 or \
-            plan.col.numel() != plan.nnz or plan.val.numel() != plan.nnz:
-        raise EngineError('the plan no longer holds its CSR (rowptr, col, '
-                          'val): the sub-gridscale launch reads it')
+    if x_src_fold:
+        _check_fold(plan.n_a, x_src_fold, x_outer_stride, f_outer_stride)
+    _check_reach('X', X, plan.n_a, x_row_stride, x_batch_stride, 1, n_batch,
+                 k_inner, x_src_fold, x_outer_stride)
+    _check_reach('F', F, plan.n_a, f_row_stride, f_batch_stride,
+                 f_inner_stride, n_batch, k_inner, x_src_fold,
+                 f_outer_stride)
+    _check_reach('Y', Y, plan.n_b, y_row_stride, y_batch_stride, 1, n_batch,
+                 k_inner)
+    _holds_csr(plan, ('rowptr', 'col', 'val'),
+               'the sub-gridscale launch reads it')
     args = _SgsArgs()
-    args.A.n_rows = plan.n_b
-    args.A.n_cols = plan.n_a
-    args.A.nnz = plan.nnz
-    args.A.rowptr = plan.rowptr.data_ptr()
-    args.A.col = plan.col.data_ptr()
-    args.A.val = plan.val.data_ptr()
-    args.A.max_row_nnz = plan.max_row_nnz
-    args.A.csr_pad = plan.csr_pad
+    args.A = plan._csr_struct()
     args.row_begin = row_begin
     args.row_end = end
     args.X = X.data_ptr()
@@ -2298,11 +2244,7 @@ def sgs_strided(plan, X, F, Y, *, n_batch, k_inner, x_row_stride,
     args.n_batch = int(n_batch)
     args.k_inner = int(k_inner)
     args.threshold = float(threshold)
-    stream = ctypes.c_void_p(
-        torch.cuda.current_stream(plan.device).cuda_stream)
-    with torch.cuda.device(plan.device):
-        _check(lib.remap_apply_sgs(ctypes.byref(args), stream),
-               'remap_apply_sgs')
+    _launch(torch, plan, lib.remap_apply_sgs, 'remap_apply_sgs', args)
 
 
 def _prod(seq):
@@ -2367,6 +2309,114 @@ def check_field_extents(n_a, n_b, n_b_global, dst_grid_dims, shape,
     return axes, dst_shape
 
 
+#: How a field is laid out for its launches (:func:`field_layout`).
+#:   route      'direct' | 'fold' | 'permute'
+#:   order      None: X is the contiguous field; else X is the field permuted
+#:              by ``order`` and flattened to ``(n_a, K)``
+#:   y_shape    shape of the float64 buffer the launches write
+#:   out_shape  shape of the caller's result
+#:   n_launch   launches; launch ``li`` takes row ``li`` of X and of the
+#:              buffer, each reshaped to ``(n_launch, -1)``
+#:   strides    the keywords every launch has in common: ``n_batch``,
+#:              ``k_inner``, the X and Y strides and, on the 'fold' route,
+#:              ``x_src_fold`` and ``x_outer_stride``
+#:   groups     the field's other axes as ``(lead, between, tail)``: the
+#:              launches, the batches and the inner index on the 'fold'
+#:              route; the batches, none and the inner index on 'direct';
+#:              on 'permute' all of them are ``tail``
+#:   back       None: the buffer is the result; else ``(shape, unpermute)``:
+#:              the buffer reshaped and permuted is
+FieldLayout = collections.namedtuple(
+    'FieldLayout', 'route order y_shape out_shape n_launch strides groups '
+                   'back')
+
+
+def field_layout(plan, shape, remap_axes, dst_shape, fold=True):
+    """
+    The one statement of how a field of ``shape`` whose (non-negative) axes
+    ``remap_axes`` hold the source grid is addressed by the launches, and how
+    their buffer becomes the result with ``dst_shape`` at ``min(remap_axes)``
+    (``remap_numpy.py:254-256`` and ``:280-295``).  Pure shape arithmetic.
+
+    'direct'   source axes adjacent: addressed in place, strides do the
+               permute and the flatten;
+    'fold'     two source axes with other dims BETWEEN them -- (lat, M, lon[,
+               T]) -- in place too: the dims between are the batches of the
+               launch, a source cell is addressed through two strides
+               (``x_src_fold``), one launch per index of the dims in front
+               (``fold=False``: not taken);
+    'permute'  general axis order: one device transpose to ``(n_a, K)``, the
+               kernel, one transpose back.
+    """
+    # (the in-place route first, with nothing worked out that it does not
+    # need: it sits in front of every variable of a Dataset)
+    ndim = len(shape)
+    lead = min(remap_axes)
+    end = lead + len(remap_axes)
+    if remap_axes == list(range(lead, end)):    # (in_place_addressable)
+        lead_shape = [int(s) for s in shape[:lead]]
+        tail_shape = [int(s) for s in shape[end:]]
+        k_inner = _prod(tail_shape)
+        out_shape = lead_shape + dst_shape + tail_shape
+        strides = dict(n_batch=_prod(lead_shape), k_inner=k_inner,
+                       x_row_stride=k_inner,
+                       x_batch_stride=plan.n_a * k_inner,
+                       y_row_stride=k_inner,
+                       y_batch_stride=plan.n_b * k_inner)
+        groups = (range(lead), (), range(end, ndim))
+        return FieldLayout('direct', None, out_shape, out_shape, 1, strides,
+                           groups, None)
+    shape = [int(s) for s in shape]
+    extra_axes = [ax for ax in range(ndim) if ax not in remap_axes]
+    out_shape = shape[:lead] + dst_shape + \
+        [shape[ax] for ax in extra_axes if ax > lead]
+    if fold and len(remap_axes) == 2 and remap_axes[0] < remap_axes[1]:
+        a0, a1 = remap_axes
+        nx = shape[a1]
+        M = _prod(shape[a0 + 1:a1])
+        T = _prod(shape[a1 + 1:])
+        strides = dict(n_batch=M, k_inner=T, x_row_stride=T,
+                       x_batch_stride=nx * T, y_row_stride=M * T,
+                       y_batch_stride=T, x_src_fold=nx,
+                       x_outer_stride=M * nx * T)
+        groups = (range(a0), range(a0 + 1, a1), range(a1 + 1, ndim))
+        return FieldLayout('fold', None, out_shape, out_shape,
+                           _prod(shape[:a0]), strides, groups, None)
+    K = _prod(shape[ax] for ax in extra_axes)
+    strides = dict(n_batch=1, k_inner=K, x_row_stride=K, x_batch_stride=0,
+                   y_row_stride=K, y_batch_stride=0)
+    n_dst = len(dst_shape)
+    tail = list(range(n_dst, n_dst + len(extra_axes)))
+    unpermute = tail[:lead] + list(range(n_dst)) + tail[lead:]
+    back = (dst_shape + [shape[ax] for ax in extra_axes], unpermute)
+    return FieldLayout('permute', remap_axes + extra_axes, [plan.n_b, K],
+                       out_shape, 1, strides, ((), (), extra_axes), back)
+
+
+def _launch_source(plan, lay, t, k):
+    """``t`` (the field, or what is laid out like it) as the launches read
+    it: contiguous, or permuted to ``(n_a, k)``."""
+    if lay.order is None:
+        return t.contiguous()
+    return t.permute(lay.order).reshape(plan.n_a, k).contiguous()
+
+
+def _launch_rows(n, *tensors):
+    """Per launch, the contiguous piece of each tensor (None stays None)."""
+    if n == 1:
+        return [tensors]
+    rows = [None if t is None else t.reshape(n, t.numel() // n if n else 0)
+            for t in tensors]
+    return [[None if r is None else r[li] for r in rows] for li in range(n)]
+
+
+def _launch_result(lay, t):
+    if lay.back is None:
+        return t
+    shape, unpermute = lay.back
+    return t.reshape(shape).permute(unpermute).contiguous()
+
+
 def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
                  want_mask=False, flags=0, tune=None, out=None, gate=None,
                  gate_value=0, mask_out=None, limiter=None, row_weight=None):
@@ -2411,20 +2461,13 @@ def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
     remap_axes, dst_shape = check_field_extents(
         plan.n_a, plan.n_b, plan.n_b_global, dst_grid_dims, field.shape,
         remap_axes)
-    ndim = field.ndim
-    extra_axes = [ax for ax in range(ndim) if ax not in remap_axes]
     if field.dtype not in (torch.float64, torch.float32):
         # scipy upcasts everything else to float64 before the product
         field = field.to(torch.float64)
-
-    lead = min(remap_axes)
-    contiguous_block = remap_axes == list(range(lead, lead + len(remap_axes)))
-    lead_shape = [int(s) for s in field.shape[:lead]]
-    tail_shape = [int(field.shape[ax]) for ax in extra_axes if ax > lead]
-    n_batch = _prod(lead_shape)
-    k_inner = _prod(tail_shape)
-    direct = in_place_addressable(field.shape, remap_axes)
-    out_shape = lead_shape + dst_shape + tail_shape
+    lay = field_layout(plan, field.shape, remap_axes, dst_shape,
+                       fold=out is None and gate is None and mask_out is None)
+    direct = lay.route == 'direct'
+    out_shape = lay.out_shape
     if out is not None:
         # the kernel writes through out.data_ptr(): anything but a float64,
         # contiguous tensor of exactly the result's shape on the plan's
@@ -2444,102 +2487,31 @@ def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
         raise ValueError(
             f'mask_out must be a contiguous uint8 tensor of shape '
             f'{tuple(out_shape)} on {plan.device}')
-
-    if direct:
-        # strides do the permute/flatten of remap_numpy.py:254-256
-        X = field.contiguous()
-        Y = out if out is not None else torch.empty(
-            out_shape, dtype=torch.float64, device=field.device)
-        mask = None
-        if want_mask:
-            mask = mask_out if mask_out is not None else torch.empty(
-                out_shape, dtype=torch.uint8, device=field.device)
-        apply_strided(
-            plan, X, Y, n_batch=n_batch, k_inner=k_inner,
-            x_row_stride=k_inner, x_batch_stride=plan.n_a * k_inner,
-            y_row_stride=k_inner, y_batch_stride=plan.n_b * k_inner,
-            mode=mode, threshold=threshold, mask_out=mask, flags=flags,
-            tune=tune, gate=gate, gate_value=gate_value)
-        if limiter is not None:
-            _limit_after_apply(
-                plan, limiter, weight, X, Y, n_batch=n_batch,
-                k_inner=k_inner, x_row_stride=k_inner,
-                x_batch_stride=plan.n_a * k_inner, y_row_stride=k_inner,
-                y_batch_stride=plan.n_b * k_inner)
-        return (Y, mask) if want_mask else Y
-    if len(remap_axes) == 2 and remap_axes[0] < remap_axes[1] and \
-            out is None and gate is None and mask_out is None:
-        # Two source axes with other dims BETWEEN them -- (lat, M, lon[, T])
-        # -- in place too: the dims between are the batches of the launch,
-        # a source cell is addressed through two strides (x_src_fold), and
-        # the lanes-across-rows kernels do the rest; one launch per index of
-        # the dims in front.  (remap_numpy.py:254-256 transposes.)
-        a0, a1 = remap_axes
-        X = field.contiguous()
-        lead_n = _prod(X.shape[:a0])
-        ny, nx = int(X.shape[a0]), int(X.shape[a1])
-        M = _prod(X.shape[a0 + 1:a1])
-        T = _prod(X.shape[a1 + 1:])
-        between = [int(s) for s in X.shape[a0 + 1:a1]]
-        trailing = [int(s) for s in X.shape[a1 + 1:]]
-        full_shape = [int(s) for s in X.shape[:a0]] + dst_shape + \
-            between + trailing
-        Y = torch.empty(full_shape, dtype=torch.float64, device=X.device)
-        mask = torch.empty(full_shape, dtype=torch.uint8,
-                           device=X.device) if want_mask else None
-        per_x, per_y = ny * M * nx * T, _prod(dst_shape) * M * T
-        Xl = X.reshape(lead_n, per_x)
-        Yl = Y.reshape(lead_n, per_y)
-        Ml = mask.reshape(lead_n, per_y) if want_mask else None
-        for li in range(lead_n):
-            apply_strided(
-                plan, Xl[li], Yl[li], n_batch=M, k_inner=T,
-                x_row_stride=T, x_batch_stride=nx * T,
-                y_row_stride=M * T, y_batch_stride=T, mode=mode,
-                threshold=threshold,
-                mask_out=Ml[li] if want_mask else None, flags=flags,
-                tune=tune, x_src_fold=nx, x_outer_stride=M * nx * T)
-            if limiter is not None:
-                _limit_after_apply(
-                    plan, limiter, weight, Xl[li], Yl[li], n_batch=M,
-                    k_inner=T, x_row_stride=T, x_batch_stride=nx * T,
-                    y_row_stride=M * T, y_batch_stride=T, x_src_fold=nx,
-                    x_outer_stride=M * nx * T)
-        return (Y, mask) if want_mask else Y
-    if gate is not None or mask_out is not None:
+    if not direct and (gate is not None or mask_out is not None):
         raise ValueError('gated launches and caller-supplied masks need the '
                          'source axes adjacent (in-place addressing)')
 
-    # general axis order (or a very short contiguous run): one device
-    # transpose to (n_a, K), the kernel, one transpose back
-    K = _prod(field.shape[ax] for ax in extra_axes)
-    X = field.permute(remap_axes + extra_axes).reshape(plan.n_a, K)\
-        .contiguous()
-    Y = torch.empty((plan.n_b, K), dtype=torch.float64, device=field.device)
-    mask = torch.empty((plan.n_b, K), dtype=torch.uint8,
-                       device=field.device) if want_mask else None
-    apply_strided(plan, X, Y, n_batch=1, k_inner=K, x_row_stride=K,
-                  x_batch_stride=0, y_row_stride=K, y_batch_stride=0,
-                  mode=mode, threshold=threshold, mask_out=mask, flags=flags,
-                  tune=tune)
-    if limiter is not None:
-        # (before the transpose back: the kernel's (n_b, K) layout)
-        _limit_after_apply(plan, limiter, weight, X, Y, n_batch=1, k_inner=K,
-                           x_row_stride=K, x_batch_stride=0, y_row_stride=K,
-                           y_batch_stride=0)
-    extra_shape = [int(field.shape[ax]) for ax in extra_axes]
-    n_dst = len(dst_shape)
-    tail = list(range(n_dst, n_dst + len(extra_shape)))
-    unpermute = tail[:lead] + list(range(n_dst)) + tail[lead:]
-
-    def back(t):
-        t = t.reshape(dst_shape + extra_shape).permute(unpermute).contiguous()
-        return t
-    Y = back(Y)
-    if out is not None:
-        out.copy_(Y)
-        Y = out
-    return (Y, back(mask)) if want_mask else Y
+    X = _launch_source(plan, lay, field, lay.strides['k_inner'])
+    Y = out if direct and out is not None else torch.empty(
+        lay.y_shape, dtype=torch.float64, device=field.device)
+    mask = None
+    if want_mask:
+        mask = mask_out if mask_out is not None else torch.empty(
+            lay.y_shape, dtype=torch.uint8, device=field.device)
+    gated = dict(gate=gate, gate_value=gate_value) if direct else {}
+    for Xl, Yl, Ml in _launch_rows(lay.n_launch, X, Y, mask):
+        apply_strided(plan, Xl, Yl, mode=mode, threshold=threshold,
+                      mask_out=Ml, flags=flags, tune=tune, **gated,
+                      **lay.strides)
+        if limiter is not None:
+            # (on the launch's own buffer: before any transpose back)
+            _limit_after_apply(plan, limiter, weight, Xl, Yl, **lay.strides)
+    if lay.back is not None:
+        Y = _launch_result(lay, Y)
+        if out is not None:
+            out.copy_(Y)
+            Y = out
+    return (Y, _launch_result(lay, mask)) if want_mask else Y
 
 
 def _sgs_group(frac, shape, axes):
@@ -2574,10 +2546,7 @@ def remap_tensor_sgs(plan, dst_grid_dims, field, frac, remap_axes,
     One device only.
     """
     torch = _torch()
-    if hasattr(plan, 'shards') or not isinstance(plan, RemapPlan):
-        raise NotImplementedError(
-            'sub-gridscale weighting serves one device: not with a '
-            'multi-device or process-group plan')
+    _one_device(plan, 'sub-gridscale weighting')
     remap_axes, dst_shape = check_field_extents(
         plan.n_a, plan.n_b, plan.n_b_global, dst_grid_dims, field.shape,
         remap_axes)
@@ -2594,88 +2563,38 @@ def remap_tensor_sgs(plan, dst_grid_dims, field, frac, remap_axes,
                 f'frac of shape {tuple(frac.shape)} against a field of shape '
                 f'{tuple(field.shape)}: axis {ax} must have extent {want}' +
                 ('' if ax in remap_axes else ' or 1'))
-    extra_axes = [ax for ax in range(ndim) if ax not in remap_axes]
     if field.dtype not in (torch.float64, torch.float32):
         field = field.to(torch.float64)
     if frac.dtype not in (torch.float64, torch.float32):
         frac = frac.to(torch.float64)
-    lead = min(remap_axes)
-    lead_shape = [int(s) for s in field.shape[:lead]]
-    tail_shape = [int(field.shape[ax]) for ax in extra_axes if ax > lead]
-
-    if in_place_addressable(field.shape, remap_axes):
-        n_batch = _prod(lead_shape)
-        k_inner = _prod(tail_shape)
-        X = field.contiguous()
-        frac, lead_full = _sgs_group(frac, X.shape, list(range(lead)))
-        frac, tail_full = _sgs_group(
-            frac, X.shape, list(range(lead + len(remap_axes), ndim)))
-        F = frac.contiguous()
-        kf = k_inner if tail_full else 1
-        Y = torch.empty(lead_shape + dst_shape + tail_shape,
-                        dtype=torch.float64, device=X.device)
-        sgs_strided(
-            plan, X, F, Y, n_batch=n_batch, k_inner=k_inner,
-            x_row_stride=k_inner, x_batch_stride=plan.n_a * k_inner,
-            f_row_stride=kf,
-            f_batch_stride=plan.n_a * kf if lead_full else 0,
-            f_inner_stride=1 if tail_full else 0,
-            y_row_stride=k_inner, y_batch_stride=plan.n_b * k_inner,
-            threshold=threshold)
-        return Y
-    if len(remap_axes) == 2 and remap_axes[0] < remap_axes[1]:
-        # two source axes with other dims between them, as remap_tensor
-        # serves them: the dims between are the batches, a source cell is
-        # addressed through two strides, one launch per index of the dims in
-        # front
-        a0, a1 = remap_axes
-        X = field.contiguous()
-        lead_n = _prod(X.shape[:a0])
-        ny, nx = int(X.shape[a0]), int(X.shape[a1])
-        M = _prod(X.shape[a0 + 1:a1])
-        T = _prod(X.shape[a1 + 1:])
-        between = [int(s) for s in X.shape[a0 + 1:a1]]
-        trailing = [int(s) for s in X.shape[a1 + 1:]]
-        frac, lead_full = _sgs_group(frac, X.shape, list(range(a0)))
-        frac, mid_full = _sgs_group(frac, X.shape, list(range(a0 + 1, a1)))
-        frac, tail_full = _sgs_group(frac, X.shape,
-                                     list(range(a1 + 1, ndim)))
-        F = frac.contiguous()
-        Mf = M if mid_full else 1
-        Tf = T if tail_full else 1
-        Y = torch.empty([int(s) for s in X.shape[:a0]] + dst_shape +
-                        between + trailing, dtype=torch.float64,
-                        device=X.device)
-        Xl = X.reshape(lead_n, ny * M * nx * T)
-        Fl = F.reshape(lead_n if lead_full else 1, ny * Mf * nx * Tf)
-        Yl = Y.reshape(lead_n, _prod(dst_shape) * M * T)
-        for li in range(lead_n):
-            sgs_strided(
-                plan, Xl[li], Fl[li if lead_full else 0], Yl[li], n_batch=M,
-                k_inner=T, x_row_stride=T, x_batch_stride=nx * T,
-                f_row_stride=Tf, f_batch_stride=nx * Tf if mid_full else 0,
-                f_inner_stride=1 if tail_full else 0, y_row_stride=M * T,
-                y_batch_stride=T, threshold=threshold, x_src_fold=nx,
-                x_outer_stride=M * nx * T, f_outer_stride=Mf * nx * Tf)
-        return Y
-    # general axis order: one device transpose to (n_a, K), the kernel, one
-    # transpose back
-    K = _prod(field.shape[ax] for ax in extra_axes)
-    order = remap_axes + extra_axes
-    X = field.permute(order).reshape(plan.n_a, K).contiguous()
-    frac, full = _sgs_group(frac, field.shape, extra_axes)
-    Kf = K if full else 1
-    F = frac.permute(order).reshape(plan.n_a, Kf).contiguous()
-    Y = torch.empty((plan.n_b, K), dtype=torch.float64, device=field.device)
-    sgs_strided(plan, X, F, Y, n_batch=1, k_inner=K, x_row_stride=K,
-                x_batch_stride=0, f_row_stride=Kf, f_batch_stride=0,
-                f_inner_stride=1 if full else 0, y_row_stride=K,
-                y_batch_stride=0, threshold=threshold)
-    extra_shape = [int(field.shape[ax]) for ax in extra_axes]
-    n_dst = len(dst_shape)
-    tail = list(range(n_dst, n_dst + len(extra_shape)))
-    unpermute = tail[:lead] + list(range(n_dst)) + tail[lead:]
-    return Y.reshape(dst_shape + extra_shape).permute(unpermute).contiguous()
+    lay = field_layout(plan, field.shape, remap_axes, dst_shape)
+    # the fraction's strides: every group of axes is there in full, or is
+    # broadcast (a stride of 0)
+    frac, lead_full = _sgs_group(frac, field.shape, lay.groups[0])
+    frac, mid_full = _sgs_group(frac, field.shape, lay.groups[1])
+    frac, tail_full = _sgs_group(frac, field.shape, lay.groups[2])
+    k_inner = lay.strides['k_inner']
+    kf = k_inner if tail_full else 1
+    f_strides = dict(f_row_stride=kf, f_batch_stride=0,
+                     f_inner_stride=1 if tail_full else 0)
+    f_launches = 1
+    if lay.route == 'direct' and lead_full:
+        f_strides['f_batch_stride'] = plan.n_a * kf
+    elif lay.route == 'fold':
+        nx = lay.strides['x_src_fold']
+        if mid_full:
+            f_strides['f_batch_stride'] = nx * kf
+        f_strides['f_outer_stride'] = \
+            (lay.strides['n_batch'] if mid_full else 1) * nx * kf
+        f_launches = lay.n_launch if lead_full else 1
+    X = _launch_source(plan, lay, field, k_inner)
+    F = _launch_source(plan, lay, frac, kf)
+    Y = torch.empty(lay.y_shape, dtype=torch.float64, device=field.device)
+    Fs = [Fl for Fl, in _launch_rows(f_launches, F)]
+    for li, (Xl, Yl) in enumerate(_launch_rows(lay.n_launch, X, Y)):
+        sgs_strided(plan, Xl, Fs[li if f_launches > 1 else 0], Yl,
+                    threshold=threshold, **f_strides, **lay.strides)
+    return _launch_result(lay, Y)
 
 
 def scan_nan(x, flag):
@@ -2747,8 +2666,9 @@ def remap_tensor_auto_mode(plan, dst_grid_dims, field, remap_axes, threshold,
     weight = _limiter_arguments(plan, limiter, row_weight)
     # (before the scan below is enqueued: remap_tensor would say the same,
     # but only after it)
-    check_field_extents(plan.n_a, plan.n_b, plan.n_b_global, dst_grid_dims,
-                        field.shape, remap_axes)
+    axes, dst_shape = check_field_extents(
+        plan.n_a, plan.n_b, plan.n_b_global, dst_grid_dims, field.shape,
+        remap_axes)
     if hasattr(plan, 'shards'):
         if out is not None or flag is not None:
             raise ValueError("out / flag address ONE device's launch; not "
@@ -2764,17 +2684,11 @@ def remap_tensor_auto_mode(plan, dst_grid_dims, field, remap_axes, threshold,
                             flags=flags, out=out, limiter=limiter,
                             row_weight=weight)
     X = field.contiguous()
+    lay = field_layout(plan, X.shape, axes, dst_shape)    # ('direct')
 
     def limited(Y):
         if limiter is not None:
-            axes = [int(a) % X.ndim for a in remap_axes]
-            n_batch = _prod(X.shape[:min(axes)])
-            k_inner = _prod(X.shape[min(axes) + len(axes):])
-            _limit_after_apply(
-                plan, limiter, weight, X, Y, n_batch=n_batch,
-                k_inner=k_inner, x_row_stride=k_inner,
-                x_batch_stride=plan.n_a * k_inner, y_row_stride=k_inner,
-                y_batch_stride=plan.n_b * k_inner)
+            _limit_after_apply(plan, limiter, weight, X, Y, **lay.strides)
         return Y
     if flag is None and cell_mask_form(plan):
         # entry-rich mapping: the scan -- told where the cells and the
@@ -2783,10 +2697,7 @@ def remap_tensor_auto_mode(plan, dst_grid_dims, field, remap_axes, threshold,
         # (bathymetry), and the masked branch comes in the form that suits
         # (REMAP_FLAG_CELL_MASKS / REMAP_FLAG_BATCH_MASKS / neither): up to
         # four gated launches, one of which runs
-        axes = [int(a) % X.ndim for a in remap_axes]
-        lead = min(axes)
-        n_batch = _prod(X.shape[:lead])
-        k_inner = _prod(X.shape[lead + len(axes):])
+        n_batch, k_inner = lay.strides['n_batch'], lay.strides['k_inner']
         hints = FLAG_CELL_MASKS | FLAG_BATCH_MASKS
         flags &= ~hints
         kinds = torch.zeros(4, dtype=torch.int32, device=field.device)
