@@ -1875,6 +1875,83 @@ typedef struct remap_sgs_args {
 REMAP_API int remap_apply_sgs(const struct remap_sgs_args *args,
                               void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Vector fields (csrc/remap_vector.hip; DESIGN.md section 22;
+ * pyremap_amd.vector is the same statement in numpy).
+ *
+ * The zonal and meridional components of a velocity, a wind stress or an ice
+ * drift are no scalars: the east and north directions of the source cells of
+ * one row's stencil differ from those at the destination point, near a pole
+ * by tens of degrees.  This launch rotates every source vector to Cartesian
+ * (x, y, z), sums the three components with the row's weights and projects
+ * the sum on the destination cell's east and north, in one pass: U and V are
+ * read once each, YU and YV written once each.
+ *
+ * Inputs: two source fields U (eastward) and V (northward) of one shape,
+ * dtype and layout, a source basis BA (n_a, 5) fp64 with rows
+ * (ex, ey, nx, ny, nz) and a destination basis BB (n_b, 5) fp64 of the same
+ * kind, with
+ *   ex = -sin(lon), ey = cos(lon),
+ *   nx = -sin(lat) cos(lon), ny = -sin(lat) sin(lon), nz = cos(lat)
+ * (the z-component of east is 0).  The bases are made on the host from the
+ * centres in the mapping file: device trigonometry never enters the bits.
+ *
+ * For destination element (i, b, k) the entries j of row i are walked in CSR
+ * order.  Four float64 accumulators start at +0.0.
+ *
+ *   u = (double) U[cell(col_j), b, k];  v = (double) V[cell(col_j), b, k]
+ *   the entry counts iff neither is a NaN; then, with the basis row of cell col_j:
+ *     px = u*ex + v*nx;   py = u*ey + v*ny;   pz = v*nz      (each product rounded, then the sum)
+ *     cx += S_j*px;  cy += S_j*py;  cz += S_j*pz;  valid += S_j
+ *   with the basis row (Ex, Ey, Nx, Ny, Nz) of destination cell i:
+ *     tu = cx*Ex + cy*Ey;      tv = (cx*Nx + cy*Ny) + cz*Nz
+ *     valid > threshold:  yu = tu / valid,  yv = tv / valid
+ *     otherwise:          both NaN
+ *
+ * No FMA contraction; an entry that does not count is skipped, not added as
+ * a zero.  Every NaN written is the quiet NaN 0x7ff8000000000000, also where
+ * a quotient is itself a NaN.  This is the reference's masked branch
+ * (remap_numpy.py:262-266) with the mask the union of the two components'.
+ * With every basis row (1, 0, 0, 1, 0) and finite fields YU and YV are byte
+ * for byte REMAP_MODE_MASKED of U and of V under that union.
+ *
+ * U and V are addressed as X is in remap_sgs_args, with ONE dtype and one
+ * set of strides (x_src_fold included); YU and YV like Y, with one set of
+ * strides.  BA and BB are dense, row stride 5.
+ *
+ * Elements of rows outside [row_begin, row_end) are not written.
+ * Asynchronous on `stream`; nothing is allocated, freed or synchronised.
+ * REMAP_ERR_ARG: a NULL array that is needed, a negative stride or size, a
+ * row range outside [0, A.n_rows], an x_dtype that is no REMAP_DTYPE_*, an
+ * x_src_fold that does not divide A.n_cols, more elements than one launch
+ * serves.
+ * ---------------------------------------------------------------------------
+ */
+typedef struct remap_vector_args {
+    remap_csr A;            /* rowptr, col and val are all read              */
+    int64_t row_begin;      /* rows [row_begin, row_end) of A are computed;  */
+    int64_t row_end;        /* YU, YV and BB are indexed by row              */
+    const void *U;          /* (device) eastward source component            */
+    const void *V;          /* (device) northward source component           */
+    int32_t x_dtype;        /* REMAP_DTYPE_*, of U and of V                  */
+    int64_t x_row_stride;   /* of U and of V                                 */
+    int64_t x_batch_stride;
+    int64_t x_src_fold;     /* as in remap_apply_args (0: one stride)        */
+    int64_t x_outer_stride;
+    const double *BA;       /* (device) (A.n_cols, 5) source basis           */
+    const double *BB;       /* (device) (A.n_rows, 5) destination basis      */
+    double *YU;             /* (device) eastward destination component       */
+    double *YV;             /* (device) northward destination component      */
+    int64_t y_row_stride;   /* of YU and of YV                               */
+    int64_t y_batch_stride;
+    int64_t n_batch;
+    int64_t k_inner;
+    double threshold;       /* of `valid`, as REMAP_MODE_MASKED has it       */
+} remap_vector_args;
+
+REMAP_API int remap_apply_vector(const struct remap_vector_args *args,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 // rowpass.h -- what the passes that walk the rows of the plan's CSR beside
-// the SpMM apply share (remap_limit.hip, remap_sgs.hip): the checks of their
-// argument structs, the addressing of a source cell, the packed loads and
-// stores, and the work list of the rowwave form.  A pass comes in two forms:
+// the SpMM apply share (remap_limit.hip, remap_sgs.hip, remap_vector.hip):
+// the checks of their argument structs, the addressing of a source cell, the
+// packed loads and stores, and the work list of the rowwave form.  A pass
+// comes in two forms:
 //   rowlane  one lane per (row, column), for runs shorter than a wave;
 //   rowwave  one wave per (row, chunk of kWave * VEC contiguous columns),
 //            lanes across the columns, for runs of >= kWave columns.  The
@@ -34,9 +35,9 @@ namespace rowpass {
 // but it moves them to the front of the kernel arguments, and the scalar
 // registers the kernels take follow that layout.)
 
-// The checks remap_limit_args and remap_sgs_args share, under the entry
-// point's name `fn`; fills `p`.  `empty`: the arguments are fine and there is
-// nothing to do.
+// The checks remap_limit_args, remap_sgs_args and remap_vector_args share,
+// under the entry point's name `fn`; fills `p`.  `empty`: the arguments are
+// fine and there is nothing to do.
 template <typename Args, typename P>
 int check_args(const char *fn, const Args &a, P &p, bool &empty)
 {

@@ -98,7 +98,7 @@ EXPORTS = (
     'remap_conserve2nd_sizes', 'remap_conserve2nd_assemble',
     'remap_node_rings_workspace', 'remap_node_rings', 'remap_patch_fits',
     'remap_patch_sizes_workspace', 'remap_patch_sizes', 'remap_patch_rows',
-    'remap_limit_rows', 'remap_apply_sgs',
+    'remap_limit_rows', 'remap_apply_sgs', 'remap_apply_vector',
 )
 
 #: what ``limiter=`` accepts (remap_tensor, Remapper.limiter)
@@ -211,6 +211,30 @@ class _SgsArgs(ctypes.Structure):       # struct remap_sgs_args
         ('f_inner_stride', ctypes.c_int64),
         ('f_outer_stride', ctypes.c_int64),
         ('Y', ctypes.c_void_p),
+        ('y_row_stride', ctypes.c_int64),
+        ('y_batch_stride', ctypes.c_int64),
+        ('n_batch', ctypes.c_int64),
+        ('k_inner', ctypes.c_int64),
+        ('threshold', ctypes.c_double),
+    ]
+
+
+class _VectorArgs(ctypes.Structure):    # struct remap_vector_args
+    _fields_ = [
+        ('A', _CSR),
+        ('row_begin', ctypes.c_int64),
+        ('row_end', ctypes.c_int64),
+        ('U', ctypes.c_void_p),
+        ('V', ctypes.c_void_p),
+        ('x_dtype', ctypes.c_int32),
+        ('x_row_stride', ctypes.c_int64),
+        ('x_batch_stride', ctypes.c_int64),
+        ('x_src_fold', ctypes.c_int64),
+        ('x_outer_stride', ctypes.c_int64),
+        ('BA', ctypes.c_void_p),
+        ('BB', ctypes.c_void_p),
+        ('YU', ctypes.c_void_p),
+        ('YV', ctypes.c_void_p),
         ('y_row_stride', ctypes.c_int64),
         ('y_batch_stride', ctypes.c_int64),
         ('n_batch', ctypes.c_int64),
@@ -679,6 +703,9 @@ def load_library():
     lib.remap_apply_sgs.restype = ctypes.c_int
     lib.remap_apply_sgs.argtypes = [ctypes.POINTER(_SgsArgs),
                                     ctypes.c_void_p]
+    lib.remap_apply_vector.restype = ctypes.c_int
+    lib.remap_apply_vector.argtypes = [ctypes.POINTER(_VectorArgs),
+                                       ctypes.c_void_p]
     if lib.remap_abi_version() != ABI_VERSION:
         raise EngineError(
             f'{path} has ABI {lib.remap_abi_version()}, expected '
@@ -2247,6 +2274,90 @@ def sgs_strided(plan, X, F, Y, *, n_batch, k_inner, x_row_stride,
     _launch(torch, plan, lib.remap_apply_sgs, 'remap_apply_sgs', args)
 
 
+def _check_basis(torch, plan, name, B, rows):
+    """A basis of the vector launch: a contiguous float64 ``(rows, 5)``
+    tensor on the plan's device."""
+    if B.device != plan.device:
+        raise ValueError('U, V, BA, BB, YU, YV and the plan must live on '
+                         'the same device')
+    if B.dtype != torch.float64:
+        raise TypeError(f'{name} must be float64')
+    if tuple(B.shape) != (rows, 5) or not B.is_contiguous():
+        raise ValueError(f'{name} of shape {tuple(B.shape)}: expected a '
+                         f'contiguous ({rows}, 5)')
+
+
+def vector_strided(plan, U, V, BA, BB, YU, YV, *, n_batch, k_inner,
+                   x_row_stride, x_batch_stride, y_row_stride,
+                   y_batch_stride, threshold, row_begin=0, row_end=None,
+                   x_src_fold=0, x_outer_stride=0):
+    """
+    One asynchronous ``remap_apply_vector`` launch on torch's current stream:
+    the eastward and northward components ``U`` and ``V`` are rotated to
+    Cartesian with the source basis ``BA (n_a, 5)``, summed with the rows'
+    weights and projected on the destination basis ``BB (n_b, 5)`` into rows
+    ``[row_begin, row_end)`` of ``YU`` and ``YV`` (:mod:`pyremap_amd.vector`
+    has the semantics; strides in elements).  ``U`` and ``V`` share one
+    dtype and one set of strides, addressed as :func:`apply_strided`
+    addresses ``X``; ``YU`` and ``YV`` share the strides of ``Y``.
+
+    The launch reads the plan's own CSR (``rowptr``, ``col``, ``val``), never
+    a schedule: a plan applied as short and long rows (``plan._split``) is
+    served as the one matrix it is.
+    """
+    torch = _torch()
+    lib = load_library()
+    _one_device(plan, 'the vector remap')
+    for name, t in (('U', U), ('V', V), ('YU', YU), ('YV', YV)):
+        if t.device != plan.device:
+            raise ValueError('U, V, BA, BB, YU, YV and the plan must live '
+                             'on the same device')
+        if not t.is_contiguous():
+            raise ValueError(f'{name} must be contiguous')
+    if YU.dtype != torch.float64 or YV.dtype != torch.float64:
+        raise TypeError('YU and YV must be float64')
+    x_dtype = _float_dtype(torch, 'U', U)
+    if V.dtype != U.dtype:
+        raise TypeError(f'U and V must have one dtype, not {U.dtype} and '
+                        f'{V.dtype}')
+    _check_basis(torch, plan, 'BA', BA, plan.n_a)
+    _check_basis(torch, plan, 'BB', BB, plan.n_b)
+    row_begin, end = _row_range(plan, row_begin, row_end)
+    if n_batch < 0 or k_inner < 0:
+        raise ValueError('n_batch and k_inner must not be negative')
+    if x_src_fold:
+        _check_fold(plan.n_a, x_src_fold, x_outer_stride)
+    for name, t in (('U', U), ('V', V)):
+        _check_reach(name, t, plan.n_a, x_row_stride, x_batch_stride, 1,
+                     n_batch, k_inner, x_src_fold, x_outer_stride)
+    for name, t in (('YU', YU), ('YV', YV)):
+        _check_reach(name, t, plan.n_b, y_row_stride, y_batch_stride, 1,
+                     n_batch, k_inner)
+    _holds_csr(plan, ('rowptr', 'col', 'val'),
+               'the vector launch reads it')
+    args = _VectorArgs()
+    args.A = plan._csr_struct()
+    args.row_begin = row_begin
+    args.row_end = end
+    args.U = U.data_ptr()
+    args.V = V.data_ptr()
+    args.x_dtype = x_dtype
+    args.x_row_stride = int(x_row_stride)
+    args.x_batch_stride = int(x_batch_stride)
+    args.x_src_fold = int(x_src_fold)
+    args.x_outer_stride = int(x_outer_stride)
+    args.BA = BA.data_ptr()
+    args.BB = BB.data_ptr()
+    args.YU = YU.data_ptr()
+    args.YV = YV.data_ptr()
+    args.y_row_stride = int(y_row_stride)
+    args.y_batch_stride = int(y_batch_stride)
+    args.n_batch = int(n_batch)
+    args.k_inner = int(k_inner)
+    args.threshold = float(threshold)
+    _launch(torch, plan, lib.remap_apply_vector, 'remap_apply_vector', args)
+
+
 def _prod(seq):
     out = 1
     for s in seq:
@@ -2595,6 +2706,45 @@ def remap_tensor_sgs(plan, dst_grid_dims, field, frac, remap_axes,
         sgs_strided(plan, Xl, Fs[li if f_launches > 1 else 0], Yl,
                     threshold=threshold, **f_strides, **lay.strides)
     return _launch_result(lay, Y)
+
+
+def remap_tensor_vector(plan, dst_grid_dims, u, v, basis_a, basis_b,
+                        remap_axes, threshold=0.0):
+    """
+    :func:`remap_tensor` for the eastward and northward components ``u`` and
+    ``v`` of a vector field (:mod:`pyremap_amd.vector`): every source vector
+    is rotated to Cartesian with ``basis_a (n_a, 5)``, the rows' weighted sums
+    are projected on ``basis_b (n_b, 5)``, NaN in either component is
+    skipped, all in ONE launch per :func:`field_layout` launch
+    (``remap_apply_vector``).  Returns ``(yu, yv)``, each with the result
+    shape and axis order of :func:`remap_tensor`, NaN where ``valid <=
+    threshold``.  ``u`` and ``v`` have one shape, dtype and device; nothing
+    is copied where a field is addressable in place.  One device only.
+    """
+    torch = _torch()
+    _one_device(plan, 'the vector remap')
+    if tuple(u.shape) != tuple(v.shape) or u.dtype != v.dtype:
+        raise ValueError(
+            f'u of shape {tuple(u.shape)} and dtype {u.dtype}, v of shape '
+            f'{tuple(v.shape)} and dtype {v.dtype}: expected one shape and '
+            f'one dtype')
+    if u.device != v.device:
+        raise ValueError('u and v must live on the same device')
+    remap_axes, dst_shape = check_field_extents(
+        plan.n_a, plan.n_b, plan.n_b_global, dst_grid_dims, u.shape,
+        remap_axes)
+    if u.dtype not in (torch.float64, torch.float32):
+        u, v = u.to(torch.float64), v.to(torch.float64)
+    lay = field_layout(plan, u.shape, remap_axes, dst_shape)
+    k_inner = lay.strides['k_inner']
+    U = _launch_source(plan, lay, u, k_inner)
+    V = _launch_source(plan, lay, v, k_inner)
+    YU = torch.empty(lay.y_shape, dtype=torch.float64, device=u.device)
+    YV = torch.empty(lay.y_shape, dtype=torch.float64, device=u.device)
+    for Ul, Vl, YUl, YVl in _launch_rows(lay.n_launch, U, V, YU, YV):
+        vector_strided(plan, Ul, Vl, basis_a, basis_b, YUl, YVl,
+                       threshold=threshold, **lay.strides)
+    return _launch_result(lay, YU), _launch_result(lay, YV)
 
 
 def scan_nan(x, flag):

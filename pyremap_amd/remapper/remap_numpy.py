@@ -23,7 +23,7 @@ import sys
 
 import numpy as np
 
-from pyremap_amd import engine, host_path, xr_lite
+from pyremap_amd import engine, host_path, vector, xr_lite
 from pyremap_amd.io.mapfile import read_mapping
 
 try:  # real xarray is honoured when present; it is optional
@@ -69,6 +69,26 @@ class _MapInfo:
         #: row weights of the 'caas' limiter
         self.area_b = getattr(mapping, 'area_b', None)
         self._row_weight = {}
+        #: cell centres in degrees (None: the file has none); the east /
+        #: north bases of the vector remap are made from them
+        for name in CENTRES:
+            setattr(self, name, getattr(mapping, name, None))
+        self._bases = {}
+
+    def bases(self, plan):
+        """``(BA, BB)`` on ``plan``'s device: the ``(n, 5)`` east / north
+        bases of the source and destination cells (``vector.basis`` of the
+        file's centres, made on the host), uploaded once per device."""
+        _require_centres(self)
+        key = str(plan.device)
+        if key not in self._bases:
+            torch = engine.require_gpu()
+            self._bases[key] = tuple(
+                torch.from_numpy(vector.basis(
+                    np.deg2rad(getattr(self, 'yc_' + side)),
+                    np.deg2rad(getattr(self, 'xc_' + side)))).to(plan.device)
+                for side in 'ab')
+        return self._bases[key]
 
     def row_weight(self, plan):
         """``area_b * frac_b`` on ``plan``'s device (the 'caas' limiter's
@@ -88,6 +108,18 @@ def _require_area_b(info):
         raise ValueError(
             "limiter 'caas' restores the area_b * frac_b integral, but the "
             "mapping file has no variable 'area_b'")
+
+
+#: the cell centres a vector remap takes its bases from
+CENTRES = ('xc_a', 'yc_a', 'xc_b', 'yc_b')
+
+
+def _require_centres(info):
+    if any(getattr(info, name, None) is None for name in CENTRES):
+        raise ValueError(
+            'a vector remap takes the east and north directions from the '
+            "cell centres, but the mapping file lacks one of the variables "
+            "'xc_a', 'yc_a', 'xc_b', 'yc_b'")
 
 
 def _check_limiter(remapper, limiter=None):
@@ -192,6 +224,124 @@ def _sgs_fraction(remapper, ds):
     return _SgsFraction(name, ds[name], remapper.src_descriptor.dims)
 
 
+def _check_vector_alone(remapper):
+    """What the vector remap does not go together with."""
+    if getattr(remapper, 'limiter', None) is not None:
+        raise NotImplementedError(
+            'a vector remap together with a limiter is not served: the '
+            'bounds of a component are no bounds of the rotated vector')
+    if getattr(remapper, 'sgs_frac', None) is not None:
+        raise NotImplementedError(
+            'a vector remap together with sgs_frac is not served')
+    if getattr(remapper, '_process_group', None) is not None or \
+            len(getattr(remapper, 'devices', None) or ()) > 1:
+        raise NotImplementedError(
+            'the vector remap serves one device: not with devices=[...] or '
+            'a process group')
+
+
+def _check_vector_pairs(remapper):
+    """The Remapper's ``vector_pairs`` as a list of ``(u_name, v_name)``
+    tuples (None without any), and what it does not go together with."""
+    pairs = getattr(remapper, 'vector_pairs', None)
+    if pairs is None:
+        return None
+    if isinstance(pairs, (str, bytes)):
+        raise TypeError(f'vector_pairs must be None or a list of (u_name, '
+                        f'v_name) pairs, not {pairs!r}')
+    pairs = [tuple(pair) if not isinstance(pair, (str, bytes)) else pair
+             for pair in pairs]
+    seen = set()
+    for pair in pairs:
+        if not isinstance(pair, tuple) or len(pair) != 2 or \
+                not all(isinstance(name, str) for name in pair):
+            raise TypeError(f'vector_pairs must be None or a list of '
+                            f'(u_name, v_name) pairs, not {pair!r}')
+        for name in pair:
+            if name in seen:
+                raise ValueError(f'the variable {name!r} stands in '
+                                 f'vector_pairs twice')
+            seen.add(name)
+    if not pairs:
+        return None
+    _check_vector_alone(remapper)
+    return pairs
+
+
+class _VectorPairs:
+    """The vector pairs of one ``remap_numpy`` / ``ncremap`` call
+    (``Remapper.vector_pairs``): the two members of a pair are remapped
+    together, in one launch, when the first of them is asked for; the
+    partner's result waits on the device until it is asked for."""
+
+    def __init__(self, pairs, ds):
+        self.ds = ds
+        self.pair_of = {}
+        for pair in pairs:
+            for name in pair:
+                self.pair_of[name] = pair
+        self._held = {}
+
+    def __contains__(self, name):
+        return name in self.pair_of
+
+    def start(self, da, remapper, remap_axes, threshold):
+        """Enqueue (or pick up) the remap of member ``da``; returns the
+        ``host_path.OnDevice`` that hands its result down."""
+        held = self._held.pop(da.name, None)
+        if held is not None:
+            return held
+        torch = engine.require_gpu()
+        plan = remapper._matrix
+        u_name, v_name = self.pair_of[da.name]
+        BA, BB = remapper._ds_map.bases(plan)
+        fields = [torch.from_numpy(host_path._as_uploadable(
+            self.ds[name].values)).to(plan.device)
+            for name in (u_name, v_name)]
+        if fields[0].dtype != fields[1].dtype:
+            fields = [f.to(torch.float64) for f in fields]
+        yu, yv = engine.remap_tensor_vector(
+            plan, remapper._ds_map.dst_grid_dims, fields[0], fields[1], BA,
+            BB, remap_axes, threshold=0.0 if threshold is None else threshold)
+        # (the downloads wait until the results are asked for)
+        pending = {u_name: host_path.OnDevice(yu, tuple(yu.shape)),
+                   v_name: host_path.OnDevice(yv, tuple(yv.shape))}
+        partner = v_name if da.name == u_name else u_name
+        self._held[partner] = pending[partner]
+        return pending[da.name]
+
+
+def _vector_pairs(remapper, ds, pairs):
+    """None without pairs; else the call's :class:`_VectorPairs` after the
+    checks of the Dataset: every name is a variable of it (``KeyError``
+    naming it), the two members of a pair have the same dims and both or
+    neither of them survive ``_check_drop`` (``ValueError``)."""
+    if pairs is None:
+        return None
+    if not _is_dataset(ds):
+        raise KeyError(
+            f'vector_pairs names the variables {pairs[0][0]!r} and '
+            f'{pairs[0][1]!r}: a Dataset that holds them is needed, not a '
+            f'DataArray')
+    for pair in pairs:
+        for name in pair:
+            if name not in ds.variables:
+                raise KeyError(
+                    f'vector_pairs names the variable {name!r}, which is '
+                    f'not in the Dataset')
+        u, v = ds[pair[0]], ds[pair[1]]
+        if tuple(u.dims) != tuple(v.dims) or \
+                tuple(u.shape) != tuple(v.shape):
+            raise ValueError(
+                f'the vector pair {pair!r} has dims {tuple(u.dims)} of '
+                f'shape {tuple(u.shape)} and {tuple(v.dims)} of shape '
+                f'{tuple(v.shape)}: expected the same')
+        if _check_drop(remapper, u) != _check_drop(remapper, v):
+            raise ValueError(f'only one member of the vector pair {pair!r} '
+                             f'can be remapped')
+    return _VectorPairs(pairs, ds)
+
+
 def _remap_numpy(remapper, ds, renormalization_threshold):
     """
     Remap a Dataset or DataArray, possibly masked and renormalized
@@ -202,8 +352,12 @@ def _remap_numpy(remapper, ds, renormalization_threshold):
         raise ValueError('No mapping file has been defined')
     # (before anything is loaded: a refusal or a missing fraction variable
     # costs nothing)
+    pairs = _check_vector_pairs(remapper)
     sgs = _sgs_fraction(remapper, ds)
+    vec = _vector_pairs(remapper, ds, pairs)
     _load_mapping(remapper, limiter=_check_limiter(remapper))
+    if vec is not None:
+        _require_centres(remapper._ds_map)
 
     expected = remapper._ds_map.src_grid_dims
     for dim, size in zip(remapper.src_descriptor.dims, expected):
@@ -226,11 +380,11 @@ def _remap_numpy(remapper, ds, renormalization_threshold):
             # is lazy too -- each variable is read, remapped and handed to the
             # writer in turn, never all of them at once
             result = _lazy_dataset(remapper, kept, renormalization_threshold,
-                                   sgs=sgs)
+                                   sgs=sgs, vec=vec)
         else:
             result = kept.map(
                 _LookAhead(remapper, kept, list(kept.data_vars),
-                           renormalization_threshold, sgs=sgs),
+                           renormalization_threshold, sgs=sgs, vec=vec),
                 keep_attrs=True)
     else:
         raise TypeError('ds not an xarray Dataset or DataArray.')
@@ -406,7 +560,8 @@ def _plan_data_array(da, remapper):
     return remap_axes, dims, coords
 
 
-def _lazy_dataset(remapper, ds, renormalization_threshold, sgs=None):
+def _lazy_dataset(remapper, ds, renormalization_threshold, sgs=None,
+                  vec=None):
     """
     ``ds.map(_remap_data_array, keep_attrs=True)`` for a Dataset whose
     variables are (partly) still on disk: same variables, dims, coordinates
@@ -434,7 +589,8 @@ def _lazy_dataset(remapper, ds, renormalization_threshold, sgs=None):
             def start(da=da):
                 finish = _start_data_array(da, remapper,
                                            renormalization_threshold,
-                                           keep_on_device=True, sgs=sgs)
+                                           keep_on_device=True, sgs=sgs,
+                                           vec=vec)
                 return lambda: finish().values
             out = xr_lite.DataArray(
                 xr_lite.LazyValues(shape, np.float64,
@@ -450,7 +606,7 @@ def _lazy_dataset(remapper, ds, renormalization_threshold, sgs=None):
 
 
 def _start_data_array(da, remapper, renormalization_threshold,
-                      keep_on_device=False, sgs=None):
+                      keep_on_device=False, sgs=None, vec=None):
     """
     Enqueue the remap of one variable -- upload, NaN scan, launch, download,
     none of which waits for the host -- and return the function that waits
@@ -459,12 +615,23 @@ def _start_data_array(da, remapper, renormalization_threshold,
     host then holds one result at a time).  ``sgs``: the call's
     :class:`_SgsFraction` (``Remapper.sgs_frac``); a variable it weights
     takes the whole-array route -- upload, ``engine.remap_tensor_sgs``,
-    download.
+    download.  ``vec``: the call's :class:`_VectorPairs`
+    (``Remapper.vector_pairs``); a member of a pair is remapped together
+    with its partner, ``engine.remap_tensor_vector``, when the first of the
+    two gets here.
     """
     plan = _plan_data_array(da, remapper)
     if plan is None:
         return lambda: da  # nothing to remap
     remap_axes, dims, coords = plan
+
+    if vec is not None and da.name in vec:
+        pending = vec.start(da, remapper, remap_axes,
+                            renormalization_threshold)
+        make = _array_class(da).from_dict
+        attrs, name = da.attrs, da.name
+        return lambda: make({'coords': coords, 'attrs': attrs, 'dims': dims,
+                             'data': pending.result(), 'name': name})
 
     if sgs is not None and sgs.weights(da):
         torch = engine.require_gpu()
@@ -606,12 +773,17 @@ class _LookAhead:
     (reference: the per-variable loop of ``remap_numpy.py:42-55``).
     """
 
-    def __init__(self, remapper, ds, names, threshold, depth=2, sgs=None):
+    def __init__(self, remapper, ds, names, threshold, depth=2, sgs=None,
+                 vec=None):
         self.remapper, self.ds, self.names = remapper, ds, list(names)
         self.threshold, self.depth, self.sgs = threshold, depth, sgs
+        self.vec = vec
         self.started = {}
         self.position = 0
-        self.batches = _batches(remapper, ds, self.names)
+        # (the members of a vector pair are not stacked with other variables)
+        self.batches = _batches(
+            remapper, ds, [name for name in self.names
+                           if vec is None or name not in vec])
 
     def _start_up_to(self, last):
         while self.position <= min(last, len(self.names) - 1):
@@ -626,7 +798,7 @@ class _LookAhead:
                 else:
                     self.started[name] = _start_data_array(
                         self.ds[name], self.remapper, self.threshold,
-                        sgs=self.sgs)
+                        sgs=self.sgs, vec=self.vec)
             self.position += 1
 
     def __call__(self, da, *unused):
@@ -742,6 +914,55 @@ def _remap_array_sgs(remapper, in_field, sgs_frac, remap_axes,
         return out
     out = out.cpu().numpy()
     return np.ma.masked_array(out, mask=np.isnan(out))
+
+
+def _remap_array_vector(remapper, u, v, remap_axes,
+                        renormalization_threshold):
+    """
+    One pair of arrays through ``engine.remap_tensor_vector``: device tensors
+    in, two device tensors out (NaN where masked); numpy in, two
+    ``numpy.ma.MaskedArray`` out with the masks taken from NaN.  ``None``
+    threshold means 0.0.
+    """
+    _check_vector_alone(remapper)
+    torch = engine.require_gpu()
+    plan = remapper._matrix
+    threshold = 0.0 if renormalization_threshold is None else \
+        float(renormalization_threshold)
+    remap_axes = [int(a) for a in remap_axes]
+    on_device = isinstance(u, torch.Tensor)
+    if on_device != isinstance(v, torch.Tensor):
+        raise TypeError('u and v must both be device tensors or both host '
+                        'arrays')
+    if on_device:
+        fields = [u.to(plan.device), v.to(plan.device)]
+    else:
+        fields = [_host_values(torch, u, plan.device),
+                  _host_values(torch, v, plan.device)]
+    BA, BB = remapper._ds_map.bases(plan)
+    out = engine.remap_tensor_vector(
+        plan, remapper._ds_map.dst_grid_dims, fields[0], fields[1], BA, BB,
+        remap_axes, threshold=threshold)
+    if on_device:
+        return out
+    out = [y.cpu().numpy() for y in out]
+    return tuple(np.ma.masked_array(y, mask=np.isnan(y)) for y in out)
+
+
+def _check_vector_fields(u, v):
+    """``u`` and ``v`` of one kind (``TypeError``), one shape and one dtype
+    (``ValueError``); no device is needed to be told so."""
+    tensors = [type(f).__module__.split('.')[0] == 'torch' for f in (u, v)]
+    if tensors[0] != tensors[1]:
+        raise TypeError('u and v must both be device tensors or both host '
+                        'arrays')
+    shapes = [tuple(getattr(f, 'shape', np.shape(f))) for f in (u, v)]
+    dtypes = [getattr(f, 'dtype', None) for f in (u, v)]
+    if shapes[0] != shapes[1] or dtypes[0] != dtypes[1]:
+        raise ValueError(
+            f'u of shape {shapes[0]} and dtype {dtypes[0]}, v of shape '
+            f'{shapes[1]} and dtype {dtypes[1]}: expected one shape and one '
+            f'dtype')
 
 
 def _remap_numpy_array(remapper, in_field, remap_axes,

@@ -11,9 +11,13 @@ knobs and :meth:`from_triplets` for mapping data that is already in memory.
 from pyremap_amd.remapper.remap_numpy import (
     _check_limiter,
     _check_sgs_alone,
+    _check_vector_alone,
+    _check_vector_fields,
     _load_mapping,
     _remap_numpy,
     _remap_array_sgs,
+    _remap_array_vector,
+    _require_centres,
     _remap_numpy_array,
 )
 from pyremap_amd.remapper.setup import _setup_remapper
@@ -54,6 +58,16 @@ class Remapper:
         variable whose dims contain the fraction's as a mean over that
         fraction (:mod:`pyremap_amd.sgs`); :meth:`remap_array_sgs` is the
         array-level entry
+    vector_pairs : None or list of (str, str)
+        set after construction (default ``None``: nothing changes): the
+        names of the eastward and northward components of vector fields --
+        ``[('velocityZonal', 'velocityMeridional')]``.  ``remap_numpy`` and
+        ``ncremap`` then remap the two members of every pair together: the
+        source vectors are rotated to Cartesian, summed and projected on the
+        destination's east and north (:mod:`pyremap_amd.vector`), instead of
+        each component as a scalar; :meth:`remap_array_vector` is the
+        array-level entry.  The mapping file must hold the cell centres
+        ``xc_a, yc_a, xc_b, yc_b``
     """
 
     def __init__(
@@ -99,6 +113,14 @@ class Remapper:
         #: fraction variable itself, and variables that lack one of its dims,
         #: are remapped as without it.
         self.sgs_frac = None
+        #: vector fields (None | a list of (u_name, v_name) pairs of Dataset
+        #: variables: eastward and northward components), honoured by
+        #: remap_numpy and ncremap: the two members of a pair are remapped
+        #: together, in one launch, as the vector they are -- rotated to
+        #: Cartesian with the source cells' east / north, summed, projected
+        #: on the destination cell's (pyremap_amd.vector).  Every other
+        #: variable is remapped as without it.
+        self.vector_pairs = None
         self.src_scrip_filename = 'src_mesh.nc'
         self.dst_scrip_filename = 'dst_mesh.nc'
         self.format = 'NETCDF3_64BIT_DATA'
@@ -412,6 +434,34 @@ class Remapper:
         _load_mapping(self)
         return _remap_array_sgs(self, field, sgs_frac, remap_axes,
                                 renormalization_threshold)
+
+    def remap_array_vector(self, u, v, remap_axes,
+                           renormalization_threshold=None):
+        """
+        :meth:`remap_array` for the eastward and northward components ``u``
+        and ``v`` of a vector field (a velocity, a wind stress, an ice
+        drift): every source vector is rotated to Cartesian with its cell's
+        east and north, the weighted sums are projected on the destination
+        cell's east and north, in one launch (:mod:`pyremap_amd.vector` has
+        the definition to the bit).  Device tensors in -> two device tensors
+        out, NaN where masked; numpy in -> two ``numpy.ma.MaskedArray`` out,
+        the masks taken from NaN.
+
+        ``u`` and ``v`` have one shape and one dtype (``ValueError``); a NaN
+        in either masks the cell for both.  A destination cell is masked
+        where the valid weight is not above ``renormalization_threshold``
+        (``None``: 0.0).  The directions come from the cell centres ``xc_a,
+        yc_a, xc_b, yc_b`` of the mapping file (``ValueError`` if it has
+        none).
+        """
+        if self.map_filename is None:
+            raise ValueError('No mapping file has been defined')
+        _check_vector_alone(self)
+        _check_vector_fields(u, v)
+        _load_mapping(self)
+        _require_centres(self._ds_map)
+        return _remap_array_vector(self, u, v, remap_axes,
+                                   renormalization_threshold)
 
     # pyremap-1.x names used by BASELINE.json's north_star
     remap = remap_numpy
