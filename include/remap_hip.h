@@ -1952,6 +1952,92 @@ typedef struct remap_vector_args {
 REMAP_API int remap_apply_vector(const struct remap_vector_args *args,
                                  void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Columns interpolated to target levels inside the apply: depth slices
+ * (csrc/remap_levels.hip; pyremap_amd.levels is the
+ * same statement in numpy).
+ *
+ * Level k of an MPAS-Ocean (Time, nCells, nVertLevels) field sits at another
+ * depth in every cell (zMid), and its columns end at another bottom in every
+ * cell.  This launch interpolates, for every entry of a row, the source
+ * column to the target level first and lets the value enter the masked,
+ * renormalised sum then: the field at a depth, in one pass, without the
+ * (.., nCells, L) intermediate.  An entry whose column does not reach the
+ * level is skipped exactly as a NaN is.
+ *
+ * Inputs: the source field X[cell, b, k], k < n_levels, fp32 or fp64; the
+ * level coordinate Z[cell, b', k], fp32 or fp64 independently of X; the
+ * targets T[l], l < k_inner, fp64 on the device, in any order, duplicates
+ * allowed.  Every float32 widens to double first.
+ *
+ * For destination element (i, b, l), the entries j of row i are walked in CSR
+ * order.  Two float64 accumulators start at +0.0.
+ *
+ *   t = T[l];   z_k = (double) Z[cell(col_j), b', k];   x_k = (double) X[cell(col_j), b, k]
+ *   walk k = 0 .. n_levels-1 in ascending order and stop at the first hit:
+ *     node hit:      t == z_k:   v = x_k      (x_{k+1} is not looked at)
+ *     interior hit:  k+1 < n_levels and (z_k < t && t < z_{k+1}  or  z_k > t && t > z_{k+1}):
+ *                    w = (t - z_k) / (z_{k+1} - z_k);   v = x_k + w * (x_{k+1} - x_k)
+ *     no hit:        the column has no value at this level
+ *   the entry counts iff its column has a hit and v is no NaN
+ *   counts:  num += S_j * v;   valid += S_j      (every operation rounded on its own: no FMA contraction)
+ *   y = (valid > threshold) ? num / valid : NaN
+ *
+ * Comparisons with a NaN are false, so a NaN in Z never brackets anything.
+ * Columns may rise or fall; nothing assumes that they are monotone; nothing
+ * is extrapolated above the first or below the last valid level.  Every NaN
+ * written is the quiet NaN 0x7ff8000000000000, also where num / valid is
+ * itself a NaN.  The result is byte for byte REMAP_MODE_MASKED, at the same
+ * threshold, of the array of column values with NaN where an entry does not
+ * count.  With one strictly monotone Z shared by all cells and T = Z[ks] it
+ * is the masked apply of X[..., ks].
+ *
+ * X and Y are addressed as in remap_sgs_args (x_src_fold included), with
+ * n_levels the inner extent of X (stride 1) and k_inner = L the inner extent
+ * of Y.  Z is addressed like X with strides of its own:
+ *   Z[b * z_batch_stride + cell(a) + k],
+ *   cell(a) = a * z_row_stride, or with x_src_fold != 0
+ *   (a / x_src_fold) * z_outer_stride + (a % x_src_fold) * z_row_stride.
+ * z_row_stride == 0 (with z_outer_stride == 0) is one coordinate for all
+ * cells, z_batch_stride == 0 a time-invariant coordinate.
+ *
+ * Elements of rows outside [row_begin, row_end) are not written.
+ * Asynchronous on `stream`; nothing is allocated, freed or synchronised.
+ * REMAP_ERR_ARG: what remap_apply_sgs refuses (a NULL array that is needed,
+ * a negative stride or size, a row range outside [0, A.n_rows], an x_dtype
+ * that is no REMAP_DTYPE_*, an x_src_fold that does not divide A.n_cols, more
+ * elements than one launch serves), n_levels < 1, a NULL Z or T, a negative Z
+ * stride, a z_dtype that is no REMAP_DTYPE_*.
+ * ---------------------------------------------------------------------------
+ */
+typedef struct remap_levels_args {
+    remap_csr A;            /* rowptr, col and val are all read              */
+    int64_t row_begin;      /* rows [row_begin, row_end) of A are computed;  */
+    int64_t row_end;        /* Y is indexed by row                           */
+    const void *X;          /* (device) source field, n_levels per column    */
+    int32_t x_dtype;        /* REMAP_DTYPE_*                                 */
+    int64_t x_row_stride;
+    int64_t x_batch_stride;
+    int64_t x_src_fold;     /* as in remap_apply_args (0: one stride)        */
+    int64_t x_outer_stride;
+    int64_t n_levels;       /* inner extent of X and of Z, stride 1          */
+    const void *Z;          /* (device) level coordinate                     */
+    int32_t z_dtype;        /* REMAP_DTYPE_*                                 */
+    int64_t z_row_stride;   /* 0: one coordinate for all cells               */
+    int64_t z_batch_stride; /* 0: the same coordinate in every batch         */
+    int64_t z_outer_stride; /* with x_src_fold != 0, as x_outer_stride       */
+    const double *T;        /* (device) k_inner target levels                */
+    double *Y;              /* (device) destination field, float64           */
+    int64_t y_row_stride;
+    int64_t y_batch_stride;
+    int64_t n_batch;
+    int64_t k_inner;        /* L: the inner extent of Y                      */
+    double threshold;       /* of `valid`, as REMAP_MODE_MASKED has it       */
+} remap_levels_args;
+
+REMAP_API int remap_apply_levels(const struct remap_levels_args *args,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

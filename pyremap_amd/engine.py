@@ -99,6 +99,7 @@ EXPORTS = (
     'remap_node_rings_workspace', 'remap_node_rings', 'remap_patch_fits',
     'remap_patch_sizes_workspace', 'remap_patch_sizes', 'remap_patch_rows',
     'remap_limit_rows', 'remap_apply_sgs', 'remap_apply_vector',
+    'remap_apply_levels',
 )
 
 #: what ``limiter=`` accepts (remap_tensor, Remapper.limiter)
@@ -210,6 +211,33 @@ class _SgsArgs(ctypes.Structure):       # struct remap_sgs_args
         ('f_batch_stride', ctypes.c_int64),
         ('f_inner_stride', ctypes.c_int64),
         ('f_outer_stride', ctypes.c_int64),
+        ('Y', ctypes.c_void_p),
+        ('y_row_stride', ctypes.c_int64),
+        ('y_batch_stride', ctypes.c_int64),
+        ('n_batch', ctypes.c_int64),
+        ('k_inner', ctypes.c_int64),
+        ('threshold', ctypes.c_double),
+    ]
+
+
+class _LevelsArgs(ctypes.Structure):    # struct remap_levels_args
+    _fields_ = [
+        ('A', _CSR),
+        ('row_begin', ctypes.c_int64),
+        ('row_end', ctypes.c_int64),
+        ('X', ctypes.c_void_p),
+        ('x_dtype', ctypes.c_int32),
+        ('x_row_stride', ctypes.c_int64),
+        ('x_batch_stride', ctypes.c_int64),
+        ('x_src_fold', ctypes.c_int64),
+        ('x_outer_stride', ctypes.c_int64),
+        ('n_levels', ctypes.c_int64),
+        ('Z', ctypes.c_void_p),
+        ('z_dtype', ctypes.c_int32),
+        ('z_row_stride', ctypes.c_int64),
+        ('z_batch_stride', ctypes.c_int64),
+        ('z_outer_stride', ctypes.c_int64),
+        ('T', ctypes.c_void_p),
         ('Y', ctypes.c_void_p),
         ('y_row_stride', ctypes.c_int64),
         ('y_batch_stride', ctypes.c_int64),
@@ -705,6 +733,9 @@ def load_library():
                                     ctypes.c_void_p]
     lib.remap_apply_vector.restype = ctypes.c_int
     lib.remap_apply_vector.argtypes = [ctypes.POINTER(_VectorArgs),
+                                       ctypes.c_void_p]
+    lib.remap_apply_levels.restype = ctypes.c_int
+    lib.remap_apply_levels.argtypes = [ctypes.POINTER(_LevelsArgs),
                                        ctypes.c_void_p]
     if lib.remap_abi_version() != ABI_VERSION:
         raise EngineError(
@@ -2274,6 +2305,91 @@ def sgs_strided(plan, X, F, Y, *, n_batch, k_inner, x_row_stride,
     _launch(torch, plan, lib.remap_apply_sgs, 'remap_apply_sgs', args)
 
 
+def levels_strided(plan, X, Z, T, Y, *, n_batch, n_levels, k_inner,
+                   x_row_stride, x_batch_stride, z_row_stride,
+                   z_batch_stride, y_row_stride, y_batch_stride, threshold,
+                   row_begin=0, row_end=None, x_src_fold=0, x_outer_stride=0,
+                   z_outer_stride=0):
+    """
+    One asynchronous ``remap_apply_levels`` launch on torch's current stream:
+    every entry of a row interpolates its source column ``X[cell, b, :]`` on
+    the level coordinate ``Z[cell, b', :]`` (``n_levels`` each, stride 1) to
+    the ``k_inner`` targets ``T`` and enters the masked, renormalised sum of
+    rows ``[row_begin, row_end)`` of ``Y`` (:mod:`pyremap_amd.levels` has the
+    semantics; strides in elements).  ``X`` and ``Y`` are addressed as
+    :func:`apply_strided` addresses them, with ``n_levels`` the inner extent
+    of ``X`` and ``k_inner`` that of ``Y``; ``Z`` like ``X`` with strides of
+    its own: ``z_row_stride == 0`` is one coordinate for all cells,
+    ``z_batch_stride == 0`` a time-invariant one; ``z_outer_stride`` goes
+    with ``x_src_fold``.  ``T``: a float64 device tensor of ``k_inner``
+    targets, in any order.
+
+    The launch reads the plan's own CSR (``rowptr``, ``col``, ``val``), never
+    a schedule: a plan applied as short and long rows (``plan._split``) is
+    served as the one matrix it is.
+    """
+    torch = _torch()
+    lib = load_library()
+    _one_device(plan, 'the level interpolation')
+    for name, t in (('X', X), ('Z', Z), ('T', T), ('Y', Y)):
+        if t.device != plan.device:
+            raise ValueError('X, Z, T, Y and the plan must live on the same '
+                             'device')
+        if not t.is_contiguous():
+            raise ValueError(f'{name} must be contiguous')
+    if Y.dtype != torch.float64:
+        raise TypeError('Y must be float64')
+    if T.dtype != torch.float64:
+        raise TypeError('T must be float64')
+    x_dtype = _float_dtype(torch, 'X', X)
+    z_dtype = _float_dtype(torch, 'Z', Z)
+    row_begin, end = _row_range(plan, row_begin, row_end)
+    if n_batch < 0 or k_inner < 0:
+        raise ValueError('n_batch and k_inner must not be negative')
+    if n_levels < 1:
+        raise ValueError(f'n_levels {n_levels}: expected >= 1')
+    if T.numel() < k_inner:
+        raise ValueError(f'T holds {T.numel()} targets; k_inner is '
+                         f'{k_inner}')
+    if x_src_fold:
+        _check_fold(plan.n_a, x_src_fold, x_outer_stride, z_outer_stride)
+    # (a launch without batches or targets reads nothing; one with them
+    # reads whole columns)
+    columns = n_levels if k_inner > 0 else 0
+    _check_reach('X', X, plan.n_a, x_row_stride, x_batch_stride, 1, n_batch,
+                 columns, x_src_fold, x_outer_stride)
+    _check_reach('Z', Z, plan.n_a, z_row_stride, z_batch_stride, 1, n_batch,
+                 columns, x_src_fold, z_outer_stride)
+    _check_reach('Y', Y, plan.n_b, y_row_stride, y_batch_stride, 1, n_batch,
+                 k_inner)
+    _holds_csr(plan, ('rowptr', 'col', 'val'),
+               'the level interpolation reads it')
+    args = _LevelsArgs()
+    args.A = plan._csr_struct()
+    args.row_begin = row_begin
+    args.row_end = end
+    args.X = X.data_ptr()
+    args.x_dtype = x_dtype
+    args.x_row_stride = int(x_row_stride)
+    args.x_batch_stride = int(x_batch_stride)
+    args.x_src_fold = int(x_src_fold)
+    args.x_outer_stride = int(x_outer_stride)
+    args.n_levels = int(n_levels)
+    args.Z = Z.data_ptr()
+    args.z_dtype = z_dtype
+    args.z_row_stride = int(z_row_stride)
+    args.z_batch_stride = int(z_batch_stride)
+    args.z_outer_stride = int(z_outer_stride)
+    args.T = T.data_ptr()
+    args.Y = Y.data_ptr()
+    args.y_row_stride = int(y_row_stride)
+    args.y_batch_stride = int(y_batch_stride)
+    args.n_batch = int(n_batch)
+    args.k_inner = int(k_inner)
+    args.threshold = float(threshold)
+    _launch(torch, plan, lib.remap_apply_levels, 'remap_apply_levels', args)
+
+
 def _check_basis(torch, plan, name, B, rows):
     """A basis of the vector launch: a contiguous float64 ``(rows, 5)``
     tensor on the plan's device."""
@@ -2706,6 +2822,169 @@ def remap_tensor_sgs(plan, dst_grid_dims, field, frac, remap_axes,
         sgs_strided(plan, Xl, Fs[li if f_launches > 1 else 0], Yl,
                     threshold=threshold, **f_strides, **lay.strides)
     return _launch_result(lay, Y)
+
+
+def _levels_targets(torch, targets, device):
+    """``targets`` as a contiguous 1-D float64 tensor on ``device``."""
+    if isinstance(targets, torch.Tensor):
+        if targets.device != device:
+            raise ValueError('targets and the field must live on the same '
+                             'device')
+        if not (targets.dtype.is_floating_point or
+                targets.dtype in (torch.int32, torch.int64)):
+            raise ValueError(f'targets of dtype {targets.dtype}: expected '
+                             f'numbers')
+        T = targets.to(torch.float64)
+    else:
+        T = torch.as_tensor(targets, dtype=torch.float64).to(device)
+    if T.ndim != 1 or T.numel() == 0:
+        raise ValueError(f'targets of shape {tuple(T.shape)}: expected a '
+                         f'non-empty 1-D list of levels')
+    return T.contiguous()
+
+
+def remap_tensor_levels(plan, dst_grid_dims, field, z, targets, remap_axes,
+                        threshold=0.0):
+    """
+    :func:`remap_tensor` of a field interpolated to target levels
+    (:mod:`pyremap_amd.levels`; depth slices): the LAST axis of ``field`` is
+    its level axis, ``z`` the coordinate of every level (``zMid``),
+    ``targets`` the ``L`` levels asked for, in any order.  Every entry of a
+    row interpolates its source column to the target level first -- linear
+    between the two levels that bracket it, no value where none do, nothing
+    extrapolated -- and enters the masked, renormalised sum then, in ONE
+    launch per :func:`field_layout` launch (``remap_apply_levels``).  The
+    result has the shape and axis order of :func:`remap_tensor` with ``L`` in
+    place of ``n_levels``; float64, NaN where ``valid <= threshold``.
+
+    ``z`` has ``field``'s number of axes, the level axis at full extent, the
+    remap axes at full extent or all 1 (one coordinate for all cells) and
+    every other axis at the field's extent or 1 (a time-invariant
+    coordinate).  Groups of axes that are uniformly full or uniformly 1
+    become strides (a stride of 0 broadcasts); a group that mixes the two is
+    expanded once on the device.  One device only.
+    """
+    torch = _torch()
+    _one_device(plan, 'the level interpolation')
+    ndim = field.ndim
+    for name, t in (('field', field), ('z', z)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f'{name} must be a device tensor')
+        if not t.dtype.is_floating_point:
+            raise ValueError(f'{name} of dtype {t.dtype}: expected a '
+                             f'floating dtype')
+    if ndim < 2:
+        raise ValueError('the field needs a level axis behind its remap axes')
+    remap_axes, dst_shape = check_field_extents(
+        plan.n_a, plan.n_b, plan.n_b_global, dst_grid_dims, field.shape,
+        remap_axes)
+    if ndim - 1 in remap_axes:
+        raise ValueError('the last axis of the field is its level axis: it '
+                         'cannot be a remap axis')
+    if z.ndim != ndim:
+        raise ValueError(f'z has {z.ndim} axes, the field {ndim}')
+    if z.device != field.device:
+        raise ValueError('z and the field must live on the same device')
+    shape = [int(s) for s in field.shape]
+    n_levels = shape[-1]
+    if n_levels < 1:
+        raise ValueError('the level axis is empty')
+    z_cells = [int(z.shape[ax]) == shape[ax] for ax in remap_axes]
+    for ax in range(ndim):
+        have, want = int(z.shape[ax]), shape[ax]
+        full_only = ax == ndim - 1
+        if have != want and (full_only or have != 1):
+            raise ValueError(
+                f'z of shape {tuple(z.shape)} against a field of shape '
+                f'{tuple(field.shape)}: axis {ax} must have extent {want}' +
+                ('' if full_only else ' or 1'))
+    if not all(z_cells) and any(int(z.shape[ax]) != 1 for ax in remap_axes):
+        raise ValueError(
+            f'z of shape {tuple(z.shape)}: the remap axes {remap_axes} must '
+            f'all have the field\'s extent or all have extent 1')
+    z_cells = all(z_cells)
+    T = _levels_targets(torch, targets, field.device)
+    L = int(T.numel())
+    if field.dtype not in (torch.float64, torch.float32):
+        field = field.to(torch.float64)
+    if z.dtype not in (torch.float64, torch.float32):
+        z = z.to(torch.float64)
+    lay = field_layout(plan, shape, remap_axes, dst_shape)
+    if lay.route == 'fold' and len(lay.groups[2]) > 1:
+        # (dims between the last source axis and the levels: transposed)
+        lay = field_layout(plan, shape, remap_axes, dst_shape, fold=False)
+    n_a, n_b = plan.n_a, plan.n_b
+    n_az = n_a if z_cells else 1
+    nl = n_levels
+    level_axis = ndim - 1
+    if lay.route == 'permute':
+        extras = [ax for ax in lay.groups[2] if ax != level_axis]
+        z, mid_full = _sgs_group(z, shape, extras)
+        M = _prod(shape[ax] for ax in extras)
+        Mz = M if mid_full else 1
+        X = field.permute(lay.order).reshape(n_a, M * nl).contiguous()
+        Z = z.permute(lay.order).reshape(n_az, Mz * nl).contiguous()
+        strides = dict(n_batch=M, x_batch_stride=nl, x_row_stride=M * nl,
+                       y_batch_stride=L, y_row_stride=M * L,
+                       z_batch_stride=nl if mid_full else 0,
+                       z_row_stride=Mz * nl if z_cells else 0)
+        n_launch, lead_full = 1, False
+        y_shape = [n_b, M * L]
+        back_shape, unpermute = lay.back
+        back = (list(back_shape[:-1]) + [L], unpermute)
+    elif lay.route == 'fold':
+        lead, mid = list(lay.groups[0]), list(lay.groups[1])
+        z, lead_full = _sgs_group(z, shape, lead)
+        z, mid_full = _sgs_group(z, shape, mid)
+        nx = lay.strides['x_src_fold']
+        M = lay.strides['n_batch']
+        Mz = M if mid_full else 1
+        X, Z = field.contiguous(), z.contiguous()
+        strides = dict(n_batch=M, x_row_stride=nl, x_batch_stride=nx * nl,
+                       x_src_fold=nx, x_outer_stride=M * nx * nl,
+                       y_row_stride=M * L, y_batch_stride=L)
+        if z_cells:
+            strides.update(z_row_stride=nl, z_outer_stride=Mz * nx * nl,
+                           z_batch_stride=nx * nl if mid_full else 0)
+        else:
+            strides.update(z_row_stride=0, z_outer_stride=0,
+                           z_batch_stride=nl if mid_full else 0)
+        n_launch = lay.n_launch
+        y_shape, back = list(lay.out_shape[:-1]) + [L], None
+    else:
+        lead = list(lay.groups[0])
+        mid = [ax for ax in lay.groups[2] if ax != level_axis]
+        z, lead_full = _sgs_group(z, shape, lead)
+        z, mid_full = _sgs_group(z, shape, mid)
+        NB = _prod(shape[ax] for ax in lead)
+        M = _prod(shape[ax] for ax in mid)
+        Mz = M if mid_full else 1
+        X, Z = field.contiguous(), z.contiguous()
+        if M == 1:
+            # (Time, nCells, nVertLevels): the dims in front are the batches
+            strides = dict(n_batch=NB, x_row_stride=nl,
+                           x_batch_stride=n_a * nl, y_row_stride=L,
+                           y_batch_stride=n_b * L,
+                           z_row_stride=nl if z_cells else 0,
+                           z_batch_stride=n_az * nl if lead_full else 0)
+            n_launch, lead_full = 1, False
+        else:
+            # dims between the source axes and the levels are the batches,
+            # one launch per index of the dims in front
+            strides = dict(n_batch=M, x_batch_stride=nl, x_row_stride=M * nl,
+                           y_batch_stride=L, y_row_stride=M * L,
+                           z_batch_stride=nl if mid_full else 0,
+                           z_row_stride=Mz * nl if z_cells else 0)
+            n_launch = NB
+        y_shape, back = list(lay.out_shape[:-1]) + [L], None
+    Y = torch.empty(y_shape, dtype=torch.float64, device=field.device)
+    Zs = [Zl for Zl, in _launch_rows(n_launch if lead_full else 1, Z)]
+    for li, (Xl, Yl) in enumerate(_launch_rows(n_launch, X, Y)):
+        levels_strided(plan, Xl, Zs[li if lead_full else 0], T, Yl,
+                       n_levels=nl, k_inner=L, threshold=threshold, **strides)
+    if back is None:
+        return Y
+    return Y.reshape(back[0]).permute(back[1]).contiguous()
 
 
 def remap_tensor_vector(plan, dst_grid_dims, u, v, basis_a, basis_b,

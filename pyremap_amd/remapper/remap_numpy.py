@@ -224,6 +224,165 @@ def _sgs_fraction(remapper, ds):
     return _SgsFraction(name, ds[name], remapper.src_descriptor.dims)
 
 
+def _check_levels(remapper):
+    """The Remapper's ``levels`` as ``(coordinate, targets, out_dim)`` --
+    ``targets`` a 1-D float64 array -- or None, and what it does not go
+    together with."""
+    spec = getattr(remapper, 'levels', None)
+    if spec is None:
+        return None
+    wording = "levels must be None or dict(coordinate='zMid', " \
+        "targets=[...], out_dim='level')"
+    if not isinstance(spec, dict) or \
+            not {'coordinate', 'targets'} <= set(spec) or \
+            not set(spec) <= {'coordinate', 'targets', 'out_dim'}:
+        raise TypeError(f'{wording}, not {spec!r}')
+    coordinate, out_dim = spec['coordinate'], spec.get('out_dim', 'level')
+    if not isinstance(coordinate, str) or not isinstance(out_dim, str):
+        raise TypeError(f'{wording}: coordinate and out_dim are names, not '
+                        f'{coordinate!r} and {out_dim!r}')
+    targets = spec['targets']
+    if isinstance(targets, (str, bytes)) or np.ndim(targets) != 1:
+        raise TypeError(f'{wording}: targets is a list of numbers, not '
+                        f'{targets!r}')
+    try:
+        targets = np.asarray(targets, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise TypeError(f'{wording}: targets is a list of numbers, not '
+                        f'{targets!r}') from None
+    if targets.size == 0:
+        raise ValueError('levels names no target level: targets is empty')
+    _check_levels_alone(remapper)
+    return coordinate, targets, out_dim
+
+
+def _check_levels_alone(remapper):
+    """What the level interpolation does not go together with."""
+    if getattr(remapper, 'limiter', None) is not None:
+        raise NotImplementedError(
+            'levels together with a limiter is not served: one or the other')
+    if getattr(remapper, 'sgs_frac', None) is not None:
+        raise NotImplementedError(
+            'levels together with sgs_frac is not served')
+    if getattr(remapper, 'vector_pairs', None):
+        raise NotImplementedError(
+            'levels together with vector_pairs is not served')
+    if getattr(remapper, '_process_group', None) is not None or \
+            len(getattr(remapper, 'devices', None) or ()) > 1:
+        raise NotImplementedError(
+            'levels serves one device: not with devices=[...] or a process '
+            'group')
+
+
+class _LevelCoordinate:
+    """The level coordinate of one ``remap_numpy`` / ``ncremap`` call
+    (``Remapper.levels``): read and uploaded once, when the first
+    interpolated variable asks for it."""
+
+    def __init__(self, name, da, src_dims, targets, out_dim):
+        missing = [dim for dim in src_dims if dim not in da.dims]
+        if missing:
+            raise ValueError(
+                f'the levels coordinate {name!r} has dims {tuple(da.dims)}: '
+                f'it lacks the source dims {missing}')
+        if da.dims[-1] in src_dims:
+            raise ValueError(
+                f'the levels coordinate {name!r} has dims {tuple(da.dims)}: '
+                f'its last dim is the level dim, and {da.dims[-1]!r} is a '
+                f'source dim')
+        self.name, self.da = name, da
+        self.dims = list(da.dims)
+        self.level_dim = self.dims[-1]
+        if out_dim == self.level_dim:
+            raise ValueError(
+                f'out_dim {out_dim!r} is the level dim of the coordinate '
+                f'{name!r}: the target levels need a dim of their own')
+        self.targets, self.out_dim = targets, out_dim
+        self._device = None
+        self._targets = None
+
+    def interpolates(self, da):
+        """Is ``da`` interpolated?  Every remapped variable whose dims
+        contain all dims of the coordinate is; the coordinate itself is
+        not."""
+        return da.name != self.name and \
+            all(dim in da.dims for dim in self.dims)
+
+    def out_dims(self, dims):
+        """``dims`` with the target dim in place of the level dim."""
+        return [self.out_dim if dim == self.level_dim else dim
+                for dim in dims]
+
+    def on_device(self, plan, dims):
+        """``(z, targets)`` on the plan's device: the coordinate with one
+        axis per entry of ``dims`` (an interpolated variable's, the level
+        dim last), extent 1 where the coordinate has no such dim."""
+        torch = engine.require_gpu()
+        if self._device is None:
+            values = host_path._as_uploadable(self.da.values)
+            self._device = torch.from_numpy(values).to(plan.device)
+            self._targets = torch.from_numpy(self.targets).to(plan.device)
+        have = [dim for dim in dims if dim in self.dims]
+        z = self._device.permute([self.dims.index(dim) for dim in have])
+        for axis, dim in enumerate(dims):
+            if dim not in self.dims:
+                z = z.unsqueeze(axis)
+        return z, self._targets
+
+    def start(self, da, remapper, threshold):
+        """Enqueue the remap of the interpolated variable ``da``; returns
+        the ``host_path.OnDevice`` that hands its result down, with the
+        target dim where the level dim was."""
+        torch = engine.require_gpu()
+        plan = remapper._matrix
+        src_dims = remapper.src_descriptor.dims
+        # the level axis last (a view: the engine makes the copy)
+        dims = [dim for dim in da.dims if dim != self.level_dim] + \
+            [self.level_dim]
+        field = torch.from_numpy(host_path._as_uploadable(da.values)) \
+            .to(plan.device).permute([da.dims.index(dim) for dim in dims])
+        z, targets = self.on_device(plan, dims)
+        remap_axes = [axis for axis, dim in enumerate(dims)
+                      if dim in src_dims]
+        y_d = engine.remap_tensor_levels(
+            plan, remapper._ds_map.dst_grid_dims, field, z, targets,
+            remap_axes, threshold=0.0 if threshold is None else threshold)
+        # the axis order of the result as it stands, and as it is asked for
+        have = _result_dims(dims, remapper)
+        want = _result_dims(list(da.dims), remapper)
+        if have != want:
+            y_d = y_d.permute([have.index(dim) for dim in want]).contiguous()
+        return host_path.OnDevice(y_d, tuple(y_d.shape))
+
+
+def _result_dims(dims, remapper):
+    """The dims of a remapped variable of dims ``dims``: the destination
+    dims where the first source dim was, the other source dims gone."""
+    src_dims = remapper.src_descriptor.dims
+    first = min(axis for axis, dim in enumerate(dims) if dim in src_dims)
+    return list(dims[:first]) + list(remapper.dst_descriptor.dims) + \
+        [dim for dim in dims[first:] if dim not in src_dims]
+
+
+def _level_coordinate(remapper, ds):
+    """None without ``Remapper.levels``; else the coordinate variable of
+    ``ds`` (``KeyError`` naming it if ``ds`` has none)."""
+    spec = _check_levels(remapper)
+    if spec is None:
+        return None
+    name, targets, out_dim = spec
+    if not _is_dataset(ds) or name not in ds.variables:
+        raise KeyError(
+            f'levels names the coordinate variable {name!r}, which is not '
+            f'in the Dataset')
+    if out_dim in ds.variables or out_dim in ds.sizes:
+        raise ValueError(
+            f'out_dim {out_dim!r} is already a variable or a dim of the '
+            f'Dataset')
+    return _LevelCoordinate(name, ds[name], remapper.src_descriptor.dims,
+                            targets, out_dim)
+
+
 def _check_vector_alone(remapper):
     """What the vector remap does not go together with."""
     if getattr(remapper, 'limiter', None) is not None:
@@ -352,6 +511,7 @@ def _remap_numpy(remapper, ds, renormalization_threshold):
         raise ValueError('No mapping file has been defined')
     # (before anything is loaded: a refusal or a missing fraction variable
     # costs nothing)
+    lev = _level_coordinate(remapper, ds)
     pairs = _check_vector_pairs(remapper)
     sgs = _sgs_fraction(remapper, ds)
     vec = _vector_pairs(remapper, ds, pairs)
@@ -380,11 +540,12 @@ def _remap_numpy(remapper, ds, renormalization_threshold):
             # is lazy too -- each variable is read, remapped and handed to the
             # writer in turn, never all of them at once
             result = _lazy_dataset(remapper, kept, renormalization_threshold,
-                                   sgs=sgs, vec=vec)
+                                   sgs=sgs, vec=vec, lev=lev)
         else:
             result = kept.map(
                 _LookAhead(remapper, kept, list(kept.data_vars),
-                           renormalization_threshold, sgs=sgs, vec=vec),
+                           renormalization_threshold, sgs=sgs, vec=vec,
+                           lev=lev),
                 keep_attrs=True)
     else:
         raise TypeError('ds not an xarray Dataset or DataArray.')
@@ -531,11 +692,14 @@ def _remap_data_array(da, remapper, renormalization_threshold):
     return _start_data_array(da, remapper, renormalization_threshold)()
 
 
-def _plan_data_array(da, remapper):
+def _plan_data_array(da, remapper, lev=None):
     """
     The bookkeeping of reference ``_remap_data_array`` :150-199 without
     touching the values: ``(remap_axes, dims, coords)`` of the result, or
-    ``None`` for a variable without source dims.
+    ``None`` for a variable without source dims.  ``lev``: the call's
+    :class:`_LevelCoordinate`; a variable it interpolates comes out with the
+    target dim in place of the level dim, loses the coordinates along the
+    level dim and gains the target levels as a coordinate.
     """
     src_dims = remapper.src_descriptor.dims
     remap_axes = [axis for axis, dim in enumerate(da.dims)
@@ -557,11 +721,16 @@ def _plan_data_array(da, remapper):
         if not any(dim in coord.dims for dim in src_dims):
             coords[name] = {'dims': coord.dims, 'data': coord.values}
     coords.update(remapper.dst_descriptor.coords)
+    if lev is not None and lev.interpolates(da):
+        dims = lev.out_dims(dims)
+        coords = {name: coord for name, coord in coords.items()
+                  if lev.level_dim not in coord['dims']}
+        coords[lev.out_dim] = {'dims': (lev.out_dim,), 'data': lev.targets}
     return remap_axes, dims, coords
 
 
 def _lazy_dataset(remapper, ds, renormalization_threshold, sgs=None,
-                  vec=None):
+                  vec=None, lev=None):
     """
     ``ds.map(_remap_data_array, keep_attrs=True)`` for a Dataset whose
     variables are (partly) still on disk: same variables, dims, coordinates
@@ -575,22 +744,25 @@ def _lazy_dataset(remapper, ds, renormalization_threshold, sgs=None,
     results = {}
     for name in ds.data_vars:
         da = ds[name]
-        plan = _plan_data_array(da, remapper)
+        plan = _plan_data_array(da, remapper, lev)
         if plan is None:
             out = da
         else:
             remap_axes, dims, coords = plan
             first = remap_axes[0]
-            shape = list(da.shape[:first]) + \
+            sizes = list(da.shape)
+            if lev is not None and lev.interpolates(da):
+                sizes[da.dims.index(lev.level_dim)] = lev.targets.size
+            shape = sizes[:first] + \
                 [int(s) for s in remapper._ds_map.dst_grid_dims] + \
-                [size for axis, size in enumerate(da.shape)
+                [size for axis, size in enumerate(sizes)
                  if axis > first and axis not in remap_axes]
 
             def start(da=da):
                 finish = _start_data_array(da, remapper,
                                            renormalization_threshold,
                                            keep_on_device=True, sgs=sgs,
-                                           vec=vec)
+                                           vec=vec, lev=lev)
                 return lambda: finish().values
             out = xr_lite.DataArray(
                 xr_lite.LazyValues(shape, np.float64,
@@ -606,7 +778,7 @@ def _lazy_dataset(remapper, ds, renormalization_threshold, sgs=None,
 
 
 def _start_data_array(da, remapper, renormalization_threshold,
-                      keep_on_device=False, sgs=None, vec=None):
+                      keep_on_device=False, sgs=None, vec=None, lev=None):
     """
     Enqueue the remap of one variable -- upload, NaN scan, launch, download,
     none of which waits for the host -- and return the function that waits
@@ -618,12 +790,21 @@ def _start_data_array(da, remapper, renormalization_threshold,
     download.  ``vec``: the call's :class:`_VectorPairs`
     (``Remapper.vector_pairs``); a member of a pair is remapped together
     with its partner, ``engine.remap_tensor_vector``, when the first of the
-    two gets here.
+    two gets here.  ``lev``: the call's :class:`_LevelCoordinate`
+    (``Remapper.levels``); a variable it interpolates takes the whole-array
+    route too -- upload, ``engine.remap_tensor_levels``, download.
     """
-    plan = _plan_data_array(da, remapper)
+    plan = _plan_data_array(da, remapper, lev)
     if plan is None:
         return lambda: da  # nothing to remap
     remap_axes, dims, coords = plan
+
+    if lev is not None and lev.interpolates(da):
+        pending = lev.start(da, remapper, renormalization_threshold)
+        make = _array_class(da).from_dict
+        attrs, name = da.attrs, da.name
+        return lambda: make({'coords': coords, 'attrs': attrs, 'dims': dims,
+                             'data': pending.result(), 'name': name})
 
     if vec is not None and da.name in vec:
         pending = vec.start(da, remapper, remap_axes,
@@ -700,9 +881,10 @@ def _batches(remapper, ds, names):
     if getattr(remapper, '_process_group', None) is not None or \
             plan is None or hasattr(plan, 'shards') or \
             getattr(remapper, 'limiter', None) is not None or \
-            getattr(remapper, 'sgs_frac', None) is not None:
-        # (a limited or fraction-weighted variable takes the whole-array
-        # route, one at a time)
+            getattr(remapper, 'sgs_frac', None) is not None or \
+            getattr(remapper, 'levels', None) is not None:
+        # (a limited, fraction-weighted or interpolated variable takes the
+        # whole-array route, one at a time)
         return {}
     groups = {}
     src_dims = remapper.src_descriptor.dims
@@ -774,10 +956,10 @@ class _LookAhead:
     """
 
     def __init__(self, remapper, ds, names, threshold, depth=2, sgs=None,
-                 vec=None):
+                 vec=None, lev=None):
         self.remapper, self.ds, self.names = remapper, ds, list(names)
         self.threshold, self.depth, self.sgs = threshold, depth, sgs
-        self.vec = vec
+        self.vec, self.lev = vec, lev
         self.started = {}
         self.position = 0
         # (the members of a vector pair are not stacked with other variables)
@@ -798,7 +980,7 @@ class _LookAhead:
                 else:
                     self.started[name] = _start_data_array(
                         self.ds[name], self.remapper, self.threshold,
-                        sgs=self.sgs, vec=self.vec)
+                        sgs=self.sgs, vec=self.vec, lev=self.lev)
             self.position += 1
 
     def __call__(self, da, *unused):
@@ -910,6 +1092,66 @@ def _remap_array_sgs(remapper, in_field, sgs_frac, remap_axes,
     out = engine.remap_tensor_sgs(
         plan, remapper._ds_map.dst_grid_dims, field, frac, remap_axes,
         threshold=threshold)
+    if on_device:
+        return out
+    out = out.cpu().numpy()
+    return np.ma.masked_array(out, mask=np.isnan(out))
+
+
+def _check_level_arrays(field, z, targets, level_axis):
+    """``field`` and ``z`` of one kind (``TypeError``) and one number of
+    axes, a level axis inside them and at least one target
+    (``ValueError``); no device is needed to be told so."""
+    tensors = [type(f).__module__.split('.')[0] == 'torch' for f in (field, z)]
+    if tensors[0] != tensors[1]:
+        raise TypeError('field and z must both be device tensors or both '
+                        'host arrays')
+    ndims = [len(getattr(f, 'shape', np.shape(f))) for f in (field, z)]
+    if ndims[0] != ndims[1]:
+        raise ValueError(f'z has {ndims[1]} axes, the field {ndims[0]}')
+    if not -ndims[0] <= int(level_axis) < ndims[0]:
+        raise ValueError(f'level_axis {level_axis} is no axis of a field of '
+                         f'{ndims[0]} axes')
+    if len(getattr(targets, 'shape', np.shape(targets))) != 1 or \
+            len(targets) == 0:
+        raise ValueError('targets must be a non-empty 1-D list of levels')
+
+
+def _remap_array_levels(remapper, in_field, z, targets, remap_axes,
+                        renormalization_threshold, level_axis=-1):
+    """
+    One array through ``engine.remap_tensor_levels``: device tensors in,
+    device tensor out (NaN where masked); numpy in, ``numpy.ma.MaskedArray``
+    out with the mask taken from NaN.  ``None`` threshold means 0.0.  A level
+    axis that is not the last is moved there (the engine copies), and the
+    target axis stands behind the other axes of the result.
+    """
+    _check_levels_alone(remapper)
+    _check_level_arrays(in_field, z, targets, level_axis)
+    torch = engine.require_gpu()
+    plan = remapper._matrix
+    threshold = 0.0 if renormalization_threshold is None else \
+        float(renormalization_threshold)
+    on_device = isinstance(in_field, torch.Tensor)
+    if on_device:
+        field, coord = in_field.to(plan.device), z.to(plan.device)
+    else:
+        field = _host_values(torch, in_field, plan.device)
+        coord = _host_values(torch, z, plan.device)
+    ndim = field.ndim
+    level_axis = int(level_axis) % ndim
+    remap_axes = [int(a) % ndim for a in remap_axes]
+    if level_axis != ndim - 1:
+        order = [ax for ax in range(ndim) if ax != level_axis] + [level_axis]
+        field, coord = field.permute(order), coord.permute(order)
+        remap_axes = [order.index(ax) for ax in remap_axes]
+    if isinstance(targets, torch.Tensor):
+        targets = targets.to(plan.device)
+    else:
+        targets = np.asarray(targets, dtype=np.float64)
+    out = engine.remap_tensor_levels(
+        plan, remapper._ds_map.dst_grid_dims, field, coord, targets,
+        remap_axes, threshold=threshold)
     if on_device:
         return out
     out = out.cpu().numpy()

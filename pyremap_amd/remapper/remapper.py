@@ -9,12 +9,15 @@ Added on top of the reference surface: ``remap`` / ``remap_file`` aliases
 knobs and :meth:`from_triplets` for mapping data that is already in memory.
 """
 from pyremap_amd.remapper.remap_numpy import (
+    _check_level_arrays,
+    _check_levels_alone,
     _check_limiter,
     _check_sgs_alone,
     _check_vector_alone,
     _check_vector_fields,
     _load_mapping,
     _remap_numpy,
+    _remap_array_levels,
     _remap_array_sgs,
     _remap_array_vector,
     _require_centres,
@@ -68,6 +71,18 @@ class Remapper:
         each component as a scalar; :meth:`remap_array_vector` is the
         array-level entry.  The mapping file must hold the cell centres
         ``xc_a, yc_a, xc_b, yc_b``
+    levels : None or dict
+        set after construction (default ``None``: nothing changes):
+        ``dict(coordinate='zMid', targets=[-200.0, ...], out_dim='level')``,
+        the name of the Dataset variable that holds the level coordinate
+        (its last dim is the level dim; it may lack dims the fields have,
+        such as ``Time``), the levels asked for and the name of their dim
+        (default ``'level'``).  ``remap_numpy`` and ``ncremap`` then
+        interpolate every variable whose dims contain the coordinate's to
+        the target levels, column by column inside the remap
+        (:mod:`pyremap_amd.levels`): the field at a depth, a column that
+        does not reach the depth skipped as a NaN is;
+        :meth:`remap_array_levels` is the array-level entry
     """
 
     def __init__(
@@ -121,6 +136,17 @@ class Remapper:
         #: on the destination cell's (pyremap_amd.vector).  Every other
         #: variable is remapped as without it.
         self.vector_pairs = None
+        #: depth slices (None | dict(coordinate='zMid', targets=[...],
+        #: out_dim='level')), honoured by remap_numpy and ncremap: every
+        #: remapped variable whose dims contain all dims of the coordinate
+        #: variable -- its last dim is the level dim -- is interpolated to
+        #: the target levels column by column inside the remap, in one
+        #: launch, and comes out with out_dim (of extent len(targets)) in
+        #: place of the level dim (pyremap_amd.levels); the output gains the
+        #: float64 variable out_dim that holds the targets.  The coordinate
+        #: variable itself, and variables that lack one of its dims, are
+        #: remapped as without it.
+        self.levels = None
         self.src_scrip_filename = 'src_mesh.nc'
         self.dst_scrip_filename = 'dst_mesh.nc'
         self.format = 'NETCDF3_64BIT_DATA'
@@ -462,6 +488,42 @@ class Remapper:
         _require_centres(self._ds_map)
         return _remap_array_vector(self, u, v, remap_axes,
                                    renormalization_threshold)
+
+    def remap_array_levels(self, field, z, targets, remap_axes,
+                           renormalization_threshold=None, level_axis=-1):
+        """
+        :meth:`remap_array` of a field AT LEVELS (depth slices): ``field``
+        has a level axis whose level ``k`` sits at ``z[..., k]`` -- another
+        depth in every cell, ``zMid`` of MPAS-Ocean -- and the result holds
+        the field at the ``L`` levels ``targets``, in any order.  Every
+        entry of a row interpolates its source column to the target level
+        first (linear between the two levels that bracket it; no value
+        where none do: nothing is extrapolated, a column that ends above
+        the level is skipped exactly as a NaN is) and enters the masked,
+        renormalised sum then, in one launch (:mod:`pyremap_amd.levels` has
+        the definition to the bit).  Device tensors in -> device tensor
+        out, NaN where masked; numpy in -> ``numpy.ma.MaskedArray`` out, the
+        mask taken from NaN.
+
+        The level axis is ``level_axis`` of ``field`` and of ``z`` (default:
+        the last).  A level axis that is not the last is moved there with a
+        copy on the device, and the target axis is the LAST axis of the
+        result: the shape and axis order of :meth:`remap_array` for the
+        field with its level axis last, with ``L`` in place of the number of
+        levels.  ``z`` has ``field``'s number of axes, the level axis at
+        full extent, the remap axes at full extent or all 1 and every other
+        axis at the field's extent or 1 (a time-invariant coordinate).  A
+        destination cell is masked where the valid weight is not above
+        ``renormalization_threshold`` (``None``: 0.0).
+        """
+        if self.map_filename is None:
+            raise ValueError('No mapping file has been defined')
+        _check_levels_alone(self)
+        _check_level_arrays(field, z, targets, level_axis)
+        _load_mapping(self)
+        return _remap_array_levels(self, field, z, targets, remap_axes,
+                                   renormalization_threshold,
+                                   level_axis=level_axis)
 
     # pyremap-1.x names used by BASELINE.json's north_star
     remap = remap_numpy
