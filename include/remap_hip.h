@@ -2038,6 +2038,98 @@ typedef struct remap_levels_args {
 REMAP_API int remap_apply_levels(const struct remap_levels_args *args,
                                  void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Columns averaged or integrated over depth ranges inside the apply: layer
+ * means, heat content (csrc/remap_layers.hip; DESIGN.md section 24;
+ * pyremap_amd.layers is the same statement in numpy).
+ *
+ * remap_apply_levels gives the field AT a depth; this launch gives the field
+ * OVER a depth range.  Every entry of a row first reduces its source column
+ * over the range -- the overlap of every layer with the range weighs the
+ * layer's value; a range may cut through a layer, a column may end inside
+ * the range or above it -- and enters the masked, renormalised sum then: one
+ * pass, without the (.., nCells, R) intermediate.
+ *
+ * Inputs: the source field X[cell, b, k], k < n_levels, fp32 or fp64; the
+ * layer thicknesses H[cell, b', k], fp32 or fp64 independently of X; the
+ * ranges bounds[2 r] = A_r, bounds[2 r + 1] = B_r, r < k_inner, fp64 on the
+ * device, in any order, duplicates allowed.  Every float32 widens to double
+ * first.  Depths are positive downward, measured from the top of each
+ * column's first layer.
+ *
+ * For destination element (i, b, r), with range [A, B] = [A_r, B_r], the
+ * entries j of row i are walked in CSR order.  Two float64 accumulators num
+ * and valid start at +0.0.  For each entry the source column c = cell(col_j)
+ * is walked k = 0 .. n_levels-1 ascending, from d = v = t = +0.0:
+ *
+ *   h = (double) H[c, b', k]
+ *   if !(h > 0): the layer is not there (NaN, zero, negative): skip it, d stays
+ *   top = d;  d = d + h
+ *   lo = top > A ? top : A;   hi = d < B ? d : B
+ *   if hi > lo:  o = hi - lo;  x = (double) X[c, b, k]
+ *                if x == x:  p = o * x;  v = v + p;  t = t + o
+ *   (the walk may stop once top >= B: nothing further can overlap)
+ *   the entry counts iff t > 0 and q is no NaN:  q = v / t (mean),  q = v (integral)
+ *   counts:  p = S_j * q;  num = num + p;  valid = valid + S_j      (every operation rounded on its own: no FMA contraction)
+ *   y = (valid > threshold) ? num / valid : NaN
+ *
+ * Comparisons with a NaN are false: a NaN bound gives an empty range, B =
+ * +inf means "to the bottom".  A layer whose value is a NaN leaves both sums
+ * of its column; a column that ends above A is skipped exactly as a NaN is
+ * (the bathymetry mask needs no input of its own); a column that ends inside
+ * the range contributes what it has.  Every NaN written is the quiet NaN
+ * 0x7ff8000000000000, also where num / valid is itself a NaN.  The result is
+ * byte for byte REMAP_MODE_MASKED, at the same threshold, of the array of
+ * column values q with NaN where an entry does not count.
+ *
+ * X and Y are addressed as in remap_levels_args (x_src_fold included), with
+ * n_levels the inner extent of X (stride 1) and k_inner = R the inner extent
+ * of Y.  H is addressed like X with strides of its own:
+ *   H[b * h_batch_stride + cell(a) + k],
+ *   cell(a) = a * h_row_stride, or with x_src_fold != 0
+ *   (a / x_src_fold) * h_outer_stride + (a % x_src_fold) * h_row_stride.
+ * h_row_stride == 0 (with h_outer_stride == 0) is one thickness column for
+ * all cells, h_batch_stride == 0 a time-invariant thickness.
+ *
+ * Elements of rows outside [row_begin, row_end) are not written.
+ * Asynchronous on `stream`; nothing is allocated, freed or synchronised.
+ * REMAP_ERR_ARG: what remap_apply_levels refuses of the members the two
+ * share, n_levels < 1, a NULL H or bounds, a negative H stride, an h_dtype
+ * that is no REMAP_DTYPE_*, a reduce that is no REMAP_REDUCE_*.
+ * ---------------------------------------------------------------------------
+ */
+#define REMAP_REDUCE_MEAN 0      /* q = v / t: the thickness-weighted mean  */
+#define REMAP_REDUCE_INTEGRAL 1  /* q = v: the integral over the range      */
+
+typedef struct remap_layers_args {
+    remap_csr A;            /* rowptr, col and val are all read              */
+    int64_t row_begin;      /* rows [row_begin, row_end) of A are computed;  */
+    int64_t row_end;        /* Y is indexed by row                           */
+    const void *X;          /* (device) source field, n_levels per column    */
+    int32_t x_dtype;        /* REMAP_DTYPE_*                                 */
+    int64_t x_row_stride;
+    int64_t x_batch_stride;
+    int64_t x_src_fold;     /* as in remap_apply_args (0: one stride)        */
+    int64_t x_outer_stride;
+    int64_t n_levels;       /* inner extent of X and of H, stride 1          */
+    const void *H;          /* (device) layer thicknesses                    */
+    int32_t h_dtype;        /* REMAP_DTYPE_*                                 */
+    int64_t h_row_stride;   /* 0: one thickness column for all cells         */
+    int64_t h_batch_stride; /* 0: the same thicknesses in every batch        */
+    int64_t h_outer_stride; /* with x_src_fold != 0, as x_outer_stride       */
+    const double *bounds;   /* (device) 2 * k_inner doubles: A_0, B_0, A_1.. */
+    double *Y;              /* (device) destination field, float64           */
+    int64_t y_row_stride;
+    int64_t y_batch_stride;
+    int64_t n_batch;
+    int64_t k_inner;        /* R: the inner extent of Y                      */
+    double threshold;       /* of `valid`, as REMAP_MODE_MASKED has it       */
+    int32_t reduce;         /* REMAP_REDUCE_*                                */
+} remap_layers_args;
+
+REMAP_API int remap_apply_layers(const struct remap_layers_args *args,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

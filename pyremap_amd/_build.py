@@ -19,7 +19,8 @@ SOURCES = ['remap_spmm.hip', 'remap_csr.hip', 'remap_schedule.hip',
            'remap_nearest.hip', 'remap_locate.hip', 'remap_quads.hip',
            'remap_expand.hip', 'remap_geometry.hip',
            'remap_conserve2nd.hip', 'remap_patch.hip', 'remap_limit.hip',
-           'remap_sgs.hip', 'remap_vector.hip', 'remap_levels.hip']
+           'remap_sgs.hip', 'remap_vector.hip', 'remap_levels.hip',
+           'remap_layers.hip']
 ARCH = 'gfx950'
 
 

@@ -1,8 +1,9 @@
 // rowpass.h -- what the passes that walk the rows of the plan's CSR beside
-// the SpMM apply share (remap_limit.hip, remap_sgs.hip, remap_vector.hip):
-// the checks of their argument structs, the addressing of a source cell, the
-// packed loads and stores, and the work list of the rowwave form.  A pass
-// comes in two forms:
+// the SpMM apply share (remap_limit.hip, remap_sgs.hip, remap_vector.hip,
+// remap_levels.hip, remap_layers.hip): the checks of their argument structs,
+// the addressing of a source cell, the packed loads and stores, and the work
+// list of the rowwave form.  A pass comes in two forms (remap_levels.hip and
+// remap_layers.hip have the first alone):
 //   rowlane  one lane per (row, column), for runs shorter than a wave;
 //   rowwave  one wave per (row, chunk of kWave * VEC contiguous columns),
 //            lanes across the columns, for runs of >= kWave columns.  The
@@ -35,8 +36,9 @@ namespace rowpass {
 // but it moves them to the front of the kernel arguments, and the scalar
 // registers the kernels take follow that layout.)
 
-// The checks remap_limit_args, remap_sgs_args and remap_vector_args share,
-// under the entry point's name `fn`; fills `p`.  `empty`: the arguments are
+// The checks remap_limit_args, remap_sgs_args, remap_vector_args,
+// remap_levels_args and remap_layers_args share, under the entry point's
+// name `fn`; fills `p`.  `empty`: the arguments are
 // fine and there is nothing to do.
 template <typename Args, typename P>
 int check_args(const char *fn, const Args &a, P &p, bool &empty)

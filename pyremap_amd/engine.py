@@ -54,6 +54,9 @@ CELL_MAX_RUN = 4
 DTYPE_F64 = 0
 DTYPE_F32 = 1
 
+#: what ``reduce=`` accepts (layers_strided, Remapper.layers): REMAP_REDUCE_*
+REDUCE = {'mean': 0, 'integral': 1}
+
 ABI_VERSION = 31
 
 #: the largest k of nearest_k_points (REMAP_NEAREST_K_MAX)
@@ -99,7 +102,7 @@ EXPORTS = (
     'remap_node_rings_workspace', 'remap_node_rings', 'remap_patch_fits',
     'remap_patch_sizes_workspace', 'remap_patch_sizes', 'remap_patch_rows',
     'remap_limit_rows', 'remap_apply_sgs', 'remap_apply_vector',
-    'remap_apply_levels',
+    'remap_apply_levels', 'remap_apply_layers',
 )
 
 #: what ``limiter=`` accepts (remap_tensor, Remapper.limiter)
@@ -244,6 +247,34 @@ class _LevelsArgs(ctypes.Structure):    # struct remap_levels_args
         ('n_batch', ctypes.c_int64),
         ('k_inner', ctypes.c_int64),
         ('threshold', ctypes.c_double),
+    ]
+
+
+class _LayersArgs(ctypes.Structure):    # struct remap_layers_args
+    _fields_ = [
+        ('A', _CSR),
+        ('row_begin', ctypes.c_int64),
+        ('row_end', ctypes.c_int64),
+        ('X', ctypes.c_void_p),
+        ('x_dtype', ctypes.c_int32),
+        ('x_row_stride', ctypes.c_int64),
+        ('x_batch_stride', ctypes.c_int64),
+        ('x_src_fold', ctypes.c_int64),
+        ('x_outer_stride', ctypes.c_int64),
+        ('n_levels', ctypes.c_int64),
+        ('H', ctypes.c_void_p),
+        ('h_dtype', ctypes.c_int32),
+        ('h_row_stride', ctypes.c_int64),
+        ('h_batch_stride', ctypes.c_int64),
+        ('h_outer_stride', ctypes.c_int64),
+        ('bounds', ctypes.c_void_p),
+        ('Y', ctypes.c_void_p),
+        ('y_row_stride', ctypes.c_int64),
+        ('y_batch_stride', ctypes.c_int64),
+        ('n_batch', ctypes.c_int64),
+        ('k_inner', ctypes.c_int64),
+        ('threshold', ctypes.c_double),
+        ('reduce', ctypes.c_int32),
     ]
 
 
@@ -736,6 +767,9 @@ def load_library():
                                        ctypes.c_void_p]
     lib.remap_apply_levels.restype = ctypes.c_int
     lib.remap_apply_levels.argtypes = [ctypes.POINTER(_LevelsArgs),
+                                       ctypes.c_void_p]
+    lib.remap_apply_layers.restype = ctypes.c_int
+    lib.remap_apply_layers.argtypes = [ctypes.POINTER(_LayersArgs),
                                        ctypes.c_void_p]
     if lib.remap_abi_version() != ABI_VERSION:
         raise EngineError(
@@ -2390,6 +2424,91 @@ def levels_strided(plan, X, Z, T, Y, *, n_batch, n_levels, k_inner,
     _launch(torch, plan, lib.remap_apply_levels, 'remap_apply_levels', args)
 
 
+def layers_strided(plan, X, H, bounds, Y, *, n_batch, n_levels, k_inner,
+                   x_row_stride, x_batch_stride, h_row_stride,
+                   h_batch_stride, y_row_stride, y_batch_stride, threshold,
+                   reduce='mean', row_begin=0, row_end=None, x_src_fold=0,
+                   x_outer_stride=0, h_outer_stride=0):
+    """
+    One asynchronous ``remap_apply_layers`` launch on torch's current stream:
+    every entry of a row reduces its source column ``X[cell, b, :]`` with the
+    layer thicknesses ``H[cell, b', :]`` (``n_levels`` each, stride 1) over
+    the ``k_inner`` depth ranges ``bounds`` -- the thickness-weighted mean
+    (``reduce='mean'``) or the integral (``'integral'``) -- and enters the
+    masked, renormalised sum of rows ``[row_begin, row_end)`` of ``Y``
+    (:mod:`pyremap_amd.layers` has the semantics; strides in elements).
+    ``X``, ``Y`` and ``H`` are addressed as :func:`levels_strided` addresses
+    ``X``, ``Y`` and ``Z``: ``h_row_stride == 0`` is one thickness column for
+    all cells, ``h_batch_stride == 0`` a time-invariant thickness;
+    ``h_outer_stride`` goes with ``x_src_fold``.  ``bounds``: a float64
+    device tensor of ``2 * k_inner`` numbers, ``A_0, B_0, A_1, ...``.
+
+    The launch reads the plan's own CSR (``rowptr``, ``col``, ``val``), never
+    a schedule.
+    """
+    torch = _torch()
+    lib = load_library()
+    _one_device(plan, 'the layer reduction')
+    code = _reduce_code(reduce)
+    for name, t in (('X', X), ('H', H), ('bounds', bounds), ('Y', Y)):
+        if t.device != plan.device:
+            raise ValueError('X, H, bounds, Y and the plan must live on the '
+                             'same device')
+        if not t.is_contiguous():
+            raise ValueError(f'{name} must be contiguous')
+    if Y.dtype != torch.float64:
+        raise TypeError('Y must be float64')
+    if bounds.dtype != torch.float64:
+        raise TypeError('bounds must be float64')
+    x_dtype = _float_dtype(torch, 'X', X)
+    h_dtype = _float_dtype(torch, 'H', H)
+    row_begin, end = _row_range(plan, row_begin, row_end)
+    if n_batch < 0 or k_inner < 0:
+        raise ValueError('n_batch and k_inner must not be negative')
+    if n_levels < 1:
+        raise ValueError(f'n_levels {n_levels}: expected >= 1')
+    if bounds.numel() < 2 * k_inner:
+        raise ValueError(f'bounds holds {bounds.numel()} numbers; k_inner is '
+                         f'{k_inner}')
+    if x_src_fold:
+        _check_fold(plan.n_a, x_src_fold, x_outer_stride, h_outer_stride)
+    # (a launch without batches or ranges reads nothing; one with them reads
+    # whole columns)
+    columns = n_levels if k_inner > 0 else 0
+    _check_reach('X', X, plan.n_a, x_row_stride, x_batch_stride, 1, n_batch,
+                 columns, x_src_fold, x_outer_stride)
+    _check_reach('H', H, plan.n_a, h_row_stride, h_batch_stride, 1, n_batch,
+                 columns, x_src_fold, h_outer_stride)
+    _check_reach('Y', Y, plan.n_b, y_row_stride, y_batch_stride, 1, n_batch,
+                 k_inner)
+    _holds_csr(plan, ('rowptr', 'col', 'val'), 'the layer reduction reads it')
+    args = _LayersArgs()
+    args.A = plan._csr_struct()
+    args.row_begin = row_begin
+    args.row_end = end
+    args.X = X.data_ptr()
+    args.x_dtype = x_dtype
+    args.x_row_stride = int(x_row_stride)
+    args.x_batch_stride = int(x_batch_stride)
+    args.x_src_fold = int(x_src_fold)
+    args.x_outer_stride = int(x_outer_stride)
+    args.n_levels = int(n_levels)
+    args.H = H.data_ptr()
+    args.h_dtype = h_dtype
+    args.h_row_stride = int(h_row_stride)
+    args.h_batch_stride = int(h_batch_stride)
+    args.h_outer_stride = int(h_outer_stride)
+    args.bounds = bounds.data_ptr()
+    args.Y = Y.data_ptr()
+    args.y_row_stride = int(y_row_stride)
+    args.y_batch_stride = int(y_batch_stride)
+    args.n_batch = int(n_batch)
+    args.k_inner = int(k_inner)
+    args.threshold = float(threshold)
+    args.reduce = code
+    _launch(torch, plan, lib.remap_apply_layers, 'remap_apply_layers', args)
+
+
 def _check_basis(torch, plan, name, B, rows):
     """A basis of the vector launch: a contiguous float64 ``(rows, 5)``
     tensor on the plan's device."""
@@ -2864,10 +2983,99 @@ def remap_tensor_levels(plan, dst_grid_dims, field, z, targets, remap_axes,
     become strides (a stride of 0 broadcasts); a group that mixes the two is
     expanded once on the device.  One device only.
     """
-    torch = _torch()
     _one_device(plan, 'the level interpolation')
+
+    def launch(X, Z, T, Y, strides):
+        levels_strided(plan, X, Z, T, Y, threshold=threshold, **strides)
+
+    def outputs(torch, device):
+        T = _levels_targets(torch, targets, device)
+        return T, int(T.numel())
+    return _remap_tensor_columns(plan, dst_grid_dims, field, z, 'z',
+                                 remap_axes, outputs, launch)
+
+
+def _layers_bounds(torch, bounds, device):
+    """``bounds`` -- ``R`` pairs ``(A, B)`` -- as a contiguous float64
+    ``(R, 2)`` tensor on ``device``."""
+    if isinstance(bounds, torch.Tensor):
+        if bounds.device != device:
+            raise ValueError('bounds and the field must live on the same '
+                             'device')
+        if not (bounds.dtype.is_floating_point or
+                bounds.dtype in (torch.int32, torch.int64)):
+            raise ValueError(f'bounds of dtype {bounds.dtype}: expected '
+                             f'numbers')
+        Bd = bounds.to(torch.float64)
+    else:
+        Bd = torch.as_tensor(bounds, dtype=torch.float64).to(device)
+    if Bd.ndim != 2 or Bd.shape[1] != 2 or Bd.shape[0] == 0:
+        raise ValueError(f'bounds of shape {tuple(Bd.shape)}: expected a '
+                         f'non-empty list of (top, bottom) pairs')
+    return Bd.contiguous()
+
+
+def _reduce_code(reduce):
+    if reduce not in REDUCE:
+        raise ValueError(f'reduce {reduce!r}: expected one of '
+                         f'{sorted(REDUCE)}')
+    return REDUCE[reduce]
+
+
+def remap_tensor_layers(plan, dst_grid_dims, field, thickness, bounds,
+                        remap_axes, threshold=0.0, reduce='mean'):
+    """
+    :func:`remap_tensor` of a field averaged (``reduce='mean'``) or
+    integrated (``'integral'``) over depth ranges (:mod:`pyremap_amd.layers`;
+    layer means, heat content): the LAST axis of ``field`` is its level axis,
+    ``thickness`` the thickness of every layer (``layerThickness``),
+    ``bounds`` the ``R`` ranges ``(A, B)`` asked for, depths positive
+    downward from the top of each column, in any order, ``B = inf`` "to the
+    bottom".  Every entry of a row reduces its source column over the range
+    first -- every layer weighted by its overlap with the range, a column
+    that ends above the range skipped as a NaN is -- and enters the masked,
+    renormalised sum then, in ONE launch per :func:`field_layout` launch
+    (``remap_apply_layers``).  The result has the shape and axis order of
+    :func:`remap_tensor` with ``R`` in place of ``n_levels``; float64, NaN
+    where ``valid <= threshold``.
+
+    ``thickness`` broadcasts as ``z`` of :func:`remap_tensor_levels` does:
+    the level axis at full extent, the remap axes at full extent or all 1,
+    every other axis at the field's extent or 1 (a time-invariant thickness),
+    through strides of 0.  One device only.
+    """
+    _one_device(plan, 'the layer reduction')
+    _reduce_code(reduce)
+
+    def launch(X, H, Bd, Y, strides):
+        strides = {('h' + name[1:] if name.startswith('z_') else name): s
+                   for name, s in strides.items()}
+        layers_strided(plan, X, H, Bd, Y, threshold=threshold, reduce=reduce,
+                       **strides)
+
+    def outputs(torch, device):
+        Bd = _layers_bounds(torch, bounds, device)
+        return Bd, int(Bd.shape[0])
+    return _remap_tensor_columns(plan, dst_grid_dims, field, thickness,
+                                 'thickness', remap_axes, outputs, launch)
+
+
+def _remap_tensor_columns(plan, dst_grid_dims, field, z, zname, remap_axes,
+                          outputs, launch):
+    """
+    What :func:`remap_tensor_levels` and :func:`remap_tensor_layers` share: a
+    field whose LAST axis is its level axis, reduced column by column inside
+    the apply with a companion ``z`` (called ``zname`` in messages: the level
+    coordinate, the layer thicknesses) that broadcasts over the field.  The
+    checks, the routes and strides of :func:`field_layout` and the launches.
+    ``outputs(torch, device)``: the float64 device tensor of what is asked
+    for (targets; ranges) and the inner extent of the result (their number);
+    ``launch(X, Z, T, Y, strides)``: one launch, the companion's strides
+    under the names ``z_row_stride``, ``z_batch_stride``, ``z_outer_stride``.
+    """
+    torch = _torch()
     ndim = field.ndim
-    for name, t in (('field', field), ('z', z)):
+    for name, t in (('field', field), (zname, z)):
         if not isinstance(t, torch.Tensor):
             raise ValueError(f'{name} must be a device tensor')
         if not t.dtype.is_floating_point:
@@ -2882,9 +3090,10 @@ def remap_tensor_levels(plan, dst_grid_dims, field, z, targets, remap_axes,
         raise ValueError('the last axis of the field is its level axis: it '
                          'cannot be a remap axis')
     if z.ndim != ndim:
-        raise ValueError(f'z has {z.ndim} axes, the field {ndim}')
+        raise ValueError(f'{zname} has {z.ndim} axes, the field {ndim}')
     if z.device != field.device:
-        raise ValueError('z and the field must live on the same device')
+        raise ValueError(f'{zname} and the field must live on the same '
+                         f'device')
     shape = [int(s) for s in field.shape]
     n_levels = shape[-1]
     if n_levels < 1:
@@ -2895,16 +3104,15 @@ def remap_tensor_levels(plan, dst_grid_dims, field, z, targets, remap_axes,
         full_only = ax == ndim - 1
         if have != want and (full_only or have != 1):
             raise ValueError(
-                f'z of shape {tuple(z.shape)} against a field of shape '
+                f'{zname} of shape {tuple(z.shape)} against a field of shape '
                 f'{tuple(field.shape)}: axis {ax} must have extent {want}' +
                 ('' if full_only else ' or 1'))
     if not all(z_cells) and any(int(z.shape[ax]) != 1 for ax in remap_axes):
         raise ValueError(
-            f'z of shape {tuple(z.shape)}: the remap axes {remap_axes} must '
-            f'all have the field\'s extent or all have extent 1')
+            f'{zname} of shape {tuple(z.shape)}: the remap axes {remap_axes} '
+            f'must all have the field\'s extent or all have extent 1')
     z_cells = all(z_cells)
-    T = _levels_targets(torch, targets, field.device)
-    L = int(T.numel())
+    T, L = outputs(torch, field.device)
     if field.dtype not in (torch.float64, torch.float32):
         field = field.to(torch.float64)
     if z.dtype not in (torch.float64, torch.float32):
@@ -2980,8 +3188,8 @@ def remap_tensor_levels(plan, dst_grid_dims, field, z, targets, remap_axes,
     Y = torch.empty(y_shape, dtype=torch.float64, device=field.device)
     Zs = [Zl for Zl, in _launch_rows(n_launch if lead_full else 1, Z)]
     for li, (Xl, Yl) in enumerate(_launch_rows(n_launch, X, Y)):
-        levels_strided(plan, Xl, Zs[li if lead_full else 0], T, Yl,
-                       n_levels=nl, k_inner=L, threshold=threshold, **strides)
+        launch(Xl, Zs[li if lead_full else 0], T, Yl,
+               dict(strides, n_levels=nl, k_inner=L))
     if back is None:
         return Y
     return Y.reshape(back[0]).permute(back[1]).contiguous()

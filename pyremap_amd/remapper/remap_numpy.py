@@ -267,6 +267,9 @@ def _check_levels_alone(remapper):
     if getattr(remapper, 'vector_pairs', None):
         raise NotImplementedError(
             'levels together with vector_pairs is not served')
+    if getattr(remapper, 'layers', None) is not None:
+        raise NotImplementedError(
+            'levels together with layers is not served: one or the other')
     if getattr(remapper, '_process_group', None) is not None or \
             len(getattr(remapper, 'devices', None) or ()) > 1:
         raise NotImplementedError(
@@ -279,15 +282,18 @@ class _LevelCoordinate:
     (``Remapper.levels``): read and uploaded once, when the first
     interpolated variable asks for it."""
 
+    #: what error messages call the variable
+    role = 'levels coordinate'
+
     def __init__(self, name, da, src_dims, targets, out_dim):
         missing = [dim for dim in src_dims if dim not in da.dims]
         if missing:
             raise ValueError(
-                f'the levels coordinate {name!r} has dims {tuple(da.dims)}: '
+                f'the {self.role} {name!r} has dims {tuple(da.dims)}: '
                 f'it lacks the source dims {missing}')
         if da.dims[-1] in src_dims:
             raise ValueError(
-                f'the levels coordinate {name!r} has dims {tuple(da.dims)}: '
+                f'the {self.role} {name!r} has dims {tuple(da.dims)}: '
                 f'its last dim is the level dim, and {da.dims[-1]!r} is a '
                 f'source dim')
         self.name, self.da = name, da
@@ -295,8 +301,8 @@ class _LevelCoordinate:
         self.level_dim = self.dims[-1]
         if out_dim == self.level_dim:
             raise ValueError(
-                f'out_dim {out_dim!r} is the level dim of the coordinate '
-                f'{name!r}: the target levels need a dim of their own')
+                f'out_dim {out_dim!r} is the level dim of the {self.role} '
+                f'{name!r}: the results need a dim of their own')
         self.targets, self.out_dim = targets, out_dim
         self._device = None
         self._targets = None
@@ -307,6 +313,17 @@ class _LevelCoordinate:
         not."""
         return da.name != self.name and \
             all(dim in da.dims for dim in self.dims)
+
+    def remap(self, plan, dst_grid_dims, field, z, targets, remap_axes,
+              threshold):
+        return engine.remap_tensor_levels(plan, dst_grid_dims, field, z,
+                                          targets, remap_axes,
+                                          threshold=threshold)
+
+    def out_coords(self):
+        """What a variable gains with the target dim: the target levels."""
+        return {self.out_dim: {'dims': (self.out_dim,),
+                               'data': self.targets}}
 
     def out_dims(self, dims):
         """``dims`` with the target dim in place of the level dim."""
@@ -344,9 +361,9 @@ class _LevelCoordinate:
         z, targets = self.on_device(plan, dims)
         remap_axes = [axis for axis, dim in enumerate(dims)
                       if dim in src_dims]
-        y_d = engine.remap_tensor_levels(
+        y_d = self.remap(
             plan, remapper._ds_map.dst_grid_dims, field, z, targets,
-            remap_axes, threshold=0.0 if threshold is None else threshold)
+            remap_axes, 0.0 if threshold is None else threshold)
         # the axis order of the result as it stands, and as it is asked for
         have = _result_dims(dims, remapper)
         want = _result_dims(list(da.dims), remapper)
@@ -381,6 +398,121 @@ def _level_coordinate(remapper, ds):
             f'Dataset')
     return _LevelCoordinate(name, ds[name], remapper.src_descriptor.dims,
                             targets, out_dim)
+
+
+def _check_layers(remapper):
+    """The Remapper's ``layers`` as ``(thickness, bounds, out_dim, reduce)``
+    -- ``bounds`` a float64 ``(R, 2)`` array -- or None, and what it does not
+    go together with."""
+    spec = getattr(remapper, 'layers', None)
+    if spec is None:
+        return None
+    wording = "layers must be None or dict(thickness='layerThickness', " \
+        "bounds=[(top, bottom), ...], out_dim='depthRange', reduce='mean')"
+    if not isinstance(spec, dict) or \
+            not {'thickness', 'bounds'} <= set(spec) or \
+            not set(spec) <= {'thickness', 'bounds', 'out_dim', 'reduce'}:
+        raise TypeError(f'{wording}, not {spec!r}')
+    thickness = spec['thickness']
+    out_dim = spec.get('out_dim', 'depthRange')
+    reduce = spec.get('reduce', 'mean')
+    if not isinstance(thickness, str) or not isinstance(out_dim, str):
+        raise TypeError(f'{wording}: thickness and out_dim are names, not '
+                        f'{thickness!r} and {out_dim!r}')
+    if not isinstance(reduce, str):
+        raise TypeError(f'{wording}: reduce is a name, not {reduce!r}')
+    bounds = spec['bounds']
+    try:
+        if isinstance(bounds, (str, bytes)):
+            raise TypeError
+        bounds = np.asarray(bounds, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise TypeError(f'{wording}: bounds is a list of pairs of numbers, '
+                        f'not {bounds!r}') from None
+    if bounds.ndim == 1 and bounds.size == 0:
+        raise ValueError('layers names no depth range: bounds is empty')
+    if bounds.ndim != 2 or bounds.shape[1] != 2:
+        raise TypeError(f'{wording}: bounds is a list of pairs of numbers, '
+                        f'not {spec["bounds"]!r}')
+    if bounds.shape[0] == 0:
+        raise ValueError('layers names no depth range: bounds is empty')
+    if reduce not in engine.REDUCE:
+        raise ValueError(f'layers: reduce {reduce!r}: expected one of '
+                         f'{sorted(engine.REDUCE)}')
+    _check_layers_alone(remapper)
+    return thickness, bounds, out_dim, reduce
+
+
+def _check_layers_alone(remapper):
+    """What the layer reduction does not go together with."""
+    if getattr(remapper, 'limiter', None) is not None:
+        raise NotImplementedError(
+            'layers together with a limiter is not served: one or the other')
+    if getattr(remapper, 'sgs_frac', None) is not None:
+        raise NotImplementedError(
+            'layers together with sgs_frac is not served')
+    if getattr(remapper, 'vector_pairs', None):
+        raise NotImplementedError(
+            'layers together with vector_pairs is not served')
+    if getattr(remapper, 'levels', None) is not None:
+        raise NotImplementedError(
+            'layers together with levels is not served: one or the other')
+    if getattr(remapper, '_process_group', None) is not None or \
+            len(getattr(remapper, 'devices', None) or ()) > 1:
+        raise NotImplementedError(
+            'layers serves one device: not with devices=[...] or a process '
+            'group')
+
+
+class _LayerThickness(_LevelCoordinate):
+    """The layer thicknesses of one ``remap_numpy`` / ``ncremap`` call
+    (``Remapper.layers``): the companion variable of the reduced variables,
+    as the level coordinate is of the interpolated ones.  ``targets`` holds
+    the ``(R, 2)`` bounds."""
+
+    role = 'layers thickness'
+
+    def __init__(self, name, da, src_dims, bounds, out_dim, reduce):
+        super().__init__(name, da, src_dims, bounds, out_dim)
+        self.reduce = reduce
+
+    def remap(self, plan, dst_grid_dims, field, z, targets, remap_axes,
+              threshold):
+        return engine.remap_tensor_layers(plan, dst_grid_dims, field, z,
+                                          targets, remap_axes,
+                                          threshold=threshold,
+                                          reduce=self.reduce)
+
+    def out_coords(self):
+        """(the bounds are a variable of the result, not a coordinate: their
+        second dim is no dim of a reduced variable)"""
+        return {}
+
+    def bounds_variable(self):
+        """``(name, DataArray)``: the float64 ``(out_dim, 'nbnd')`` variable
+        the result gains."""
+        return self.out_dim + '_bnds', _array_class(self.da)(
+            self.targets.copy(), dims=(self.out_dim, 'nbnd'))
+
+
+def _layer_thickness(remapper, ds):
+    """None without ``Remapper.layers``; else the thickness variable of
+    ``ds`` (``KeyError`` naming it if ``ds`` has none)."""
+    spec = _check_layers(remapper)
+    if spec is None:
+        return None
+    name, bounds, out_dim, reduce = spec
+    if not _is_dataset(ds) or name not in ds.variables:
+        raise KeyError(
+            f'layers names the thickness variable {name!r}, which is not in '
+            f'the Dataset')
+    for taken in (out_dim, out_dim + '_bnds'):
+        if taken in ds.variables or taken in ds.sizes:
+            raise ValueError(
+                f'out_dim {out_dim!r}: {taken!r} is already a variable or a '
+                f'dim of the Dataset')
+    return _LayerThickness(name, ds[name], remapper.src_descriptor.dims,
+                           bounds, out_dim, reduce)
 
 
 def _check_vector_alone(remapper):
@@ -511,7 +643,12 @@ def _remap_numpy(remapper, ds, renormalization_threshold):
         raise ValueError('No mapping file has been defined')
     # (before anything is loaded: a refusal or a missing fraction variable
     # costs nothing)
+    lay = _layer_thickness(remapper, ds)
     lev = _level_coordinate(remapper, ds)
+    if lay is not None:
+        # (not together with levels: the reduced variables take the
+        # interpolated variables' way through the call)
+        lev = lay
     pairs = _check_vector_pairs(remapper)
     sgs = _sgs_fraction(remapper, ds)
     vec = _vector_pairs(remapper, ds, pairs)
@@ -547,6 +684,9 @@ def _remap_numpy(remapper, ds, renormalization_threshold):
                            renormalization_threshold, sgs=sgs, vec=vec,
                            lev=lev),
                 keep_attrs=True)
+        if lay is not None:
+            name, bnds = lay.bounds_variable()
+            result[name] = bnds
     else:
         raise TypeError('ds not an xarray Dataset or DataArray.')
 
@@ -725,7 +865,7 @@ def _plan_data_array(da, remapper, lev=None):
         dims = lev.out_dims(dims)
         coords = {name: coord for name, coord in coords.items()
                   if lev.level_dim not in coord['dims']}
-        coords[lev.out_dim] = {'dims': (lev.out_dim,), 'data': lev.targets}
+        coords.update(lev.out_coords())
     return remap_axes, dims, coords
 
 
@@ -752,7 +892,7 @@ def _lazy_dataset(remapper, ds, renormalization_threshold, sgs=None,
             first = remap_axes[0]
             sizes = list(da.shape)
             if lev is not None and lev.interpolates(da):
-                sizes[da.dims.index(lev.level_dim)] = lev.targets.size
+                sizes[da.dims.index(lev.level_dim)] = len(lev.targets)
             shape = sizes[:first] + \
                 [int(s) for s in remapper._ds_map.dst_grid_dims] + \
                 [size for axis, size in enumerate(sizes)
@@ -882,9 +1022,10 @@ def _batches(remapper, ds, names):
             plan is None or hasattr(plan, 'shards') or \
             getattr(remapper, 'limiter', None) is not None or \
             getattr(remapper, 'sgs_frac', None) is not None or \
-            getattr(remapper, 'levels', None) is not None:
-        # (a limited, fraction-weighted or interpolated variable takes the
-        # whole-array route, one at a time)
+            getattr(remapper, 'levels', None) is not None or \
+            getattr(remapper, 'layers', None) is not None:
+        # (a limited, fraction-weighted, interpolated or depth-reduced
+        # variable takes the whole-array route, one at a time)
         return {}
     groups = {}
     src_dims = remapper.src_descriptor.dims
@@ -1152,6 +1293,62 @@ def _remap_array_levels(remapper, in_field, z, targets, remap_axes,
     out = engine.remap_tensor_levels(
         plan, remapper._ds_map.dst_grid_dims, field, coord, targets,
         remap_axes, threshold=threshold)
+    if on_device:
+        return out
+    out = out.cpu().numpy()
+    return np.ma.masked_array(out, mask=np.isnan(out))
+
+
+def _check_layer_arrays(field, thickness, bounds, reduce):
+    """``field`` and ``thickness`` of one kind (``TypeError``) and one number
+    of axes, ranges that are pairs and a reduction that exists
+    (``ValueError``); no device is needed to be told so."""
+    tensors = [type(f).__module__.split('.')[0] == 'torch'
+               for f in (field, thickness)]
+    if tensors[0] != tensors[1]:
+        raise TypeError('field and thickness must both be device tensors or '
+                        'both host arrays')
+    ndims = [len(getattr(f, 'shape', np.shape(f))) for f in (field, thickness)]
+    if ndims[0] != ndims[1]:
+        raise ValueError(f'thickness has {ndims[1]} axes, the field '
+                         f'{ndims[0]}')
+    shape = tuple(getattr(bounds, 'shape', np.shape(bounds)))
+    if len(shape) != 2 or shape[1] != 2 or shape[0] == 0:
+        raise ValueError('bounds must be a non-empty list of (top, bottom) '
+                         'pairs')
+    if reduce not in engine.REDUCE:
+        raise ValueError(f'reduce {reduce!r}: expected one of '
+                         f'{sorted(engine.REDUCE)}')
+
+
+def _remap_array_layers(remapper, in_field, thickness, bounds, remap_axes,
+                        renormalization_threshold, reduce='mean'):
+    """
+    One array through ``engine.remap_tensor_layers``: device tensors in,
+    device tensor out (NaN where masked); numpy in, ``numpy.ma.MaskedArray``
+    out with the mask taken from NaN.  ``None`` threshold means 0.0.  The
+    level axis is the last.
+    """
+    _check_layers_alone(remapper)
+    _check_layer_arrays(in_field, thickness, bounds, reduce)
+    torch = engine.require_gpu()
+    plan = remapper._matrix
+    threshold = 0.0 if renormalization_threshold is None else \
+        float(renormalization_threshold)
+    on_device = isinstance(in_field, torch.Tensor)
+    if on_device:
+        field, h = in_field.to(plan.device), thickness.to(plan.device)
+    else:
+        field = _host_values(torch, in_field, plan.device)
+        h = _host_values(torch, thickness, plan.device)
+    remap_axes = [int(a) % field.ndim for a in remap_axes]
+    if isinstance(bounds, torch.Tensor):
+        bounds = bounds.to(plan.device)
+    else:
+        bounds = np.asarray(bounds, dtype=np.float64)
+    out = engine.remap_tensor_layers(
+        plan, remapper._ds_map.dst_grid_dims, field, h, bounds, remap_axes,
+        threshold=threshold, reduce=reduce)
     if on_device:
         return out
     out = out.cpu().numpy()

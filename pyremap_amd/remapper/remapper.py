@@ -9,6 +9,8 @@ Added on top of the reference surface: ``remap`` / ``remap_file`` aliases
 knobs and :meth:`from_triplets` for mapping data that is already in memory.
 """
 from pyremap_amd.remapper.remap_numpy import (
+    _check_layer_arrays,
+    _check_layers_alone,
     _check_level_arrays,
     _check_levels_alone,
     _check_limiter,
@@ -17,6 +19,7 @@ from pyremap_amd.remapper.remap_numpy import (
     _check_vector_fields,
     _load_mapping,
     _remap_numpy,
+    _remap_array_layers,
     _remap_array_levels,
     _remap_array_sgs,
     _remap_array_vector,
@@ -83,6 +86,20 @@ class Remapper:
         (:mod:`pyremap_amd.levels`): the field at a depth, a column that
         does not reach the depth skipped as a NaN is;
         :meth:`remap_array_levels` is the array-level entry
+    layers : None or dict
+        set after construction (default ``None``: nothing changes):
+        ``dict(thickness='layerThickness', bounds=[(0., 700.), (700., 2000.),
+        (0., inf)], out_dim='depthRange', reduce='mean')``, the name of the
+        Dataset variable that holds the layer thicknesses (its last dim is
+        the level dim; it may lack dims the fields have, such as ``Time``),
+        the depth ranges asked for -- positive downward from the top of each
+        column, ``inf``: to the bottom --, the name of their dim (default
+        ``'depthRange'``) and ``'mean'`` (default) or ``'integral'``.
+        ``remap_numpy`` and ``ncremap`` then reduce every variable whose dims
+        contain the thickness variable's over the ranges, column by column
+        inside the remap (:mod:`pyremap_amd.layers`): the field over a depth
+        range, a column that ends above the range skipped as a NaN is;
+        :meth:`remap_array_layers` is the array-level entry
     """
 
     def __init__(
@@ -147,6 +164,18 @@ class Remapper:
         #: variable itself, and variables that lack one of its dims, are
         #: remapped as without it.
         self.levels = None
+        #: depth-range means and integrals (None | dict(thickness=
+        #: 'layerThickness', bounds=[(top, bottom), ...], out_dim=
+        #: 'depthRange', reduce='mean' | 'integral')), honoured by
+        #: remap_numpy and ncremap: every remapped variable whose dims contain
+        #: all dims of the thickness variable -- its last dim is the level
+        #: dim -- is reduced over the ranges column by column inside the
+        #: remap, in one launch, and comes out with out_dim (of extent
+        #: len(bounds)) in place of the level dim (pyremap_amd.layers); the
+        #: output gains the float64 variable <out_dim>_bnds of dims (out_dim,
+        #: 'nbnd') that holds the bounds.  The thickness variable itself, and
+        #: variables that lack one of its dims, are remapped as without it.
+        self.layers = None
         self.src_scrip_filename = 'src_mesh.nc'
         self.dst_scrip_filename = 'dst_mesh.nc'
         self.format = 'NETCDF3_64BIT_DATA'
@@ -524,6 +553,43 @@ class Remapper:
         return _remap_array_levels(self, field, z, targets, remap_axes,
                                    renormalization_threshold,
                                    level_axis=level_axis)
+
+    def remap_array_layers(self, field, thickness, bounds, remap_axes,
+                           renormalization_threshold=None, reduce='mean'):
+        """
+        :meth:`remap_array` of a field OVER DEPTH RANGES (layer means, heat
+        content): the last axis of ``field`` is its level axis, layer ``k``
+        is ``thickness[..., k]`` thick -- another thickness and another
+        bottom in every cell, ``layerThickness`` of MPAS-Ocean, NaN or 0
+        where a layer is not there -- and the result holds, for each of the
+        ``R`` ranges ``bounds = [(top, bottom), ...]`` (depths positive
+        downward from the top of each column, ``inf``: to the bottom), the
+        thickness-weighted mean of the field over the range
+        (``reduce='mean'``) or its integral (``'integral'``).  Every entry of
+        a row reduces its source column first (a range may cut through a
+        layer; a column that ends inside the range contributes what it has;
+        one that ends above it is skipped exactly as a NaN is) and enters the
+        masked, renormalised sum then, in one launch
+        (:mod:`pyremap_amd.layers` has the definition to the bit).  Device
+        tensors in -> device tensor out, NaN where masked; numpy in ->
+        ``numpy.ma.MaskedArray`` out, the mask taken from NaN.
+
+        The result has the shape and axis order of :meth:`remap_array` with
+        ``R`` in place of the number of levels.  ``thickness`` has
+        ``field``'s number of axes, the level axis at full extent, the remap
+        axes at full extent or all 1 and every other axis at the field's
+        extent or 1 (a time-invariant thickness).  A destination cell is
+        masked where the valid weight is not above
+        ``renormalization_threshold`` (``None``: 0.0).
+        """
+        if self.map_filename is None:
+            raise ValueError('No mapping file has been defined')
+        _check_layers_alone(self)
+        _check_layer_arrays(field, thickness, bounds, reduce)
+        _load_mapping(self)
+        return _remap_array_layers(self, field, thickness, bounds,
+                                   remap_axes, renormalization_threshold,
+                                   reduce=reduce)
 
     # pyremap-1.x names used by BASELINE.json's north_star
     remap = remap_numpy
