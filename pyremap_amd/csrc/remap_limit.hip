@@ -327,4 +327,13 @@ int remap_limit_rows(const struct remap_limit_args *args, void *stream)
     return remap::limit_rows(args, static_cast<hipStream_t>(stream));
 }
 
+#ifdef REMAP_ROWPASS_WIDE_INDEX
+// the mark of the tests' wide-index build (rowpass::narrow_index); the
+// product does not define it and include/remap_hip.h does not declare it
+REMAP_API int remap_rowpass_wide_index(void)
+{
+    return 1;
+}
+#endif
+
 }  // extern "C"

@@ -113,11 +113,19 @@ inline dim3 rowlane_grid(int64_t total)
 }
 
 // the type the rowlane form splits its flat index in: 32 bits where total
-// fits (the 64-bit division is a long instruction sequence)
+// fits (the 64-bit division is a long instruction sequence).
+// REMAP_ROWPASS_WIDE_INDEX: the tests' build of the library
+// (_build.build_wide_index_library), which takes the 64-bit instantiations on
+// problems of any size; the product is built without it.
 template <typename P>
 inline bool narrow_index(const P &p)
 {
+#ifdef REMAP_ROWPASS_WIDE_INDEX
+    (void)p;
+    return false;
+#else
     return p.total <= static_cast<int64_t>(UINT32_MAX);
+#endif
 }
 
 // Element offsets of source cell a in N arrays of row strides ld and outer

@@ -475,6 +475,18 @@ def load_library():
                 f'run `python -c "import __graft_entry__ as g; g.build()"` '
                 f'on a machine with ROCm')
         _build.build_library()
+    _lib = open_library(path)
+    return _lib
+
+
+def open_library(path):
+    """
+    ``ctypes.CDLL(path)``, checked against ``EXPORTS`` and the ABI version,
+    with every entry point's restype and argtypes set.  ``load_library`` keeps
+    the one the package works with; a second library of the same ABI (the
+    tests' wide-index build, ``_build.WIDE_LIB_PATH``) is opened with this and
+    put in its place by setting ``engine._lib``.
+    """
     lib = ctypes.CDLL(path)
     missing = [name for name in EXPORTS if not hasattr(lib, name)]
     if missing:
@@ -775,7 +787,6 @@ def load_library():
         raise EngineError(
             f'{path} has ABI {lib.remap_abi_version()}, expected '
             f'{ABI_VERSION}; rebuild it')
-    _lib = lib
     return lib
 
 

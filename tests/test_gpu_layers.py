@@ -11,8 +11,9 @@ order (the library is built without contraction), and every NaN written is
 the one quiet NaN: every comparison but the last is an equality of the BYTES
 of ``Y``.
 
-The 64-bit index instantiations (more than 2^32 elements a launch) have no
-switch that forces them on a small problem: they are compiled and not covered.
+The 64-bit index instantiations (more than 2^32 elements a launch) run in
+tests/test_gpu_wide_index.py, on a build of the library that takes them on
+small problems.
 """
 import os
 
@@ -282,6 +283,52 @@ def test_pointers_off_the_16_byte_grid():
             assert cases.same_bytes(got, ref), (dtype, off)
 
 
+def test_split_plan_is_served_as_one_matrix():
+    """Pole caps: the two outer lines of a 45 x 90 grid take a whole source
+    line (180 entries) among rows of 4, and the plan is applied as short and
+    long rows (``plan._split``); the layers launch walks the unsplit CSR."""
+    torch = _torch()
+    from pyremap_amd import engine, layers
+    rng = np.random.default_rng(21)
+    ny, nx, n_a = 45, 90, 90 * 180
+    rows = []
+    for j in range(ny):
+        for i in range(nx):
+            if j in (0, ny - 1):
+                rows.append(list(range((j > 0) * (n_a - 180),
+                                       (j > 0) * (n_a - 180) + 180)))
+            else:
+                base = 2 * j * 180 + 2 * i
+                rows.append([base, base + 1, base + 180, base + 181])
+    indptr, indices, data = cases.cases._csr(rows, rng)
+    data = np.abs(data)
+    plan = engine.RemapPlan.from_csr(indptr, indices, data,
+                                     np.ones(ny * nx), n_a, device='cuda:0')
+    plan.auto_schedule([ny, nx])
+    assert plan._split is not None and plan.max_row_nnz == 180
+    B, nl = 2, 6
+    X, H = cases.shared_case(B, nl, n_a=n_a, form='time')
+    AB = np.array([(0.0, 10.0), (20.0, float('inf')), (60.0, 100.0),
+                   (1000.0, 2000.0)])
+    for reduce in ('mean', 'integral'):
+        ref = layers.apply(indptr, indices, data, X, H, AB, 0.0,
+                           reduce)[0]                       # (n_b, B, R)
+        assert np.isnan(ref).any() and not np.isnan(ref).all()
+        got = engine.remap_tensor_layers(
+            plan, [ny, nx], torch.from_numpy(X.copy()).to('cuda:0'),
+            torch.from_numpy(H.copy()).to('cuda:0'), AB, [0],
+            reduce=reduce).cpu().numpy()
+        assert cases.same_bytes(got, ref.reshape(ny, nx, B, len(AB)))
+        got = engine.remap_tensor_layers(
+            plan, [ny, nx],
+            torch.from_numpy(np.array(X.transpose(1, 0, 2), order='C'))
+            .to('cuda:0'),
+            torch.from_numpy(np.array(H.transpose(1, 0, 2), order='C'))
+            .to('cuda:0'), AB.tolist(), [1], reduce=reduce).cpu().numpy()
+        assert cases.same_bytes(
+            got, ref.transpose(1, 0, 2).reshape(B, ny, nx, len(AB)))
+
+
 # ---------------------------------------------------------------------------
 # 2. against independent code
 # ---------------------------------------------------------------------------
@@ -407,6 +454,69 @@ def test_bad_arguments_raise_before_the_launch():
     # and a launch that is fine: x = 0 on layers of 1, both ranges reached
     call(plan, x, h, b, y, **strides)
     torch.cuda.synchronize()
+    lens = np.diff(plan.to_host_csr()[0])
+    host = y.cpu().numpy()
+    assert np.all(host[lens > 0] == 0.0) and np.all(np.isnan(host[lens == 0]))
+
+
+def test_c_abi_argument_checks():
+    """Each returns REMAP_ERR_ARG with device pointers in place: the six
+    checks of the entry point's own and the shared ones.  None of them
+    launches."""
+    import ctypes
+    torch = _torch()
+    from pyremap_amd import engine
+    lib = engine.load_library()
+    plan, _, _, _ = _plan()
+    k, R = 4, 2
+    x = torch.zeros((N_A, k), dtype=torch.float64, device='cuda:0')
+    h = torch.ones((N_A, k), dtype=torch.float64, device='cuda:0')
+    b = torch.tensor([0.0, 1.5, 1.0, 9.0], dtype=torch.float64,
+                     device='cuda:0')
+    y = torch.full((N_B, R), 2.0, dtype=torch.float64, device='cuda:0')
+
+    def good():
+        a = engine._LayersArgs()
+        a.A.n_rows, a.A.n_cols, a.A.nnz = plan.n_b, plan.n_a, plan.nnz
+        a.A.rowptr, a.A.col = plan.rowptr.data_ptr(), plan.col.data_ptr()
+        a.A.val = plan.val.data_ptr()
+        a.row_begin, a.row_end = 0, plan.n_b
+        a.X, a.H, a.Y = x.data_ptr(), h.data_ptr(), y.data_ptr()
+        a.bounds = b.data_ptr()
+        a.x_dtype = a.h_dtype = engine.DTYPE_F64
+        a.x_row_stride = a.h_row_stride = k
+        a.y_row_stride = R
+        a.n_levels = k
+        a.n_batch, a.k_inner = 1, R
+        a.reduce = engine.REDUCE['mean']
+        return a
+    bad = [('n_levels', 0), ('n_levels', -2), ('h_dtype', -1),
+           ('h_dtype', 2), ('reduce', 2), ('reduce', -1),
+           ('h_row_stride', -1), ('h_batch_stride', -1), ('H', None),
+           ('bounds', None), ('X', None), ('Y', None),
+           ('row_end', plan.n_b + 1), ('row_begin', -1), ('n_batch', -1),
+           ('x_dtype', 5), ('x_row_stride', -1), ('x_batch_stride', -1),
+           ('y_row_stride', -1), ('y_batch_stride', -1), ('x_src_fold', 7),
+           ('k_inner', 1 << 62)]
+    for name, value in bad:
+        a = good()
+        setattr(a, name, value)
+        assert lib.remap_apply_layers(ctypes.byref(a), None) == -1, name
+        msg = lib.remap_last_error()
+        assert msg and b'remap_apply_layers' in msg, name
+    a = good()
+    a.A.val = None
+    assert lib.remap_apply_layers(ctypes.byref(a), None) == -1
+    a = good()
+    a.x_src_fold, a.h_outer_stride = 20, -1
+    assert lib.remap_apply_layers(ctypes.byref(a), None) == -1
+    assert b'h_outer_stride' in lib.remap_last_error()
+    torch.cuda.synchronize()
+    assert bool((y == 2.0).all())         # nothing ran
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert lib.remap_apply_layers(ctypes.byref(good()), stream) == 0
+    torch.cuda.synchronize()
+    # (x = 0 on layers of 1: both ranges are reached)
     lens = np.diff(plan.to_host_csr()[0])
     host = y.cpu().numpy()
     assert np.all(host[lens > 0] == 0.0) and np.all(np.isnan(host[lens == 0]))

@@ -9,6 +9,10 @@ made on the GPU.
 Bytes.  Kernel and statement perform the same IEEE operations in the same
 order (the library is built without contraction), and every NaN written is
 the one quiet NaN: every comparison is an equality of the BYTES of ``Y``.
+
+The 64-bit index instantiations (more than 2^32 elements a launch) run in
+tests/test_gpu_wide_index.py, on a build of the library that takes them on
+small problems.
 """
 import os
 

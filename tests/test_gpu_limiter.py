@@ -6,7 +6,10 @@ place, and ``limiter='clip'`` / ``'caas'`` end to end through the Remapper on
 maps made on the GPU.
 
 Bounds.  The clip is comparisons and copies: every comparison with
-``limiter.clip`` is an equality of BYTES (``Y``, ``lo`` and ``hi``).
+``limiter.clip`` is an equality of BYTES (``Y``, ``lo`` and ``hi``).  The
+64-bit index instantiations (more than 2^32 elements a launch) run in
+tests/test_gpu_wide_index.py, on a build of the library that takes them on
+small problems.
 
 CAAS.  ``n`` terms added in any order carry at most ``(n - 1) u sum|t|``,
 ``u = 2^-53``.  The device sums M = sum w y, Mc = sum w yc and C = sum w cap
@@ -313,6 +316,64 @@ def test_bad_bounds_raise_before_the_launch():
                              **strides)
     torch.cuda.synchronize()
     assert bool((y == 2.0).all())         # nothing ran
+
+
+def test_c_abi_argument_checks():
+    """Each returns REMAP_ERR_ARG with device pointers in place.  None of
+    them launches."""
+    import ctypes
+    torch = _torch()
+    from pyremap_amd import engine
+    lib = engine.load_library()
+    plan, _, _ = _plan()
+    k = 4
+    x = torch.zeros((N_A, k), dtype=torch.float64, device='cuda:0')
+    y = torch.full((N_B, k), 2.0, dtype=torch.float64, device='cuda:0')
+    lo = torch.full((N_B, k), 2.0, dtype=torch.float64, device='cuda:0')
+    hi = torch.full((N_B, k), 2.0, dtype=torch.float64, device='cuda:0')
+
+    def good():
+        a = engine._LimitArgs()
+        a.A.n_rows, a.A.n_cols, a.A.nnz = plan.n_b, plan.n_a, plan.nnz
+        a.A.rowptr, a.A.col = plan.rowptr.data_ptr(), plan.col.data_ptr()
+        a.row_begin, a.row_end = 0, plan.n_b
+        a.X, a.Y = x.data_ptr(), y.data_ptr()
+        a.lo, a.hi = lo.data_ptr(), hi.data_ptr()
+        a.x_dtype = engine.DTYPE_F64
+        a.x_row_stride = a.y_row_stride = k
+        a.n_batch, a.k_inner = 1, k
+        return a
+    bad = [('X', None), ('Y', None), ('row_end', plan.n_b + 1),
+           ('row_begin', -1), ('row_begin', plan.n_b + 1), ('n_batch', -1),
+           ('k_inner', -1), ('x_dtype', 5), ('x_dtype', -1),
+           ('x_row_stride', -1), ('x_batch_stride', -1),
+           ('y_row_stride', -1), ('y_batch_stride', -1), ('x_src_fold', 7),
+           ('x_src_fold', -1), ('k_inner', 1 << 62)]
+    for name, value in bad:
+        a = good()
+        setattr(a, name, value)
+        assert lib.remap_limit_rows(ctypes.byref(a), None) == -1, name
+        msg = lib.remap_last_error()
+        assert msg and b'remap_limit_rows' in msg, name
+    a = good()
+    a.A.rowptr = None
+    assert lib.remap_limit_rows(ctypes.byref(a), None) == -1
+    a = good()
+    a.x_src_fold, a.x_outer_stride = 20, -1
+    assert lib.remap_limit_rows(ctypes.byref(a), None) == -1
+    assert lib.remap_limit_rows(None, None) == -1
+    torch.cuda.synchronize()
+    assert all(bool((t == 2.0).all()) for t in (y, lo, hi))   # nothing ran
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert lib.remap_limit_rows(ctypes.byref(good()), stream) == 0
+    torch.cuda.synchronize()
+    # (x is 0: every row with entries is clamped to [0, 0]; an empty row
+    # keeps its value as its bounds)
+    lens = np.diff(plan.to_host_csr()[0])
+    for t in (y, lo, hi):
+        host = t.cpu().numpy()
+        assert np.all(host[lens > 0] == 0.0) and np.all(host[lens == 0] == 2.0)
+    assert (lens == 0).any() and (lens > 0).any()
 
 
 # ---------------------------------------------------------------------------

@@ -7,7 +7,9 @@ on every layout the apply path addresses in place, and ``Remapper.sgs_frac``
 Bytes.  Kernel and statement perform the same IEEE operations in the same
 order (the library is built without contraction), and every NaN written is
 the one quiet NaN: every comparison with ``sgs.apply`` is an equality of the
-BYTES of ``Y``.
+BYTES of ``Y``.  The 64-bit index instantiations (more than 2^32 elements a
+launch) run in tests/test_gpu_wide_index.py, on a build of the library that
+takes them on small problems.
 
 Conservation, end to end.  For a first-order conservative map ``area_b_i
 S_ij`` is the overlap area of destination cell i and source cell j, and

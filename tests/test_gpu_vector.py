@@ -10,6 +10,10 @@ host), and every NaN written is the one quiet NaN: every comparison with
 ``vector.apply`` is an equality of the BYTES of ``YU`` and ``YV``.
 
 The solid-body bound is derived in test_vector_cpu.py.
+
+The 64-bit index instantiations (more than 2^32 elements a launch) run in
+tests/test_gpu_wide_index.py, on a build of the library that takes them on
+small problems.
 """
 import os
 
@@ -358,6 +362,47 @@ def test_remap_tensor_vector_layouts(shape, axes, route):
         r = r.reshape([N_B] + [shape[ax] for ax in extra])
         r = r.transpose(tail[:lead] + [0] + tail[lead:])
         assert cases.same_bytes(y.cpu().numpy(), r)
+
+
+def test_split_plan_is_served_as_one_matrix():
+    """Pole caps: the two outer lines of a 45 x 90 grid take a whole source
+    line (180 entries) among rows of 4, and the plan is applied as short and
+    long rows (``plan._split``); the vector launch walks the unsplit CSR."""
+    torch = _torch()
+    from pyremap_amd import engine, vector
+    rng = np.random.default_rng(21)
+    ny, nx, n_a = 45, 90, 90 * 180
+    rows = []
+    for j in range(ny):
+        for i in range(nx):
+            if j in (0, ny - 1):
+                rows.append(list(range((j > 0) * (n_a - 180),
+                                       (j > 0) * (n_a - 180) + 180)))
+            else:
+                base = 2 * j * 180 + 2 * i
+                rows.append([base, base + 1, base + 180, base + 181])
+    indptr, indices, data = cases.cases._csr(rows, rng)
+    data = np.abs(data)
+    plan = engine.RemapPlan.from_csr(indptr, indices, data,
+                                     np.ones(ny * nx), n_a, device='cuda:0')
+    plan.auto_schedule([ny, nx])
+    assert plan._split is not None and plan.max_row_nnz == 180
+    BA, BB = cases.random_basis(n_a, 33), cases.random_basis(ny * nx, 34)
+    BA_d, BB_d = (torch.from_numpy(t).to('cuda:0') for t in (BA, BB))
+    for shape, axes in (((n_a, 3), [0]), ((n_a, 64), [0]), ((5, n_a), [1])):
+        U, V = _fields(shape, seed=50 + shape[-1], nan_share=0.3)
+        got = engine.remap_tensor_vector(
+            plan, [ny, nx], torch.from_numpy(U).to('cuda:0'),
+            torch.from_numpy(V).to('cuda:0'), BA_d, BB_d, axes)
+        if axes == [0]:
+            ref = vector.apply(indptr, indices, data, U, V, BA, BB)[:2]
+        else:
+            ref = tuple(y.T for y in vector.apply(
+                indptr, indices, data, U.T, V.T, BA, BB)[:2])
+        for y, r in zip(got, ref):
+            y = y.cpu().numpy()
+            assert cases.same_bytes(y, r.reshape(y.shape)), (shape, axes)
+            assert np.isnan(r).any() and not np.isnan(r).all()
 
 
 class _Desc:
