@@ -3,7 +3,8 @@
 // remap_levels.hip, remap_layers.hip): the checks of their argument structs,
 // the addressing of a source cell, the packed loads and stores, and the work
 // list of the rowwave form.  A pass comes in two forms (remap_levels.hip and
-// remap_layers.hip have the first alone):
+// remap_layers.hip have the first alone, and have it, their parameters and
+// their launch from colpass.h, which stands on this header):
 //   rowlane  one lane per (row, column), for runs shorter than a wave;
 //   rowwave  one wave per (row, chunk of kWave * VEC contiguous columns),
 //            lanes across the columns, for runs of >= kWave columns.  The

@@ -2350,6 +2350,93 @@ def sgs_strided(plan, X, F, Y, *, n_batch, k_inner, x_row_stride,
     _launch(torch, plan, lib.remap_apply_sgs, 'remap_apply_sgs', args)
 
 
+#: A column pass (csrc/colpass.h) as :func:`_columns_strided` is told of it:
+#: the argument struct and the entry point; the companion array and the array
+#: of what is asked for, as messages and the struct's fields name them (the
+#: companion's other fields carry its name in lower case); the numbers asked
+#: for per output and what messages call them; the pass in words.
+_ColumnPass = collections.namedtuple(
+    '_ColumnPass', 'args entry companion query per_output numbers activity')
+_LEVELS = _ColumnPass(_LevelsArgs, 'remap_apply_levels', 'Z', 'T', 1,
+                      'targets', 'the level interpolation')
+_LAYERS = _ColumnPass(_LayersArgs, 'remap_apply_layers', 'H', 'bounds', 2,
+                      'numbers', 'the layer reduction')
+
+
+def _columns_strided(cp, plan, X, C, Q, Y, *, n_batch, n_levels, k_inner,
+                     x_row_stride, x_batch_stride, c_row_stride,
+                     c_batch_stride, y_row_stride, y_batch_stride, threshold,
+                     row_begin=0, row_end=None, x_src_fold=0,
+                     x_outer_stride=0, c_outer_stride=0, **own):
+    """What :func:`levels_strided` and :func:`layers_strided` share: one
+    launch of the column pass ``cp`` with the companion ``C``, its strides
+    under the names ``c_*``, and the outputs' ``Q``.  ``own``: the fields of
+    the argument struct that are the pass's alone."""
+    torch = _torch()
+    lib = load_library()
+    _one_device(plan, cp.activity)
+    arrays = (('X', X), (cp.companion, C), (cp.query, Q), ('Y', Y))
+    for name, t in arrays:
+        if t.device != plan.device:
+            raise ValueError(', '.join(n for n, _ in arrays[:-1]) +
+                             ', Y and the plan must live on the same device')
+        if not t.is_contiguous():
+            raise ValueError(f'{name} must be contiguous')
+    if Y.dtype != torch.float64:
+        raise TypeError('Y must be float64')
+    if Q.dtype != torch.float64:
+        raise TypeError(f'{cp.query} must be float64')
+    x_dtype = _float_dtype(torch, 'X', X)
+    c_dtype = _float_dtype(torch, cp.companion, C)
+    row_begin, end = _row_range(plan, row_begin, row_end)
+    if n_batch < 0 or k_inner < 0:
+        raise ValueError('n_batch and k_inner must not be negative')
+    if n_levels < 1:
+        raise ValueError(f'n_levels {n_levels}: expected >= 1')
+    if Q.numel() < cp.per_output * k_inner:
+        raise ValueError(f'{cp.query} holds {Q.numel()} {cp.numbers}; '
+                         f'k_inner is {k_inner}')
+    if x_src_fold:
+        _check_fold(plan.n_a, x_src_fold, x_outer_stride, c_outer_stride)
+    # (a launch without batches or outputs reads nothing; one with them reads
+    # whole columns)
+    columns = n_levels if k_inner > 0 else 0
+    _check_reach('X', X, plan.n_a, x_row_stride, x_batch_stride, 1, n_batch,
+                 columns, x_src_fold, x_outer_stride)
+    _check_reach(cp.companion, C, plan.n_a, c_row_stride, c_batch_stride, 1,
+                 n_batch, columns, x_src_fold, c_outer_stride)
+    _check_reach('Y', Y, plan.n_b, y_row_stride, y_batch_stride, 1, n_batch,
+                 k_inner)
+    _holds_csr(plan, ('rowptr', 'col', 'val'), cp.activity + ' reads it')
+    args = cp.args()
+    args.A = plan._csr_struct()
+    args.row_begin = row_begin
+    args.row_end = end
+    args.X = X.data_ptr()
+    args.x_dtype = x_dtype
+    args.x_row_stride = int(x_row_stride)
+    args.x_batch_stride = int(x_batch_stride)
+    args.x_src_fold = int(x_src_fold)
+    args.x_outer_stride = int(x_outer_stride)
+    args.n_levels = int(n_levels)
+    c = cp.companion.lower()
+    setattr(args, cp.companion, C.data_ptr())
+    setattr(args, c + '_dtype', c_dtype)
+    setattr(args, c + '_row_stride', int(c_row_stride))
+    setattr(args, c + '_batch_stride', int(c_batch_stride))
+    setattr(args, c + '_outer_stride', int(c_outer_stride))
+    setattr(args, cp.query, Q.data_ptr())
+    args.Y = Y.data_ptr()
+    args.y_row_stride = int(y_row_stride)
+    args.y_batch_stride = int(y_batch_stride)
+    args.n_batch = int(n_batch)
+    args.k_inner = int(k_inner)
+    args.threshold = float(threshold)
+    for name, value in own.items():
+        setattr(args, name, value)
+    _launch(torch, plan, getattr(lib, cp.entry), cp.entry, args)
+
+
 def levels_strided(plan, X, Z, T, Y, *, n_batch, n_levels, k_inner,
                    x_row_stride, x_batch_stride, z_row_stride,
                    z_batch_stride, y_row_stride, y_batch_stride, threshold,
@@ -2373,66 +2460,14 @@ def levels_strided(plan, X, Z, T, Y, *, n_batch, n_levels, k_inner,
     a schedule: a plan applied as short and long rows (``plan._split``) is
     served as the one matrix it is.
     """
-    torch = _torch()
-    lib = load_library()
-    _one_device(plan, 'the level interpolation')
-    for name, t in (('X', X), ('Z', Z), ('T', T), ('Y', Y)):
-        if t.device != plan.device:
-            raise ValueError('X, Z, T, Y and the plan must live on the same '
-                             'device')
-        if not t.is_contiguous():
-            raise ValueError(f'{name} must be contiguous')
-    if Y.dtype != torch.float64:
-        raise TypeError('Y must be float64')
-    if T.dtype != torch.float64:
-        raise TypeError('T must be float64')
-    x_dtype = _float_dtype(torch, 'X', X)
-    z_dtype = _float_dtype(torch, 'Z', Z)
-    row_begin, end = _row_range(plan, row_begin, row_end)
-    if n_batch < 0 or k_inner < 0:
-        raise ValueError('n_batch and k_inner must not be negative')
-    if n_levels < 1:
-        raise ValueError(f'n_levels {n_levels}: expected >= 1')
-    if T.numel() < k_inner:
-        raise ValueError(f'T holds {T.numel()} targets; k_inner is '
-                         f'{k_inner}')
-    if x_src_fold:
-        _check_fold(plan.n_a, x_src_fold, x_outer_stride, z_outer_stride)
-    # (a launch without batches or targets reads nothing; one with them
-    # reads whole columns)
-    columns = n_levels if k_inner > 0 else 0
-    _check_reach('X', X, plan.n_a, x_row_stride, x_batch_stride, 1, n_batch,
-                 columns, x_src_fold, x_outer_stride)
-    _check_reach('Z', Z, plan.n_a, z_row_stride, z_batch_stride, 1, n_batch,
-                 columns, x_src_fold, z_outer_stride)
-    _check_reach('Y', Y, plan.n_b, y_row_stride, y_batch_stride, 1, n_batch,
-                 k_inner)
-    _holds_csr(plan, ('rowptr', 'col', 'val'),
-               'the level interpolation reads it')
-    args = _LevelsArgs()
-    args.A = plan._csr_struct()
-    args.row_begin = row_begin
-    args.row_end = end
-    args.X = X.data_ptr()
-    args.x_dtype = x_dtype
-    args.x_row_stride = int(x_row_stride)
-    args.x_batch_stride = int(x_batch_stride)
-    args.x_src_fold = int(x_src_fold)
-    args.x_outer_stride = int(x_outer_stride)
-    args.n_levels = int(n_levels)
-    args.Z = Z.data_ptr()
-    args.z_dtype = z_dtype
-    args.z_row_stride = int(z_row_stride)
-    args.z_batch_stride = int(z_batch_stride)
-    args.z_outer_stride = int(z_outer_stride)
-    args.T = T.data_ptr()
-    args.Y = Y.data_ptr()
-    args.y_row_stride = int(y_row_stride)
-    args.y_batch_stride = int(y_batch_stride)
-    args.n_batch = int(n_batch)
-    args.k_inner = int(k_inner)
-    args.threshold = float(threshold)
-    _launch(torch, plan, lib.remap_apply_levels, 'remap_apply_levels', args)
+    _columns_strided(
+        _LEVELS, plan, X, Z, T, Y, n_batch=n_batch, n_levels=n_levels,
+        k_inner=k_inner, x_row_stride=x_row_stride,
+        x_batch_stride=x_batch_stride, c_row_stride=z_row_stride,
+        c_batch_stride=z_batch_stride, y_row_stride=y_row_stride,
+        y_batch_stride=y_batch_stride, threshold=threshold,
+        row_begin=row_begin, row_end=row_end, x_src_fold=x_src_fold,
+        x_outer_stride=x_outer_stride, c_outer_stride=z_outer_stride)
 
 
 def layers_strided(plan, X, H, bounds, Y, *, n_batch, n_levels, k_inner,
@@ -2457,67 +2492,16 @@ def layers_strided(plan, X, H, bounds, Y, *, n_batch, n_levels, k_inner,
     The launch reads the plan's own CSR (``rowptr``, ``col``, ``val``), never
     a schedule.
     """
-    torch = _torch()
-    lib = load_library()
-    _one_device(plan, 'the layer reduction')
-    code = _reduce_code(reduce)
-    for name, t in (('X', X), ('H', H), ('bounds', bounds), ('Y', Y)):
-        if t.device != plan.device:
-            raise ValueError('X, H, bounds, Y and the plan must live on the '
-                             'same device')
-        if not t.is_contiguous():
-            raise ValueError(f'{name} must be contiguous')
-    if Y.dtype != torch.float64:
-        raise TypeError('Y must be float64')
-    if bounds.dtype != torch.float64:
-        raise TypeError('bounds must be float64')
-    x_dtype = _float_dtype(torch, 'X', X)
-    h_dtype = _float_dtype(torch, 'H', H)
-    row_begin, end = _row_range(plan, row_begin, row_end)
-    if n_batch < 0 or k_inner < 0:
-        raise ValueError('n_batch and k_inner must not be negative')
-    if n_levels < 1:
-        raise ValueError(f'n_levels {n_levels}: expected >= 1')
-    if bounds.numel() < 2 * k_inner:
-        raise ValueError(f'bounds holds {bounds.numel()} numbers; k_inner is '
-                         f'{k_inner}')
-    if x_src_fold:
-        _check_fold(plan.n_a, x_src_fold, x_outer_stride, h_outer_stride)
-    # (a launch without batches or ranges reads nothing; one with them reads
-    # whole columns)
-    columns = n_levels if k_inner > 0 else 0
-    _check_reach('X', X, plan.n_a, x_row_stride, x_batch_stride, 1, n_batch,
-                 columns, x_src_fold, x_outer_stride)
-    _check_reach('H', H, plan.n_a, h_row_stride, h_batch_stride, 1, n_batch,
-                 columns, x_src_fold, h_outer_stride)
-    _check_reach('Y', Y, plan.n_b, y_row_stride, y_batch_stride, 1, n_batch,
-                 k_inner)
-    _holds_csr(plan, ('rowptr', 'col', 'val'), 'the layer reduction reads it')
-    args = _LayersArgs()
-    args.A = plan._csr_struct()
-    args.row_begin = row_begin
-    args.row_end = end
-    args.X = X.data_ptr()
-    args.x_dtype = x_dtype
-    args.x_row_stride = int(x_row_stride)
-    args.x_batch_stride = int(x_batch_stride)
-    args.x_src_fold = int(x_src_fold)
-    args.x_outer_stride = int(x_outer_stride)
-    args.n_levels = int(n_levels)
-    args.H = H.data_ptr()
-    args.h_dtype = h_dtype
-    args.h_row_stride = int(h_row_stride)
-    args.h_batch_stride = int(h_batch_stride)
-    args.h_outer_stride = int(h_outer_stride)
-    args.bounds = bounds.data_ptr()
-    args.Y = Y.data_ptr()
-    args.y_row_stride = int(y_row_stride)
-    args.y_batch_stride = int(y_batch_stride)
-    args.n_batch = int(n_batch)
-    args.k_inner = int(k_inner)
-    args.threshold = float(threshold)
-    args.reduce = code
-    _launch(torch, plan, lib.remap_apply_layers, 'remap_apply_layers', args)
+    _one_device(plan, _LAYERS.activity)
+    _columns_strided(
+        _LAYERS, plan, X, H, bounds, Y, n_batch=n_batch, n_levels=n_levels,
+        k_inner=k_inner, x_row_stride=x_row_stride,
+        x_batch_stride=x_batch_stride, c_row_stride=h_row_stride,
+        c_batch_stride=h_batch_stride, y_row_stride=y_row_stride,
+        y_batch_stride=y_batch_stride, threshold=threshold,
+        row_begin=row_begin, row_end=row_end, x_src_fold=x_src_fold,
+        x_outer_stride=x_outer_stride, c_outer_stride=h_outer_stride,
+        reduce=_reduce_code(reduce))
 
 
 def _check_basis(torch, plan, name, B, rows):
@@ -2954,23 +2938,25 @@ def remap_tensor_sgs(plan, dst_grid_dims, field, frac, remap_axes,
     return _launch_result(lay, Y)
 
 
-def _levels_targets(torch, targets, device):
-    """``targets`` as a contiguous 1-D float64 tensor on ``device``."""
-    if isinstance(targets, torch.Tensor):
-        if targets.device != device:
-            raise ValueError('targets and the field must live on the same '
-                             'device')
-        if not (targets.dtype.is_floating_point or
-                targets.dtype in (torch.int32, torch.int64)):
-            raise ValueError(f'targets of dtype {targets.dtype}: expected '
+def _asked_for(torch, values, name, device, shape_ok, expected):
+    """What a column pass is asked for (``name``: the targets, the bounds) as
+    a contiguous float64 tensor on ``device``, of a shape that ``shape_ok``
+    accepts (``expected`` in words)."""
+    if isinstance(values, torch.Tensor):
+        if values.device != device:
+            raise ValueError(f'{name} and the field must live on the same '
+                             f'device')
+        if not (values.dtype.is_floating_point or
+                values.dtype in (torch.int32, torch.int64)):
+            raise ValueError(f'{name} of dtype {values.dtype}: expected '
                              f'numbers')
-        T = targets.to(torch.float64)
+        Q = values.to(torch.float64)
     else:
-        T = torch.as_tensor(targets, dtype=torch.float64).to(device)
-    if T.ndim != 1 or T.numel() == 0:
-        raise ValueError(f'targets of shape {tuple(T.shape)}: expected a '
-                         f'non-empty 1-D list of levels')
-    return T.contiguous()
+        Q = torch.as_tensor(values, dtype=torch.float64).to(device)
+    if not shape_ok(Q):
+        raise ValueError(f'{name} of shape {tuple(Q.shape)}: expected a '
+                         f'non-empty {expected}')
+    return Q.contiguous()
 
 
 def remap_tensor_levels(plan, dst_grid_dims, field, z, targets, remap_axes,
@@ -2996,34 +2982,20 @@ def remap_tensor_levels(plan, dst_grid_dims, field, z, targets, remap_axes,
     """
     _one_device(plan, 'the level interpolation')
 
-    def launch(X, Z, T, Y, strides):
-        levels_strided(plan, X, Z, T, Y, threshold=threshold, **strides)
+    def launch(X, Z, T, Y, *, c_row_stride, c_batch_stride, c_outer_stride=0,
+               **strides):
+        levels_strided(plan, X, Z, T, Y, threshold=threshold,
+                       z_row_stride=c_row_stride,
+                       z_batch_stride=c_batch_stride,
+                       z_outer_stride=c_outer_stride, **strides)
 
     def outputs(torch, device):
-        T = _levels_targets(torch, targets, device)
+        T = _asked_for(torch, targets, 'targets', device,
+                       lambda T: T.ndim == 1 and T.numel() > 0,
+                       '1-D list of levels')
         return T, int(T.numel())
     return _remap_tensor_columns(plan, dst_grid_dims, field, z, 'z',
                                  remap_axes, outputs, launch)
-
-
-def _layers_bounds(torch, bounds, device):
-    """``bounds`` -- ``R`` pairs ``(A, B)`` -- as a contiguous float64
-    ``(R, 2)`` tensor on ``device``."""
-    if isinstance(bounds, torch.Tensor):
-        if bounds.device != device:
-            raise ValueError('bounds and the field must live on the same '
-                             'device')
-        if not (bounds.dtype.is_floating_point or
-                bounds.dtype in (torch.int32, torch.int64)):
-            raise ValueError(f'bounds of dtype {bounds.dtype}: expected '
-                             f'numbers')
-        Bd = bounds.to(torch.float64)
-    else:
-        Bd = torch.as_tensor(bounds, dtype=torch.float64).to(device)
-    if Bd.ndim != 2 or Bd.shape[1] != 2 or Bd.shape[0] == 0:
-        raise ValueError(f'bounds of shape {tuple(Bd.shape)}: expected a '
-                         f'non-empty list of (top, bottom) pairs')
-    return Bd.contiguous()
 
 
 def _reduce_code(reduce):
@@ -3058,14 +3030,17 @@ def remap_tensor_layers(plan, dst_grid_dims, field, thickness, bounds,
     _one_device(plan, 'the layer reduction')
     _reduce_code(reduce)
 
-    def launch(X, H, Bd, Y, strides):
-        strides = {('h' + name[1:] if name.startswith('z_') else name): s
-                   for name, s in strides.items()}
+    def launch(X, H, Bd, Y, *, c_row_stride, c_batch_stride, c_outer_stride=0,
+               **strides):
         layers_strided(plan, X, H, Bd, Y, threshold=threshold, reduce=reduce,
-                       **strides)
+                       h_row_stride=c_row_stride,
+                       h_batch_stride=c_batch_stride,
+                       h_outer_stride=c_outer_stride, **strides)
 
     def outputs(torch, device):
-        Bd = _layers_bounds(torch, bounds, device)
+        Bd = _asked_for(torch, bounds, 'bounds', device,
+                        lambda Bd: Bd.ndim == 2 and Bd.shape[1] == 2 and
+                        Bd.shape[0] > 0, 'list of (top, bottom) pairs')
         return Bd, int(Bd.shape[0])
     return _remap_tensor_columns(plan, dst_grid_dims, field, thickness,
                                  'thickness', remap_axes, outputs, launch)
@@ -3081,8 +3056,8 @@ def _remap_tensor_columns(plan, dst_grid_dims, field, z, zname, remap_axes,
     checks, the routes and strides of :func:`field_layout` and the launches.
     ``outputs(torch, device)``: the float64 device tensor of what is asked
     for (targets; ranges) and the inner extent of the result (their number);
-    ``launch(X, Z, T, Y, strides)``: one launch, the companion's strides
-    under the names ``z_row_stride``, ``z_batch_stride``, ``z_outer_stride``.
+    ``launch(X, Z, T, Y, **strides)``: one launch, the companion's strides
+    under the names ``c_row_stride``, ``c_batch_stride``, ``c_outer_stride``.
     """
     torch = _torch()
     ndim = field.ndim
@@ -3145,8 +3120,8 @@ def _remap_tensor_columns(plan, dst_grid_dims, field, z, zname, remap_axes,
         Z = z.permute(lay.order).reshape(n_az, Mz * nl).contiguous()
         strides = dict(n_batch=M, x_batch_stride=nl, x_row_stride=M * nl,
                        y_batch_stride=L, y_row_stride=M * L,
-                       z_batch_stride=nl if mid_full else 0,
-                       z_row_stride=Mz * nl if z_cells else 0)
+                       c_batch_stride=nl if mid_full else 0,
+                       c_row_stride=Mz * nl if z_cells else 0)
         n_launch, lead_full = 1, False
         y_shape = [n_b, M * L]
         back_shape, unpermute = lay.back
@@ -3163,11 +3138,11 @@ def _remap_tensor_columns(plan, dst_grid_dims, field, z, zname, remap_axes,
                        x_src_fold=nx, x_outer_stride=M * nx * nl,
                        y_row_stride=M * L, y_batch_stride=L)
         if z_cells:
-            strides.update(z_row_stride=nl, z_outer_stride=Mz * nx * nl,
-                           z_batch_stride=nx * nl if mid_full else 0)
+            strides.update(c_row_stride=nl, c_outer_stride=Mz * nx * nl,
+                           c_batch_stride=nx * nl if mid_full else 0)
         else:
-            strides.update(z_row_stride=0, z_outer_stride=0,
-                           z_batch_stride=nl if mid_full else 0)
+            strides.update(c_row_stride=0, c_outer_stride=0,
+                           c_batch_stride=nl if mid_full else 0)
         n_launch = lay.n_launch
         y_shape, back = list(lay.out_shape[:-1]) + [L], None
     else:
@@ -3184,23 +3159,23 @@ def _remap_tensor_columns(plan, dst_grid_dims, field, z, zname, remap_axes,
             strides = dict(n_batch=NB, x_row_stride=nl,
                            x_batch_stride=n_a * nl, y_row_stride=L,
                            y_batch_stride=n_b * L,
-                           z_row_stride=nl if z_cells else 0,
-                           z_batch_stride=n_az * nl if lead_full else 0)
+                           c_row_stride=nl if z_cells else 0,
+                           c_batch_stride=n_az * nl if lead_full else 0)
             n_launch, lead_full = 1, False
         else:
             # dims between the source axes and the levels are the batches,
             # one launch per index of the dims in front
             strides = dict(n_batch=M, x_batch_stride=nl, x_row_stride=M * nl,
                            y_batch_stride=L, y_row_stride=M * L,
-                           z_batch_stride=nl if mid_full else 0,
-                           z_row_stride=Mz * nl if z_cells else 0)
+                           c_batch_stride=nl if mid_full else 0,
+                           c_row_stride=Mz * nl if z_cells else 0)
             n_launch = NB
         y_shape, back = list(lay.out_shape[:-1]) + [L], None
     Y = torch.empty(y_shape, dtype=torch.float64, device=field.device)
     Zs = [Zl for Zl, in _launch_rows(n_launch if lead_full else 1, Z)]
     for li, (Xl, Yl) in enumerate(_launch_rows(n_launch, X, Y)):
-        launch(Xl, Zs[li if lead_full else 0], T, Yl,
-               dict(strides, n_levels=nl, k_inner=L))
+        launch(Xl, Zs[li if lead_full else 0], T, Yl, **strides,
+               n_levels=nl, k_inner=L)
     if back is None:
         return Y
     return Y.reshape(back[0]).permute(back[1]).contiguous()

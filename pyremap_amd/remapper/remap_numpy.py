@@ -18,6 +18,7 @@ reference (remap_numpy.py)      here
                                 transpose copies, one fused HIP launch
 ==============================  ============================================
 """
+import functools
 import os
 import sys
 
@@ -157,21 +158,47 @@ def _check_sgs(remapper):
     if not isinstance(name, str):
         raise TypeError(f'sgs_frac must be None or a variable name, not '
                         f'{name!r}')
-    _check_sgs_alone(remapper)
+    _check_alone(remapper, 'sgs_frac')
     return name
 
 
-def _check_sgs_alone(remapper):
-    """What sub-gridscale weighting does not go together with."""
-    if getattr(remapper, 'limiter', None) is not None:
-        raise NotImplementedError(
-            'sgs_frac together with a limiter is not served: one or the '
-            'other')
+#: What each switch of a Remapper is not served together with: switch ->
+#: (what the messages call it, in "together with" and in "serves one device";
+#: the other switches in the order they are looked at, each with what follows
+#: "is not served").
+_ONE_OR_THE_OTHER = ': one or the other'
+_ALONE = {
+    'sgs_frac': ('sgs_frac', 'sgs_frac', (('limiter', _ONE_OR_THE_OTHER),)),
+    'levels': ('levels', 'levels', (
+        ('limiter', _ONE_OR_THE_OTHER), ('sgs_frac', ''),
+        ('vector_pairs', ''), ('layers', _ONE_OR_THE_OTHER))),
+    'layers': ('layers', 'layers', (
+        ('limiter', _ONE_OR_THE_OTHER), ('sgs_frac', ''),
+        ('vector_pairs', ''), ('levels', _ONE_OR_THE_OTHER))),
+    'vector_pairs': ('a vector remap', 'the vector remap', (
+        ('limiter', ': the bounds of a component are no bounds of the '
+                    'rotated vector'), ('sgs_frac', ''))),
+}
+
+
+def _check_alone(remapper, switch):
+    """What the switch ``switch`` of ``remapper`` -- sub-gridscale weighting,
+    the level interpolation, the layer reduction, the vector remap -- does
+    not go together with."""
+    called, serves, others = _ALONE[switch]
+    for other, why in others:
+        value = getattr(remapper, other, None)
+        # (an empty list of vector pairs is none)
+        if value if other == 'vector_pairs' else value is not None:
+            raise NotImplementedError(
+                f'{called} together with '
+                f'{"a limiter" if other == "limiter" else other} is not '
+                f'served{why}')
     if getattr(remapper, '_process_group', None) is not None or \
             len(getattr(remapper, 'devices', None) or ()) > 1:
         raise NotImplementedError(
-            'sgs_frac serves one device: not with devices=[...] or a '
-            'process group')
+            f'{serves} serves one device: not with devices=[...] or a '
+            f'process group')
 
 
 class _SgsFraction:
@@ -252,29 +279,8 @@ def _check_levels(remapper):
                         f'{targets!r}') from None
     if targets.size == 0:
         raise ValueError('levels names no target level: targets is empty')
-    _check_levels_alone(remapper)
+    _check_alone(remapper, 'levels')
     return coordinate, targets, out_dim
-
-
-def _check_levels_alone(remapper):
-    """What the level interpolation does not go together with."""
-    if getattr(remapper, 'limiter', None) is not None:
-        raise NotImplementedError(
-            'levels together with a limiter is not served: one or the other')
-    if getattr(remapper, 'sgs_frac', None) is not None:
-        raise NotImplementedError(
-            'levels together with sgs_frac is not served')
-    if getattr(remapper, 'vector_pairs', None):
-        raise NotImplementedError(
-            'levels together with vector_pairs is not served')
-    if getattr(remapper, 'layers', None) is not None:
-        raise NotImplementedError(
-            'levels together with layers is not served: one or the other')
-    if getattr(remapper, '_process_group', None) is not None or \
-            len(getattr(remapper, 'devices', None) or ()) > 1:
-        raise NotImplementedError(
-            'levels serves one device: not with devices=[...] or a process '
-            'group')
 
 
 class _LevelCoordinate:
@@ -439,29 +445,8 @@ def _check_layers(remapper):
     if reduce not in engine.REDUCE:
         raise ValueError(f'layers: reduce {reduce!r}: expected one of '
                          f'{sorted(engine.REDUCE)}')
-    _check_layers_alone(remapper)
+    _check_alone(remapper, 'layers')
     return thickness, bounds, out_dim, reduce
-
-
-def _check_layers_alone(remapper):
-    """What the layer reduction does not go together with."""
-    if getattr(remapper, 'limiter', None) is not None:
-        raise NotImplementedError(
-            'layers together with a limiter is not served: one or the other')
-    if getattr(remapper, 'sgs_frac', None) is not None:
-        raise NotImplementedError(
-            'layers together with sgs_frac is not served')
-    if getattr(remapper, 'vector_pairs', None):
-        raise NotImplementedError(
-            'layers together with vector_pairs is not served')
-    if getattr(remapper, 'levels', None) is not None:
-        raise NotImplementedError(
-            'layers together with levels is not served: one or the other')
-    if getattr(remapper, '_process_group', None) is not None or \
-            len(getattr(remapper, 'devices', None) or ()) > 1:
-        raise NotImplementedError(
-            'layers serves one device: not with devices=[...] or a process '
-            'group')
 
 
 class _LayerThickness(_LevelCoordinate):
@@ -515,22 +500,6 @@ def _layer_thickness(remapper, ds):
                            bounds, out_dim, reduce)
 
 
-def _check_vector_alone(remapper):
-    """What the vector remap does not go together with."""
-    if getattr(remapper, 'limiter', None) is not None:
-        raise NotImplementedError(
-            'a vector remap together with a limiter is not served: the '
-            'bounds of a component are no bounds of the rotated vector')
-    if getattr(remapper, 'sgs_frac', None) is not None:
-        raise NotImplementedError(
-            'a vector remap together with sgs_frac is not served')
-    if getattr(remapper, '_process_group', None) is not None or \
-            len(getattr(remapper, 'devices', None) or ()) > 1:
-        raise NotImplementedError(
-            'the vector remap serves one device: not with devices=[...] or '
-            'a process group')
-
-
 def _check_vector_pairs(remapper):
     """The Remapper's ``vector_pairs`` as a list of ``(u_name, v_name)``
     tuples (None without any), and what it does not go together with."""
@@ -555,7 +524,7 @@ def _check_vector_pairs(remapper):
             seen.add(name)
     if not pairs:
         return None
-    _check_vector_alone(remapper)
+    _check_alone(remapper, 'vector_pairs')
     return pairs
 
 
@@ -1215,7 +1184,7 @@ def _remap_array_sgs(remapper, in_field, sgs_frac, remap_axes,
     tensor out (NaN where masked); numpy in, ``numpy.ma.MaskedArray`` out
     with the mask taken from NaN.  ``None`` threshold means 0.0.
     """
-    _check_sgs_alone(remapper)
+    _check_alone(remapper, 'sgs_frac')
     torch = engine.require_gpu()
     plan = remapper._matrix
     threshold = 0.0 if renormalization_threshold is None else \
@@ -1267,32 +1236,42 @@ def _remap_array_levels(remapper, in_field, z, targets, remap_axes,
     axis that is not the last is moved there (the engine copies), and the
     target axis stands behind the other axes of the result.
     """
-    _check_levels_alone(remapper)
+    _check_alone(remapper, 'levels')
     _check_level_arrays(in_field, z, targets, level_axis)
+    return _remap_array_columns(remapper, in_field, z, targets, remap_axes,
+                                renormalization_threshold,
+                                engine.remap_tensor_levels, level_axis)
+
+
+def _remap_array_columns(remapper, in_field, companion, asked, remap_axes,
+                         renormalization_threshold, remap, level_axis=-1):
+    """What :func:`_remap_array_levels` and :func:`_remap_array_layers` share
+    behind their checks: the field and its ``companion`` (the coordinate, the
+    thicknesses) and what is ``asked`` for (the targets, the bounds) on the
+    plan's device, through ``remap`` (the engine's function) and back."""
     torch = engine.require_gpu()
     plan = remapper._matrix
     threshold = 0.0 if renormalization_threshold is None else \
         float(renormalization_threshold)
     on_device = isinstance(in_field, torch.Tensor)
     if on_device:
-        field, coord = in_field.to(plan.device), z.to(plan.device)
+        field, comp = in_field.to(plan.device), companion.to(plan.device)
     else:
         field = _host_values(torch, in_field, plan.device)
-        coord = _host_values(torch, z, plan.device)
+        comp = _host_values(torch, companion, plan.device)
     ndim = field.ndim
     level_axis = int(level_axis) % ndim
     remap_axes = [int(a) % ndim for a in remap_axes]
     if level_axis != ndim - 1:
         order = [ax for ax in range(ndim) if ax != level_axis] + [level_axis]
-        field, coord = field.permute(order), coord.permute(order)
+        field, comp = field.permute(order), comp.permute(order)
         remap_axes = [order.index(ax) for ax in remap_axes]
-    if isinstance(targets, torch.Tensor):
-        targets = targets.to(plan.device)
+    if isinstance(asked, torch.Tensor):
+        asked = asked.to(plan.device)
     else:
-        targets = np.asarray(targets, dtype=np.float64)
-    out = engine.remap_tensor_levels(
-        plan, remapper._ds_map.dst_grid_dims, field, coord, targets,
-        remap_axes, threshold=threshold)
+        asked = np.asarray(asked, dtype=np.float64)
+    out = remap(plan, remapper._ds_map.dst_grid_dims, field, comp, asked,
+                remap_axes, threshold=threshold)
     if on_device:
         return out
     out = out.cpu().numpy()
@@ -1329,30 +1308,12 @@ def _remap_array_layers(remapper, in_field, thickness, bounds, remap_axes,
     out with the mask taken from NaN.  ``None`` threshold means 0.0.  The
     level axis is the last.
     """
-    _check_layers_alone(remapper)
+    _check_alone(remapper, 'layers')
     _check_layer_arrays(in_field, thickness, bounds, reduce)
-    torch = engine.require_gpu()
-    plan = remapper._matrix
-    threshold = 0.0 if renormalization_threshold is None else \
-        float(renormalization_threshold)
-    on_device = isinstance(in_field, torch.Tensor)
-    if on_device:
-        field, h = in_field.to(plan.device), thickness.to(plan.device)
-    else:
-        field = _host_values(torch, in_field, plan.device)
-        h = _host_values(torch, thickness, plan.device)
-    remap_axes = [int(a) % field.ndim for a in remap_axes]
-    if isinstance(bounds, torch.Tensor):
-        bounds = bounds.to(plan.device)
-    else:
-        bounds = np.asarray(bounds, dtype=np.float64)
-    out = engine.remap_tensor_layers(
-        plan, remapper._ds_map.dst_grid_dims, field, h, bounds, remap_axes,
-        threshold=threshold, reduce=reduce)
-    if on_device:
-        return out
-    out = out.cpu().numpy()
-    return np.ma.masked_array(out, mask=np.isnan(out))
+    return _remap_array_columns(
+        remapper, in_field, thickness, bounds, remap_axes,
+        renormalization_threshold,
+        functools.partial(engine.remap_tensor_layers, reduce=reduce))
 
 
 def _remap_array_vector(remapper, u, v, remap_axes,
@@ -1363,7 +1324,7 @@ def _remap_array_vector(remapper, u, v, remap_axes,
     ``numpy.ma.MaskedArray`` out with the masks taken from NaN.  ``None``
     threshold means 0.0.
     """
-    _check_vector_alone(remapper)
+    _check_alone(remapper, 'vector_pairs')
     torch = engine.require_gpu()
     plan = remapper._matrix
     threshold = 0.0 if renormalization_threshold is None else \

@@ -9,13 +9,10 @@ Added on top of the reference surface: ``remap`` / ``remap_file`` aliases
 knobs and :meth:`from_triplets` for mapping data that is already in memory.
 """
 from pyremap_amd.remapper.remap_numpy import (
+    _check_alone,
     _check_layer_arrays,
-    _check_layers_alone,
     _check_level_arrays,
-    _check_levels_alone,
     _check_limiter,
-    _check_sgs_alone,
-    _check_vector_alone,
     _check_vector_fields,
     _load_mapping,
     _remap_numpy,
@@ -485,7 +482,7 @@ class Remapper:
         """
         if self.map_filename is None:
             raise ValueError('No mapping file has been defined')
-        _check_sgs_alone(self)
+        _check_alone(self, 'sgs_frac')
         _load_mapping(self)
         return _remap_array_sgs(self, field, sgs_frac, remap_axes,
                                 renormalization_threshold)
@@ -511,7 +508,7 @@ class Remapper:
         """
         if self.map_filename is None:
             raise ValueError('No mapping file has been defined')
-        _check_vector_alone(self)
+        _check_alone(self, 'vector_pairs')
         _check_vector_fields(u, v)
         _load_mapping(self)
         _require_centres(self._ds_map)
@@ -547,7 +544,7 @@ class Remapper:
         """
         if self.map_filename is None:
             raise ValueError('No mapping file has been defined')
-        _check_levels_alone(self)
+        _check_alone(self, 'levels')
         _check_level_arrays(field, z, targets, level_axis)
         _load_mapping(self)
         return _remap_array_levels(self, field, z, targets, remap_axes,
@@ -584,7 +581,7 @@ class Remapper:
         """
         if self.map_filename is None:
             raise ValueError('No mapping file has been defined')
-        _check_layers_alone(self)
+        _check_alone(self, 'layers')
         _check_layer_arrays(field, thickness, bounds, reduce)
         _load_mapping(self)
         return _remap_array_layers(self, field, thickness, bounds,

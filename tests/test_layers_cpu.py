@@ -354,6 +354,9 @@ def test_the_definition_stands_in_header_statement_kernel_and_design():
         assert line in layers.__doc__, line
         assert line in kernel, line
         assert line in design, line
+    # (the lane walk and its stores stand in colpass.h)
+    assert '#include "colpass.h"' in kernel
+    kernel += open(os.path.join(_build.CSRC, 'colpass.h')).read()
     flat = ' '.join(kernel.split())
     assert '__builtin_nontemporal_store' in kernel
     assert 'rowpass.h' in kernel

@@ -313,6 +313,9 @@ def test_the_definition_stands_in_header_statement_and_kernel():
         assert line in _header(), line
         assert line in levels.__doc__, line
         assert line in kernel, line
+    # (the lane walk and its stores stand in colpass.h)
+    assert '#include "colpass.h"' in kernel
+    kernel += open(os.path.join(_build.CSRC, 'colpass.h')).read()
     flat = ' '.join(kernel.split())
     assert '__builtin_nontemporal_store' in kernel
     assert 'fma' not in kernel.replace('FMA contraction', '')
