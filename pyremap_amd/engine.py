@@ -1,6 +1,8 @@
 """
-Host side of the MI355X weight-application engine: the ctypes binding of
-``libremap_hip.so`` (``include/remap_hip.h``) plus the device-resident plan.
+Host side of the MI355X weight-application engine: ``libremap_hip.so``
+(``include/remap_hip.h``; ``_abi.py`` is its ctypes mirror) loaded, the
+device-resident plan and the launches.  The weight-generation wrappers live
+in ``geometry.py`` and are re-exported at the end of this file.
 
 This is the layer that replaces, for ``Remapper.remap_numpy``:
 
@@ -18,12 +20,15 @@ raises.
 import collections
 import contextlib
 import ctypes
-import numbers
 import os
 
 import numpy as np
 
-from pyremap_amd import _build
+from pyremap_amd import _abi, _build
+from pyremap_amd._abi import (  # noqa: F401  (tests and tools read them here)
+    EXPORTS, _ApplyArgs, _CSR, _Field, _LayersArgs, _LevelsArgs, _LimitArgs,
+    _OverlapGeom, _OverlapGrid, _OverlapMesh, _OverlapPieces, _OverlapSide,
+    _PlanInfo, _Schedule, _SgsArgs, _Strips, _VectorArgs)
 
 MODE_RAW = 0
 MODE_FRACB = 1
@@ -59,8 +64,6 @@ REDUCE = {'mean': 0, 'integral': 1}
 
 ABI_VERSION = 31
 
-#: the largest k of nearest_k_points (REMAP_NEAREST_K_MAX)
-NEAREST_K_MAX = 16
 #: readable pad entries kept behind col/val (remap_csr.csr_pad)
 CSR_PAD = 8
 #: LDS a workgroup of the lanes-across-rows kernel may take (kPatchLdsMax)
@@ -70,376 +73,11 @@ _LONG_WAVE_TT = None   # (tests: columns per wave of family 9, 0 = auto)
 _CELL_TUNE = None      # (tools/tn_probe.py: [TT, one-chunk kernel?] of family 7)
 _RUNS_TUNE = None      # (tools/runs_probe.py: the batch-at-a-time launch's tune)
 
-#: every symbol ``include/remap_hip.h`` declares
-EXPORTS = (
-    'remap_abi_version', 'remap_arch', 'remap_last_error',
-    'remap_device_count', 'remap_apply_f64', 'remap_csr_from_coo_workspace',
-    'remap_csr_from_coo', 'remap_stream_copy', 'remap_scan_nan',
-    'remap_scan_nan_kinds', 'remap_scan_nan_layout',
-    'remap_groups_workspace', 'remap_groups_build', 'remap_share_build',
-    'remap_patches_workspace', 'remap_patches_build',
-    'remap_schedule_sizes', 'remap_schedule_auto',
-    'remap_plan_create', 'remap_plan_destroy', 'remap_plan_query',
-    'remap_plan_apply', 'remap_plan_apply_auto',
-    'remap_pack_columns_workspace', 'remap_pack_columns',
-    'remap_gather_rows', 'remap_plan_prepare_short_runs',
-    'remap_clock_probe',
-    'remap_overlap_latlon_sizes', 'remap_overlap_latlon',
-    'remap_overlap_meshes_sizes', 'remap_overlap_meshes',
-    'remap_overlap_pieces_sizes', 'remap_overlap_pieces',
-    'remap_overlap_pieces_timed',
-    'remap_overlap_grids_sizes', 'remap_overlap_grids',
-    'remap_nearest_workspace', 'remap_nearest', 'remap_nearest_timed',
-    'remap_nearest_k_workspace', 'remap_nearest_k',
-    'remap_locate_workspace', 'remap_locate', 'remap_locate_timed',
-    'remap_quads_workspace', 'remap_quads', 'remap_quads_timed',
-    'remap_expand_cells',
-    'remap_cell_areas', 'remap_column_fractions_workspace',
-    'remap_column_fractions',
-    'remap_cell_moments', 'remap_overlap_moments_workspace',
-    'remap_overlap_moments', 'remap_gradient_stencils',
-    'remap_conserve2nd_sizes', 'remap_conserve2nd_assemble',
-    'remap_node_rings_workspace', 'remap_node_rings', 'remap_patch_fits',
-    'remap_patch_sizes_workspace', 'remap_patch_sizes', 'remap_patch_rows',
-    'remap_limit_rows', 'remap_apply_sgs', 'remap_apply_vector',
-    'remap_apply_levels', 'remap_apply_layers',
-)
-
 #: what ``limiter=`` accepts (remap_tensor, Remapper.limiter)
 LIMITERS = (None, 'clip', 'caas')
 
 
-class _CSR(ctypes.Structure):
-    _fields_ = [
-        ('n_rows', ctypes.c_int64),
-        ('n_cols', ctypes.c_int64),
-        ('nnz', ctypes.c_int64),
-        ('rowptr', ctypes.c_void_p),
-        ('col', ctypes.c_void_p),
-        ('val', ctypes.c_void_p),
-        ('max_row_nnz', ctypes.c_int64),
-        ('csr_pad', ctypes.c_int64),
-    ]
-
-
-class _ApplyArgs(ctypes.Structure):
-    _fields_ = [
-        ('A', _CSR),
-        ('row_begin', ctypes.c_int64),
-        ('row_end', ctypes.c_int64),
-        ('X', ctypes.c_void_p),
-        ('x_dtype', ctypes.c_int32),
-        ('mode', ctypes.c_int32),
-        ('x_row_stride', ctypes.c_int64),
-        ('x_batch_stride', ctypes.c_int64),
-        ('Y', ctypes.c_void_p),
-        ('y_row_stride', ctypes.c_int64),
-        ('y_batch_stride', ctypes.c_int64),
-        ('n_batch', ctypes.c_int64),
-        ('k_inner', ctypes.c_int64),
-        ('frac_b', ctypes.c_void_p),
-        ('threshold', ctypes.c_double),
-        ('mask_out', ctypes.c_void_p),
-        ('row_order', ctypes.c_void_p),
-        ('patch_ptr', ctypes.c_void_p),
-        ('patch_ucol', ctypes.c_void_p),
-        ('patch_rowptr', ctypes.c_void_p),
-        ('patch_lidx', ctypes.c_void_p),
-        ('patch_val', ctypes.c_void_p),
-        ('patch_rows', ctypes.c_int32),
-        ('patch_umax', ctypes.c_int32),
-        ('patch_emax', ctypes.c_int32),
-        ('patch_row_bytes', ctypes.c_int32),
-        ('n_patches', ctypes.c_int64),
-        ('group_meta', ctypes.c_void_p),
-        ('group_col', ctypes.c_void_p),
-        ('group_w', ctypes.c_void_p),
-        ('group_mask', ctypes.c_void_p),
-        ('group_rid', ctypes.c_void_p),
-        ('group_frac', ctypes.c_void_p),
-        ('n_groups', ctypes.c_int64),
-        ('group_rows', ctypes.c_int32),
-        ('group_reserved', ctypes.c_int32),
-        ('gate', ctypes.c_void_p),
-        ('gate_value', ctypes.c_int32),
-        ('flags', ctypes.c_uint32),
-        ('tune', ctypes.c_int32 * 8),
-        ('x_src_fold', ctypes.c_int64),
-        ('x_outer_stride', ctypes.c_int64),
-        ('patch_ell_base', ctypes.c_void_p),
-        ('strips', ctypes.c_void_p),
-        ('share_meta', ctypes.c_void_p),
-        ('share_col', ctypes.c_void_p),
-        ('share_mask', ctypes.c_void_p),
-        ('share_waves', ctypes.c_int32),
-        ('share_reserved', ctypes.c_int32),
-    ]
-
-
-class _LimitArgs(ctypes.Structure):     # struct remap_limit_args
-    _fields_ = [
-        ('A', _CSR),
-        ('row_begin', ctypes.c_int64),
-        ('row_end', ctypes.c_int64),
-        ('X', ctypes.c_void_p),
-        ('x_dtype', ctypes.c_int32),
-        ('x_row_stride', ctypes.c_int64),
-        ('x_batch_stride', ctypes.c_int64),
-        ('x_src_fold', ctypes.c_int64),
-        ('x_outer_stride', ctypes.c_int64),
-        ('Y', ctypes.c_void_p),
-        ('y_row_stride', ctypes.c_int64),
-        ('y_batch_stride', ctypes.c_int64),
-        ('n_batch', ctypes.c_int64),
-        ('k_inner', ctypes.c_int64),
-        ('lo', ctypes.c_void_p),
-        ('hi', ctypes.c_void_p),
-    ]
-
-
-class _SgsArgs(ctypes.Structure):       # struct remap_sgs_args
-    _fields_ = [
-        ('A', _CSR),
-        ('row_begin', ctypes.c_int64),
-        ('row_end', ctypes.c_int64),
-        ('X', ctypes.c_void_p),
-        ('x_dtype', ctypes.c_int32),
-        ('x_row_stride', ctypes.c_int64),
-        ('x_batch_stride', ctypes.c_int64),
-        ('x_src_fold', ctypes.c_int64),
-        ('x_outer_stride', ctypes.c_int64),
-        ('F', ctypes.c_void_p),
-        ('f_dtype', ctypes.c_int32),
-        ('f_row_stride', ctypes.c_int64),
-        ('f_batch_stride', ctypes.c_int64),
-        ('f_inner_stride', ctypes.c_int64),
-        ('f_outer_stride', ctypes.c_int64),
-        ('Y', ctypes.c_void_p),
-        ('y_row_stride', ctypes.c_int64),
-        ('y_batch_stride', ctypes.c_int64),
-        ('n_batch', ctypes.c_int64),
-        ('k_inner', ctypes.c_int64),
-        ('threshold', ctypes.c_double),
-    ]
-
-
-class _LevelsArgs(ctypes.Structure):    # struct remap_levels_args
-    _fields_ = [
-        ('A', _CSR),
-        ('row_begin', ctypes.c_int64),
-        ('row_end', ctypes.c_int64),
-        ('X', ctypes.c_void_p),
-        ('x_dtype', ctypes.c_int32),
-        ('x_row_stride', ctypes.c_int64),
-        ('x_batch_stride', ctypes.c_int64),
-        ('x_src_fold', ctypes.c_int64),
-        ('x_outer_stride', ctypes.c_int64),
-        ('n_levels', ctypes.c_int64),
-        ('Z', ctypes.c_void_p),
-        ('z_dtype', ctypes.c_int32),
-        ('z_row_stride', ctypes.c_int64),
-        ('z_batch_stride', ctypes.c_int64),
-        ('z_outer_stride', ctypes.c_int64),
-        ('T', ctypes.c_void_p),
-        ('Y', ctypes.c_void_p),
-        ('y_row_stride', ctypes.c_int64),
-        ('y_batch_stride', ctypes.c_int64),
-        ('n_batch', ctypes.c_int64),
-        ('k_inner', ctypes.c_int64),
-        ('threshold', ctypes.c_double),
-    ]
-
-
-class _LayersArgs(ctypes.Structure):    # struct remap_layers_args
-    _fields_ = [
-        ('A', _CSR),
-        ('row_begin', ctypes.c_int64),
-        ('row_end', ctypes.c_int64),
-        ('X', ctypes.c_void_p),
-        ('x_dtype', ctypes.c_int32),
-        ('x_row_stride', ctypes.c_int64),
-        ('x_batch_stride', ctypes.c_int64),
-        ('x_src_fold', ctypes.c_int64),
-        ('x_outer_stride', ctypes.c_int64),
-        ('n_levels', ctypes.c_int64),
-        ('H', ctypes.c_void_p),
-        ('h_dtype', ctypes.c_int32),
-        ('h_row_stride', ctypes.c_int64),
-        ('h_batch_stride', ctypes.c_int64),
-        ('h_outer_stride', ctypes.c_int64),
-        ('bounds', ctypes.c_void_p),
-        ('Y', ctypes.c_void_p),
-        ('y_row_stride', ctypes.c_int64),
-        ('y_batch_stride', ctypes.c_int64),
-        ('n_batch', ctypes.c_int64),
-        ('k_inner', ctypes.c_int64),
-        ('threshold', ctypes.c_double),
-        ('reduce', ctypes.c_int32),
-    ]
-
-
-class _VectorArgs(ctypes.Structure):    # struct remap_vector_args
-    _fields_ = [
-        ('A', _CSR),
-        ('row_begin', ctypes.c_int64),
-        ('row_end', ctypes.c_int64),
-        ('U', ctypes.c_void_p),
-        ('V', ctypes.c_void_p),
-        ('x_dtype', ctypes.c_int32),
-        ('x_row_stride', ctypes.c_int64),
-        ('x_batch_stride', ctypes.c_int64),
-        ('x_src_fold', ctypes.c_int64),
-        ('x_outer_stride', ctypes.c_int64),
-        ('BA', ctypes.c_void_p),
-        ('BB', ctypes.c_void_p),
-        ('YU', ctypes.c_void_p),
-        ('YV', ctypes.c_void_p),
-        ('y_row_stride', ctypes.c_int64),
-        ('y_batch_stride', ctypes.c_int64),
-        ('n_batch', ctypes.c_int64),
-        ('k_inner', ctypes.c_int64),
-        ('threshold', ctypes.c_double),
-    ]
-
-
-class _Strips(ctypes.Structure):         # struct remap_strips
-    _fields_ = [
-        ('n_units', ctypes.c_int64),
-        ('steps_per_unit', ctypes.c_int32),
-        ('rows_per_wave', ctypes.c_int32),
-        ('ring_slots', ctypes.c_int32),
-        ('depth', ctypes.c_int32),
-        ('meta_slot_bytes', ctypes.c_int32),
-        ('waves', ctypes.c_int32),
-        ('unit_steps', ctypes.c_void_p),
-        ('arr_ptr', ctypes.c_void_p),
-        ('arr_src', ctypes.c_void_p),
-        ('arr_slot', ctypes.c_void_p),
-        ('meta_ptr', ctypes.c_void_p),
-        ('meta', ctypes.c_void_p),
-    ]
-
-
-class _Schedule(ctypes.Structure):
-    _fields_ = [
-        ('family', ctypes.c_int32),
-        ('entry_rich', ctypes.c_int32),
-        ('row_order', ctypes.c_void_p),
-        ('patch_ptr', ctypes.c_void_p),
-        ('patch_ucol', ctypes.c_void_p),
-        ('patch_rowptr', ctypes.c_void_p),
-        ('patch_lidx', ctypes.c_void_p),
-        ('patch_val', ctypes.c_void_p),
-        ('patch_rows', ctypes.c_int32),
-        ('patch_umax', ctypes.c_int32),
-        ('patch_emax', ctypes.c_int32),
-        ('patch_row_bytes', ctypes.c_int32),
-        ('n_patches', ctypes.c_int64),
-        ('group_meta', ctypes.c_void_p),
-        ('group_col', ctypes.c_void_p),
-        ('group_w', ctypes.c_void_p),
-        ('group_mask', ctypes.c_void_p),
-        ('group_rid', ctypes.c_void_p),
-        ('group_frac', ctypes.c_void_p),
-        ('n_groups', ctypes.c_int64),
-        ('group_rows', ctypes.c_int32),
-        ('super_tile', ctypes.c_int32),
-        ('tile_y', ctypes.c_int32),
-        ('tile_x', ctypes.c_int32),
-        ('ratio', ctypes.c_double),
-        ('n_distinct', ctypes.c_int64),
-        ('tune', (ctypes.c_int32 * 8) * 3),
-        ('arena_used', ctypes.c_size_t),
-        ('share_meta', ctypes.c_void_p),
-        ('share_col', ctypes.c_void_p),
-        ('share_mask', ctypes.c_void_p),
-        ('share_waves', ctypes.c_int32),
-        ('share_reserved', ctypes.c_int32),
-        ('n_share_union', ctypes.c_int64),
-    ]
-
-
-class _PlanInfo(ctypes.Structure):     # struct remap_plan_info
-    _fields_ = [
-        ('n_a', ctypes.c_int64),
-        ('n_b', ctypes.c_int64),
-        ('nnz', ctypes.c_int64),
-        ('max_row_nnz', ctypes.c_int64),
-        ('family', ctypes.c_int32),
-        ('group_rows', ctypes.c_int32),
-        ('ratio', ctypes.c_double),
-        ('device_bytes', ctypes.c_size_t),
-        ('cell_patch_rows', ctypes.c_int32),
-        ('reserved', ctypes.c_int32),
-    ]
-
-
-class _Field(ctypes.Structure):        # struct remap_field
-    _fields_ = [
-        ('X', ctypes.c_void_p),
-        ('x_dtype', ctypes.c_int32),
-        ('mode', ctypes.c_int32),
-        ('n_batch', ctypes.c_int64),
-        ('k_inner', ctypes.c_int64),
-        ('x_row_stride', ctypes.c_int64),
-        ('x_batch_stride', ctypes.c_int64),
-        ('Y', ctypes.c_void_p),
-        ('y_row_stride', ctypes.c_int64),
-        ('y_batch_stride', ctypes.c_int64),
-        ('threshold', ctypes.c_double),
-        ('mask_out', ctypes.c_void_p),
-        ('gate', ctypes.c_void_p),
-        ('gate_value', ctypes.c_int32),
-        ('flags', ctypes.c_uint32),
-    ]
-
-
 _lib = None
-
-
-class _OverlapGeom(ctypes.Structure):  # struct remap_overlap_geom
-    _fields_ = [('n_cells', ctypes.c_int64),
-                ('n_vertices', ctypes.c_int64),
-                ('n_lat', ctypes.c_int64),
-                ('n_lon', ctypes.c_int64),
-                ('max_edges', ctypes.c_int32),
-                ('reserved', ctypes.c_int32),
-                ('lat_slack', ctypes.c_double),
-                ('vertices_on_cell', ctypes.c_void_p),
-                ('n_edges_on_cell', ctypes.c_void_p),
-                ('lat_vertex', ctypes.c_void_p),
-                ('lon_vertex', ctypes.c_void_p),
-                ('lat_corner', ctypes.c_void_p),
-                ('lon_corner', ctypes.c_void_p)]
-
-
-class _OverlapMesh(ctypes.Structure):  # struct remap_overlap_mesh
-    _fields_ = [('n_cells', ctypes.c_int64),
-                ('n_vertices', ctypes.c_int64),
-                ('max_edges', ctypes.c_int32),
-                ('reserved', ctypes.c_int32),
-                ('vertices_on_cell', ctypes.c_void_p),
-                ('n_edges_on_cell', ctypes.c_void_p),
-                ('lat_vertex', ctypes.c_void_p),
-                ('lon_vertex', ctypes.c_void_p)]
-
-
-class _OverlapPieces(ctypes.Structure):  # struct remap_overlap_pieces
-    _fields_ = [('mesh', _OverlapMesh),
-                ('n_parents', ctypes.c_int64),
-                ('parent', ctypes.c_void_p)]
-
-
-class _OverlapGrid(ctypes.Structure):  # struct remap_overlap_grid
-    _fields_ = [('ny', ctypes.c_int64),
-                ('nx', ctypes.c_int64),
-                ('lat_corner', ctypes.c_void_p),
-                ('lon_corner', ctypes.c_void_p)]
-
-
-class _OverlapSide(ctypes.Structure):  # struct remap_overlap_side
-    _fields_ = [('mesh', ctypes.POINTER(_OverlapMesh)),
-                ('grid', ctypes.POINTER(_OverlapGrid))]
 
 
 class EngineError(RuntimeError):
@@ -482,7 +120,7 @@ def load_library():
 def open_library(path):
     """
     ``ctypes.CDLL(path)``, checked against ``EXPORTS`` and the ABI version,
-    with every entry point's restype and argtypes set.  ``load_library`` keeps
+    with every entry point's prototype declared.  ``load_library`` keeps
     the one the package works with; a second library of the same ABI (the
     tests' wide-index build, ``_build.WIDE_LIB_PATH``) is opened with this and
     put in its place by setting ``engine._lib``.
@@ -491,298 +129,7 @@ def open_library(path):
     missing = [name for name in EXPORTS if not hasattr(lib, name)]
     if missing:
         raise EngineError(f'{path} lacks symbols {missing}')
-    lib.remap_abi_version.restype = ctypes.c_int
-    lib.remap_arch.restype = ctypes.c_char_p
-    lib.remap_last_error.restype = ctypes.c_char_p
-    lib.remap_device_count.restype = ctypes.c_int
-    lib.remap_apply_f64.restype = ctypes.c_int
-    lib.remap_apply_f64.argtypes = [ctypes.POINTER(_ApplyArgs),
-                                    ctypes.c_void_p]
-    lib.remap_csr_from_coo_workspace.restype = ctypes.c_int
-    lib.remap_csr_from_coo_workspace.argtypes = [
-        ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]
-    lib.remap_csr_from_coo.restype = ctypes.c_int
-    lib.remap_csr_from_coo.argtypes = [
-        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib.remap_groups_workspace.restype = ctypes.c_int
-    lib.remap_groups_workspace.argtypes = [
-        ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]
-    lib.remap_groups_build.restype = ctypes.c_int
-    lib.remap_groups_build.argtypes = [
-        ctypes.POINTER(_CSR), ctypes.c_void_p, ctypes.c_int32,
-        ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, ctypes.c_int32,
-        ctypes.c_int32] + \
-        [ctypes.c_void_p] * 9 + [ctypes.c_size_t, ctypes.c_void_p]
-    lib.remap_share_build.restype = ctypes.c_int
-    lib.remap_share_build.argtypes = [
-        ctypes.POINTER(_CSR), ctypes.c_void_p, ctypes.c_int32] + \
-        [ctypes.c_void_p] * 5 + [ctypes.c_size_t, ctypes.c_void_p]
-    lib.remap_patches_workspace.restype = ctypes.c_int
-    lib.remap_patches_workspace.argtypes = [
-        ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]
-    lib.remap_patches_build.restype = ctypes.c_int
-    lib.remap_patches_build.argtypes = [
-        ctypes.POINTER(_CSR), ctypes.POINTER(ctypes.c_int64), ctypes.c_int64,
-        ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 8 + \
-        [ctypes.c_size_t, ctypes.c_void_p]
-    lib.remap_schedule_sizes.restype = ctypes.c_int
-    lib.remap_schedule_sizes.argtypes = [
-        ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t),
-        ctypes.POINTER(ctypes.c_size_t)]
-    lib.remap_schedule_auto.restype = ctypes.c_int
-    lib.remap_schedule_auto.argtypes = [
-        ctypes.POINTER(_CSR), ctypes.c_void_p,
-        ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, ctypes.c_int64,
-        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
-        ctypes.POINTER(_Schedule), ctypes.c_void_p]
-    lib.remap_plan_create.restype = ctypes.c_int
-    lib.remap_plan_create.argtypes = [
-        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-        ctypes.c_int32, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32,
-        ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]
-    lib.remap_plan_destroy.restype = None
-    lib.remap_plan_destroy.argtypes = [ctypes.c_void_p]
-    lib.remap_plan_query.restype = ctypes.c_int
-    lib.remap_plan_query.argtypes = [ctypes.c_void_p,
-                                     ctypes.POINTER(_PlanInfo)]
-    lib.remap_plan_prepare_short_runs.restype = ctypes.c_int
-    lib.remap_plan_prepare_short_runs.argtypes = [ctypes.c_void_p,
-                                                  ctypes.c_void_p]
-    lib.remap_plan_apply.restype = ctypes.c_int
-    lib.remap_plan_apply.argtypes = [ctypes.c_void_p,
-                                     ctypes.POINTER(_Field), ctypes.c_void_p]
-    lib.remap_plan_apply_auto.restype = ctypes.c_int
-    lib.remap_plan_apply_auto.argtypes = [
-        ctypes.c_void_p, ctypes.POINTER(_Field), ctypes.c_int64,
-        ctypes.c_void_p, ctypes.c_void_p]
-    lib.remap_pack_columns_workspace.restype = ctypes.c_int
-    lib.remap_pack_columns_workspace.argtypes = [
-        ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]
-    lib.remap_pack_columns.restype = ctypes.c_int
-    lib.remap_pack_columns.argtypes = [
-        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_size_t, ctypes.c_void_p]
-    lib.remap_gather_rows.restype = ctypes.c_int
-    lib.remap_gather_rows.argtypes = [
-        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-        ctypes.c_void_p]
-    lib.remap_scan_nan.restype = ctypes.c_int
-    lib.remap_scan_nan.argtypes = [ctypes.c_void_p, ctypes.c_int32,
-                                   ctypes.c_int64, ctypes.c_void_p,
-                                   ctypes.c_void_p]
-    lib.remap_scan_nan_kinds.restype = ctypes.c_int
-    lib.remap_scan_nan_kinds.argtypes = [ctypes.c_void_p, ctypes.c_int32,
-                                   ctypes.c_int64, ctypes.c_void_p,
-                                   ctypes.c_void_p]
-    lib.remap_scan_nan_layout.restype = ctypes.c_int
-    lib.remap_scan_nan_layout.argtypes = [
-        ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
-        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
-        ctypes.c_void_p]
-    lib.remap_stream_copy.restype = ctypes.c_int
-    lib.remap_stream_copy.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
-                                      ctypes.c_size_t, ctypes.c_void_p]
-    lib.remap_clock_probe.restype = ctypes.c_int
-    lib.remap_clock_probe.argtypes = [ctypes.c_void_p, ctypes.c_int32,
-                                      ctypes.c_void_p]
-    lib.remap_overlap_latlon_sizes.restype = ctypes.c_int
-    lib.remap_overlap_latlon_sizes.argtypes = [
-        ctypes.POINTER(_OverlapGeom), ctypes.c_void_p,
-        ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_size_t),
-        ctypes.c_void_p]
-    lib.remap_overlap_latlon.restype = ctypes.c_int
-    lib.remap_overlap_latlon.argtypes = [
-        ctypes.POINTER(_OverlapGeom), ctypes.c_int32, ctypes.c_int64,
-        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]
-    lib.remap_overlap_meshes_sizes.restype = ctypes.c_int
-    lib.remap_overlap_meshes_sizes.argtypes = [
-        ctypes.POINTER(_OverlapMesh), ctypes.POINTER(_OverlapMesh),
-        ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
-        ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
-    lib.remap_overlap_meshes.restype = ctypes.c_int
-    lib.remap_overlap_meshes.argtypes = [
-        ctypes.POINTER(_OverlapMesh), ctypes.POINTER(_OverlapMesh),
-        ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
-        ctypes.c_void_p]
-    lib.remap_overlap_pieces_sizes.restype = ctypes.c_int
-    lib.remap_overlap_pieces_sizes.argtypes = [
-        ctypes.POINTER(_OverlapPieces), ctypes.POINTER(_OverlapPieces),
-        ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
-        ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
-    lib.remap_overlap_pieces.restype = ctypes.c_int
-    lib.remap_overlap_pieces.argtypes = [
-        ctypes.POINTER(_OverlapPieces), ctypes.POINTER(_OverlapPieces),
-        ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
-        ctypes.c_void_p]
-    lib.remap_overlap_pieces_timed.restype = ctypes.c_int
-    lib.remap_overlap_pieces_timed.argtypes = [
-        ctypes.POINTER(_OverlapPieces), ctypes.POINTER(_OverlapPieces),
-        ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
-        ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
-    lib.remap_overlap_grids_sizes.restype = ctypes.c_int
-    lib.remap_overlap_grids_sizes.argtypes = [
-        ctypes.POINTER(_OverlapSide), ctypes.POINTER(_OverlapSide),
-        ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_size_t),
-        ctypes.c_void_p]
-    lib.remap_overlap_grids.restype = ctypes.c_int
-    lib.remap_overlap_grids.argtypes = [
-        ctypes.POINTER(_OverlapSide), ctypes.POINTER(_OverlapSide),
-        ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
-        ctypes.c_void_p]
-    lib.remap_nearest_workspace.restype = ctypes.c_int
-    lib.remap_nearest_workspace.argtypes = [
-        ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]
-    lib.remap_nearest.restype = ctypes.c_int
-    lib.remap_nearest.argtypes = [
-        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib.remap_nearest_timed.restype = ctypes.c_int
-    lib.remap_nearest_timed.argtypes = [
-        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-        ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
-    lib.remap_nearest_k_workspace.restype = ctypes.c_int
-    lib.remap_nearest_k_workspace.argtypes = [
-        ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-        ctypes.POINTER(ctypes.c_size_t)]
-    lib.remap_nearest_k.restype = ctypes.c_int
-    lib.remap_nearest_k.argtypes = [
-        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
-        ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_size_t, ctypes.c_void_p]
-    lib.remap_locate_workspace.restype = ctypes.c_int
-    lib.remap_locate_workspace.argtypes = [
-        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-        ctypes.POINTER(ctypes.c_size_t)]
-    lib.remap_locate.restype = ctypes.c_int
-    lib.remap_locate.argtypes = [
-        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
-        ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib.remap_locate_timed.restype = ctypes.c_int
-    lib.remap_locate_timed.argtypes = [
-        ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
-        ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-        ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
-    lib.remap_quads_workspace.restype = ctypes.c_int
-    lib.remap_quads_workspace.argtypes = [
-        ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
-        ctypes.POINTER(ctypes.c_size_t)]
-    lib.remap_quads.restype = ctypes.c_int
-    lib.remap_quads.argtypes = [
-        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-        ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib.remap_quads_timed.restype = ctypes.c_int
-    lib.remap_quads_timed.argtypes = [
-        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
-        ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-        ctypes.POINTER(ctypes.c_float), ctypes.c_void_p]
-    lib.remap_expand_cells.restype = ctypes.c_int
-    lib.remap_expand_cells.argtypes = [
-        ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.remap_cell_areas.restype = ctypes.c_int
-    lib.remap_cell_areas.argtypes = [
-        ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.remap_column_fractions_workspace.restype = ctypes.c_int
-    lib.remap_column_fractions_workspace.argtypes = [
-        ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]
-    lib.remap_column_fractions.restype = ctypes.c_int
-    lib.remap_column_fractions.argtypes = [
-        ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-    lib.remap_cell_moments.restype = ctypes.c_int
-    lib.remap_cell_moments.argtypes = lib.remap_cell_areas.argtypes
-    lib.remap_overlap_moments_workspace.restype = ctypes.c_int
-    lib.remap_overlap_moments_workspace.argtypes = [
-        ctypes.c_int64, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
-        ctypes.POINTER(ctypes.c_size_t)]
-    lib.remap_overlap_moments.restype = ctypes.c_int
-    lib.remap_overlap_moments.argtypes = [ctypes.c_int64] + \
-        [ctypes.c_void_p] * 3 + \
-        [ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 5 + \
-        [ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 3 + \
-        [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-         ctypes.c_void_p]
-    lib.remap_gradient_stencils.restype = ctypes.c_int
-    lib.remap_gradient_stencils.argtypes = [
-        ctypes.c_int64, ctypes.c_int32] + [ctypes.c_void_p] * 7
-    lib.remap_conserve2nd_sizes.restype = ctypes.c_int
-    lib.remap_conserve2nd_sizes.argtypes = [
-        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_size_t),
-        ctypes.c_void_p]
-    lib.remap_conserve2nd_assemble.restype = ctypes.c_int
-    lib.remap_conserve2nd_assemble.argtypes = [ctypes.c_int64] + \
-        [ctypes.c_void_p] * 4 + [ctypes.c_int64, ctypes.c_int32] + \
-        [ctypes.c_void_p] * 6 + [ctypes.c_int64, ctypes.c_void_p,
-                                 ctypes.c_int64, ctypes.c_void_p,
-                                 ctypes.c_size_t] + \
-        [ctypes.c_void_p] * 4 + [ctypes.POINTER(ctypes.c_int64),
-                                 ctypes.c_void_p]
-    lib.remap_node_rings_workspace.restype = ctypes.c_int
-    lib.remap_node_rings_workspace.argtypes = [
-        ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]
-    lib.remap_node_rings.restype = ctypes.c_int
-    lib.remap_node_rings.argtypes = [
-        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
-        ctypes.c_void_p]
-    lib.remap_patch_fits.restype = ctypes.c_int
-    lib.remap_patch_fits.argtypes = [ctypes.c_int64] + [ctypes.c_void_p] * 7
-    lib.remap_patch_sizes_workspace.restype = ctypes.c_int
-    lib.remap_patch_sizes_workspace.argtypes = [
-        ctypes.c_int64, ctypes.POINTER(ctypes.c_size_t)]
-    lib.remap_patch_sizes.restype = ctypes.c_int
-    lib.remap_patch_sizes.argtypes = [
-        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] + \
-        [ctypes.c_void_p] * 4 + [ctypes.c_int64] + [ctypes.c_void_p] * 3 + \
-        [ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p, ctypes.c_void_p,
-         ctypes.c_size_t, ctypes.c_void_p]
-    lib.remap_patch_rows.restype = ctypes.c_int
-    lib.remap_patch_rows.argtypes = [
-        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] + \
-        [ctypes.c_void_p] * 5 + [ctypes.c_int64] + [ctypes.c_void_p] * 4 + \
-        [ctypes.c_int64] + [ctypes.c_void_p] * 5
-    lib.remap_limit_rows.restype = ctypes.c_int
-    lib.remap_limit_rows.argtypes = [ctypes.POINTER(_LimitArgs),
-                                     ctypes.c_void_p]
-    lib.remap_apply_sgs.restype = ctypes.c_int
-    lib.remap_apply_sgs.argtypes = [ctypes.POINTER(_SgsArgs),
-                                    ctypes.c_void_p]
-    lib.remap_apply_vector.restype = ctypes.c_int
-    lib.remap_apply_vector.argtypes = [ctypes.POINTER(_VectorArgs),
-                                       ctypes.c_void_p]
-    lib.remap_apply_levels.restype = ctypes.c_int
-    lib.remap_apply_levels.argtypes = [ctypes.POINTER(_LevelsArgs),
-                                       ctypes.c_void_p]
-    lib.remap_apply_layers.restype = ctypes.c_int
-    lib.remap_apply_layers.argtypes = [ctypes.POINTER(_LayersArgs),
-                                       ctypes.c_void_p]
+    _abi.declare(lib)
     if lib.remap_abi_version() != ABI_VERSION:
         raise EngineError(
             f'{path} has ABI {lib.remap_abi_version()}, expected '
@@ -2124,6 +1471,88 @@ def apply_strided(plan, X, Y, *, n_batch, k_inner, x_row_stride,
             enter=torch.cuda.current_device() != plan.device.index)
 
 
+#: An array a row pass reads by source cell, as :func:`_row_pass` is told of
+#: it: its name in messages and in the argument struct, the tensor, and its
+#: strides in elements (``outer`` goes with ``x_src_fold``).
+_Source = collections.namedtuple('_Source',
+                                 'name tensor row batch inner outer')
+
+
+def _row_pass(args_type, entry, plan, reads, sources, results, own,
+              *, n_batch, k_inner, y_row_stride, y_batch_stride, row_begin,
+              row_end, x_src_fold, threshold=None, beside=(), limits=(),
+              depth=None, csr=('rowptr', 'col', 'val'), strict=True):
+    """
+    What the launches beside the apply share, as ``rowpass::check_args``
+    states it on the C side: their checks, the fields every ``remap_*_args``
+    has, and the launch of ``entry`` with an ``args_type`` on torch's current
+    stream.
+
+    ``sources``: the :class:`_Source` arrays, the first of them the one the
+    ``x_*`` fields describe; ``results``: ``(name, tensor)`` of the float64
+    arrays addressed by destination row with the ``y_*`` strides.  Both go
+    into the field of their name.  ``beside``: ``(name, tensor)`` of the
+    pass's other arrays, which the device message names between the two;
+    ``limits``: ``(name, tensor or None)`` of optional arrays addressed like
+    the results.  ``depth``: the inner extent of the sources where it is not
+    ``k_inner``.  ``own``: the fields that are the pass's alone.
+
+    ``reads`` says why the plan must still hold the ``csr`` arrays.  The
+    caller has refused a multi-device plan (:func:`_one_device`) before it
+    looked at an array of its own.
+    ``strict=False`` is the limiter's older contract: arrays need not be
+    contiguous, and a launch without batches leaves the fold to the library.
+    """
+    torch = _torch()
+    lib = load_library()
+    arrays = [(s.name, s.tensor) for s in sources] + list(beside) + \
+        list(results)
+    for name, t in arrays:
+        if t.device != plan.device:
+            raise ValueError(', '.join(n for n, _ in arrays) +
+                             ' and the plan must live on the same device')
+        if strict and not t.is_contiguous():
+            raise ValueError(f'{name} must be contiguous')
+    if any(t.dtype != torch.float64 for _, t in results):
+        raise TypeError(' and '.join(n for n, _ in results) +
+                        ' must be float64')
+    x = sources[0]
+    x_dtype = _float_dtype(torch, x.name, x.tensor)
+    row_begin, end = _row_range(plan, row_begin, row_end)
+    if n_batch < 0 or k_inner < 0:
+        raise ValueError('n_batch and k_inner must not be negative')
+    if strict and x_src_fold:
+        _check_fold(plan.n_a, x_src_fold, *(s.outer for s in sources))
+    for s in sources:
+        _check_reach(s.name, s.tensor, plan.n_a, s.row, s.batch, s.inner,
+                     n_batch, k_inner if depth is None else depth,
+                     x_src_fold, s.outer)
+    for name, t in list(results) + list(limits):
+        _check_reach(name, t, plan.n_b, y_row_stride, y_batch_stride, 1,
+                     n_batch, k_inner)
+    _holds_csr(plan, csr, reads)
+    args = args_type()
+    args.A = plan._csr_struct()
+    args.row_begin = row_begin
+    args.row_end = end
+    args.x_dtype = x_dtype
+    args.x_row_stride = int(x.row)
+    args.x_batch_stride = int(x.batch)
+    args.x_src_fold = int(x_src_fold)
+    args.x_outer_stride = int(x.outer)
+    args.y_row_stride = int(y_row_stride)
+    args.y_batch_stride = int(y_batch_stride)
+    args.n_batch = int(n_batch)
+    args.k_inner = int(k_inner)
+    if threshold is not None:
+        args.threshold = float(threshold)
+    for name, t in arrays:
+        setattr(args, name, t.data_ptr())
+    for name, value in own.items():
+        setattr(args, name, value)
+    _launch(torch, plan, getattr(lib, entry), entry, args)
+
+
 def check_limiter(limiter):
     """``limiter`` is one of ``None | 'clip' | 'caas'``."""
     if limiter not in LIMITERS:
@@ -2150,46 +1579,21 @@ def limit_strided(plan, X, Y, *, n_batch, k_inner, x_row_stride,
     limited as the one matrix it is, a row slice over its own rows.
     """
     torch = _torch()
-    lib = load_library()
     _one_device(plan, 'the limiter')
-    if X.device != plan.device or Y.device != plan.device:
-        raise ValueError('X, Y and the plan must live on the same device')
-    if Y.dtype != torch.float64:
-        raise TypeError('Y must be float64')
-    x_dtype = _float_dtype(torch, 'X', X)
     for name, t in (('lo', lo), ('hi', hi)):
         if t is not None and (t.dtype != torch.float64 or
                               t.device != plan.device):
             raise TypeError(f'{name} must be a float64 tensor on the plan '
                             f'device')
-    row_begin, end = _row_range(plan, row_begin, row_end)
-    _check_reach('X', X, plan.n_a, x_row_stride, x_batch_stride, 1, n_batch,
-                 k_inner, x_src_fold, x_outer_stride)
-    for name, t in (('Y', Y), ('lo', lo), ('hi', hi)):
-        _check_reach(name, t, plan.n_b, y_row_stride, y_batch_stride, 1,
-                     n_batch, k_inner)
-    if n_batch < 0 or k_inner < 0:
-        raise ValueError('n_batch and k_inner must not be negative')
-    _holds_csr(plan, ('rowptr', 'col'),
-               "the limiter gathers a row's sources from it")
-    args = _LimitArgs()
-    args.A = plan._csr_struct()
-    args.row_begin = row_begin
-    args.row_end = end
-    args.X = X.data_ptr()
-    args.x_dtype = x_dtype
-    args.x_row_stride = int(x_row_stride)
-    args.x_batch_stride = int(x_batch_stride)
-    args.x_src_fold = int(x_src_fold)
-    args.x_outer_stride = int(x_outer_stride)
-    args.Y = Y.data_ptr()
-    args.y_row_stride = int(y_row_stride)
-    args.y_batch_stride = int(y_batch_stride)
-    args.n_batch = int(n_batch)
-    args.k_inner = int(k_inner)
-    args.lo = lo.data_ptr() if lo is not None else None
-    args.hi = hi.data_ptr() if hi is not None else None
-    _launch(torch, plan, lib.remap_limit_rows, 'remap_limit_rows', args)
+    _row_pass(
+        _LimitArgs, 'remap_limit_rows', plan,
+        "the limiter gathers a row's sources from it",
+        [_Source('X', X, x_row_stride, x_batch_stride, 1, x_outer_stride)],
+        [('Y', Y)], dict(lo=_ptr(lo), hi=_ptr(hi)),
+        n_batch=n_batch, k_inner=k_inner, y_row_stride=y_row_stride,
+        y_batch_stride=y_batch_stride, row_begin=row_begin, row_end=row_end,
+        x_src_fold=x_src_fold, limits=(('lo', lo), ('hi', hi)),
+        csr=('rowptr', 'col'), strict=False)
 
 
 def _caas_mass(Yv, row_weight):
@@ -2295,59 +1699,25 @@ def sgs_strided(plan, X, F, Y, *, n_batch, k_inner, x_row_stride,
     a schedule: a plan applied as short and long rows (``plan._split``) is
     served as the one matrix it is.
     """
-    torch = _torch()
-    lib = load_library()
     _one_device(plan, 'sub-gridscale weighting')
-    for name, t in (('X', X), ('F', F), ('Y', Y)):
-        if t.device != plan.device:
-            raise ValueError('X, F, Y and the plan must live on the same '
-                             'device')
-        if not t.is_contiguous():
-            raise ValueError(f'{name} must be contiguous')
-    if Y.dtype != torch.float64:
-        raise TypeError('Y must be float64')
-    x_dtype = _float_dtype(torch, 'X', X)
-    f_dtype = _float_dtype(torch, 'F', F)
-    row_begin, end = _row_range(plan, row_begin, row_end)
-    if n_batch < 0 or k_inner < 0:
-        raise ValueError('n_batch and k_inner must not be negative')
+    f_dtype = _float_dtype(_torch(), 'F', F)
     if f_inner_stride not in (0, 1):
         raise ValueError(f'f_inner_stride {f_inner_stride}: expected 0 '
                          f'(broadcast) or 1')
-    if x_src_fold:
-        _check_fold(plan.n_a, x_src_fold, x_outer_stride, f_outer_stride)
-    _check_reach('X', X, plan.n_a, x_row_stride, x_batch_stride, 1, n_batch,
-                 k_inner, x_src_fold, x_outer_stride)
-    _check_reach('F', F, plan.n_a, f_row_stride, f_batch_stride,
-                 f_inner_stride, n_batch, k_inner, x_src_fold,
-                 f_outer_stride)
-    _check_reach('Y', Y, plan.n_b, y_row_stride, y_batch_stride, 1, n_batch,
-                 k_inner)
-    _holds_csr(plan, ('rowptr', 'col', 'val'),
-               'the sub-gridscale launch reads it')
-    args = _SgsArgs()
-    args.A = plan._csr_struct()
-    args.row_begin = row_begin
-    args.row_end = end
-    args.X = X.data_ptr()
-    args.x_dtype = x_dtype
-    args.x_row_stride = int(x_row_stride)
-    args.x_batch_stride = int(x_batch_stride)
-    args.x_src_fold = int(x_src_fold)
-    args.x_outer_stride = int(x_outer_stride)
-    args.F = F.data_ptr()
-    args.f_dtype = f_dtype
-    args.f_row_stride = int(f_row_stride)
-    args.f_batch_stride = int(f_batch_stride)
-    args.f_inner_stride = int(f_inner_stride)
-    args.f_outer_stride = int(f_outer_stride)
-    args.Y = Y.data_ptr()
-    args.y_row_stride = int(y_row_stride)
-    args.y_batch_stride = int(y_batch_stride)
-    args.n_batch = int(n_batch)
-    args.k_inner = int(k_inner)
-    args.threshold = float(threshold)
-    _launch(torch, plan, lib.remap_apply_sgs, 'remap_apply_sgs', args)
+    _row_pass(
+        _SgsArgs, 'remap_apply_sgs', plan,
+        'the sub-gridscale launch reads it',
+        [_Source('X', X, x_row_stride, x_batch_stride, 1, x_outer_stride),
+         _Source('F', F, f_row_stride, f_batch_stride, f_inner_stride,
+                 f_outer_stride)],
+        [('Y', Y)],
+        dict(f_dtype=f_dtype, f_row_stride=int(f_row_stride),
+             f_batch_stride=int(f_batch_stride),
+             f_inner_stride=int(f_inner_stride),
+             f_outer_stride=int(f_outer_stride)),
+        n_batch=n_batch, k_inner=k_inner, y_row_stride=y_row_stride,
+        y_batch_stride=y_batch_stride, row_begin=row_begin, row_end=row_end,
+        x_src_fold=x_src_fold, threshold=threshold)
 
 
 #: A column pass (csrc/colpass.h) as :func:`_columns_strided` is told of it:
@@ -2373,68 +1743,32 @@ def _columns_strided(cp, plan, X, C, Q, Y, *, n_batch, n_levels, k_inner,
     under the names ``c_*``, and the outputs' ``Q``.  ``own``: the fields of
     the argument struct that are the pass's alone."""
     torch = _torch()
-    lib = load_library()
     _one_device(plan, cp.activity)
-    arrays = (('X', X), (cp.companion, C), (cp.query, Q), ('Y', Y))
-    for name, t in arrays:
-        if t.device != plan.device:
-            raise ValueError(', '.join(n for n, _ in arrays[:-1]) +
-                             ', Y and the plan must live on the same device')
-        if not t.is_contiguous():
-            raise ValueError(f'{name} must be contiguous')
-    if Y.dtype != torch.float64:
-        raise TypeError('Y must be float64')
     if Q.dtype != torch.float64:
         raise TypeError(f'{cp.query} must be float64')
-    x_dtype = _float_dtype(torch, 'X', X)
-    c_dtype = _float_dtype(torch, cp.companion, C)
-    row_begin, end = _row_range(plan, row_begin, row_end)
-    if n_batch < 0 or k_inner < 0:
-        raise ValueError('n_batch and k_inner must not be negative')
+    c = cp.companion.lower()
+    own[c + '_dtype'] = _float_dtype(torch, cp.companion, C)
     if n_levels < 1:
         raise ValueError(f'n_levels {n_levels}: expected >= 1')
     if Q.numel() < cp.per_output * k_inner:
         raise ValueError(f'{cp.query} holds {Q.numel()} {cp.numbers}; '
                          f'k_inner is {k_inner}')
-    if x_src_fold:
-        _check_fold(plan.n_a, x_src_fold, x_outer_stride, c_outer_stride)
-    # (a launch without batches or outputs reads nothing; one with them reads
-    # whole columns)
-    columns = n_levels if k_inner > 0 else 0
-    _check_reach('X', X, plan.n_a, x_row_stride, x_batch_stride, 1, n_batch,
-                 columns, x_src_fold, x_outer_stride)
-    _check_reach(cp.companion, C, plan.n_a, c_row_stride, c_batch_stride, 1,
-                 n_batch, columns, x_src_fold, c_outer_stride)
-    _check_reach('Y', Y, plan.n_b, y_row_stride, y_batch_stride, 1, n_batch,
-                 k_inner)
-    _holds_csr(plan, ('rowptr', 'col', 'val'), cp.activity + ' reads it')
-    args = cp.args()
-    args.A = plan._csr_struct()
-    args.row_begin = row_begin
-    args.row_end = end
-    args.X = X.data_ptr()
-    args.x_dtype = x_dtype
-    args.x_row_stride = int(x_row_stride)
-    args.x_batch_stride = int(x_batch_stride)
-    args.x_src_fold = int(x_src_fold)
-    args.x_outer_stride = int(x_outer_stride)
-    args.n_levels = int(n_levels)
-    c = cp.companion.lower()
-    setattr(args, cp.companion, C.data_ptr())
-    setattr(args, c + '_dtype', c_dtype)
-    setattr(args, c + '_row_stride', int(c_row_stride))
-    setattr(args, c + '_batch_stride', int(c_batch_stride))
-    setattr(args, c + '_outer_stride', int(c_outer_stride))
-    setattr(args, cp.query, Q.data_ptr())
-    args.Y = Y.data_ptr()
-    args.y_row_stride = int(y_row_stride)
-    args.y_batch_stride = int(y_batch_stride)
-    args.n_batch = int(n_batch)
-    args.k_inner = int(k_inner)
-    args.threshold = float(threshold)
-    for name, value in own.items():
-        setattr(args, name, value)
-    _launch(torch, plan, getattr(lib, cp.entry), cp.entry, args)
+    own.update({'n_levels': int(n_levels),
+                c + '_row_stride': int(c_row_stride),
+                c + '_batch_stride': int(c_batch_stride),
+                c + '_outer_stride': int(c_outer_stride)})
+    _row_pass(
+        cp.args, cp.entry, plan, cp.activity + ' reads it',
+        [_Source('X', X, x_row_stride, x_batch_stride, 1, x_outer_stride),
+         _Source(cp.companion, C, c_row_stride, c_batch_stride, 1,
+                 c_outer_stride)],
+        [('Y', Y)], own, beside=[(cp.query, Q)],
+        n_batch=n_batch, k_inner=k_inner, y_row_stride=y_row_stride,
+        y_batch_stride=y_batch_stride, row_begin=row_begin, row_end=row_end,
+        x_src_fold=x_src_fold, threshold=threshold,
+        # (a launch without batches or outputs reads nothing; one with them
+        # reads whole columns)
+        depth=n_levels if k_inner > 0 else 0)
 
 
 def levels_strided(plan, X, Z, T, Y, *, n_batch, n_levels, k_inner,
@@ -2504,12 +1838,9 @@ def layers_strided(plan, X, H, bounds, Y, *, n_batch, n_levels, k_inner,
         reduce=_reduce_code(reduce))
 
 
-def _check_basis(torch, plan, name, B, rows):
+def _check_basis(torch, name, B, rows):
     """A basis of the vector launch: a contiguous float64 ``(rows, 5)``
-    tensor on the plan's device."""
-    if B.device != plan.device:
-        raise ValueError('U, V, BA, BB, YU, YV and the plan must live on '
-                         'the same device')
+    tensor (:func:`_row_pass` holds it to the plan's device)."""
     if B.dtype != torch.float64:
         raise TypeError(f'{name} must be float64')
     if tuple(B.shape) != (rows, 5) or not B.is_contiguous():
@@ -2536,56 +1867,22 @@ def vector_strided(plan, U, V, BA, BB, YU, YV, *, n_batch, k_inner,
     served as the one matrix it is.
     """
     torch = _torch()
-    lib = load_library()
     _one_device(plan, 'the vector remap')
-    for name, t in (('U', U), ('V', V), ('YU', YU), ('YV', YV)):
-        if t.device != plan.device:
-            raise ValueError('U, V, BA, BB, YU, YV and the plan must live '
-                             'on the same device')
-        if not t.is_contiguous():
-            raise ValueError(f'{name} must be contiguous')
-    if YU.dtype != torch.float64 or YV.dtype != torch.float64:
-        raise TypeError('YU and YV must be float64')
-    x_dtype = _float_dtype(torch, 'U', U)
+    _float_dtype(torch, 'U', U)
     if V.dtype != U.dtype:
         raise TypeError(f'U and V must have one dtype, not {U.dtype} and '
                         f'{V.dtype}')
-    _check_basis(torch, plan, 'BA', BA, plan.n_a)
-    _check_basis(torch, plan, 'BB', BB, plan.n_b)
-    row_begin, end = _row_range(plan, row_begin, row_end)
-    if n_batch < 0 or k_inner < 0:
-        raise ValueError('n_batch and k_inner must not be negative')
-    if x_src_fold:
-        _check_fold(plan.n_a, x_src_fold, x_outer_stride)
-    for name, t in (('U', U), ('V', V)):
-        _check_reach(name, t, plan.n_a, x_row_stride, x_batch_stride, 1,
-                     n_batch, k_inner, x_src_fold, x_outer_stride)
-    for name, t in (('YU', YU), ('YV', YV)):
-        _check_reach(name, t, plan.n_b, y_row_stride, y_batch_stride, 1,
-                     n_batch, k_inner)
-    _holds_csr(plan, ('rowptr', 'col', 'val'),
-               'the vector launch reads it')
-    args = _VectorArgs()
-    args.A = plan._csr_struct()
-    args.row_begin = row_begin
-    args.row_end = end
-    args.U = U.data_ptr()
-    args.V = V.data_ptr()
-    args.x_dtype = x_dtype
-    args.x_row_stride = int(x_row_stride)
-    args.x_batch_stride = int(x_batch_stride)
-    args.x_src_fold = int(x_src_fold)
-    args.x_outer_stride = int(x_outer_stride)
-    args.BA = BA.data_ptr()
-    args.BB = BB.data_ptr()
-    args.YU = YU.data_ptr()
-    args.YV = YV.data_ptr()
-    args.y_row_stride = int(y_row_stride)
-    args.y_batch_stride = int(y_batch_stride)
-    args.n_batch = int(n_batch)
-    args.k_inner = int(k_inner)
-    args.threshold = float(threshold)
-    _launch(torch, plan, lib.remap_apply_vector, 'remap_apply_vector', args)
+    _check_basis(torch, 'BA', BA, plan.n_a)
+    _check_basis(torch, 'BB', BB, plan.n_b)
+    _row_pass(
+        _VectorArgs, 'remap_apply_vector', plan,
+        'the vector launch reads it',
+        [_Source(name, t, x_row_stride, x_batch_stride, 1, x_outer_stride)
+         for name, t in (('U', U), ('V', V))],
+        [('YU', YU), ('YV', YV)], {}, beside=[('BA', BA), ('BB', BB)],
+        n_batch=n_batch, k_inner=k_inner, y_row_stride=y_row_stride,
+        y_batch_stride=y_batch_stride, row_begin=row_begin, row_end=row_end,
+        x_src_fold=x_src_fold, threshold=threshold)
 
 
 def _prod(seq):
@@ -3424,1160 +2721,13 @@ def stream_copy(dst, src):
 
 
 # ---------------------------------------------------------------------------
-# conservative overlaps: what the four remap_overlap_* calls share
+# weight generation (geometry.py), under the names the package calls it by
 # ---------------------------------------------------------------------------
 
-def _mesh_struct(torch, arrays, keep):
-    """The ``remap_overlap_mesh`` of ``(verticesOnCell, nEdgesOnCell,
-    latVertex, lonVertex)``; the converted tensors its pointers look into
-    join ``keep``, which has to outlive the call."""
-    voc = arrays[0].to(torch.int32).contiguous()
-    noc = arrays[1].to(torch.int32).contiguous()
-    lat_v = arrays[2].to(torch.float64).contiguous()
-    lon_v = arrays[3].to(torch.float64).contiguous()
-    keep.extend((voc, noc, lat_v, lon_v))
-    return _OverlapMesh(voc.shape[0], lat_v.numel(), voc.shape[1], 0,
-                        voc.data_ptr(), noc.data_ptr(), lat_v.data_ptr(),
-                        lon_v.data_ptr())
-
-
-def _overlap(kind, dev, sides, n_a, n_b, flag, n_dst, timing, counter_words=0,
-             b_padded=True, arg_errors=False, phases=()):
-    """
-    ``remap_overlap_<kind>_sizes``, the workspace and the outputs, then
-    ``remap_overlap_<kind>`` on the current stream of ``dev``: ``sides`` are
-    the call's leading structs (one geometry, or sides a and b, of ``n_a``
-    and ``n_b`` cells; the caller keeps the tensors behind them alive),
-    ``flag`` its direction argument and ``n_dst`` the number of destination
-    cells that follows from it.  ``counter_words``: the int64 words of the
-    counter ``_sizes`` takes (0: it takes none).  ``b_padded=False``: the
-    b-area array has exactly ``n_b`` elements.  ``arg_errors``: the library's
-    ``REMAP_ERR_ARG`` is a ``ValueError``.  ``phases``: with ``timing`` the
-    call goes through ``remap_overlap_<kind>_timed``, which reports these.
-
-    Returns ``(dst, src, A, frac_b, a_area, b_area)`` cut to their lengths;
-    ``timing`` receives ``n_pairs``, ``ms`` and the phases.
-    """
-    torch = _torch()
-    lib = load_library()
-    what = f'remap_overlap_{kind}'
-
-    def check(rc, name):
-        if arg_errors and rc == -1:     # REMAP_ERR_ARG
-            raise ValueError(
-                f'{name}: ' +
-                lib.remap_last_error().decode('utf-8', 'replace'))
-        _check(rc, name)
-
-    def empty(n, dtype=torch.float64):
-        # (never empty: the C side wants every output pointer, even for a
-        # mesh without cells)
-        return torch.empty(max(n, 1), dtype=dtype, device=dev)
-    sides = [ctypes.byref(s) for s in sides]
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        counter = []
-        if counter_words:
-            words = torch.zeros(counter_words, dtype=torch.int64, device=dev)
-            counter = [_ptr(words)]
-        n_pairs = ctypes.c_int64()
-        nbytes = ctypes.c_size_t()
-        check(getattr(lib, what + '_sizes')(
-            *sides, *counter, ctypes.byref(n_pairs), ctypes.byref(nbytes),
-            stream), what + '_sizes')
-        n = n_pairs.value
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        dst, src, A = empty(n, torch.int32), empty(n, torch.int32), empty(n)
-        a_area = empty(n_a)
-        b_area = empty(n_b) if b_padded else \
-            torch.empty(n_b, dtype=torch.float64, device=dev)
-        frac_b = empty(n_dst)
-        n_entries = ctypes.c_int64()
-        args = (*sides, 1 if flag else 0, n, _ptr(ws), nbytes.value,
-                _ptr(dst), _ptr(src), _ptr(A), _ptr(frac_b), _ptr(a_area),
-                _ptr(b_area), ctypes.byref(n_entries))
-        if phases and timing is not None:
-            what += '_timed'
-            ms = (ctypes.c_float * len(phases))()
-            args += (ms,)
-        with _gpu_ms(torch, timing):
-            check(getattr(lib, what)(*args, stream), what)
-        if timing is not None:
-            timing['n_pairs'] = n
-            if phases:
-                timing.update(zip(phases, (float(x) for x in ms)))
-        # (as in nearest_points: torch's allocator keeps the workspace for
-        # this stream, so later work is ordered behind the call)
-        del ws
-        m = n_entries.value
-    return (dst[:m], src[:m], A[:m], frac_b[:n_dst], a_area[:n_a],
-            b_area[:n_b])
-
-
-# ---------------------------------------------------------------------------
-# conservative overlaps: MPAS cell mesh <-> lat-lon grid
-# ---------------------------------------------------------------------------
-
-def overlap_latlon(vertices_on_cell, n_edges_on_cell, lat_vertex, lon_vertex,
-                   lat_corner, lon_corner, lat_slack, dst_is_mesh,
-                   timing=None):
-    """
-    The overlap areas between the cells of an MPAS mesh (``verticesOnCell``
-    1-based, ``nEdgesOnCell``, ``latVertex`` / ``lonVertex`` in radians) and
-    the cells of a lat-lon grid (corner axes in radians; cell ``j * n_lon +
-    i``), through ``remap_overlap_latlon`` (``include/remap_hip.h``).  All
-    tensors on one HIP device; ``lat_slack``: the grid's great-circle bulge
-    (radians).
-
-    Returns ``(dst, src, A, frac_b, mesh_area, grid_area)``: 0-based int32
-    indices and float64 areas (steradians) of the entries sorted by
-    ``(dst, src)`` -- the mesh is the destination when ``dst_is_mesh`` --
-    ``frac_b`` per destination cell, and both sets of polygon areas.
-    ``timing``: a dict that receives ``n_pairs`` and the GPU ``ms`` of the
-    overlap call (events on the stream).
-    """
-    torch = require_gpu()
-    dev = vertices_on_cell.device
-    voc = vertices_on_cell.to(torch.int32).contiguous()
-    noc = n_edges_on_cell.to(torch.int32).contiguous()
-    lat_v = lat_vertex.to(torch.float64).contiguous()
-    lon_v = lon_vertex.to(torch.float64).contiguous()
-    lat_c = lat_corner.to(torch.float64).contiguous()
-    lon_c = lon_corner.to(torch.float64).contiguous()
-    n_cells, max_edges = voc.shape
-    n_lat, n_lon = lat_c.numel() - 1, lon_c.numel() - 1
-    geom = _OverlapGeom(n_cells, lat_v.numel(), n_lat, n_lon, max_edges, 0,
-                        float(lat_slack), voc.data_ptr(), noc.data_ptr(),
-                        lat_v.data_ptr(), lon_v.data_ptr(), lat_c.data_ptr(),
-                        lon_c.data_ptr())
-    n_grid = n_lat * n_lon
-    return _overlap('latlon', dev, (geom,), n_cells, n_grid, dst_is_mesh,
-                    n_cells if dst_is_mesh else n_grid, timing,
-                    counter_words=2, b_padded=False)
-
-
-# ---------------------------------------------------------------------------
-# conservative overlaps: MPAS cell mesh <-> MPAS cell mesh
-# (overlap_meshes, like overlap_pieces and overlap_grids below, builds its two
-# side structs and leaves the rest to _overlap)
-# ---------------------------------------------------------------------------
-
-def overlap_meshes(mesh_a, mesh_b, dst_is_b, timing=None):
-    """
-    The overlap areas between the cells of two MPAS meshes, each given as
-    ``(verticesOnCell 1-based, nEdgesOnCell, latVertex, lonVertex)`` (radians)
-    tensors on one HIP device, through ``remap_overlap_meshes``
-    (``include/remap_hip.h``).  Mesh a's polygons are clipped by mesh b's,
-    which must be convex; both directions use the same overlap list.
-
-    Returns ``(dst, src, A, frac_b, a_area, b_area)``: 0-based int32 indices
-    and float64 areas (steradians) of the entries sorted by ``(dst, src)``
-    -- mesh b is the destination when ``dst_is_b`` -- ``frac_b`` per
-    destination cell, and both sets of polygon areas.  ``timing``: a dict
-    that receives ``n_pairs`` (candidates) and the GPU ``ms`` of the overlap
-    call (events on the stream).
-    """
-    torch = require_gpu()
-    keep = []
-    ga = _mesh_struct(torch, mesh_a, keep)
-    gb = _mesh_struct(torch, mesh_b, keep)
-    n_a, n_b = ga.n_cells, gb.n_cells
-    return _overlap('meshes', mesh_a[0].device, (ga, gb), n_a, n_b, dst_is_b,
-                    n_b if dst_is_b else n_a, timing, counter_words=4)
-
-
-# ---------------------------------------------------------------------------
-# conservative overlaps between cells that come in convex pieces
-# ---------------------------------------------------------------------------
-
-#: the phases ``remap_overlap_pieces_timed`` reports, in order
-PIECES_PHASES = ('prep_ms', 'pairs_ms', 'clip_ms', 'sort_ms', 'merge_ms')
-
-
-def overlap_pieces(pieces_a, pieces_b, dst_is_b, timing=None):
-    """
-    The overlap areas between the cells of two polygon soups, each cell given
-    as one or more convex pieces, through ``remap_overlap_pieces``
-    (``include/remap_hip.h``).  A side is ``(verticesOnCell 1-based,
-    nEdgesOnCell, latVertex, lonVertex, parent, n_parents)``: the first four
-    describe the PIECES as :func:`overlap_meshes` takes a mesh, ``parent``
-    (int32, 0-based, non-decreasing, every cell at least once) says which
-    cell a piece belongs to -- ``None``: piece k is cell k, and ``n_parents``
-    is the number of pieces.  Side a's pieces are clipped by side b's, which
-    must be convex.
-
-    Returns ``(dst, src, A, frac_b, a_area, b_area)`` as
-    :func:`overlap_meshes` does, in cells: the areas of the piece pairs of a
-    pair of cells added in ascending (dst piece, src piece) order.  With
-    ``parent=None`` on both sides the bytes are those of
-    :func:`overlap_meshes`.  ``timing``: a dict that receives ``n_pairs``
-    (candidate piece pairs), the GPU ``ms`` of the call and its phases
-    (:data:`PIECES_PHASES`, the merge ``merge_ms``) from
-    ``remap_overlap_pieces_timed``.
-
-    A ``parent`` that decreases, leaves ``[0, n_parents)`` or skips a cell is
-    a ``ValueError`` (the library's ``REMAP_ERR_ARG``).
-    """
-    torch = require_gpu()
-    dev = pieces_a[0].device
-    keep = []
-
-    def side(p):
-        mesh = _mesh_struct(torch, p, keep)
-        parent, n_parents = p[4], int(p[5])
-        ptr = None
-        if parent is not None:
-            parent = parent.to(device=dev, dtype=torch.int32).contiguous()
-            if parent.numel() != mesh.n_cells:
-                raise ValueError(
-                    f'overlap_pieces: {parent.numel()} parents for '
-                    f'{mesh.n_cells} pieces')
-            keep.append(parent)
-            ptr = parent.data_ptr()
-        return _OverlapPieces(mesh, n_parents, ptr)
-    ga, gb = side(pieces_a), side(pieces_b)
-    n_a, n_b = ga.n_parents, gb.n_parents
-    return _overlap('pieces', dev, (ga, gb), n_a, n_b, dst_is_b,
-                    n_b if dst_is_b else n_a, timing, counter_words=4,
-                    arg_errors=True, phases=PIECES_PHASES)
-
-
-# ---------------------------------------------------------------------------
-# conservative overlaps with a structured 2-D grid on one side or both
-# ---------------------------------------------------------------------------
-
-def overlap_grids(side_a, side_b, dst_is_b, timing=None):
-    """
-    The overlap areas between the cells of two sides, at least one of them a
-    structured 2-D grid, through ``remap_overlap_grids``
-    (``include/remap_hip.h``).  A side is a grid ``(lat_corner, lon_corner)``
-    -- two ``(ny + 1, nx + 1)`` tensors in radians, cell ``j * nx + i`` --
-    or an MPAS mesh ``(verticesOnCell 1-based, nEdgesOnCell, latVertex,
-    lonVertex)`` as in :func:`overlap_meshes`; all tensors on one HIP device.
-    Side a's polygons are clipped by side b's, which must be convex; both
-    directions use the same overlap list.
-
-    Returns ``(dst, src, A, frac_b, a_area, b_area)`` as
-    :func:`overlap_meshes` does -- side b is the destination when
-    ``dst_is_b``.  ``timing``: a dict that receives ``n_pairs`` (candidates)
-    and the GPU ``ms`` of the overlap call (events on the stream).
-    """
-    torch = require_gpu()
-    keep = []
-
-    def side(arrays):
-        if len(arrays) == 2:
-            lat = arrays[0].to(torch.float64).contiguous()
-            lon = arrays[1].to(torch.float64).contiguous()
-            if lat.dim() != 2 or lat.shape != lon.shape or \
-                    min(lat.shape) < 2:
-                raise ValueError(
-                    f'grid corners of shapes {tuple(lat.shape)} and '
-                    f'{tuple(lon.shape)}: expected two (ny + 1, nx + 1) '
-                    f'arrays')
-            g = _OverlapGrid(lat.shape[0] - 1, lat.shape[1] - 1,
-                             lat.data_ptr(), lon.data_ptr())
-            keep.extend((lat, lon, g))
-            return _OverlapSide(None, ctypes.pointer(g)), int(g.ny * g.nx)
-        m = _mesh_struct(torch, arrays, keep)
-        keep.append(m)
-        return _OverlapSide(ctypes.pointer(m), None), int(m.n_cells)
-    (ga, n_a), (gb, n_b) = side(side_a), side(side_b)
-    return _overlap('grids', side_a[0].device, (ga, gb), n_a, n_b, dst_is_b,
-                    n_b if dst_is_b else n_a, timing)
-
-
-# ---------------------------------------------------------------------------
-# nearest source point of every destination point (ESMF's neareststod)
-# ---------------------------------------------------------------------------
-
-def nearest_points(src_xyz, dst_xyz, timing=None, phases=False):
-    """
-    The index (0-based, ``int32``) of the source point nearest to every
-    destination point, through ``remap_nearest`` (``include/remap_hip.h``):
-    ``src_xyz (n_src, 3)`` and ``dst_xyz (n_dst, 3)`` are contiguous fp64
-    tensors on one HIP device, finite.  Exact: the minimum of ``d2 = (dx*dx +
-    dy*dy) + dz*dz`` in fp64 in that order, the lowest source index among
-    equal ``d2``; two calls give identical bytes.  Asynchronous on the
-    current stream.
-
-    ``timing``: a dict that receives the GPU ``ms`` of the call (events on
-    the stream).  With ``phases=True`` (measurements only: the library then
-    waits for the walk before it returns) the call goes through
-    ``remap_nearest_timed`` and the dict also receives ``sort_ms``,
-    ``pyramid_ms`` and ``walk_ms``.
-    """
-    torch = require_gpu()
-    lib = load_library()
-    for name, t in (('src_xyz', src_xyz), ('dst_xyz', dst_xyz)):
-        if not torch.is_tensor(t) or not t.is_cuda or \
-                t.dtype != torch.float64 or t.dim() != 2 or \
-                t.shape[1] != 3 or not t.is_contiguous():
-            raise ValueError(
-                f'{name}: expected a contiguous (n, 3) float64 tensor on a '
-                f'HIP device')
-    if src_xyz.device != dst_xyz.device:
-        raise ValueError(
-            f'src_xyz on {src_xyz.device}, dst_xyz on {dst_xyz.device}: '
-            f'expected one device')
-    n_src, n_dst = src_xyz.shape[0], dst_xyz.shape[0]
-    if n_src < 1:
-        raise ValueError('nearest_points needs at least one source point')
-    if phases and timing is None:
-        raise ValueError('phases=True needs a timing dict to fill')
-    dev = src_xyz.device
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        nbytes = ctypes.c_size_t()
-        _check(lib.remap_nearest_workspace(n_src, n_dst,
-                                           ctypes.byref(nbytes)),
-               'remap_nearest_workspace')
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        out = torch.empty(n_dst, dtype=torch.int32, device=dev)
-        with _gpu_ms(torch, timing):
-            if phases:
-                ms = (ctypes.c_float * 3)()
-                _check(lib.remap_nearest_timed(
-                    _ptr(src_xyz), n_src, _ptr(dst_xyz), n_dst, _ptr(out),
-                    _ptr(ws), nbytes.value, ms, stream),
-                    'remap_nearest_timed')
-            else:
-                _check(lib.remap_nearest(
-                    _ptr(src_xyz), n_src, _ptr(dst_xyz), n_dst, _ptr(out),
-                    _ptr(ws), nbytes.value, stream), 'remap_nearest')
-        if phases:
-            timing['sort_ms'], timing['pyramid_ms'], \
-                timing['walk_ms'] = (float(v) for v in ms)
-        # the workspace's memory returns to torch's allocator, which keeps it
-        # for this stream: later work on the stream is ordered behind the walk
-        del ws
-    return out
-
-
-def nearest_k_points(src_xyz, dst_xyz, k, timing=None):
-    """
-    The ``k`` nearest source points of every destination point, through
-    ``remap_nearest_k`` (``include/remap_hip.h``): ``(idx, d2)``, an
-    ``int32`` and a ``float64`` tensor of shape ``(n_dst, k)``.  Row ``i``
-    holds the ``min(k, n_src)`` sources that come first in ``(d2, index)``
-    order, ascending, with ``d2`` as in :func:`nearest_points`; the slots
-    behind them hold index -1 and ``d2`` = +inf.  The tensors are as for
-    :func:`nearest_points`, ``k`` is 1 .. ``NEAREST_K_MAX``; exact, two calls
-    give identical bytes, ``k = 1`` gives :func:`nearest_points`' indices.
-    Asynchronous on the current stream.  ``timing``: a dict that receives
-    the GPU ``ms`` of the call.
-    """
-    torch = require_gpu()
-    lib = load_library()
-    for name, t in (('src_xyz', src_xyz), ('dst_xyz', dst_xyz)):
-        if not torch.is_tensor(t) or not t.is_cuda or \
-                t.dtype != torch.float64 or t.dim() != 2 or \
-                t.shape[1] != 3 or not t.is_contiguous():
-            raise ValueError(
-                f'{name}: expected a contiguous (n, 3) float64 tensor on a '
-                f'HIP device')
-    if src_xyz.device != dst_xyz.device:
-        raise ValueError(
-            f'src_xyz on {src_xyz.device}, dst_xyz on {dst_xyz.device}: '
-            f'expected one device')
-    n_src, n_dst = src_xyz.shape[0], dst_xyz.shape[0]
-    if n_src < 1:
-        raise ValueError('nearest_k_points needs at least one source point')
-    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or \
-            not 1 <= k <= NEAREST_K_MAX:
-        raise ValueError(f'k = {k!r}: expected an integer from 1 to '
-                         f'{NEAREST_K_MAX}')
-    k = int(k)
-    dev = src_xyz.device
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        nbytes = ctypes.c_size_t()
-        _check(lib.remap_nearest_k_workspace(n_src, n_dst, k,
-                                             ctypes.byref(nbytes)),
-               'remap_nearest_k_workspace')
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        idx = torch.empty((n_dst, k), dtype=torch.int32, device=dev)
-        d2 = torch.empty((n_dst, k), dtype=torch.float64, device=dev)
-        with _gpu_ms(torch, timing):
-            _check(lib.remap_nearest_k(
-                _ptr(src_xyz), n_src, _ptr(dst_xyz), n_dst, k, _ptr(idx),
-                _ptr(d2), _ptr(ws), nbytes.value, stream), 'remap_nearest_k')
-        # (as in nearest_points: torch's allocator keeps the workspace for
-        # this stream)
-        del ws
-    return idx, d2
-
-
-# ---------------------------------------------------------------------------
-# the triangle that holds every point (bilinear from an MPAS mesh)
-# ---------------------------------------------------------------------------
-
-def locate_in_triangles(xyz, tri, points, tol=1e-12, timing=None,
-                        phases=False):
-    """
-    For every point the lowest-numbered spherical triangle that holds it and
-    the weights of its three corners, through ``remap_locate``
-    (``include/remap_hip.h`` has the definition): ``xyz (n_nodes, 3)`` and
-    ``points (n_pts, 3)`` are contiguous fp64 tensors, ``tri (n_tri, 3)`` a
-    contiguous int32 tensor of node ids, all on one HIP device; nodes and
-    points are unit vectors.  Returns ``(found int32 (n_pts,), weights fp64
-    (n_pts, 3))`` on that device: ``found`` is -1, and the weights zero, where
-    no triangle holds the point.  Exact in fp64 (the barycentric coordinates
-    of the point's central projection, a corner accepted down to ``-tol``);
-    two calls give identical bytes.  Asynchronous on the current stream.
-
-    ``timing``: a dict that receives the GPU ``ms`` of the call (events on
-    the stream).  With ``phases=True`` (measurements only: the library then
-    waits for the walk before it returns) the call goes through
-    ``remap_locate_timed`` and the dict also receives ``sort_ms``,
-    ``setup_ms`` and ``walk_ms``.
-    """
-    torch = require_gpu()
-    lib = load_library()
-    for name, t, dtype in (('xyz', xyz, torch.float64),
-                           ('tri', tri, torch.int32),
-                           ('points', points, torch.float64)):
-        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or \
-                t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
-            kind = 'int32' if dtype == torch.int32 else 'float64'
-            raise ValueError(
-                f'{name}: expected a contiguous (n, 3) {kind} tensor on a '
-                f'HIP device')
-    if not (xyz.device == tri.device == points.device):
-        raise ValueError(
-            f'xyz on {xyz.device}, tri on {tri.device}, points on '
-            f'{points.device}: expected one device')
-    n_nodes, n_tri, n_pts = xyz.shape[0], tri.shape[0], points.shape[0]
-    if n_tri < 1 or n_nodes < 1:
-        raise ValueError('locate_in_triangles needs at least one triangle '
-                         'and one node')
-    tol = float(tol)
-    if not tol >= 0.0:
-        raise ValueError(f'tol {tol}: expected a number >= 0')
-    if phases and timing is None:
-        raise ValueError('phases=True needs a timing dict to fill')
-    dev = xyz.device
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        nbytes = ctypes.c_size_t()
-        _check(lib.remap_locate_workspace(n_nodes, n_tri, n_pts,
-                                          ctypes.byref(nbytes)),
-               'remap_locate_workspace')
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        found = torch.empty(n_pts, dtype=torch.int32, device=dev)
-        weights = torch.empty((n_pts, 3), dtype=torch.float64, device=dev)
-        with _gpu_ms(torch, timing):
-            if phases:
-                ms = (ctypes.c_float * 3)()
-                _check(lib.remap_locate_timed(
-                    _ptr(xyz), n_nodes, _ptr(tri), n_tri, _ptr(points),
-                    n_pts, tol, _ptr(found), _ptr(weights), _ptr(ws),
-                    nbytes.value, ms, stream), 'remap_locate_timed')
-            else:
-                _check(lib.remap_locate(
-                    _ptr(xyz), n_nodes, _ptr(tri), n_tri, _ptr(points),
-                    n_pts, tol, _ptr(found), _ptr(weights), _ptr(ws),
-                    nbytes.value, stream), 'remap_locate')
-        if phases:
-            timing['sort_ms'], timing['setup_ms'], \
-                timing['walk_ms'] = (float(v) for v in ms)
-        # (as in nearest_points: torch's allocator keeps the workspace for
-        # this stream, so later work is ordered behind the walk)
-        del ws
-    return found, weights
-
-
-# ---------------------------------------------------------------------------
-# the quad of four cell centres that holds every point (bilinear from a grid
-# given by 2-D latitude / longitude arrays)
-# ---------------------------------------------------------------------------
-
-def locate_in_quads(nodes, points, periodic=False, tol=1e-10, timing=None,
-                    phases=False):
-    """
-    For every point the lowest-numbered quad of four neighbouring cell
-    centres whose bilinear patch holds it, and the patch's weights of the
-    four corners, through ``remap_quads`` (``include/remap_hip.h`` has the
-    definition): ``nodes (ny, nx, 3)`` and ``points (n_pts, 3)`` are
-    contiguous fp64 tensors of unit vectors on one HIP device, ``ny >= 2``
-    and ``nx >= 2``; with ``periodic`` column ``nx - 1`` closes onto column
-    0.  Quad ``k = j * nqx + i`` (``nqx = nx - 1 + periodic``) has the corners
-    ``(j, i)``, ``(j, i1)``, ``(j + 1, i1)``, ``(j + 1, i)`` with ``i1 = (i +
-    1) % nx``, the order of the weights.  Returns ``(found int32 (n_pts,),
-    weights fp64 (n_pts, 4))`` on that device: ``found`` is -1, and the
-    weights zero, where no quad holds the point.  Exact in fp64 (a Newton
-    solve per point and quad with a stopping rule of its own, the patch
-    coordinates accepted up to ``1 + tol``); two calls give identical bytes.
-    Asynchronous on the current stream.
-
-    ``timing``: a dict that receives the GPU ``ms`` of the call (events on
-    the stream).  With ``phases=True`` (measurements only: the library then
-    waits for the walk before it returns) the call goes through
-    ``remap_quads_timed`` and the dict also receives ``sort_ms``,
-    ``setup_ms`` and ``walk_ms``.
-    """
-    torch = require_gpu()
-    lib = load_library()
-    for name, t, dim in (('nodes', nodes, 3), ('points', points, 2)):
-        if not torch.is_tensor(t) or not t.is_cuda or \
-                t.dtype != torch.float64 or t.dim() != dim or \
-                t.shape[-1] != 3 or not t.is_contiguous():
-            shape = '(ny, nx, 3)' if dim == 3 else '(n, 3)'
-            raise ValueError(
-                f'{name}: expected a contiguous {shape} float64 tensor on a '
-                f'HIP device')
-    if nodes.device != points.device:
-        raise ValueError(
-            f'nodes on {nodes.device}, points on {points.device}: expected '
-            f'one device')
-    ny, nx, n_pts = nodes.shape[0], nodes.shape[1], points.shape[0]
-    if ny < 2 or nx < 2:
-        raise ValueError(f'locate_in_quads needs at least 2 x 2 nodes, not '
-                         f'{ny} x {nx}')
-    periodic = 1 if periodic else 0
-    tol = float(tol)
-    if not tol >= 0.0:
-        raise ValueError(f'tol {tol}: expected a number >= 0')
-    if phases and timing is None:
-        raise ValueError('phases=True needs a timing dict to fill')
-    dev = nodes.device
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        nbytes = ctypes.c_size_t()
-        _check(lib.remap_quads_workspace(ny, nx, periodic, n_pts,
-                                         ctypes.byref(nbytes)),
-               'remap_quads_workspace')
-        ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        found = torch.empty(n_pts, dtype=torch.int32, device=dev)
-        weights = torch.empty((n_pts, 4), dtype=torch.float64, device=dev)
-        with _gpu_ms(torch, timing):
-            if phases:
-                ms = (ctypes.c_float * 3)()
-                _check(lib.remap_quads_timed(
-                    _ptr(nodes), ny, nx, periodic, _ptr(points), n_pts, tol,
-                    _ptr(found), _ptr(weights), _ptr(ws), nbytes.value, ms,
-                    stream), 'remap_quads_timed')
-            else:
-                _check(lib.remap_quads(
-                    _ptr(nodes), ny, nx, periodic, _ptr(points), n_pts, tol,
-                    _ptr(found), _ptr(weights), _ptr(ws), nbytes.value,
-                    stream), 'remap_quads')
-        if phases:
-            timing['sort_ms'], timing['setup_ms'], \
-                timing['walk_ms'] = (float(v) for v in ms)
-        # (as in nearest_points: torch's allocator keeps the workspace for
-        # this stream, so later work is ordered behind the walk)
-        del ws
-    return found, weights
-
-
-# ---------------------------------------------------------------------------
-# cells widened about their centres (expand_dist / expand_factor)
-# ---------------------------------------------------------------------------
-
-def expand_cells(centre_lat, centre_lon, corner_lat, corner_lon, count,
-                 expand_dist=None, expand_factor=None, timing=None):
-    """
-    The corners of every cell moved away from the cell's centre, through
-    ``remap_expand_cells`` (``include/remap_hip.h`` has the definition and
-    its three rules; :func:`pyremap_amd.weights.expand_cells` is the same
-    statement in numpy): ``centre_lat`` / ``centre_lon`` ``(n,)``,
-    ``corner_lat`` / ``corner_lon`` ``(n, width)`` fp64 tensors in radians
-    and ``count (n,)`` integers, all on one HIP device.  ``expand_dist``
-    (metres; ``None``: 0) and ``expand_factor`` (``None``: 1) are numbers or
-    ``(n,)`` arrays / tensors, one value per cell.
-
-    Returns ``(lat, lon)``, two new ``(n, width)`` fp64 tensors on that
-    device; slots beyond ``count[i]`` hold copies.  Runs on the current
-    stream and waits for it (the status is read back).  ``n = 0`` is legal.
-    A NaN, a count outside ``[0, width]`` or a corner whose new distance
-    ``factor * d + dist`` is not positive is a ``ValueError`` that names the
-    first such cell (the library's ``REMAP_ERR_ARG``).  ``timing``: a dict
-    that receives the GPU ``ms`` of the call (events on the stream).
-    """
-    torch = require_gpu()
-    lib = load_library()
-    if not torch.is_tensor(corner_lat) or not corner_lat.is_cuda or \
-            corner_lat.dim() != 2 or corner_lat.shape[1] < 1:
-        raise ValueError('corner_lat: expected an (n, width) tensor on a HIP '
-                         'device, width >= 1')
-    dev = corner_lat.device
-    n, width = corner_lat.shape
-
-    def f64(name, t, shape):
-        if not torch.is_tensor(t) or t.device != dev or \
-                tuple(t.shape) != shape:
-            raise ValueError(
-                f'{name}: expected a tensor of shape {shape} on {dev}')
-        return t.to(torch.float64).contiguous()
-
-    def per_cell(name, value, default):
-        if value is None:
-            value = default
-        if not torch.is_tensor(value):
-            value = torch.as_tensor(np.asarray(value, dtype=np.float64))
-        value = value.to(device=dev, dtype=torch.float64).contiguous()
-        if value.dim() == 0:
-            return value.reshape(1), 0
-        if tuple(value.shape) != (n,):
-            raise ValueError(
-                f'{name} of shape {tuple(value.shape)}: expected a number '
-                f'or one value for each of the {n} cells')
-        # (a one-cell array has one value either way)
-        return (value, 1) if n > 0 else (value.new_zeros(1), 0)
-    corner_lat = f64('corner_lat', corner_lat, (n, width))
-    corner_lon = f64('corner_lon', corner_lon, (n, width))
-    centre_lat = f64('centre_lat', centre_lat, (n,))
-    centre_lon = f64('centre_lon', centre_lon, (n,))
-    if not torch.is_tensor(count) or count.device != dev or \
-            tuple(count.shape) != (n,) or count.dtype.is_floating_point:
-        raise ValueError(f'count: expected {n} integers on {dev}')
-    count = count.to(torch.int32).contiguous()
-    dist, dist_stride = per_cell('expand_dist', expand_dist, 0.0)
-    factor, factor_stride = per_cell('expand_factor', expand_factor, 1.0)
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        out_lat = torch.empty_like(corner_lat)
-        out_lon = torch.empty_like(corner_lon)
-        status = torch.zeros(2, dtype=torch.int32, device=dev)
-        with _gpu_ms(torch, timing):
-            rc = lib.remap_expand_cells(
-                n, width, _ptr(centre_lat), _ptr(centre_lon),
-                _ptr(corner_lat), _ptr(corner_lon), _ptr(count), _ptr(dist),
-                dist_stride, _ptr(factor), factor_stride, _ptr(out_lat),
-                _ptr(out_lon), _ptr(status), stream)
-            if rc == -1:     # REMAP_ERR_ARG
-                raise ValueError(
-                    lib.remap_last_error().decode('utf-8', 'replace'))
-            _check(rc, 'remap_expand_cells')
-    return out_lat, out_lon
-
-
-# ---------------------------------------------------------------------------
-# what a complete mapping file says about its grids: areas and frac_a
-# ---------------------------------------------------------------------------
-
-#: REMAP_CELL_AREAS_MAX_WIDTH
-CELL_AREAS_MAX_WIDTH = 32
-
-
-def cell_areas(corner_lat, corner_lon, count, timing=None):
-    """
-    The area in steradians of every cell given in SCRIP layout, through
-    ``remap_cell_areas`` (``include/remap_hip.h`` has the definition;
-    :func:`pyremap_amd.weights.cell_areas` is the same statement in numpy):
-    ``corner_lat`` / ``corner_lon`` ``(n, width)`` fp64 tensors in radians
-    and ``count (n,)`` integers on one HIP device, the first ``count[i]``
-    corners of row i the cell's great-circle polygon.  Returns a new ``(n,)``
-    fp64 tensor.  Runs on the current stream and waits for it.  A count
-    outside ``[0, width]`` is a ``ValueError`` that names the first such
-    cell (the library's ``REMAP_ERR_ARG``).  ``timing``: a dict that
-    receives the GPU ``ms`` of the call.
-    """
-    torch = require_gpu()
-    lib = load_library()
-    if not torch.is_tensor(corner_lat) or not corner_lat.is_cuda or \
-            corner_lat.dim() != 2 or corner_lat.shape[1] < 1:
-        raise ValueError('corner_lat: expected an (n, width) tensor on a HIP '
-                         'device, width >= 1')
-    dev = corner_lat.device
-    n, width = corner_lat.shape
-    if not torch.is_tensor(corner_lon) or corner_lon.device != dev or \
-            tuple(corner_lon.shape) != (n, width):
-        raise ValueError(f'corner_lon: expected a tensor of shape '
-                         f'{(n, width)} on {dev}')
-    if not torch.is_tensor(count) or count.device != dev or \
-            tuple(count.shape) != (n,) or count.dtype.is_floating_point:
-        raise ValueError(f'count: expected {n} integers on {dev}')
-    corner_lat = corner_lat.to(torch.float64).contiguous()
-    corner_lon = corner_lon.to(torch.float64).contiguous()
-    count = count.to(torch.int32).contiguous()
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        area = torch.empty(n, dtype=torch.float64, device=dev)
-        status = torch.zeros(2, dtype=torch.int32, device=dev)
-        with _gpu_ms(torch, timing):
-            rc = lib.remap_cell_areas(n, width, _ptr(corner_lat),
-                                      _ptr(corner_lon), _ptr(count),
-                                      _ptr(area), _ptr(status), stream)
-            if rc == -1:     # REMAP_ERR_ARG
-                raise ValueError(
-                    lib.remap_last_error().decode('utf-8', 'replace'))
-            _check(rc, 'remap_cell_areas')
-    return area
-
-
-def column_fractions(col, value, n_cols, denom=None, clamp=False,
-                     index_base=0, timing=None):
-    """
-    ``out[j] = sum of value[k] over col[k] - index_base == j``, added in
-    ascending k -- ``np.bincount(col, weights=value, minlength=n_cols)``, bit
-    for bit -- then divided by ``denom[j]`` when ``denom`` is given and cut
-    to at most 1 when ``clamp`` is set; a column without entries is 0.
-    Through ``remap_column_fractions`` (``include/remap_hip.h``;
-    :func:`pyremap_amd.weights.column_fractions` is the numpy statement):
-    ``col`` integers and ``value`` fp64, 1-D tensors of one length on one
-    HIP device, ``denom`` ``(n_cols,)`` fp64 there.  Returns a new
-    ``(n_cols,)`` fp64 tensor; two calls give the same bytes.  An entry whose
-    column is outside ``[0, n_cols)`` is a ``ValueError`` (the count is read
-    back, which waits for the stream).  ``timing``: a dict that receives the
-    GPU ``ms`` of the call.
-    """
-    torch = require_gpu()
-    lib = load_library()
-    if not torch.is_tensor(value) or not value.is_cuda or value.dim() != 1:
-        raise ValueError('value: expected a 1-D tensor on a HIP device')
-    dev = value.device
-    n = value.shape[0]
-    n_cols = int(n_cols)
-    if not torch.is_tensor(col) or col.device != dev or \
-            tuple(col.shape) != (n,) or col.dtype.is_floating_point:
-        raise ValueError(f'col: expected {n} integers on {dev}')
-    if n and (int(col.max()) > 2 ** 31 - 1 or int(col.min()) < -2 ** 31):
-        raise ValueError('col: beyond int32')
-    if denom is not None and (
-            not torch.is_tensor(denom) or denom.device != dev or
-            tuple(denom.shape) != (n_cols,)):
-        raise ValueError(f'denom: expected a tensor of shape ({n_cols},) on '
-                         f'{dev}')
-    col = col.to(torch.int32).contiguous()
-    value = value.to(torch.float64).contiguous()
-    if denom is not None:
-        denom = denom.to(torch.float64).contiguous()
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        need = ctypes.c_size_t(0)
-        _check(lib.remap_column_fractions_workspace(n, ctypes.byref(need)),
-               'remap_column_fractions_workspace')
-        workspace = torch.empty(max(need.value, 1), dtype=torch.uint8,
-                                device=dev)
-        out = torch.empty(n_cols, dtype=torch.float64, device=dev)
-        bad = torch.zeros(1, dtype=torch.int64, device=dev)
-        with _gpu_ms(torch, timing):
-            _check(lib.remap_column_fractions(
-                n, n_cols, _ptr(col), int(index_base), _ptr(value),
-                _ptr(denom), 1 if clamp else 0, _ptr(out), _ptr(bad),
-                _ptr(workspace), need.value, stream),
-                'remap_column_fractions')
-        n_bad = int(bad.item())
-    if n_bad:
-        raise ValueError(f'{n_bad} entries name a column outside '
-                         f'[0, {n_cols})')
-    return out
-
-
-# ---------------------------------------------------------------------------
-# second-order conservative maps: moments, gradient stencils, the assembly
-# ---------------------------------------------------------------------------
-
-#: REMAP_OVERLAP_MAX_EDGES
-OVERLAP_MAX_EDGES = 10
-
-
-def _scrip_cells(torch, name, corner_lat, corner_lon, count, dev=None):
-    """``(lat, lon, count)`` of one side in SCRIP layout, checked the way
-    :func:`cell_areas` checks its own and made fp64 / int32, contiguous."""
-    if not torch.is_tensor(corner_lat) or not corner_lat.is_cuda or \
-            corner_lat.dim() != 2 or corner_lat.shape[1] < 1 or \
-            (dev is not None and corner_lat.device != dev):
-        raise ValueError(
-            f'{name}corner_lat: expected an (n, width) tensor on '
-            f'{"a HIP device" if dev is None else dev}, width >= 1')
-    dev = corner_lat.device
-    n, width = corner_lat.shape
-    if not torch.is_tensor(corner_lon) or corner_lon.device != dev or \
-            tuple(corner_lon.shape) != (n, width):
-        raise ValueError(f'{name}corner_lon: expected a tensor of shape '
-                         f'{(n, width)} on {dev}')
-    if not torch.is_tensor(count) or count.device != dev or \
-            tuple(count.shape) != (n,) or count.dtype.is_floating_point:
-        raise ValueError(f'{name}count: expected {n} integers on {dev}')
-    return (corner_lat.to(torch.float64).contiguous(),
-            corner_lon.to(torch.float64).contiguous(),
-            count.to(torch.int32).contiguous())
-
-
-def _f64(torch, name, t, shape, dev):
-    if not torch.is_tensor(t) or t.device != dev or \
-            tuple(t.shape) != shape or not t.dtype.is_floating_point:
-        raise ValueError(f'{name}: expected a floating-point tensor of shape '
-                         f'{shape} on {dev}')
-    return t.to(torch.float64).contiguous()
-
-
-def _i32(torch, name, t, shape, dev):
-    if not torch.is_tensor(t) or t.device != dev or \
-            tuple(t.shape) != shape or t.dtype.is_floating_point:
-        raise ValueError(f'{name}: expected integers of shape {shape} on '
-                         f'{dev}')
-    return t.to(torch.int32).contiguous()
-
-
-def _checked(lib, rc, what):
-    if rc == -1:     # REMAP_ERR_ARG
-        raise ValueError(lib.remap_last_error().decode('utf-8', 'replace'))
-    _check(rc, what)
-
-
-def cell_moments(corner_lat, corner_lon, count, timing=None):
-    """
-    The first moment ``M = integral of r dA`` (unit sphere) of every cell
-    given in SCRIP layout, through ``remap_cell_moments``
-    (``include/remap_hip.h`` has the definition;
-    :func:`pyremap_amd.weights.cell_moments` is the same statement in
-    numpy): the arguments and the errors of :func:`cell_areas`.  Returns a
-    new ``(n, 3)`` fp64 tensor.  Runs on the current stream and waits for
-    it.  ``timing``: a dict that receives the GPU ``ms`` of the call.
-    """
-    torch = require_gpu()
-    lib = load_library()
-    corner_lat, corner_lon, count = _scrip_cells(torch, '', corner_lat,
-                                                 corner_lon, count)
-    dev = corner_lat.device
-    n, width = corner_lat.shape
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        moment = torch.empty((n, 3), dtype=torch.float64, device=dev)
-        status = torch.zeros(2, dtype=torch.int32, device=dev)
-        with _gpu_ms(torch, timing):
-            _checked(lib, lib.remap_cell_moments(
-                n, width, _ptr(corner_lat), _ptr(corner_lon), _ptr(count),
-                _ptr(moment), _ptr(status), stream), 'remap_cell_moments')
-    return moment
-
-
-def overlap_moments(dst, src, area, src_cells, src_area, src_moment,
-                    dst_cells, timing=None):
-    """
-    ``M_ij``, the first moment of (source cell ``src[e]`` n destination cell
-    ``dst[e]``) for every first-order entry, through
-    ``remap_overlap_moments`` (``include/remap_hip.h``): ``dst`` / ``src``
-    0-based integers and ``area`` (``A_ij``) as an ``overlap_*`` call returns
-    them, ``src_cells`` / ``dst_cells`` the two sides as ``(corner_lat,
-    corner_lon, count)`` in SCRIP layout (radians, width at most
-    ``OVERLAP_MAX_EDGES``: an :class:`EngineError` otherwise), ``src_area``
-    ``(n_src,)`` and ``src_moment`` ``(n_src, 3)``; everything on one HIP
-    device.  An entry whose clip leaves fewer than 3 corners gets ``A_ij *
-    M_j / A_j``.  Returns a new ``(n_entries, 3)`` fp64 tensor.  Runs on the
-    current stream and waits for it.  ``ValueError``: a wrong shape, dtype
-    or device, an entry outside its side, a count outside ``[0, width]``.
-    """
-    torch = require_gpu()
-    lib = load_library()
-    s_lat, s_lon, s_count = _scrip_cells(torch, 'source ', *src_cells)
-    dev = s_lat.device
-    d_lat, d_lon, d_count = _scrip_cells(torch, 'destination ', *dst_cells,
-                                         dev=dev)
-    n_src, w_src = s_lat.shape
-    n_dst, w_dst = d_lat.shape
-    if not torch.is_tensor(area) or area.dim() != 1:
-        raise ValueError('area: expected a 1-D tensor')
-    n = area.shape[0]
-    area = _f64(torch, 'area', area, (n,), dev)
-    dst = _i32(torch, 'dst', dst, (n,), dev)
-    src = _i32(torch, 'src', src, (n,), dev)
-    src_area = _f64(torch, 'src_area', src_area, (n_src,), dev)
-    src_moment = _f64(torch, 'src_moment', src_moment, (n_src, 3), dev)
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        need = ctypes.c_size_t(0)
-        _checked(lib, lib.remap_overlap_moments_workspace(
-            n_src, w_src, n_dst, w_dst, ctypes.byref(need)),
-            'remap_overlap_moments_workspace')
-        workspace = torch.empty(max(need.value, 1), dtype=torch.uint8,
-                                device=dev)
-        moment = torch.empty((n, 3), dtype=torch.float64, device=dev)
-        status = torch.zeros(2, dtype=torch.int32, device=dev)
-        with _gpu_ms(torch, timing):
-            _checked(lib, lib.remap_overlap_moments(
-                n, _ptr(dst), _ptr(src), _ptr(area), n_src, w_src,
-                _ptr(s_lat), _ptr(s_lon), _ptr(s_count), _ptr(src_area),
-                _ptr(src_moment), n_dst, w_dst, _ptr(d_lat), _ptr(d_lon),
-                _ptr(d_count), _ptr(moment), _ptr(status), _ptr(workspace),
-                need.value, stream), 'remap_overlap_moments')
-        del workspace
-    return moment
-
-
-def gradient_stencils(nbr, count, centroid, timing=None):
-    """
-    The gradient coefficients of every cell over its edge neighbours,
-    through ``remap_gradient_stencils`` (``include/remap_hip.h``;
-    :func:`pyremap_amd.weights.gradient_stencils` is the numpy statement):
-    ``nbr`` ``(n, width)`` integers (-1: no cell across that edge),
-    ``count`` ``(n,)`` integers and ``centroid`` ``(n, 3)`` unit vectors on
-    one HIP device, width at most ``OVERLAP_MAX_EDGES``.  Returns ``(coef
-    (n, width + 1, 3) fp64, has (n,) int32)``: slot 0 the cell itself, slot
-    ``1 + t`` neighbour ``t``; all 0 where ``has`` is 0.  Runs on the
-    current stream and waits for it.
-    """
-    torch = require_gpu()
-    lib = load_library()
-    if not torch.is_tensor(nbr) or not nbr.is_cuda or nbr.dim() != 2 or \
-            nbr.shape[1] < 1 or nbr.dtype.is_floating_point:
-        raise ValueError('nbr: expected (n, width) integers on a HIP '
-                         'device, width >= 1')
-    dev = nbr.device
-    n, width = nbr.shape
-    nbr = nbr.to(torch.int32).contiguous()
-    count = _i32(torch, 'count', count, (n,), dev)
-    centroid = _f64(torch, 'centroid', centroid, (n, 3), dev)
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        coef = torch.empty((n, width + 1, 3), dtype=torch.float64,
-                           device=dev)
-        has = torch.empty(n, dtype=torch.int32, device=dev)
-        status = torch.zeros(2, dtype=torch.int32, device=dev)
-        with _gpu_ms(torch, timing):
-            _checked(lib, lib.remap_gradient_stencils(
-                n, width, _ptr(nbr), _ptr(count), _ptr(centroid), _ptr(coef),
-                _ptr(has), _ptr(status), stream), 'remap_gradient_stencils')
-    return coef, has
-
-
-def conserve2nd_assemble(dst, src, area, moment, nbr, count, coef, has,
-                         src_area, src_moment, dst_area, timing=None):
-    """
-    The second-order map from its pieces, through
-    ``remap_conserve2nd_sizes`` / ``remap_conserve2nd_assemble``
-    (``include/remap_hip.h``; :func:`pyremap_amd.weights.second_order_entries`
-    is the numpy statement): the first-order entries ``dst`` / ``src`` /
-    ``area`` with their moments ``(n_entries, 3)``, the source's ``nbr (n_src,
-    width)``, ``count``, ``coef (n_src, width + 1, 3)`` and ``has``,
-    ``src_area``, ``src_moment (n_src, 3)`` and ``dst_area (n_dst,)``, all on
-    one HIP device.  Returns ``(row, col, S)``, new tensors (int32 0-based,
-    fp64) sorted by ``(row, col)`` and unique; zero sums are kept.  Two
-    calls give the same bytes.  Runs on the current stream and waits for it
-    twice (the triple count, the entry count).  ``timing`` receives the GPU
-    ``ms`` of the assembly call.
-    """
-    torch = require_gpu()
-    lib = load_library()
-    if not torch.is_tensor(area) or not area.is_cuda or area.dim() != 1:
-        raise ValueError('area: expected a 1-D tensor on a HIP device')
-    dev = area.device
-    n = area.shape[0]
-    if not torch.is_tensor(nbr) or nbr.dim() != 2 or nbr.shape[1] < 1:
-        raise ValueError('nbr: expected (n_src, width) integers, width >= 1')
-    n_src, width = nbr.shape
-    if not torch.is_tensor(dst_area) or dst_area.dim() != 1:
-        raise ValueError('dst_area: expected a 1-D tensor')
-    n_dst = dst_area.shape[0]
-    area = _f64(torch, 'area', area, (n,), dev)
-    dst = _i32(torch, 'dst', dst, (n,), dev)
-    src = _i32(torch, 'src', src, (n,), dev)
-    moment = _f64(torch, 'moment', moment, (n, 3), dev)
-    nbr = _i32(torch, 'nbr', nbr, (n_src, width), dev)
-    count = _i32(torch, 'count', count, (n_src,), dev)
-    coef = _f64(torch, 'coef', coef, (n_src, width + 1, 3), dev)
-    has = _i32(torch, 'has', has, (n_src,), dev)
-    src_area = _f64(torch, 'src_area', src_area, (n_src,), dev)
-    src_moment = _f64(torch, 'src_moment', src_moment, (n_src, 3), dev)
-    dst_area = _f64(torch, 'dst_area', dst_area, (n_dst,), dev)
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        counters = torch.zeros(2, dtype=torch.int64, device=dev)
-        capacity = ctypes.c_int64(0)
-        need = ctypes.c_size_t(0)
-        _checked(lib, lib.remap_conserve2nd_sizes(
-            n, _ptr(src), n_src, width, _ptr(count), _ptr(has),
-            _ptr(counters), ctypes.byref(capacity), ctypes.byref(need),
-            stream), 'remap_conserve2nd_sizes')
-        cap = capacity.value
-        workspace = torch.empty(max(need.value, 1), dtype=torch.uint8,
-                                device=dev)
-        row = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-        col = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
-        S = torch.empty(max(cap, 1), dtype=torch.float64, device=dev)
-        n_out = ctypes.c_int64(0)
-        with _gpu_ms(torch, timing):
-            _checked(lib, lib.remap_conserve2nd_assemble(
-                n, _ptr(dst), _ptr(src), _ptr(area), _ptr(moment), n_src,
-                width, _ptr(nbr), _ptr(count), _ptr(coef), _ptr(has),
-                _ptr(src_area), _ptr(src_moment), n_dst, _ptr(dst_area), cap,
-                _ptr(workspace), need.value, _ptr(row), _ptr(col), _ptr(S),
-                _ptr(counters), ctypes.byref(n_out), stream),
-                'remap_conserve2nd_assemble')
-        del workspace
-    k = n_out.value
-    return row[:k], col[:k], S[:k]
-
-
-# ---------------------------------------------------------------------------
-# patch-recovery maps: one-rings, a quadratic per node, the rows
-# ---------------------------------------------------------------------------
-
-#: REMAP_PATCH_MAX_RING, REMAP_PATCH_FIT_WIDTH
-PATCH_MAX_RING = 16
-PATCH_FIT_WIDTH = 22
-
-
-def _patch_args(torch, specs):
-    """Every ``(name, tensor, dtype, trailing shape)`` of ``specs`` is a
-    contiguous tensor of that dtype and shape ``(n,) + trailing`` on one HIP
-    device, or a ``ValueError`` that names the argument.  Returns the
-    device."""
-    for name, t, dtype, tail in specs:
-        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or \
-                t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail or \
-                not t.is_contiguous():
-            kind = 'int32' if dtype == torch.int32 else 'float64'
-            shape = '(n, ' + ', '.join(str(k) for k in tail) + ')' \
-                if tail else '(n,)'
-            raise ValueError(
-                f'{name}: expected a contiguous {shape} {kind} tensor on a '
-                f'HIP device')
-    devices = {t.device for _, t, _, _ in specs}
-    if len(devices) != 1:
-        where = ', '.join(f'{name} on {t.device}' for name, t, _, _ in specs)
-        raise ValueError(f'{where}: expected one device')
-    return specs[0][1].device
-
-
-def _same_length(specs):
-    """Every ``(name, tensor, n, of)`` has ``n`` rows (one per ``of``)."""
-    for name, t, n, of in specs:
-        if t.shape[0] != n:
-            raise ValueError(f'{name}: {t.shape[0]} rows, expected one for '
-                             f'each of the {n} {of}')
-
-
-def node_rings(tri, n_nodes, timing=None):
-    """
-    The one-ring of every node of the triangles ``tri (n_tri, 3)`` (a
-    contiguous int32 tensor of node ids below ``n_nodes`` on a HIP device),
-    through ``remap_node_rings`` (``include/remap_hip.h`` has the
-    definition; :func:`pyremap_amd.weights.node_rings` is the numpy
-    statement).  Returns ``(ring int32 (n_nodes, PATCH_MAX_RING), count
-    int32 (n_nodes,))``: the distinct nodes that share a triangle with each
-    node, ascending, padded with -1, and their true number (of which the
-    lowest ``PATCH_MAX_RING`` are kept).  Two calls give identical bytes.
-    Runs on the current stream and waits for it.  ``ValueError``: a triangle
-    names a node outside ``[0, n_nodes)``.  ``timing``: a dict that receives
-    the GPU ``ms`` of the call.
-    """
-    torch = require_gpu()
-    lib = load_library()
-    dev = _patch_args(torch, (('tri', tri, torch.int32, (3,)),))
-    n_nodes = int(n_nodes)
-    if n_nodes < 1:
-        raise ValueError(f'n_nodes {n_nodes}: expected at least one node')
-    n_tri = tri.shape[0]
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        need = ctypes.c_size_t(0)
-        _checked(lib, lib.remap_node_rings_workspace(
-            n_tri, n_nodes, ctypes.byref(need)), 'remap_node_rings_workspace')
-        workspace = torch.empty(max(need.value, 1), dtype=torch.uint8,
-                                device=dev)
-        ring = torch.empty((n_nodes, PATCH_MAX_RING), dtype=torch.int32,
-                           device=dev)
-        count = torch.empty(n_nodes, dtype=torch.int32, device=dev)
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-        with _gpu_ms(torch, timing):
-            _checked(lib, lib.remap_node_rings(
-                n_tri, _ptr(tri), n_nodes, _ptr(ring), _ptr(count),
-                _ptr(status), _ptr(workspace), need.value, stream),
-                'remap_node_rings')
-        del workspace
-    return ring, count
-
-
-def patch_fits(xyz, ring, count, timing=None):
-    """
-    The least-squares quadratic of every node over itself and its ring,
-    through ``remap_patch_fits`` (``include/remap_hip.h``;
-    :func:`pyremap_amd.weights.patch_fits` is the numpy statement): ``xyz
-    (n, 3)`` fp64 unit vectors, ``ring (n, PATCH_MAX_RING)`` and ``count
-    (n,)`` int32 as :func:`node_rings` returns them, contiguous, on one HIP
-    device.  Returns ``(fit fp64 (n, PATCH_FIT_WIDTH), has int32 (n,))``:
-    the scale ``h`` and the upper triangle of ``N^-1`` where the node has a
-    patch, zeros where ``has`` is 0.  Runs on the current stream and waits
-    for it.  ``timing``: a dict that receives the GPU ``ms`` of the call.
-    """
-    torch = require_gpu()
-    lib = load_library()
-    dev = _patch_args(torch, (
-        ('xyz', xyz, torch.float64, (3,)),
-        ('ring', ring, torch.int32, (PATCH_MAX_RING,)),
-        ('count', count, torch.int32, ())))
-    n = xyz.shape[0]
-    if n < 1:
-        raise ValueError('patch_fits needs at least one node')
-    _same_length((('ring', ring, n, 'nodes'), ('count', count, n, 'nodes')))
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        fit = torch.empty((n, PATCH_FIT_WIDTH), dtype=torch.float64,
-                          device=dev)
-        has = torch.empty(n, dtype=torch.int32, device=dev)
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-        with _gpu_ms(torch, timing):
-            _checked(lib, lib.remap_patch_fits(
-                n, _ptr(xyz), _ptr(ring), _ptr(count), _ptr(fit), _ptr(has),
-                _ptr(status), stream), 'remap_patch_fits')
-    return fit, has
-
-
-def patch_rows(xyz, tri, ring, count, fit, has, found, w, points,
-               timing=None):
-    """
-    The patch map's rows, through ``remap_patch_sizes`` /
-    ``remap_patch_rows`` (``include/remap_hip.h``;
-    :func:`pyremap_amd.weights.patch_entries` is the numpy statement):
-    ``xyz``, ``tri`` and ``points`` as :func:`locate_in_triangles` takes
-    them, ``found (n_pts,)`` / ``w (n_pts, 3)`` as it returns them, ``ring``
-    / ``count`` of :func:`node_rings` and ``fit`` / ``has`` of
-    :func:`patch_fits`; contiguous fp64 / int32 tensors on one HIP device.
-    Returns ``(row, col, S)``, new tensors (int32 0-based, fp64) sorted by
-    ``(row, col)`` and unique; zero sums are kept; a point with ``found =
-    -1`` has no row.  A point whose triangle touches a node without a patch
-    keeps its three located weights, bit for bit.  Two calls give the same
-    bytes.  Runs on the current stream and waits for it twice (the entry
-    count, the status).  ``timing`` receives the GPU ``ms`` of both passes.
-    """
-    torch = require_gpu()
-    lib = load_library()
-    dev = _patch_args(torch, (
-        ('xyz', xyz, torch.float64, (3,)),
-        ('tri', tri, torch.int32, (3,)),
-        ('ring', ring, torch.int32, (PATCH_MAX_RING,)),
-        ('count', count, torch.int32, ()),
-        ('fit', fit, torch.float64, (PATCH_FIT_WIDTH,)),
-        ('has', has, torch.int32, ()),
-        ('found', found, torch.int32, ()),
-        ('w', w, torch.float64, (3,)),
-        ('points', points, torch.float64, (3,))))
-    n, n_tri, n_pts = xyz.shape[0], tri.shape[0], points.shape[0]
-    if n < 1:
-        raise ValueError('patch_rows needs at least one node')
-    _same_length((('ring', ring, n, 'nodes'), ('count', count, n, 'nodes'),
-                  ('fit', fit, n, 'nodes'), ('has', has, n, 'nodes'),
-                  ('found', found, n_pts, 'points'),
-                  ('w', w, n_pts, 'points')))
-    with torch.cuda.device(dev):
-        stream = _stream_ptr(dev)
-        need = ctypes.c_size_t(0)
-        _checked(lib, lib.remap_patch_sizes_workspace(
-            n_pts, ctypes.byref(need)), 'remap_patch_sizes_workspace')
-        workspace = torch.empty(max(need.value, 1), dtype=torch.uint8,
-                                device=dev)
-        offsets = torch.empty(n_pts + 1, dtype=torch.int64, device=dev)
-        status = torch.zeros(1, dtype=torch.int32, device=dev)
-        total = ctypes.c_int64(0)
-        with _gpu_ms(torch, timing):
-            _checked(lib, lib.remap_patch_sizes(
-                n, _ptr(xyz), n_tri, _ptr(tri), _ptr(ring), _ptr(count),
-                _ptr(has), n_pts, _ptr(found), _ptr(points), _ptr(offsets),
-                ctypes.byref(total), _ptr(status), _ptr(workspace),
-                need.value, stream), 'remap_patch_sizes')
-            cap = total.value
-            row = torch.empty(cap, dtype=torch.int32, device=dev)
-            col = torch.empty(cap, dtype=torch.int32, device=dev)
-            S = torch.empty(cap, dtype=torch.float64, device=dev)
-            _checked(lib, lib.remap_patch_rows(
-                n, _ptr(xyz), n_tri, _ptr(tri), _ptr(ring), _ptr(count),
-                _ptr(fit), _ptr(has), n_pts, _ptr(found), _ptr(w),
-                _ptr(points), _ptr(offsets), cap, _ptr(row), _ptr(col),
-                _ptr(S), _ptr(status), stream), 'remap_patch_rows')
-        del workspace
-    return row, col, S
+from pyremap_amd.geometry import (  # noqa: E402,F401
+    CELL_AREAS_MAX_WIDTH, NEAREST_K_MAX, OVERLAP_MAX_EDGES, PATCH_FIT_WIDTH,
+    PATCH_MAX_RING, PIECES_PHASES, cell_areas, cell_moments,
+    column_fractions, conserve2nd_assemble, expand_cells, gradient_stencils,
+    locate_in_quads, locate_in_triangles, nearest_k_points, nearest_points,
+    node_rings, overlap_grids, overlap_latlon, overlap_meshes,
+    overlap_moments, overlap_pieces, patch_fits, patch_rows)

@@ -80,6 +80,131 @@ def test_struct_layout_matches_header():
     assert fields('remap_strips') == [f[0] for f in engine._Strips._fields_]
 
 
+def _header_code():
+    """include/remap_hip.h without comments and preprocessor lines."""
+    text = open(os.path.join(REPO, 'include', 'remap_hip.h')).read()
+    text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
+    return re.sub(r'^[ \t]*#.*$', '', text, flags=re.M)
+
+
+def _header_structs():
+    """name -> member names of every struct the header defines, typedef'd
+    (``typedef struct X {...} X;``) or a bare tag (``struct X {...};``)."""
+    found = re.findall(r'\bstruct\s+(remap_\w+)\s*\{(.*?)\}\s*\w*\s*;',
+                       _header_code(), flags=re.S)
+    return {name: [re.sub(r'\[.*\]', '', m) for m in
+                   re.findall(r'([A-Za-z_0-9\[\]]+)\s*;', body)]
+            for name, body in found}
+
+
+_SCALARS = {'int': 'i32', 'int32_t': 'i32', 'int64_t': 'i64',
+            'double': 'f64', 'float': 'f32', 'size_t': 'size'}
+
+
+def _parameter_class(text, structs):
+    """A C parameter's class: 'pointer', ('struct', name) for a pointer to
+    one of the header's structs, or one of _SCALARS' values."""
+    words = [w for w in re.findall(r'\w+|\*', text)
+             if w not in ('const', 'struct')]
+    if '*' in words:
+        if words[0] in structs and words.count('*') == 1:
+            return ('struct', words[0])
+        return 'pointer'
+    assert len(words) == 2, text          # a type and the parameter's name
+    return _SCALARS[words[0]]
+
+
+def _header_prototypes():
+    """name -> (what it returns, [every parameter's class]) of every
+    REMAP_API declaration, wherever its line breaks are."""
+    structs = _header_structs()
+    out = {}
+    for returns, name, parameters in re.findall(
+            r'\bREMAP_API\s+([\w\s\*]*?)\b(remap_\w+)\s*\(([^()]*)\)\s*;',
+            _header_code()):
+        assert name not in out, name
+        returns = ' '.join(returns.split())
+        parameters = [p.strip() for p in parameters.split(',')]
+        if parameters == ['void']:
+            parameters = []
+        out[name] = (returns, [_parameter_class(p, structs)
+                               for p in parameters])
+    return out
+
+
+def test_every_prototype_matches_the_header():
+    """Each entry point's argtypes: as many as the header's parameters, each
+    of the parameter's class -- a pointer where it takes one, 4 bytes where
+    it reads 4 -- and a pointer to a struct typed as that struct's mirror;
+    restype as the header returns."""
+    import ctypes
+    from pyremap_amd import _abi, engine
+    classes = {ctypes.c_int32: 'i32', ctypes.c_int64: 'i64',
+               ctypes.c_double: 'f64', ctypes.c_float: 'f32',
+               ctypes.c_size_t: 'size', ctypes.c_void_p: 'pointer'}
+    returns = {'int': ctypes.c_int, 'const char *': ctypes.c_char_p,
+               'void': None}
+    lib = engine.load_library()
+    header = _header_prototypes()
+    assert len(header) == len(engine.EXPORTS) == 69
+    assert sorted(header) == sorted(engine.EXPORTS)
+    for name, (returned, parameters) in header.items():
+        fn = getattr(lib, name)
+        assert fn.restype is returns[returned], name
+        argtypes = list(fn.argtypes or ())
+        assert len(argtypes) == len(parameters), name
+        for i, (have, want) in enumerate(zip(argtypes, parameters)):
+            where = f'{name}, parameter {i}'
+            if isinstance(want, tuple):
+                assert have is ctypes.POINTER(_abi.STRUCTS[want[1]]), where
+            elif issubclass(have, ctypes._Pointer):
+                assert want == 'pointer', where
+            else:
+                assert classes[have] == want, where
+
+
+def test_every_struct_is_laid_out_as_the_c_compiler_lays_it_out(tmp_path):
+    """sizeof, and every member's offsetof and size, as the host C compiler
+    sees include/remap_hip.h == the ctypes mirror's, for all 16 structs."""
+    import ctypes
+    import shutil
+    import subprocess
+    from pyremap_amd import _abi
+    structs = _header_structs()
+    assert sorted(structs) == sorted(_abi.STRUCTS) and len(structs) == 16
+    lines = ['#include <stddef.h>', '#include <stdio.h>',
+             '#include "remap_hip.h"', 'int main(void)', '{']
+    for name, members in structs.items():
+        lines.append(f'    printf("{name} . %zu 0\\n", '
+                     f'sizeof(struct {name}));')
+        lines += [f'    printf("{name} {m} %zu %zu\\n", '
+                  f'offsetof(struct {name}, {m}), '
+                  f'sizeof(((struct {name} *)0)->{m}));' for m in members]
+    lines += ['    return 0;', '}']
+    source = tmp_path / 'layout.c'
+    source.write_text('\n'.join(lines) + '\n')
+    cc = shutil.which('cc') or shutil.which('gcc') or \
+        shutil.which('clang', path='/opt/rocm/lib/llvm/bin')
+    assert cc, 'no host C compiler (the library needs one to build)'
+    subprocess.run([cc, '-I', os.path.join(REPO, 'include'), str(source),
+                    '-o', str(tmp_path / 'layout')], check=True)
+    out = subprocess.run([str(tmp_path / 'layout')], capture_output=True,
+                         text=True, check=True).stdout
+    seen = {name: [] for name in structs}
+    for line in out.splitlines():
+        name, member, offset, size = line.split()
+        mirror = _abi.STRUCTS[name]
+        if member == '.':
+            assert ctypes.sizeof(mirror) == int(offset), name
+            continue
+        field = getattr(mirror, member)
+        assert (field.offset, field.size) == (int(offset), int(size)), \
+            f'{name}.{member}'
+        seen[name].append(member)
+    for name, mirror in _abi.STRUCTS.items():
+        assert seen[name] == [f[0] for f in mirror._fields_], name
+
+
 def test_no_gpu_means_loud_failure():
     """Without a device the product path raises; it never falls back."""
     import torch
