@@ -34,10 +34,9 @@
 #include <cstring>
 #include <string.h>
 
-#include <rocprim/rocprim.hpp>
-
 #include "remap_clip.h"
 #include "remap_common.h"
+#include "remap_host.h"
 #include "remap_sphere.h"
 
 namespace remap {
@@ -56,11 +55,6 @@ constexpr int kErrCount = 1;
 constexpr int kErrIndex = 64;
 constexpr int kErrCapacity = 128;
 constexpr uint64_t kLow = 0xffffffffull;
-constexpr size_t kAlign = 256;
-
-size_t align_up(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
-uint32_t blocks(int64_t n, int per) { return static_cast<uint32_t>((n + per - 1) / per); }
-size_t at_least_one(int64_t n) { return static_cast<size_t>(n > 0 ? n : 1); }
 
 // m += 1/2 theta n of the arc p -> q; nothing for p == q (or antipodes)
 __device__ inline void add_arc(V3 p, V3 q, V3 *m)
@@ -535,7 +529,7 @@ __global__ __launch_bounds__(kBlock) void scatter_triples(
 }
 
 struct MomentsLayout {
-    size_t xyz_src, nv_src, centre_src, xyz_dst, nv_dst, total;
+    size_t xyz_src, nv_src, centre_src, xyz_dst, nv_dst, centre_dst, total;
 };
 
 MomentsLayout moments_layout(int64_t n_src, int32_t width_src, int64_t n_dst,
@@ -543,13 +537,13 @@ MomentsLayout moments_layout(int64_t n_src, int32_t width_src, int64_t n_dst,
 {
     MomentsLayout lay;
     size_t off = 0;
-    lay.xyz_src = off;    off += align_up(at_least_one(n_src) * width_src * 24);
-    lay.nv_src = off;     off += align_up(at_least_one(n_src) * 4);
-    lay.centre_src = off; off += align_up(at_least_one(n_src) * 24);
-    lay.xyz_dst = off;    off += align_up(at_least_one(n_dst) * width_dst * 24);
-    lay.nv_dst = off;     off += align_up(at_least_one(n_dst) * 4);
+    lay.xyz_src = take(&off, at_least_one(n_src) * width_src * 24);
+    lay.nv_src = take(&off, at_least_one(n_src) * 4);
+    lay.centre_src = take(&off, at_least_one(n_src) * 24);
+    lay.xyz_dst = take(&off, at_least_one(n_dst) * width_dst * 24);
+    lay.nv_dst = take(&off, at_least_one(n_dst) * 4);
     // (the destination's centres: written by ring_prep, read by nobody)
-    off += align_up(at_least_one(n_dst) * 24);
+    lay.centre_dst = take(&off, at_least_one(n_dst) * 24);
     lay.total = off;
     return lay;
 }
@@ -564,32 +558,23 @@ int assemble_layout(int64_t n_entries, int64_t capacity, AssembleLayout *lay)
 {
     const size_t n = at_least_one(n_entries), cap = at_least_one(capacity);
     size_t scan_n = 0, scan_cap = 0, sort = 0;
-    REMAP_HIP_CHECK((rocprim::exclusive_scan(
-        nullptr, scan_n, static_cast<const uint32_t *>(nullptr),
-        static_cast<uint32_t *>(nullptr), 0u, n, rocprim::plus<uint32_t>())));
-    REMAP_HIP_CHECK((rocprim::exclusive_scan(
-        nullptr, scan_cap, static_cast<const uint32_t *>(nullptr),
-        static_cast<uint32_t *>(nullptr), 0u, cap,
-        rocprim::plus<uint32_t>())));
-    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-        nullptr, sort, static_cast<const uint64_t *>(nullptr),
-        static_cast<uint64_t *>(nullptr),
-        static_cast<const uint32_t *>(nullptr),
-        static_cast<uint32_t *>(nullptr), cap, 0u, 64u)));
+    REMAP_TRY(scan_temp<uint32_t>(n, &scan_n));
+    REMAP_TRY(scan_temp<uint32_t>(cap, &scan_cap));
+    REMAP_TRY(sort_pairs_temp<uint32_t>(cap, &sort));
     lay->temp_bytes = scan_n > scan_cap ? scan_n : scan_cap;
     if (sort > lay->temp_bytes)
         lay->temp_bytes = sort;
     size_t off = 0;
-    lay->cnt = off;      off += align_up(n * 4);
-    lay->off = off;      off += align_up(n * 4);
-    lay->keys_in = off;  off += align_up(cap * 8);   // later: the runs' sums
-    lay->pos_in = off;   off += align_up(cap * 4);
-    lay->w = off;        off += align_up(cap * 8);
-    lay->keys_out = off; off += align_up(cap * 8);
-    lay->pos_out = off;  off += align_up(cap * 4);
-    lay->head = off;     off += align_up(cap * 4);
-    lay->slot = off;     off += align_up(cap * 4);
-    lay->temp = off;     off += align_up(lay->temp_bytes);
+    lay->cnt = take(&off, n * 4);
+    lay->off = take(&off, n * 4);
+    lay->keys_in = take(&off, cap * 8);   // later: the runs' sums
+    lay->pos_in = take(&off, cap * 4);
+    lay->w = take(&off, cap * 8);
+    lay->keys_out = take(&off, cap * 8);
+    lay->pos_out = take(&off, cap * 4);
+    lay->head = take(&off, cap * 4);
+    lay->slot = take(&off, cap * 4);
+    lay->temp = take(&off, lay->temp_bytes);
     lay->total = off;
     return REMAP_OK;
 }
@@ -614,14 +599,6 @@ int check_cells(const char *name, int64_t n_cells, int32_t width,
         return fail(REMAP_ERR_UNSUPPORTED,
                     "%s: width %d, this build serves up to %d corners a cell",
                     name, width, max_width);
-    return REMAP_OK;
-}
-
-int read_status(int32_t *err, const int32_t *status, hipStream_t stream)
-{
-    REMAP_HIP_CHECK(hipMemcpyAsync(err, status, 2 * sizeof(int32_t),
-                                   hipMemcpyDeviceToHost, stream));
-    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
     return REMAP_OK;
 }
 
@@ -655,8 +632,7 @@ int cell_moments(int64_t n_cells, int32_t width, const double *corner_lat,
                  double *moment_out, int32_t *status, hipStream_t stream)
 {
     const char *name = "remap_cell_moments";
-    if (const int rc = check_cells(name, n_cells, width, kMaxWidth))
-        return rc;
+    REMAP_TRY(check_cells(name, n_cells, width, kMaxWidth));
     if (!status)
         return fail(REMAP_ERR_ARG, "%s: NULL status", name);
     if (n_cells == 0)
@@ -665,13 +641,12 @@ int cell_moments(int64_t n_cells, int32_t width, const double *corner_lat,
         return fail(REMAP_ERR_ARG, "%s: NULL array", name);
     const size_t lds_bytes = sizeof(double) * 3 * kCells * width;
     REMAP_HIP_CHECK(hipMemsetAsync(status, 0, 2 * sizeof(int32_t), stream));
-    hipLaunchKernelGGL(cell_moments_kernel, dim3(blocks(n_cells, kCells)),
-                       dim3(kBlock), lds_bytes, stream, n_cells, width,
-                       corner_lat, corner_lon, count, moment_out, status);
-    REMAP_HIP_CHECK(hipGetLastError());
+    REMAP_TRY(launch_blocks(cell_moments_kernel, blocks(n_cells, kCells),
+                            kBlock, lds_bytes, stream, n_cells, width,
+                            corner_lat, corner_lon, count, moment_out,
+                            status));
     int32_t err[2] = {0, 0};
-    if (const int rc = read_status(err, status, stream))
-        return rc;
+    REMAP_TRY(read_back(err, status, sizeof(err), stream));
     if (err[0])
         return count_fail(name, width, n_cells, err);
     return REMAP_OK;
@@ -683,10 +658,8 @@ int overlap_moments_workspace(int64_t n_src, int32_t width_src, int64_t n_dst,
     const char *name = "remap_overlap_moments_workspace";
     if (!bytes_out)
         return fail(REMAP_ERR_ARG, "%s: NULL bytes_out", name);
-    if (const int rc = check_cells(name, n_src, width_src, kMaxEdges))
-        return rc;
-    if (const int rc = check_cells(name, n_dst, width_dst, kMaxEdges))
-        return rc;
+    REMAP_TRY(check_cells(name, n_src, width_src, kMaxEdges));
+    REMAP_TRY(check_cells(name, n_dst, width_dst, kMaxEdges));
     *bytes_out = moments_layout(n_src, width_src, n_dst, width_dst).total;
     return REMAP_OK;
 }
@@ -706,10 +679,8 @@ int overlap_moments(int64_t n_entries, const int32_t *dst, const int32_t *src,
         return fail(REMAP_ERR_ARG, "%s: n_entries %lld: expected 0 <= "
                     "n_entries < 2^31", name,
                     static_cast<long long>(n_entries));
-    if (const int rc = check_cells(name, n_src, width_src, kMaxEdges))
-        return rc;
-    if (const int rc = check_cells(name, n_dst, width_dst, kMaxEdges))
-        return rc;
+    REMAP_TRY(check_cells(name, n_src, width_src, kMaxEdges));
+    REMAP_TRY(check_cells(name, n_dst, width_dst, kMaxEdges));
     if (!status)
         return fail(REMAP_ERR_ARG, "%s: NULL status", name);
     if (n_entries == 0)
@@ -720,50 +691,34 @@ int overlap_moments(int64_t n_entries, const int32_t *dst, const int32_t *src,
         return fail(REMAP_ERR_ARG, "%s: NULL array", name);
     const MomentsLayout lay =
         moments_layout(n_src, width_src, n_dst, width_dst);
-    if (!workspace || workspace_bytes < lay.total)
-        return fail(REMAP_ERR_WORKSPACE,
-                    "%s: workspace of %zu bytes, need %zu", name,
-                    workspace_bytes, lay.total);
+    REMAP_TRY(need_workspace(name, workspace, workspace_bytes, lay.total));
     char *ws = static_cast<char *>(workspace);
-    double *xyz_src = reinterpret_cast<double *>(ws + lay.xyz_src);
-    int32_t *nv_src = reinterpret_cast<int32_t *>(ws + lay.nv_src);
-    double *centre_src = reinterpret_cast<double *>(ws + lay.centre_src);
-    double *xyz_dst = reinterpret_cast<double *>(ws + lay.xyz_dst);
-    int32_t *nv_dst = reinterpret_cast<int32_t *>(ws + lay.nv_dst);
-    double *centre_dst = reinterpret_cast<double *>(
-        ws + lay.nv_dst + align_up(at_least_one(n_dst) * 4));
+    double *xyz_src = at<double>(ws, lay.xyz_src);
+    int32_t *nv_src = at<int32_t>(ws, lay.nv_src);
+    double *centre_src = at<double>(ws, lay.centre_src);
+    double *xyz_dst = at<double>(ws, lay.xyz_dst);
+    int32_t *nv_dst = at<int32_t>(ws, lay.nv_dst);
+    double *centre_dst = at<double>(ws, lay.centre_dst);
     int32_t err[2] = {0, 0};
 
     // the two sides' counts are checked one after the other, so that the
     // message can name the side
     REMAP_HIP_CHECK(hipMemsetAsync(status, 0, 2 * sizeof(int32_t), stream));
-    if (n_src > 0) {
-        hipLaunchKernelGGL(ring_prep, dim3(blocks(n_src, kClipBlock)),
-                           dim3(kClipBlock), 0, stream, n_src, width_src,
-                           src_lat, src_lon, src_count, false, xyz_src,
-                           nv_src, centre_src, status);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
-    if (const int rc = read_status(err, status, stream))
-        return rc;
+    REMAP_TRY(launch(ring_prep, n_src, kClipBlock, stream, n_src, width_src,
+                     src_lat, src_lon, src_count, false, xyz_src, nv_src,
+                     centre_src, status));
+    REMAP_TRY(read_back(err, status, sizeof(err), stream));
     if (err[0] & kErrCount)
         return count_fail("remap_overlap_moments (source)", width_src, n_src,
                           err);
-    if (n_dst > 0) {
-        hipLaunchKernelGGL(ring_prep, dim3(blocks(n_dst, kClipBlock)),
-                           dim3(kClipBlock), 0, stream, n_dst, width_dst,
-                           dst_lat, dst_lon, dst_count, true, xyz_dst, nv_dst,
-                           centre_dst, status);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(overlap_moments_kernel,
-                       dim3(blocks(n_entries, kClipBlock)), dim3(kClipBlock),
-                       0, stream, n_entries, dst, src, area, n_src, width_src,
-                       xyz_src, nv_src, centre_src, src_area, src_moment,
-                       n_dst, width_dst, xyz_dst, nv_dst, moment_out, status);
-    REMAP_HIP_CHECK(hipGetLastError());
-    if (const int rc = read_status(err, status, stream))
-        return rc;
+    REMAP_TRY(launch(ring_prep, n_dst, kClipBlock, stream, n_dst, width_dst,
+                     dst_lat, dst_lon, dst_count, true, xyz_dst, nv_dst,
+                     centre_dst, status));
+    REMAP_TRY(launch(overlap_moments_kernel, n_entries, kClipBlock, stream,
+                     n_entries, dst, src, area, n_src, width_src, xyz_src,
+                     nv_src, centre_src, src_area, src_moment, n_dst,
+                     width_dst, xyz_dst, nv_dst, moment_out, status));
+    REMAP_TRY(read_back(err, status, sizeof(err), stream));
     if (err[0] & kErrCount)
         return count_fail("remap_overlap_moments (destination)", width_dst,
                           n_dst, err);
@@ -794,8 +749,7 @@ int gradient_stencils(int64_t n_cells, int32_t width, const int32_t *nbr,
                       hipStream_t stream)
 {
     const char *name = "remap_gradient_stencils";
-    if (const int rc = check_cells(name, n_cells, width, kMaxEdges))
-        return rc;
+    REMAP_TRY(check_cells(name, n_cells, width, kMaxEdges));
     if (!status)
         return fail(REMAP_ERR_ARG, "%s: NULL status", name);
     if (n_cells == 0)
@@ -803,14 +757,11 @@ int gradient_stencils(int64_t n_cells, int32_t width, const int32_t *nbr,
     if (!nbr || !count || !centroid || !coef_out || !has_out)
         return fail(REMAP_ERR_ARG, "%s: NULL array", name);
     REMAP_HIP_CHECK(hipMemsetAsync(status, 0, 2 * sizeof(int32_t), stream));
-    hipLaunchKernelGGL(gradient_stencils_kernel,
-                       dim3(blocks(n_cells, kBlock)), dim3(kBlock), 0, stream,
-                       n_cells, width, nbr, count, centroid, coef_out,
-                       has_out, status);
-    REMAP_HIP_CHECK(hipGetLastError());
+    REMAP_TRY(launch(gradient_stencils_kernel, n_cells, kBlock, stream,
+                     n_cells, width, nbr, count, centroid, coef_out, has_out,
+                     status));
     int32_t err[2] = {0, 0};
-    if (const int rc = read_status(err, status, stream))
-        return rc;
+    REMAP_TRY(read_back(err, status, sizeof(err), stream));
     if (err[0] & kErrCount)
         return count_fail(name, width, n_cells, err);
     if (err[0] & kErrIndex)
@@ -825,8 +776,7 @@ int conserve2nd_sizes(int64_t n_entries, const int32_t *src, int64_t n_src,
                       size_t *workspace_bytes_out, hipStream_t stream)
 {
     const char *name = "remap_conserve2nd_sizes";
-    if (const int rc = check_assemble(name, n_entries, n_src, width))
-        return rc;
+    REMAP_TRY(check_assemble(name, n_entries, n_src, width));
     if (!counters || !capacity_out || !workspace_bytes_out)
         return fail(REMAP_ERR_ARG, "%s: NULL counters or output", name);
     int64_t host[2] = {0, 0};
@@ -835,15 +785,10 @@ int conserve2nd_sizes(int64_t n_entries, const int32_t *src, int64_t n_src,
             return fail(REMAP_ERR_ARG, "%s: NULL array", name);
         REMAP_HIP_CHECK(hipMemsetAsync(counters, 0, 2 * sizeof(int64_t),
                                        stream));
-        hipLaunchKernelGGL(triple_counts, dim3(blocks(n_entries, kBlock)),
-                           dim3(kBlock), 0, stream, n_entries, n_src, width,
-                           src, count, has, static_cast<uint32_t *>(nullptr),
-                           reinterpret_cast<unsigned long long *>(counters),
-                           counters + 1);
-        REMAP_HIP_CHECK(hipGetLastError());
-        REMAP_HIP_CHECK(hipMemcpyAsync(host, counters, sizeof(host),
-                                       hipMemcpyDeviceToHost, stream));
-        REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+        REMAP_TRY(launch(triple_counts, n_entries, kBlock, stream, n_entries,
+                         n_src, width, src, count, has, nullptr,
+                         as<unsigned long long>(counters), counters + 1));
+        REMAP_TRY(read_back(host, counters, sizeof(host), stream));
         if (host[1])
             return status_fail(name, host[1]);
     }
@@ -852,8 +797,7 @@ int conserve2nd_sizes(int64_t n_entries, const int32_t *src, int64_t n_src,
                     "%s: %lld triples, beyond 32-bit positions", name,
                     static_cast<long long>(host[0]));
     AssembleLayout lay;
-    if (const int rc = assemble_layout(n_entries, host[0], &lay))
-        return rc;
+    REMAP_TRY(assemble_layout(n_entries, host[0], &lay));
     *capacity_out = host[0];
     *workspace_bytes_out = lay.total;
     return REMAP_OK;
@@ -872,8 +816,7 @@ int conserve2nd_assemble(int64_t n_entries, const int32_t *dst,
                          int64_t *n_out, hipStream_t stream)
 {
     const char *name = "remap_conserve2nd_assemble";
-    if (const int rc = check_assemble(name, n_entries, n_src, width))
-        return rc;
+    REMAP_TRY(check_assemble(name, n_entries, n_src, width));
     if (n_dst < 0 || n_dst > INT32_MAX || capacity < n_entries ||
         capacity >= (int64_t(1) << 32) - 1)
         return fail(REMAP_ERR_ARG, "%s: n_dst %lld, capacity %lld", name,
@@ -889,66 +832,45 @@ int conserve2nd_assemble(int64_t n_entries, const int32_t *dst,
         !s_out)
         return fail(REMAP_ERR_ARG, "%s: NULL array", name);
     AssembleLayout lay;
-    if (const int rc = assemble_layout(n_entries, capacity, &lay))
-        return rc;
-    if (!workspace || workspace_bytes < lay.total)
-        return fail(REMAP_ERR_WORKSPACE,
-                    "%s: workspace of %zu bytes, need %zu", name,
-                    workspace_bytes, lay.total);
+    REMAP_TRY(assemble_layout(n_entries, capacity, &lay));
+    REMAP_TRY(need_workspace(name, workspace, workspace_bytes, lay.total));
     char *ws = static_cast<char *>(workspace);
-    uint32_t *cnt = reinterpret_cast<uint32_t *>(ws + lay.cnt);
-    uint32_t *off = reinterpret_cast<uint32_t *>(ws + lay.off);
-    uint64_t *keys_in = reinterpret_cast<uint64_t *>(ws + lay.keys_in);
-    double *sums = reinterpret_cast<double *>(ws + lay.keys_in);
-    uint32_t *pos_in = reinterpret_cast<uint32_t *>(ws + lay.pos_in);
-    double *w = reinterpret_cast<double *>(ws + lay.w);
-    uint64_t *keys_out = reinterpret_cast<uint64_t *>(ws + lay.keys_out);
-    uint32_t *pos_out = reinterpret_cast<uint32_t *>(ws + lay.pos_out);
-    uint32_t *head = reinterpret_cast<uint32_t *>(ws + lay.head);
-    uint32_t *slot = reinterpret_cast<uint32_t *>(ws + lay.slot);
+    uint32_t *cnt = at<uint32_t>(ws, lay.cnt);
+    uint32_t *off = at<uint32_t>(ws, lay.off);
+    uint64_t *keys_in = at<uint64_t>(ws, lay.keys_in);
+    // (keys_in is free once the sort has read it: the runs' sums go there)
+    double *sums = at<double>(ws, lay.keys_in);
+    uint32_t *pos_in = at<uint32_t>(ws, lay.pos_in);
+    double *w = at<double>(ws, lay.w);
+    uint64_t *keys_out = at<uint64_t>(ws, lay.keys_out);
+    uint32_t *pos_out = at<uint32_t>(ws, lay.pos_out);
+    uint32_t *head = at<uint32_t>(ws, lay.head);
+    uint32_t *slot = at<uint32_t>(ws, lay.slot);
     void *temp = ws + lay.temp;
-    const size_t n = static_cast<size_t>(n_entries);
-    const size_t cap = static_cast<size_t>(capacity);
 
     REMAP_HIP_CHECK(hipMemsetAsync(counters, 0, 2 * sizeof(int64_t), stream));
-    hipLaunchKernelGGL(triple_counts, dim3(blocks(n_entries, kBlock)),
-                       dim3(kBlock), 0, stream, n_entries, n_src, width, src,
-                       count, has, cnt,
-                       static_cast<unsigned long long *>(nullptr),
-                       counters + 1);
-    REMAP_HIP_CHECK(hipGetLastError());
-    size_t tb = lay.temp_bytes;
-    REMAP_HIP_CHECK((rocprim::exclusive_scan(
-        temp, tb, static_cast<const uint32_t *>(cnt), off, 0u, n,
-        rocprim::plus<uint32_t>(), stream)));
-    hipLaunchKernelGGL(fill_triples, dim3(blocks(n_entries, kBlock)),
-                       dim3(kBlock), 0, stream, n_entries, dst, src, area,
-                       moment, n_src, width, nbr, coef, src_area, src_moment,
-                       n_dst, dst_area, capacity, cnt, off, keys_in, pos_in,
-                       w, counters + 1);
-    REMAP_HIP_CHECK(hipGetLastError());
+    REMAP_TRY(launch(triple_counts, n_entries, kBlock, stream, n_entries,
+                     n_src, width, src, count, has, cnt, nullptr,
+                     counters + 1));
+    REMAP_TRY(exclusive_scan(temp, lay.temp_bytes, cnt, off, n_entries,
+                             stream));
+    REMAP_TRY(launch(fill_triples, n_entries, kBlock, stream, n_entries, dst,
+                     src, area, moment, n_src, width, nbr, coef, src_area,
+                     src_moment, n_dst, dst_area, capacity, cnt, off, keys_in,
+                     pos_in, w, counters + 1));
     // (a capacity that differs leaves slots unwritten: the status is read
     // with the count, and nothing below reads beyond the workspace)
-    tb = lay.temp_bytes;
-    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-        temp, tb, static_cast<const uint64_t *>(keys_in), keys_out,
-        static_cast<const uint32_t *>(pos_in), pos_out, cap, 0u, 64u,
-        stream)));
-    hipLaunchKernelGGL(sum_runs, dim3(blocks(capacity, kBlock)), dim3(kBlock),
-                       0, stream, capacity, keys_out, pos_out, w, sums, head);
-    REMAP_HIP_CHECK(hipGetLastError());
-    tb = lay.temp_bytes;
-    REMAP_HIP_CHECK((rocprim::exclusive_scan(
-        temp, tb, static_cast<const uint32_t *>(head), slot, 0u, cap,
-        rocprim::plus<uint32_t>(), stream)));
-    hipLaunchKernelGGL(scatter_triples, dim3(blocks(capacity, kBlock)),
-                       dim3(kBlock), 0, stream, capacity, keys_out, sums,
-                       head, slot, row_out, col_out, s_out, counters);
-    REMAP_HIP_CHECK(hipGetLastError());
+    REMAP_TRY(radix_sort_pairs(temp, lay.temp_bytes, keys_in, keys_out,
+                               pos_in, pos_out, capacity, stream));
+    REMAP_TRY(launch(sum_runs, capacity, kBlock, stream, capacity, keys_out,
+                     pos_out, w, sums, head));
+    REMAP_TRY(exclusive_scan(temp, lay.temp_bytes, head, slot, capacity,
+                             stream));
+    REMAP_TRY(launch(scatter_triples, capacity, kBlock, stream, capacity,
+                     keys_out, sums, head, slot, row_out, col_out, s_out,
+                     counters));
     int64_t host[2] = {0, 0};
-    REMAP_HIP_CHECK(hipMemcpyAsync(host, counters, sizeof(host),
-                                   hipMemcpyDeviceToHost, stream));
-    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+    REMAP_TRY(read_back(host, counters, sizeof(host), stream));
     if (host[1])
         return status_fail(name, host[1]);
     *n_out = host[0];

@@ -36,6 +36,7 @@
 #include <cstdint>
 
 #include "remap_common.h"
+#include "remap_host.h"
 
 namespace remap {
 namespace {
@@ -160,16 +161,12 @@ int expand_cells(int64_t n_cells, int32_t width, const double *centre_lat,
                     "remap_expand_cells: %lld corner slots are more than one "
                     "launch serves", static_cast<long long>(slots));
     REMAP_HIP_CHECK(hipMemsetAsync(status, 0, 2 * sizeof(int32_t), stream));
-    hipLaunchKernelGGL(expand_slots, dim3(static_cast<unsigned>(n_blocks)),
-                       dim3(kBlock), 0, stream, n_cells, width, centre_lat,
-                       centre_lon, corner_lat, corner_lon, count, dist,
-                       dist_stride, factor, factor_stride, out_lat, out_lon,
-                       status);
-    REMAP_HIP_CHECK(hipGetLastError());
+    REMAP_TRY(launch(expand_slots, slots, kBlock, stream, n_cells, width,
+                     centre_lat, centre_lon, corner_lat, corner_lon, count,
+                     dist, dist_stride, factor, factor_stride, out_lat,
+                     out_lon, status));
     int32_t err[2] = {0, 0};
-    REMAP_HIP_CHECK(hipMemcpyAsync(err, status, sizeof(err),
-                                   hipMemcpyDeviceToHost, stream));
-    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+    REMAP_TRY(read_back(err, status, sizeof(err), stream));
     if (err[0]) {
         const long long cell = static_cast<long long>(n_cells) - err[1];
         return fail(REMAP_ERR_ARG,

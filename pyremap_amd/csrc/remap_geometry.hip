@@ -37,9 +37,8 @@
 #include <cstring>
 #include <string.h>
 
-#include <rocprim/rocprim.hpp>
-
 #include "remap_common.h"
+#include "remap_host.h"
 #include "remap_sphere.h"
 
 namespace remap {
@@ -47,9 +46,8 @@ namespace {
 
 constexpr int kCells = kWave;     // cells per block: one per lane of wave 0
 constexpr int kMaxWidth = REMAP_CELL_AREAS_MAX_WIDTH;
-constexpr size_t kAlign = 256;
-
-size_t align_up(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
+// a column's key: its 32 bits are what the sort looks at
+constexpr unsigned kKeyBits = 32;
 
 __global__ __launch_bounds__(kBlock) void cell_areas_kernel(
     int64_t n_cells, int32_t width, const double *__restrict__ corner_lat,
@@ -119,18 +117,14 @@ struct Layout {
 
 int make_layout(int64_t n_entries, Layout *lay)
 {
-    const size_t n = static_cast<size_t>(n_entries > 0 ? n_entries : 1);
-    size_t sort_bytes = 0;
-    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-        nullptr, sort_bytes, static_cast<const uint32_t *>(nullptr),
-        static_cast<uint32_t *>(nullptr), static_cast<const double *>(nullptr),
-        static_cast<double *>(nullptr), n, 0u, 32u)));
-    lay->temp_bytes = sort_bytes;
+    const size_t n = at_least_one(n_entries);
+    REMAP_TRY((sort_pairs_temp<double, uint32_t>(n, &lay->temp_bytes,
+                                                 kKeyBits)));
     size_t off = 0;
-    lay->keys_in = off;  off += align_up(n * 4);
-    lay->keys_out = off; off += align_up(n * 4);
-    lay->vals_out = off; off += align_up(n * 8);
-    lay->temp = off;     off += align_up(lay->temp_bytes);
+    lay->keys_in = take(&off, n * 4);
+    lay->keys_out = take(&off, n * 4);
+    lay->vals_out = take(&off, n * 8);
+    lay->temp = take(&off, lay->temp_bytes);
     lay->total = off;
     return REMAP_OK;
 }
@@ -205,18 +199,13 @@ int cell_areas(int64_t n_cells, int32_t width, const double *corner_lat,
         return REMAP_OK;
     if (!corner_lat || !corner_lon || !count || !area_out)
         return fail(REMAP_ERR_ARG, "remap_cell_areas: NULL array");
-    const int64_t n_blocks = (n_cells + kCells - 1) / kCells;
     const size_t lds_bytes = sizeof(double) * 3 * kCells * width;
     REMAP_HIP_CHECK(hipMemsetAsync(status, 0, 2 * sizeof(int32_t), stream));
-    hipLaunchKernelGGL(cell_areas_kernel,
-                       dim3(static_cast<unsigned>(n_blocks)), dim3(kBlock),
-                       lds_bytes, stream, n_cells, width, corner_lat,
-                       corner_lon, count, area_out, status);
-    REMAP_HIP_CHECK(hipGetLastError());
+    REMAP_TRY(launch_blocks(cell_areas_kernel, blocks(n_cells, kCells),
+                            kBlock, lds_bytes, stream, n_cells, width,
+                            corner_lat, corner_lon, count, area_out, status));
     int32_t err[2] = {0, 0};
-    REMAP_HIP_CHECK(hipMemcpyAsync(err, status, sizeof(err),
-                                   hipMemcpyDeviceToHost, stream));
-    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
+    REMAP_TRY(read_back(err, status, sizeof(err), stream));
     if (err[0])
         return fail(REMAP_ERR_ARG,
                     "remap_cell_areas: a count outside [0, %d], first at "
@@ -231,9 +220,7 @@ int column_fractions_workspace(int64_t n_entries, size_t *bytes_out)
         return fail(REMAP_ERR_ARG,
                     "remap_column_fractions_workspace: bad args");
     Layout lay;
-    const int rc = make_layout(n_entries, &lay);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(make_layout(n_entries, &lay));
     *bytes_out = lay.total;
     return REMAP_OK;
 }
@@ -259,42 +246,23 @@ int column_fractions(int64_t n_entries, int64_t n_cols, const int32_t *col,
     if (n_cols > 0 && !out)
         return fail(REMAP_ERR_ARG, "remap_column_fractions: NULL out");
     Layout lay;
-    const int rc = make_layout(n_entries, &lay);
-    if (rc != REMAP_OK)
-        return rc;
-    if (!workspace || workspace_bytes < lay.total)
-        return fail(REMAP_ERR_WORKSPACE,
-                    "remap_column_fractions: workspace of %zu bytes, need "
-                    "%zu", workspace_bytes, lay.total);
+    REMAP_TRY(make_layout(n_entries, &lay));
+    REMAP_TRY(need_workspace("remap_column_fractions", workspace,
+                             workspace_bytes, lay.total));
     char *ws = static_cast<char *>(workspace);
-    uint32_t *keys_in = reinterpret_cast<uint32_t *>(ws + lay.keys_in);
-    uint32_t *keys_out = reinterpret_cast<uint32_t *>(ws + lay.keys_out);
-    double *vals_out = reinterpret_cast<double *>(ws + lay.vals_out);
-    void *temp = ws + lay.temp;
+    uint32_t *keys_in = at<uint32_t>(ws, lay.keys_in);
+    uint32_t *keys_out = at<uint32_t>(ws, lay.keys_out);
+    double *vals_out = at<double>(ws, lay.vals_out);
 
     REMAP_HIP_CHECK(hipMemsetAsync(bad_out, 0, sizeof(int64_t), stream));
-    if (n_entries > 0) {
-        const uint32_t nblk =
-            static_cast<uint32_t>((n_entries + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(column_keys, dim3(nblk), dim3(kBlock), 0, stream,
-                           n_entries, n_cols, index_base, col, keys_in,
-                           bad_out);
-        REMAP_HIP_CHECK(hipGetLastError());
-        size_t tb = lay.temp_bytes;
-        REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-            temp, tb, static_cast<const uint32_t *>(keys_in), keys_out,
-            value, vals_out, static_cast<size_t>(n_entries), 0u, 32u,
-            stream)));
-    }
-    if (n_cols > 0) {
-        const uint32_t cblk =
-            static_cast<uint32_t>((n_cols + kBlock - 1) / kBlock);
-        hipLaunchKernelGGL(column_sums, dim3(cblk), dim3(kBlock), 0, stream,
-                           n_entries, n_cols, keys_out, vals_out, denom,
-                           clamp, out);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
-    return REMAP_OK;
+    REMAP_TRY(launch(column_keys, n_entries, kBlock, stream, n_entries,
+                     n_cols, index_base, col, keys_in, bad_out));
+    if (n_entries > 0)
+        REMAP_TRY(radix_sort_pairs(ws + lay.temp, lay.temp_bytes, keys_in,
+                                   keys_out, value, vals_out, n_entries,
+                                   stream, kKeyBits));
+    return launch(column_sums, n_cols, kBlock, stream, n_entries, n_cols,
+                  keys_out, vals_out, denom, clamp, out);
 }
 
 }  // namespace remap

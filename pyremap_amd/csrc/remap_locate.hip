@@ -80,20 +80,17 @@
 #include <cstring>
 #include <string.h>
 
-#include <rocprim/rocprim.hpp>
-
 #include "remap_common.h"
+#include "remap_sphere.h"
 #include "remap_tree.h"
 
 namespace remap {
 namespace {
 
-constexpr int kWalkBlock = 64;
+// (kWalkBlock lanes a walking block, kWalkChunk points a launch: remap_tree.h)
 // every child whose box holds the point is stacked, then one is popped: at
 // most kFan - 1 stay behind a level above level 0, and kFan at the last
 constexpr int stack_depth(int levels) { return (kFan - 1) * (levels - 1) + 1; }
-// one walk launch: its block count stays far below the grid limit
-constexpr int64_t kWalkChunk = int64_t(1) << 30;
 constexpr uint32_t kNoTriangle = 0xffffffffu;
 
 static_assert(kBlock % kLeaf == 0 && kWave % kLeaf == 0 &&
@@ -102,61 +99,12 @@ static_assert(kBlock % kLeaf == 0 && kWave % kLeaf == 0 &&
 static_assert(stack_depth(kMaxLevels) * kWalkBlock * 4 <= 64 * 1024,
               "the walk's stack must fit in a workgroup's LDS");
 
-struct Layout {
-    Tree tree;
-    size_t keys_in, keys_out, idx_in, idx_out, normals, boxes, temp, total;
-    size_t temp_bytes;
-};
-
-int make_layout(int64_t n_tri, Layout *lay)
-{
-    const size_t n = static_cast<size_t>(n_tri);
-    const int64_t nodes = make_tree(n_tri, &lay->tree);
-    size_t sort_bytes = 0;
-    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-        nullptr, sort_bytes, static_cast<const uint64_t *>(nullptr),
-        static_cast<uint64_t *>(nullptr),
-        static_cast<const uint32_t *>(nullptr),
-        static_cast<uint32_t *>(nullptr), n, 0u, 63u)));
-    lay->temp_bytes = sort_bytes;
-    size_t off = 0;
-    lay->keys_in = off;  off += align_up(n * 8);
-    lay->keys_out = off; off += align_up(n * 8);
-    lay->idx_in = off;   off += align_up(n * 4);
-    lay->idx_out = off;  off += align_up(n * 4);
-    lay->normals = off;  off += align_up(n * 72);
-    lay->boxes = off;    off += align_up(static_cast<size_t>(nodes) * 48);
-    lay->temp = off;     off += align_up(lay->temp_bytes);
-    lay->total = off;
-    return REMAP_OK;
-}
-
-struct Vec3 {
-    double x, y, z;
-};
-
-__device__ inline Vec3 load3(const double *__restrict__ p, int64_t i)
-{
-    return Vec3{p[3 * i], p[3 * i + 1], p[3 * i + 2]};
-}
-
-__device__ inline Vec3 cross(const Vec3 &u, const Vec3 &v)
-{
-    return Vec3{u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z,
-                u.x * v.y - u.y * v.x};
-}
-
-__device__ inline double dot(const Vec3 &u, const Vec3 &v)
-{
-    return (u.x * v.x + u.y * v.y) + u.z * v.z;
-}
-
 // the corners of triangle t; false if one of its node ids is out of range
 // (then nothing was read through them)
 __device__ inline bool corners(int64_t t, int64_t n_nodes,
                                const double *__restrict__ xyz,
-                               const int32_t *__restrict__ tri, Vec3 &a,
-                               Vec3 &b, Vec3 &c)
+                               const int32_t *__restrict__ tri, V3 &a,
+                               V3 &b, V3 &c)
 {
     const int64_t ia = tri[3 * t], ib = tri[3 * t + 1], ic = tri[3 * t + 2];
     if (ia < 0 || ia >= n_nodes || ib < 0 || ib >= n_nodes || ic < 0 ||
@@ -181,7 +129,7 @@ __global__ __launch_bounds__(kBlock) void centroid_keys(
     const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (t >= n_tri)
         return;
-    Vec3 a, b, c;
+    V3 a, b, c;
     uint64_t key = 0;
     if (corners(t, n_nodes, xyz, tri, a, b, c) &&
         usable(dot(a, cross(b, c))))
@@ -201,12 +149,6 @@ __device__ inline double max3(double a, double b, double c)
     return fmax(fmax(a, b), c);
 }
 
-__device__ inline double edge2(const Vec3 &u, const Vec3 &v)
-{
-    const double dx = u.x - v.x, dy = u.y - v.y, dz = u.z - v.z;
-    return (dx * dx + dy * dy) + dz * dz;
-}
-
 // one lane per sorted triangle; the lanes past the last triangle of the last
 // leaf stay in for the joins with an empty box
 __global__ __launch_bounds__(kBlock) void setup(
@@ -218,17 +160,17 @@ __global__ __launch_bounds__(kBlock) void setup(
     const double inf = __builtin_huge_val();
     double box[6] = {inf, inf, inf, -inf, -inf, -inf};   // holds no point
     if (k < n_tri) {
-        Vec3 a, b, c;
-        Vec3 n0{0.0, 0.0, 0.0}, n1 = n0, n2 = n0;
+        V3 a, b, c;
+        V3 n0{0.0, 0.0, 0.0}, n1 = n0, n2 = n0;
         if (corners(orig[k], n_nodes, xyz, tri, a, b, c)) {
-            const Vec3 bc = cross(b, c);
+            const V3 bc = cross(b, c);
             const double D = dot(a, bc);
             if (usable(D)) {
                 const double s = D < 0.0 ? -1.0 : 1.0;
-                const Vec3 ca = cross(c, a), ab = cross(a, b);
-                n0 = Vec3{s * bc.x, s * bc.y, s * bc.z};
-                n1 = Vec3{s * ca.x, s * ca.y, s * ca.z};
-                n2 = Vec3{s * ab.x, s * ab.y, s * ab.z};
+                const V3 ca = cross(c, a), ab = cross(a, b);
+                n0 = V3{s * bc.x, s * bc.y, s * bc.z};
+                n1 = V3{s * ca.x, s * ca.y, s * ca.z};
+                n2 = V3{s * ab.x, s * ab.y, s * ab.z};
                 const double e2 = max3(edge2(a, b), edge2(b, c), edge2(c, a));
                 const double m = e2 / 3.0 + 1e-5 + 32.0 * tol +
                                  2e-12 / fabs(D);
@@ -269,11 +211,7 @@ __global__ __launch_bounds__(kBlock) void setup(
     }
 }
 
-__device__ inline bool in_box(const double *__restrict__ b, const Vec3 &q)
-{
-    return q.x >= b[0] && q.x <= b[3] && q.y >= b[1] && q.y <= b[4] &&
-           q.z >= b[2] && q.z <= b[5];
-}
+// (in_box, push_children: remap_tree.h)
 
 // one lane per point
 __global__ __launch_bounds__(kWalkBlock) void locate_walk(
@@ -292,7 +230,7 @@ __global__ __launch_bounds__(kWalkBlock) void locate_walk(
     const int64_t w = (int64_t)blockIdx.x * kWalkBlock + lane;
     if (w >= n_pts)
         return;
-    const Vec3 q = load3(points, w);
+    const V3 q = load3(points, w);
     uint32_t best = kNoTriangle;
     int top = 0;
     if (in_box(boxes + T.first[T.levels - 1] * 6, q))
@@ -309,9 +247,9 @@ __global__ __launch_bounds__(kWalkBlock) void locate_walk(
                 if (i >= best)
                     continue;
                 const double *n = normals + p * 9;
-                const double w0 = dot(q, Vec3{n[0], n[1], n[2]});
-                const double w1 = dot(q, Vec3{n[3], n[4], n[5]});
-                const double w2 = dot(q, Vec3{n[6], n[7], n[8]});
+                const double w0 = dot(q, V3{n[0], n[1], n[2]});
+                const double w1 = dot(q, V3{n[3], n[4], n[5]});
+                const double w2 = dot(q, V3{n[6], n[7], n[8]});
                 const double tot = (w0 + w1) + w2;
                 const double least = -tol * tot;
                 if (tot > 0.0 && w0 >= least && w1 >= least && w2 >= least)
@@ -319,20 +257,13 @@ __global__ __launch_bounds__(kWalkBlock) void locate_walk(
             }
             continue;
         }
-        const int64_t n_below = T.count[l - 1];
-        const double *below = boxes + T.first[l - 1] * 6;
-        const int64_t c0 = k * kFan;
-        const uint32_t tag = static_cast<uint32_t>(l - 1) << kNodeBits;
-#pragma unroll
-        for (int c = kFan - 1; c >= 0; --c)
-            if (c0 + c < n_below && in_box(below + (c0 + c) * 6, q))
-                stack[top++][lane] = tag | static_cast<uint32_t>(c0 + c);
+        push_children(T, boxes, l, k, q, stack, lane, top);
     }
     double S0 = 0.0, S1 = 0.0, S2 = 0.0;
-    Vec3 a, b, c;
+    V3 a, b, c;
     if (best != kNoTriangle && corners(best, n_nodes, xyz, tri, a, b, c)) {
         // the definition, on the winner alone
-        const Vec3 bc = cross(b, c), ca = cross(c, a), ab = cross(a, b);
+        const V3 bc = cross(b, c), ca = cross(c, a), ab = cross(a, b);
         const double s = dot(a, bc) < 0.0 ? -1.0 : 1.0;
         const double w0 = s * dot(q, bc), w1 = s * dot(q, ca),
                      w2 = s * dot(q, ab);
@@ -367,57 +298,35 @@ int check_args(const double *xyz, int64_t n_nodes, const int32_t *tri,
     return REMAP_OK;
 }
 
+// a leaf holds its triangles' three edge normals
+constexpr size_t kPayload = 72;
+
 // the three phases; ev (NULL, or 4 events) is recorded around them
-int run(const Layout &lay, const double *xyz, int64_t n_nodes,
+int run(const TreeLayout &lay, const double *xyz, int64_t n_nodes,
         const int32_t *tri, int64_t n_tri, const double *points,
         int64_t n_pts, double tol, int32_t *found_out, double *weights_out,
         void *workspace, hipStream_t stream, hipEvent_t *ev)
 {
-    char *ws = static_cast<char *>(workspace);
-    uint64_t *keys_in = reinterpret_cast<uint64_t *>(ws + lay.keys_in);
-    uint64_t *keys_out = reinterpret_cast<uint64_t *>(ws + lay.keys_out);
-    uint32_t *idx_in = reinterpret_cast<uint32_t *>(ws + lay.idx_in);
-    uint32_t *idx_out = reinterpret_cast<uint32_t *>(ws + lay.idx_out);
-    double *normals = reinterpret_cast<double *>(ws + lay.normals);
-    double *boxes = reinterpret_cast<double *>(ws + lay.boxes);
+    const TreeArrays A = tree_arrays(lay, workspace);
     const Tree &T = lay.tree;
-
-    if (ev)
-        REMAP_HIP_CHECK(hipEventRecord(ev[0], stream));
-    hipLaunchKernelGGL(centroid_keys, dim3(blocks(n_tri, kBlock)),
-                       dim3(kBlock), 0, stream, n_tri, n_nodes, xyz, tri,
-                       keys_in, idx_in);
-    REMAP_HIP_CHECK(hipGetLastError());
-    size_t tb = lay.temp_bytes;
-    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-        ws + lay.temp, tb, static_cast<const uint64_t *>(keys_in), keys_out,
-        static_cast<const uint32_t *>(idx_in), idx_out,
-        static_cast<size_t>(n_tri), 0u, 63u, stream)));
-    if (ev)
-        REMAP_HIP_CHECK(hipEventRecord(ev[1], stream));
-    hipLaunchKernelGGL(setup, dim3(blocks(n_tri, kBlock)), dim3(kBlock), 0,
-                       stream, n_tri, n_nodes, xyz, tri, idx_out, tol,
-                       normals, boxes);
-    REMAP_HIP_CHECK(hipGetLastError());
-    for (int l = 1; l < T.levels; ++l) {
-        hipLaunchKernelGGL(upper_boxes, dim3(blocks(T.count[l], kBlock)),
-                           dim3(kBlock), 0, stream, T.count[l],
-                           T.count[l - 1], boxes + T.first[l - 1] * 6,
-                           boxes + T.first[l] * 6);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
-    if (ev)
-        REMAP_HIP_CHECK(hipEventRecord(ev[2], stream));
+    REMAP_TRY(build_tree(
+        lay, A, n_tri, workspace, stream, ev,
+        [&] {
+            return launch(centroid_keys, n_tri, kBlock, stream, n_tri,
+                          n_nodes, xyz, tri, A.keys_in, A.idx_in);
+        },
+        nothing_sorted,
+        [&] {
+            return launch(setup, n_tri, kBlock, stream, n_tri, n_nodes, xyz,
+                          tri, A.orig, tol, A.payload, A.boxes);
+        }));
     const size_t lds = size_t(stack_depth(T.levels)) * kWalkBlock * 4;
-    for (int64_t at = 0; at < n_pts; at += kWalkChunk) {
-        const int64_t m = n_pts - at < kWalkChunk ? n_pts - at : kWalkChunk;
-        const dim3 grid(blocks(m, kWalkBlock)), block(kWalkBlock);
-        hipLaunchKernelGGL(locate_walk, grid, block, lds, stream, T, n_tri,
-                           normals, idx_out, boxes, n_nodes, xyz, tri, m,
-                           points + 3 * at, tol, found_out + at,
-                           weights_out + 3 * at);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
+    REMAP_TRY(walk_chunks(n_pts, [&](int64_t at, int64_t m) {
+        return launch_blocks(locate_walk, blocks(m, kWalkBlock), kWalkBlock,
+                             lds, stream, T, n_tri, A.payload, A.orig,
+                             A.boxes, n_nodes, xyz, tri, m, points + 3 * at,
+                             tol, found_out + at, weights_out + 3 * at);
+    }));
     if (ev)
         REMAP_HIP_CHECK(hipEventRecord(ev[3], stream));
     return REMAP_OK;
@@ -431,10 +340,8 @@ int locate_workspace(int64_t n_nodes, int64_t n_tri, int64_t n_pts,
     if (!bytes_out || n_nodes < 1 || n_tri < 1 || n_pts < 0 ||
         n_tri > INT32_MAX)
         return fail(REMAP_ERR_ARG, "remap_locate_workspace: bad args");
-    Layout lay;
-    const int rc = make_layout(n_tri, &lay);
-    if (rc != REMAP_OK)
-        return rc;
+    TreeLayout lay;
+    REMAP_TRY(make_tree_layout(n_tri, kPayload, &lay));
     *bytes_out = lay.total;
     return REMAP_OK;
 }
@@ -444,43 +351,22 @@ int locate(const double *xyz, int64_t n_nodes, const int32_t *tri,
            int32_t *found_out, double *weights_out, void *workspace,
            size_t workspace_bytes, hipStream_t stream, float *phase_ms)
 {
-    int rc = check_args(xyz, n_nodes, tri, n_tri, points, n_pts, tol,
-                        found_out, weights_out);
-    if (rc != REMAP_OK)
-        return rc;
-    Layout lay;
-    rc = make_layout(n_tri, &lay);
-    if (rc != REMAP_OK)
-        return rc;
-    if (!workspace || workspace_bytes < lay.total)
-        return fail(REMAP_ERR_WORKSPACE,
-                    "remap_locate: workspace of %zu bytes, need %zu",
-                    workspace_bytes, lay.total);
+    REMAP_TRY(check_args(xyz, n_nodes, tri, n_tri, points, n_pts, tol,
+                         found_out, weights_out));
+    TreeLayout lay;
+    REMAP_TRY(make_tree_layout(n_tri, kPayload, &lay));
+    REMAP_TRY(need_workspace("remap_locate", workspace, workspace_bytes,
+                             lay.total));
     if (!phase_ms) {
         if (n_pts == 0)
             return REMAP_OK;
         return run(lay, xyz, n_nodes, tri, n_tri, points, n_pts, tol,
                    found_out, weights_out, workspace, stream, nullptr);
     }
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipError_t err = hipSuccess;
-    for (int k = 0; k < 4 && err == hipSuccess; ++k)
-        err = hipEventCreate(&ev[k]);
-    if (err == hipSuccess) {
-        rc = run(lay, xyz, n_nodes, tri, n_tri, points, n_pts, tol,
-                 found_out, weights_out, workspace, stream, ev);
-        if (rc == REMAP_OK)
-            err = hipEventSynchronize(ev[3]);
-        for (int k = 0; k < 3 && rc == REMAP_OK && err == hipSuccess; ++k)
-            err = hipEventElapsedTime(&phase_ms[k], ev[k], ev[k + 1]);
-    }
-    for (int k = 0; k < 4; ++k)
-        if (ev[k])
-            (void)hipEventDestroy(ev[k]);
-    if (rc != REMAP_OK)
-        return rc;
-    REMAP_HIP_CHECK(err);
-    return REMAP_OK;
+    return timed_phases<4>(phase_ms, [&](hipEvent_t *ev) {
+        return run(lay, xyz, n_nodes, tri, n_tri, points, n_pts, tol,
+                   found_out, weights_out, workspace, stream, ev);
+    });
 }
 
 }  // namespace remap

@@ -47,7 +47,7 @@
 // the output holds the min(k, n_src) sources that come first in (d2(i, j), j)
 // lexicographic order, ascending; the slots behind them hold index -1 and
 // d2 = +inf.  k = 1 is remap_nearest's answer.  Everything before the walk
-// is shared (build_tree); nearest_k_walk is nearest_walk with "best" read as
+// is shared (build); nearest_k_walk is nearest_walk with "best" read as
 // "k-th best":
 //   * beside the stack a lane keeps its k best in LDS, [entry][lane], d2
 //     (fp64) then index (int32), ascending in (d2, index).  Every slot starts
@@ -75,24 +75,20 @@
 #include <cstring>
 #include <string.h>
 
-#include <rocprim/rocprim.hpp>
-
 #include "remap_common.h"
 #include "remap_tree.h"
 
 namespace remap {
 namespace {
 
-constexpr int kWalkBlock = 64;
-// (kLeaf sorted points a leaf, kFan nodes below a node: remap_tree.h)
+// (kWalkBlock lanes a walking block, kWalkChunk points a launch,
+// kLeaf sorted points a leaf, kFan nodes below a node: remap_tree.h)
 // the walk steps into one child and stacks at most kFan - 1 a level above
 // level 0, so that bounds the stack whatever the points are.  The launch
 // sizes the LDS by the tree at hand (8 bytes an entry and lane): the fewer
 // levels, the more walking waves fit beside each other in a CU
 constexpr int stack_depth(int levels) { return (kFan - 1) * (levels - 1); }
 constexpr uint32_t kNone = 0xffffffffu;   // no node (levels end at 14)
-// one walk launch: its block count stays far below the grid limit
-constexpr int64_t kWalkChunk = int64_t(1) << 30;
 
 static_assert(kFan == 4, "nearest_walk sorts four children by hand");
 static_assert(stack_depth(kMaxLevels) * kWalkBlock * 8 <= 64 * 1024,
@@ -102,35 +98,6 @@ constexpr size_t list_bytes(int k) { return size_t(k) * kWalkBlock * 12; }
 static_assert(stack_depth(kMaxLevels) * kWalkBlock * 8 +
                       list_bytes(REMAP_NEAREST_K_MAX) <= 64 * 1024,
               "the k-walk's stack and list must fit in a workgroup's LDS");
-
-struct Layout {
-    Tree tree;
-    size_t keys_in, keys_out, idx_in, idx_out, xyz, boxes, temp, total;
-    size_t temp_bytes;
-};
-
-int make_layout(int64_t n_src, Layout *lay)
-{
-    const size_t n = static_cast<size_t>(n_src);
-    const int64_t nodes = make_tree(n_src, &lay->tree);
-    size_t sort_bytes = 0;
-    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-        nullptr, sort_bytes, static_cast<const uint64_t *>(nullptr),
-        static_cast<uint64_t *>(nullptr),
-        static_cast<const uint32_t *>(nullptr),
-        static_cast<uint32_t *>(nullptr), n, 0u, 63u)));
-    lay->temp_bytes = sort_bytes;
-    size_t off = 0;
-    lay->keys_in = off;  off += align_up(n * 8);
-    lay->keys_out = off; off += align_up(n * 8);
-    lay->idx_in = off;   off += align_up(n * 4);
-    lay->idx_out = off;  off += align_up(n * 4);
-    lay->xyz = off;      off += align_up(n * 24);
-    lay->boxes = off;    off += align_up(static_cast<size_t>(nodes) * 48);
-    lay->temp = off;     off += align_up(lay->temp_bytes);
-    lay->total = off;
-    return REMAP_OK;
-}
 
 __global__ __launch_bounds__(kBlock) void morton_keys(
     int64_t n, const double *__restrict__ xyz, uint64_t *__restrict__ keys,
@@ -472,109 +439,66 @@ int check_args(const double *src_xyz, int64_t n_src, const double *dst_xyz,
     return REMAP_OK;
 }
 
-// what a walk reads in the workspace once build_tree() has run
-struct Built {
-    const double *sorted;
-    const uint32_t *orig;
-    const double *boxes;
-};
+// a leaf holds its points' xyz, gathered into sorted order
+constexpr size_t kPayload = 24;
 
-// the two phases before a walk: sort and boxes; ev (NULL, or at least 3
-// events) is recorded around them
-int build_tree(const Layout &lay, const double *src_xyz, int64_t n_src,
-               void *workspace, hipStream_t stream, hipEvent_t *ev,
-               Built *built)
+// the two phases before a walk: sort (with the gather) and boxes; ev (NULL,
+// or at least 3 events) is recorded around them
+int build(const TreeLayout &lay, const TreeArrays &A, const double *src_xyz,
+          int64_t n_src, void *workspace, hipStream_t stream, hipEvent_t *ev)
 {
-    char *ws = static_cast<char *>(workspace);
-    uint64_t *keys_in = reinterpret_cast<uint64_t *>(ws + lay.keys_in);
-    uint64_t *keys_out = reinterpret_cast<uint64_t *>(ws + lay.keys_out);
-    uint32_t *idx_in = reinterpret_cast<uint32_t *>(ws + lay.idx_in);
-    uint32_t *idx_out = reinterpret_cast<uint32_t *>(ws + lay.idx_out);
-    double *sorted = reinterpret_cast<double *>(ws + lay.xyz);
-    double *boxes = reinterpret_cast<double *>(ws + lay.boxes);
-    const Tree &T = lay.tree;
-    built->sorted = sorted;
-    built->orig = idx_out;
-    built->boxes = boxes;
-
-    if (ev)
-        REMAP_HIP_CHECK(hipEventRecord(ev[0], stream));
-    hipLaunchKernelGGL(morton_keys, dim3(blocks(n_src, kBlock)), dim3(kBlock),
-                       0, stream, n_src, src_xyz, keys_in, idx_in);
-    REMAP_HIP_CHECK(hipGetLastError());
-    size_t tb = lay.temp_bytes;
-    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-        ws + lay.temp, tb, static_cast<const uint64_t *>(keys_in), keys_out,
-        static_cast<const uint32_t *>(idx_in), idx_out,
-        static_cast<size_t>(n_src), 0u, 63u, stream)));
-    hipLaunchKernelGGL(gather_sorted, dim3(blocks(n_src, kBlock)),
-                       dim3(kBlock), 0, stream, n_src, src_xyz, idx_out,
-                       sorted);
-    REMAP_HIP_CHECK(hipGetLastError());
-    if (ev)
-        REMAP_HIP_CHECK(hipEventRecord(ev[1], stream));
-    hipLaunchKernelGGL(leaf_boxes, dim3(blocks(T.count[0], kBlock)),
-                       dim3(kBlock), 0, stream, n_src, T.count[0], sorted,
-                       boxes);
-    REMAP_HIP_CHECK(hipGetLastError());
-    for (int l = 1; l < T.levels; ++l) {
-        hipLaunchKernelGGL(upper_boxes, dim3(blocks(T.count[l], kBlock)),
-                           dim3(kBlock), 0, stream, T.count[l],
-                           T.count[l - 1], boxes + T.first[l - 1] * 6,
-                           boxes + T.first[l] * 6);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
-    if (ev)
-        REMAP_HIP_CHECK(hipEventRecord(ev[2], stream));
-    return REMAP_OK;
+    return build_tree(
+        lay, A, n_src, workspace, stream, ev,
+        [&] {
+            return launch(morton_keys, n_src, kBlock, stream, n_src, src_xyz,
+                          A.keys_in, A.idx_in);
+        },
+        [&] {
+            return launch(gather_sorted, n_src, kBlock, stream, n_src,
+                          src_xyz, A.orig, A.payload);
+        },
+        [&] {
+            const int64_t n_leaves = lay.tree.count[0];
+            return launch(leaf_boxes, n_leaves, kBlock, stream, n_src,
+                          n_leaves, A.payload, A.boxes);
+        });
 }
 
 // the three phases; ev (NULL, or 4 events) is recorded around them
-int run(const Layout &lay, const double *src_xyz, int64_t n_src,
+int run(const TreeLayout &lay, const double *src_xyz, int64_t n_src,
         const double *dst_xyz, int64_t n_dst, int32_t *nearest_out,
         void *workspace, hipStream_t stream, hipEvent_t *ev)
 {
-    Built t;
-    const int rc = build_tree(lay, src_xyz, n_src, workspace, stream, ev, &t);
-    if (rc != REMAP_OK)
-        return rc;
+    const TreeArrays A = tree_arrays(lay, workspace);
+    REMAP_TRY(build(lay, A, src_xyz, n_src, workspace, stream, ev));
     const Tree &T = lay.tree;
     const size_t lds = size_t(stack_depth(T.levels)) * kWalkBlock * 8;
-    for (int64_t at = 0; at < n_dst; at += kWalkChunk) {
-        const int64_t m = n_dst - at < kWalkChunk ? n_dst - at : kWalkChunk;
-        const dim3 grid(blocks(m, kWalkBlock)), block(kWalkBlock);
-        hipLaunchKernelGGL(nearest_walk, grid, block, lds, stream, T, n_src,
-                           t.sorted, t.orig, t.boxes, m, dst_xyz + 3 * at,
-                           nearest_out + at);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
+    REMAP_TRY(walk_chunks(n_dst, [&](int64_t at, int64_t m) {
+        return launch_blocks(nearest_walk, blocks(m, kWalkBlock), kWalkBlock,
+                             lds, stream, T, n_src, A.payload, A.orig,
+                             A.boxes, m, dst_xyz + 3 * at, nearest_out + at);
+    }));
     if (ev)
         REMAP_HIP_CHECK(hipEventRecord(ev[3], stream));
     return REMAP_OK;
 }
 
 // sort, boxes, then the k-walk
-int run_k(const Layout &lay, const double *src_xyz, int64_t n_src,
+int run_k(const TreeLayout &lay, const double *src_xyz, int64_t n_src,
           const double *dst_xyz, int64_t n_dst, int k, int32_t *idx_out,
           double *d2_out, void *workspace, hipStream_t stream)
 {
-    Built t;
-    const int rc = build_tree(lay, src_xyz, n_src, workspace, stream, nullptr,
-                              &t);
-    if (rc != REMAP_OK)
-        return rc;
+    const TreeArrays A = tree_arrays(lay, workspace);
+    REMAP_TRY(build(lay, A, src_xyz, n_src, workspace, stream, nullptr));
     const Tree &T = lay.tree;
     const size_t lds = list_bytes(k) +
         size_t(stack_depth(T.levels)) * kWalkBlock * 8;
-    for (int64_t at = 0; at < n_dst; at += kWalkChunk) {
-        const int64_t m = n_dst - at < kWalkChunk ? n_dst - at : kWalkChunk;
-        const dim3 grid(blocks(m, kWalkBlock)), block(kWalkBlock);
-        hipLaunchKernelGGL(nearest_k_walk, grid, block, lds, stream, T, n_src,
-                           t.sorted, t.orig, t.boxes, m, dst_xyz + 3 * at, k,
-                           idx_out + at * k, d2_out + at * k);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
-    return REMAP_OK;
+    return walk_chunks(n_dst, [&](int64_t at, int64_t m) {
+        return launch_blocks(nearest_k_walk, blocks(m, kWalkBlock),
+                             kWalkBlock, lds, stream, T, n_src, A.payload,
+                             A.orig, A.boxes, m, dst_xyz + 3 * at, k,
+                             idx_out + at * k, d2_out + at * k);
+    });
 }
 
 }  // namespace
@@ -583,10 +507,8 @@ int nearest_workspace(int64_t n_src, int64_t n_dst, size_t *bytes_out)
 {
     if (!bytes_out || n_src < 1 || n_dst < 0 || n_src > INT32_MAX)
         return fail(REMAP_ERR_ARG, "remap_nearest_workspace: bad args");
-    Layout lay;
-    const int rc = make_layout(n_src, &lay);
-    if (rc != REMAP_OK)
-        return rc;
+    TreeLayout lay;
+    REMAP_TRY(make_tree_layout(n_src, kPayload, &lay));
     *bytes_out = lay.total;
     return REMAP_OK;
 }
@@ -595,42 +517,21 @@ int nearest(const double *src_xyz, int64_t n_src, const double *dst_xyz,
             int64_t n_dst, int32_t *nearest_out, void *workspace,
             size_t workspace_bytes, hipStream_t stream, float *phase_ms)
 {
-    int rc = check_args(src_xyz, n_src, dst_xyz, n_dst, nearest_out);
-    if (rc != REMAP_OK)
-        return rc;
-    Layout lay;
-    rc = make_layout(n_src, &lay);
-    if (rc != REMAP_OK)
-        return rc;
-    if (!workspace || workspace_bytes < lay.total)
-        return fail(REMAP_ERR_WORKSPACE,
-                    "remap_nearest: workspace of %zu bytes, need %zu",
-                    workspace_bytes, lay.total);
+    REMAP_TRY(check_args(src_xyz, n_src, dst_xyz, n_dst, nearest_out));
+    TreeLayout lay;
+    REMAP_TRY(make_tree_layout(n_src, kPayload, &lay));
+    REMAP_TRY(need_workspace("remap_nearest", workspace, workspace_bytes,
+                             lay.total));
     if (!phase_ms) {
         if (n_dst == 0)
             return REMAP_OK;
         return run(lay, src_xyz, n_src, dst_xyz, n_dst, nearest_out,
                    workspace, stream, nullptr);
     }
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipError_t err = hipSuccess;
-    for (int k = 0; k < 4 && err == hipSuccess; ++k)
-        err = hipEventCreate(&ev[k]);
-    if (err == hipSuccess) {
-        rc = run(lay, src_xyz, n_src, dst_xyz, n_dst, nearest_out, workspace,
-                 stream, ev);
-        if (rc == REMAP_OK)
-            err = hipEventSynchronize(ev[3]);
-        for (int k = 0; k < 3 && rc == REMAP_OK && err == hipSuccess; ++k)
-            err = hipEventElapsedTime(&phase_ms[k], ev[k], ev[k + 1]);
-    }
-    for (int k = 0; k < 4; ++k)
-        if (ev[k])
-            (void)hipEventDestroy(ev[k]);
-    if (rc != REMAP_OK)
-        return rc;
-    REMAP_HIP_CHECK(err);
-    return REMAP_OK;
+    return timed_phases<4>(phase_ms, [&](hipEvent_t *ev) {
+        return run(lay, src_xyz, n_src, dst_xyz, n_dst, nearest_out,
+                   workspace, stream, ev);
+    });
 }
 
 int nearest_k_workspace(int64_t n_src, int64_t n_dst, int32_t k,
@@ -639,10 +540,8 @@ int nearest_k_workspace(int64_t n_src, int64_t n_dst, int32_t k,
     if (!bytes_out || n_src < 1 || n_dst < 0 || n_src > INT32_MAX || k < 1 ||
         k > REMAP_NEAREST_K_MAX)
         return fail(REMAP_ERR_ARG, "remap_nearest_k_workspace: bad args");
-    Layout lay;
-    const int rc = make_layout(n_src, &lay);
-    if (rc != REMAP_OK)
-        return rc;
+    TreeLayout lay;
+    REMAP_TRY(make_tree_layout(n_src, kPayload, &lay));
     *bytes_out = lay.total;
     return REMAP_OK;
 }
@@ -660,14 +559,10 @@ int nearest_k(const double *src_xyz, int64_t n_src, const double *dst_xyz,
                     REMAP_NEAREST_K_MAX);
     if (!src_xyz || (n_dst > 0 && (!dst_xyz || !idx_out || !d2_out)))
         return fail(REMAP_ERR_ARG, "remap_nearest_k: NULL array");
-    Layout lay;
-    const int rc = make_layout(n_src, &lay);
-    if (rc != REMAP_OK)
-        return rc;
-    if (!workspace || workspace_bytes < lay.total)
-        return fail(REMAP_ERR_WORKSPACE,
-                    "remap_nearest_k: workspace of %zu bytes, need %zu",
-                    workspace_bytes, lay.total);
+    TreeLayout lay;
+    REMAP_TRY(make_tree_layout(n_src, kPayload, &lay));
+    REMAP_TRY(need_workspace("remap_nearest_k", workspace, workspace_bytes,
+                             lay.total));
     if (n_dst == 0)
         return REMAP_OK;
     return run_k(lay, src_xyz, n_src, dst_xyz, n_dst, k, idx_out, d2_out,

@@ -44,9 +44,10 @@
 // are re-keyed to their cells, sorted, and merge_runs adds every run of equal
 // keys up in a fixed order before the sliver rule is applied to the sum.
 //
-// The host side is written with a few helpers (launch, at, read_back, the
-// typed rocPRIM calls), one Route table per entry point that turns the error
-// bits into text (route_fail), and take() for every workspace layout.
+// The host side is written with remap_host.h's helpers (launch, at,
+// read_back, the typed rocPRIM calls, take() for every workspace layout) and
+// one Route table per entry point that turns the error bits into text
+// (route_fail).
 // Host read-backs: one in remap_overlap_latlon, two in remap_overlap_meshes,
 // one in remap_overlap_grids (the entry count with every error bit, before
 // the sort), remap_overlap_meshes' two and up to two more in
@@ -58,10 +59,9 @@
 #include <cstring>
 #include <string.h>
 
-#include <rocprim/rocprim.hpp>
-
 #include "remap_clip.h"
 #include "remap_common.h"
+#include "remap_host.h"
 #include "remap_sphere.h"
 
 namespace remap {
@@ -81,137 +81,6 @@ constexpr int kPrepBlock = 64;
 constexpr double kSliver = 1e-14;
 // slack of the boxes, radians (rounding of the corners' lat / lon)
 constexpr double kBoxEps = 1e-9;
-
-constexpr size_t kAlign = 256;
-size_t align_up(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
-
-uint32_t blocks(int64_t n, int per) { return static_cast<uint32_t>((n + per - 1) / per); }
-// (no buffer and no rocPRIM call is sized 0)
-size_t at_least_one(int64_t n) { return static_cast<size_t>(n > 0 ? n : 1); }
-
-#define REMAP_TRY(expr)                                         \
-    do {                                                        \
-        const int rc__ = (expr);                                \
-        if (rc__ != REMAP_OK)                                   \
-            return rc__;                                        \
-    } while (0)
-
-// ---------------------------------------------------------------------------
-// host helpers: every launch, rocPRIM call, workspace pointer and read-back
-// of this file goes through these (each returns REMAP_OK or what fail() gave)
-// ---------------------------------------------------------------------------
-
-// one lane per item in blocks of `block`; nothing to launch for no items
-template <class... P, class... A>
-int launch(void (*kernel)(P...), int64_t n_items, int block,
-           hipStream_t stream, A... args)
-{
-    if (n_items <= 0)
-        return REMAP_OK;
-    hipLaunchKernelGGL(kernel, dim3(blocks(n_items, block)), dim3(block), 0,
-                       stream, static_cast<P>(args)...);
-    REMAP_HIP_CHECK(hipGetLastError());
-    return REMAP_OK;
-}
-
-template <class T>
-T *at(char *ws, size_t off)
-{
-    return reinterpret_cast<T *>(ws + off);
-}
-
-// a word of a counter block as what a kernel writes there
-template <class T, class U>
-T *as(U *word)
-{
-    return reinterpret_cast<T *>(word);
-}
-
-// bytes from the device, waited for
-int read_back(void *dst, const void *src, size_t bytes, hipStream_t stream)
-{
-    REMAP_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost,
-                                   stream));
-    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
-    return REMAP_OK;
-}
-
-// rocPRIM, typed; *_temp: the bytes of temporary storage n items need
-template <class T>
-int exclusive_scan(void *temp, size_t temp_bytes, const T *in, T *out,
-                   int64_t n, hipStream_t stream)
-{
-    REMAP_HIP_CHECK((rocprim::exclusive_scan(temp, temp_bytes, in, out, T(0),
-                                             static_cast<size_t>(n),
-                                             rocprim::plus<T>(), stream)));
-    return REMAP_OK;
-}
-
-template <class T>
-int scan_temp(size_t n, size_t *bytes)
-{
-    REMAP_HIP_CHECK((rocprim::exclusive_scan(
-        nullptr, *bytes, static_cast<const T *>(nullptr),
-        static_cast<T *>(nullptr), T(0), n, rocprim::plus<T>())));
-    return REMAP_OK;
-}
-
-int radix_sort_keys(void *temp, size_t temp_bytes, const uint64_t *in,
-                    uint64_t *out, int64_t n, hipStream_t stream)
-{
-    REMAP_HIP_CHECK((rocprim::radix_sort_keys(temp, temp_bytes, in, out,
-                                              static_cast<size_t>(n), 0u, 64u,
-                                              stream)));
-    return REMAP_OK;
-}
-
-int sort_keys_temp(size_t n, size_t *bytes)
-{
-    REMAP_HIP_CHECK((rocprim::radix_sort_keys(
-        nullptr, *bytes, static_cast<const uint64_t *>(nullptr),
-        static_cast<uint64_t *>(nullptr), n, 0u, 64u)));
-    return REMAP_OK;
-}
-
-// V: double (areas) or uint32_t (positions)
-template <class V>
-int radix_sort_pairs(void *temp, size_t temp_bytes, const uint64_t *keys_in,
-                     uint64_t *keys_out, const V *in, V *out, int64_t n,
-                     hipStream_t stream)
-{
-    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-        temp, temp_bytes, keys_in, keys_out, in, out, static_cast<size_t>(n),
-        0u, 64u, stream)));
-    return REMAP_OK;
-}
-
-template <class V>
-int sort_pairs_temp(size_t n, size_t *bytes)
-{
-    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-        nullptr, *bytes, static_cast<const uint64_t *>(nullptr),
-        static_cast<uint64_t *>(nullptr), static_cast<const V *>(nullptr),
-        static_cast<V *>(nullptr), n, 0u, 64u)));
-    return REMAP_OK;
-}
-
-int unique(void *temp, size_t temp_bytes, const uint64_t *in, uint64_t *out,
-           uint64_t *n_unique, int64_t n, hipStream_t stream)
-{
-    REMAP_HIP_CHECK((rocprim::unique(temp, temp_bytes, in, out, n_unique,
-                                     static_cast<size_t>(n),
-                                     rocprim::equal_to<uint64_t>(), stream)));
-    return REMAP_OK;
-}
-
-int unique_temp(size_t n, size_t *bytes)
-{
-    REMAP_HIP_CHECK((rocprim::unique(
-        nullptr, *bytes, static_cast<const uint64_t *>(nullptr),
-        static_cast<uint64_t *>(nullptr), static_cast<uint64_t *>(nullptr),
-        n)));
-    return REMAP_OK;
-}
 
 // the lat-lon cell with 0-based index g = j * n_lon + i, corners SW, SE, NE,
 // NW (swapped to SW, NW, NE, SE when exactly one axis descends, so that the
@@ -784,13 +653,6 @@ int check_call(const char *who, int64_t n_pairs, const Outputs &out)
     return REMAP_OK;
 }
 
-size_t take(size_t *off, size_t bytes)
-{
-    const size_t at = *off;
-    *off += align_up(bytes);
-    return at;
-}
-
 // one side's prepared cells in the workspace (radius: the mesh and grid
 // routes' cell_shape; the lat-lon route takes none)
 struct SideLayout {
@@ -1017,10 +879,8 @@ int overlap(const remap_overlap_geom *geom, int32_t dst_is_mesh,
     REMAP_TRY(check_call(kLatlon.who, n_pairs, out));
     Layout lay;
     REMAP_TRY(make_layout(G, n_pairs, &lay));
-    if (!workspace || workspace_bytes < lay.total)
-        return fail(REMAP_ERR_WORKSPACE,
-                    "remap_overlap_latlon: workspace of %zu bytes, need %zu",
-                    workspace_bytes, lay.total);
+    REMAP_TRY(need_workspace("remap_overlap_latlon", workspace,
+                             workspace_bytes, lay.total));
     bool swap = false;
     REMAP_TRY(axis_swap(G, stream, &swap));
     char *ws = static_cast<char *>(workspace);
@@ -2019,26 +1879,10 @@ int pieces_timed(const PiecesArg *pa, const PiecesArg *pb, int32_t dst_is_b,
 {
     if (!phase_ms)
         return fail(REMAP_ERR_ARG, "remap_overlap_pieces_timed: NULL phase_ms");
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipError_t err = hipSuccess;
-    for (int k = 0; k < 6 && err == hipSuccess; ++k)
-        err = hipEventCreate(&ev[k]);
-    int rc = REMAP_OK;
-    if (err == hipSuccess) {
-        rc = pieces(pa, pb, dst_is_b, n_pairs, workspace, workspace_bytes, out,
-                    stream, ev);
-        if (rc == REMAP_OK)
-            err = hipEventSynchronize(ev[5]);
-        for (int k = 0; k < 5 && rc == REMAP_OK && err == hipSuccess; ++k)
-            err = hipEventElapsedTime(&phase_ms[k], ev[k], ev[k + 1]);
-    }
-    for (int k = 0; k < 6; ++k)
-        if (ev[k])
-            (void)hipEventDestroy(ev[k]);
-    if (rc != REMAP_OK)
-        return rc;
-    REMAP_HIP_CHECK(err);
-    return REMAP_OK;
+    return timed_phases<6>(phase_ms, [&](hipEvent_t *ev) {
+        return pieces(pa, pb, dst_is_b, n_pairs, workspace, workspace_bytes,
+                      out, stream, ev);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -2506,10 +2350,8 @@ int grids(const remap_overlap_side *side_a, const remap_overlap_side *side_b,
     REMAP_TRY(grid_fixed_layout(A, B, &L));
     REMAP_TRY(mesh_var_layout(0, 0, n_pairs, &L.m));
     const MeshLayout &lay = L.m;
-    if (!workspace || workspace_bytes < lay.total)
-        return fail(REMAP_ERR_WORKSPACE,
-                    "remap_overlap_grids: workspace of %zu bytes, need %zu",
-                    workspace_bytes, lay.total);
+    REMAP_TRY(need_workspace("remap_overlap_grids", workspace,
+                             workspace_bytes, lay.total));
     char *ws = static_cast<char *>(workspace);
     Pyramid P;
     REMAP_TRY(grid_candidates(A, B, L, ws, out.a_area, out.b_area, &P,

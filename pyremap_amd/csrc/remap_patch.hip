@@ -33,10 +33,9 @@
 #include <cstring>
 #include <string.h>
 
-#include <rocprim/rocprim.hpp>
-
 #include "remap_clip.h"
 #include "remap_common.h"
+#include "remap_host.h"
 #include "remap_sphere.h"
 
 namespace remap {
@@ -56,11 +55,6 @@ constexpr int kErrIndex = 1;
 constexpr int kErrFound = 2;
 constexpr int kErrCapacity = 4;
 constexpr int32_t kNone = INT32_MAX;
-constexpr size_t kAlign = 256;
-
-size_t align_up(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
-uint32_t blocks(int64_t n, int per) { return static_cast<uint32_t>((n + per - 1) / per); }
-size_t at_least_one(int64_t n) { return static_cast<size_t>(n > 0 ? n : 1); }
 
 __device__ inline V3 node_at(const double *xyz, int64_t v)
 {
@@ -552,20 +546,16 @@ int rings_layout(int64_t n_tri, int64_t n_nodes, RingsLayout *lay)
 {
     const size_t n = at_least_one(n_tri) * 6;
     size_t sort = 0, scan = 0;
-    REMAP_HIP_CHECK((rocprim::radix_sort_keys(
-        nullptr, sort, static_cast<const uint64_t *>(nullptr),
-        static_cast<uint64_t *>(nullptr), n, 0u, 64u)));
-    REMAP_HIP_CHECK((rocprim::exclusive_scan(
-        nullptr, scan, static_cast<const uint32_t *>(nullptr),
-        static_cast<uint32_t *>(nullptr), 0u, n, rocprim::plus<uint32_t>())));
+    REMAP_TRY(sort_keys_temp(n, &sort));
+    REMAP_TRY(scan_temp<uint32_t>(n, &scan));
     lay->temp_bytes = sort > scan ? sort : scan;
     size_t off = 0;
-    lay->keys_in = off;  off += align_up(n * 8);
-    lay->keys_out = off; off += align_up(n * 8);
-    lay->head = off;     off += align_up(n * 4);
-    lay->rank = off;     off += align_up(n * 4);
-    lay->first = off;    off += align_up(at_least_one(n_nodes) * 4);
-    lay->temp = off;     off += align_up(lay->temp_bytes);
+    lay->keys_in = take(&off, n * 8);
+    lay->keys_out = take(&off, n * 8);
+    lay->head = take(&off, n * 4);
+    lay->rank = take(&off, n * 4);
+    lay->first = take(&off, at_least_one(n_nodes) * 4);
+    lay->temp = take(&off, lay->temp_bytes);
     lay->total = off;
     return REMAP_OK;
 }
@@ -583,14 +573,6 @@ int check_sizes(const char *name, int64_t n_nodes, int64_t n_tri)
     return REMAP_OK;
 }
 
-int read_status(int32_t *err, const int32_t *status, hipStream_t stream)
-{
-    REMAP_HIP_CHECK(hipMemcpyAsync(err, status, sizeof(int32_t),
-                                   hipMemcpyDeviceToHost, stream));
-    REMAP_HIP_CHECK(hipStreamSynchronize(stream));
-    return REMAP_OK;
-}
-
 int status_fail(const char *name, int32_t bits)
 {
     if (bits & kErrIndex)
@@ -604,12 +586,30 @@ int status_fail(const char *name, int32_t bits)
                 name);
 }
 
-int scan_bytes(int64_t n_pts, size_t *bytes)
+// the status word read back (the one read-back of a call, waited for): what
+// its bits say, or REMAP_OK
+int status_check(const char *name, const int32_t *status, hipStream_t stream)
 {
-    REMAP_HIP_CHECK((rocprim::exclusive_scan(
-        nullptr, *bytes, static_cast<const int64_t *>(nullptr),
-        static_cast<int64_t *>(nullptr), int64_t(0),
-        static_cast<size_t>(n_pts) + 1, rocprim::plus<int64_t>())));
+    int32_t err = 0;
+    REMAP_TRY(read_back(&err, status, sizeof(int32_t), stream));
+    if (err)
+        return status_fail(name, err);
+    return REMAP_OK;
+}
+
+// remap_patch_sizes' workspace: the n_pts + 1 counts, then the scan's scratch
+struct SizesLayout {
+    size_t cnt, temp, total, temp_bytes;
+};
+
+int sizes_layout(int64_t n_pts, SizesLayout *lay)
+{
+    REMAP_TRY(scan_temp<int64_t>(static_cast<size_t>(n_pts) + 1,
+                                 &lay->temp_bytes));
+    size_t off = 0;
+    lay->cnt = take(&off, static_cast<size_t>(n_pts + 1) * 8);
+    lay->temp = take(&off, lay->temp_bytes);
+    lay->total = off;
     return REMAP_OK;
 }
 
@@ -620,11 +620,9 @@ int node_rings_workspace(int64_t n_tri, int64_t n_nodes, size_t *bytes_out)
     const char *name = "remap_node_rings_workspace";
     if (!bytes_out)
         return fail(REMAP_ERR_ARG, "%s: NULL bytes_out", name);
-    if (const int rc = check_sizes(name, n_nodes, n_tri))
-        return rc;
+    REMAP_TRY(check_sizes(name, n_nodes, n_tri));
     RingsLayout lay;
-    if (const int rc = rings_layout(n_tri, n_nodes, &lay))
-        return rc;
+    REMAP_TRY(rings_layout(n_tri, n_nodes, &lay));
     *bytes_out = lay.total;
     return REMAP_OK;
 }
@@ -634,17 +632,12 @@ int node_rings(int64_t n_tri, const int32_t *tri, int64_t n_nodes,
                void *workspace, size_t workspace_bytes, hipStream_t stream)
 {
     const char *name = "remap_node_rings";
-    if (const int rc = check_sizes(name, n_nodes, n_tri))
-        return rc;
+    REMAP_TRY(check_sizes(name, n_nodes, n_tri));
     if (!ring_out || !count_out || !status || (n_tri > 0 && !tri))
         return fail(REMAP_ERR_ARG, "%s: NULL array", name);
     RingsLayout lay;
-    if (const int rc = rings_layout(n_tri, n_nodes, &lay))
-        return rc;
-    if (!workspace || workspace_bytes < lay.total)
-        return fail(REMAP_ERR_WORKSPACE,
-                    "%s: workspace of %zu bytes, need %zu", name,
-                    workspace_bytes, lay.total);
+    REMAP_TRY(rings_layout(n_tri, n_nodes, &lay));
+    REMAP_TRY(need_workspace(name, workspace, workspace_bytes, lay.total));
     REMAP_HIP_CHECK(hipMemsetAsync(status, 0, sizeof(int32_t), stream));
     REMAP_HIP_CHECK(hipMemsetAsync(ring_out, 0xff,
                                    sizeof(int32_t) * n_nodes * kRing, stream));
@@ -653,40 +646,23 @@ int node_rings(int64_t n_tri, const int32_t *tri, int64_t n_nodes,
     if (n_tri == 0)
         return REMAP_OK;
     char *ws = static_cast<char *>(workspace);
-    uint64_t *keys_in = reinterpret_cast<uint64_t *>(ws + lay.keys_in);
-    uint64_t *keys = reinterpret_cast<uint64_t *>(ws + lay.keys_out);
-    uint32_t *head = reinterpret_cast<uint32_t *>(ws + lay.head);
-    uint32_t *rank = reinterpret_cast<uint32_t *>(ws + lay.rank);
-    uint32_t *first = reinterpret_cast<uint32_t *>(ws + lay.first);
+    uint64_t *keys_in = at<uint64_t>(ws, lay.keys_in);
+    uint64_t *keys = at<uint64_t>(ws, lay.keys_out);
+    uint32_t *head = at<uint32_t>(ws, lay.head);
+    uint32_t *rank = at<uint32_t>(ws, lay.rank);
+    uint32_t *first = at<uint32_t>(ws, lay.first);
     void *temp = ws + lay.temp;
     const int64_t n = n_tri * 6;
-    hipLaunchKernelGGL(ring_pairs, dim3(blocks(n_tri, kBlock)), dim3(kBlock),
-                       0, stream, n_tri, tri, n_nodes, keys_in, status);
-    REMAP_HIP_CHECK(hipGetLastError());
-    size_t tb = lay.temp_bytes;
-    REMAP_HIP_CHECK((rocprim::radix_sort_keys(
-        temp, tb, static_cast<const uint64_t *>(keys_in), keys,
-        static_cast<size_t>(n), 0u, 64u, stream)));
-    hipLaunchKernelGGL(ring_heads, dim3(blocks(n, kBlock)), dim3(kBlock), 0,
-                       stream, n, keys, head);
-    REMAP_HIP_CHECK(hipGetLastError());
-    tb = lay.temp_bytes;
-    REMAP_HIP_CHECK((rocprim::exclusive_scan(
-        temp, tb, static_cast<const uint32_t *>(head), rank, 0u,
-        static_cast<size_t>(n), rocprim::plus<uint32_t>(), stream)));
-    hipLaunchKernelGGL(ring_firsts, dim3(blocks(n, kBlock)), dim3(kBlock), 0,
-                       stream, n, keys, rank, n_nodes, first);
-    REMAP_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(ring_fill, dim3(blocks(n, kBlock)), dim3(kBlock), 0,
-                       stream, n, keys, head, rank, first, n_nodes, ring_out,
-                       count_out);
-    REMAP_HIP_CHECK(hipGetLastError());
-    int32_t err = 0;
-    if (const int rc = read_status(&err, status, stream))
-        return rc;
-    if (err)
-        return status_fail(name, err);
-    return REMAP_OK;
+    REMAP_TRY(launch(ring_pairs, n_tri, kBlock, stream, n_tri, tri, n_nodes,
+                     keys_in, status));
+    REMAP_TRY(radix_sort_keys(temp, lay.temp_bytes, keys_in, keys, n, stream));
+    REMAP_TRY(launch(ring_heads, n, kBlock, stream, n, keys, head));
+    REMAP_TRY(exclusive_scan(temp, lay.temp_bytes, head, rank, n, stream));
+    REMAP_TRY(launch(ring_firsts, n, kBlock, stream, n, keys, rank, n_nodes,
+                     first));
+    REMAP_TRY(launch(ring_fill, n, kBlock, stream, n, keys, head, rank, first,
+                     n_nodes, ring_out, count_out));
+    return status_check(name, status, stream);
 }
 
 int patch_fits(int64_t n_nodes, const double *xyz, const int32_t *ring,
@@ -694,28 +670,19 @@ int patch_fits(int64_t n_nodes, const double *xyz, const int32_t *ring,
                int32_t *status, hipStream_t stream)
 {
     const char *name = "remap_patch_fits";
-    if (const int rc = check_sizes(name, n_nodes, 0))
-        return rc;
+    REMAP_TRY(check_sizes(name, n_nodes, 0));
     if (!xyz || !ring || !count || !fit_out || !has_out || !status)
         return fail(REMAP_ERR_ARG, "%s: NULL array", name);
     REMAP_HIP_CHECK(hipMemsetAsync(status, 0, sizeof(int32_t), stream));
-    hipLaunchKernelGGL(patch_fits_kernel, dim3(blocks(n_nodes, kBlock)),
-                       dim3(kBlock), 0, stream, n_nodes, xyz, ring, count,
-                       fit_out, has_out, status);
-    REMAP_HIP_CHECK(hipGetLastError());
-    int32_t err = 0;
-    if (const int rc = read_status(&err, status, stream))
-        return rc;
-    if (err)
-        return status_fail(name, err);
-    return REMAP_OK;
+    REMAP_TRY(launch(patch_fits_kernel, n_nodes, kBlock, stream, n_nodes, xyz,
+                     ring, count, fit_out, has_out, status));
+    return status_check(name, status, stream);
 }
 
 int check_points(const char *name, int64_t n_nodes, int64_t n_tri,
                  int64_t n_pts)
 {
-    if (const int rc = check_sizes(name, n_nodes, n_tri))
-        return rc;
+    REMAP_TRY(check_sizes(name, n_nodes, n_tri));
     if (n_tri > INT32_MAX || n_pts < 0 || n_pts > INT32_MAX)
         return fail(REMAP_ERR_ARG,
                     "%s: n_tri %lld, n_pts %lld: expected n_tri < 2^31 and "
@@ -732,11 +699,9 @@ int patch_sizes_workspace(int64_t n_pts, size_t *bytes_out)
     if (n_pts < 0 || n_pts > INT32_MAX)
         return fail(REMAP_ERR_ARG, "%s: n_pts %lld: expected 0 <= n_pts < "
                     "2^31", name, static_cast<long long>(n_pts));
-    size_t scan = 0;
-    if (const int rc = scan_bytes(n_pts, &scan))
-        return rc;
-    *bytes_out = align_up(static_cast<size_t>(n_pts + 1) * 8) +
-        align_up(scan);
+    SizesLayout lay;
+    REMAP_TRY(sizes_layout(n_pts, &lay));
+    *bytes_out = lay.total;
     return REMAP_OK;
 }
 
@@ -748,42 +713,28 @@ int patch_sizes(int64_t n_nodes, const double *xyz, int64_t n_tri,
                 size_t workspace_bytes, hipStream_t stream)
 {
     const char *name = "remap_patch_sizes";
-    if (const int rc = check_points(name, n_nodes, n_tri, n_pts))
-        return rc;
+    REMAP_TRY(check_points(name, n_nodes, n_tri, n_pts));
     if (!xyz || !ring || !count || !has || !offsets_out || !total_out ||
         !status || (n_tri > 0 && !tri) || (n_pts > 0 && (!found || !points)))
         return fail(REMAP_ERR_ARG, "%s: NULL array", name);
-    size_t scan = 0;
-    if (const int rc = scan_bytes(n_pts, &scan))
-        return rc;
-    const size_t need = align_up(static_cast<size_t>(n_pts + 1) * 8) +
-        align_up(scan);
-    if (!workspace || workspace_bytes < need)
-        return fail(REMAP_ERR_WORKSPACE,
-                    "%s: workspace of %zu bytes, need %zu", name,
-                    workspace_bytes, need);
+    SizesLayout lay;
+    REMAP_TRY(sizes_layout(n_pts, &lay));
+    REMAP_TRY(need_workspace(name, workspace, workspace_bytes, lay.total));
     char *ws = static_cast<char *>(workspace);
-    int64_t *cnt = reinterpret_cast<int64_t *>(ws);
-    void *temp = ws + align_up(static_cast<size_t>(n_pts + 1) * 8);
+    int64_t *cnt = at<int64_t>(ws, lay.cnt);
     *total_out = 0;
     REMAP_HIP_CHECK(hipMemsetAsync(status, 0, sizeof(int32_t), stream));
-    hipLaunchKernelGGL(patch_sizes_kernel, dim3(blocks(n_pts + 1, kBlock)),
-                       dim3(kBlock), 0, stream, n_nodes, xyz, n_tri, tri,
-                       ring, count, has, n_pts, found, points, cnt, status);
-    REMAP_HIP_CHECK(hipGetLastError());
-    REMAP_HIP_CHECK((rocprim::exclusive_scan(
-        temp, scan, static_cast<const int64_t *>(cnt), offsets_out,
-        int64_t(0), static_cast<size_t>(n_pts) + 1, rocprim::plus<int64_t>(),
-        stream)));
+    // (n_pts + 1 >= 1 lanes: the last writes the count behind the rows)
+    REMAP_TRY(launch(patch_sizes_kernel, n_pts + 1, kBlock, stream, n_nodes,
+                     xyz, n_tri, tri, ring, count, has, n_pts, found, points,
+                     cnt, status));
+    REMAP_TRY(exclusive_scan(ws + lay.temp, lay.temp_bytes, cnt, offsets_out,
+                             n_pts + 1, stream));
     int64_t total = 0;
     REMAP_HIP_CHECK(hipMemcpyAsync(&total, offsets_out + n_pts,
                                    sizeof(int64_t), hipMemcpyDeviceToHost,
                                    stream));
-    int32_t err = 0;
-    if (const int rc = read_status(&err, status, stream))
-        return rc;
-    if (err)
-        return status_fail(name, err);
+    REMAP_TRY(status_check(name, status, stream));
     *total_out = total;
     return REMAP_OK;
 }
@@ -797,8 +748,7 @@ int patch_rows(int64_t n_nodes, const double *xyz, int64_t n_tri,
                hipStream_t stream)
 {
     const char *name = "remap_patch_rows";
-    if (const int rc = check_points(name, n_nodes, n_tri, n_pts))
-        return rc;
+    REMAP_TRY(check_points(name, n_nodes, n_tri, n_pts));
     if (capacity < 0)
         return fail(REMAP_ERR_ARG, "%s: capacity %lld", name,
                     static_cast<long long>(capacity));
@@ -811,17 +761,11 @@ int patch_rows(int64_t n_nodes, const double *xyz, int64_t n_tri,
         (capacity > 0 && (!row_out || !col_out || !s_out)))
         return fail(REMAP_ERR_ARG, "%s: NULL array", name);
     REMAP_HIP_CHECK(hipMemsetAsync(status, 0, sizeof(int32_t), stream));
-    hipLaunchKernelGGL(patch_rows_kernel, dim3(blocks(n_pts, kBlock)),
-                       dim3(kBlock), 0, stream, n_nodes, xyz, n_tri, tri,
-                       ring, count, fit, has, n_pts, found, w, points, offsets,
-                       capacity, row_out, col_out, s_out, status);
-    REMAP_HIP_CHECK(hipGetLastError());
-    int32_t err = 0;
-    if (const int rc = read_status(&err, status, stream))
-        return rc;
-    if (err)
-        return status_fail(name, err);
-    return REMAP_OK;
+    REMAP_TRY(launch(patch_rows_kernel, n_pts, kBlock, stream, n_nodes, xyz,
+                     n_tri, tri, ring, count, fit, has, n_pts, found, w,
+                     points, offsets, capacity, row_out, col_out, s_out,
+                     status));
+    return status_check(name, status, stream);
 }
 
 }  // namespace remap

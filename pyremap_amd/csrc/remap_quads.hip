@@ -110,20 +110,16 @@
 #include <cstring>
 #include <string.h>
 
-#include <rocprim/rocprim.hpp>
-
 #include "remap_common.h"
 #include "remap_tree.h"
 
 namespace remap {
 namespace {
 
-constexpr int kWalkBlock = 64;
+// (kWalkBlock lanes a walking block, kWalkChunk points a launch: remap_tree.h)
 // every child whose box holds the point is stacked, then one is popped: at
 // most kFan - 1 stay behind a level above level 0, and kFan at the last
 constexpr int stack_depth(int levels) { return (kFan - 1) * (levels - 1) + 1; }
-// one walk launch: its block count stays far below the grid limit
-constexpr int64_t kWalkChunk = int64_t(1) << 30;
 constexpr uint32_t kNoQuad = 0xffffffffu;
 constexpr int kNewtonSteps = 12;
 
@@ -137,35 +133,6 @@ static_assert(stack_depth(kMaxLevels) * kWalkBlock * 4 <= 64 * 1024,
 struct Grid {
     int64_t ny, nx, nqx, n_quads;
 };
-
-struct Layout {
-    Tree tree;
-    size_t keys_in, keys_out, idx_in, idx_out, coef, boxes, temp, total;
-    size_t temp_bytes;
-};
-
-int make_layout(int64_t n_quads, Layout *lay)
-{
-    const size_t n = static_cast<size_t>(n_quads);
-    const int64_t nodes = make_tree(n_quads, &lay->tree);
-    size_t sort_bytes = 0;
-    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-        nullptr, sort_bytes, static_cast<const uint64_t *>(nullptr),
-        static_cast<uint64_t *>(nullptr),
-        static_cast<const uint32_t *>(nullptr),
-        static_cast<uint32_t *>(nullptr), n, 0u, 63u)));
-    lay->temp_bytes = sort_bytes;
-    size_t off = 0;
-    lay->keys_in = off;  off += align_up(n * 8);
-    lay->keys_out = off; off += align_up(n * 8);
-    lay->idx_in = off;   off += align_up(n * 4);
-    lay->idx_out = off;  off += align_up(n * 4);
-    lay->coef = off;     off += align_up(n * 96);
-    lay->boxes = off;    off += align_up(static_cast<size_t>(nodes) * 48);
-    lay->temp = off;     off += align_up(lay->temp_bytes);
-    lay->total = off;
-    return REMAP_OK;
-}
 
 // (ny, nx, periodic) checked: the grid, or false
 bool make_grid(int64_t ny, int64_t nx, int32_t periodic, Grid *g)
@@ -403,11 +370,7 @@ __global__ __launch_bounds__(kBlock) void setup(
     }
 }
 
-__device__ inline bool in_box(const double *__restrict__ b, const Vec3 &q)
-{
-    return q.x >= b[0] && q.x <= b[3] && q.y >= b[1] && q.y <= b[4] &&
-           q.z >= b[2] && q.z <= b[5];
-}
+// (in_box, push_children: remap_tree.h)
 
 // one lane per point
 __global__ __launch_bounds__(kWalkBlock) void quad_walk(
@@ -453,14 +416,7 @@ __global__ __launch_bounds__(kWalkBlock) void quad_walk(
             }
             continue;
         }
-        const int64_t n_below = T.count[l - 1];
-        const double *below = boxes + T.first[l - 1] * 6;
-        const int64_t c0 = k * kFan;
-        const uint32_t tag = static_cast<uint32_t>(l - 1) << kNodeBits;
-#pragma unroll
-        for (int c = kFan - 1; c >= 0; --c)
-            if (c0 + c < n_below && in_box(below + (c0 + c) * 6, q))
-                stack[top++][lane] = tag | static_cast<uint32_t>(c0 + c);
+        push_children(T, boxes, l, k, q, stack, lane, top);
     }
     double S0 = 0.0, S1 = 0.0, S2 = 0.0, S3 = 0.0;
     int32_t out = -1;
@@ -498,55 +454,36 @@ int check_args(const char *what, int64_t ny, int64_t nx, int32_t periodic,
     return REMAP_OK;
 }
 
+// a leaf holds its quads' four bilinear coefficients
+constexpr size_t kPayload = 96;
+
 // the three phases; ev (NULL, or 4 events) is recorded around them
-int run(const Layout &lay, const Grid &G, const double *nodes,
+int run(const TreeLayout &lay, const Grid &G, const double *nodes,
         const double *points, int64_t n_pts, double tol, int32_t *found_out,
         double *weights_out, void *workspace, hipStream_t stream,
         hipEvent_t *ev)
 {
-    char *ws = static_cast<char *>(workspace);
-    uint64_t *keys_in = reinterpret_cast<uint64_t *>(ws + lay.keys_in);
-    uint64_t *keys_out = reinterpret_cast<uint64_t *>(ws + lay.keys_out);
-    uint32_t *idx_in = reinterpret_cast<uint32_t *>(ws + lay.idx_in);
-    uint32_t *idx_out = reinterpret_cast<uint32_t *>(ws + lay.idx_out);
-    double *coef = reinterpret_cast<double *>(ws + lay.coef);
-    double *boxes = reinterpret_cast<double *>(ws + lay.boxes);
+    const TreeArrays A = tree_arrays(lay, workspace);
     const Tree &T = lay.tree;
     const int64_t n = G.n_quads;
-
-    if (ev)
-        REMAP_HIP_CHECK(hipEventRecord(ev[0], stream));
-    hipLaunchKernelGGL(centre_keys, dim3(blocks(n, kBlock)), dim3(kBlock), 0,
-                       stream, G, nodes, keys_in, idx_in);
-    REMAP_HIP_CHECK(hipGetLastError());
-    size_t tb = lay.temp_bytes;
-    REMAP_HIP_CHECK((rocprim::radix_sort_pairs(
-        ws + lay.temp, tb, static_cast<const uint64_t *>(keys_in), keys_out,
-        static_cast<const uint32_t *>(idx_in), idx_out,
-        static_cast<size_t>(n), 0u, 63u, stream)));
-    if (ev)
-        REMAP_HIP_CHECK(hipEventRecord(ev[1], stream));
-    hipLaunchKernelGGL(setup, dim3(blocks(n, kBlock)), dim3(kBlock), 0,
-                       stream, G, nodes, idx_out, tol, coef, boxes);
-    REMAP_HIP_CHECK(hipGetLastError());
-    for (int l = 1; l < T.levels; ++l) {
-        hipLaunchKernelGGL(upper_boxes, dim3(blocks(T.count[l], kBlock)),
-                           dim3(kBlock), 0, stream, T.count[l],
-                           T.count[l - 1], boxes + T.first[l - 1] * 6,
-                           boxes + T.first[l] * 6);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
-    if (ev)
-        REMAP_HIP_CHECK(hipEventRecord(ev[2], stream));
+    REMAP_TRY(build_tree(
+        lay, A, n, workspace, stream, ev,
+        [&] {
+            return launch(centre_keys, n, kBlock, stream, G, nodes, A.keys_in,
+                          A.idx_in);
+        },
+        nothing_sorted,
+        [&] {
+            return launch(setup, n, kBlock, stream, G, nodes, A.orig, tol,
+                          A.payload, A.boxes);
+        }));
     const size_t lds = size_t(stack_depth(T.levels)) * kWalkBlock * 4;
-    for (int64_t at = 0; at < n_pts; at += kWalkChunk) {
-        const int64_t m = n_pts - at < kWalkChunk ? n_pts - at : kWalkChunk;
-        const dim3 grid(blocks(m, kWalkBlock)), block(kWalkBlock);
-        hipLaunchKernelGGL(quad_walk, grid, block, lds, stream, T, G, coef,
-                           idx_out, boxes, nodes, m, points + 3 * at, tol,
-                           found_out + at, weights_out + 4 * at);
-        REMAP_HIP_CHECK(hipGetLastError());
-    }
+    REMAP_TRY(walk_chunks(n_pts, [&](int64_t at, int64_t m) {
+        return launch_blocks(quad_walk, blocks(m, kWalkBlock), kWalkBlock,
+                             lds, stream, T, G, A.payload, A.orig, A.boxes,
+                             nodes, m, points + 3 * at, tol, found_out + at,
+                             weights_out + 4 * at);
+    }));
     if (ev)
         REMAP_HIP_CHECK(hipEventRecord(ev[3], stream));
     return REMAP_OK;
@@ -560,13 +497,10 @@ int quads_workspace(int64_t ny, int64_t nx, int32_t periodic, int64_t n_pts,
     if (!bytes_out)
         return fail(REMAP_ERR_ARG, "remap_quads_workspace: NULL output");
     Grid G;
-    int rc = check_args("remap_quads_workspace", ny, nx, periodic, n_pts, &G);
-    if (rc != REMAP_OK)
-        return rc;
-    Layout lay;
-    rc = make_layout(G.n_quads, &lay);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(check_args("remap_quads_workspace", ny, nx, periodic, n_pts,
+                         &G));
+    TreeLayout lay;
+    REMAP_TRY(make_tree_layout(G.n_quads, kPayload, &lay));
     *bytes_out = lay.total;
     return REMAP_OK;
 }
@@ -577,46 +511,25 @@ int quads(const double *nodes, int64_t ny, int64_t nx, int32_t periodic,
           hipStream_t stream, float *phase_ms)
 {
     Grid G;
-    int rc = check_args("remap_quads", ny, nx, periodic, n_pts, &G);
-    if (rc != REMAP_OK)
-        return rc;
+    REMAP_TRY(check_args("remap_quads", ny, nx, periodic, n_pts, &G));
     if (!(tol >= 0.0))
         return fail(REMAP_ERR_ARG, "remap_quads: tol %g (>= 0)", tol);
     if (!nodes || (n_pts > 0 && (!points || !found_out || !weights_out)))
         return fail(REMAP_ERR_ARG, "remap_quads: NULL array");
-    Layout lay;
-    rc = make_layout(G.n_quads, &lay);
-    if (rc != REMAP_OK)
-        return rc;
-    if (!workspace || workspace_bytes < lay.total)
-        return fail(REMAP_ERR_WORKSPACE,
-                    "remap_quads: workspace of %zu bytes, need %zu",
-                    workspace_bytes, lay.total);
+    TreeLayout lay;
+    REMAP_TRY(make_tree_layout(G.n_quads, kPayload, &lay));
+    REMAP_TRY(need_workspace("remap_quads", workspace, workspace_bytes,
+                             lay.total));
     if (!phase_ms) {
         if (n_pts == 0)
             return REMAP_OK;
         return run(lay, G, nodes, points, n_pts, tol, found_out, weights_out,
                    workspace, stream, nullptr);
     }
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipError_t err = hipSuccess;
-    for (int k = 0; k < 4 && err == hipSuccess; ++k)
-        err = hipEventCreate(&ev[k]);
-    if (err == hipSuccess) {
-        rc = run(lay, G, nodes, points, n_pts, tol, found_out, weights_out,
-                 workspace, stream, ev);
-        if (rc == REMAP_OK)
-            err = hipEventSynchronize(ev[3]);
-        for (int k = 0; k < 3 && rc == REMAP_OK && err == hipSuccess; ++k)
-            err = hipEventElapsedTime(&phase_ms[k], ev[k], ev[k + 1]);
-    }
-    for (int k = 0; k < 4; ++k)
-        if (ev[k])
-            (void)hipEventDestroy(ev[k]);
-    if (rc != REMAP_OK)
-        return rc;
-    REMAP_HIP_CHECK(err);
-    return REMAP_OK;
+    return timed_phases<4>(phase_ms, [&](hipEvent_t *ev) {
+        return run(lay, G, nodes, points, n_pts, tol, found_out, weights_out,
+                   workspace, stream, ev);
+    });
 }
 
 }  // namespace remap

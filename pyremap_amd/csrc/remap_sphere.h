@@ -1,6 +1,7 @@
 // Points and triangles on the unit sphere: the device functions the overlap
 // kernels (remap_overlap.hip) and the cell areas (remap_geometry.hip) share,
-// so that one cell's area has the same bits wherever it is computed.
+// so that one cell's area has the same bits wherever it is computed, and the
+// vector type of the point locations (remap_locate.hip, remap_quads.hip).
 #ifndef REMAP_SPHERE_H
 #define REMAP_SPHERE_H
 
@@ -16,12 +17,24 @@ struct V3 {
     double x, y, z;
 };
 
+// point i of an array of xyz triples
+__device__ inline V3 load3(const double *__restrict__ p, int64_t i)
+{
+    return V3{p[3 * i], p[3 * i + 1], p[3 * i + 2]};
+}
+
 __device__ inline V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 __device__ inline double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 __device__ inline V3 cross(V3 a, V3 b)
 {
     return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z,
             a.x * b.y - a.y * b.x};
+}
+// the squared length of the chord from u to v
+__device__ inline double edge2(V3 u, V3 v)
+{
+    const double dx = u.x - v.x, dy = u.y - v.y, dz = u.z - v.z;
+    return (dx * dx + dy * dy) + dz * dz;
 }
 __device__ inline V3 normalized(V3 a)
 {

@@ -1,7 +1,11 @@
-// The Morton-sorted box tree remap_nearest.hip and remap_locate.hip walk: the
-// shape of its levels, the 63-bit key its leaves are sorted by, and the
-// kernel that makes a level's boxes from the level below.  What a leaf holds
-// (points, triangles) and how its box is made is the including file's.
+// The Morton-sorted box tree remap_nearest.hip, remap_locate.hip and
+// remap_quads.hip walk: the shape of its levels, the 63-bit key its leaves are
+// sorted by, its place in a workspace (TreeLayout), the build from the
+// including file's own key and leaf kernels (build_tree), the chunked launch
+// of a walk (walk_chunks) and, on the device, the kernel that makes a level's
+// boxes from the level below and the descent of a walk that looks for the
+// boxes holding a point (in_box, push_children).  What a leaf holds (points,
+// triangles, quads) and how its box is made is the including file's.
 #ifndef REMAP_TREE_H
 #define REMAP_TREE_H
 
@@ -11,11 +15,11 @@
 #include <cstdint>
 
 #include "remap_common.h"
+#include "remap_host.h"
 
 namespace remap {
 namespace {
 
-constexpr size_t kAlign = 256;
 constexpr int kLeaf = 8;       // sorted items a leaf
 constexpr int kFan = 4;        // nodes below a node
 // n <= 2^31 - 1 items: 2^28 leaves, a quarter as many nodes a level above
@@ -23,13 +27,12 @@ constexpr int kMaxLevels = 15;
 // a node on a walk's stack: its level above kNodeBits, its index below
 constexpr uint32_t kNodeBits = 28;
 constexpr uint32_t kNodeMask = (1u << kNodeBits) - 1u;
-
-size_t align_up(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
-
-uint32_t blocks(int64_t n, int per)
-{
-    return static_cast<uint32_t>((n + per - 1) / per);
-}
+// the bits of a Morton key: what the sort of the leaves looks at
+constexpr unsigned kKeyBits = 63;
+// a walk: one lane per point in blocks of kWalkBlock, at most kWalkChunk
+// points a launch (its block count stays far below the grid limit)
+constexpr int kWalkBlock = 64;
+constexpr int64_t kWalkChunk = int64_t(1) << 30;
 
 // level l holds count[l] nodes, its boxes (6 doubles each: lo, then hi, an
 // axis) from node first[l]
@@ -112,6 +115,119 @@ __global__ __launch_bounds__(kBlock) void upper_boxes(
 #pragma unroll
     for (int a = 0; a < 6; ++a)
         o[a] = b[a];
+}
+
+// whether the box b holds the point q (a struct of x, y, z)
+template <class Point>
+__device__ inline bool in_box(const double *__restrict__ b, const Point &q)
+{
+    return q.x >= b[0] && q.x <= b[3] && q.y >= b[1] && q.y <= b[4] &&
+           q.z >= b[2] && q.z <= b[5];
+}
+
+// a walk for the boxes that hold q, at node k of level l >= 1: its children
+// whose box holds q go onto the lane's stack (LDS, [entry][lane]), the last
+// first
+template <class Point>
+__device__ inline void push_children(
+    const Tree &T, const double *__restrict__ boxes, int l, int64_t k,
+    const Point &q, uint32_t (*stack)[kWalkBlock], int lane, int &top)
+{
+    const int64_t n_below = T.count[l - 1];
+    const double *below = boxes + T.first[l - 1] * 6;
+    const int64_t c0 = k * kFan;
+    const uint32_t tag = static_cast<uint32_t>(l - 1) << kNodeBits;
+#pragma unroll
+    for (int c = kFan - 1; c >= 0; --c)
+        if (c0 + c < n_below && in_box(below + (c0 + c) * 6, q))
+            stack[top++][lane] = tag | static_cast<uint32_t>(c0 + c);
+}
+
+// the tree over n items in a workspace: the keys and indices on both sides
+// of the sort, what the leaves hold (payload, so many bytes an item, in
+// sorted order), the boxes of every level, rocPRIM's scratch
+struct TreeLayout {
+    Tree tree;
+    size_t keys_in, keys_out, idx_in, idx_out, payload, boxes, temp, total;
+    size_t temp_bytes;
+};
+
+int make_tree_layout(int64_t n_items, size_t payload_bytes_per_item,
+                     TreeLayout *lay)
+{
+    const size_t n = static_cast<size_t>(n_items);
+    const int64_t nodes = make_tree(n_items, &lay->tree);
+    REMAP_TRY(sort_pairs_temp<uint32_t>(n, &lay->temp_bytes, kKeyBits));
+    size_t off = 0;
+    lay->keys_in = take(&off, n * 8);
+    lay->keys_out = take(&off, n * 8);
+    lay->idx_in = take(&off, n * 4);
+    lay->idx_out = take(&off, n * 4);
+    lay->payload = take(&off, n * payload_bytes_per_item);
+    lay->boxes = take(&off, static_cast<size_t>(nodes) * 48);
+    lay->temp = take(&off, lay->temp_bytes);
+    lay->total = off;
+    return REMAP_OK;
+}
+
+// the arrays of a TreeLayout in a workspace; a walk reads orig (the sorted
+// items' original indices), payload and boxes once build_tree() has run
+struct TreeArrays {
+    uint64_t *keys_in, *keys_out;
+    uint32_t *idx_in, *orig;
+    double *payload, *boxes;
+};
+
+TreeArrays tree_arrays(const TreeLayout &lay, void *workspace)
+{
+    char *ws = static_cast<char *>(workspace);
+    return {at<uint64_t>(ws, lay.keys_in), at<uint64_t>(ws, lay.keys_out),
+            at<uint32_t>(ws, lay.idx_in), at<uint32_t>(ws, lay.idx_out),
+            at<double>(ws, lay.payload), at<double>(ws, lay.boxes)};
+}
+
+// the two phases before a walk.  Sort: keys() fills A.keys_in and A.idx_in
+// for the n items, the pairs are sorted, sorted() runs what the file still
+// counts to the sort (or nothing).  Boxes: leaves() writes level 0 of
+// A.boxes (and the payload), upper_boxes the levels above.  ev (NULL, or at
+// least 3 events) is recorded around the phases
+template <class Keys, class Sorted, class Leaves>
+int build_tree(const TreeLayout &lay, const TreeArrays &A, int64_t n,
+               void *workspace, hipStream_t stream, hipEvent_t *ev, Keys keys,
+               Sorted sorted, Leaves leaves)
+{
+    const Tree &T = lay.tree;
+    if (ev)
+        REMAP_HIP_CHECK(hipEventRecord(ev[0], stream));
+    REMAP_TRY(keys());
+    REMAP_TRY(radix_sort_pairs(static_cast<char *>(workspace) + lay.temp,
+                               lay.temp_bytes, A.keys_in, A.keys_out,
+                               A.idx_in, A.orig, n, stream, kKeyBits));
+    REMAP_TRY(sorted());
+    if (ev)
+        REMAP_HIP_CHECK(hipEventRecord(ev[1], stream));
+    REMAP_TRY(leaves());
+    for (int l = 1; l < T.levels; ++l)
+        REMAP_TRY(launch(upper_boxes, T.count[l], kBlock, stream, T.count[l],
+                         T.count[l - 1], A.boxes + T.first[l - 1] * 6,
+                         A.boxes + T.first[l] * 6));
+    if (ev)
+        REMAP_HIP_CHECK(hipEventRecord(ev[2], stream));
+    return REMAP_OK;
+}
+
+// nothing between the sort and the leaves
+inline int nothing_sorted() { return REMAP_OK; }
+
+// a walk over n_pts points: walk(at, m) launches points [at, at + m)
+template <class Walk>
+int walk_chunks(int64_t n_pts, Walk walk)
+{
+    for (int64_t at = 0; at < n_pts; at += kWalkChunk) {
+        const int64_t m = n_pts - at < kWalkChunk ? n_pts - at : kWalkChunk;
+        REMAP_TRY(walk(at, m));
+    }
+    return REMAP_OK;
 }
 
 }  // namespace
