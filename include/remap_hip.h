@@ -88,7 +88,36 @@ enum {
      * from NaN in X (as _remap_data_array builds it, :201-204):
      * num = A.(X, NaN->+0), den = A.(!isnan X); Y = den > threshold ?
      * num / den : NaN. */
-    REMAP_MODE_MASKED = 2
+    REMAP_MODE_MASKED = 2,
+    /* largest area fraction (CDO's remaplaf), for fields whose values are
+     * labels -- region ids, land-cover classes, 0/1/2 flags: no num at all,
+     * every destination element takes the source value whose weights in its
+     * row add up to the most.  (An added enumerator of ABI 31: no existing
+     * caller changes, the version stays.)  For destination element (i, b, k)
+     * the entries j of row i are walked in CSR order, which is ascending
+     * source cell:
+     *   x = (double) X[cell(col_j), b, k]
+     *   a NaN x is skipped; +-inf are values like any other
+     *   the entry's class is the first earlier counted value of the row with
+     *   value == x (so -0.0 and +0.0 are one class, and the class keeps the
+     *   bits of its first member); no such value: a new class, w_c = +0.0
+     *   w_c = w_c + S_j;   valid = valid + S_j
+     *   (valid starts at +0.0; every sum rounded, in CSR order)
+     *   winner: the classes in order of first appearance; the first one sets
+     *   best; a later one replaces it iff w_c > best
+     *   (strict: the first seen wins a tie; a NaN sum never replaces)
+     *   y = (a class exists && valid > threshold) ? the winner's value : NaN
+     * Every NaN written is 0x7ff8000000000000; mask_out, where given, gets 1
+     * where NaN was written and 0 elsewhere.  Nothing is multiplied or
+     * divided: REMAP_FLAG_FMA, REMAP_FLAG_TREE and the mask hints have no
+     * meaning and are ignored, and so are frac_b, tune, row_order and every
+     * attached schedule (patch plan, row groups, share lists, strips): the
+     * mode picks its own launch (csrc/apply_laf.h).  gate / gate_value are
+     * honoured, rows outside [row_begin, row_end) are not written, x_dtype
+     * F64 and F32 are served (float32 widens exactly), x_src_fold and every
+     * stride are addressed as in the other modes.  Signed weights
+     * (conserve2nd, patch, a file) are legal: the sums are what they are. */
+    REMAP_MODE_LAF = 3
 };
 
 enum {
@@ -242,7 +271,7 @@ typedef struct remap_apply_args {
     int64_t n_batch;
     int64_t k_inner;
     const double *frac_b;   /* (device) n_rows; REMAP_MODE_FRACB only        */
-    double threshold;       /* REMAP_MODE_MASKED only                        */
+    double threshold;       /* REMAP_MODE_MASKED and REMAP_MODE_LAF          */
     uint8_t *mask_out;      /* (device) optional, addressed like Y; 1 where
                                the reference's result is masked (~ok)        */
     const int32_t *row_order; /* (device) optional processing order: entry s
@@ -676,7 +705,9 @@ typedef struct remap_plan_info {
 typedef struct remap_field {
     const void *X;               /* (device) source field                    */
     int32_t x_dtype;             /* REMAP_DTYPE_*                            */
-    int32_t mode;                /* REMAP_MODE_*                             */
+    int32_t mode;                /* REMAP_MODE_* (REMAP_MODE_LAF walks ONE
+                                  * CSR: REMAP_ERR_UNSUPPORTED on a plan that
+                                  * keeps its long rows apart)               */
     int64_t n_batch;
     int64_t k_inner;
     int64_t x_row_stride;        /* elements                                 */
@@ -684,7 +715,7 @@ typedef struct remap_field {
     double *Y;                   /* (device) float64 result                  */
     int64_t y_row_stride;
     int64_t y_batch_stride;
-    double threshold;            /* REMAP_MODE_MASKED                        */
+    double threshold;            /* REMAP_MODE_MASKED, REMAP_MODE_LAF        */
     uint8_t *mask_out;           /* (device) or NULL                         */
     const int32_t *gate;         /* (device) or NULL: see remap_apply_args   */
     int32_t gate_value;

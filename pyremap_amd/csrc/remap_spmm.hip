@@ -42,6 +42,7 @@
 #include <utility>
 
 #include "remap_common.h"
+#include "apply_laf.h"
 
 namespace remap {
 
@@ -571,9 +572,11 @@ int check_args(const remap_apply_args *a, Call &c)
     if (a->x_dtype != REMAP_DTYPE_F64 && a->x_dtype != REMAP_DTYPE_F32)
         return fail(REMAP_ERR_ARG, "remap_apply_f64: unknown x_dtype %d",
                     a->x_dtype);
-    if (a->mode < REMAP_MODE_RAW || a->mode > REMAP_MODE_MASKED)
+    if (a->mode < REMAP_MODE_RAW || a->mode > REMAP_MODE_LAF)
         return fail(REMAP_ERR_ARG, "remap_apply_f64: unknown mode %d",
                     a->mode);
+    if (a->mode == REMAP_MODE_LAF)
+        return REMAP_OK;  // (tune, flags and schedules are not looked at)
     if (a->mode == REMAP_MODE_FRACB && !a->frac_b)
         return fail(REMAP_ERR_ARG,
                     "remap_apply_f64: REMAP_MODE_FRACB needs frac_b");
@@ -1576,6 +1579,9 @@ int apply(const remap_apply_args *a, hipStream_t stream)
     const int rc = check_args(a, c);
     if (rc != REMAP_OK || c.K == 0)
         return rc;
+    // largest area fraction picks its own launch (apply_laf.h)
+    if (a->mode == REMAP_MODE_LAF)
+        return laf::apply(a, stream);
     // a preferred family that cannot serve this call gives way to the
     // automatic choice instead of failing
     remap_apply_args relaxed;

@@ -33,6 +33,7 @@ from pyremap_amd._abi import (  # noqa: F401  (tests and tools read them here)
 MODE_RAW = 0
 MODE_FRACB = 1
 MODE_MASKED = 2
+MODE_LAF = 3           # largest area fraction, for labels (pyremap_amd.laf)
 
 FLAG_FMA = 1
 FLAG_TUNE_HINT = 4
@@ -1333,9 +1334,15 @@ def apply_strided(plan, X, Y, *, n_batch, k_inner, x_row_stride,
     (:meth:`RemapPlan.cell_patches`: allocations and one readback): make it
     -- or call ``plan.cell_patches()`` -- before capturing launches in a
     hipGraph.
+
+    ``mode=MODE_LAF`` (largest area fraction, :mod:`pyremap_amd.laf`) is a
+    row pass over the plan's own CSR: ``flags``, ``tune`` and every schedule
+    are ignored, nothing is built, one device only.
     """
     torch = _torch()
     lib = load_library()
+    if mode == MODE_LAF:
+        _one_device(plan, 'largest area fraction')
     if X.device != plan.device or Y.device != plan.device:
         raise ValueError('X, Y and the plan must live on the same device')
     if Y.dtype != torch.float64:
@@ -1350,6 +1357,34 @@ def apply_strided(plan, X, Y, *, n_batch, k_inner, x_row_stride,
                                  mask_out.device != plan.device):
         raise TypeError('mask_out must be a uint8 tensor on the plan device')
     end = plan.n_b if row_end is None else row_end
+    if mode == MODE_LAF:
+        # a row pass over the plan's own CSR (csrc/apply_laf.h): no schedule,
+        # no tune, no split into short and long rows; flags mean nothing
+        row_begin, end = _row_range(plan, row_begin, row_end)
+        _holds_csr(plan, ('rowptr', 'col', 'val'),
+                   "largest area fraction adds a row's weights from it")
+        args = _ApplyArgs()
+        args.A = plan._csr_struct()
+        args.row_begin, args.row_end = row_begin, end
+        args.X, args.x_dtype, args.mode = X.data_ptr(), x_dtype, mode
+        args.x_row_stride = int(x_row_stride)
+        args.x_batch_stride = int(x_batch_stride)
+        args.Y = Y.data_ptr()
+        args.y_row_stride = int(y_row_stride)
+        args.y_batch_stride = int(y_batch_stride)
+        args.n_batch, args.k_inner = int(n_batch), int(k_inner)
+        args.threshold = float(threshold)
+        args.mask_out = mask_out.data_ptr() if mask_out is not None else None
+        if gate is not None:
+            if gate.dtype != torch.int32 or gate.device != plan.device:
+                raise TypeError('gate must be an int32 tensor on the plan '
+                                'device')
+            args.gate = gate.data_ptr()
+            args.gate_value = int(gate_value)
+        args.x_src_fold = int(x_src_fold)
+        args.x_outer_stride = int(x_outer_stride)
+        _launch(torch, plan, lib.remap_apply_f64, 'remap_apply_f64', args)
+        return
     whole = row_begin == 0 and end == plan.n_b
     if plan._split is not None and whole and not tune:
         # a few long rows hold a large share of the entries (pole caps of a
@@ -2069,6 +2104,11 @@ def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
     dimension is replaced by the shard's row count (the result is the flat
     slab of rows ``[plan.row_offset, plan.row_offset + plan.n_b)``).
 
+    ``mode=MODE_LAF``: largest area fraction for labels
+    (:mod:`pyremap_amd.laf`) -- float64 too, same layout, NaN where no class
+    exists or ``valid <= threshold``; one device, never limited; ``flags``
+    and ``tune`` are ignored.
+
     ``limiter`` (``None | 'clip' | 'caas'``; :mod:`pyremap_amd.limiter`):
     after the apply, on the same stream, every value is clamped to the bounds
     of the source values of its row's entries (``remap_limit_rows``; whatever
@@ -2086,6 +2126,12 @@ def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
     if limiter is not None and gate is not None:
         raise ValueError('a gated launch is not limited: run the limiter '
                          'behind the gated launches')
+    if mode == MODE_LAF:
+        # labels: every value is a source value of its own row already
+        if limiter is not None:
+            raise ValueError('largest area fraction is not limited: its '
+                             'values are source values of their own rows')
+        _one_device(plan, 'largest area fraction')
     if hasattr(plan, 'shards'):
         # a parallel.MultiDeviceRemap standing where the plan stands
         # (Remapper(..., devices=[...])): rows sharded over several GPUs

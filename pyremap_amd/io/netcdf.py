@@ -241,8 +241,11 @@ def write_netcdf(ds, filename, format='NETCDF3_64BIT', fillvalues=None,
     out_vars = []
     for name in names:
         var = ds.variables[name]
+        # (an integer variable's own _FillValue stays: its values hold it
+        # already -- a categorical variable's masked cells)
         attrs = OrderedDict((k, v) for k, v in var.attrs.items()
-                            if k != '_FillValue')
+                            if k != '_FillValue' or
+                            np.dtype(var.dtype).kind in 'iu')
         if getattr(var, 'is_lazy', False) and var._data.dtype.kind == 'f':
             # values produced when the writer reaches the variable: whether
             # they hold NaNs -- hence whether the variable gets a _FillValue

@@ -178,6 +178,10 @@ _ALONE = {
     'vector_pairs': ('a vector remap', 'the vector remap', (
         ('limiter', ': the bounds of a component are no bounds of the '
                     'rotated vector'), ('sgs_frac', ''))),
+    # (a limiter goes with it: the listed variables skip it)
+    'categorical': ('categorical', 'categorical', (
+        ('sgs_frac', ''), ('vector_pairs', ''), ('levels', ''),
+        ('layers', ''))),
 }
 
 
@@ -199,6 +203,135 @@ def _check_alone(remapper, switch):
         raise NotImplementedError(
             f'{serves} serves one device: not with devices=[...] or a '
             f'process group')
+
+
+#: netCDF's default fill values of the integer types
+NC_FILL = {'i1': -127, 'u1': 255, 'i2': -32767, 'u2': 65535,
+           'i4': -2147483647, 'u4': 4294967295,
+           'i8': -9223372036854775806, 'u8': 18446744073709551614}
+#: integers beyond +-2^53 are no float64: a label would come out as another
+_EXACT = 2 ** 53
+
+
+def _check_categorical(remapper):
+    """The Remapper's ``categorical`` (None or a list / tuple of variable
+    names) as a tuple of names or None, and what it does not go together
+    with."""
+    names = getattr(remapper, 'categorical', None)
+    if names is None:
+        return None
+    if not isinstance(names, (list, tuple)) or \
+            not all(isinstance(name, str) for name in names):
+        raise TypeError(f'categorical must be None or a list of variable '
+                        f'names, not {names!r}')
+    _check_alone(remapper, 'categorical')
+    return tuple(names)
+
+
+def _categorical(remapper, ds):
+    """None without ``Remapper.categorical``; else the names of the variables
+    of ``ds`` that are remapped by largest area fraction (``KeyError`` naming
+    the first one ``ds`` does not hold)."""
+    names = _check_categorical(remapper)
+    if names is None:
+        return None
+    held = ds.variables if _is_dataset(ds) else (getattr(ds, 'name', None),)
+    for name in names:
+        if name not in held:
+            raise KeyError(
+                f'categorical names the variable {name!r}, which is not in '
+                f'the Dataset')
+    return frozenset(names)
+
+
+def _check_label_field(field):
+    """An integer field of labels must fit float64 exactly (``ValueError``);
+    no device is needed to be told so."""
+    if isinstance(field, np.ma.MaskedArray):
+        field = field.compressed()
+    dtype = str(getattr(field, 'dtype', '')).replace('torch.', '')
+    if dtype not in ('int64', 'uint64') or not field.shape or \
+            not min(field.shape):
+        return
+    low, high = int(field.min()), int(field.max())
+    if low < -_EXACT or high > _EXACT:
+        raise ValueError(
+            f'a categorical field of dtype {dtype} with values in [{low}, '
+            f'{high}]: labels beyond +-2^53 are not exact in float64')
+
+
+def _label_output(da):
+    """``(dtype, fill)`` of a categorical variable's result: None, None for a
+    float variable (NaN where masked, as every other variable); an integer
+    variable keeps its dtype, and its masked cells get its ``_FillValue`` if
+    it has one, else netCDF's default fill value of that type.  A variable
+    read from a file whose integers came up as floats because of their
+    ``_FillValue`` goes back to the integer type of that attribute.  bool:
+    int8 (netCDF has no bool)."""
+    dtype = np.dtype(da.dtype)
+    encoding = getattr(getattr(da, 'variable', da), 'encoding', None) or {}
+    fill = da.attrs.get('_FillValue', encoding.get('_FillValue'))
+    if dtype.kind == 'f':
+        packed = any(k in encoding for k in ('scale_factor', 'add_offset'))
+        if fill is None or packed or np.asarray(fill).dtype.kind not in 'iu':
+            return None, None
+        dtype = np.asarray(fill).dtype
+    elif dtype.kind == 'b':
+        dtype = np.dtype(np.int8)
+    elif dtype.kind not in 'iu':
+        raise TypeError(f'the categorical variable {da.name!r} has dtype '
+                        f'{dtype}: expected a float, integer or bool type')
+    if fill is None:
+        fill = NC_FILL[f'{dtype.kind}{dtype.itemsize}']
+    return dtype, dtype.type(np.asarray(fill).reshape(-1)[0])
+
+
+def _label_values(values, fill):
+    """The values of a categorical variable as the launch takes them: floats
+    as they are; integers and bools as float64 with NaN where they equal
+    ``fill`` (the variable's own ``_FillValue``, or None)."""
+    values = np.asarray(values)
+    if values.dtype.kind == 'f':
+        return host_path._as_uploadable(values)
+    hit = None if fill is None else values == fill
+    _check_label_field(values if hit is None else
+                       np.ma.masked_array(values, mask=hit))
+    out = values.astype(np.float64)
+    if hit is not None:
+        out[hit] = np.nan
+    return out
+
+
+def _start_categorical(da, remapper, remap_axes, threshold):
+    """Enqueue the remap of one categorical variable -- upload,
+    ``engine.remap_tensor`` in ``MODE_LAF``, no limiter -- and return
+    ``(finish, attrs)``: the function that downloads the values in the
+    variable's own type, and its attributes (``_FillValue`` among them for an
+    integer type)."""
+    torch = engine.require_gpu()
+    matrix = remapper._matrix
+    dtype, fill = _label_output(da)
+    attrs = type(da.attrs)(da.attrs)
+    own = da.attrs.get('_FillValue') if np.dtype(da.dtype).kind in 'iu' \
+        else None
+    values = _label_values(da.values, own)
+    y_d = engine.remap_tensor(
+        matrix, remapper._ds_map.dst_grid_dims,
+        torch.from_numpy(values).to(matrix.device), remap_axes,
+        engine.MODE_LAF, threshold=0.0 if threshold is None else threshold)
+    # (the download waits until the result is asked for)
+    pending = host_path.OnDevice(y_d, tuple(y_d.shape))
+    if dtype is None:
+        return pending.result, attrs
+    attrs['_FillValue'] = fill
+
+    def finish():
+        data = pending.result()
+        masked = np.isnan(data)
+        out = np.where(masked, 0.0, data).astype(dtype)
+        out[masked] = fill
+        return out
+    return finish, attrs
 
 
 class _SgsFraction:
@@ -612,6 +745,7 @@ def _remap_numpy(remapper, ds, renormalization_threshold):
         raise ValueError('No mapping file has been defined')
     # (before anything is loaded: a refusal or a missing fraction variable
     # costs nothing)
+    cat = _categorical(remapper, ds)
     lay = _layer_thickness(remapper, ds)
     lev = _level_coordinate(remapper, ds)
     if lay is not None:
@@ -632,9 +766,9 @@ def _remap_numpy(remapper, ds, renormalization_threshold):
                 f"data set and remapping source dimension {dim} don't "
                 f'have the same size: {size} != {ds.sizes[dim]}')
 
-    args = (remapper, renormalization_threshold)
     if _is_data_array(ds):
-        result = _remap_data_array(ds, *args)
+        result = _start_data_array(ds, remapper, renormalization_threshold,
+                                   cat=cat)()
     elif _is_dataset(ds):
         # variables holding only part of the source dims cannot be remapped
         partial = [name for name in ds.data_vars
@@ -646,13 +780,21 @@ def _remap_numpy(remapper, ds, renormalization_threshold):
             # is lazy too -- each variable is read, remapped and handed to the
             # writer in turn, never all of them at once
             result = _lazy_dataset(remapper, kept, renormalization_threshold,
-                                   sgs=sgs, vec=vec, lev=lev)
+                                   sgs=sgs, vec=vec, lev=lev, cat=cat)
         else:
             result = kept.map(
                 _LookAhead(remapper, kept, list(kept.data_vars),
                            renormalization_threshold, sgs=sgs, vec=vec,
-                           lev=lev),
+                           lev=lev, cat=cat),
                 keep_attrs=True)
+        for name in cat or ():
+            # (Dataset.map hands the input's attributes on: the fill value
+            # of an integer result is added behind it)
+            if name in kept.data_vars and \
+                    _plan_data_array(kept[name], remapper) is not None:
+                fill = _label_output(kept[name])[1]
+                if fill is not None:
+                    result[name].attrs['_FillValue'] = fill
         if lay is not None:
             name, bnds = lay.bounds_variable()
             result[name] = bnds
@@ -839,7 +981,7 @@ def _plan_data_array(da, remapper, lev=None):
 
 
 def _lazy_dataset(remapper, ds, renormalization_threshold, sgs=None,
-                  vec=None, lev=None):
+                  vec=None, lev=None, cat=None):
     """
     ``ds.map(_remap_data_array, keep_attrs=True)`` for a Dataset whose
     variables are (partly) still on disk: same variables, dims, coordinates
@@ -871,10 +1013,13 @@ def _lazy_dataset(remapper, ds, renormalization_threshold, sgs=None,
                 finish = _start_data_array(da, remapper,
                                            renormalization_threshold,
                                            keep_on_device=True, sgs=sgs,
-                                           vec=vec, lev=lev)
+                                           vec=vec, lev=lev, cat=cat)
                 return lambda: finish().values
+            # (a categorical integer variable keeps its type)
+            label_dtype, label_fill = _label_output(da) \
+                if cat is not None and name in cat else (None, None)
             out = xr_lite.DataArray(
-                xr_lite.LazyValues(shape, np.float64,
+                xr_lite.LazyValues(shape, label_dtype or np.float64,
                                    load=lambda start=start: start()(),
                                    prefetch=start),
                 coords={k: xr_lite.DataArray(v['data'], dims=v['dims'],
@@ -882,12 +1027,15 @@ def _lazy_dataset(remapper, ds, renormalization_threshold, sgs=None,
                         for k, v in coords.items()},
                 dims=dims, name=name)
         out.attrs = type(out.attrs)(ds.variables[name].attrs)  # keep_attrs
+        if plan is not None and label_dtype is not None:
+            out.attrs['_FillValue'] = label_fill
         results[name] = out
     return xr_lite.Dataset(results, attrs=ds.attrs)
 
 
 def _start_data_array(da, remapper, renormalization_threshold,
-                      keep_on_device=False, sgs=None, vec=None, lev=None):
+                      keep_on_device=False, sgs=None, vec=None, lev=None,
+                      cat=None):
     """
     Enqueue the remap of one variable -- upload, NaN scan, launch, download,
     none of which waits for the host -- and return the function that waits
@@ -901,12 +1049,24 @@ def _start_data_array(da, remapper, renormalization_threshold,
     with its partner, ``engine.remap_tensor_vector``, when the first of the
     two gets here.  ``lev``: the call's :class:`_LevelCoordinate`
     (``Remapper.levels``); a variable it interpolates takes the whole-array
-    route too -- upload, ``engine.remap_tensor_levels``, download.
+    route too -- upload, ``engine.remap_tensor_levels``, download.  ``cat``:
+    the names of the call's categorical variables
+    (``Remapper.categorical``); one of them takes the whole-array route too
+    -- upload, ``engine.remap_tensor`` by largest area fraction, download in
+    its own type -- and skips the limiter.
     """
     plan = _plan_data_array(da, remapper, lev)
     if plan is None:
         return lambda: da  # nothing to remap
     remap_axes, dims, coords = plan
+
+    if cat is not None and da.name in cat:
+        values, attrs = _start_categorical(da, remapper, remap_axes,
+                                           renormalization_threshold)
+        make = _array_class(da).from_dict
+        name = da.name
+        return lambda: make({'coords': coords, 'attrs': attrs, 'dims': dims,
+                             'data': values(), 'name': name})
 
     if lev is not None and lev.interpolates(da):
         pending = lev.start(da, remapper, renormalization_threshold)
@@ -1066,16 +1226,18 @@ class _LookAhead:
     """
 
     def __init__(self, remapper, ds, names, threshold, depth=2, sgs=None,
-                 vec=None, lev=None):
+                 vec=None, lev=None, cat=None):
         self.remapper, self.ds, self.names = remapper, ds, list(names)
         self.threshold, self.depth, self.sgs = threshold, depth, sgs
-        self.vec, self.lev = vec, lev
+        self.vec, self.lev, self.cat = vec, lev, cat
         self.started = {}
         self.position = 0
-        # (the members of a vector pair are not stacked with other variables)
+        # (the members of a vector pair and the categorical variables are not
+        # stacked with other variables)
         self.batches = _batches(
             remapper, ds, [name for name in self.names
-                           if vec is None or name not in vec])
+                           if (vec is None or name not in vec) and
+                           (cat is None or name not in cat)])
 
     def _start_up_to(self, last):
         while self.position <= min(last, len(self.names) - 1):
@@ -1090,7 +1252,8 @@ class _LookAhead:
                 else:
                     self.started[name] = _start_data_array(
                         self.ds[name], self.remapper, self.threshold,
-                        sgs=self.sgs, vec=self.vec, lev=self.lev)
+                        sgs=self.sgs, vec=self.vec, lev=self.lev,
+                        cat=self.cat)
             self.position += 1
 
     def __call__(self, da, *unused):
@@ -1206,6 +1369,46 @@ def _remap_array_sgs(remapper, in_field, sgs_frac, remap_axes,
         return out
     out = out.cpu().numpy()
     return np.ma.masked_array(out, mask=np.isnan(out))
+
+
+def _remap_array_laf(remapper, in_field, remap_axes,
+                     renormalization_threshold):
+    """
+    One array of labels through ``engine.remap_tensor`` in ``MODE_LAF``:
+    device tensor in, device tensor out; numpy in, ``numpy.ma.MaskedArray``
+    out with the mask taken from NaN.  Float fields go as they are; integer
+    and bool fields travel as float64 (exact: :func:`_check_label_field`) and
+    come back in their own type, 0 / False under the mask (a device tensor
+    of integers has no other way to say "masked": ask for the float result
+    where that matters).  ``None`` threshold means 0.0.
+    """
+    _check_alone(remapper, 'categorical')
+    _check_label_field(in_field)
+    torch = engine.require_gpu()
+    plan = remapper._matrix
+    threshold = 0.0 if renormalization_threshold is None else \
+        float(renormalization_threshold)
+    remap_axes = [int(a) for a in remap_axes]
+    on_device = isinstance(in_field, torch.Tensor)
+    if on_device:
+        field = in_field.to(plan.device)
+        floating = field.dtype.is_floating_point
+        if not floating:
+            field = field.to(torch.float64)
+    else:
+        floating = np.asarray(in_field).dtype.kind == 'f'
+        field = _host_values(torch, in_field, plan.device)
+    out = engine.remap_tensor(plan, remapper._ds_map.dst_grid_dims, field,
+                              remap_axes, engine.MODE_LAF,
+                              threshold=threshold)
+    if on_device:
+        return out if floating else \
+            torch.nan_to_num(out, nan=0.0).to(in_field.dtype)
+    out = out.cpu().numpy()
+    mask = np.isnan(out)
+    if not floating:
+        out = np.where(mask, 0.0, out).astype(np.asarray(in_field).dtype)
+    return np.ma.masked_array(out, mask=mask)
 
 
 def _check_level_arrays(field, z, targets, level_axis):

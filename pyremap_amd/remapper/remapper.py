@@ -10,12 +10,14 @@ knobs and :meth:`from_triplets` for mapping data that is already in memory.
 """
 from pyremap_amd.remapper.remap_numpy import (
     _check_alone,
+    _check_label_field,
     _check_layer_arrays,
     _check_level_arrays,
     _check_limiter,
     _check_vector_fields,
     _load_mapping,
     _remap_numpy,
+    _remap_array_laf,
     _remap_array_layers,
     _remap_array_levels,
     _remap_array_sgs,
@@ -97,6 +99,18 @@ class Remapper:
         inside the remap (:mod:`pyremap_amd.layers`): the field over a depth
         range, a column that ends above the range skipped as a NaN is;
         :meth:`remap_array_layers` is the array-level entry
+    categorical : None or list of str
+        set after construction (default ``None``: nothing changes): the
+        names of the Dataset variables whose values are labels --
+        ``['regionId', 'landIceMask']``.  ``remap_numpy`` and ``ncremap``
+        then remap exactly those by largest area fraction
+        (:mod:`pyremap_amd.laf`; CDO's ``remaplaf``) from the rows of the
+        same map, with source cells at the variable's own ``_FillValue``
+        counted as missing: only values the input
+        holds come out.  An integer variable keeps its dtype, its masked
+        cells get its ``_FillValue`` (netCDF's default fill value of the
+        type if it has none); the listed variables skip the ``limiter``;
+        :meth:`remap_array_laf` is the array-level entry
     """
 
     def __init__(
@@ -173,6 +187,15 @@ class Remapper:
         #: 'nbnd') that holds the bounds.  The thickness variable itself, and
         #: variables that lack one of its dims, are remapped as without it.
         self.layers = None
+        #: categorical variables (None | a list of names of Dataset
+        #: variables: region ids, masks, classes), honoured by remap_numpy
+        #: and ncremap: exactly those variables are remapped by largest area
+        #: fraction (pyremap_amd.laf; CDO's remaplaf) -- every destination
+        #: cell takes the source value whose weights add up to the most --
+        #: and skip the limiter; an integer variable keeps its dtype and gets
+        #: its _FillValue (netCDF's default of its type if it has none) where
+        #: masked.  Every other variable is remapped as without it.
+        self.categorical = None
         self.src_scrip_filename = 'src_mesh.nc'
         self.dst_scrip_filename = 'dst_mesh.nc'
         self.format = 'NETCDF3_64BIT_DATA'
@@ -587,6 +610,35 @@ class Remapper:
         return _remap_array_layers(self, field, thickness, bounds,
                                    remap_axes, renormalization_threshold,
                                    reduce=reduce)
+
+    def remap_array_laf(self, field, remap_axes,
+                        renormalization_threshold=None):
+        """
+        :meth:`remap_array` for a field whose values are LABELS -- region
+        and basin ids, land-cover classes, 0/1/2 flags -- by largest area
+        fraction (CDO's ``remaplaf``): every destination cell takes the
+        source value whose weights in its row add up to the most, in one
+        launch (:mod:`pyremap_amd.laf` has the definition to the bit), so
+        only values the input holds come out.  It needs nothing but the rows
+        of the map -- a ``conserve`` map is the one to use.  Device tensor in
+        -> device tensor out; numpy in -> ``numpy.ma.MaskedArray`` out, the
+        mask taken from NaN.
+
+        Float fields go as they are (NaN: missing).  Integer and bool fields
+        travel as float64 and come back in their own type, exactly, with 0
+        under the mask; an int64 / uint64 field with a value beyond +-2^53
+        is a ``ValueError``.  A destination cell is masked where its row
+        holds no value or the valid weight is not above
+        ``renormalization_threshold`` (``None``: 0.0).  One device; never
+        limited.
+        """
+        if self.map_filename is None:
+            raise ValueError('No mapping file has been defined')
+        _check_alone(self, 'categorical')
+        _check_label_field(field)
+        _load_mapping(self)
+        return _remap_array_laf(self, field, remap_axes,
+                                renormalization_threshold)
 
     # pyremap-1.x names used by BASELINE.json's north_star
     remap = remap_numpy
