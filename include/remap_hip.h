@@ -117,7 +117,57 @@ enum {
      * F64 and F32 are served (float32 widens exactly), x_src_fold and every
      * stride are addressed as in the other modes.  Signed weights
      * (conserve2nd, patch, a file) are legal: the sums are what they are. */
-    REMAP_MODE_LAF = 3
+    REMAP_MODE_LAF = 3,
+    /* (4 to 7 are not assigned: "unknown mode") */
+    /* Sub-grid statistics (CDO's remapmin, remapmax, remapvar, remapmedian):
+     * what the spread of the source values under a destination cell is --
+     * the roughness of a topography, the shallowest and deepest depth, a
+     * median that outliers do not pull.  (Added enumerators of ABI 31: no
+     * existing caller changes, the version stays.)
+     * For destination element (i, b, k) the entries j of row i are walked in
+     * CSR order:
+     *   x_j = (double) X[cell(col_j), b, k]
+     *   an entry counts iff x_j is no NaN; +-inf are values like any other
+     *   valid starts at +0.0; for every counted entry, in CSR order,
+     *   valid = valid + S_j, each sum rounded
+     *   ok = (some entry counts) && valid > threshold; where !ok, y = NaN
+     * MIN / MAX:
+     *   the first counted x sets m; after it, if (x < m) m = x  (MAX: >)
+     *   strict, so the first seen wins a tie and -0.0 against +0.0 is
+     *   decided by CSR order (remap_limit_rows has the same rule)
+     *   weights enter only through valid; y = m
+     * VAR (weighted population variance, in two walks):
+     *   walk 1: num starts at +0.0; for counted entries
+     *   num = num + (S_j * x_j), the product rounded and the sum rounded;
+     *   mean = num / valid
+     *   walk 2: m2 starts at +0.0; for counted entries d = x_j - mean;
+     *   m2 = m2 + (S_j * (d * d)), every operation rounded, no FMA
+     *   contraction
+     *   y = m2 / valid; a NaN result is written as the canonical NaN (an inf
+     *   among the values gives inf - inf)
+     * MEDIAN (lower weighted median, needs no table):
+     *   half = 0.5 * valid
+     *   for a counted entry j, below_j starts at +0.0 and adds S_q, in CSR
+     *   order, over the counted q of the row with x_q <= x_j (j itself
+     *   included)
+     *   j qualifies iff below_j >= half
+     *   y is the least x_j among the qualifying entries (strict <: the first
+     *   seen wins a tie); none qualifies: y = NaN
+     * Every NaN written is 0x7ff8000000000000; mask_out, where given, gets 1
+     * where NaN was written and 0 elsewhere.  No division but num / valid
+     * and m2 / valid, no transcendental: the standard deviation is the
+     * caller's square root of VAR.  As in REMAP_MODE_LAF, flags, tune,
+     * frac_b, row_order and every attached schedule are ignored and the
+     * modes pick their own launch (csrc/apply_rowstat.h); gate / gate_value
+     * are honoured, rows outside [row_begin, row_end) are not written,
+     * x_dtype F64 and F32 are served (float32 widens exactly), x_src_fold
+     * and every stride are addressed as in the other modes.  Signed weights
+     * (conserve2nd, patch) are legal and give what the definition gives;
+     * with non-negative weights MEDIAN is the usual weighted median. */
+    REMAP_MODE_MIN = 8,
+    REMAP_MODE_MAX = 9,
+    REMAP_MODE_VAR = 10,
+    REMAP_MODE_MEDIAN = 11
 };
 
 enum {
@@ -271,7 +321,7 @@ typedef struct remap_apply_args {
     int64_t n_batch;
     int64_t k_inner;
     const double *frac_b;   /* (device) n_rows; REMAP_MODE_FRACB only        */
-    double threshold;       /* REMAP_MODE_MASKED and REMAP_MODE_LAF          */
+    double threshold;       /* REMAP_MODE_MASKED, _LAF, _MIN .. _MEDIAN      */
     uint8_t *mask_out;      /* (device) optional, addressed like Y; 1 where
                                the reference's result is masked (~ok)        */
     const int32_t *row_order; /* (device) optional processing order: entry s
@@ -705,8 +755,9 @@ typedef struct remap_plan_info {
 typedef struct remap_field {
     const void *X;               /* (device) source field                    */
     int32_t x_dtype;             /* REMAP_DTYPE_*                            */
-    int32_t mode;                /* REMAP_MODE_* (REMAP_MODE_LAF walks ONE
-                                  * CSR: REMAP_ERR_UNSUPPORTED on a plan that
+    int32_t mode;                /* REMAP_MODE_* (REMAP_MODE_LAF and _MIN ..
+                                  * _MEDIAN walk ONE CSR:
+                                  * REMAP_ERR_UNSUPPORTED on a plan that
                                   * keeps its long rows apart)               */
     int64_t n_batch;
     int64_t k_inner;
@@ -715,7 +766,7 @@ typedef struct remap_field {
     double *Y;                   /* (device) float64 result                  */
     int64_t y_row_stride;
     int64_t y_batch_stride;
-    double threshold;            /* REMAP_MODE_MASKED, REMAP_MODE_LAF        */
+    double threshold;            /* REMAP_MODE_MASKED, _LAF, _MIN .. _MEDIAN */
     uint8_t *mask_out;           /* (device) or NULL                         */
     const int32_t *gate;         /* (device) or NULL: see remap_apply_args   */
     int32_t gate_value;

@@ -36,6 +36,26 @@ inline int hip_fail(hipError_t err, const char *what)
             return ::remap::hip_fail(err__, #expr);             \
     } while (0)
 
+// The modes of remap_apply_f64 and remap_plan_apply.  (The enumerators are
+// not contiguous: 4 to 7 are not assigned.)
+inline bool is_rowstat_mode(int mode)
+{
+    return mode >= REMAP_MODE_MIN && mode <= REMAP_MODE_MEDIAN;
+}
+
+inline bool is_known_mode(int mode)
+{
+    return (mode >= REMAP_MODE_RAW && mode <= REMAP_MODE_LAF) ||
+           is_rowstat_mode(mode);
+}
+
+// the modes that are a row pass over ONE CSR and pick their own launch: no
+// schedule, no tune, no flags (apply_laf.h, apply_rowstat.h)
+inline bool is_rowpass_mode(int mode)
+{
+    return mode == REMAP_MODE_LAF || is_rowstat_mode(mode);
+}
+
 constexpr int kWave = 64;        // gfx950 wavefront
 constexpr int kBlock = 256;      // 4 waves per workgroup
 constexpr int kWavesPerBlock = kBlock / kWave;

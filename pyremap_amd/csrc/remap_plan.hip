@@ -952,16 +952,22 @@ int remap_plan_apply(const remap_plan *plan, const remap_field *f,
 {
     if (!plan || !f)
         return remap::fail(REMAP_ERR_ARG, "remap_plan_apply: NULL argument");
-    if (f->mode < 0 || f->mode > REMAP_MODE_LAF)
+    if (!remap::is_known_mode(f->mode))
         return remap::fail(REMAP_ERR_ARG, "remap_plan_apply: mode %d",
                            f->mode);
-    // largest area fraction walks the rows of ONE CSR and takes no schedule;
-    // a plan that keeps its long rows apart holds two
+    // largest area fraction and the sub-grid statistics walk the rows of ONE
+    // CSR and take no schedule; a plan that keeps its long rows apart holds
+    // two
     if (f->mode == REMAP_MODE_LAF && plan->n_long != 0)
         return remap::fail(REMAP_ERR_UNSUPPORTED,
                            "remap_plan_apply: REMAP_MODE_LAF is not served "
                            "by a plan that keeps %lld long rows apart",
                            (long long)plan->n_long);
+    if (remap::is_rowstat_mode(f->mode) && plan->n_long != 0)
+        return remap::fail(REMAP_ERR_UNSUPPORTED,
+                           "remap_plan_apply: mode %d (a row statistic) is "
+                           "not served by a plan that keeps %lld long rows "
+                           "apart", f->mode, (long long)plan->n_long);
     // A launch goes to the calling thread's current device; the plan's
     // arrays (and the stream, X and Y the caller passes) belong to the device
     // the plan was created on.  Refuse instead of launching against another
@@ -1005,7 +1011,7 @@ int remap_plan_apply(const remap_plan *plan, const remap_field *f,
     a.gate_value = f->gate_value;
     a.flags = f->flags;
     const remap_schedule &s = plan->sched;
-    if (f->mode == REMAP_MODE_LAF)
+    if (remap::is_rowpass_mode(f->mode))
         return remap_apply_f64(&a, stream);     // (no schedule, no tune)
     // fields whose contiguous run behind the source axes is short, in
     // several batches -- (Time, nCells) -- take the LDS-staged

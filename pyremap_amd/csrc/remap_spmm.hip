@@ -43,6 +43,7 @@
 
 #include "remap_common.h"
 #include "apply_laf.h"
+#include "apply_rowstat.h"
 
 namespace remap {
 
@@ -572,10 +573,10 @@ int check_args(const remap_apply_args *a, Call &c)
     if (a->x_dtype != REMAP_DTYPE_F64 && a->x_dtype != REMAP_DTYPE_F32)
         return fail(REMAP_ERR_ARG, "remap_apply_f64: unknown x_dtype %d",
                     a->x_dtype);
-    if (a->mode < REMAP_MODE_RAW || a->mode > REMAP_MODE_LAF)
+    if (!is_known_mode(a->mode))
         return fail(REMAP_ERR_ARG, "remap_apply_f64: unknown mode %d",
                     a->mode);
-    if (a->mode == REMAP_MODE_LAF)
+    if (is_rowpass_mode(a->mode))
         return REMAP_OK;  // (tune, flags and schedules are not looked at)
     if (a->mode == REMAP_MODE_FRACB && !a->frac_b)
         return fail(REMAP_ERR_ARG,
@@ -1582,6 +1583,9 @@ int apply(const remap_apply_args *a, hipStream_t stream)
     // largest area fraction picks its own launch (apply_laf.h)
     if (a->mode == REMAP_MODE_LAF)
         return laf::apply(a, stream);
+    // ... and so do the sub-grid statistics (apply_rowstat.h)
+    if (is_rowstat_mode(a->mode))
+        return rowstat::apply(a, stream);
     // a preferred family that cannot serve this call gives way to the
     // automatic choice instead of failing
     remap_apply_args relaxed;

@@ -1,9 +1,10 @@
 // rowpass.h -- what the passes that walk the rows of the plan's CSR beside
 // the SpMM apply share (remap_limit.hip, remap_sgs.hip, remap_vector.hip,
-// remap_levels.hip, remap_layers.hip, and apply_laf.h, the one mode of the
-// apply itself that is such a pass): the checks of their argument structs,
-// the addressing of a source cell, the packed loads and stores, and the work
-// list of the rowwave form.  A pass comes in two forms (remap_levels.hip and
+// remap_levels.hip, remap_layers.hip, and apply_laf.h and apply_rowstat.h, the
+// modes of the apply itself that are such passes): the checks of their
+// argument structs, the addressing of a source cell, the packed loads and
+// stores, and the work list of the rowwave form.  A pass comes in two forms
+// (remap_levels.hip and
 // remap_layers.hip have the first alone, and have it, their parameters and
 // their launch from colpass.h, which stands on this header):
 //   rowlane  one lane per (row, column), for runs shorter than a wave;

@@ -34,6 +34,17 @@ MODE_RAW = 0
 MODE_FRACB = 1
 MODE_MASKED = 2
 MODE_LAF = 3           # largest area fraction, for labels (pyremap_amd.laf)
+# sub-grid statistics (pyremap_amd.rowstat); 4 to 7 are not assigned
+MODE_MIN = 8
+MODE_MAX = 9
+MODE_VAR = 10
+MODE_MEDIAN = 11
+#: the modes that are a row pass over the plan's own CSR: no schedule, no
+#: tune, no split, one device; what an error message calls each
+_ROW_PASS_MODES = {MODE_LAF: 'largest area fraction',
+                   MODE_MIN: 'a row statistic', MODE_MAX: 'a row statistic',
+                   MODE_VAR: 'a row statistic',
+                   MODE_MEDIAN: 'a row statistic'}
 
 FLAG_FMA = 1
 FLAG_TUNE_HINT = 4
@@ -1337,12 +1348,14 @@ def apply_strided(plan, X, Y, *, n_batch, k_inner, x_row_stride,
 
     ``mode=MODE_LAF`` (largest area fraction, :mod:`pyremap_amd.laf`) is a
     row pass over the plan's own CSR: ``flags``, ``tune`` and every schedule
-    are ignored, nothing is built, one device only.
+    are ignored, nothing is built, one device only.  ``MODE_MIN``,
+    ``MODE_MAX``, ``MODE_VAR`` and ``MODE_MEDIAN`` (sub-grid statistics,
+    :mod:`pyremap_amd.rowstat`) are such passes too.
     """
     torch = _torch()
     lib = load_library()
-    if mode == MODE_LAF:
-        _one_device(plan, 'largest area fraction')
+    if mode in _ROW_PASS_MODES:
+        _one_device(plan, _ROW_PASS_MODES[mode])
     if X.device != plan.device or Y.device != plan.device:
         raise ValueError('X, Y and the plan must live on the same device')
     if Y.dtype != torch.float64:
@@ -1357,12 +1370,13 @@ def apply_strided(plan, X, Y, *, n_batch, k_inner, x_row_stride,
                                  mask_out.device != plan.device):
         raise TypeError('mask_out must be a uint8 tensor on the plan device')
     end = plan.n_b if row_end is None else row_end
-    if mode == MODE_LAF:
-        # a row pass over the plan's own CSR (csrc/apply_laf.h): no schedule,
-        # no tune, no split into short and long rows; flags mean nothing
+    if mode in _ROW_PASS_MODES:
+        # a row pass over the plan's own CSR (csrc/apply_laf.h,
+        # csrc/apply_rowstat.h): no schedule, no tune, no split into short
+        # and long rows; flags mean nothing
         row_begin, end = _row_range(plan, row_begin, row_end)
         _holds_csr(plan, ('rowptr', 'col', 'val'),
-                   "largest area fraction adds a row's weights from it")
+                   f"{_ROW_PASS_MODES[mode]} adds a row's weights from it")
         args = _ApplyArgs()
         args.A = plan._csr_struct()
         args.row_begin, args.row_end = row_begin, end
@@ -2107,7 +2121,9 @@ def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
     ``mode=MODE_LAF``: largest area fraction for labels
     (:mod:`pyremap_amd.laf`) -- float64 too, same layout, NaN where no class
     exists or ``valid <= threshold``; one device, never limited; ``flags``
-    and ``tune`` are ignored.
+    and ``tune`` are ignored.  ``MODE_MIN``, ``MODE_MAX``, ``MODE_VAR`` and
+    ``MODE_MEDIAN``: sub-grid statistics (:mod:`pyremap_amd.rowstat`), under
+    the same terms.
 
     ``limiter`` (``None | 'clip' | 'caas'``; :mod:`pyremap_amd.limiter`):
     after the apply, on the same stream, every value is clamped to the bounds
@@ -2132,6 +2148,12 @@ def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
             raise ValueError('largest area fraction is not limited: its '
                              'values are source values of their own rows')
         _one_device(plan, 'largest area fraction')
+    elif mode in _ROW_PASS_MODES:
+        # what a limiter clamps to are the bounds of a mean
+        if limiter is not None:
+            raise ValueError('a row statistic is not limited: the bounds of '
+                             'a row are no bounds of its spread')
+        _one_device(plan, _ROW_PASS_MODES[mode])
     if hasattr(plan, 'shards'):
         # a parallel.MultiDeviceRemap standing where the plan stands
         # (Remapper(..., devices=[...])): rows sharded over several GPUs

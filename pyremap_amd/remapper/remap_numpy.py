@@ -24,7 +24,7 @@ import sys
 
 import numpy as np
 
-from pyremap_amd import engine, host_path, vector, xr_lite
+from pyremap_amd import engine, host_path, rowstat, vector, xr_lite
 from pyremap_amd.io.mapfile import read_mapping
 
 try:  # real xarray is honoured when present; it is optional
@@ -332,6 +332,118 @@ def _start_categorical(da, remapper, remap_axes, threshold):
         out[masked] = fill
         return out
     return finish, attrs
+
+
+#: the launch behind each statistic ('std': the VAR launch, then a square
+#: root on the device)
+_STAT_MODES = {'min': engine.MODE_MIN, 'max': engine.MODE_MAX,
+               'var': engine.MODE_VAR, 'std': engine.MODE_VAR,
+               'median': engine.MODE_MEDIAN}
+
+
+def _check_statistics(remapper):
+    """The Remapper's ``statistics`` (None or a dict: variable name -> list
+    of statistics) as a dict of tuples or None, and what it does not go
+    together with (``ValueError``)."""
+    wanted = getattr(remapper, 'statistics', None)
+    if wanted is None:
+        return None
+    if not isinstance(wanted, dict) or not all(
+            isinstance(name, str) and isinstance(stats, (list, tuple))
+            for name, stats in wanted.items()):
+        raise TypeError(f'statistics must be None or a dict of variable '
+                        f'names and lists of statistics, not {wanted!r}')
+    for stats in wanted.values():
+        for stat in stats:
+            rowstat.check_statistic(stat)
+    for other in ('sgs_frac', 'levels', 'layers'):
+        if getattr(remapper, other, None) is not None:
+            raise ValueError(f'statistics together with {other} is not '
+                             f'served')
+    categorical = getattr(remapper, 'categorical', None) or ()
+    paired = [name for pair in getattr(remapper, 'vector_pairs', None) or ()
+              for name in pair]
+    for name in wanted:
+        if name in categorical:
+            raise ValueError(f'the variable {name!r} is listed in statistics '
+                             f'and in categorical: a label has no spread')
+        if name in paired:
+            raise ValueError(f'the variable {name!r} is listed in statistics '
+                             f'and is a member of a vector pair')
+    if getattr(remapper, '_process_group', None) is not None or \
+            len(getattr(remapper, 'devices', None) or ()) > 1:
+        raise NotImplementedError(
+            'statistics serves one device: not with devices=[...] or a '
+            'process group')
+    return {name: tuple(stats) for name, stats in wanted.items()}
+
+
+def _statistics(remapper, ds):
+    """None without ``Remapper.statistics``; else ``[(variable, statistic,
+    output name), ...]`` after the checks of the Dataset: every listed
+    variable is in it (``KeyError``) with all the source dims, and no output
+    name is taken (``ValueError``)."""
+    wanted = _check_statistics(remapper)
+    if wanted is None:
+        return None
+    if not _is_dataset(ds):
+        raise KeyError(f'statistics names the variables {sorted(wanted)}: a '
+                       f'Dataset that holds them is needed, not a DataArray')
+    out = []
+    for name, stats in wanted.items():
+        if name not in ds.variables:
+            raise KeyError(f'statistics names the variable {name!r}, which '
+                           f'is not in the Dataset')
+        src_dims = remapper.src_descriptor.dims
+        if not all(dim in ds[name].dims for dim in src_dims):
+            raise ValueError(
+                f'statistics names the variable {name!r} with dims '
+                f'{tuple(ds[name].dims)}, which lacks the source dims '
+                f'{tuple(src_dims)}')
+        for stat in stats:
+            new = f'{name}_{stat}'
+            if new in ds.variables or new in [o[2] for o in out]:
+                raise ValueError(
+                    f'the statistic {stat!r} of {name!r} would be written '
+                    f'as {new!r}, which the Dataset already holds')
+            out.append((name, stat, new))
+    return out
+
+
+def _remap_statistic(da, remapper, stat, new, threshold):
+    """One statistic of one variable as a DataArray named ``new``: upload,
+    ``engine.remap_tensor`` in the statistic's mode (one launch, no limiter),
+    download.  The dims, coordinates and attributes are the remapped
+    variable's, plus ``remap_statistic``; an integer variable keeps its dtype
+    and gets its ``_FillValue`` for min, max and median (categorical's rule),
+    var and std are float64."""
+    torch = engine.require_gpu()
+    matrix = remapper._matrix
+    remap_axes, dims, coords = _plan_data_array(da, remapper)
+    own = da.attrs.get('_FillValue') if np.dtype(da.dtype).kind in 'iu' \
+        else None
+    values = _label_values(np.asarray(da.values), own)
+    y_d = engine.remap_tensor(
+        matrix, remapper._ds_map.dst_grid_dims,
+        torch.from_numpy(values).to(matrix.device), remap_axes,
+        _STAT_MODES[stat], threshold=0.0 if threshold is None else threshold)
+    if stat == 'std':
+        y_d = torch.sqrt(y_d)
+    data = y_d.cpu().numpy()
+    attrs = type(da.attrs)(da.attrs)
+    dtype, fill = _label_output(da) if stat in ('min', 'max', 'median') \
+        else (None, None)
+    if dtype is not None:
+        masked = np.isnan(data)
+        data = np.where(masked, 0.0, data).astype(dtype)
+        data[masked] = fill
+        attrs['_FillValue'] = fill
+    elif np.dtype(da.dtype).kind != 'f':
+        attrs.pop('_FillValue', None)   # (no fill value of a float result)
+    attrs['remap_statistic'] = stat
+    return _array_class(da).from_dict(
+        {'coords': coords, 'attrs': attrs, 'dims': dims, 'data': data,
+         'name': new})
 
 
 class _SgsFraction:
@@ -746,6 +858,7 @@ def _remap_numpy(remapper, ds, renormalization_threshold):
     # (before anything is loaded: a refusal or a missing fraction variable
     # costs nothing)
     cat = _categorical(remapper, ds)
+    stats = _statistics(remapper, ds)
     lay = _layer_thickness(remapper, ds)
     lev = _level_coordinate(remapper, ds)
     if lay is not None:
@@ -798,6 +911,11 @@ def _remap_numpy(remapper, ds, renormalization_threshold):
         if lay is not None:
             name, bnds = lay.bounds_variable()
             result[name] = bnds
+        for name, stat, new in stats or ():
+            # (beside the variable's own remap, which is what it was; never
+            # limited)
+            result[new] = _remap_statistic(ds[name], remapper, stat, new,
+                                           renormalization_threshold)
     else:
         raise TypeError('ds not an xarray Dataset or DataArray.')
 
@@ -1409,6 +1527,39 @@ def _remap_array_laf(remapper, in_field, remap_axes,
     if not floating:
         out = np.where(mask, 0.0, out).astype(np.asarray(in_field).dtype)
     return np.ma.masked_array(out, mask=mask)
+
+
+def _remap_array_stat(remapper, in_field, stat, remap_axes,
+                      renormalization_threshold):
+    """
+    One statistic of one array through ``engine.remap_tensor`` in the
+    statistic's mode: device tensor in, float64 device tensor out; numpy in,
+    ``numpy.ma.MaskedArray`` (float64) out with the mask taken from NaN.
+    ``'std'`` is the VAR launch and a square root on the device.  ``None``
+    threshold means 0.0.
+    """
+    rowstat.check_statistic(stat)
+    torch = engine.require_gpu()
+    plan = remapper._matrix
+    threshold = 0.0 if renormalization_threshold is None else \
+        float(renormalization_threshold)
+    remap_axes = [int(a) for a in remap_axes]
+    on_device = isinstance(in_field, torch.Tensor)
+    if on_device:
+        field = in_field.to(plan.device)
+        if not field.dtype.is_floating_point:
+            field = field.to(torch.float64)
+    else:
+        field = _host_values(torch, in_field, plan.device)
+    out = engine.remap_tensor(plan, remapper._ds_map.dst_grid_dims, field,
+                              remap_axes, _STAT_MODES[stat],
+                              threshold=threshold)
+    if stat == 'std':
+        out = torch.sqrt(out)
+    if on_device:
+        return out
+    out = out.cpu().numpy()
+    return np.ma.masked_array(out, mask=np.isnan(out))
 
 
 def _check_level_arrays(field, z, targets, level_axis):

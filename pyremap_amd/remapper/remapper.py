@@ -11,6 +11,7 @@ knobs and :meth:`from_triplets` for mapping data that is already in memory.
 from pyremap_amd.remapper.remap_numpy import (
     _check_alone,
     _check_label_field,
+    _check_statistics,
     _check_layer_arrays,
     _check_level_arrays,
     _check_limiter,
@@ -21,11 +22,13 @@ from pyremap_amd.remapper.remap_numpy import (
     _remap_array_layers,
     _remap_array_levels,
     _remap_array_sgs,
+    _remap_array_stat,
     _remap_array_vector,
     _require_centres,
     _remap_numpy_array,
 )
 from pyremap_amd.remapper.setup import _setup_remapper
+from pyremap_amd.rowstat import check_statistic
 
 
 class Remapper:
@@ -111,6 +114,15 @@ class Remapper:
         cells get its ``_FillValue`` (netCDF's default fill value of the
         type if it has none); the listed variables skip the ``limiter``;
         :meth:`remap_array_laf` is the array-level entry
+    statistics : None or dict
+        set after construction (default ``None``: nothing changes):
+        ``{'bottomDepth': ['min', 'max', 'std']}`` -- for each listed
+        Dataset variable, which sub-grid statistics
+        (:mod:`pyremap_amd.rowstat`: ``'min'``, ``'max'``, ``'var'``,
+        ``'std'``, ``'median'`` of the source values under each destination
+        cell; CDO's ``remapmin`` ...) ``remap_numpy`` and ``ncremap`` add to
+        the output as ``<name>_<stat>``, beside the variable remapped as
+        before; :meth:`remap_array_stat` is the array-level entry
     """
 
     def __init__(
@@ -196,6 +208,20 @@ class Remapper:
         #: its _FillValue (netCDF's default of its type if it has none) where
         #: masked.  Every other variable is remapped as without it.
         self.categorical = None
+        #: sub-grid statistics (None | a dict: name of a Dataset variable ->
+        #: list of 'min', 'max', 'var', 'std', 'median'), honoured by
+        #: remap_numpy and ncremap: every listed variable is remapped as
+        #: without it, and the output gains <name>_<stat> -- the statistic of
+        #: the source values under each destination cell
+        #: (pyremap_amd.rowstat), with the dims and attributes of the
+        #: remapped variable plus the attribute remap_statistic.  An integer
+        #: variable keeps its dtype and gets its _FillValue for min, max and
+        #: median (categorical's rule); var and std are float64.  The
+        #: threshold is renormalization_threshold; the extra outputs skip the
+        #: limiter.  Not together with sgs_frac, levels or layers, nor for a
+        #: variable that is categorical or a member of a vector pair
+        #: (ValueError).
+        self.statistics = None
         self.src_scrip_filename = 'src_mesh.nc'
         self.dst_scrip_filename = 'dst_mesh.nc'
         self.format = 'NETCDF3_64BIT_DATA'
@@ -639,6 +665,30 @@ class Remapper:
         _load_mapping(self)
         return _remap_array_laf(self, field, remap_axes,
                                 renormalization_threshold)
+
+    def remap_array_stat(self, field, stat, remap_axes, threshold=None):
+        """
+        :meth:`remap_array` for a sub-grid statistic: ``stat`` is ``'min'``,
+        ``'max'``, ``'var'``, ``'std'`` or ``'median'`` of the source values
+        under each destination cell (CDO's ``remapmin``, ``remapmax``,
+        ``remapvar``, ``remapstd``, ``remapmedian``;
+        :mod:`pyremap_amd.rowstat` has the definitions to the bit), in one
+        launch from the rows of the map -- a ``conserve`` map is the one to
+        use.  ``'var'`` is the weighted population variance, ``'std'`` its
+        square root (taken on the device), ``'median'`` the lower weighted
+        median.  Device tensor in -> float64 device tensor out; numpy in ->
+        ``numpy.ma.MaskedArray`` out, the mask taken from NaN.
+
+        NaN in the field is missing.  A destination cell is masked where its
+        row holds no value or the valid weight is not above ``threshold``
+        (``None``: 0.0).  One device; never limited.
+        """
+        if self.map_filename is None:
+            raise ValueError('No mapping file has been defined')
+        check_statistic(stat)
+        _check_statistics(self)
+        _load_mapping(self)
+        return _remap_array_stat(self, field, stat, remap_axes, threshold)
 
     # pyremap-1.x names used by BASELINE.json's north_star
     remap = remap_numpy
