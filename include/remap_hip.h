@@ -167,7 +167,42 @@ enum {
     REMAP_MODE_MIN = 8,
     REMAP_MODE_MAX = 9,
     REMAP_MODE_VAR = 10,
-    REMAP_MODE_MEDIAN = 11
+    REMAP_MODE_MEDIAN = 11,
+    /* (12 is not assigned: "unknown mode") */
+    /* Sub-grid composition: what share of a destination cell every class or
+     * value range takes -- percent cover per land-cover type, elevation and
+     * depth bands (a histogram of a continuous field whose values the caller
+     * turned into bin indices), fractional region masks.  REMAP_MODE_LAF is
+     * the argmax of exactly these sums.  (An added enumerator of ABI 31: no
+     * existing caller changes, the version stays.)
+     * The arguments are read in their own way:
+     *   X holds class indices as numbers (x_dtype F64 or F32) and is ONE
+     *   batch: x_batch_stride must be 0 (REMAP_ERR_ARG otherwise);
+     *   n_batch is the number of classes C, 1 <= C <= 256 (REMAP_ERR_ARG
+     *   beyond: 8-bit rasters, and a result of (C, n_b, k_inner));
+     *   the batches of Y, and of mask_out where given, are the classes:
+     *   Y[c * y_batch_stride + i * y_row_stride + k].
+     * For destination element (i, k) the entries j of row i are walked in
+     * CSR order:
+     *   x = (double) X[cell(col_j), k]
+     *   the entry counts iff x is no NaN; then valid = valid + S_j
+     *   a counted entry belongs to class c iff x == (double) c for an integer c
+     *   in [0, C); -0.0 is class 0; a non-integer, +-inf or a value outside the
+     *   range counts in valid alone
+     *   w_c = w_c + S_j for the entry's class and for no other
+     *   valid and every w_c start at +0.0; every sum rounded, in CSR order
+     *   y_c = valid > threshold ? w_c / valid : NaN, for every c: one division
+     *   a NaN quotient is written as the canonical NaN 0x7ff8000000000000
+     * mask_out, where given, gets 1 where NaN was written and 0 elsewhere.
+     * With every value a class the fractions of an element add up to 1 within
+     * rounding; a value that is no class lowers the sum.  flags, tune, frac_b,
+     * row_order and every attached schedule are ignored and the mode picks its
+     * own launch (csrc/apply_classfrac.h); x_src_fold, x_outer_stride,
+     * row_begin / row_end and gate / gate_value work as in REMAP_MODE_LAF.
+     * Through remap_plan_apply the mode gives REMAP_ERR_UNSUPPORTED on a plan
+     * that keeps long rows apart, as LAF does.  Signed weights (conserve2nd,
+     * patch) are legal and give what the definition gives. */
+    REMAP_MODE_CLASSFRAC = 13
 };
 
 enum {

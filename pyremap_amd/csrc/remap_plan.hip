@@ -955,9 +955,9 @@ int remap_plan_apply(const remap_plan *plan, const remap_field *f,
     if (!remap::is_known_mode(f->mode))
         return remap::fail(REMAP_ERR_ARG, "remap_plan_apply: mode %d",
                            f->mode);
-    // largest area fraction and the sub-grid statistics walk the rows of ONE
-    // CSR and take no schedule; a plan that keeps its long rows apart holds
-    // two
+    // largest area fraction, the sub-grid statistics and the class fractions
+    // walk the rows of ONE CSR and take no schedule; a plan that keeps its
+    // long rows apart holds two
     if (f->mode == REMAP_MODE_LAF && plan->n_long != 0)
         return remap::fail(REMAP_ERR_UNSUPPORTED,
                            "remap_plan_apply: REMAP_MODE_LAF is not served "
@@ -968,6 +968,11 @@ int remap_plan_apply(const remap_plan *plan, const remap_field *f,
                            "remap_plan_apply: mode %d (a row statistic) is "
                            "not served by a plan that keeps %lld long rows "
                            "apart", f->mode, (long long)plan->n_long);
+    if (f->mode == REMAP_MODE_CLASSFRAC && plan->n_long != 0)
+        return remap::fail(REMAP_ERR_UNSUPPORTED,
+                           "remap_plan_apply: REMAP_MODE_CLASSFRAC is not "
+                           "served by a plan that keeps %lld long rows apart",
+                           (long long)plan->n_long);
     // A launch goes to the calling thread's current device; the plan's
     // arrays (and the stream, X and Y the caller passes) belong to the device
     // the plan was created on.  Refuse instead of launching against another

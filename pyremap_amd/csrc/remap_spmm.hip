@@ -42,6 +42,7 @@
 #include <utility>
 
 #include "remap_common.h"
+#include "apply_classfrac.h"
 #include "apply_laf.h"
 #include "apply_rowstat.h"
 
@@ -1586,6 +1587,9 @@ int apply(const remap_apply_args *a, hipStream_t stream)
     // ... and so do the sub-grid statistics (apply_rowstat.h)
     if (is_rowstat_mode(a->mode))
         return rowstat::apply(a, stream);
+    // ... and the class and bin area fractions (apply_classfrac.h)
+    if (a->mode == REMAP_MODE_CLASSFRAC)
+        return classfrac::apply(a, stream);
     // a preferred family that cannot serve this call gives way to the
     // automatic choice instead of failing
     remap_apply_args relaxed;

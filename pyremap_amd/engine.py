@@ -39,12 +39,15 @@ MODE_MIN = 8
 MODE_MAX = 9
 MODE_VAR = 10
 MODE_MEDIAN = 11
+# class and bin area fractions (pyremap_amd.classfrac); 12 is not assigned
+MODE_CLASSFRAC = 13
 #: the modes that are a row pass over the plan's own CSR: no schedule, no
 #: tune, no split, one device; what an error message calls each
 _ROW_PASS_MODES = {MODE_LAF: 'largest area fraction',
                    MODE_MIN: 'a row statistic', MODE_MAX: 'a row statistic',
                    MODE_VAR: 'a row statistic',
-                   MODE_MEDIAN: 'a row statistic'}
+                   MODE_MEDIAN: 'a row statistic',
+                   MODE_CLASSFRAC: 'class fractions'}
 
 FLAG_FMA = 1
 FLAG_TUNE_HINT = 4
@@ -1350,7 +1353,12 @@ def apply_strided(plan, X, Y, *, n_batch, k_inner, x_row_stride,
     row pass over the plan's own CSR: ``flags``, ``tune`` and every schedule
     are ignored, nothing is built, one device only.  ``MODE_MIN``,
     ``MODE_MAX``, ``MODE_VAR`` and ``MODE_MEDIAN`` (sub-grid statistics,
-    :mod:`pyremap_amd.rowstat`) are such passes too.
+    :mod:`pyremap_amd.rowstat`) are such passes too, and so is
+    ``MODE_CLASSFRAC`` (:mod:`pyremap_amd.classfrac`), which reads its
+    arguments in its own way: ``X`` is ONE batch of class indices
+    (``x_batch_stride=0``), ``n_batch`` the number of classes and the batches
+    of ``Y`` and ``mask_out`` are the classes
+    (:func:`remap_tensor_fractions` is the entry that lays them out).
     """
     torch = _torch()
     lib = load_library()
@@ -1372,8 +1380,8 @@ def apply_strided(plan, X, Y, *, n_batch, k_inner, x_row_stride,
     end = plan.n_b if row_end is None else row_end
     if mode in _ROW_PASS_MODES:
         # a row pass over the plan's own CSR (csrc/apply_laf.h,
-        # csrc/apply_rowstat.h): no schedule, no tune, no split into short
-        # and long rows; flags mean nothing
+        # csrc/apply_rowstat.h, csrc/apply_classfrac.h): no schedule, no tune,
+        # no split into short and long rows; flags mean nothing
         row_begin, end = _row_range(plan, row_begin, row_end)
         _holds_csr(plan, ('rowptr', 'col', 'val'),
                    f"{_ROW_PASS_MODES[mode]} adds a row's weights from it")
@@ -2148,6 +2156,9 @@ def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
             raise ValueError('largest area fraction is not limited: its '
                              'values are source values of their own rows')
         _one_device(plan, 'largest area fraction')
+    elif mode == MODE_CLASSFRAC:
+        raise ValueError('class fractions have one more axis than the field: '
+                         'remap_tensor_fractions lays them out')
     elif mode in _ROW_PASS_MODES:
         # what a limiter clamps to are the bounds of a mean
         if limiter is not None:
@@ -2218,6 +2229,112 @@ def remap_tensor(plan, dst_grid_dims, field, remap_axes, mode, threshold=0.0,
             out.copy_(Y)
             Y = out
     return (Y, _launch_result(lay, mask)) if want_mask else Y
+
+
+def _ascending_tensor(torch, values, device, check):
+    """``values`` (a sequence, an array or a tensor) through ``check`` of
+    :mod:`pyremap_amd.classfrac` as a float64 tensor on ``device``."""
+    if isinstance(values, torch.Tensor):
+        values = values.detach().cpu().numpy()
+    return torch.from_numpy(check(values)).to(device)
+
+
+def _label_source(torch, values):
+    if not isinstance(values, torch.Tensor):
+        raise TypeError('values must be a tensor (pyremap_amd.classfrac has '
+                        'the numpy twins)')
+    return values.to(torch.float64)
+
+
+def class_labels(values, classes):
+    """:func:`pyremap_amd.classfrac.labels_from_classes` on a tensor: the
+    index of every value in the strictly ascending ``classes`` as float32
+    (indices up to 256 are exact), -1 for a value that is not listed, NaN
+    stays NaN."""
+    from pyremap_amd import classfrac
+    torch = _torch()
+    v = _label_source(torch, values)
+    c = _ascending_tensor(torch, classes, v.device, classfrac.check_classes)
+    idx = torch.searchsorted(c, v.contiguous()).clamp_(max=c.numel() - 1)
+    out = torch.where(c[idx] == v, idx.to(torch.float32),
+                      torch.full((), -1.0, dtype=torch.float32,
+                                 device=v.device))
+    return torch.where(torch.isnan(v), torch.full_like(out, float('nan')),
+                       out)
+
+
+def bin_labels(values, edges):
+    """:func:`pyremap_amd.classfrac.labels_from_bins` on a tensor: the bin of
+    every value as float32, bin ``c`` being ``edges[c] <= x < edges[c + 1]``
+    (+-inf edges allowed), -1 outside the edges, NaN stays NaN."""
+    from pyremap_amd import classfrac
+    torch = _torch()
+    v = _label_source(torch, values)
+    e = _ascending_tensor(torch, edges, v.device, classfrac.check_edges)
+    idx = torch.searchsorted(e, v.contiguous(), right=True) - 1
+    inside = (idx >= 0) & (idx < e.numel() - 1)
+    out = torch.where(inside, idx.to(torch.float32),
+                      torch.full((), -1.0, dtype=torch.float32,
+                                 device=v.device))
+    return torch.where(torch.isnan(v), torch.full_like(out, float('nan')),
+                       out)
+
+
+def remap_tensor_fractions(plan, dst_grid_dims, labels, n_classes, remap_axes,
+                           threshold=0.0, want_mask=False):
+    """
+    Class (or bin) area fractions of a field of labels
+    (:mod:`pyremap_amd.classfrac`; ``MODE_CLASSFRAC``): ``labels`` is a device
+    tensor of class indices held as numbers (:func:`class_labels`,
+    :func:`bin_labels`; NaN is missing, anything that is no integer in ``[0,
+    n_classes)`` counts in the denominator alone) whose axes ``remap_axes``
+    hold the source grid.  Returns the float64 tensor of shape ``(n_classes,)
+    +`` the shape :func:`remap_tensor` would give, NaN where ``valid <=
+    threshold``, and the uint8 mask (1 = masked) of that shape when
+    ``want_mask``.
+
+    The labels are gathered once per tile of 16 classes, not once per class.
+    Dims in front of adjacent source axes (Time) are served by one launch
+    each, dims behind them are the contiguous run of the launch; any other
+    axis order is permuted to ``(n_a, K)`` first.  One device, never limited.
+    """
+    from pyremap_amd import classfrac
+    torch = _torch()
+    _one_device(plan, _ROW_PASS_MODES[MODE_CLASSFRAC])
+    C = classfrac.check_n_classes(n_classes)
+    remap_axes, dst_shape = check_field_extents(
+        plan.n_a, plan.n_b, plan.n_b_global, dst_grid_dims, labels.shape,
+        remap_axes)
+    if labels.dtype not in (torch.float64, torch.float32):
+        labels = labels.to(torch.float64)
+    lay = field_layout(plan, labels.shape, remap_axes, dst_shape, fold=False)
+    # 'direct': the dims in front are launches here (X is ONE batch)
+    n_launch = lay.strides['n_batch']
+    k = lay.strides['k_inner']
+    X = _launch_source(plan, lay, labels, k)
+    Y = torch.empty([C] + list(lay.y_shape), dtype=torch.float64,
+                    device=labels.device)
+    mask = torch.empty(Y.shape, dtype=torch.uint8, device=labels.device) \
+        if want_mask else None
+    piece = plan.n_b * k
+    strides = dict(n_batch=C, k_inner=k, x_row_stride=k, x_batch_stride=0,
+                   y_row_stride=k, y_batch_stride=n_launch * piece)
+    if Y.numel():
+        Xs = X.reshape(n_launch, plan.n_a * k)
+        for li in range(n_launch):
+            # launch li writes Y[:, li]: its own piece of every class
+            apply_strided(
+                plan, Xs[li], Y.reshape(-1)[li * piece:],
+                mode=MODE_CLASSFRAC, threshold=threshold,
+                mask_out=None if mask is None else
+                mask.reshape(-1)[li * piece:], **strides)
+    if lay.back is not None:
+        shape, unpermute = lay.back
+        order = [0] + [u + 1 for u in unpermute]
+        Y = Y.reshape([C] + list(shape)).permute(order).contiguous()
+        if mask is not None:
+            mask = mask.reshape([C] + list(shape)).permute(order).contiguous()
+    return (Y, mask) if want_mask else Y
 
 
 def _sgs_group(frac, shape, axes):

@@ -24,7 +24,8 @@ import sys
 
 import numpy as np
 
-from pyremap_amd import engine, host_path, rowstat, vector, xr_lite
+from pyremap_amd import (classfrac, engine, host_path, rowstat, vector,
+                         xr_lite)
 from pyremap_amd.io.mapfile import read_mapping
 
 try:  # real xarray is honoured when present; it is optional
@@ -446,6 +447,181 @@ def _remap_statistic(da, remapper, stat, new, threshold):
          'name': new})
 
 
+def _fraction_spec(name, spec):
+    """One entry of ``Remapper.fractions`` as ``(kind, values)``: ``('class',
+    None | the strictly ascending classes)`` or ``('bin', the strictly
+    ascending edges)``."""
+    if not isinstance(spec, dict) or len(spec) != 1 or \
+            next(iter(spec)) not in ('classes', 'bins'):
+        raise TypeError(
+            f'fractions[{name!r}] must be dict(classes=[...] | None) or '
+            f'dict(bins=[...]), not {spec!r}')
+    if 'classes' in spec:
+        values = spec['classes']
+        return 'class', None if values is None else \
+            classfrac.check_classes(values)
+    if spec['bins'] is None:
+        raise ValueError(f'fractions[{name!r}]: bins needs its edges')
+    return 'bin', classfrac.check_edges(spec['bins'])
+
+
+def _check_fractions_alone(remapper):
+    """What class fractions do not go together with (``ValueError``), and
+    that they serve one device (``NotImplementedError``)."""
+    for other in ('sgs_frac', 'levels', 'layers'):
+        if getattr(remapper, other, None) is not None:
+            raise ValueError(f'fractions together with {other} is not '
+                             f'served')
+    if getattr(remapper, '_process_group', None) is not None or \
+            len(getattr(remapper, 'devices', None) or ()) > 1:
+        raise NotImplementedError(
+            'fractions serves one device: not with devices=[...] or a '
+            'process group')
+
+
+def _check_fractions(remapper):
+    """The Remapper's ``fractions`` (None or a dict: variable name ->
+    ``dict(classes=...)`` or ``dict(bins=...)``) as a dict of ``(kind,
+    values)`` or None, and what it does not go together with
+    (``ValueError``).  A variable may be categorical or have statistics
+    too."""
+    wanted = getattr(remapper, 'fractions', None)
+    if wanted is None:
+        return None
+    if not isinstance(wanted, dict) or not all(
+            isinstance(name, str) for name in wanted):
+        raise TypeError(f'fractions must be None or a dict of variable names '
+                        f'and dict(classes=...) or dict(bins=...), not '
+                        f'{wanted!r}')
+    out = {name: _fraction_spec(name, spec) for name, spec in wanted.items()}
+    paired = [name for pair in getattr(remapper, 'vector_pairs', None) or ()
+              for name in pair]
+    for name in wanted:
+        if name in paired:
+            raise ValueError(f'the variable {name!r} is listed in fractions '
+                             f'and is a member of a vector pair')
+    _check_fractions_alone(remapper)
+    return out
+
+
+def _fraction_names(name, kind):
+    """What the fractions of ``name`` are written as: ``(variable, class or
+    bin dim, the variable that says what the classes or bins are)``."""
+    dim = f'{name}_{kind}'
+    return f'{name}_frac', dim, dim if kind == 'class' else dim + '_bnds'
+
+
+def _fractions(remapper, ds):
+    """None without ``Remapper.fractions``; else ``[(variable, kind,
+    values), ...]`` after the checks of the Dataset: every listed variable is
+    in it (``KeyError``) with all the source dims, and no output name is
+    taken (``ValueError``)."""
+    wanted = _check_fractions(remapper)
+    if wanted is None:
+        return None
+    if not _is_dataset(ds):
+        raise KeyError(f'fractions names the variables {sorted(wanted)}: a '
+                       f'Dataset that holds them is needed, not a DataArray')
+    taken = set(ds.variables) | set(ds.sizes)
+    for stat_name, stats in (getattr(remapper, 'statistics', None)
+                             or {}).items():
+        taken |= {f'{stat_name}_{stat}' for stat in stats}
+    out = []
+    for name, (kind, values) in wanted.items():
+        if name not in ds.variables:
+            raise KeyError(f'fractions names the variable {name!r}, which '
+                           f'is not in the Dataset')
+        src_dims = remapper.src_descriptor.dims
+        if not all(dim in ds[name].dims for dim in src_dims):
+            raise ValueError(
+                f'fractions names the variable {name!r} with dims '
+                f'{tuple(ds[name].dims)}, which lacks the source dims '
+                f'{tuple(src_dims)}')
+        for new in dict.fromkeys(_fraction_names(name, kind)):
+            if new in taken:
+                raise ValueError(
+                    f'the fractions of {name!r} would be written with '
+                    f'{new!r}, which the Dataset already holds')
+            taken.add(new)
+        if kind == 'bin' and ds.sizes.get('nbnd', 2) != 2:
+            raise ValueError(
+                f"the bins of {name!r} would be written along 'nbnd', which "
+                f'the Dataset holds with size {ds.sizes["nbnd"]}')
+        out.append((name, kind, values))
+    return out
+
+
+def _discover_classes(values):
+    """The sorted distinct non-NaN values of a float array or tensor, as a
+    float64 array (``ValueError`` naming their number beyond 256)."""
+    if isinstance(values, np.ndarray):
+        found = np.unique(values[~np.isnan(values)]).astype(np.float64)
+    else:
+        torch = engine.require_gpu()
+        found = torch.unique(values[~torch.isnan(values)]).to(
+            torch.float64).cpu().numpy()
+    found = np.unique(found)        # (-0.0 and 0.0 are one class)
+    if found.size > classfrac.MAX_CLASSES:
+        raise ValueError(
+            f'the field holds {found.size} distinct values: more than '
+            f'{classfrac.MAX_CLASSES} classes are not served (give classes '
+            f'or bins)')
+    if found.size == 0:
+        raise ValueError('the field holds no value: no class to discover')
+    return found
+
+
+def _fraction_launch(remapper, values_d, kind, values, remap_axes, threshold):
+    """Labels and launch: the float64 ``(C,) + remapped shape`` tensor of a
+    float device tensor ``values_d`` for the classes or bin edges
+    ``values``."""
+    if kind == 'class':
+        labels = engine.class_labels(values_d, values)
+        n = len(values)
+    else:
+        labels = engine.bin_labels(values_d, values)
+        n = len(values) - 1
+    return engine.remap_tensor_fractions(
+        remapper._matrix, remapper._ds_map.dst_grid_dims, labels, n,
+        remap_axes, threshold=0.0 if threshold is None else float(threshold))
+
+
+def _remap_fractions(da, remapper, name, kind, values, threshold):
+    """The variables the fractions of one variable add, as ``{name:
+    DataArray}``: ``<name>_frac`` (float64, the class or bin dim in front of
+    the remapped dims, NaN where masked) and ``<name>_class`` (the class
+    values in the variable's dtype) or ``<name>_bin_bnds`` (``(bins, 'nbnd')``
+    as ``layers`` writes its bounds).  An integer variable's ``_FillValue``
+    is missing data (categorical's rule)."""
+    torch = engine.require_gpu()
+    matrix = remapper._matrix
+    remap_axes, dims, coords = _plan_data_array(da, remapper)
+    frac_name, dim, what_name = _fraction_names(name, kind)
+    dtype = np.dtype(da.dtype)
+    own = da.attrs.get('_FillValue') if dtype.kind in 'iu' else None
+    host = _label_values(np.asarray(da.values), own)
+    if kind == 'class' and values is None:
+        values = _discover_classes(host)
+    y_d = _fraction_launch(remapper, torch.from_numpy(host).to(matrix.device),
+                           kind, values, remap_axes, threshold)
+    cls = _array_class(da)
+    which = 'class' if kind == 'class' else 'bin'
+    attrs = {'units': '1', 'remap_fraction': which,
+             'long_name': f'area fraction of each {which} of {name}'}
+    out = {frac_name: cls.from_dict(
+        {'coords': coords, 'attrs': attrs, 'dims': [dim] + list(dims),
+         'data': y_d.cpu().numpy(), 'name': frac_name})}
+    if kind == 'class':
+        # (the variable's own type: bool is int8, and integers that a file's
+        # _FillValue made floats are integers again -- categorical's rule)
+        out[what_name] = cls(values.astype(_label_output(da)[0] or dtype),
+                             dims=(dim,), name=what_name)
+    else:
+        out[what_name] = cls(np.stack([values[:-1], values[1:]], axis=1),
+                             dims=(dim, 'nbnd'), name=what_name)
+    return out
+
+
 class _SgsFraction:
     """The fraction variable of one ``remap_numpy`` / ``ncremap`` call
     (``Remapper.sgs_frac``): read and uploaded once, when the first weighted
@@ -859,6 +1035,7 @@ def _remap_numpy(remapper, ds, renormalization_threshold):
     # costs nothing)
     cat = _categorical(remapper, ds)
     stats = _statistics(remapper, ds)
+    fracs = _fractions(remapper, ds)
     lay = _layer_thickness(remapper, ds)
     lev = _level_coordinate(remapper, ds)
     if lay is not None:
@@ -916,6 +1093,12 @@ def _remap_numpy(remapper, ds, renormalization_threshold):
             # limited)
             result[new] = _remap_statistic(ds[name], remapper, stat, new,
                                            renormalization_threshold)
+        for name, kind, values in fracs or ():
+            # (beside the variable's own remap too; never limited)
+            for new, da in _remap_fractions(
+                    ds[name], remapper, name, kind, values,
+                    renormalization_threshold).items():
+                result[new] = da
     else:
         raise TypeError('ds not an xarray Dataset or DataArray.')
 
@@ -1560,6 +1743,46 @@ def _remap_array_stat(remapper, in_field, stat, remap_axes,
         return out
     out = out.cpu().numpy()
     return np.ma.masked_array(out, mask=np.isnan(out))
+
+
+def _remap_array_fractions(remapper, in_field, remap_axes, classes, bins,
+                           renormalization_threshold):
+    """
+    The class or bin area fractions of one array through
+    ``engine.remap_tensor_fractions``: ``(fractions, classes_or_edges)``.
+    Device tensor in, float64 device tensor out (NaN where masked); numpy in,
+    ``numpy.ma.MaskedArray`` out with the mask taken from NaN.  The second
+    member is a numpy array: the classes (the discovered ones in the field's
+    dtype) or the float64 edges.  ``None`` threshold means 0.0.
+    """
+    torch = engine.require_gpu()
+    plan = remapper._matrix
+    remap_axes = [int(a) for a in remap_axes]
+    on_device = isinstance(in_field, torch.Tensor)
+    if on_device:
+        field = in_field.to(plan.device)
+        if not field.dtype.is_floating_point:
+            field = field.to(torch.float64)
+        in_dtype = None
+    else:
+        field = _host_values(torch, in_field, plan.device)
+        in_dtype = np.asarray(in_field).dtype
+    if bins is not None:
+        kind, values = 'bin', classfrac.check_edges(bins)
+        what = values
+    elif classes is not None:
+        kind, values = 'class', classfrac.check_classes(classes)
+        what = np.asarray(classes)
+    else:
+        kind, values = 'class', _discover_classes(field)
+        what = values if in_dtype is None or in_dtype.kind == 'b' else \
+            values.astype(in_dtype)
+    out = _fraction_launch(remapper, field, kind, values, remap_axes,
+                           renormalization_threshold)
+    if on_device:
+        return out, what
+    out = out.cpu().numpy()
+    return np.ma.masked_array(out, mask=np.isnan(out)), what
 
 
 def _check_level_arrays(field, z, targets, level_axis):

@@ -12,6 +12,7 @@ from pyremap_amd.remapper.remap_numpy import (
     _check_alone,
     _check_label_field,
     _check_statistics,
+    _check_fractions_alone,
     _check_layer_arrays,
     _check_level_arrays,
     _check_limiter,
@@ -23,11 +24,13 @@ from pyremap_amd.remapper.remap_numpy import (
     _remap_array_levels,
     _remap_array_sgs,
     _remap_array_stat,
+    _remap_array_fractions,
     _remap_array_vector,
     _require_centres,
     _remap_numpy_array,
 )
 from pyremap_amd.remapper.setup import _setup_remapper
+from pyremap_amd.classfrac import check_classes, check_edges
 from pyremap_amd.rowstat import check_statistic
 
 
@@ -123,6 +126,16 @@ class Remapper:
         cell; CDO's ``remapmin`` ...) ``remap_numpy`` and ``ncremap`` add to
         the output as ``<name>_<stat>``, beside the variable remapped as
         before; :meth:`remap_array_stat` is the array-level entry
+    fractions : None or dict
+        set after construction (default ``None``: nothing changes):
+        ``{'landCover': dict(classes=[...] | None), 'bottomDepth':
+        dict(bins=[...])}`` -- for each listed Dataset variable,
+        ``remap_numpy`` and ``ncremap`` add ``<name>_frac``: what share of
+        every destination cell each class (``classes=None``: the distinct
+        values of the variable) or each value range ``bins[c] <= x <
+        bins[c + 1]`` takes (:mod:`pyremap_amd.classfrac`), beside the
+        variable remapped as before; :meth:`remap_array_fractions` is the
+        array-level entry
     """
 
     def __init__(
@@ -222,6 +235,23 @@ class Remapper:
         #: variable that is categorical or a member of a vector pair
         #: (ValueError).
         self.statistics = None
+        #: sub-grid composition (None | a dict: name of a Dataset variable ->
+        #: dict(classes=[...] | None) or dict(bins=[...])), honoured by
+        #: remap_numpy and ncremap: every listed variable is remapped as
+        #: without it, and the output gains <name>_frac -- float64, dims
+        #: ('<name>_class' | '<name>_bin',) + the remapped dims, the share of
+        #: each destination cell that each class or bin takes
+        #: (pyremap_amd.classfrac; units '1', remap_fraction 'class' | 'bin')
+        #: -- plus <name>_class (the class values in the variable's dtype) or
+        #: <name>_bin_bnds (('<name>_bin', 'nbnd')).  classes=None: the sorted
+        #: distinct values of the variable (at most 256).  A value that is no
+        #: listed class or lies outside the bins counts in the denominator
+        #: only; an integer variable's _FillValue is missing data.  The
+        #: threshold is renormalization_threshold; the extra outputs skip the
+        #: limiter.  A variable may be categorical or have statistics too.
+        #: Not together with sgs_frac, levels or layers, nor for a member of
+        #: a vector pair (ValueError).
+        self.fractions = None
         self.src_scrip_filename = 'src_mesh.nc'
         self.dst_scrip_filename = 'dst_mesh.nc'
         self.format = 'NETCDF3_64BIT_DATA'
@@ -689,6 +719,45 @@ class Remapper:
         _check_statistics(self)
         _load_mapping(self)
         return _remap_array_stat(self, field, stat, remap_axes, threshold)
+
+    def remap_array_fractions(self, field, remap_axes, classes=None,
+                              bins=None, renormalization_threshold=None):
+        """
+        :meth:`remap_array` for the composition under each destination cell:
+        ``(fractions, classes_or_edges)``, where ``fractions`` has shape
+        ``(C,) +`` the remapped shape and ``fractions[c]`` is the share of the
+        valid area of every destination cell that class ``c`` takes
+        (:mod:`pyremap_amd.classfrac` has the definition to the bit), in one
+        launch per index of the dims in front of the source axes -- a
+        ``conserve`` map is the one to use.
+
+        ``classes``: the strictly ascending values that are classes (land
+        cover types, region ids); ``bins``: strictly ascending edges, bin
+        ``c`` being ``bins[c] <= x < bins[c + 1]``, +-inf allowed (elevation
+        or depth bands).  At most one of the two; neither: the sorted
+        distinct non-NaN values of the field are the classes (``ValueError``
+        naming their number beyond 256).  Device tensor in -> float64 device
+        tensor out, NaN where masked; numpy in -> ``numpy.ma.MaskedArray``
+        out.  The second member is a numpy array of the classes or edges.
+
+        NaN in the field is missing.  A value that is no listed class, or
+        lies outside the bins, counts in the denominator only: the fractions
+        of such a cell add up to less than 1.  A destination cell is masked
+        where the valid weight is not above ``renormalization_threshold``
+        (``None``: 0.0).  One device; never limited.
+        """
+        if self.map_filename is None:
+            raise ValueError('No mapping file has been defined')
+        if classes is not None and bins is not None:
+            raise ValueError('classes and bins: at most one of the two')
+        if classes is not None:
+            check_classes(classes)
+        if bins is not None:
+            check_edges(bins)
+        _check_fractions_alone(self)
+        _load_mapping(self)
+        return _remap_array_fractions(self, field, remap_axes, classes, bins,
+                                      renormalization_threshold)
 
     # pyremap-1.x names used by BASELINE.json's north_star
     remap = remap_numpy
