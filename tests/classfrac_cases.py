@@ -27,8 +27,10 @@ DEFINITION = [
     'a NaN quotient is written as the canonical NaN 0x7ff8000000000000',
 ]
 
-#: C: one class, two, around the tile, several tiles with a tail, the most
-CLASS_COUNTS = (1, 2, TILE - 1, TILE, TILE + 1, 2 * TILE + 3, MAX_CLASSES)
+#: C: one class, two (the tile of 4), 5 and 8 (the tile of 8: its least and
+#: its most), around the tile of 16, several tiles with a tail, the most
+CLASS_COUNTS = (1, 2, 5, 8, TILE - 1, TILE, TILE + 1, 2 * TILE + 3,
+                MAX_CLASSES)
 #: k_inner: a lane per element (1 ... 63), a wave per (row, chunk) with two
 #: columns a lane (64, 66, 130, 192) and one (none of these is odd from 64 on;
 #: odd strides and pointers give that form), chunk tails (66, 130)

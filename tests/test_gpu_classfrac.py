@@ -124,9 +124,10 @@ def test_kernel_matches_statement_bytes(C, k):
     """Rows of 0, 1, 2 ... 40 entries with signed weights.  Up to 63
     contiguous columns a lane per (row, column); from 64 a wave per (row,
     chunk), two columns a lane, with a chunk tail (66, 130) and several
-    chunks (130, 192).  One class, two, a tile less one, a tile, a tile and
-    one (a second walk for one class), two tiles and three, and 256 (sixteen
-    walks).  float64 and float32 labels with 20 % NaN, a row that is all NaN,
+    chunks (130, 192).  One class, two (the tile of 4), 5 and 8 (the tile of
+    8), a tile less one, a tile, a tile and one (a second walk for one
+    class), two tiles and three, and 256 (sixteen walks: the tile of 16).
+    float64 and float32 labels with 20 % NaN, a row that is all NaN,
     and -1, C, 2.5, +-inf, 1e300, -0.0 among them; float64 labels without NaN
     or other values."""
     assert np.array_equal(np.diff(_plan()[1])[:41], np.arange(41))
