@@ -1652,8 +1652,9 @@ int remap_column_fractions(int64_t n_entries, int64_t n_cols,
  * The map's triples are (i, j, A_ij / A_i) for every first-order entry and,
  * where cell j has a gradient, (i, k, G_jk . d_ij) for k = j and j's edge
  * neighbours, d_ij = (M_ij - A_ij M_j / A_j) / A_i.  The G of a cell sum to
- * 0, so the rows keep their first-order sums; sum_i M_ij = M_j, so
- * sum_i A_i S_ik = A_k for every fully covered source cell.  This is ESMF's
+ * 0, so the rows keep their first-order sums; sum_i M_ij = M_j for a fully
+ * covered source cell j, so sum_i A_i S_ik = A_k for every source cell k that
+ * is fully covered together with its edge neighbours.  This is ESMF's
  * conserve2nd in structure, not in bytes.  All calls: fp64, on the caller's
  * stream, no floating-point atomics (two calls give the same bytes).
  *

@@ -2817,7 +2817,9 @@ def conserve2nd(src_descriptor, dst_descriptor, device=None, timing=None):
        ``frac_b`` are the first-order map's.
 
     Rows keep their first-order sums (the coefficients of a cell sum to 0)
-    and ``sum_i A_i S_ik = A_k`` for every fully covered source cell.  A
+    and ``sum_i A_i S_ik = A_k`` for every source cell that is fully covered
+    together with its edge neighbours (a partly covered neighbour's gradient
+    reaches into its stencil's columns: the rim of a regional grid).  A
     cell with an edge that has no neighbour (a coast) stays first-order.
     ``timing``: a dict that receives the GPU ``ms`` of the steps
     (``overlap_ms``, ``cell_moments_ms``, ``stencils_ms``,

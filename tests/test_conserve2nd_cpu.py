@@ -399,3 +399,189 @@ def test_the_abi_names_the_conserve2nd_functions():
     for name in ('cell_moments', 'overlap_moments', 'gradient_stencils',
                  'conserve2nd_assemble'):
         assert callable(getattr(engine, name))
+
+
+# ---------------------------------------------------------------------------
+# the references of tests/test_gpu_conserve2nd_edges.py, checked here
+# ---------------------------------------------------------------------------
+
+#: the largest |dM|_max / (2^-52 x diameter) of weights.cell_moments against
+#: the definition in mpmath over the named cells (measured below)
+C_REF = 0.54
+
+
+def moment_error(got, lat, lon, count):
+    """|got - exact_moment|_max / (2^-52 x diameter) of every cell."""
+    from conserve2nd_cases import EPS, diameter, exact_moment
+    want = np.array([exact_moment(lat[c, :k], lon[c, :k])
+                     for c, k in enumerate(count)])
+    return np.abs(got - want).max(axis=1) / (EPS * diameter(lat, lon, count))
+
+
+def test_cell_moments_against_the_definition():
+    """Measured with numpy against mpmath at 50 digits, as |dM|_max / (2^-52
+    x the largest chord from corner 0): pole inside 0.08 and 0.23, a corner
+    on the pole 0.20, across +-pi 0.41 / 0.49 / 0.29 ([-pi, pi), [0, 2 pi),
+    beyond), across 0 0.12 / 0.17 / 0.35, the 32-gon 0.27, the triangle
+    0.18, radius 1e-3 0.20, 1e-6 0.16, 1e-9 0.38, 1.2 rad 0.54.  The
+    largest is C_REF = 0.54; the GPU is held to 8 x C_REF
+    (tests/test_gpu_conserve2nd_edges.py)."""
+    from conserve2nd_cases import NAMED, POLE_INSIDE, ngon_cells
+    from pyremap_amd.weights import cell_moments
+    lat, lon, count = ngon_cells()
+    assert lat.shape == (len(NAMED), 32) and count.max() == 32
+    M = cell_moments(lat, lon, count)
+    err = moment_error(M, lat, lon, count)
+    for name, e in zip(NAMED, err):
+        print(f'{name}: |dM| / (2^-52 diameter) = {e:.3g}')
+    print('C_REF =', err.max())
+    assert err.max() <= 2 * C_REF
+    for c, name in enumerate(NAMED):
+        if name in POLE_INSIDE:
+            # the pole is strictly inside: every longitude sector is covered
+            gaps = np.diff(np.sort(np.mod(lon[c, :count[c]], 2 * np.pi)))
+            assert gaps.max() < np.pi and \
+                (np.abs(lat[c, :count[c]]) < 0.5 * np.pi).all()
+            assert M[c, 2] * POLE_INSIDE[name] > 0.99 * np.linalg.norm(M[c])
+    pole = list(NAMED).index('corner_on_north_pole')
+    assert lat[pole, 0] == 0.5 * np.pi
+    for name in ('across_pi_pm_pi', 'across_zero_0_2pi'):
+        c = list(NAMED).index(name)
+        assert np.ptp(lon[c, :count[c]]) > 6.0          # written over a seam
+
+
+def test_ring_variants_give_the_same_moment():
+    """Measured: reversed 0.46, rotated 1.07, longitudes +2 pi 1.07, -2 pi
+    0.54 (x 2^-52 x diameter, against the definition).
+    Closed, repeated and padded rings give the same bytes: the dropped
+    corners add nothing.  A ring written clockwise, rotated or with its
+    longitudes shifted by 2 pi adds other roundings of the same arcs (p x (q
+    - p) is not -(q x (p - q)) in floating point; the shifted corners differ
+    by an ulp): held to the bound against the definition."""
+    from conserve2nd_cases import NAMED, exact_moment, ngon_cells, scrip
+    from pyremap_amd.weights import cell_moments
+    plain = ngon_cells()
+    M = cell_moments(*plain)
+    for kind in ('close', 'repeat'):
+        cells = ngon_cells(variant=kind)
+        assert cells[0].shape[1] == 32 + (1 if kind == 'close' else 2)
+        assert np.array_equal(cell_moments(*cells), M), kind
+    assert np.array_equal(cell_moments(*ngon_cells(width=40)), M)
+    for kind in ('reverse', 'rotate', 'lon+', 'lon-'):
+        cells = ngon_cells(variant=kind)
+        err = moment_error(cell_moments(*cells), *cells)
+        print(kind, 'max |dM| / (2^-52 diameter) =', err.max())
+        assert err.max() <= 2 * C_REF
+        if kind == 'reverse':
+            # clockwise as written: the flip is what makes these agree
+            v = cell_moments(*cells)
+            assert (np.einsum('ij,ij->i', v, M) > 0.0).all()
+    # a, b, a, b: four corners, none equal to the one before it, so the ring
+    # rule of include/remap_hip.h keeps all four; its arcs cancel
+    la, lo = np.array([0.1, 0.2, 0.1, 0.2]), np.array([0.3, 0.5, 0.3, 0.5])
+    cells = scrip([(la, lo)])
+    assert np.array_equal(exact_moment(la, lo), np.zeros(3))
+    from conserve2nd_cases import diameter
+    assert np.abs(cell_moments(*cells)).max() <= \
+        2 * C_REF * 2.0 ** -52 * diameter(*cells)[0]
+    assert len(NAMED) == len(M)
+
+
+@pytest.mark.parametrize('width', [3, 6, 10])
+def test_gradient_stencils_on_a_constructed_ring(width):
+    from conserve2nd_cases import RING_KINDS, ring_mesh
+    from pyremap_amd.weights import gradient_stencils
+    nbr, count, centroid, has_made = ring_mesh(64, width)
+    coef, has = gradient_stencils(nbr, count, centroid)
+    print('width', width, 'has[:8] =', has[:8], 'by', RING_KINDS)
+    assert np.array_equal(has, has_made)
+    assert list(has[:8]) == [1, 1, 0, 0, 0, 1, 0, 1]
+    assert (coef[has == 0] == 0.0).all()
+    assert (np.abs(coef[has == 1, 0]).max(axis=1) > 0.0).all()
+    k = np.arange(width)[None, :]
+    assert ((nbr >= 0) | ((k == count[:, None] - 1) &
+                          (np.arange(64) % 8 == 6)[:, None])).all()
+    # clockwise = counter-clockwise with the slots reversed
+    nbr_r, count_r, _, has_r = ring_mesh(64, width, clockwise=True)
+    coef_r, got_r = gradient_stencils(nbr_r, count_r, centroid)
+    assert np.array_equal(count_r, count) and np.array_equal(got_r, has)
+    scale = np.abs(coef).max()
+    worst = 0.0
+    for j in np.nonzero(has)[0]:
+        assert np.array_equal(nbr_r[j, :count[j]], nbr[j, :count[j]][::-1])
+        back = np.r_[coef_r[j, :1], coef_r[j, count[j]:0:-1]]
+        worst = max(worst, np.abs(back - coef[j, :1 + count[j]]).max())
+    print('clockwise against counter-clockwise:', worst / scale)
+    assert worst <= 1e-13 * scale
+    assert np.abs(coef.sum(axis=1)).max() <= 1e-13 * max(scale, 1.0)
+    # one cell alone: every neighbour is the cell itself
+    nbr1, count1, c1, has1 = ring_mesh(1, width)
+    coef1, got1 = gradient_stencils(nbr1, count1, c1)
+    assert not has1.any() and not got1.any() and (coef1 == 0.0).all()
+
+
+TWO_SIDED = [(g, m) for g in ('south_cap_across_180', 'north_cap_across_0',
+                              'regional_m30_30') for m in (True, False)]
+
+
+@pytest.mark.parametrize('grid, mesh_is_src', TWO_SIDED)
+def test_moment_pairs_close_and_survive_a_swap(grid, mesh_is_src):
+    """Measured with numpy (closure as max |sum_i M_ij - M_j| / A_j over the
+    fully covered source cells; swap as max |M(clip(s, d)) - M(clip(d, s))| /
+    A_i, held to half of the 1e-13 the GPU is held to), icosahedral n = 4 as
+    source / as destination: the south cap (3 degree rows, 61 pairs) swap
+    9.8e-15 / 3.5e-16, closure - / 3.5e-15; the north cap 9.8e-15 / 4.6e-16,
+    closure - / 4.3e-15; the regional grid (4 degrees, 242 pairs) swap
+    1.8e-14 / 7.0e-16, closure 7.6e-16 / 6.3e-15."""
+    from conserve2nd_cases import swap_asymmetry, two_sided
+    s = two_sided(grid, mesh_is_src)
+    n_src = len(s['src_area'])
+    assert not s['no_polygon'].any() and len(s['dst']) >= 20
+    part = np.bincount(s['src'], weights=s['area'], minlength=n_src)
+    full = np.abs(part - s['src_area']) <= 1e-9 * s['src_area']
+    total = np.zeros((n_src, 3))
+    for k in range(3):
+        total[:, k] = np.bincount(s['src'], weights=s['moment'][:, k],
+                                  minlength=n_src)
+    closure = np.abs(total - s['src_moment']).max(axis=1)[full] / \
+        s['src_area'][full]
+    swap = swap_asymmetry(s)
+    length = np.linalg.norm(s['moment'], axis=1) / s['area']
+    print(f'{grid}, mesh_is_src={mesh_is_src}: {len(s["dst"])} pairs, '
+          f'{full.sum()} cells covered, closure '
+          f'{closure.max() if full.any() else 0.0:.2e}, swap {swap:.2e}, '
+          f'|M| / A in [{length.min():.5f}, {length.max():.5f}]')
+    assert full.any() == (not mesh_is_src or grid == 'regional_m30_30')
+    assert not full.any() or closure.max() <= 1e-12
+    assert swap <= 0.5e-13
+    assert (length > 0.98).all() and (length <= 1.0 + 1e-12).all()
+    if 'cap' in grid:
+        # the polar row is triangles, and the south cap is written clockwise
+        cells = s['cells_dst' if mesh_is_src else 'cells_src']
+        D = s['D' if mesh_is_src else 'S']
+        assert np.abs(cells[0]).max() == 0.5 * np.pi
+        assert {len(p) for p in D} == {3, 4}
+
+
+def test_second_order_entries_add_repeats_in_emission_order():
+    from conserve2nd_cases import assembly_by_the_book, assembly_case
+    from pyremap_amd.weights import second_order_entries
+    for kw in (dict(repeats=40), dict(repeats=40, tiny=True),
+               dict(has='none'), dict(has='all')):
+        case = assembly_case(200, 6, 7, **kw)
+        if kw.get('repeats'):
+            at = (200 - 40) // 3
+            pairs = np.stack([case['dst'], case['src']])
+            assert (pairs[:, at:at + 41] == pairs[:, at:at + 1]).all()
+        row, col, S = second_order_entries(*case.values())
+        brow, bcol, bS, R, _, _, _ = assembly_by_the_book(*case.values())
+        assert np.array_equal(row, brow) and np.array_equal(col, bcol)
+        assert np.array_equal(S, bS)
+        assert R.max() >= (41 if kw.get('repeats') else 2)
+        if kw.get('has') == 'none':
+            assert np.array_equal(np.unique(R), np.unique(
+                np.unique(pairs_of(case), return_counts=True)[1]))
+
+
+def pairs_of(case):
+    return case['dst'].astype(np.int64) << 32 | case['src']

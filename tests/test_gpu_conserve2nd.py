@@ -283,7 +283,10 @@ def _moments_of(m, side):
     return weights.cell_moments(np.radians(yv), np.radians(xv), count)
 
 
-def check_map(m2, m1, name, conservation_bound=1e-12, covered_only=False):
+def check_map(m2, m1, name, conservation_bound=1e-12, covered_only=False,
+              covered=None):
+    """``covered``: the source cells conservation is held over, where that is
+    not all of them or (``covered_only``) those with ``frac_a`` = 1."""
     row, col = m2.row.astype(np.int64) - 1, m2.col.astype(np.int64) - 1
     row1, col1 = m1.row.astype(np.int64) - 1, m1.col.astype(np.int64) - 1
     key = row << 32 | col
@@ -294,6 +297,8 @@ def check_map(m2, m1, name, conservation_bound=1e-12, covered_only=False):
     cols = np.bincount(col, weights=m2.S * m2.area_b[row], minlength=m2.n_a)
     full = m2.frac_a > 1.0 - 1e-9 if covered_only else \
         np.ones(m2.n_a, dtype=bool)
+    if covered is not None:
+        full = covered
     conservation = np.abs(cols / m2.area_a - 1.0)[full].max()
     Ma, Mb = _moments_of(m2, 'a'), _moments_of(m2, 'b')
     f_src = Ma @ FIELD / m2.area_a
