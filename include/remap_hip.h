@@ -202,7 +202,52 @@ enum {
      * Through remap_plan_apply the mode gives REMAP_ERR_UNSUPPORTED on a plan
      * that keeps long rows apart, as LAF does.  Signed weights (conserve2nd,
      * patch) are legal and give what the definition gives. */
-    REMAP_MODE_CLASSFRAC = 13
+    REMAP_MODE_CLASSFRAC = 13,
+    /* (14 and 15 are not assigned: "unknown mode") */
+    /* The cotangent of the division: the first step of the adjoint apply,
+     * which carries a cotangent G of a forward result y back to the field X
+     * (gX = dL/dX for G = dL/dy).  (Added enumerators of ABI 31: no existing
+     * caller changes, the version stays.)  S is the plan's CSR, (n_b, n_a); X
+     * the forward's field; G has the shape and layout of the forward's
+     * result; gX has the shape of X.
+     * 1. Cotangent of the division, T by destination element (i, b, k) --
+     *    these two modes; a masked element is a selection, not a product:
+     *   forward REMAP_MODE_RAW: T = G (no launch)
+     *   REMAP_MODE_COTAN_FRACB (forward REMAP_MODE_FRACB):
+     *   T = frac_b_i > 0 ? G / frac_b_i : +0.0
+     *   REMAP_MODE_COTAN_MASKED (forward REMAP_MODE_MASKED):
+     *   den starts at +0.0; for the entries j of row i, in CSR order,
+     *   den = den + S_j iff X[cell(col_j), b, k] is no NaN, each sum rounded
+     *   (the forward's own den)
+     *   T = den > threshold ? G / den : +0.0, one IEEE division
+     *   where the forward wrote NaN, G is not looked at, even if it is NaN
+     * 2. Transposed sum: REMAP_MODE_RAW applied with the canonical CSR of S^T
+     *    (within a source cell its entries in ascending destination row),
+     *    flags 0, exactly:
+     *   acc starts at +0.0; acc = acc + (S_ij * T_i), the product rounded, then
+     *   the sum; no FMA; an empty column gives +0.0
+     * 3. Missing sources (MASKED forward only):
+     *   gX = +0.0 where X is NaN
+     * The arguments are read in their own way:
+     *   A is S;
+     *   Y holds G on entry and T on exit: every element in rows [row_begin,
+     *   row_end) is read once and then written once, through the y_* strides;
+     *   X is the forward's field, read for NaN only: x_dtype F64 and F32 are
+     *   served, the x_* strides, x_src_fold and x_outer_stride are those of
+     *   the forward launch; REMAP_MODE_COTAN_FRACB does not read X and it may
+     *   be NULL (x_dtype and the x_* strides are still checked);
+     *   frac_b is used by REMAP_MODE_COTAN_FRACB only (REMAP_ERR_ARG if
+     *   NULL), threshold by REMAP_MODE_COTAN_MASKED only;
+     *   mask_out must be NULL (REMAP_ERR_ARG);
+     *   gate / gate_value are honoured: rows outside the range and a closed
+     *   gate leave Y untouched;
+     *   flags, tune, row_order and every attached schedule are ignored and the
+     *   modes pick their own launch (csrc/apply_cotangent.h).
+     * Through remap_plan_apply the modes give REMAP_ERR_UNSUPPORTED on a plan
+     * that keeps long rows apart, as REMAP_MODE_LAF does.  Signed weights and
+     * a negative threshold are legal and give what the definition gives. */
+    REMAP_MODE_COTAN_FRACB = 16,
+    REMAP_MODE_COTAN_MASKED = 17
 };
 
 enum {

@@ -37,25 +37,33 @@ inline int hip_fail(hipError_t err, const char *what)
     } while (0)
 
 // The modes of remap_apply_f64 and remap_plan_apply.  (The enumerators are
-// not contiguous: 4 to 7 and 12 are not assigned.)
+// not contiguous: 4 to 7, 12, 14 and 15 are not assigned.)
 inline bool is_rowstat_mode(int mode)
 {
     return mode >= REMAP_MODE_MIN && mode <= REMAP_MODE_MEDIAN;
 }
 
+// the cotangent of the division, the first step of the adjoint apply
+// (apply_cotangent.h)
+inline bool is_cotangent_mode(int mode)
+{
+    return mode == REMAP_MODE_COTAN_FRACB || mode == REMAP_MODE_COTAN_MASKED;
+}
+
 inline bool is_known_mode(int mode)
 {
     return (mode >= REMAP_MODE_RAW && mode <= REMAP_MODE_LAF) ||
-           is_rowstat_mode(mode) || mode == REMAP_MODE_CLASSFRAC;
+           is_rowstat_mode(mode) || mode == REMAP_MODE_CLASSFRAC ||
+           is_cotangent_mode(mode);
 }
 
 // the modes that are a row pass over ONE CSR and pick their own launch: no
 // schedule, no tune, no flags (apply_laf.h, apply_rowstat.h,
-// apply_classfrac.h)
+// apply_classfrac.h, apply_cotangent.h)
 inline bool is_rowpass_mode(int mode)
 {
     return mode == REMAP_MODE_LAF || is_rowstat_mode(mode) ||
-           mode == REMAP_MODE_CLASSFRAC;
+           mode == REMAP_MODE_CLASSFRAC || is_cotangent_mode(mode);
 }
 
 constexpr int kWave = 64;        // gfx950 wavefront

@@ -973,6 +973,11 @@ int remap_plan_apply(const remap_plan *plan, const remap_field *f,
                            "remap_plan_apply: REMAP_MODE_CLASSFRAC is not "
                            "served by a plan that keeps %lld long rows apart",
                            (long long)plan->n_long);
+    if (remap::is_cotangent_mode(f->mode) && plan->n_long != 0)
+        return remap::fail(REMAP_ERR_UNSUPPORTED,
+                           "remap_plan_apply: mode %d (a cotangent) is not "
+                           "served by a plan that keeps %lld long rows apart",
+                           f->mode, (long long)plan->n_long);
     // A launch goes to the calling thread's current device; the plan's
     // arrays (and the stream, X and Y the caller passes) belong to the device
     // the plan was created on.  Refuse instead of launching against another
@@ -1009,7 +1014,9 @@ int remap_plan_apply(const remap_plan *plan, const remap_field *f,
     a.y_batch_stride = f->y_batch_stride;
     a.n_batch = f->n_batch;
     a.k_inner = f->k_inner;
-    a.frac_b = f->mode == REMAP_MODE_FRACB ? plan->frac_b : nullptr;
+    a.frac_b = f->mode == REMAP_MODE_FRACB ||
+                       f->mode == REMAP_MODE_COTAN_FRACB
+                   ? plan->frac_b : nullptr;
     a.threshold = f->threshold;
     a.mask_out = f->mask_out;
     a.gate = f->gate;

@@ -43,6 +43,7 @@
 
 #include "remap_common.h"
 #include "apply_classfrac.h"
+#include "apply_cotangent.h"
 #include "apply_laf.h"
 #include "apply_rowstat.h"
 
@@ -567,7 +568,9 @@ int check_args(const remap_apply_args *a, Call &c)
         c.K = 0;
         return REMAP_OK;  // empty output: nothing to launch
     }
-    if (!A.rowptr || !a->Y || (!a->X && A.n_cols > 0))
+    // (REMAP_MODE_COTAN_FRACB does not read X)
+    if (!A.rowptr || !a->Y ||
+        (!a->X && A.n_cols > 0 && a->mode != REMAP_MODE_COTAN_FRACB))
         return fail(REMAP_ERR_ARG, "remap_apply_f64: NULL device pointer");
     if (A.nnz > 0 && (!A.col || !A.val))
         return fail(REMAP_ERR_ARG, "remap_apply_f64: NULL col/val");
@@ -1590,6 +1593,9 @@ int apply(const remap_apply_args *a, hipStream_t stream)
     // ... and the class and bin area fractions (apply_classfrac.h)
     if (a->mode == REMAP_MODE_CLASSFRAC)
         return classfrac::apply(a, stream);
+    // ... and the cotangent of the division (apply_cotangent.h)
+    if (is_cotangent_mode(a->mode))
+        return cotangent::apply(a, stream);
     // a preferred family that cannot serve this call gives way to the
     // automatic choice instead of failing
     remap_apply_args relaxed;

@@ -1,7 +1,7 @@
 // rowpass.h -- what the passes that walk the rows of the plan's CSR beside
 // the SpMM apply share (remap_limit.hip, remap_sgs.hip, remap_vector.hip,
-// remap_levels.hip, remap_layers.hip, and apply_laf.h, apply_rowstat.h and
-// apply_classfrac.h, the
+// remap_levels.hip, remap_layers.hip, and apply_laf.h, apply_rowstat.h,
+// apply_classfrac.h and apply_cotangent.h, the
 // modes of the apply itself that are such passes): the checks of their
 // argument structs, the addressing of a source cell, the packed loads and
 // stores, and the work list of the rowwave form.  A pass comes in two forms

@@ -41,6 +41,10 @@ MODE_VAR = 10
 MODE_MEDIAN = 11
 # class and bin area fractions (pyremap_amd.classfrac); 12 is not assigned
 MODE_CLASSFRAC = 13
+# the cotangent of the division, the first step of the adjoint apply
+# (pyremap_amd.adjoint; cotangent_strided); 14 and 15 are not assigned
+MODE_COTAN_FRACB = 16
+MODE_COTAN_MASKED = 17
 #: the modes that are a row pass over the plan's own CSR: no schedule, no
 #: tune, no split, one device; what an error message calls each
 _ROW_PASS_MODES = {MODE_LAF: 'largest area fraction',
@@ -1257,6 +1261,49 @@ class RemapPlan:
         return (self.rowptr.cpu().numpy(), self.col.cpu().numpy(),
                 self.val.cpu().numpy())
 
+    def transposed(self):
+        """
+        The plan of ``S^T``, ``(n_a, n_b)``, built on the device once and kept
+        (:meth:`release_transposed` drops it): the triplets of this plan's CSR
+        with row and column swapped through the COO -> CSR sort a mapping file
+        takes, so inside a source cell the entries are in ascending destination
+        row (:func:`pyremap_amd.adjoint.transpose` is the same statement in
+        numpy).  Its ``frac_b`` is ones: it is applied in ``MODE_RAW``
+        (:func:`remap_tensor_adjoint`).  Rows that hold a large share of the
+        entries -- the source cells of a coarse -> fine map -- are kept apart
+        as in any plan (:meth:`_split_long_rows`); no destination grid is
+        known for it, so no other schedule is attached.  The build allocates
+        and reads counts back: make it before capturing launches in a
+        hipGraph.
+        """
+        hit = self.__dict__.get('_transposed')
+        if hit is not None:
+            return hit
+        torch = _torch()
+        _one_device(self, 'the transposed plan')
+        if self.n_b != self.n_b_global:
+            raise NotImplementedError(
+                'the transposed plan of a row shard holds part of every sum: '
+                'not with a sharded plan')
+        _holds_csr(self, ('rowptr', 'col', 'val'),
+                   'the transposed plan is sorted from its triplets')
+        with torch.cuda.device(self.device):
+            row = torch.repeat_interleave(
+                torch.arange(self.n_b, dtype=torch.int32, device=self.device),
+                self.rowptr[1:] - self.rowptr[:-1], output_size=self.nnz)
+            t = RemapPlan.from_triplets(
+                row=self.col, col=row, S=self.val,
+                frac_b=torch.ones(self.n_a, dtype=torch.float64,
+                                  device=self.device),
+                n_a=self.n_b, n_b=self.n_a, index_base=0, device=self.device)
+            t._split = t._split_long_rows()
+        self._transposed = t
+        return t
+
+    def release_transposed(self):
+        """Drop the plan :meth:`transposed` keeps (its device memory)."""
+        self._transposed = None
+
 
 # ---------------------------------------------------------------------------
 # launches
@@ -1362,6 +1409,9 @@ def apply_strided(plan, X, Y, *, n_batch, k_inner, x_row_stride,
     """
     torch = _torch()
     lib = load_library()
+    if mode in (MODE_COTAN_FRACB, MODE_COTAN_MASKED):
+        raise ValueError('the cotangent modes read their arguments in their '
+                         'own way: cotangent_strided launches them')
     if mode in _ROW_PASS_MODES:
         _one_device(plan, _ROW_PASS_MODES[mode])
     if X.device != plan.device or Y.device != plan.device:
@@ -1608,6 +1658,74 @@ def _row_pass(args_type, entry, plan, reads, sources, results, own,
     for name, value in own.items():
         setattr(args, name, value)
     _launch(torch, plan, getattr(lib, entry), entry, args)
+
+
+def cotangent_strided(plan, X, Y, *, mode, n_batch, k_inner, x_row_stride,
+                      x_batch_stride, y_row_stride, y_batch_stride,
+                      threshold=0.0, row_begin=0, row_end=None, gate=None,
+                      gate_value=0, x_src_fold=0, x_outer_stride=0):
+    """
+    One asynchronous launch of the cotangent of the division
+    (``MODE_COTAN_FRACB`` / ``MODE_COTAN_MASKED`` of ``remap_apply_f64``,
+    ``csrc/apply_cotangent.h``; :mod:`pyremap_amd.adjoint` has the definition
+    to the bit) on torch's current stream.  ``Y`` (float64) holds the
+    cotangent ``G`` of the forward's result on entry and ``T`` on exit,
+    addressed with the forward's ``y_*`` strides; ``X`` is the forward's
+    field (float64 or float32), read for NaN only with the forward's ``x_*``
+    strides -- ``MODE_COTAN_FRACB`` does not read it and takes ``None``.  A
+    row pass over the plan's own CSR: no schedule, no tune, one device; rows
+    outside ``[row_begin, row_end)`` and a closed ``gate`` leave ``Y``
+    untouched.
+    """
+    torch = _torch()
+    lib = load_library()
+    _one_device(plan, 'the cotangent of the division')
+    if mode not in (MODE_COTAN_FRACB, MODE_COTAN_MASKED):
+        raise ValueError(f'mode {mode} is no cotangent: expected '
+                         f'MODE_COTAN_FRACB or MODE_COTAN_MASKED')
+    masked = mode == MODE_COTAN_MASKED
+    if masked and X is None:
+        raise ValueError("MODE_COTAN_MASKED needs X, the forward's field")
+    if not masked:
+        X = None
+    for name, t in (('X', X), ('Y', Y)):
+        if t is not None and t.device != plan.device:
+            raise ValueError('X, Y and the plan must live on the same device')
+    if Y.dtype != torch.float64:
+        raise TypeError('Y must be float64')
+    x_dtype = DTYPE_F64 if X is None else _float_dtype(torch, 'X', X)
+    row_begin, end = _row_range(plan, row_begin, row_end)
+    if n_batch < 0 or k_inner < 0:
+        raise ValueError('n_batch and k_inner must not be negative')
+    if x_src_fold:
+        _check_fold(plan.n_a, x_src_fold, x_outer_stride)
+    _check_reach('X', X, plan.n_a, x_row_stride, x_batch_stride, 1, n_batch,
+                 k_inner, x_src_fold, x_outer_stride)
+    _check_reach('Y', Y, plan.n_b, y_row_stride, y_batch_stride, 1, n_batch,
+                 k_inner)
+    _holds_csr(plan, ('rowptr', 'col', 'val'),
+               "the cotangent adds a row's weights from it")
+    args = _ApplyArgs()
+    args.A = plan._csr_struct()
+    args.row_begin, args.row_end = row_begin, end
+    args.X = X.data_ptr() if X is not None else None
+    args.x_dtype, args.mode = x_dtype, mode
+    args.x_row_stride = int(x_row_stride)
+    args.x_batch_stride = int(x_batch_stride)
+    args.Y = Y.data_ptr()
+    args.y_row_stride = int(y_row_stride)
+    args.y_batch_stride = int(y_batch_stride)
+    args.n_batch, args.k_inner = int(n_batch), int(k_inner)
+    args.frac_b = None if masked else plan.frac_b.data_ptr()
+    args.threshold = float(threshold)
+    if gate is not None:
+        if gate.dtype != torch.int32 or gate.device != plan.device:
+            raise TypeError('gate must be an int32 tensor on the plan device')
+        args.gate = gate.data_ptr()
+        args.gate_value = int(gate_value)
+    args.x_src_fold = int(x_src_fold)
+    args.x_outer_stride = int(x_outer_stride)
+    _launch(torch, plan, lib.remap_apply_f64, 'remap_apply_f64', args)
 
 
 def check_limiter(limiter):
@@ -2830,6 +2948,184 @@ def remap_tensor_auto_mode(plan, dst_grid_dims, field, remap_axes, threshold,
     return limited(remap_tensor(
         plan, dst_grid_dims, X, remap_axes, MODE_FRACB, flags=flags, out=Y,
         gate=flag, gate_value=0))
+
+
+def _adjoint_field_shape(cot_shape, remap_axes, src_grid_dims, n_dst):
+    """The shape of the field whose result has ``cot_shape``: the source dims
+    at ``remap_axes``, the result's other dims, in their order, elsewhere."""
+    src = [int(d) for d in src_grid_dims]
+    if len(src) != len(remap_axes):
+        raise ValueError(f'src_grid_dims {src} and remap_axes '
+                         f'{list(remap_axes)} differ in length')
+    ndim = len(cot_shape) - n_dst + len(src)
+    if ndim < len(src):
+        raise ValueError(f'a cotangent of shape {tuple(cot_shape)} is no '
+                         f'result on {n_dst} destination dims')
+    axes = [int(a) % ndim for a in remap_axes]
+    lead = min(axes)
+    extras = iter(list(cot_shape[:lead]) + list(cot_shape[lead + n_dst:]))
+    return [src[axes.index(ax)] if ax in axes else int(next(extras))
+            for ax in range(ndim)]
+
+
+def _argsort(perm):
+    return sorted(range(len(perm)), key=perm.__getitem__)
+
+
+def _adjoint(plan, src_grid_dims, cotangent, remap_axes, field, passes,
+             dst_grid_dims, fill):
+    """What :func:`remap_tensor_adjoint` and its auto mode share.  ``passes``:
+    the cotangent launches as ``(mode, threshold, gate, gate_value)``."""
+    torch = _torch()
+    G = cotangent
+    if G.device != plan.device or (field is not None and
+                                   field.device != plan.device):
+        raise ValueError('the cotangent, the field and the plan must live on '
+                         'the same device')
+    if not G.dtype.is_floating_point:
+        raise TypeError(f'the cotangent must be floating point, not '
+                        f'{G.dtype}')
+    dst_shape = [plan.n_b] if dst_grid_dims is None else \
+        [int(d) for d in dst_grid_dims]
+    if field is not None:
+        shape = [int(s) for s in field.shape]
+        if field.dtype not in (torch.float64, torch.float32):
+            field = field.to(torch.float64)     # (as the forward read it)
+    else:
+        shape = _adjoint_field_shape(G.shape, remap_axes, src_grid_dims,
+                                     len(dst_shape))
+    axes, dst_shape = check_field_extents(
+        plan.n_a, plan.n_b, plan.n_b_global, dst_shape, shape, remap_axes)
+    if field is not None and src_grid_dims is not None and \
+            _prod(src_grid_dims) != plan.n_a:
+        raise ValueError(f'src_grid_dims {list(src_grid_dims)} do not hold '
+                         f'n_a = {plan.n_a} cells')
+    gated = any(p[2] is not None for p in passes)
+    lay = field_layout(plan, shape, axes, dst_shape, fold=not gated)
+    if tuple(G.shape) != tuple(lay.out_shape):
+        raise ValueError(
+            f'the cotangent has shape {tuple(G.shape)}; the result of a '
+            f'field of shape {tuple(shape)} has {tuple(lay.out_shape)}')
+    if gated and lay.route != 'direct':
+        raise ValueError('gated launches need the source axes adjacent '
+                         '(in-place addressing)')
+    tplan = plan.transposed()
+    # 1. G into the buffer the forward's launches wrote, float64
+    T = torch.empty(lay.y_shape, dtype=torch.float64, device=plan.device)
+    if lay.back is None:
+        T.copy_(G)
+    else:
+        back_shape, unpermute = lay.back
+        T.view(back_shape).copy_(G.permute(_argsort(unpermute)))
+    # 2. the cotangent of the division, in place, with the forward's strides
+    needs_x = any(p[0] == MODE_COTAN_MASKED for p in passes)
+    X = _launch_source(plan, lay, field, lay.strides['k_inner']) \
+        if needs_x else None
+    for Xl, Tl in _launch_rows(lay.n_launch, X, T):
+        for mode, threshold, gate, gate_value in passes:
+            cotangent_strided(plan, Xl, Tl, mode=mode, threshold=threshold,
+                              gate=gate, gate_value=gate_value, **lay.strides)
+    # 3. the transposed sum: MODE_RAW with S^T over the one axis of rows
+    if lay.route == 'direct':
+        lead = [shape[ax] for ax in lay.groups[0]]
+        tail = [shape[ax] for ax in lay.groups[2]]
+        Tv, axis = T.view(lead + [plan.n_b] + tail), len(lead)
+    elif lay.route == 'fold':
+        Tv, axis = T.view(lay.n_launch, plan.n_b, -1), 1
+    else:
+        Tv, axis = T, 0
+    gX = remap_tensor(tplan, None, Tv, [axis], MODE_RAW, flags=0)
+    # 4. into the field's shape
+    if lay.route == 'fold':
+        a0, a1 = axes
+        ny, nx = shape[a0], shape[a1]
+        M, Tt = lay.strides['n_batch'], lay.strides['k_inner']
+        gX = gX.view(lay.n_launch, ny, nx, M, Tt).permute(0, 1, 3, 2, 4)
+    elif lay.route == 'permute':
+        gX = gX.view([shape[ax] for ax in lay.order]).permute(
+            _argsort(lay.order))
+    gX = gX.reshape(shape).contiguous()
+    # 5. missing sources take nothing
+    if fill:
+        gX.masked_fill_(torch.isnan(field), 0.0)
+    return gX
+
+
+_COTAN_OF = {MODE_FRACB: MODE_COTAN_FRACB, MODE_MASKED: MODE_COTAN_MASKED}
+
+
+def remap_tensor_adjoint(plan, src_grid_dims, cotangent, remap_axes, mode,
+                         field=None, threshold=0.0, gate=None, gate_value=0,
+                         dst_grid_dims=None):
+    """
+    The adjoint of :func:`remap_tensor` in ``mode`` (``MODE_RAW``,
+    ``MODE_FRACB`` or ``MODE_MASKED``): ``gX = dL/dfield`` for the cotangent
+    ``dL/dy`` of its result, a float64 device tensor of the field's shape
+    (:mod:`pyremap_amd.adjoint` has the definition to the bit).
+
+    ``cotangent`` has the shape of the forward's result; ``remap_axes`` are
+    the forward's, the axes of the FIELD that hold the source grid, in place,
+    folded or permuted as the forward accepts them.  ``field`` is the
+    forward's field: required behind ``MODE_MASKED`` (read for NaN only),
+    else optional -- without it ``src_grid_dims`` (C order) says what
+    ``remap_axes`` hold.  ``dst_grid_dims``: the destination dims of the
+    forward (``None``: flat rows).
+
+    The cotangent is copied into a float64 buffer, divided in place by one
+    launch of ``csrc/apply_cotangent.h`` with the forward's own strides
+    (``gate`` / ``gate_value`` gate it, in-place layouts only; ``MODE_RAW``:
+    no launch), summed by ``remap_tensor(plan.transposed(), ..., MODE_RAW,
+    flags=0)`` and brought into the field's shape; behind ``MODE_MASKED``
+    ``+0.0`` is filled in where the field is NaN.  The first call builds
+    ``plan.transposed()``.  One device; no limiter has an adjoint.
+    """
+    _one_device(plan, 'the adjoint apply')
+    if mode not in (MODE_RAW, MODE_FRACB, MODE_MASKED):
+        raise ValueError(f'the adjoint apply serves MODE_RAW, MODE_FRACB and '
+                         f'MODE_MASKED, not mode {mode}')
+    if mode == MODE_MASKED and field is None:
+        raise ValueError("the adjoint of the masked mode needs the forward's "
+                         'field: its NaNs say what the forward divided by')
+    if field is None and src_grid_dims is None:
+        raise ValueError('give the field or src_grid_dims')
+    passes = [] if mode == MODE_RAW else \
+        [(_COTAN_OF[mode], threshold, gate, gate_value)]
+    return _adjoint(plan, src_grid_dims, cotangent, remap_axes, field, passes,
+                    dst_grid_dims, fill=mode == MODE_MASKED)
+
+
+def remap_tensor_adjoint_auto_mode(plan, src_grid_dims, cotangent, remap_axes,
+                                   field, threshold, dst_grid_dims=None,
+                                   flag=None):
+    """
+    The adjoint of :func:`remap_tensor_auto_mode`, with its branch and, like
+    it, without a host round trip: one scan of ``field`` into a flag, the
+    masked cotangent gated on a NaN found, the ``frac_b`` one on none, one
+    transposed sum, the fill.  A field whose source axes are not adjacent
+    decides with one readback, as the forward does.
+    """
+    torch = _torch()
+    _one_device(plan, 'the adjoint apply')
+    if field is None:
+        raise ValueError("the adjoint of the auto mode needs the forward's "
+                         'field')
+    if field.dtype not in (torch.float64, torch.float32):
+        field = field.to(torch.float64)
+    if not in_place_addressable(field.shape, remap_axes):
+        masked = bool(torch.isnan(field).any())
+        return remap_tensor_adjoint(
+            plan, src_grid_dims, cotangent, remap_axes,
+            MODE_MASKED if masked else MODE_FRACB, field=field,
+            threshold=threshold if masked else 0.0,
+            dst_grid_dims=dst_grid_dims)
+    X = field.contiguous()
+    if flag is None:
+        flag = torch.zeros(1, dtype=torch.int32, device=field.device)
+    scan_nan(X, flag)
+    passes = [(MODE_COTAN_MASKED, threshold, flag, 1),
+              (MODE_COTAN_FRACB, 0.0, flag, 0)]
+    return _adjoint(plan, src_grid_dims, cotangent, remap_axes, X, passes,
+                    dst_grid_dims, fill=True)
 
 
 def gather_rows(field, axis, rows, out=None):

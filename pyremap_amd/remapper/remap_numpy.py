@@ -1968,6 +1968,12 @@ def _remap_numpy_array(remapper, in_field, remap_axes,
     dst_grid_dims = remapper._ds_map.dst_grid_dims
     remap_axes = [int(a) for a in remap_axes]
 
+    if isinstance(in_field, torch.Tensor) and in_field.requires_grad and \
+            torch.is_grad_enabled():
+        # a gradient is asked for: the same calls, recorded for autograd
+        return _remap_with_grad(remapper, in_field, remap_axes,
+                                renormalization_threshold, limiter)
+
     if getattr(remapper, '_process_group', None) is not None:
         # collective: rank src's data, every rank gets the full result
         is_ma = isinstance(in_field, np.ma.MaskedArray)
@@ -2024,3 +2030,126 @@ def _remap_numpy_array(remapper, in_field, remap_axes,
         want_mask=True, flags=remapper.engine_flags,
         host_mask=host_mask, **limit).result()
     return np.ma.masked_array(out, mask=mask)
+
+
+# ---------------------------------------------------------------------------
+# the adjoint of remap_array (pyremap_amd.adjoint; engine.remap_tensor_adjoint)
+# ---------------------------------------------------------------------------
+
+def _refuse_no_adjoint(remapper, limiter):
+    """What has no adjoint here: several devices, a process group, a
+    limiter."""
+    if getattr(remapper, '_process_group', None) is not None or \
+            hasattr(remapper._matrix, 'shards'):
+        raise NotImplementedError(
+            'the adjoint apply serves one device: not with a multi-device '
+            'or process-group Remapper')
+    if limiter is not None:
+        raise NotImplementedError(
+            f'no gradient passes through a limiter ({limiter!r}): its clamp '
+            f'has no adjoint here; remap without it where a gradient is '
+            f'required')
+
+
+def _adjoint_tensor(remapper, cotangent, remap_axes, field, src_dims,
+                    threshold):
+    """The branch ``_remap_numpy_array`` takes for a device tensor, backwards:
+    ``frac_b`` without a threshold, the device-side auto mode with one."""
+    plan = remapper._matrix
+    dst_grid_dims = remapper._ds_map.dst_grid_dims
+    cotangent = cotangent.to(plan.device)
+    if field is not None:
+        field = field.to(plan.device)
+    if threshold is None:
+        return engine.remap_tensor_adjoint(
+            plan, src_dims, cotangent, remap_axes, engine.MODE_FRACB,
+            field=field, dst_grid_dims=dst_grid_dims)
+    return engine.remap_tensor_adjoint_auto_mode(
+        plan, src_dims, cotangent, remap_axes, field, threshold,
+        dst_grid_dims=dst_grid_dims)
+
+
+@functools.lru_cache(maxsize=None)
+def _remap_function():
+    """The ``torch.autograd.Function`` of ``remap_array`` (made on first use:
+    torch is imported late everywhere in this package)."""
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    class RemapArray(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, field, remapper, remap_axes, threshold):
+            ctx.remapper, ctx.remap_axes = remapper, remap_axes
+            ctx.threshold = threshold
+            ctx.like = (tuple(field.shape), field.dtype, field.device)
+            if threshold is not None:
+                # (its NaNs say what the forward divided by)
+                ctx.save_for_backward(field)
+            # the calls of a field that asks for no gradient: the same bytes
+            return _remap_numpy_array(remapper, field.detach(), remap_axes,
+                                      threshold)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, cotangent):
+            shape, dtype, device = ctx.like
+            field = ctx.saved_tensors[0] if ctx.threshold is not None \
+                else None
+            src_dims = [shape[ax] for ax in ctx.remap_axes]
+            gX = _adjoint_tensor(ctx.remapper, cotangent, ctx.remap_axes,
+                                 field, src_dims, ctx.threshold)
+            # (a float32 field: its float64 gradient rounded once)
+            return gX.to(device=device, dtype=dtype), None, None, None
+
+    return RemapArray
+
+
+def _remap_with_grad(remapper, in_field, remap_axes, threshold, limiter):
+    _refuse_no_adjoint(remapper, limiter)
+    return _remap_function().apply(in_field, remapper, remap_axes, threshold)
+
+
+def _remap_array_adjoint(remapper, cotangent, remap_axes, field, threshold):
+    """
+    ``Remapper.remap_array_adjoint``: the gradient with respect to the field
+    of ``remap_array`` for the cotangent of its result, by the branch
+    ``remap_array`` takes.  Device tensors in -> float64 device tensor out;
+    numpy in -> float64 ``numpy.ndarray`` out (masked mode iff ``field`` is a
+    MaskedArray and a threshold is given, the mask burnt in as NaN).
+    """
+    torch = engine.require_gpu()
+    _refuse_no_adjoint(remapper, _check_limiter(remapper))
+    if threshold is not None and field is None:
+        raise ValueError('field is required when a renormalization_threshold '
+                         'is given: its missing values say what the forward '
+                         'divided by')
+    plan = remapper._matrix
+    remap_axes = [int(a) for a in remap_axes]
+    src_dims = remapper._ds_map.src_grid_dims if field is None else \
+        [field.shape[ax] for ax in remap_axes]
+    if isinstance(cotangent, torch.Tensor):
+        if field is not None and not isinstance(field, torch.Tensor):
+            raise TypeError('a device cotangent goes with a device field')
+        return _adjoint_tensor(remapper, cotangent, remap_axes, field,
+                               src_dims, threshold)
+    if isinstance(field, torch.Tensor):
+        raise TypeError('a host cotangent goes with a host field')
+
+    def upload(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(plan.device)
+    G = upload(np.asarray(np.ma.getdata(cotangent), dtype=np.float64))
+    masked = isinstance(field, np.ma.MaskedArray) and threshold is not None
+    X = None
+    if field is not None:
+        data = np.ma.getdata(field)
+        if data.dtype not in (np.float64, np.float32):
+            data = data.astype(np.float64)
+        if masked:
+            data = np.where(np.ma.getmaskarray(field), np.nan, data)
+        X = upload(data)
+    gX = engine.remap_tensor_adjoint(
+        plan, src_dims, G, remap_axes,
+        engine.MODE_MASKED if masked else engine.MODE_FRACB, field=X,
+        threshold=threshold if masked else 0.0,
+        dst_grid_dims=remapper._ds_map.dst_grid_dims)
+    return gX.cpu().numpy()

@@ -22,6 +22,7 @@ from pyremap_amd.remapper.remap_numpy import (
     _remap_array_laf,
     _remap_array_layers,
     _remap_array_levels,
+    _remap_array_adjoint,
     _remap_array_sgs,
     _remap_array_stat,
     _remap_array_fractions,
@@ -534,6 +535,14 @@ class Remapper:
         the bounds cannot hold the mass, every value ends on its bound and
         the integral is not reached).  Host arrays then take the whole-array
         route: upload, remap, download.
+
+        Differentiable.  A device tensor with ``requires_grad=True``, under
+        grad mode, comes back with a ``grad_fn``: the forward makes the same
+        calls (the bytes of the result do not change) and the backward is the
+        adjoint apply (:meth:`remap_array_adjoint`; once differentiable; a
+        float32 field gets its float64 gradient rounded once).  With a
+        ``limiter``, several devices or a process group that is a
+        ``NotImplementedError``.  Every other call is untouched.
         """
         if self.map_filename is None:
             raise ValueError('No mapping file has been defined')
@@ -541,6 +550,31 @@ class Remapper:
         _load_mapping(self, limiter=limiter)
         return _remap_numpy_array(self, field, remap_axes,
                                   renormalization_threshold, limiter=limiter)
+
+    def remap_array_adjoint(self, cotangent, remap_axes, field=None,
+                            renormalization_threshold=None):
+        """
+        The adjoint of :meth:`remap_array`: the gradient ``dL/dfield`` for
+        ``cotangent = dL/dy`` of its result ``y``, in the field's shape
+        (:mod:`pyremap_amd.adjoint` has the definition to the bit): the
+        cotangent divided by what the forward divided by, where it divided,
+        in one launch of new HIP; the transposed sum through the apply
+        kernels on the plan of the transposed map, built on the device on
+        first use; ``+0.0`` where a masked forward found the field missing.
+
+        ``remap_axes`` are the FORWARD's: the axes of the field that hold the
+        source grid.  The branch is chosen as :meth:`remap_array` chooses it:
+        without a threshold the ``frac_b`` one; with one, ``field`` -- the
+        forward's field -- is required, a device tensor decides by its NaNs on
+        the device, a ``numpy.ma.MaskedArray`` takes the masked branch.
+        Device tensors in -> float64 device tensor out; numpy in -> float64
+        ``numpy.ndarray`` out.  One device, no limiter.
+        """
+        if self.map_filename is None:
+            raise ValueError('No mapping file has been defined')
+        _load_mapping(self)
+        return _remap_array_adjoint(self, cotangent, remap_axes, field,
+                                    renormalization_threshold)
 
     def remap_array_sgs(self, field, sgs_frac, remap_axes,
                         renormalization_threshold=None):
@@ -558,6 +592,9 @@ class Remapper:
         ``renormalization_threshold`` (``None``: 0.0) or the remapped
         fraction is not positive -- which a map with signed weights
         (``conserve2nd``, ``patch``) can give next to the ice edge.
+
+        No gradient passes: the result is detached from ``field`` and
+        ``sgs_frac`` (only :meth:`remap_array` is differentiable).
         """
         if self.map_filename is None:
             raise ValueError('No mapping file has been defined')
@@ -584,6 +621,9 @@ class Remapper:
         (``None``: 0.0).  The directions come from the cell centres ``xc_a,
         yc_a, xc_b, yc_b`` of the mapping file (``ValueError`` if it has
         none).
+
+        No gradient passes: the results are detached from ``u`` and ``v``
+        (only :meth:`remap_array` is differentiable).
         """
         if self.map_filename is None:
             raise ValueError('No mapping file has been defined')
@@ -620,6 +660,9 @@ class Remapper:
         axis at the field's extent or 1 (a time-invariant coordinate).  A
         destination cell is masked where the valid weight is not above
         ``renormalization_threshold`` (``None``: 0.0).
+
+        No gradient passes: the result is detached from its inputs (only
+        :meth:`remap_array` is differentiable).
         """
         if self.map_filename is None:
             raise ValueError('No mapping file has been defined')
@@ -657,6 +700,9 @@ class Remapper:
         extent or 1 (a time-invariant thickness).  A destination cell is
         masked where the valid weight is not above
         ``renormalization_threshold`` (``None``: 0.0).
+
+        No gradient passes: the result is detached from its inputs (only
+        :meth:`remap_array` is differentiable).
         """
         if self.map_filename is None:
             raise ValueError('No mapping file has been defined')
@@ -686,7 +732,8 @@ class Remapper:
         is a ``ValueError``.  A destination cell is masked where its row
         holds no value or the valid weight is not above
         ``renormalization_threshold`` (``None``: 0.0).  One device; never
-        limited.
+        limited; no gradient passes (the result is detached: a label has no
+        derivative).
         """
         if self.map_filename is None:
             raise ValueError('No mapping file has been defined')
@@ -711,7 +758,8 @@ class Remapper:
 
         NaN in the field is missing.  A destination cell is masked where its
         row holds no value or the valid weight is not above ``threshold``
-        (``None``: 0.0).  One device; never limited.
+        (``None``: 0.0).  One device; never limited; no gradient passes (the
+        result is detached from ``field``).
         """
         if self.map_filename is None:
             raise ValueError('No mapping file has been defined')
@@ -744,7 +792,8 @@ class Remapper:
         lies outside the bins, counts in the denominator only: the fractions
         of such a cell add up to less than 1.  A destination cell is masked
         where the valid weight is not above ``renormalization_threshold``
-        (``None``: 0.0).  One device; never limited.
+        (``None``: 0.0).  One device; never limited; no gradient passes (the
+        result is detached from ``field``).
         """
         if self.map_filename is None:
             raise ValueError('No mapping file has been defined')
