@@ -247,7 +247,49 @@ enum {
      * that keeps long rows apart, as REMAP_MODE_LAF does.  Signed weights and
      * a negative threshold are legal and give what the definition gives. */
     REMAP_MODE_COTAN_FRACB = 16,
-    REMAP_MODE_COTAN_MASKED = 17
+    REMAP_MODE_COTAN_MASKED = 17,
+    /* (18 and 19 are not assigned: "unknown mode") */
+    /* One pass of a creeping fill: missing cells of a field take values from
+     * their valid neighbours on the SAME grid (compass' extrap_woa, CDO's
+     * fillmiss / setmisstonn, ESMF's --extrap_method creep); repeated by the
+     * caller between two buffers until nothing fillable is left, one more
+     * ring of cells per pass.  (Added enumerators of ABI 31: no existing
+     * caller changes, the version stays.)
+     * The arguments are read in their own way:
+     *   A is the neighbour matrix of the grid: square (REMAP_ERR_ARG
+     *   otherwise), row i holding the neighbours of cell i and their weights,
+     *   no diagonal entry needed;
+     *   X is a field on that grid, Y the filled field; Y must not be X: equal
+     *   pointers give REMAP_ERR_ARG.
+     * For element (i, b, k), with x_i = (double) X[cell(i), b, k]:
+     *   x_i is no NaN: y = x_i (a copy: float32 widens exactly), mask 0
+     *   x_i is NaN: the entries j of row i are walked in CSR order (ascending col)
+     *     x_j = (double) X[cell(col_j), b, k]
+     *     an entry counts iff x_j is no NaN; +-inf are values like any other
+     *   FILL_BEST: the first counted entry sets best = S_j, v = x_j; a later one
+     *     replaces both iff S_j > best (strict: the lowest col wins a tie, a NaN
+     *     S_j never replaces)
+     *     y = some entry counts ? v : NaN
+     *   FILL_MEAN: num and den start at +0.0; for every counted entry, in CSR order,
+     *     num = num + (S_j * x_j), den = den + S_j, the product rounded, then each
+     *     sum; no FMA contraction
+     *     y = den > threshold ? num / den : NaN, one IEEE division
+     * Every NaN written is 0x7ff8000000000000; mask_out, where given, gets 1 where
+     * NaN was written and 0 elsewhere.  Only X is read: no value written by this
+     * launch is looked at.
+     * The arguments are otherwise read as in REMAP_MODE_LAF: flags, tune,
+     * frac_b, row_order and every attached schedule are ignored and the
+     * modes pick their own launch (csrc/apply_fill.h); gate / gate_value are
+     * honoured, rows outside [row_begin, row_end) are not written, x_dtype
+     * F64 and F32 are served, every stride, x_src_fold and x_outer_stride
+     * address cells as in the other modes, for the element's own cell too.
+     * threshold is used by FILL_MEAN only.  Through remap_plan_apply the
+     * modes give REMAP_ERR_UNSUPPORTED on a plan that keeps long rows apart.
+     * With non-negative weights FILL_MEAN at a missing element is byte for
+     * byte REMAP_MODE_MASKED of the same matrix, field and threshold: the
+     * whole pass is where(isnan(X), masked apply, X). */
+    REMAP_MODE_FILL_BEST = 20,
+    REMAP_MODE_FILL_MEAN = 21
 };
 
 enum {

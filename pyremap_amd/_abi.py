@@ -8,6 +8,11 @@ the two together (every parameter's class, every member's offset).
 import ctypes
 from ctypes import POINTER
 
+#: REMAP_MODE_FILL_BEST / REMAP_MODE_FILL_MEAN: one pass of a creeping fill
+#: (``pyremap_amd.engine`` holds the other modes by their numbers)
+MODE_FILL_BEST = 20
+MODE_FILL_MEAN = 21
+
 
 class _CSR(ctypes.Structure):
     _fields_ = [

@@ -50,20 +50,27 @@ inline bool is_cotangent_mode(int mode)
     return mode == REMAP_MODE_COTAN_FRACB || mode == REMAP_MODE_COTAN_MASKED;
 }
 
+// one pass of a creeping fill over a grid's neighbour matrix (apply_fill.h)
+inline bool is_fill_mode(int mode)
+{
+    return mode == REMAP_MODE_FILL_BEST || mode == REMAP_MODE_FILL_MEAN;
+}
+
 inline bool is_known_mode(int mode)
 {
     return (mode >= REMAP_MODE_RAW && mode <= REMAP_MODE_LAF) ||
            is_rowstat_mode(mode) || mode == REMAP_MODE_CLASSFRAC ||
-           is_cotangent_mode(mode);
+           is_cotangent_mode(mode) || is_fill_mode(mode);
 }
 
 // the modes that are a row pass over ONE CSR and pick their own launch: no
 // schedule, no tune, no flags (apply_laf.h, apply_rowstat.h,
-// apply_classfrac.h, apply_cotangent.h)
+// apply_classfrac.h, apply_cotangent.h, apply_fill.h)
 inline bool is_rowpass_mode(int mode)
 {
     return mode == REMAP_MODE_LAF || is_rowstat_mode(mode) ||
-           mode == REMAP_MODE_CLASSFRAC || is_cotangent_mode(mode);
+           mode == REMAP_MODE_CLASSFRAC || is_cotangent_mode(mode) ||
+           is_fill_mode(mode);
 }
 
 constexpr int kWave = 64;        // gfx950 wavefront

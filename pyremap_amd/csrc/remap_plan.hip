@@ -978,6 +978,11 @@ int remap_plan_apply(const remap_plan *plan, const remap_field *f,
                            "remap_plan_apply: mode %d (a cotangent) is not "
                            "served by a plan that keeps %lld long rows apart",
                            f->mode, (long long)plan->n_long);
+    if (remap::is_fill_mode(f->mode) && plan->n_long != 0)
+        return remap::fail(REMAP_ERR_UNSUPPORTED,
+                           "remap_plan_apply: mode %d (a fill) is not served "
+                           "by a plan that keeps %lld long rows apart",
+                           f->mode, (long long)plan->n_long);
     // A launch goes to the calling thread's current device; the plan's
     // arrays (and the stream, X and Y the caller passes) belong to the device
     // the plan was created on.  Refuse instead of launching against another

@@ -44,6 +44,7 @@
 #include "remap_common.h"
 #include "apply_classfrac.h"
 #include "apply_cotangent.h"
+#include "apply_fill.h"
 #include "apply_laf.h"
 #include "apply_rowstat.h"
 
@@ -1596,6 +1597,9 @@ int apply(const remap_apply_args *a, hipStream_t stream)
     // ... and the cotangent of the division (apply_cotangent.h)
     if (is_cotangent_mode(a->mode))
         return cotangent::apply(a, stream);
+    // ... and a pass of the creeping fill (apply_fill.h)
+    if (is_fill_mode(a->mode))
+        return fill::apply(a, stream);
     // a preferred family that cannot serve this call gives way to the
     // automatic choice instead of failing
     remap_apply_args relaxed;

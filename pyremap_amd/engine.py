@@ -45,13 +45,22 @@ MODE_CLASSFRAC = 13
 # (pyremap_amd.adjoint; cotangent_strided); 14 and 15 are not assigned
 MODE_COTAN_FRACB = 16
 MODE_COTAN_MASKED = 17
+# one pass of a creeping fill over a grid's neighbour plan (pyremap_amd.fill;
+# fill_tensor repeats it); 18 and 19 are not assigned
+MODE_FILL_BEST = _abi.MODE_FILL_BEST
+MODE_FILL_MEAN = _abi.MODE_FILL_MEAN
 #: the modes that are a row pass over the plan's own CSR: no schedule, no
 #: tune, no split, one device; what an error message calls each
 _ROW_PASS_MODES = {MODE_LAF: 'largest area fraction',
                    MODE_MIN: 'a row statistic', MODE_MAX: 'a row statistic',
                    MODE_VAR: 'a row statistic',
                    MODE_MEDIAN: 'a row statistic',
-                   MODE_CLASSFRAC: 'class fractions'}
+                   MODE_CLASSFRAC: 'class fractions',
+                   MODE_FILL_BEST: 'a fill', MODE_FILL_MEAN: 'a fill'}
+#: what ``method=`` of a fill accepts (fill_tensor, Remapper.fill)
+FILL_METHODS = {'nearest': MODE_FILL_BEST, 'mean': MODE_FILL_MEAN}
+#: passes fill_tensor launches between two looks at the missing count
+FILL_CHECK_EVERY = 4
 
 FLAG_FMA = 1
 FLAG_TUNE_HINT = 4
@@ -2453,6 +2462,131 @@ def remap_tensor_fractions(plan, dst_grid_dims, labels, n_classes, remap_axes,
         if mask is not None:
             mask = mask.reshape([C] + list(shape)).permute(order).contiguous()
     return (Y, mask) if want_mask else Y
+
+
+def fill_tensor(plan, field, axes, method='nearest', passes=None,
+                threshold=0.0, info=None):
+    """
+    Fill the missing (NaN) elements of ``field`` from their valid neighbours
+    (:mod:`pyremap_amd.fill` has the definition to the bit): ``plan`` is the
+    neighbour plan of ONE grid (``RemapPlan.from_triplets`` of
+    :func:`pyremap_amd.fill.neighbour_graph`; square), ``field`` a float64 or
+    float32 device tensor whose axes ``axes`` hold that grid.  Returns a new
+    float64 tensor of the field's shape, detached from it.
+
+    ``method``: ``'nearest'`` (``MODE_FILL_BEST``: the value of the valid
+    neighbour with the largest weight; only values the field holds come out)
+    or ``'mean'`` (``MODE_FILL_MEAN``: the weighted mean of the valid
+    neighbours, ``threshold`` on their weight).  One pass fills one ring of
+    cells; the pass is repeated between two buffers, the first one reading
+    the field as it is (float32 too), every later one the float64 result.
+
+    ``passes=k`` makes exactly ``k`` launches and never synchronises.
+    ``passes=None`` repeats until a pass leaves the number of missing
+    elements unchanged, zero included.  The count comes from the launch's
+    ``mask_out`` and reading it back is the only synchronisation.  A pass
+    that fills nothing is the identity, so the count is looked at only every
+    ``FILL_CHECK_EVERY`` passes, and the result is still the one defined by
+    "repeat until nothing changes": the passes launched beyond the last one
+    that filled something change no byte.  A component of the graph with no
+    valid value in some column stays NaN there.
+
+    Axes that are adjacent and ascending are addressed in place: the dims in
+    front are the batches of the launch, the dims behind its contiguous run.
+    Any other order is permuted to ``(n, K)`` first and back afterwards.
+    ``info``: a dict that receives ``passes`` (launches made) and, with
+    ``passes=None``, ``missing`` (elements left).  One device.
+    """
+    from pyremap_amd import fill as fill_statement
+    torch = _torch()
+    _one_device(plan, _ROW_PASS_MODES[MODE_FILL_BEST])
+    mode = FILL_METHODS[fill_statement.check_method(method)]
+    passes = fill_statement.check_passes(passes)
+    if plan.n_a != plan.n_b:
+        raise ValueError(f'a fill needs the neighbour plan of one grid, and '
+                         f'a ({plan.n_b}, {plan.n_a}) plan is not square')
+    n = plan.n_b
+    if not isinstance(field, torch.Tensor):
+        raise TypeError('field must be a tensor (pyremap_amd.fill has the '
+                        'numpy twin)')
+    field = field.detach()
+    if field.device != plan.device:
+        raise ValueError('the field and the plan must live on the same '
+                         'device')
+    shape = [int(s) for s in field.shape]
+    axes = [int(ax) + len(shape) if int(ax) < 0 else int(ax) for ax in axes]
+    if not axes or len(set(axes)) != len(axes) or \
+            any(ax < 0 or ax >= len(shape) for ax in axes):
+        raise ValueError(f'axes {axes} are no distinct axes of a field of '
+                         f'shape {tuple(shape)}')
+    cells = 1
+    for ax in axes:
+        cells *= shape[ax]
+    if cells != n:
+        raise ValueError(f'the axes {axes} of a field of shape '
+                         f'{tuple(shape)} hold {cells} cells, the grid of the '
+                         f'neighbour plan {n}')
+    if field.dtype not in (torch.float64, torch.float32):
+        field = field.to(torch.float64)
+    direct = axes == list(range(axes[0], axes[0] + len(axes)))
+    if direct:
+        X = field.contiguous()
+        B = 1
+        for s in shape[:axes[0]]:
+            B *= s
+        k = 1
+        for s in shape[axes[-1] + 1:]:
+            k *= s
+        back = None
+    else:
+        others = [ax for ax in range(len(shape)) if ax not in axes]
+        order = axes + others
+        X = field.permute(order).contiguous()
+        B, k = 1, X.numel() // n if n else 0
+        back = (list(X.shape), [order.index(ax) for ax in range(len(shape))])
+    if info is not None:
+        info['passes'] = 0
+    out = None
+    if X.numel() and (passes is None or passes > 0):
+        strides = dict(n_batch=B, k_inner=k, x_row_stride=k,
+                       x_batch_stride=n * k, y_row_stride=k,
+                       y_batch_stride=n * k, mode=mode, threshold=threshold)
+        flat = X.reshape(-1)
+        bufs = [torch.empty(flat.numel(), dtype=torch.float64,
+                            device=plan.device) for _ in
+                range(1 if passes == 1 else 2)]
+        mask = torch.empty(flat.numel(), dtype=torch.uint8,
+                           device=plan.device) if passes is None else None
+        cur, done = flat, 0
+        while passes is None or done < passes:
+            group = FILL_CHECK_EVERY if passes is None else passes - done
+            counts = []
+            for g in range(group):
+                nxt = bufs[done % len(bufs)]
+                apply_strided(plan, cur, nxt, mask_out=mask, **strides)
+                cur, done = nxt, done + 1
+                if mask is not None and g >= group - 2:
+                    counts.append(mask.sum(dtype=torch.int64))
+            if passes is not None:
+                break
+            before, after = (int(c) for c in torch.stack(counts).cpu())
+            if after == 0 or after == before:
+                if info is not None:
+                    info['missing'] = after
+                break
+        out = cur
+        if info is not None:
+            info['passes'] = done
+    if out is None:
+        out = X.to(torch.float64).reshape(-1)
+        if out.data_ptr() == field.data_ptr():
+            out = out.clone()
+        if info is not None and passes is None:
+            info['missing'] = int(torch.isnan(out).sum())
+    out = out.reshape(X.shape)
+    if back is not None:
+        out = out.permute(back[1]).contiguous()
+    return out.reshape(shape)
 
 
 def _sgs_group(frac, shape, axes):

@@ -26,6 +26,7 @@ import numpy as np
 
 from pyremap_amd import (classfrac, engine, host_path, rowstat, vector,
                          xr_lite)
+from pyremap_amd import fill as fill_mod
 from pyremap_amd.io.mapfile import read_mapping
 
 try:  # real xarray is honoured when present; it is optional
@@ -1033,6 +1034,7 @@ def _remap_numpy(remapper, ds, renormalization_threshold):
         raise ValueError('No mapping file has been defined')
     # (before anything is loaded: a refusal or a missing fraction variable
     # costs nothing)
+    _check_fill(remapper)
     cat = _categorical(remapper, ds)
     stats = _statistics(remapper, ds)
     fracs = _fractions(remapper, ds)
@@ -1334,9 +1336,129 @@ def _lazy_dataset(remapper, ds, renormalization_threshold, sgs=None,
     return xr_lite.Dataset(results, attrs=ds.attrs)
 
 
+def _check_fill(remapper, fill=None):
+    """The fill of one call: the keyword if given, else the Remapper's
+    attribute ``fill``; ``None`` or ``(method, passes, dist_exponent)``
+    (:func:`pyremap_amd.fill.check_spec`).  The neighbour plan comes from
+    ``dst_descriptor``: a Remapper without one is a ``ValueError``."""
+    if fill is None:
+        fill = getattr(remapper, 'fill', None)
+    spec = fill_mod.check_spec(fill)
+    if spec is None:
+        return None
+    if getattr(remapper, 'dst_descriptor', None) is None:
+        raise ValueError(
+            'a fill walks the neighbour graph of the destination grid, which '
+            'is made from dst_descriptor, and this Remapper has none')
+    if getattr(remapper, '_process_group', None) is not None or \
+            len(getattr(remapper, 'devices', None) or ()) > 1:
+        raise NotImplementedError(
+            'a fill serves one device: not with devices=[...] or a process '
+            'group')
+    return spec
+
+
+def _fill_plan(remapper, dist_exponent):
+    """The neighbour plan of the destination grid
+    (:func:`pyremap_amd.fill.neighbour_plan`), built once per Remapper,
+    destination descriptor and exponent and kept, as
+    ``RemapPlan.transposed()`` is kept."""
+    engine.require_gpu()
+    kept = remapper.__dict__.setdefault('_fill_plans', {})
+    descriptor = remapper.dst_descriptor
+    key = (id(descriptor), float(dist_exponent))
+    if key not in kept or kept[key][0] is not descriptor:
+        device = getattr(getattr(remapper, '_matrix', None), 'device', None)
+        kept[key] = (descriptor, fill_mod.neighbour_plan(
+            descriptor, dist_exponent,
+            device=remapper.device if device is None else device))
+    return kept[key][1]
+
+
+def _fill_array(remapper, field, axes, spec, info=None):
+    """One array on the destination grid through ``engine.fill_tensor``:
+    device tensor in, float64 device tensor out; numpy or MaskedArray in (the
+    mask as NaN), ``numpy.ma.MaskedArray`` out with the mask taken from
+    NaN."""
+    torch = engine.require_gpu()
+    method, passes, dist_exponent = spec
+    plan = _fill_plan(remapper, dist_exponent)
+    axes = [int(a) for a in axes]
+    # (what the last fill did: the launches made and, where the count was
+    # read, the elements left)
+    info = remapper.fill_info = {} if info is None else info
+    if isinstance(field, torch.Tensor):
+        return engine.fill_tensor(plan, field.to(plan.device), axes, method,
+                                  passes, info=info)
+    out = engine.fill_tensor(plan, _host_values(torch, field, plan.device),
+                             axes, method, passes, info=info).cpu().numpy()
+    return np.ma.masked_array(out, mask=np.isnan(out))
+
+
+def _fill_result(remapper, out, first, spec):
+    """The result of ``remap_array`` filled over its destination axes, which
+    start at ``first``."""
+    axes = list(range(first, first + len(remapper._ds_map.dst_grid_dims)))
+    return _fill_array(remapper, out, axes, spec)
+
+
+def _fill_values(remapper, values, axes, spec, fill_value):
+    """The values of a remapped variable filled: floats as they are (NaN:
+    missing); integers -- a categorical variable -- as float64 with NaN where
+    they equal ``fill_value``, and back in their own type with ``fill_value``
+    where the fill could not reach."""
+    values = np.asarray(values)
+    if values.dtype.kind not in 'iu':
+        return np.asarray(_fill_array(remapper, values, axes, spec).data)
+    x = values.astype(np.float64)
+    if fill_value is not None:
+        x[values == fill_value] = np.nan
+    y = np.asarray(_fill_array(remapper, x, axes, spec).data)
+    left = np.isnan(y)
+    out = np.where(left, 0.0, y).astype(values.dtype)
+    if fill_value is not None:
+        out[left] = fill_value
+    return out
+
+
 def _start_data_array(da, remapper, renormalization_threshold,
                       keep_on_device=False, sgs=None, vec=None, lev=None,
                       cat=None):
+    """
+    :func:`_start_remap` and, with ``Remapper.fill``, the fill of its result
+    over the destination dims (:mod:`pyremap_amd.fill`): every remapped
+    variable, a ``levels`` or ``layers`` result over its own shape, a
+    categorical variable always with ``'nearest'`` and in its own type.  A
+    variable weighted by ``sgs_frac`` and the members of a vector pair are
+    left as they are.
+    """
+    finish = _start_remap(da, remapper, renormalization_threshold,
+                          keep_on_device=keep_on_device, sgs=sgs, vec=vec,
+                          lev=lev, cat=cat)
+    spec = _check_fill(remapper)
+    plan = None if spec is None else _plan_data_array(da, remapper, lev)
+    if plan is None or (vec is not None and da.name in vec) or \
+            (sgs is not None and sgs.weights(da)):
+        return finish
+    _, dims, coords = plan
+    axes = [dims.index(dim) for dim in remapper.dst_descriptor.dims]
+    if cat is not None and da.name in cat:
+        spec = ('nearest',) + tuple(spec[1:])
+    make = _array_class(da).from_dict
+
+    def filled():
+        out = finish()
+        attrs = out.attrs
+        return make({'coords': coords, 'attrs': attrs, 'dims': dims,
+                     'data': _fill_values(remapper, out.values, axes, spec,
+                                          attrs.get('_FillValue')),
+                     'name': out.name})
+    return filled
+
+
+def _start_remap(da, remapper, renormalization_threshold,
+                 keep_on_device=False, sgs=None, vec=None, lev=None,
+                 cat=None):
     """
     Enqueue the remap of one variable -- upload, NaN scan, launch, download,
     none of which waits for the host -- and return the function that waits
@@ -1451,11 +1573,12 @@ def _batches(remapper, ds, names):
     if getattr(remapper, '_process_group', None) is not None or \
             plan is None or hasattr(plan, 'shards') or \
             getattr(remapper, 'limiter', None) is not None or \
+            getattr(remapper, 'fill', None) is not None or \
             getattr(remapper, 'sgs_frac', None) is not None or \
             getattr(remapper, 'levels', None) is not None or \
             getattr(remapper, 'layers', None) is not None:
-        # (a limited, fraction-weighted, interpolated or depth-reduced
-        # variable takes the whole-array route, one at a time)
+        # (a limited, filled, fraction-weighted, interpolated or
+        # depth-reduced variable takes the whole-array route, one at a time)
         return {}
     groups = {}
     src_dims = remapper.src_descriptor.dims

@@ -10,7 +10,10 @@ knobs and :meth:`from_triplets` for mapping data that is already in memory.
 """
 from pyremap_amd.remapper.remap_numpy import (
     _check_alone,
+    _check_fill,
     _check_label_field,
+    _fill_array,
+    _fill_result,
     _check_statistics,
     _check_fractions_alone,
     _check_layer_arrays,
@@ -137,6 +140,15 @@ class Remapper:
         bins[c + 1]`` takes (:mod:`pyremap_amd.classfrac`), beside the
         variable remapped as before; :meth:`remap_array_fractions` is the
         array-level entry
+    fill : None, 'nearest', 'mean' or dict
+        set after construction (default ``None``: nothing changes):
+        ``dict(method='nearest' | 'mean', passes=None, dist_exponent=2.0)``.
+        ``remap_array``, ``remap_numpy`` and ``ncremap`` then fill the
+        missing cells of every remapped variable from their valid neighbours
+        on the destination grid, after the apply and after a limiter
+        (:mod:`pyremap_amd.fill`; CDO's ``fillmiss``, ESMF's ``creep``);
+        ``categorical`` variables always with ``'nearest'``;
+        :meth:`fill_array` is the array-level entry
     """
 
     def __init__(
@@ -253,6 +265,23 @@ class Remapper:
         #: Not together with sgs_frac, levels or layers, nor for a member of
         #: a vector pair (ValueError).
         self.fractions = None
+        #: fill of missing destination cells (None | 'nearest' | 'mean' |
+        #: dict(method=..., passes=None, dist_exponent=2.0)), honoured by
+        #: remap_array, remap_numpy and ncremap: after the apply and after a
+        #: limiter, every remapped variable's missing cells take values from
+        #: their valid neighbours on the destination grid, creeping outward
+        #: one ring of cells per pass until nothing fillable is left
+        #: (pyremap_amd.fill; compass' extrap_woa, CDO's fillmiss, ESMF's
+        #: creep); every other dim is a mask of its own.  categorical
+        #: variables are always filled with 'nearest' and keep their dtype,
+        #: with fill values only where the fill could not reach; the results
+        #: of levels and layers are filled over their own shape.  Variables
+        #: weighted by sgs_frac, the members of vector_pairs and the extra
+        #: outputs of statistics and fractions are left as they are.
+        self.fill = None
+        #: what the last fill did: dict(passes=launches made, missing=
+        #: elements left where the count was read)
+        self.fill_info = None
         self.src_scrip_filename = 'src_mesh.nc'
         self.dst_scrip_filename = 'dst_mesh.nc'
         self.format = 'NETCDF3_64BIT_DATA'
@@ -543,13 +572,59 @@ class Remapper:
         float32 field gets its float64 gradient rounded once).  With a
         ``limiter``, several devices or a process group that is a
         ``NotImplementedError``.  Every other call is untouched.
+
+        With the attribute :attr:`fill` set (``'nearest'``, ``'mean'`` or a
+        dict), after the apply and after a limiter the missing cells of the
+        result take values from their valid neighbours on the destination
+        grid, as :meth:`fill_array` does it.  (The attribute, not a keyword:
+        this method's signature is pinned.)  The filled result is detached:
+        no gradient passes a fill, and a field that asks for one is a
+        ``NotImplementedError``.
         """
         if self.map_filename is None:
             raise ValueError('No mapping file has been defined')
         limiter = _check_limiter(self, limiter)
+        spec = _check_fill(self)
+        if spec is not None and getattr(field, 'requires_grad', False):
+            raise NotImplementedError(
+                'no gradient passes through a fill: remap without it where a '
+                'gradient is required')
         _load_mapping(self, limiter=limiter)
-        return _remap_numpy_array(self, field, remap_axes,
-                                  renormalization_threshold, limiter=limiter)
+        out = _remap_numpy_array(self, field, remap_axes,
+                                 renormalization_threshold, limiter=limiter)
+        if spec is None:
+            return out
+        first = min(int(a) % field.ndim for a in remap_axes)
+        return _fill_result(self, out, first, spec)
+
+    def fill_array(self, field, remap_axes, method='nearest', passes=None):
+        """
+        Fill the missing cells of a field on the DESTINATION grid from their
+        valid neighbours (compass' ``extrap_woa``, CDO's ``fillmiss``, ESMF's
+        ``creep``; :mod:`pyremap_amd.fill` has the definition to the bit):
+        ``remap_axes`` names the axes of ``field`` that are the destination
+        dims.  ``'nearest'``: the value of the closest valid neighbour (only
+        values the field holds come out: labels); ``'mean'``: the
+        inverse-distance mean of the valid neighbours.  One pass fills one
+        ring of cells; ``passes=None`` repeats until nothing fillable is
+        left, ``passes=k`` makes exactly ``k`` passes.  Every other axis is a
+        mask of its own: a level is filled from that level's values only,
+        and where a level holds no value at all it stays missing.
+
+        Device tensor in -> float64 device tensor out, NaN where still
+        missing; numpy or ``MaskedArray`` in (NaN or masked: missing) ->
+        float64 ``numpy.ma.MaskedArray`` out.  The neighbours are the 8 index
+        neighbours of a lat-lon or projection grid, the edge neighbours of
+        an MPAS cell mesh read from its file, the 8 nearest points of
+        anything else (:func:`pyremap_amd.fill.neighbour_graph`); the plan
+        is made from :attr:`dst_descriptor` once and kept.  The mapping is
+        not needed.  One device; the result is detached.
+        """
+        spec = _check_fill(self, dict(method=method, passes=passes))
+        held = getattr(self, 'fill', None)
+        if isinstance(held, dict) and 'dist_exponent' in held:
+            spec = spec[:2] + (_check_fill(self, held)[2],)
+        return _fill_array(self, field, remap_axes, spec)
 
     def remap_array_adjoint(self, cotangent, remap_axes, field=None,
                             renormalization_threshold=None):
